@@ -6,8 +6,10 @@ one batch of DISTINCT synthetic 10 s / 16 kHz utterances, alignments copied back
 Workload = BASELINE.json configs[2]: context-dependent SAT-style model (~5k pdfs × 32 Gaussians, D = 40, per-speaker
 fMLLR), beam 10 / retry 40.  `--workload mono` runs configs[1] (monophone, 1 Gaussian/state, Δ+ΔΔ features) instead.
 
-`value` follows the bench contract: inputs (PCM, graphs) resident in HBM when the timed region starts.  The same JSON
-line also carries, each from its own timed loop in this very run:
+`value` follows the bench contract: inputs (PCM, graphs) resident in HBM when the timed region starts.  A plain run sets
+up, warms up, times `--steps` steps, writes the last step's outputs when `--dump-outputs DIR` is given, and prints the
+line (`value`, `ms_per_step`, the per-stage times of the timed steps).  With `--full` the same JSON line also carries,
+each from its own timed loop in this very run:
   value_host_fed — PCM in pinned host memory, double-buffered H2D on a copy stream under the previous step's kernels,
                    outputs back on the host (SURVEY §8d "PCM in host pinned memory → alignments in host memory");
   value_bf16x3 / value_f32 — the same resident-input loop with the stricter scoring arithmetic (MFA_GMM_F16=0 /
@@ -18,9 +20,16 @@ N ranks (torch.distributed.run as a CHILD process, before anything touches the G
 Utterances are sharded by speaker, every rank runs the same per-GPU batch (weak scaling), no data-path collective;
 ranks meet only at the timing barriers.
 
-Extra objects in the line:
+Extra objects in the line (`--full` only):
   roofline     — dominant kernel of the step, measured with HIP events on the launch stream
   cpu_baseline — the CPU oracle (a port, not stock Kaldi) timed on a bounded sample of the same workload.
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller (the host copies of ali, words,
+n_words, like, status) as DIR/<name>.npy in float32 (float64 where an integer would not fit float32 exactly).  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.  With one batch in
+flight (`--inflight 1`) two runs of one build wrote bit-identical files; with the default six in flight they did not
+(`like` of about 30 % of the utterances differed, by up to 7e-4 relative, and `ali` of about 1 %), so comparisons of
+default runs need a tolerance.
 """
 from __future__ import annotations
 
@@ -59,8 +68,16 @@ def parse_args(argv=None):
     ap.add_argument("--gauss-per-pdf", type=int, default=32,  # 0 = mixture sizes as in a trained model (1..48, median 11)
                     help="triphone workload: Gaussians per pdf (BASELINE configs[2] = 32; other values exercise the other "
                          "slot classes of the scoring kernels and are NOT the headline workload)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-loops", action="store_true", help="skip the host-fed and strict-precision loops")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the host-fed, strict-precision and end-to-end "
+                         "loops, the CPU baseline, the one-batch-in-flight loop and the roofline objects (with the "
+                         "scored-cell probe step they price)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (ali, words, n_words, like, status; rank 0's) to "
+                         "DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra-loops", action="store_true",
+                    help="--full: skip the host-fed, strict-precision, end-to-end and one-batch-in-flight loops")
     ap.add_argument("--cpu-sample", type=int, default=0, help="utterances for the CPU baseline (0 = 8 per core)")
     ap.add_argument("--beam", type=float, default=10.0)
     ap.add_argument("--retry-beam", type=float, default=40.0, help="0 = no retry pass (diagnostic; not the headline config)")
@@ -92,6 +109,55 @@ def parse_args(argv=None):
 def log(rank, *a):
     if rank == 0:
         print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+DUMP_BYTES_MAX = 64_000_000   # all files together (64 MB)
+DUMP_SEED = 1234
+
+
+def _as_float(a: np.ndarray) -> np.ndarray:
+    """float32, or float64 where an integer array holds a value float32 does not represent exactly."""
+    if a.dtype.kind in "iu" and a.size and int(np.abs(a.astype(np.int64)).max()) >= 2**24:
+        return a.astype(np.float64)
+    return a.astype(np.float32)
+
+
+def dump_outputs(out_dir, host, frame_off) -> dict:
+    """--dump-outputs: the arrays one step hands its caller (``Pipeline.outputs_to_host``), written as float .npy files.
+
+    Per utterance, whole: like, status, n_words.  Per frame: ali (transition-ids) and the word ids packed at each
+    utterance's frame offset, for every utterance when they fit in DUMP_BYTES_MAX, else for a fixed seeded sample of
+    utterances (ali_utterances lists them, ali_offsets / words_offsets delimit each one's rows)."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    status, n_words, like = (host[k].numpy().copy() for k in ("status", "n_words", "like"))
+    ali, words = host["ali"].numpy(), host["words"].numpy()
+    n = len(status)
+    T = np.diff(frame_off)
+    nw = np.clip(n_words, 0, T)
+    per_utt = {"like": _as_float(like), "status": _as_float(status), "n_words": _as_float(n_words)}
+    fixed = sum(a.nbytes for a in per_utt.values()) + 8 * 128 + 2 * 8   # + .npy headers, the offsets' leading zeros
+    item = max(_as_float(ali).itemsize, _as_float(words).itemsize)
+    # bytes of utterance u's rows: ali + words + its index and two offsets
+    cost = (T + nw) * item + 3 * 8
+    if fixed + int(cost.sum()) <= DUMP_BYTES_MAX:
+        sel = np.arange(n)
+    else:
+        perm = np.random.default_rng(DUMP_SEED).permutation(n)
+        k = int(np.searchsorted(np.cumsum(cost[perm]), DUMP_BYTES_MAX - fixed, side="right"))
+        sel = np.sort(perm[:k])
+    ali_rows = [ali[frame_off[u]: frame_off[u + 1]] for u in sel]
+    word_rows = [words[frame_off[u]: frame_off[u] + nw[u]] for u in sel]
+    arrays = dict(per_utt)
+    arrays["ali"] = _as_float(np.concatenate(ali_rows) if len(sel) else ali[:0])
+    arrays["words"] = _as_float(np.concatenate(word_rows) if len(sel) else words[:0])
+    arrays["ali_utterances"] = sel.astype(np.float64)
+    arrays["ali_offsets"] = np.concatenate([[0], np.cumsum(T[sel])]).astype(np.float64)
+    arrays["words_offsets"] = np.concatenate([[0], np.cumsum(nw[sel])]).astype(np.float64)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {"dir": str(out_dir), "utterances": n, "utterances_with_frames": int(len(sel)),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 # ------------------------------------------------------------------------------------------ self-launch (N > 1)
@@ -322,12 +388,13 @@ def main():
             dist.barrier()
 
     # how much of the score matrix does one step write?  (lazy scoring: the cells inside the decoder's bands) — the work
-    # the scoring stage executes, which is what the roofline prices
-    sc = pipe.measure_scored_cells()
-    for p_ in pipes[1:]:
-        p_.cells_scored, p_.cells_scored_fraction, p_.scored_flops = pipe.cells_scored, pipe.cells_scored_fraction, pipe.scored_flops
-    log(rank, f"score cells written: {int(sc['cells'])}/{pipe.loglikes.numel()} = {sc['fraction']:.4f}; "
-              f"{sc['flops'] / 1e12:.3f} TFLOP executed per step ({pipe.gmm_flops / 1e12:.3f} for the whole reachable matrix)")
+    # the scoring stage executes, which is what the roofline prices (--full: a step of its own, untimed)
+    if args.full:
+        sc = pipe.measure_scored_cells()
+        for p_ in pipes[1:]:
+            p_.cells_scored, p_.cells_scored_fraction, p_.scored_flops = pipe.cells_scored, pipe.cells_scored_fraction, pipe.scored_flops
+        log(rank, f"score cells written: {int(sc['cells'])}/{pipe.loglikes.numel()} = {sc['fraction']:.4f}; "
+                  f"{sc['flops'] / 1e12:.3f} TFLOP executed per step ({pipe.gmm_flops / 1e12:.3f} for the whole reachable matrix)")
     if os.environ.get("MFA_GMM_STAMPS"):  # diagnostic (library built with -DGMM_BAND_STAMPS): band kernel phase ticks (100 MHz)
         import ctypes as C
         acc = torch.zeros(16, dtype=torch.int64, device=dev)
@@ -368,7 +435,8 @@ def main():
     torch.cuda.synchronize()
     status = host_out["status"].numpy().copy()
     n_ok = int(((status == 0) | (status == 1)).sum())
-    log(rank, f"warmup done: {n_ok}/{B} aligned, status counts {dict(zip(*np.unique(status, return_counts=True)))}")
+    log(rank, f"warmup done: {n_ok}/{B} aligned, status counts {dict(zip(*np.unique(status, return_counts=True)))} "
+              f"({time.time() - t_setup:.1f}s after setup began)")
     diagnostic = os.environ.get("MFA_GMM_DIAG", "0") != "0"  # timing-only kernel variants produce no valid scores
     if n_ok < 0.98 * B and not diagnostic:
         raise SystemExit(f"benchmark invalid: only {n_ok}/{B} utterances aligned")
@@ -402,9 +470,17 @@ def main():
         e_.kernel_timing(False)
     total_utts = B * args.steps * world
     value = total_utts / dt
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: its pipeline's host buffers (synchronized by timed_loop), written
+        # before any later loop of --full reuses them
+        k_last = (turn["i"] - 1) % n_inflight
+        dumped = dump_outputs(args.dump_outputs, host_outs[k_last], pipes[k_last].frame_off)
+        log(rank, f"outputs of the last timed step written to {dumped['dir']} ({dumped['bytes']} bytes, frame-level rows of "
+                  f"{dumped['utterances_with_frames']}/{dumped['utterances']} utterances)")
 
     extra = {}
-    if not args.no_extra_loops:
+    if args.full and not args.no_extra_loops:
         # ---- host-fed loop: PCM from pinned host memory; every pipeline in flight has its own device PCM buffer and copy
         # stream, so the H2D of one step travels under the kernels of the other pipeline's step (and, with one pipeline,
         # two buffers alternate: the copy of step i+1 under the kernels of step i)
@@ -485,7 +561,7 @@ def main():
     # ---- end to end through the host side (SURVEY §8d restated for configs[3]: PCM + transcripts in host memory ->
     # alignments on the host -> interval arrays -> TextGrid text): CorpusAligner over the same utterances, every rank its
     # own, barrier + max over ranks like the device loops
-    if not args.no_extra_loops:
+    if args.full and not args.no_extra_loops:
         import shutil
         import tempfile
 
@@ -547,7 +623,7 @@ def main():
     # ---- CPU baseline (rank 0, one GPU): the oracle with Kaldi's lazy decodable on a bounded sample.  Run before the
     # rooflines are written: its count of score cells the decoder asks for prices the Viterbi stage's score bytes.
     cpu_baseline, score_cells_read = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import shutil
         import tempfile
 
@@ -583,7 +659,7 @@ def main():
     # ---- the same stages with ONE batch in flight (no other stream's kernels sharing the chip): clean per-kernel times
     single = None
     kt_ss, n_ss = None, 0
-    if n_inflight > 1 and not args.no_extra_loops:
+    if args.full and n_inflight > 1 and not args.no_extra_loops:
         n_ss = 2
         engines[0].kernel_timing(True)
         engines[0].reset_kernel_times()
@@ -602,40 +678,43 @@ def main():
                   "roofline_scoring": pipe.roofline("gmm", kt_ss, n_ss, mono, args.gauss_per_pdf),
                   "roofline_viterbi": pipe.roofline("viterbi", kt_ss, n_ss, mono, args.gauss_per_pdf, score_cells_read)}
 
-    # ---- roofline of the dominant kernel of the step (largest share of the per-stage HIP-event times; with several
-    # batches in flight these are measured while other streams' kernels share the chip — what rocprofv3 sees too)
     stage_ms = {k: v["ms"] / args.steps for k, v in ktimes.items()}
-    dominant = max(stage_ms, key=stage_ms.get)
-    roofline_concurrent = pipe.roofline(dominant, ktimes, args.steps, mono, args.gauss_per_pdf, score_cells_read)
-    roofline_concurrent["measured"] = (f"timed region, {n_inflight} batches in flight: launch durations include the time other "
-                                       "streams' kernels share the chip")
-    if kt_ss is not None:
-        # the kernel's own roofline: its launch durations with the chip to itself (the one-batch-in-flight loop of this
-        # very run, HIP events on the launch stream) — what tools/profile_round.sh's --inflight 1 stats pass and the PMC
-        # passes see too.  The figure taken inside the timed region stays in the line as roofline_batches_in_flight.
-        roofline = pipe.roofline(dominant, kt_ss, n_ss, mono, args.gauss_per_pdf, score_cells_read)   # (dominant: by the timed region's stage times)
-        roofline["measured"] = "one batch in flight (same run, after the timed region): the kernel has the chip to itself"
-    else:
-        roofline = roofline_concurrent
-    # fabric-side bytes of that kernel's launches: PMC counters cannot be collected from inside this process, so the
-    # figure is the one tools/profile_round.sh measured (separate rocprofv3 --pmc passes of this very command), committed
-    # under profiles/; it applies to the default workload at the batch size in the file's name
-    prof_name = next((n_ for n_ in (f"r03_profile_summary_triphone_b{B}.json", f"r02_profile_summary_triphone_b{B}.json")
-                      if (ROOT / "profiles" / n_).exists()), None)
-    if not mono and prof_name is not None:
-        try:
-            with open(ROOT / "profiles" / prof_name) as fh:
-                tr = json.load(fh).get("bench_roofline_traffic", {}).get(roofline.get("kernel_key", ""))
-            if tr:
-                roofline["traffic"] = float(tr["bytes_per_step"])
-                roofline["traffic_source"] = f"profiles/{prof_name}: {tr['how']}"
-                # the same launches against the HBM roof (north_star asks for that fraction too): fabric bytes per step
-                # over the stage's time per step, of 8 TB/s
-                if roofline.get("ms_per_step"):
-                    gbps = roofline["traffic"] / (roofline["ms_per_step"] * 1e-3) / 1e9
-                    roofline["hbm"] = {"achieved": round(gbps, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(gbps / 8000.0, 4)}
-        except (KeyError, ValueError, OSError):
-            pass
+    rooflines = {}
+    if args.full:
+        # ---- roofline of the dominant kernel of the step (largest share of the per-stage HIP-event times; with several
+        # batches in flight these are measured while other streams' kernels share the chip — what rocprofv3 sees too)
+        dominant = max(stage_ms, key=stage_ms.get)
+        roofline_concurrent = pipe.roofline(dominant, ktimes, args.steps, mono, args.gauss_per_pdf, score_cells_read)
+        roofline_concurrent["measured"] = (f"timed region, {n_inflight} batches in flight: launch durations include the time other "
+                                           "streams' kernels share the chip")
+        if kt_ss is not None:
+            # the kernel's own roofline: its launch durations with the chip to itself (the one-batch-in-flight loop of this
+            # very run, HIP events on the launch stream) — what tools/profile_round.sh's --inflight 1 stats pass and the PMC
+            # passes see too.  The figure taken inside the timed region stays in the line as roofline_batches_in_flight.
+            roofline = pipe.roofline(dominant, kt_ss, n_ss, mono, args.gauss_per_pdf, score_cells_read)   # (dominant: by the timed region's stage times)
+            roofline["measured"] = "one batch in flight (same run, after the timed region): the kernel has the chip to itself"
+        else:
+            roofline = roofline_concurrent
+        # fabric-side bytes of that kernel's launches: PMC counters cannot be collected from inside this process, so the
+        # figure is the one tools/profile_round.sh measured (separate rocprofv3 --pmc passes of this very command), committed
+        # under profiles/; it applies to the default workload at the batch size in the file's name
+        prof_name = next((n_ for n_ in (f"r03_profile_summary_triphone_b{B}.json", f"r02_profile_summary_triphone_b{B}.json")
+                          if (ROOT / "profiles" / n_).exists()), None)
+        if not mono and prof_name is not None:
+            try:
+                with open(ROOT / "profiles" / prof_name) as fh:
+                    tr = json.load(fh).get("bench_roofline_traffic", {}).get(roofline.get("kernel_key", ""))
+                if tr:
+                    roofline["traffic"] = float(tr["bytes_per_step"])
+                    roofline["traffic_source"] = f"profiles/{prof_name}: {tr['how']}"
+                    # the same launches against the HBM roof (north_star asks for that fraction too): fabric bytes per step
+                    # over the stage's time per step, of 8 TB/s
+                    if roofline.get("ms_per_step"):
+                        gbps = roofline["traffic"] / (roofline["ms_per_step"] * 1e-3) / 1e9
+                        roofline["hbm"] = {"achieved": round(gbps, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(gbps / 8000.0, 4)}
+            except (KeyError, ValueError, OSError):
+                pass
+        rooflines = {"roofline": roofline, "roofline_batches_in_flight": roofline_concurrent}
 
     gpp = model.am.num_gauss // model.am.num_pdfs
     out = {
@@ -667,15 +746,17 @@ def main():
         "aligned_fraction": n_ok / B, **({"diagnostic_variant": os.environ["MFA_GMM_DIAG"]} if diagnostic else {}),
         "stage_ms_per_step": {k: round(v, 3) for k, v in stage_ms.items()},
         **extra,
-        "roofline": roofline,
-        "roofline_batches_in_flight": roofline_concurrent,
+        **rooflines,
         **({"single_batch_in_flight": single} if single is not None else {}),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if cpu_baseline is not None:
         out["cpu_baseline"] = cpu_baseline
         out["gpu_over_cpu"] = round(value / cpu_baseline["value"], 1) if cpu_baseline["value"] > 0 else None
     pool_proc.close()
     pool_proc.join()
+    log(rank, f"done {time.time() - t_setup:.1f}s after setup began")
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -15,7 +15,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 ARGS = ["--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", "512", "--inflight", "2",
-        "--train-utts", "40", "--no-extra-loops", "--no-cpu-baseline"]
+        "--train-utts", "40", "--full", "--no-extra-loops", "--no-cpu-baseline"]   # --full: the line's roofline is checked
 
 
 def _run(extra_env=None, timeout=900):

@@ -8,7 +8,7 @@ out=$root/gpurun_out/probe_$tag
 mkdir -p "$out"
 python3 bench.py --no-cpu-baseline --no-extra-loops --steps 10 --warmup 3 > "$out/bench.json" 2> "$out/bench.err"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -- python3 $root/bench.py --no-cpu-baseline --steps 1 --warmup 3 --inflight 1 --no-extra-loops > /dev/null 2> "$out/pmc_fetch.err"
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -- python3 $root/bench.py --full --no-cpu-baseline --steps 1 --warmup 3 --inflight 1 --no-extra-loops > /dev/null 2> "$out/pmc_fetch.err"
 cd "$root"
 python3 tools/summarize_profile.py "$out" > "$out/summary.json"
 find "$out" -name "*kernel_trace.csv" -delete; find "$out" -name "*counter_collection.csv" -delete; find "$out" -name "*agent_info.csv" -delete

@@ -6,7 +6,7 @@ root=$(pwd)
 out=$root/$1; shift
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-bench="$root/bench.py --no-cpu-baseline --steps 1 --warmup 2 --inflight 1 --no-extra-loops"
+bench="$root/bench.py --full --no-cpu-baseline --steps 1 --warmup 2 --inflight 1 --no-extra-loops"
 for v in "$@"; do
   IFS='|' read -r name envs <<< "$v"
   for e in $envs; do export "$e"; done

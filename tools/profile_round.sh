@@ -10,7 +10,7 @@ root=$(pwd)
 out=$root/gpurun_out/prof_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-bench="$root/bench.py --no-cpu-baseline"
+bench="$root/bench.py --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -- python3 $bench --steps 6 --warmup 3 > "$out/bench_under_rocprof.json" 2> "$out/stats.err"
 echo "[profile] kernel stats done"
 # the same with one batch in flight: per-kernel durations with the chip to themselves (what the bench line's `roofline` uses)

@@ -6,7 +6,7 @@ root=$(pwd)
 out=$root/$1; shift
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-bench="$root/bench.py --no-cpu-baseline --steps 1 --warmup 2 --inflight 1 --no-extra-loops $*"
+bench="$root/bench.py --full --no-cpu-baseline --steps 1 --warmup 2 --inflight 1 --no-extra-loops $*"
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE \
   --output-format csv -d "$out/a" -- python3 $bench > /dev/null 2> "$out/a.err"
 echo "[pmc] pass a done"
