@@ -156,6 +156,8 @@ class CorpusAligner:
         self._mfcc_cache_on = False
         self._intervals = None          # intervals_native.IntervalExtractor, built on first use
         self._worker = None             # one worker thread: the next batch's graphs compile under the current batch
+        self._graph_pools = None        # staging the batches' graphs compile into (three sets, this pipeline's alone)
+        self._graph_turn = 0
         self._out_pools = None          # pinned staging for the batches' outputs on their way back (two sets)
         self._out_turn = 0
 
@@ -179,10 +181,11 @@ class CorpusAligner:
     def _batches(self, utts: Sequence[CorpusUtterance]) -> List[List[int]]:
         """Length-bucketed batches (BASELINE configs[4]): sort by duration, cut at ``batch_frames``.  Computed once per run
         (``align`` asks three times: graph compilation ahead, the CMVN pass, the alignment passes)."""
-        key = (id(utts), len(utts))
+        lens = np.fromiter((len(u.pcm) for u in utts), dtype=np.int64, count=len(utts))
+        # (keyed on what the batches are a function of: not the list's identity, which a refilled or a new list can share)
+        key = (int(self.opt.batch_frames), lens.tobytes())
         if getattr(self, "_batches_key", None) == key:
             return self._batches_val
-        lens = np.fromiter((len(u.pcm) for u in utts), dtype=np.int64, count=len(utts))
         order = np.argsort(lens, kind="stable")
         frames = self.engine.num_frames_array(lens) if hasattr(self.engine, "num_frames_array") else \
             np.array([self.engine.num_frames(int(n)) for n in lens], dtype=np.int64)
@@ -280,12 +283,25 @@ class CorpusAligner:
         fsts_all = self.compiler.compile_fsts([utts[i].text for i in idx_all], self.scaled, columns=True, alloc=pool.get)
         return dict(idx_all=list(idx_all), fsts_all=fsts_all, pool=pool)
 
+    def _next_graph_pool(self):
+        """The staging pool the next batch's graphs compile into: round robin over three sets that nothing but the pipeline
+        draws from — batch b + 1 compiles while batch b is launched from its pool and batch b - 1 is still collected from
+        its own (the capacity redo packs its graphs again).  The engine's ``next_staging``, which every other packing call
+        takes from, cannot move this turn.  Waits until the copies last started from the pool are done (main thread)."""
+        if self._graph_pools is None:
+            from .engine import StagingPool
+            self._graph_pools = [StagingPool(self.engine.device) for _ in range(3)]
+        self._graph_turn = (self._graph_turn + 1) % len(self._graph_pools)
+        pool = self._graph_pools[self._graph_turn]
+        pool.wait()
+        return pool
+
     def _submit_compile(self, utts, idx_all):
         from concurrent.futures import ThreadPoolExecutor
 
         if self._worker is None:
             self._worker = ThreadPoolExecutor(1, thread_name_prefix="mfa-graphs")
-        pool = self.engine.next_staging()          # (main thread: waits for the copies last started from this pool)
+        pool = self._next_graph_pool()
         return self._worker.submit(self._compile, utts, idx_all, pool)
 
     def _prepare(self, utts, comp):

@@ -171,8 +171,9 @@ class AlignmentEngine:
         self.num_ceps = 13
         self.gmm: Optional[DiagGmmModel] = None
         self.slot_class: Optional[np.ndarray] = None
-        # three sets of pinned staging buffers: the host fills one (the graphs of batch b + 2 compile into it) while the copies
-        # out of the second are in flight and the third still backs the host-side graphs of the batch being collected
+        # pinned staging buffers for packing calls that bring no pool of their own (pack_graphs(..., pool=None)): three sets
+        # in turn, each reused once the copies last started from it are done.  (CorpusAligner's batch pipeline keeps a
+        # rotation of its own: no call here can hand out a pool that still backs one of its batches.)
         self._staging = [StagingPool(self.device), StagingPool(self.device), StagingPool(self.device)]
         self._staging_turn = 0
         self._pcm_staging = [StagingPool(self.device), StagingPool(self.device)]   # PCM has its own pair: gathered while graphs compile
@@ -188,6 +189,7 @@ class AlignmentEngine:
     def gather_pcm(self, arrays: Sequence[np.ndarray], pool: Optional[StagingPool] = None):
         """int16 arrays (one per utterance, host) → one device tensor + sample offsets: threaded gather into pinned staging
         memory (mfa_gather_pcm), one asynchronous H2D copy."""
+        arrays = [a if isinstance(a, np.ndarray) else np.asarray(a, dtype=np.int16) for a in arrays]   # (lists, tensors)
         n = len(arrays)
         lens = np.fromiter((a.shape[0] for a in arrays), dtype=np.int64, count=n)
         so = np.zeros(n + 1, dtype=np.int64)

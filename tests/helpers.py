@@ -108,3 +108,104 @@ def has_negative_eps_cycle(fst) -> bool:
             return False
         dist = new
     return True
+
+
+def with_eps(rng, f, frac=0.3):
+    """An equivalent graph with epsilon input arcs: a share of the arcs s -il:ol/w-> d is split into
+    s -eps:ol/w-> m -il:eps/0-> d through a fresh state m (the word label and the weight travel on the epsilon arc)."""
+    S = f.num_states
+    arcs_by_state = [[] for _ in range(S)]
+    for s in range(S):
+        for a in range(int(f.arc_offsets[s]), int(f.arc_offsets[s + 1])):
+            arcs_by_state[s].append(tuple(f.arcs[a]))
+    extra = []
+    final = list(f.final)
+    for s in range(S):
+        new = []
+        for (il, ol, w, d) in arcs_by_state[s]:
+            if il != 0 and d != s and rng.random() < frac:
+                m = S + len(extra)
+                extra.append([(il, 0, 0.0, d)])
+                final.append(np.inf)
+                new.append((0, ol, w, m))
+            else:
+                new.append((il, ol, w, d))
+        arcs_by_state[s] = new
+    allst = arcs_by_state + extra
+    offs = np.concatenate([[0], np.cumsum([len(x) for x in allst])]).astype(np.int64)
+    arr = np.zeros(int(offs[-1]), dtype=K.ARC_DTYPE)
+    k = 0
+    for lst in allst:
+        for t in lst:
+            arr[k] = t
+            k += 1
+    return K.Fst(f.start, offs, arr, np.asarray(final, dtype=np.float32))
+
+
+class PoolOwnership:
+    """Which batch of ``CorpusAligner._pass`` owns which staging pool, checked against every pool handed out.
+
+    The graphs of batch b are compiled into a staging pool (``alloc=pool.get``) and read from it until ``_collect(b)`` has
+    returned (the capacity redo packs them again from there).  Every hand-out — the aligner's own graph rotation and the
+    engine's ``next_staging``, which anything else that packs draws from — is logged with the batch it was made for (None
+    for everything outside ``_submit_compile``); ``check()`` asserts that no pool is handed out while a batch owns it.  A batch
+    with nothing for the wavefront decoder is never collected: its ownership ends when ``_general`` returns."""
+
+    def __init__(self, monkeypatch, al):
+        self.events: list = []
+        self._batch = None
+        eng = al.engine
+
+        def handout(fn, who):
+            def wrapped(*a, **kw):
+                pool = fn(*a, **kw)
+                self.events.append(("get", id(pool), self._batch, who))
+                return pool
+            return wrapped
+
+        monkeypatch.setattr(eng, "next_staging", handout(eng.next_staging, "engine.next_staging"))
+        if hasattr(al, "_next_graph_pool"):
+            monkeypatch.setattr(al, "_next_graph_pool", handout(al._next_graph_pool, "aligner graph rotation"))
+        submit, collect, general = al._submit_compile, al._collect, al._general
+
+        def submit_(utts, idx_all):
+            self._batch = tuple(idx_all)
+            try:
+                return submit(utts, idx_all)
+            finally:
+                self._batch = None
+
+        def collect_(utts, prep, *a, **kw):
+            out = collect(utts, prep, *a, **kw)
+            self.events.append(("done", tuple(prep["idx_all"])))
+            return out
+
+        def general_(utts, prep, *a, **kw):
+            out = general(utts, prep, *a, **kw)
+            if not prep["idx"]:
+                self.events.append(("done", tuple(prep["idx_all"])))
+            return out
+
+        monkeypatch.setattr(al, "_submit_compile", submit_)
+        monkeypatch.setattr(al, "_collect", collect_)
+        monkeypatch.setattr(al, "_general", general_)
+
+    def check(self) -> int:
+        """Asserts the invariant; returns the number of batches that compiled into a pool."""
+        owner: dict = {}
+        n = 0
+        for ev in self.events:
+            if ev[0] == "get":
+                _, pool, batch, who = ev
+                assert pool not in owner, (f"{who} handed out (for {_batch_name(batch)}) the staging pool that "
+                                           f"{_batch_name(owner[pool])} still owns: that batch is not collected yet")
+                if batch is not None:
+                    owner[pool] = batch
+                    n += 1
+            else:
+                owner = {p: b for p, b in owner.items() if b != ev[1]}
+        return n
+
+
+def _batch_name(batch) -> str:
+    return "no batch" if batch is None else f"the batch of utterances {batch[0]} … {batch[-1]} ({len(batch)})"

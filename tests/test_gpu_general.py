@@ -19,36 +19,7 @@ def _dev(e, a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(e.device)
 
 
-def _with_eps(rng, f, frac=0.3):
-    """An equivalent graph with epsilon input arcs: a share of the arcs s -il:ol/w-> d is split into
-    s -eps:ol/w-> m -il:eps/0-> d through a fresh state m (the word label and the weight travel on the epsilon arc)."""
-    S = f.num_states
-    arcs_by_state = [[] for _ in range(S)]
-    for s in range(S):
-        for a in range(int(f.arc_offsets[s]), int(f.arc_offsets[s + 1])):
-            arcs_by_state[s].append(tuple(f.arcs[a]))
-    extra = []
-    final = list(f.final)
-    for s in range(S):
-        new = []
-        for (il, ol, w, d) in arcs_by_state[s]:
-            if il != 0 and d != s and rng.random() < frac:
-                m = S + len(extra)
-                extra.append([(il, 0, 0.0, d)])
-                final.append(np.inf)
-                new.append((0, ol, w, m))
-            else:
-                new.append((il, ol, w, d))
-        arcs_by_state[s] = new
-    allst = arcs_by_state + extra
-    offs = np.concatenate([[0], np.cumsum([len(x) for x in allst])]).astype(np.int64)
-    arr = np.zeros(int(offs[-1]), dtype=K.ARC_DTYPE)
-    k = 0
-    for lst in allst:
-        for t in lst:
-            arr[k] = t
-            k += 1
-    return K.Fst(f.start, offs, arr, np.asarray(final, dtype=np.float32))
+_with_eps = helpers.with_eps          # (tools/general_rate.py imports it from here)
 
 
 def _oracle(tm, am, f, x, beam, retry):
@@ -207,6 +178,39 @@ def test_epsilon_closure_budget_hands_over_to_the_general_decoder(engine, fx, mo
     monkeypatch.delenv("MFA_VIT_EPS_POPS")
     again = al.align_utterances([eps], [x], ["b"])
     assert again[0].alignment == out[1].alignment and again[0].likelihood == out[1].likelihood
+
+
+@pytest.mark.parametrize("beam,retry", [(100.0, 400.0), (1.0e4, 0.0)])
+def test_hard_bounds_hold_for_short_epsilon_utterances(engine, fx, beam, retry):
+    """``PackedGraphs.hard_bounds`` is what the capacity redo of a status-3/4 utterance decodes with, and it promises that
+    neither status comes back at the default closure budget.  That is tightest for short utterances on epsilon graphs:
+    InitDecoding's closure writes its back-pointer records before frame 0, and the traceback's path sits behind the trail.
+    One utterance per batch (the bounds are its graph's own), wide beams so that most states are live; the result must be
+    the oracle's."""
+    tm, am = fx.mono_tm, fx.mono_am
+    engine.load_gmm(am)
+    rng = np.random.default_rng(31)
+    x = fx.mono_feats(fx.pcm[: 16000])
+    texts = ["this", "this is the acoustic corpus", "this is the acoustic corpus i'm talking pretty fast here"]
+    n_aligned = 0
+    for f in (_with_eps(rng, fx.mono_graph(t)) for t in texts):
+        assert (f.arcs["ilabel"] == 0).any() and not engine.needs_general_decoder(f)
+        g = engine.pack_graphs([f], tm)
+        mt, bp = g.hard_bounds()
+        for T in (1, 2, 3, 4, 8, 63, 64, 65):
+            fo = np.array([0, T], dtype=np.int64)
+            r = engine.align_features(g, _dev(engine, x[:T]), fo, beam=beam, retry_beam=retry, max_tokens=mt,
+                                      bp_tokens_per_frame=bp)
+            r = {k: r[k].cpu().numpy() for k in ("status", "ali", "words", "n_words", "like")}
+            st = int(r["status"][0])
+            assert st not in (3, 4), f"{f.num_states} states, {T} frames: status {st} with the hard bounds {(mt, bp)}"
+            ref = _oracle(tm, am, f, x[:T], beam, retry)
+            assert st == helpers.device_status(ref, T), (f.num_states, T, st, ref["status"])
+            if st in (0, 1):
+                assert np.array_equal(r["ali"][:T], ref["ali"]), (f.num_states, T)
+                assert np.array_equal(r["words"][: int(r["n_words"][0])], ref["words"]), (f.num_states, T)
+                n_aligned += 1
+    assert n_aligned >= 3
 
 
 def test_more_word_labels_than_frames_is_reported_not_truncated(engine, fx):
