@@ -44,7 +44,9 @@ constexpr int kMaxArcsPerState = 1 << kArcBits;
 
 enum { ST_OK = 0, ST_RETRIED = 1, ST_FAILED = 2, ST_TOKEN_OVERFLOW = 3, ST_BP_OVERFLOW = 4, ST_UNSUPPORTED = 5, ST_INTERNAL = 6, ST_WORDS = 7, ST_PENDING = -1, ST_GROW = -2 };
 
-// decoder state of one utterance between two windows (the token list itself is parked in w_state / w_cost)
+// decoder state of one utterance between two windows (the token list itself is parked in w_state / w_cost).  pad0 is the
+// utterance's lag in the 64-token first tier: 1 — its window in this launch is the previous one (a failed speculation
+// being redone with the proven band, by the first tier itself); the utterance stays one window behind from then on.
 struct VitState { int32_t n, cur, done, pad0; u32 H, pad1; u64 bp_used; };
 
 struct VitParams {
@@ -69,26 +71,17 @@ struct VitParams {
   // out-degree above counts the emitting ones): per state {first epsilon arc << 7 | number of epsilon arcs}, built once per call
   const u32 *w_epsinfo;                // [n_utt * max_states] at (utt * max_states + state), or NULL
   int eps_stride;                      // max_states
-  int lagmode;                         // windowed first-beam pass with the 64-token first tier: VitState.pad0 is the utterance's lag —
-                                       // 1: its window in this launch is the previous one (a failed speculation being redone with the
-                                       // proven band, by the first tier itself); the utterance stays one window behind from then on
   int eps_pops;                        // pops of one frame's epsilon closure before the utterance is handed back with a capacity status (64 per token slot; Kaldi has no budget: the caller's last resort is the general decoder)
   unsigned long long *stamps;          // -DVIT_STAMPS builds: per-utterance phase cycles (mfa_debug_viterbi_stamps) or NULL
   int llcap;                           // score-row cache capacity in LDS (floats); rows longer than this are read from HBM
   // windowed (resumable) decoding — mfa_align_features_batch: one launch decodes frames [t_begin, t_end) of every utterance,
   // parks the live token list in the HBM workspace and leaves the band of graph depths the NEXT window can touch
   int windowed, t_begin, t_end, next_window;
-  // Two table sizes per window (first-beam pass of mfa_align_features_batch): redo_mode 1 = the small first tier — an
-  // utterance that runs out of token slots (or enters the window with more tokens than the tier holds) is flagged in
-  // w_redo and left exactly as it was parked at the window's start; redo_mode 2 = the large tier, launched right after for
-  // the SAME window: only flagged utterances run.  0: a token overflow is final (or ST_GROW).
-  int redo_mode;
-  u32 *w_redo;                         // [n_utt]
-  int npark;                           // stride (tokens) of the parked lists: the large tier's capacity, whatever tier runs
   VitState *w_vstate;                  // [n_utt]
   // Speculative look-ahead (first-beam windowed pass): the window was scored for a band narrower than the proven one; the
-  // decoder checks every score it reads against the column ranges that were scored (spec_ranges, see mfa_band_ranges) and
-  // gives the utterance up (ST_GROW: decoded again from frame 0 by the list pass, proven bands) the moment one lies outside.
+  // decoder checks every score it reads against the column ranges that were scored (spec_ranges, see mfa_band_ranges).  The
+  // moment one lies outside, the 64-token first tier puts the utterance one window behind (VitState.pad0) and redoes the
+  // window with the proven band; the general kernel gives it up (ST_GROW: decoded again from frame 0 by the list pass).
   int spec;                            // 1: check
   const int32_t *spec_ranges;          // [n_utt][kMfaRangeSlots][2]
   const int32_t *spec_class_counts;    // [n_utt][6]
@@ -399,7 +392,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     if (p.n_list && (int)blockIdx.x >= *p.n_list) return;
     utt = p.utt_list[blockIdx.x];
   }
-  if (p.redo_mode == 2 && p.w_redo[utt] == 0u) return;   // large tier: only what the small tier handed over
   const int64_t so = p.g.d_state_off[utt];
   const int S = (int)(p.g.d_state_off[utt + 1] - so);
   const int64_t ab_ = p.g.d_arc_base[utt];
@@ -469,19 +461,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   int status = ST_OK;
   const int start = p.g.d_start[utt];
   if (S <= 0 || start < 0 || start >= S || T <= 0) status = ST_FAILED;
-  // (lagmode: an utterance one window behind — VitState.pad0 — works on [t_begin − K, t_begin))
-  const int lag = (p.lagmode && p.windowed && p.t_begin > 0) ? (p.w_vstate[utt].pad0 != 0 ? 1 : 0) : 0;
-  const int t_begin_u = p.t_begin - lag * (p.t_end - p.t_begin);
-  const bool resume = p.windowed && t_begin_u > 0;
+  const bool resume = p.windowed && p.t_begin > 0;
   int cur = 0, n = 1;
   u32 H = p.pass == 0 ? 1000u : p.w_hash[utt];
   u64 bp_used = 0;
   int t = 0;
   // token lists parked in HBM between windows (the kListsInLds = false variant keeps them there all the time)
-  const int NP = kListsInLds ? p.npark : N;
-  u32 *park_state = p.w_state + (size_t)utt * 2 * NP;
-  u32 *park_an = p.w_state + (size_t)p.g.n_utt * 2 * NP + (size_t)utt * 2 * NP;
-  double *park_cost = p.w_cost + (size_t)utt * 2 * NP;
+  u32 *park_state = p.w_state + (size_t)utt * 2 * N;
+  u32 *park_an = p.w_state + (size_t)p.g.n_utt * 2 * N + (size_t)utt * 2 * N;
+  double *park_cost = p.w_cost + (size_t)utt * 2 * N;
   if (!resume) {
     // InitDecoding: one token at the start state with cost 0 (epsilon-free graphs: ProcessNonemitting is a no-op)
     if (lane == 0) {
@@ -586,11 +574,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   } else {
     const VitState vs = p.w_vstate[utt];
     if (vs.done) return;                           // finished (or failed) in an earlier window: outputs are final
-    n = vs.n; H = vs.H; bp_used = vs.bp_used; t = t_begin_u;
-    if (p.redo_mode == 1 && n > N) {               // more live tokens than this tier holds: the large tier takes the window
-      if (lane == 0) p.w_redo[utt] = 1u;           // (cannot happen in lag mode: an utterance that outgrows the tier has left it)
-      return;
-    }
+    n = vs.n; H = vs.H; bp_used = vs.bp_used; t = p.t_begin;
     if (n < 0 || n > N) { n = 0; status = ST_INTERNAL; }
     if (kListsInLds) {
       cur = 0;
@@ -599,7 +583,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
       cur = vs.cur & 1;
     }
   }
-  const int t_stop = p.windowed ? min(T, t_begin_u + (p.t_end - p.t_begin)) : T;
+  const int t_stop = p.windowed ? min(T, p.t_end) : T;
   // score rows are staged through LDS one frame ahead (registers hold row t+1 while frame t is processed)
   constexpr int kPre = 8;
   const bool row_cached = P <= p.llcap && P <= 64 * kPre;
@@ -607,10 +591,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #pragma unroll
   for (int r = 0; r < kPre; r++) pre[r] = (row_cached && t < T && lane + 64 * r < P) ? ll[(size_t)t * P + lane + 64 * r] : 0.0f;
   WSYNC();
-  const bool spec = p.spec != 0 && p.windowed && lag == 0;
+  const bool spec = p.spec != 0 && p.windowed;
   if (spec) build_scored_bitmap(p, utt, lane, bm);
   bool viol = false;   // a score outside the scored columns was read this window
-  bool spec_failed = false;
 
 #ifdef VIT_STAMPS
   unsigned long long stamp_acc[12] = {0}, stamp_last;
@@ -944,7 +927,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     WSYNC();
     const u32 nslots = ctr[0], nstash = ctr[1];
     if (__any(bad_degree)) { status = ST_UNSUPPORTED; break; }
-    if (spec && __any(viol)) { status = ST_TOKEN_OVERFLOW; spec_failed = true; break; }   // first tier: the window is redone (large tier, or lag mode)
+    if (spec && __any(viol)) { status = ST_TOKEN_OVERFLOW; break; }   // given up as a capacity overflow is (ST_GROW)
     if (nslots > (u32)N || nstash > (u32)C || cand_base > (u32)C) { status = ST_TOKEN_OVERFLOW; break; }
     if (nslots == 0) { n = 0; t++; break; }  // everything pruned: no surviving token
 
@@ -1173,34 +1156,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   }
 #ifdef VIT_STAMPS
   // accumulated over the windows of the first tier (the caller zeroes the buffer); [11] = frames decoded
-  if (lane == 0 && p.pass == 0 && p.stamps && p.redo_mode != 2 && p.utt_list == nullptr)
+  if (lane == 0 && p.pass == 0 && p.stamps && p.utt_list == nullptr)
     for (int k = 0; k < 12; k++) p.stamps[(size_t)utt * 12 + k] += stamp_acc[k];
 #endif
   __threadfence_block();  // back-pointer records (HBM) are read back by the traceback below
-  if (p.redo_mode == 1 && status == ST_TOKEN_OVERFLOW) {
-    // small tier out of slots: nothing parked has been touched (lists and decoder state are written at a window's END
-    // only; the back-pointer records of this window are simply written again) — the large tier redoes the window
-    if (p.lagmode) {
-      // lag mode (see viterbi_small_kernel): a failed speculation puts the utterance one window behind — this kernel redoes the
-      // window in its next launch, on the proven band; a capacity overflow sends it to the from-scratch list pass
-      if (lane == 0) {
-        VitState vs;
-        if (spec_failed) {
-          if (resume) vs = p.w_vstate[utt];
-          else { vs.n = 1; vs.cur = 0; vs.H = 1000u; vs.pad1 = 0; vs.bp_used = 0; }     // (window 0: nothing was parked yet)
-          vs.done = 0; vs.pad0 = 1;
-        } else {
-          vs.n = 0; vs.cur = 0; vs.done = 1; vs.pad0 = 0; vs.H = 1000u; vs.pad1 = 0; vs.bp_used = 0;
-          p.status[utt] = ST_GROW; p.n_words[utt] = 0; p.like[utt] = 0.0f;
-        }
-        p.w_vstate[utt] = vs;
-      }
-      return;
-    }
-    if (lane == 0) p.w_redo[utt] = 1u;
-    return;
-  }
-  if (p.redo_mode == 2 && lane == 0) p.w_redo[utt] = 0u;
   u32 *c_state = l_state0 + cur * N;
   double *c_cost = l_cost0 + cur * N;
   if (p.windowed && status == ST_OK && t < T && n > 0) {
@@ -1223,7 +1182,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     dmin_inv = wave_max_u32(dmin_inv);
     if (lane == 0) {
       VitState vs;
-      vs.n = n; vs.cur = kListsInLds ? 0 : cur; vs.done = 0; vs.pad0 = lag; vs.H = H; vs.pad1 = 0; vs.bp_used = bp_used;
+      vs.n = n; vs.cur = kListsInLds ? 0 : cur; vs.done = 0; vs.pad0 = 0; vs.H = H; vs.pad1 = 0; vs.bp_used = bp_used;
       p.w_vstate[utt] = vs;
       if (p.band) {
         const long long hi = (long long)dmax + (long long)p.next_window - 1;
@@ -1235,7 +1194,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   }
   if (p.windowed && lane == 0) {   // finished one way or the other: later windows of this pass skip the utterance
     VitState vs;
-    vs.n = 0; vs.cur = 0; vs.done = 1; vs.pad0 = lag; vs.H = H; vs.pad1 = 0; vs.bp_used = bp_used;
+    vs.n = 0; vs.cur = 0; vs.done = 1; vs.pad0 = 0; vs.H = H; vs.pad1 = 0; vs.bp_used = bp_used;
     p.w_vstate[utt] = vs;
   }
   if (p.pass == 0 && lane == 0) p.w_hash[utt] = H;
@@ -1250,9 +1209,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 // same decisions, bit for bit — but straight-line wavefront code: the general kernel above carries a token-chunk loop, an
 // arc cache of eight per lane, an HBM candidate stash and the retry/grow bookkeeping through every frame (6 000
 // instructions, 139 spilled scalars), this one a third of that.  Anything outside its envelope (more tokens, more
-// candidates, a state of more than 64 arcs) flags the utterance for the large tier, which redoes the window from the
-// state parked at its start — exactly the hand-over the general kernel's first tier uses.  An utterance that reaches its
-// last frame is parked with done = 2; viterbi_finish_kernel then does ReachedFinal, traceback and outputs.
+// candidates, a state of more than 64 arcs) hands the utterance over to the table-growth list pass (ST_GROW).  An utterance
+// that reaches its last frame is parked with done = 2; viterbi_finish_kernel then does ReachedFinal, traceback and outputs.
 //   GetCutoff's min_active rule: the (min_active + 1 − k)-th smallest cost outside the beam by ballot quickselect (a
 //   handful of compare+ballot steps) instead of ranking every token against every other.
 constexpr int kSmallN = 64;
@@ -1265,10 +1223,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   const int lane = threadIdx.x;
   const int utt = blockIdx.x;
   const VitState vs0 = p.w_vstate[utt];
-  // lagmode: an utterance whose speculative window failed is one window behind from then on (VitState.pad0): this launch redoes
+  // an utterance whose speculative window failed is one window behind from then on (VitState.pad0): this launch redoes
   // that window for it — scored again with the proven band by the scoring launch before this one — without the check
   const int K_ = p.t_end - p.t_begin;
-  const int lag = (p.lagmode && p.t_begin > 0 && vs0.pad0 != 0) ? 1 : 0;
+  const int lag = (p.t_begin > 0 && vs0.pad0 != 0) ? 1 : 0;
   const int t_begin_u = p.t_begin - lag * K_;
   const bool resume = t_begin_u > 0;
   if (p.t_begin > 0 && vs0.done) return;           // finished (or failed, or waiting for the finish kernel)
@@ -1281,24 +1239,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   const int T = (int)(p.frame_off[utt + 1] - f0);
   const float *ll = p.ll + p.ll_off[utt];
   const int P = p.ll_cols[utt];
-  const int NP = p.npark;
-  u32 *park_state = p.w_state + (size_t)utt * 2 * NP;
-  u32 *park_an = p.w_state + (size_t)p.g.n_utt * 2 * NP + (size_t)utt * 2 * NP;
-  double *park_cost = p.w_cost + (size_t)utt * 2 * NP;
-  // Outside this kernel's envelope (more than 64 tokens, more than 64·kRounds candidates, a malformed graph).  Without lagmode:
-  // nothing parked has been touched, the large tier — launched right after — redoes the window.  With lagmode there is no such
-  // launch: the utterance leaves the fast track for good and is decoded from its first frame by the table-growth list pass that
-  // follows the windowed pass (general kernel, the caller's full capacity) — rare: none of the 4 096 utterances of the bench
-  // workload ever holds more than 64 tokens at beam 10.
+  // parked lists: the host lays this launch's workspace out for nmax = kSmallN tokens
+  u32 *park_state = p.w_state + (size_t)utt * 2 * N;
+  u32 *park_an = p.w_state + (size_t)p.g.n_utt * 2 * N + (size_t)utt * 2 * N;
+  double *park_cost = p.w_cost + (size_t)utt * 2 * N;
+  // Outside this kernel's envelope (more than 64 tokens, more than 64·kRounds candidates, a malformed graph): the utterance
+  // leaves the fast track for good and is decoded from its first frame by the table-growth list pass that follows the
+  // windowed pass (general kernel, the caller's full capacity) — rare: none of the 4 096 utterances of the bench workload
+  // ever holds more than 64 tokens at beam 10.
   auto hand_over = [&]() {
     if (lane != 0) return;
-    if (p.lagmode) {
-      VitState vs; vs.n = 0; vs.cur = 0; vs.done = 1; vs.pad0 = 0; vs.H = 1000u; vs.pad1 = 0; vs.bp_used = 0;
-      p.w_vstate[utt] = vs;
-      p.status[utt] = ST_GROW; p.n_words[utt] = 0; p.like[utt] = 0.0f;
-    } else {
-      p.w_redo[utt] = 1u;
-    }
+    VitState vs; vs.n = 0; vs.cur = 0; vs.done = 1; vs.pad0 = 0; vs.H = 1000u; vs.pad1 = 0; vs.bp_used = 0;
+    p.w_vstate[utt] = vs;
+    p.status[utt] = ST_GROW; p.n_words[utt] = 0; p.like[utt] = 0.0f;
   };
 
   int n = 1, t = 0;
@@ -1796,7 +1749,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         }
       }
     }
-    if (__any(broken)) { overflow = true; break; }     // (cannot happen; the large tier would report ST_INTERNAL)
+    if (__any(broken)) { overflow = true; break; }     // (cannot happen; the list pass would report ST_INTERNAL)
     WSYNC();
     if ((u32)lane < nslots_f) { hmap[s_bucket[lane]] = kEmpty; cntord[aux & 0xFFFFFFu] = 0; }
     if (lane == 0) { tokoff[t] = (u32)bp_used; ctr[0] = 0; }
@@ -1807,22 +1760,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     WSYNC();
   }
   if (overflow) { hand_over(); return; }
-  // the narrow band did not hold: nothing parked has been touched, so the window is scored again with the proven band and
-  // redone from its parked state by the large tier — the same hand-over as a capacity overflow
+  // the narrow band did not hold.  Nothing parked has been touched (lists and decoder state are written at a window's END
+  // only; the back-pointer records of this window are simply written again), so the parked state is as it was at the
+  // window's start: mark the utterance as one window behind — the next scoring launch scores this window again with the
+  // proven band, the next launch of this kernel redoes it (no separate launch for a handful of wavefronts, which with
+  // several batches in flight left the chip empty a tenth of the time)
   if (spec_fail) {
-    if (p.lagmode) {
-      // the parked state is as it was at the window's start: mark the utterance as one window behind — the next scoring launch
-      // scores this window again with the proven band, the next launch of this kernel redoes it (no separate launch for a
-      // handful of wavefronts, which with several batches in flight left the chip empty a tenth of the time)
-      if (lane == 0) {
-        VitState vs = vs0;
-        if (!resume) { vs.n = 1; vs.cur = 0; vs.H = 1000u; vs.pad1 = 0; vs.bp_used = 0; }   // (window 0: nothing was parked yet)
-        vs.done = 0; vs.pad0 = 1;
-        p.w_vstate[utt] = vs;
-      }
-      return;
+    if (lane == 0) {
+      VitState vs = vs0;
+      if (!resume) { vs.n = 1; vs.cur = 0; vs.H = 1000u; vs.pad1 = 0; vs.bp_used = 0; }   // (window 0: nothing was parked yet)
+      vs.done = 0; vs.pad0 = 1;
+      p.w_vstate[utt] = vs;
     }
-    hand_over(); return;
+    return;
   }
   __threadfence_block();
   u32 *c_state = l_state0 + cur * N;
@@ -1872,9 +1822,8 @@ __global__ __launch_bounds__(64) void viterbi_finish_kernel(VitParams p) {
   const int64_t ab_ = p.g.d_arc_base[utt];
   const int64_t f0 = p.frame_off[utt];
   const int T = (int)(p.frame_off[utt + 1] - f0);
-  const int NP = p.npark;
-  const u32 *c_state = p.w_state + (size_t)utt * 2 * NP;
-  const double *c_cost = p.w_cost + (size_t)utt * 2 * NP;
+  const u32 *c_state = p.w_state + (size_t)utt * 2 * kSmallN;   // parked with viterbi_small_kernel's stride
+  const double *c_cost = p.w_cost + (size_t)utt * 2 * kSmallN;
   if (lane == 0) { VitState d = vs; d.done = 1; p.w_vstate[utt] = d; }
   finalize_utterance(p, utt, lane, ST_OK, T, T, vs.n, c_state, c_cost, p.g.d_final + so, p.w_bp + (size_t)f0 * p.bpf,
                      p.w_tokoff + f0 + utt, f0, ab_, p.g.d_arc_weight + ab_, p.g.d_arc_col + ab_, p.ll + p.ll_off[utt],
@@ -1885,11 +1834,6 @@ __global__ __launch_bounds__(64) void viterbi_finish_kernel(VitParams p) {
 __global__ void collect_pending_kernel(const int32_t *status, int n_utt, int code, int32_t *list, int32_t *count) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_utt && status[i] == code) list[atomicAdd(count, 1)] = i;
-}
-// utterances a first-tier launch flagged for the large tier (w_redo != 0), as a list for the scoring kernels
-__global__ void collect_flagged_kernel(const u32 *flags, int n_utt, int32_t *list, int32_t *count) {
-  int u = blockIdx.x * blockDim.x + threadIdx.x;
-  if (u < n_utt && flags[u] != 0u) list[atomicAdd(count, 1)] = u;
 }
 __global__ void finalize_pending_kernel(int32_t *status, int n_utt) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1937,7 +1881,7 @@ size_t lds_bytes(int S, int N, int C, bool lists_in_lds, bool eps = false) {
 constexpr size_t kLdsLimit = 160 * 1024;
 
 struct WsLayout {
-  size_t arcnext, state, cost, sta, stb, stkey, bp, tokoff, hash, list, count, vstate, band, redo, eps, total;
+  size_t arcnext, state, cost, sta, stb, stkey, bp, tokoff, hash, list, count, vstate, band, eps, total;
 };
 WsLayout ws_layout(int n_utt, int64_t total_frames, int N, int C, int bpf, int64_t total_arcs, int64_t eps_states = 0) {
   WsLayout w; size_t o = 0;
@@ -1955,7 +1899,6 @@ WsLayout ws_layout(int n_utt, int64_t total_frames, int N, int C, int bpf, int64
   w.count = take(256);
   w.vstate = take((size_t)n_utt * sizeof(VitState));
   w.band = take((size_t)n_utt * 2 * 4);
-  w.redo = take((size_t)n_utt * 4);
   w.eps = take((size_t)eps_states * 4);
   w.total = o;
   return w;
@@ -2016,8 +1959,8 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
   int N[2], C[2];
   for (int ps = 0; ps < 2; ps++) pick_caps(o, max_states, max_arcs, ps, &N[ps], &C[ps]);
   const int Nw = passes == 2 ? N[1] : N[0], Cw = passes == 2 ? C[1] : C[0];
-  // graphs with epsilon input arcs: the general kernel's kEps instantiation on every tier (the 64-token kernel knows nothing
-  // of them), one {first epsilon arc, count} word per state in the workspace
+  // graphs with epsilon input arcs: the decoder kernels' kEps instantiations, one {first epsilon arc, count} word per state
+  // in the workspace
   const bool eps = g->d_state_nemit != nullptr;
   if (eps && max_arcs >= (1 << 24)) return c->fail("graphs with epsilon arcs and more than 2^24 arcs are not supported");
   const int64_t eps_states = eps ? (int64_t)n_utt * max_states : 0;
@@ -2033,23 +1976,20 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
   // Launch plan.  The decoder is latency-bound (one wavefront walks one utterance frame by frame), so throughput is the
   // number of wavefronts a CU can keep resident, and that is set by the LDS tables, which scale with the token capacity.
   // With the normal beam a frame rarely holds more than a few dozen tokens, so every utterance is first decoded with
-  // small tables (kSmallTokens); the few that overflow them are marked ST_GROW and decoded again, from scratch and with
+  // small tables (first_tier); the few that overflow them are marked ST_GROW and decoded again, from scratch and with
   // the same beam, at the caller's full capacity.  Then the retry-beam pass for utterances that did not reach a final state.
   if (lazy && mfa_gmm_presplit(c, lazy, d_frame_off, n_utt, total_frames) != 0) return -1;
-  struct Launch { int pass, N, C, code, grow; int N2 = 0, C2 = 0; };   // N2 > 0: a large tier redoes single windows
-  std::vector<Launch> plan;
   // First-tier capacity.  With the hashed state→slot table nothing in the decoder's LDS scales with the graph: 64 tokens
   // need 9.5 KB → 16 wavefronts per CU (a whole batch of 4 096 resident at once on 256 CUs), 128 tokens 14.6 KB → 10.
-  // MFA_VIT_TIER overrides (diagnostics).
-  int kSmallTokens = lazy ? 64 : 128;
-  { const char *e = getenv("MFA_VIT_TIER"); if (e && atoi(e) >= 64) kSmallTokens = (atoi(e) + 63) & ~63; }
-  // Speculative look-ahead of the windowed first-beam pass.  The proven band lets a token advance one arc per frame, K − 1
+  // The lazy path's first tier is viterbi_small_kernel (kSmallN tokens), the dense path's the general kernel.
+  const int first_tier = lazy ? kSmallN : 128;
+  // Speculative look-ahead of the windowed first tier.  The proven band lets a token advance one arc per frame, K − 1
   // arcs by the window's last frame; speech advances a third of that (synthetic 10 s utterances: 21 states per 64 frames on
   // average, 34 at the 99th percentile, 38 at most).  The window is scored for a look-ahead of K / 2 arcs instead (32 for
   // K = 64: a fifth fewer model blocks gathered than with 48, tools/band_study.py), the decoder checks every score it reads
   // against what was scored, and a window in which it asks for more (about 1 % of them) is scored again with the proven band
-  // and redone from the state parked at its start by the large tier — the hand-over capacity overflows already use; results
-  // cannot differ.  (Round 2 re-decoded such an utterance from frame 0, which made anything below 48 arcs a loss.)
+  // and redone from the state parked at its start by the first tier, one window later (lag mode, see the window loop);
+  // results cannot differ.  (Round 2 re-decoded such an utterance from frame 0, which made anything below 48 arcs a loss.)
   // MFA_LAZY_LOOKAHEAD=n overrides (n >= K − 1: off).
   int spec_slack = 0;
   if (lazy) {
@@ -2058,25 +1998,12 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
     spec_slack = std::max(0, lazy->window - 1 - look);
     if (lazy->plan.max_cols > 32 * kBmWords) spec_slack = 0;   // (the decoder's bitmap of scored columns holds 2 048)
   }
-  bool will_lag = false;
-  if (lazy && N[0] > kSmallTokens) {
-    // windowed first-beam pass: the small tier decodes every window; the few utterances it cannot hold in a window are
-    // decoded again — that window only, from the state parked at its start — by the large tier (LDS-resident lists,
-    // so at most 1 024 tokens; beyond that a from-scratch pass with HBM-resident lists follows, as in the dense path)
-    const int nb = std::min(N[0], 1024);
-    const int cb = std::min(C[0], 4 * nb);
-    // lag mode (see the window loop): the 64-token first tier redoes its own failed speculations one window later and sends
-    // capacity overflows to the from-scratch list pass instead of a large-tier launch per window
-    will_lag = true;                             // (either first tier: the 64-token kernel or the general one — epsilon batches)
-    { const char *e = getenv("MFA_VIT_LAG"); if (e && e[0] == '0') will_lag = false; }
-    const bool second = nb < N[0] || will_lag;   // a from-scratch list pass: table growth beyond the large tier / the first tier
-    Launch a{0, kSmallTokens, std::min(C[0], 4 * kSmallTokens), 0, second ? 1 : 0};
-    a.N2 = nb; a.C2 = cb;
-    plan.push_back(a);
-    if (second) plan.push_back({0, N[0], C[0], ST_GROW, 0});
-  } else if (N[0] > kSmallTokens) {
-    int cs = std::min(C[0], 4 * kSmallTokens);
-    plan.push_back({0, kSmallTokens, cs, 0, 1});
+  int eps_pops_env = 0;                  // MFA_VIT_EPS_POPS (tests: forces the hand-over to the general decoder)
+  { const char *e = getenv("MFA_VIT_EPS_POPS"); if (e && atoi(e) > 0) eps_pops_env = atoi(e); }
+  struct Launch { int pass, N, C, code, grow; };
+  std::vector<Launch> plan;
+  if (N[0] > first_tier) {
+    plan.push_back({0, first_tier, std::min(C[0], 4 * first_tier), 0, 1});
     plan.push_back({0, N[0], C[0], ST_GROW, 0});
   } else {
     plan.push_back({0, N[0], C[0], 0, 0});
@@ -2084,6 +2011,8 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
   if (passes == 2) plan.push_back({1, N[1], C[1], ST_PENDING, 0});
   for (Launch &L : plan) {
     const int ps = L.pass;
+    // the windowed first tier of the lazy path: viterbi_small_kernel, then viterbi_finish_kernel
+    const bool small_tier = lazy && L.grow;
     // token lists in LDS when everything fits comfortably; in HBM for big graphs / the wide retry beam; and if even the
     // atomically updated tables do not fit, shrink the token capacity (an overflow is then reported per utterance)
     // (the list passes — table growth, retry beam — hold a handful of utterances: occupancy does not matter there, the
@@ -2101,7 +2030,8 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
     p.g = *g; p.ll = d_loglikes; p.ll_off = d_ll_off; p.ll_cols = d_ll_cols; p.frame_off = d_frame_off;
     p.beam = ps == 0 ? o->beam : o->retry_beam; p.scale = o->acoustic_scale;
     p.nmax = L.N; p.cmax = L.C; p.bpf = bpf; p.pass = ps; p.grow = L.grow; p.hbits = hash_bits(max_states, L.N);
-    // workspace strides follow this launch's capacities (lists and stash are per-launch scratch)
+    // workspace strides follow this launch's capacities (lists, parked lists and stash are per-launch scratch; the
+    // largest launch's fits in `w`)
     WsLayout wp = ws_layout(n_utt, total_frames, L.N, L.C, bpf, total_arcs, eps_states);
     p.w_state = (u32 *)(base + wp.state); p.w_cost = (double *)(base + wp.cost);
     p.w_stash_a = (u32 *)(base + wp.sta); p.w_stash_b = (u32 *)(base + wp.stb); p.w_stash_key = (u64 *)(base + wp.stkey);
@@ -2109,63 +2039,28 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
     p.w_hash = (u32 *)(base + w.hash);     // fixed location across launches
     p.w_arcnext = (const uint4 *)(base + w.arcnext);
     p.w_epsinfo = eps ? (const u32 *)(base + w.eps) : nullptr; p.eps_stride = max_states;
-    int eps_pops_env = 0;                  // MFA_VIT_EPS_POPS (tests: forces the hand-over to the general decoder)
-    { const char *e = getenv("MFA_VIT_EPS_POPS"); if (e && atoi(e) > 0) eps_pops_env = atoi(e); }
     p.eps_pops = eps_pops_env ? eps_pops_env : 64 * L.N;
     p.llcap = kLlCap;
     p.stamps = (unsigned long long *)c->vit_stamps;
-    int32_t *d_list = (int32_t *)(base + w.list), *d_count = (int32_t *)(base + w.count);
     p.utt_list = nullptr; p.n_list = nullptr;
     p.ali = d_ali; p.words = d_words; p.n_words = d_n_words; p.like = d_like; p.frame_like = d_frame_like; p.status = d_status;
     if (L.code != 0) {
+      int32_t *d_list = (int32_t *)(base + w.list), *d_count = (int32_t *)(base + w.count);
       MFA_HIP_CHECK(c, hipMemsetAsync(d_count, 0, sizeof(int32_t), c->stream));
       hipLaunchKernelGGL(collect_pending_kernel, dim3((n_utt + 255) / 256), dim3(256), 0, c->stream, d_status, n_utt, L.code, d_list, d_count);
       p.utt_list = d_list; p.n_list = d_count;
     }
     p.windowed = 0; p.t_begin = 0; p.t_end = 0x7fffffff; p.next_window = 0;
     p.w_vstate = (VitState *)(base + w.vstate); p.state_depth = nullptr; p.band = nullptr;
-    p.redo_mode = 0; p.w_redo = (u32 *)(base + w.redo); p.npark = L.N2 > 0 ? L.N2 : L.N;
-    // large tier of this pass (same workspace strides as a launch of its own would have)
-    size_t lds2 = 0;
-    VitParams p2 = p;
-    if (L.N2 > 0) {
-      lds2 = lds_bytes(max_states, L.N2, L.C2, true, eps);
-      while (lds2 > kLdsLimit && L.N2 > 128) {         // (the epsilon tables can push a 1 024-token large tier over the limit)
-        L.N2 = (L.N2 / 2 + 63) & ~63;
-        if (L.C2 > 4 * L.N2) L.C2 = 4 * L.N2;
-        lds2 = lds_bytes(max_states, L.N2, L.C2, true, eps);
-      }
-      if (lds2 > kLdsLimit) return c->fail("Viterbi large tier needs %zu bytes of LDS", lds2);
-      WsLayout w2 = ws_layout(n_utt, total_frames, L.N2, L.C2, bpf, total_arcs, eps_states);
-      p2.nmax = L.N2; p2.cmax = L.C2; p2.hbits = hash_bits(max_states, L.N2);
-      p2.eps_pops = eps_pops_env ? eps_pops_env : 64 * L.N2;
-      // park arrays (state / cost) and the back-pointer trail are SHARED between the tiers: the layout of the large one
-      p2.w_state = (u32 *)(base + w2.state); p2.w_cost = (double *)(base + w2.cost);
-      p2.w_stash_a = (u32 *)(base + w2.sta); p2.w_stash_b = (u32 *)(base + w2.stb); p2.w_stash_key = (u64 *)(base + w2.stkey);
-      p2.w_bp = (u64 *)(base + w2.bp); p2.w_tokoff = (u32 *)(base + w2.tokoff);
-      p.w_state = p2.w_state; p.w_cost = p2.w_cost; p.w_bp = p2.w_bp; p.w_tokoff = p2.w_tokoff;
-      // the small tier's per-frame scratch lives inside the large tier's arrays too (its strides are smaller): a layout
-      // of its own would put its candidate stash on top of the other tier's parked lists
-      p.w_stash_a = p2.w_stash_a; p.w_stash_b = p2.w_stash_b; p.w_stash_key = p2.w_stash_key;
-      MFA_HIP_CHECK(c, hipMemsetAsync(base + w.redo, 0, (size_t)n_utt * 4, c->stream));
-    }
     // four instantiations: token lists in LDS or HBM × epsilon-free or not
     void (*k_lds)(VitParams) = eps ? viterbi_kernel<true, true> : viterbi_kernel<true, false>;
     void (*k_hbm)(VitParams) = eps ? viterbi_kernel<false, true> : viterbi_kernel<false, false>;
-    if (lists_in_lds) MFA_HIP_CHECK(c, hipFuncSetAttribute((const void *)k_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(lds, lds2)));
-    else MFA_HIP_CHECK(c, hipFuncSetAttribute((const void *)k_hbm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (lds2 > 0) MFA_HIP_CHECK(c, hipFuncSetAttribute((const void *)k_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(lds, lds2)));
+    MFA_HIP_CHECK(c, hipFuncSetAttribute((const void *)(lists_in_lds ? k_lds : k_hbm), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     auto launch_decoder = [&]() {
       KernelTimer kt(c, MFA_K_VITERBI);
       if (lists_in_lds) hipLaunchKernelGGL(k_lds, dim3(n_utt), dim3(64), lds, c->stream, p);
       else hipLaunchKernelGGL(k_hbm, dim3(n_utt), dim3(64), lds, c->stream, p);
     };
-    // first tier of the windowed pass: the dedicated 64-token kernel (MFA_VIT_LEAN=0: the general kernel as first tier)
-    constexpr int kSmallRounds = 3;
-    const size_t lds_small = (size_t)kSmallN * (8 + 16 + 6 * 4 + 8 + 8) + 256 * 4 + (size_t)64 * kSmallRounds * 4 + 16 + (size_t)kBmWords * 4 +
-                             (eps ? (size_t)kSmallN * 7 * 4 : 0);      // (epsilon closure: position / inverse / arc / vote / info + stack)
-    bool lean = lazy && L.N2 > 0 && lists_in_lds && L.code == 0 && L.N == kSmallN;
-    { const char *e = getenv("MFA_VIT_LEAN"); if (e && e[0] == '0') lean = false; }
     if (!lazy) {
       launch_decoder();
       MFA_DEBUG_POINT(c, "decoded pass=%d code=%d N=%d C=%d lds=%zu in_lds=%d", ps, L.code, L.N, L.C, lds, (int)lists_in_lds);
@@ -2175,22 +2070,22 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
       const int K = L.code == 0 ? lazy->window : std::max(lazy->window, 256);
       p.windowed = 1; p.next_window = K;
       p.state_depth = lazy->plan.d_state_depth; p.band = (int32_t *)(base + w.band);
-      // lagmode (the tiered first-beam pass, whichever kernel is its first tier; MFA_VIT_LAG=0 turns it off): an utterance whose
-      // speculative window failed is not handed to the large tier — a launch that a handful of wavefronts can use, one workgroup
-      // with up to 100 KB of LDS per utterance of the batch to find them — but falls one window behind: the next scoring launch
-      // scores the failed window again for it, with the proven band, the next first-tier launch redoes it, and so on to the end,
-      // where one extra round of launches finishes the stragglers.  Capacity overflows wait for the from-scratch list pass.
-      const bool tiered_pass = L.N2 > 0 && lists_in_lds && L.code == 0;
-      const bool lagmode = tiered_pass && will_lag;
-      p.lagmode = lagmode ? 1 : 0; p2.lagmode = p.lagmode;
-      const int t_loop_end = lazy->max_frames + (lagmode ? K : 0);
+      // Lag mode (the first tier): an utterance whose speculative window failed is not handed to a larger tier — a launch
+      // that a handful of wavefronts can use, one workgroup with up to 100 KB of LDS per utterance of the batch to find them
+      // — but falls one window behind: the next scoring launch scores the failed window again for it, with the proven band,
+      // the next first-tier launch redoes it, and so on to the end, where one extra round of launches finishes the
+      // stragglers.  Capacity overflows wait for the from-scratch list pass.  Only the first tier speculates.
+      const bool spec = small_tier && spec_slack > 0;
+      const int t_loop_end = lazy->max_frames + (small_tier ? K : 0);
+      constexpr int kSmallRounds = 3;
+      const size_t lds_small = (size_t)kSmallN * (8 + 16 + 6 * 4 + 8 + 8) + 256 * 4 + (size_t)64 * kSmallRounds * 4 + 16 + (size_t)kBmWords * 4 +
+                               (eps ? (size_t)kSmallN * 7 * 4 : 0);      // (epsilon closure: position / inverse / arc / vote / info + stack)
       for (int t0 = 0; t0 < t_loop_end; t0 += K) {
         MfaWindowScore ws;
         memset(&ws, 0, sizeof(ws));
-        if (lagmode) { ws.lag = (const int32_t *)(base + w.vstate); ws.lag_stride = (int)(sizeof(VitState) / 4); ws.lag_word = 3; }
+        if (small_tier) { ws.lag = (const int32_t *)(base + w.vstate); ws.lag_stride = (int)(sizeof(VitState) / 4); ws.lag_word = 3; }
         ws.t_begin = t0; ws.window = K; ws.band = p.band; ws.utt_list = p.utt_list; ws.n_list = p.n_list;
         ws.cols_per_wave = L.code == 0 ? 0 : 32;   // list passes: few utterances, wide bands — spread the columns over wavefronts
-        const bool spec = L.code == 0 && L.N2 > 0 && lists_in_lds && spec_slack > 0;   // (only the tiered first-beam pass speculates)
         ws.hi_slack = spec ? spec_slack : 0;
         ws.done = (const int32_t *)(base + w.vstate); ws.done_stride = (int)(sizeof(VitState) / 4); ws.done_word = 2;
         if (mfa_gmm_score_window(c, lazy, &ws, d_frame_off, n_utt, d_ll_off, (float *)d_loglikes) != 0) return -1;
@@ -2198,46 +2093,18 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
         p.t_begin = t0; p.t_end = t0 + K;
         p.spec = spec ? 1 : 0; p.spec_ranges = mfa_band_ranges(c); p.spec_class_counts = lazy->plan.d_class_counts;
         p.spec_groups = lazy->plan.groups;
-        p2.spec = p.spec; p2.spec_ranges = p.spec_ranges; p2.spec_class_counts = p.spec_class_counts; p2.spec_groups = p.spec_groups;
-        if (L.N2 > 0 && lists_in_lds) {
-          p.redo_mode = 1;
-          if (lean) {
-            KernelTimer kt1(c, MFA_K_VITERBI);
-            if (eps) hipLaunchKernelGGL((viterbi_small_kernel<kSmallRounds, true>), dim3(n_utt), dim3(64), lds_small, c->stream, p);
-            else hipLaunchKernelGGL((viterbi_small_kernel<kSmallRounds, false>), dim3(n_utt), dim3(64), lds_small, c->stream, p);
-          } else {
-            launch_decoder();
-          }
-          if (lagmode) {      // nothing else per window: failed speculations lag, capacity overflows wait for the list pass below
-            MFA_DEBUG_POINT(c, "decoded window t0=%d K=%d (first tier, lag mode)", t0, K);
-            continue;
-          }
-          p2.windowed = 1; p2.next_window = K; p2.state_depth = p.state_depth; p2.band = p.band;
-          p2.t_begin = t0; p2.t_end = t0 + K; p2.redo_mode = 2; p2.npark = p.npark; p2.grow = L.grow;
-          p2.utt_list = p.utt_list; p2.n_list = p.n_list;
-          if (spec) {
-            // Window-level redo of a failed speculation: the utterances the first tier handed over (token overflow or a
-            // score asked for outside the narrow band) get THIS window scored again with the proven band, then the large
-            // tier redoes it from the parked state without the check.  Mostly empty launches: a fraction of a percent of
-            // the (utterance, window) pairs are flagged.
-            MFA_HIP_CHECK(c, hipMemsetAsync(d_count, 0, sizeof(int32_t), c->stream));
-            hipLaunchKernelGGL(collect_flagged_kernel, dim3((n_utt + 255) / 256), dim3(256), 0, c->stream, p.w_redo, n_utt, d_list, d_count);
-            MfaWindowScore ws2 = ws;
-            ws2.hi_slack = 0; ws2.utt_list = d_list; ws2.n_list = d_count; ws2.cols_per_wave = 0;
-            if (mfa_gmm_score_window(c, lazy, &ws2, d_frame_off, n_utt, d_ll_off, (float *)d_loglikes) != 0) return -1;
-            p2.spec = 0;
-          }
-          {
-            KernelTimer kt2(c, MFA_K_VITERBI);
-            hipLaunchKernelGGL(k_lds, dim3(n_utt), dim3(64), lds2, c->stream, p2);
-          }
+        if (small_tier) {
+          KernelTimer kt(c, MFA_K_VITERBI);
+          if (eps) hipLaunchKernelGGL((viterbi_small_kernel<kSmallRounds, true>), dim3(n_utt), dim3(64), lds_small, c->stream, p);
+          else hipLaunchKernelGGL((viterbi_small_kernel<kSmallRounds, false>), dim3(n_utt), dim3(64), lds_small, c->stream, p);
         } else {
           launch_decoder();
         }
-        MFA_DEBUG_POINT(c, "decoded window t0=%d K=%d pass=%d code=%d N=%d C=%d lds=%zu in_lds=%d", t0, K, ps, L.code, L.N, L.C, lds, (int)lists_in_lds);
+        MFA_DEBUG_POINT(c, "decoded window t0=%d K=%d pass=%d code=%d N=%d C=%d lds=%zu in_lds=%d small=%d", t0, K, ps, L.code, L.N, L.C, lds,
+                        (int)lists_in_lds, (int)small_tier);
       }
-      if (lean) {   // utterances the first tier decoded to their last frame: ReachedFinal, traceback, outputs
-        KernelTimer kt3(c, MFA_K_VITERBI);
+      if (small_tier) {   // utterances the first tier decoded to their last frame: ReachedFinal, traceback, outputs
+        KernelTimer kt(c, MFA_K_VITERBI);
         hipLaunchKernelGGL(viterbi_finish_kernel, dim3(n_utt), dim3(64), 0, c->stream, p);
       }
     }

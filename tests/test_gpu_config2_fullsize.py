@@ -2,7 +2,7 @@
 (`synth.train_triphone` defaults: 4 960 pdfs × 32 Gaussians, D = 40, 51 MB of operands), per-speaker CMVN + fMLLR, beam 10 /
 retry 40, and the bench's own batch — the 4 096 distinct 10 s utterances of rank 0 — through the DEFAULT product path:
 `align_features` with grouped score plans (pdf id mod 8 runs of ≈60 columns), the ≤ 2 048-column bitmap, the speculative
-48-arc look-ahead, the 64-token first tier with its large-tier redo, and the retry-beam list pass.
+48-arc look-ahead, the 64-token first tier with its lag-mode redo, and the retry-beam list pass.
 
 Size-independent properties on all 4 096: status ∈ {0, 1}; one transition-id per frame; the alignment splits into complete
 phones that some choice of the transcript's pronunciations spells; word ids = transcript; a second run is bit-identical.
