@@ -12,7 +12,8 @@ from pathlib import Path
 
 _PKG = Path(__file__).resolve().parent
 _SO = Path(os.environ["MFA_HIP_SO"]).resolve() if os.environ.get("MFA_HIP_SO") else _PKG / "libmfa_hip.so"   # (override: A/B builds)
-_SOURCES = ["api.hip", "mfcc.hip", "feats.hip", "gmm.hip", "viterbi.hip", "viterbi_general.hip", "fmllr.hip"]
+_SOURCES = ["api.hip", "mfcc.hip", "feats.hip", "gmm.hip", "gmm_band.hip", "score_plan.cpp", "viterbi.hip", "viterbi_general.hip",
+            "fmllr.hip"]
 _LIB = None
 
 
@@ -73,7 +74,7 @@ def build_native(force: bool = False, verbose: bool = False) -> Path:
     """Compile the HIP sources for gfx950 into libmfa_hip.so next to this file (hipcc cross-compiles without a GPU)."""
     src_dir = _PKG / "csrc"
     srcs = [src_dir / s for s in _SOURCES]
-    deps = srcs + [src_dir / "ctx.hpp", _PKG.parent / "include" / "mfa_hip.h"]
+    deps = srcs + [src_dir / "ctx.hpp", src_dir / "gmm_common.hpp", _PKG.parent / "include" / "mfa_hip.h"]
     if not force and _SO.exists() and all(_SO.stat().st_mtime >= d.stat().st_mtime for d in deps if d.exists()):
         return _SO
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

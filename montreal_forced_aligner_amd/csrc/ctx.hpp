@@ -10,7 +10,7 @@
 
 #include "../../include/mfa_hip.h"
 
-// Packed model layout (built by mfa_load_gmm, read by gmm.hip and fmllr.hip).  Rows (Gaussians) are grouped in blocks of
+// Packed model layout (built by mfa_load_gmm, read by gmm.hip, gmm_band.hip and fmllr.hip).  Rows (Gaussians) are grouped in blocks of
 // 32; a block is stored operand-major: for every group m of 8 k-values and half h, the 32 rows' 4-float pieces lie side
 // by side —  float offset of (row, logical k = 8m + 2c + h):
 //     (row >> 5) · 32·kpad  +  ((2m + h) · 32 + (row & 31)) · 4  +  c
@@ -79,7 +79,7 @@ struct mfa_ctx {
   bool has_single32 = false;       // some pdf is one 32-row block (17–32 Gaussians): gmm_split_single_kernel has work
   int max_nblk = 1;                // most 32-row blocks of any pdf
   bool has_multi_block = false;    // some pdf has more than 32 Gaussians (several blocks, merged by gmm_bf16_kernel<…, true>)
-  bool all_single_block = false;   // every pdf occupies exactly one 32-row block (no work for the f32 kernel in bf16 mode)
+  bool all_pdfs_32row = false;     // every pdf is a 32-row pdf, of one block or several (no work for the f32 kernel in bf16 mode)
   int32_t *d_nrows = nullptr;  // [num_pdfs] packed rows per pdf (fmllr.hip)
   int *d_gmm_queue = nullptr;  // [8] per-XCD work-item counters of the persistent scoring kernel
   int num_cus = 0;
@@ -149,7 +149,7 @@ struct KernelTimer {
 int mfa_resolve_timers(mfa_ctx *ctx);
 
 // ---- lazy (windowed) scoring: internal interface between the decoder driver (viterbi.hip) and the scoring kernels
-// (gmm.hip).  Not part of the ABI.
+// (gmm_band.hip).  Not part of the ABI.
 struct MfaLazyScoring {
   mfa_score_plan plan;
   const float *d_feats;

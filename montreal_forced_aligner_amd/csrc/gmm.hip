@@ -1,11 +1,17 @@
-// Diagonal-GMM acoustic scoring on gfx950's matrix pipe.  Four kernel families in this file:
+// Diagonal-GMM acoustic scoring on gfx950's matrix pipe: the model packer (mfa_load_gmm), dense scoring of whole utterances
+// (mfa_gmm_score_batch) and the exact-f32 tile walk both scoring modes use.  Kernels in this file:
 //   gmm_kernel               exact-f32 MFMA (v_mfma_f32_32x32x2_f32): single-Gaussian pdfs, and everything under
 //                            MFA_GMM_BF16=0 — the description below is this kernel's;
+//   gmm_band_f32_kernel      the same tile walk (score_tile) launched over the band items of a lazy-scoring window
+//                            (mfa_gmm_launch_band_f32, for gmm_band.hip);
 //   gmm_split_single_kernel  pdfs that are one 32-row block (17–32 Gaussians): float32 products from two f16 (or three
 //                            bf16) operand pieces on v_mfma_f32_32x32x16_{f16,bf16}, blocks shared through LDS;
 //   gmm_split_small_kernel   the 16-, 8- and 4-row slot classes as gathered virtual 32-row blocks on the same pipe;
-//   gmm_bf16_kernel          pdfs of more than 32 Gaussians: runs of blocks merged by an online log-sum-exp.
-// mfa_gmm_score_batch (end of file) decides which launches a model and the environment call for.
+//   gmm_bf16_kernel          pdfs of more than 32 Gaussians: runs of blocks merged by an online log-sum-exp;
+//   gmm_naive_kernel         one thread per (frame, pdf): feature dims beyond 48, and MFA_GMM_NAIVE=1 as a cross-check;
+//   gmm_max_first_frame_kernel  the batch's largest first-reachable frame, for gmm_kernel's phase split.
+// mfa_gmm_score_batch (end of file) decides which launches a model and the environment call for.  Lazy (windowed) scoring
+// is gmm_band.hip; what the two units share is gmm_common.hpp.
 // Replaces DecodableAmDiagGmmScaled::LogLikelihood / gmm_compute_likes (MFA/alignment/multiprocessing.py:846-853, :1415;
 // Kaldi gmm/decodable-am-diag-gmm.cc, VectorBase<float>::LogSumExp).
 //
@@ -27,138 +33,25 @@
 // its frames can be asked for.
 // Output: [T][P_u] row-major, the layout the Viterbi kernel gathers from.
 #include <algorithm>
-#include <atomic>
-#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 #include <type_traits>
 #include <utility>
 #include <vector>
 
-#include "ctx.hpp"
+#include "gmm_common.hpp"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+constexpr float kPadGconst = -1.0e30f;   // gconst of pad rows: they fall under the log-sum-exp cutoff
 
-// a wavefront owns NT 32-frame tiles; a workgroup is kWaves wavefronts (template parameter)
-constexpr float kPadGconst = -1.0e30f;
-
-struct GmmParams {
-  int dim, kpad, num_rows;  // num_rows = index of the dummy row
-  const float *w; const float *gc; const int32_t *row0; const int32_t *nblk; const int32_t *slot;
-  const uint4 *wb;   // bf16×3 split of the packed rows, 32-row blocks of [step][split][half][row] 16-byte units (or NULL)
-  const uint4 *wh;   // f16×2 split of the column-scaled rows, same block layout with two pieces (or NULL)
-  const float *gch;  // gconsts × S for the f16 kernel
-  const float *fscale;   // [kpad] feature column scales S·2^-e_k for the f16 kernel
-  float acc_scale_inv;   // 1 / S
-  int *redo;         // [n_utt × tiles] tiles the f16 kernel declined (scaled feature outside the f16 range)
-  int redo_mode;     // 0: score everything; 2: score only the tiles flagged in redo
-  int *redo_count;   // number of flagged tiles (device scalar, zeroed per launch): the redo sweep returns at once when 0
-  const float *feats; const int64_t *frame_off;
-  const int32_t *pdf_list; const int64_t *pdf_off; const int32_t *class_counts; const int64_t *ll_off;
-  unsigned long long *trace;   // debug (mfa_debug_gmm_trace): per workgroup {start, end, hw id, blocks} or NULL
-  int skip_cc0;                // gmm_bf16_kernel: 1 = the single-block 32-row class was scored by gmm_split_single_kernel
-  int skip_single;             // 1: the 32-row classes (0 and 1) are left to the split kernels; 2: the 16/8/4-row classes too
-  int ff_bias;                 // debug (MFA_GMM_FF_BIAS): added to the tile's last frame before the reachability test
-  const int32_t *first_frame;  // parallel to pdf_list (ascending inside each class) or NULL: see mfa_gmm_score_batch
-  float *out;
-  float min_log_diff;  // logf(FLT_EPSILON), computed on the host so device and oracle use the same constant
-  int n_utt, tiles;    // tiles = 256-frame tiles per utterance (ceil(max_frames / 256)); items = (utterance, tile)
-  int *queue;          // [0..8) phase-1 and [8..16) phase-2 per-XCD item counters; zeroed per launch
-  const int *max_ff;   // largest first_frame of the batch (device scalar)
-  // ---- lazy (windowed) scoring, mfa_gmm_score_window: one wavefront scores the 64 frames [b_t_begin + 64 r, +64) of one
-  // utterance for the pdfs inside the band the decoder published for this window
-  int b_mode;                  // 1: band mode
-  int b_t_begin, b_sub;        // window start; 64-frame sub-tiles per window
-  const int32_t *b_band;       // [n_utt][2] {min longest-path depth of a live token, max BFS depth reachable in the window}
-  const int32_t *b_utt_list; const int32_t *b_n_list;
-  const int32_t *b_done; int b_done_stride, b_done_word;
-  // utterances one window behind the launch (their speculative window failed and is scored again, with the proven band, by the
-  // next launch): lag word of the decoder's per-utterance state, frames per window
-  const int32_t *b_lag; int b_lag_stride, b_lag_word, b_lag_frames;
-  const int32_t *last_depth;   // parallel to pdf_list: running max (inside a class) of the longest-path depth of the pdf's sources
-  int b_skip0;                 // f32 band kernel: classes 0..4 were scored by gmm_band_kernel (it keeps 5: single Gaussians, f32-exact)
-  int b_chunk, b_nchunk;       // gmm_band_kernel: columns per wavefront (0 = the whole band) and chunks per sub-tile
-  const uint4 *xsplit;         // band kernel: pre-split f16 operands [tile][2][kSteps][2][64 lanes] (gmm_presplit_kernel) or NULL
-  const int *xsplit_bad;       // [tile]: 1 = a scaled feature of the tile left the f16 range (the bf16×3 pass takes it)
-  const int32_t *col_row0;     // band kernel: row0[pdf_list[j]] of every column of the batch (gmm_col_rows_kernel) or NULL
-  int32_t *ranges;             // [n_utt][kRangeSlots][2] band index ranges of the window (gmm_band_ranges_kernel) or NULL
-  // Grouped plans (mfa_build_score_plan_grouped): class 0 of every utterance is laid out in `groups` runs (pdf id mod groups),
-  // each ordered by first depth.  gmm_band_kernel then runs `groups` wavefronts per sub-tile, wavefront x — in a workgroup
-  // with blockIdx % groups == x, i.e. (groups = 8) always on the same XCD — scoring run x: that XCD's L2 only ever sees
-  // an eighth of the model.
-  int groups;                  // 0/1: ungrouped
-  const int32_t *group_counts; // [n_utt][groups]
-  int b_split;                 // 1: this launch's grid holds `groups` workgroups per four sub-tiles (gmm_band_kernel)
-  int b_hi_slack;              // band mode: arcs taken off the band's upper depth bound (speculative look-ahead), 0 = none
-  int col_nb_packed;           // 1: col_row0 of a pdf of several blocks carries (blocks − 1) in its five low bits (rows of
-                               //    the 32-row classes are multiples of 32; models whose largest pdf has ≤ 1 024 Gaussians)
-};
-
-// Band of one (utterance, window): pdf j of a class is needed iff first_frame[j] <= hi and last_depth[j] >= lo; both keys
-// are non-decreasing along a class, so the needed pdfs are the index range [count(last_depth < lo), count(first_frame <= hi)).
-struct Band { int lo, hi; };
-__device__ __forceinline__ int band_lag(const GmmParams &p, int utt) {
-  return (p.b_lag && p.b_t_begin > 0) ? (p.b_lag[(size_t)utt * p.b_lag_stride + p.b_lag_word] != 0 ? 1 : 0) : 0;
-}
-// first frame of the utterance's window in this launch
-__device__ __forceinline__ int band_t_begin(const GmmParams &p, int utt) { return p.b_t_begin - band_lag(p, utt) * p.b_lag_frames; }
-__device__ __forceinline__ Band band_of(const GmmParams &p, int utt) {
-  Band b;
-  const int lag = band_lag(p, utt);
-  if (p.b_t_begin - lag * p.b_lag_frames <= 0) { b.lo = 0; b.hi = 64 * p.b_sub - 1; }   // only the start state is live: BFS depth 0
-  else { b.lo = p.b_band[2 * utt]; b.hi = p.b_band[2 * utt + 1]; }
-  // speculative look-ahead (the decoder checks what it reads) — not for a window that is being redone: the proven band
-  if (p.b_hi_slack > 0 && !lag && b.hi != INT32_MAX) b.hi -= p.b_hi_slack;
-  return b;
-}
-// gmm_band_kernel launches over a grouped plan: workgroup → (index of its four sub-tiles, run of class 0).  Consecutive
-// workgroups go to consecutive XCDs, so the run's XCD is blockIdx % 8.  With 16 runs an XCD serves two of them — x and
-// x + 8 — one after the other: the first half of the grid is runs 0..7, the second half runs 8..15, so that at any time an
-// XCD's L2 is asked for one sixteenth of the model.  (Measured on the 51 MB model of BASELINE configs[2]: 12.8 ms per step
-// against 11.2 with eight runs — sixteen wavefronts per sub-tile pay sixteen start-up chains; eight is the default.)
-__device__ __forceinline__ int2 band_split_block(const GmmParams &p) {
-  if (p.groups <= 8) return make_int2((int)(blockIdx.x / (unsigned)p.groups), (int)(blockIdx.x % (unsigned)p.groups));
-  const unsigned half = gridDim.x >> 1, phase = blockIdx.x >= half ? 1u : 0u, rem = blockIdx.x - phase * half;
-  return make_int2((int)(rem >> 3), (int)(phase * 8u + (rem & 7u)));
-}
-// wavefront → (utterance, 64-frame sub-tile) of a band-mode launch; false: nothing to do
-__device__ __forceinline__ bool band_item(const GmmParams &p, int wave, int &utt, int &r, int *chunk = nullptr) {
-  int witem = (p.b_split ? band_split_block(p).x : (int)blockIdx.x) * 4 + wave;
-  if (chunk) { const int q = witem / p.b_nchunk; *chunk = witem - q * p.b_nchunk; witem = q; }
-  const int item = witem / p.b_sub;
-  r = witem - item * p.b_sub;
-  const int n_items = p.b_n_list ? *p.b_n_list : p.n_utt;
-  if (item >= n_items) return false;
-  utt = p.b_utt_list ? p.b_utt_list[item] : item;
-  if (p.b_t_begin > 0 && p.b_done && p.b_done[(size_t)utt * p.b_done_stride + p.b_done_word] != 0) return false;
-  return true;
-}
+// (f32 kernels: a wavefront owns kNT 32-frame tiles; a workgroup is kWaves wavefronts — template parameters)
 
 // one past the last index (i0 + lane) whose bit is set in a 64-lane ballot, 0 if none
 __device__ __forceinline__ int prefix_end(unsigned long long mask, int i0) { return mask ? i0 + 64 - __clzll((long long)mask) : 0; }
 
-// row index (within a 32-row MFMA block) held by accumulator register r of a lane in half h
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// partner lane's value across the two 32-lane halves: one v_permlane32_swap instead of a round trip through the LDS
-// crossbar (ds_bpermute)
-__device__ __forceinline__ float swap32(float v, int h) {
-#if __has_builtin(__builtin_amdgcn_permlane32_swap)
-  unsigned u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float(h ? r[0] : r[1]);
-#else
-  return __shfl_xor(v, 32);
-#endif
-}
 // address of the 4-float piece (operand group 0, half h) of a packed row: see mfa_packed_offset in ctx.hpp
 __device__ __forceinline__ const float *row_ptr(const float *w, int kpad, int row, int h) {
   return w + (size_t)(row >> 5) * 32 * kpad + (h * 32 + (row & 31)) * 4;
@@ -232,14 +125,7 @@ struct Tile {
   }
 };
 
-// log-sum-exp pieces (Kaldi LogSumExp semantics)
-template <int R0, int R1>
-__device__ __forceinline__ float reg_max(const f32x16 &v) {
-  float m = v[R0];
-#pragma unroll
-  for (int r = R0 + 1; r < R1; r++) m = fmaxf(m, v[r]);
-  return m;
-}
+// log-sum-exp pieces (Kaldi LogSumExp semantics); reg_max, reg_expsum_fast and finish are in gmm_common.hpp
 // Σ_r exp(v[r] − mx) over the rows r ∈ [R0, R1) that pass Kaldi's cutoff (v[r] ≥ max + ln ε).
 // exp(x) = 2^(x·log2 e) on the hardware exp2 (≈1 ulp); the rounding of the product x·log2 e adds |x|·6e-8 relative
 // error to a term, which only matters for terms that are themselves ≤ e^x of the sum — below 1e-7 of the total.
@@ -260,34 +146,6 @@ __device__ __forceinline__ float reg_expsum(const f32x16 &v, float mx, float cut
 #pragma unroll
     for (int r = 0; r + w < n; r += 2 * w) e[r] += e[r + w];
   return e[0];
-}
-// split-operand paths: Σ_r exp(v[r] − mx) without Kaldi's cutoff (terms below max + ln ε add < 4e-6 to the sum in total —
-// inside those paths' tolerance, and mathematically the exact log-sum-exp), two terms per packed instruction: 16 exp2,
-// 8 v_pk_add_f32, 8 v_pk_mul_f32, 8 packed adds per tile instead of ≈110 instructions.  The difference is formed BEFORE the
-// multiplication by log2 e: fma(v, log2e, −mx·log2e) would carry the rounding of mx·log2e (2^-24·|mx|) into every term —
-// 5e-6 on the result at |mx| = 100 and an overflow to inf for an outlier frame with |mx| ≳ 1e9.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float reg_expsum_fast(const f32x16 &v, float mx, float l2e = 1.44269504088896341f) {
-  const f32x2 lv = {l2e, l2e};
-  const f32x2 mv = {mx, mx};
-  f32x2 e[8];
-#pragma unroll
-  for (int r = 0; r < 8; r++) {
-    const f32x2 x = {v[2 * r], v[2 * r + 1]};
-    const f32x2 arg = (x - mv) * lv;
-    e[r].x = __builtin_amdgcn_exp2f(arg.x);
-    e[r].y = __builtin_amdgcn_exp2f(arg.y);
-  }
-#pragma unroll
-  for (int w = 1; w < 8; w <<= 1)
-#pragma unroll
-    for (int r = 0; r + w < 8; r += 2 * w) e[r] += e[r + w];
-  return e[0].x + e[0].y;
-}
-
-// LL = max + ln(sum) with the hardware log2 (1 ulp on a value ≤ 7, i.e. ≲4e-7 absolute).
-__device__ __forceinline__ float finish(float mx, float sum) {
-  return fmaf(__builtin_amdgcn_logf(sum), 0.693147180559945309f, mx);
 }
 
 // One work item = (utterance, 64-frame tile): score_tile walks the utterance's pdf list for those frames.
@@ -311,7 +169,7 @@ __device__ __forceinline__ void score_tile(const GmmParams &p, int utt, int t_ba
   // the class, because the host ordered each class by that frame.
   int need[6], lo_[6];
   {
-    int t_last = min(T, t_base + kFramesPerWave) - 1 + p.ff_bias;
+    int t_last = min(T, t_base + kFramesPerWave) - 1;
     int d_lo = 0;
     if (p.b_mode) { const Band bd = band_of(p, utt); t_last = bd.hi; d_lo = bd.lo; }
     int off = 0;
@@ -359,7 +217,7 @@ __device__ __forceinline__ void score_tile(const GmmParams &p, int utt, int t_ba
     const int cnt = p.group_counts[(size_t)utt * p.groups + run];
     int nd = cnt, lw = 0;
     if (p.first_frame) {
-      int t_last = min(T, t_base + kFramesPerWave) - 1 + p.ff_bias, d_lo = 0;
+      int t_last = min(T, t_base + kFramesPerWave) - 1, d_lo = 0;
       if (p.b_mode) { const Band bd = band_of(p, utt); t_last = bd.hi; d_lo = bd.lo; }
       nd = 0;
       for (int i0 = 0; i0 < cnt; i0 += 64) {
@@ -411,9 +269,7 @@ __device__ __forceinline__ void score_tile(const GmmParams &p, int utt, int t_ba
       const int x_pdf3 = list[min(j + 3, last)];
       __builtin_amdgcn_sched_barrier(0);
       const float *wn = wl + (size_t)r1 * p.kpad;
-#ifndef GMM_DIAG_NO_LOADS
       Tile<M8, kNT>::load_gc32(p.gc + r1, h, g);
-#endif
 #pragma unroll
       for (int m = 0; m < M8; m++) {
 #pragma unroll
@@ -422,9 +278,7 @@ __device__ __forceinline__ void score_tile(const GmmParams &p, int utt, int t_ba
           for (int n = 0; n < kNT; n++)
             acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][cc4], tile.b[n][4 * m + cc4], acc[n], 0, 0, 0);
         }
-#ifndef GMM_DIAG_NO_LOADS   // timing-only builds (tools/: -DGMM_DIAG_*): results are wrong by construction
         a[m] = *reinterpret_cast<const f32x4 *>(wn + 256 * m);
-#endif
         __builtin_amdgcn_sched_barrier(0);
       }
       r1 = __builtin_amdgcn_readfirstlane(x_r2);
@@ -432,15 +286,11 @@ __device__ __forceinline__ void score_tile(const GmmParams &p, int utt, int t_ba
       float mx[kNT], sum[kNT];
 #pragma unroll
       for (int n = 0; n < kNT; n++) {
-#ifdef GMM_DIAG_NO_EPILOGUE
-        mx[n] = acc[n][0] + acc[n][15]; sum[n] = 1.0f;
-#else
         float m = reg_max<0, 16>(acc[n]);
         m = fmaxf(m, swap32(m, h));
         float sv = reg_expsum<0, 16>(acc[n], m, m + p.min_log_diff);
         sv += swap32(sv, h);
         mx[n] = m; sum[n] = sv;
-#endif
       }
       if constexpr (kNT == 2) {
         // both halves hold every tile's (max, sum): half h finishes tile h (one log per lane).
@@ -449,11 +299,7 @@ __device__ __forceinline__ void score_tile(const GmmParams &p, int utt, int t_ba
         const float v = finish(h ? mx[1] : mx[0], h ? sum[1] : sum[0]);
         const int jj = (j - first32) & 31;
         stage[(32 * h + col) * 33 + jj] = v;
-#ifdef GMM_DIAG_NO_FLUSH
-        if (v == 12345.678f) {   // never true, but keeps the scores alive
-#else
         if (jj == 31 || j == last) {
-#endif
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           __builtin_amdgcn_wave_barrier();
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -697,65 +543,6 @@ __global__ __launch_bounds__(64 * kWaves, kMinWaves) void gmm_kernel(GmmParams p
 // registers: 120 VGPRs) share every 32-row block through LDS, double-buffered — while block j is multiplied out of one
 // buffer, block j+1 travels global → registers → the other buffer; one barrier per block.
 // General form (models that contain multi-block pdfs); gmm_split_single_kernel below is the lean form for single-block pdfs.
-// x̃ = [x, x²] of a wavefront's two 32-frame tiles (frames t_base + 32 n + col, clamped into the utterance), split into
-// the MFMA's B operands: b[tile][step][piece], lane = (frame col, k-half h).  kPieces = 3: bf16 triples (v = v1 + v2 + v3,
-// round to nearest even each).  kPieces = 2: f16 pairs of the column-scaled value; returns true when a scaled value
-// leaves the f16 range (or is NaN) — the caller then hands the whole tile to the bf16×3 pass.
-template <int kSteps, int kPieces, typename Op8>
-__device__ __forceinline__ bool split_features(const GmmParams &p, int64_t f0, int T, int t_base, int col, int h,
-                                               Op8 (&b)[2][kSteps][kPieces]) {
-  bool bad = false;
-#pragma unroll
-  for (int n = 0; n < 2; n++) {
-    int t = t_base + 32 * n + col;
-    t = t < T ? t : T - 1;
-    t = t < 0 ? 0 : t;
-    const float *x = p.feats + (f0 + t) * p.dim;
-    const bool vec8 = (p.dim & 7) == 0;   // every group of 8 operand columns then lies wholly in x, in x² or in the padding
-#pragma unroll
-    for (int s = 0; s < kSteps; s++) {
-      float xv8[8], fs8[8];
-      {
-        const int k0 = 16 * s + 8 * h;
-        if (vec8) {   // two 16-byte loads per group instead of eight 4-byte ones (same values)
-          const int i0 = k0 < p.dim ? k0 : (k0 < 2 * p.dim ? k0 - p.dim : 0);
-          const float4 lo4 = *reinterpret_cast<const float4 *>(x + i0), hi4 = *reinterpret_cast<const float4 *>(x + i0 + 4);
-          xv8[0] = lo4.x; xv8[1] = lo4.y; xv8[2] = lo4.z; xv8[3] = lo4.w; xv8[4] = hi4.x; xv8[5] = hi4.y; xv8[6] = hi4.z; xv8[7] = hi4.w;
-          if constexpr (kPieces == 2) {
-            const float4 f0_ = *reinterpret_cast<const float4 *>(p.fscale + k0), f1_ = *reinterpret_cast<const float4 *>(p.fscale + k0 + 4);
-            fs8[0] = f0_.x; fs8[1] = f0_.y; fs8[2] = f0_.z; fs8[3] = f0_.w; fs8[4] = f1_.x; fs8[5] = f1_.y; fs8[6] = f1_.z; fs8[7] = f1_.w;
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; e++) {
-            const int k = k0 + e;
-            xv8[e] = x[k < p.dim ? k : (k < 2 * p.dim ? k - p.dim : 0)];
-            if constexpr (kPieces == 2) fs8[e] = p.fscale[k];
-          }
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        const int k = 16 * s + 8 * h + e;
-        const float xv = xv8[e];
-        const float v = k < p.dim ? xv : (k < 2 * p.dim ? xv * xv : 0.0f);
-        if constexpr (kPieces == 2) {
-          const float sv = v * fs8[e];
-          bad |= !(fabsf(sv) <= 65000.0f);
-          const _Float16 v1 = (_Float16)sv;
-          b[n][s][0][e] = v1; b[n][s][1][e] = (_Float16)(sv - (float)v1);
-        } else {
-          const __bf16 v1 = (__bf16)v;
-          const float r1 = v - (float)v1;
-          const __bf16 v2 = (__bf16)r1;
-          const float r2 = r1 - (float)v2;
-          b[n][s][0][e] = v1; b[n][s][1][e] = v2; b[n][s][2][e] = (__bf16)r2;
-        }
-      }
-    }
-  }
-  return bad;
-}
 
 // One 32-row model block (split operands in LDS: [step][piece][half][row] 16-byte units; its 32 gconsts) times a
 // wavefront's two frame tiles → acc.  Operand pieces of step s+1 are read from LDS while step s is multiplied; six (three)
@@ -847,8 +634,8 @@ __global__ __launch_bounds__(256, 2) void gmm_bf16_kernel(GmmParams p) {
       // 64 frames can be asked for; beyond them the wavefront only helps with the copies.
       int n0 = cc0, n1 = cc1, n0_mine = cc0, n1_mine = cc1;
       if (p.first_frame) {
-        const int t_last = min(T, (tl + 1) * kFramesPerTile) - 1 + p.ff_bias;
-        const int t_mine = min(T, t_base + kFramesPerWave) - 1 + p.ff_bias;
+        const int t_last = min(T, (tl + 1) * kFramesPerTile) - 1;
+        const int t_mine = min(T, t_base + kFramesPerWave) - 1;
         n0 = n1 = n0_mine = n1_mine = 0;
         for (int i0 = 0; i0 < cc0 + cc1; i0 += 64) {
           const int i = i0 + lane;
@@ -950,9 +737,7 @@ __global__ __launch_bounds__(256, 2) void gmm_bf16_kernel(GmmParams p) {
         __syncthreads();
         for (int j = c0; j < c1; j++) {
           const int buf = (j - c0) & 1;
-#ifndef BF16_DIAG_NO_FETCH   // timing-only builds (tools/gmm_ablation.sh): results are wrong by construction
           fetch(block_of(j + 1));                          // block j+1 (the chunk's last trip re-fetches its last block: harmless)
-#endif
           const int ecol = kMulti ? col_lds[j - c0] : (j | kFirst | kLast);
           const int out_col = ecol & ~(kFirst | kLast);
           const bool mine = out_col < cc0 ? out_col < n0_mine : out_col - cc0 < n1_mine;
@@ -963,15 +748,11 @@ __global__ __launch_bounds__(256, 2) void gmm_bf16_kernel(GmmParams p) {
             float mx[kNT], sum[kNT];
 #pragma unroll
             for (int n = 0; n < kNT; n++) {
-#ifdef BF16_DIAG_NO_EPILOGUE
-              mx[n] = acc[n][0] + acc[n][15]; sum[n] = 1.0f;
-#else
               float m = reg_max<0, 16>(acc[n]);
               m = fmaxf(m, swap32(m, h));
               float sv = reg_expsum_fast(acc[n], m, l2e_s);
               sv += swap32(sv, h);
               mx[n] = m; sum[n] = sv;                        // mx stays in accumulator units (× S) until the pdf's last block
-#endif
             }
             if (kMulti && !(ecol & kFirst)) {
               // online log-sum-exp: fold this block's (max, sum) into the pdf's running pair
@@ -987,11 +768,7 @@ __global__ __launch_bounds__(256, 2) void gmm_bf16_kernel(GmmParams p) {
 #pragma unroll
               for (int n = 0; n < kNT; n++) { mx_run[n] = mx[n]; sum_run[n] = sum[n]; }
             }
-#ifdef BF16_DIAG_NO_FLUSH
-            if (mx[0] == 12345.678f) {
-#else
             if (ecol & kLast) {
-#endif
               const float v = finish((h ? mx[1] : mx[0]) * inv_s, h ? sum[1] : sum[0]);
               if (staged > 0 && out_col != stage_col0 + staged) flush();   // a jump in the column sequence (class change)
               if (staged == 0) stage_col0 = out_col;
@@ -999,12 +776,8 @@ __global__ __launch_bounds__(256, 2) void gmm_bf16_kernel(GmmParams p) {
               if (++staged == 32) flush();
             }
           }
-#ifndef BF16_DIAG_NO_FETCH
           deposit(buf ^ 1);
-#endif
-#ifndef BF16_DIAG_NO_BARRIER
           __syncthreads();                               // block j+1 is in place; everybody is done with block j
-#endif
         }
         }
         if (staged > 0) flush();
@@ -1069,8 +842,8 @@ __global__ __launch_bounds__(256, 2) void gmm_split_single_kernel(GmmParams p) {
       // the wavefront only helps with the copies.
       int n_single = n_all, n_mine = n_all;
       if (p.first_frame) {
-        const int t_last = min(T, (tl + 1) * kFramesPerTile) - 1 + p.ff_bias;
-        const int t_mine = min(T, t_base + kFramesPerWave) - 1 + p.ff_bias;
+        const int t_last = min(T, (tl + 1) * kFramesPerTile) - 1;
+        const int t_mine = min(T, t_base + kFramesPerWave) - 1;
         n_single = 0; n_mine = 0;
         for (int i0 = 0; i0 < n_all; i0 += 64) {
           const int i = i0 + lane;
@@ -1130,9 +903,6 @@ __global__ __launch_bounds__(256, 2) void gmm_split_single_kernel(GmmParams p) {
         constexpr int kChunks = 27;
         // chunk c of the epilogue of the block held in pv; results are bit-identical to reg_max / reg_expsum_fast / finish
         auto epi = [&](int c, const f32x16 (&pv)[kNT], int column) {
-#ifdef BF16_DIAG_NO_EPILOGUE
-          if (c == 26) { smv[0] = pv[0][0] + pv[1][15]; stage[(32 * h + col) * 33 + column] = smv[0]; }
-#else
           const int n = (c < 3 || (c >= 6 && c < 16)) ? 0 : 1;           // tile the chunk works on
           if (c == 0 || c == 3) {
 #pragma unroll
@@ -1163,7 +933,6 @@ __global__ __launch_bounds__(256, 2) void gmm_split_single_kernel(GmmParams p) {
           } else if (c == 26) {
             stage[(32 * h + col) * 33 + column] = finish((h ? mxv[1] : mxv[0]) * inv_s, h ? smv[1] : smv[0]);
           }
-#endif
         };
         auto flush = [&](int jdone) {                        // columns [jdone − jdone%32, jdone] of the staged scores → HBM
           const int jj = jdone & 31;
@@ -1193,15 +962,11 @@ __global__ __launch_bounds__(256, 2) void gmm_split_single_kernel(GmmParams p) {
         auto trip = [&](auto par_c, int j) {
           constexpr int par = decltype(par_c)::value;
           constexpr int buf = par;
-#if !defined(BF16_DIAG_NO_FLUSH) && !defined(GMM_FLUSH_AT_END)
           // A full window of 32 staged columns (its last one, block j-2's, was written during the previous trip) goes to
           // HBM at the START of a trip: stores share vmcnt with the block copy, and this way they have a whole trip to be
           // acknowledged before landed() waits on the counter — issued at the end of a trip they were waited for at once.
           if (active && j < n_mine && j > 1 && ((j - 2) & 31) == 31) flush(j - 2);
-#endif
-#ifndef BF16_DIAG_NO_FETCH   // timing-only builds (tools/gmm_ablation.sh): results are wrong by construction
           fetch(block_of(j + 1), buf ^ 1);                 // block j+1 (the chunk's last trip re-fetches its last block: harmless)
-#endif
           if (active && j < n_mine) {
             f32x16 (&cur)[kNT] = acc2[par];
             const f32x16 (&prev)[kNT] = acc2[par ^ 1];
@@ -1239,25 +1004,14 @@ __global__ __launch_bounds__(256, 2) void gmm_split_single_kernel(GmmParams p) {
                     cur[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[pa[t6]], b[n][s][pb[t6]], cin, 0, 0, 0);
                   const int slot = (s * kProd + t6) * kNT + n;
                   if (slot % kStride == 0 && slot / kStride < kChunks) epi(slot / kStride, prev, column);
-#ifndef BF16_DIAG_NO_INTERLEAVE
                   __builtin_amdgcn_sched_barrier(0);
-#endif
                 }
 #pragma unroll
               for (int qq = 0; qq < kPieces; qq++) a_cur[qq] = a_nxt[qq];
             }
-#ifdef BF16_DIAG_NO_FLUSH
-            if (smv[0] == 12345.678f) flush(j - 1);          // timing-only build: keeps the staged values alive
-#else
-#ifdef GMM_FLUSH_AT_END
-            if (j > 0 && ((j - 1) & 31) == 31) flush(j - 1);
-#endif
-#endif
           }
           landed();
-#ifndef BF16_DIAG_NO_BARRIER
           __syncthreads();                                 // block j+1 is in place; everybody is done with block j
-#endif
         };
         for (int j = c0; j < c1; j += 2) {
           trip(std::integral_constant<int, 0>{}, j);
@@ -1266,9 +1020,7 @@ __global__ __launch_bounds__(256, 2) void gmm_split_single_kernel(GmmParams p) {
         }
         if (active && n_mine > 0) {                          // drain: the last block's epilogue and the open columns
           const int jp = n_mine - 1;
-#if !defined(BF16_DIAG_NO_FLUSH) && !defined(GMM_FLUSH_AT_END)
           if (jp > 0 && ((jp - 1) & 31) == 31) flush(jp - 1);   // a window completed by the last trip is still staged
-#endif
           if (jp & 1) {
 #pragma unroll
             for (int c = 0; c < kChunks; c++) epi(c, acc2[1], jp & 31);
@@ -1276,9 +1028,6 @@ __global__ __launch_bounds__(256, 2) void gmm_split_single_kernel(GmmParams p) {
 #pragma unroll
             for (int c = 0; c < kChunks; c++) epi(c, acc2[0], jp & 31);
           }
-#ifdef BF16_DIAG_NO_FLUSH
-          if (smv[0] == 12345.678f)
-#endif
           flush(jp);
         }
       }
@@ -1345,8 +1094,8 @@ __global__ __launch_bounds__(256, 2) void gmm_split_small_kernel(GmmParams p) {
       // the wavefront only helps with the copies.
       int n_single = n_all, n_mine = n_all;
       if (p.first_frame) {
-        const int t_last = min(T, (tl + 1) * kFramesPerTile) - 1 + p.ff_bias;
-        const int t_mine = min(T, t_base + kFramesPerWave) - 1 + p.ff_bias;
+        const int t_last = min(T, (tl + 1) * kFramesPerTile) - 1;
+        const int t_mine = min(T, t_base + kFramesPerWave) - 1;
         n_single = 0; n_mine = 0;
         for (int i0 = 0; i0 < n_all; i0 += 64) {
           const int i = i0 + lane;
@@ -1492,608 +1241,10 @@ __global__ __launch_bounds__(256, 2) void gmm_split_small_kernel(GmmParams p) {
   }
 }
 
-// Lazy scoring, once per batch: the first packed model row of every score column (saves the pdf id → row lookup, one
-// dependent load per model block and in every wavefront's start-up chain).
-__global__ void gmm_col_rows_kernel(GmmParams p, int32_t *out) {
-  const int utt = blockIdx.x;
-  const int64_t l0 = p.pdf_off[utt], l1 = p.pdf_off[utt + 1];
-  for (int64_t j = l0 + threadIdx.x; j < l1; j += blockDim.x) {
-    const int pdf = p.pdf_list[j];
-    int r = p.row0[pdf];
-    if (p.col_nb_packed) { const int nb = p.nblk[pdf]; if (nb > 1) r |= nb - 1; }
-    out[j] = r;
-  }
-}
-
-// Lazy scoring, once per window: the band's index range [lo, hi) in every run of class 0 (slots 0..groups-1; one run when the
-// plan is not grouped), in classes 2, 3, 4 and in class 1 (the slots after the runs'), relative to the class's first column — what every scoring
-// wavefront of the sub-tile would otherwise search for itself (two dependent memory trips each).  One wavefront per utterance.
-constexpr int kRunSlots = kMfaRunSlots;   // slots 0..kRunSlots-1: runs of class 0; then classes 2, 3, 4; then class 1; then class 5
-constexpr int kRangeSlots = kMfaRangeSlots;
-__global__ __launch_bounds__(256) void gmm_band_ranges_kernel(GmmParams p) {
-  const int lane = threadIdx.x & 63;
-  const int utt = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (utt >= p.n_utt) return;
-  if (p.b_t_begin > 0 && p.b_done && p.b_done[(size_t)utt * p.b_done_stride + p.b_done_word] != 0) return;
-  const int64_t l0 = p.pdf_off[utt];
-  const int32_t *cc6 = p.class_counts + (size_t)utt * 6;
-  const Band bd = band_of(p, utt);
-  const int runs = p.groups > 1 ? p.groups : 1;
-  int32_t *out = p.ranges + (size_t)utt * kRangeSlots * 2;
-  int off = 0;
-  for (int slot = 0; slot < kRangeSlots; slot++) {
-    int cnt = 0, base = 0;     // the run searched, its first column relative to the class, the class's first column in `off`
-    if (slot < kRunSlots) {
-      if (slot >= runs) continue;
-      if (p.groups > 1) { const int32_t *gc = p.group_counts + (size_t)utt * p.groups; for (int g = 0; g < slot; g++) base += gc[g]; cnt = gc[slot]; }
-      else cnt = cc6[0];
-      off = 0;
-    } else if (slot == kRunSlots + 3) {
-      off = cc6[0];
-      cnt = cc6[1];
-    } else if (slot == kRunSlots + 4) {
-      off = cc6[0] + cc6[1] + cc6[2] + cc6[3] + cc6[4];
-      cnt = cc6[5];
-    } else {
-      const int cls = slot - kRunSlots + 2;
-      off = cc6[0] + cc6[1];
-      for (int k = 2; k < cls; k++) off += cc6[k];
-      cnt = cc6[cls];
-    }
-    int nh = 0, nl = 0;
-    for (int i0 = 0; i0 < cnt; i0 += 256) {
-      int ff[4], ld[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int i = min(i0 + 64 * u + lane, cnt - 1);
-        ff[u] = p.first_frame[l0 + off + base + i]; ld[u] = p.last_depth[l0 + off + base + i];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const bool in = i0 + 64 * u + lane < cnt;
-        nh += __popcll(__ballot(in && ff[u] <= bd.hi));
-        nl += __popcll(__ballot(in && ld[u] < bd.lo));
-      }
-    }
-    if (lane == 0) { out[2 * slot] = base + min(nl, nh); out[2 * slot + 1] = base + nh; }
-  }
-}
-
-// Index of the 64-frame tile `tile` of utterance `utt` in the pre-split operand buffer: ⌊frame_off/64⌋ + utt + tile is
-// monotone and leaves every utterance room for ⌈T/64⌉ tiles without a separate offset table.
-__device__ __forceinline__ int64_t xsplit_tile_index(int64_t frame_off_u, int utt, int tile) { return (frame_off_u >> 6) + utt + tile; }
-
-// Lazy scoring pre-pass: the f16 hi/lo operands [x, x²]·scale of every 64-frame tile, in the register layout the band
-// kernel's MFMAs read (b[n][step][piece] of lane l at ((n·kSteps + step)·2 + piece)·64 + l), so that a wavefront starts
-// a window with twenty coalesced 1 KiB loads instead of 160 strided 4-byte loads and the split arithmetic — the values are
-// those of split_features bit for bit.  One wavefront per tile.
-template <int kSteps>
-__global__ __launch_bounds__(256) void gmm_presplit_kernel(GmmParams p, uint4 *out, int *bad_out, int tiles_per_utt) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t item = (int64_t)blockIdx.x * 4 + wave;
-  const int utt = (int)(item / tiles_per_utt), tile = (int)(item - (int64_t)utt * tiles_per_utt);
-  if (utt >= p.n_utt) return;
-  const int64_t f0 = p.frame_off[utt];
-  const int T = (int)(p.frame_off[utt + 1] - f0);
-  if (tile * 64 >= T) return;
-  f16x8 b[2][kSteps][2];
-  const bool bad = split_features<kSteps, 2>(p, f0, T, tile * 64, lane & 31, lane >> 5, b);
-  const int64_t ti = xsplit_tile_index(f0, utt, tile);
-  uint4 *dst = out + ti * (2 * kSteps * 2 * 64) + lane;
-#pragma unroll
-  for (int n = 0; n < 2; n++)
-#pragma unroll
-    for (int s_ = 0; s_ < kSteps; s_++)
-#pragma unroll
-      for (int q = 0; q < 2; q++) dst[((n * kSteps + s_) * 2 + q) * 64] = __builtin_bit_cast(uint4, b[n][s_][q]);
-  const bool any_bad = __ballot(bad) != 0ull;
-  if (lane == 0) bad_out[ti] = any_bad ? 1 : 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Lazy (windowed) scoring — mfa_gmm_score_window.  Kaldi evaluates its decodable lazily: a score exists only if a live
-// token's arc asked for it.  The dense kernels above score every pdf of the utterance's graph for every frame from the
-// pdf's first reachable frame on — measured, ≈9× more cells than the decoder reads.  Here the decoder runs in windows of
-// K frames and publishes, at each window end, the band of graph depths its live tokens can reach within K arcs; the
-// kernel below scores, for the window's frames, only the pdfs whose arcs leave states inside that band.
-//
-// With so few frames per (utterance, pdf) there is nothing to share a model block across: one wavefront owns one
-// (utterance, 64-frame sub-tile), keeps its x̃ operands in registers (as above) and streams the band's model blocks
-// straight from L2 / Infinity Cache into its A registers — 10 coalesced 1 KiB loads per 32-row block, each operand
-// register re-loaded for the next block as soon as the MFMAs that read it have been issued.  Per block: 30 (60) MFMAs,
-// the log-sum-exp, one staged score column.  Arithmetic per cell is that of gmm_split_single_kernel exactly (same operand
-// split, same product order, same epilogue expressions): a cell scored here is bit-identical to the dense kernel's.
-// Bound: the 10 KiB (15 KiB) of operands per block and 64 frames — fabric bandwidth, not the matrix pipe.
-template <int kSteps, int kPieces>
-__global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
-  constexpr bool kHalf = kPieces == 2;
-  using op8 = std::conditional_t<kHalf, f16x8, bf16x8>;
-  constexpr int kUnits = kSteps * kPieces * 2 * 32;    // 16-byte units per block
-  __shared__ float stage_all[4][64 * 33];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  float *stage = stage_all[wave];
-  const int grp = p.b_split ? band_split_block(p).y : 0;                          // the run of class 0 this wavefront scores
-#ifdef GMM_BAND_STAMPS
-  // phase accounting (-DGMM_BAND_STAMPS, buffer from mfa_debug_gmm_trace): Σ 100 MHz ticks of {item + band search, feature
-  // split, block loop}, wavefronts with work, blocks
-  const unsigned long long st0 = wall_clock64();
-#endif
-  int utt, r, chunk = 0;
-  if (!band_item(p, wave, utt, r, &chunk)) return;
-  const int64_t f0 = p.frame_off[utt];
-  const int T = (int)(p.frame_off[utt + 1] - f0);
-  const int t_base = band_t_begin(p, utt) + 64 * r;
-  if (t_base >= T) return;
-  int *redo_flag = p.redo + ((size_t)utt * p.b_sub + r) * p.b_nchunk + chunk;
-  if (!kHalf && p.redo_mode == 2 && *redo_flag == 0) return;          // only what the f16 pass declined
-  const int col = lane & 31, h = lane >> 5;
-  const int64_t l0 = p.pdf_off[utt];
-  const int P = (int)(p.pdf_off[utt + 1] - l0);
-  const int32_t *list = p.pdf_list + l0;
-  const int32_t *cc6 = p.class_counts + (size_t)utt * 6;
-  const Band bd = band_of(p, utt);
-  // The pre-split operands depend on nothing but the sub-tile: requested first, they travel while the band is looked up
-  // (volatile: the loads stay here instead of sinking below the early exit).
-  op8 b[2][kSteps][kPieces];
-  bool bad = false;
-  const bool presplit = kHalf && p.xsplit != nullptr;
-  if (presplit) {
-    const int64_t ti = xsplit_tile_index(f0, utt, t_base >> 6);
-    const uint4 *src = p.xsplit + ti * (2 * kSteps * 2 * 64) + lane;
-#pragma unroll
-    for (int n = 0; n < 2; n++)
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++)
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) {
-#ifndef GMM_BAND_X_STREAMING
-          uint4 v;
-          const volatile uint4 *a4 = src + ((n * kSteps + s_) * 2 + (q & 1)) * 64;
-          v.x = a4->x; v.y = a4->y; v.z = a4->z; v.w = a4->w;
-#else     // measured (-DGMM_BAND_X_STREAMING): non-temporal tile loads keep more of the model in L2 (FETCH_SIZE 30 -> 24.5 GB per
-          // step) but the kernel is 3 % slower, the throughput unchanged
-          typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-          const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(src + ((n * kSteps + s_) * 2 + (q & 1)) * 64));
-#endif
-          b[n][s_][q] = __builtin_bit_cast(op8, v);
-        }
-    bad = p.xsplit_bad[ti] != 0;
-  }
-  // band range [lo, hi) of every class this kernel scores: 0 (one 32-row block per pdf) and 2, 3, 4 (16-, 8-, 4-row slots);
-  // classes 1 (pdfs of more than 32 Gaussians) and 5 (single Gaussians) are the f32 band kernel's
-  int lo_c[5], hi_c[5], base_c[5];
-  if (p.ranges) {   // looked up once per utterance and window by gmm_band_ranges_kernel
-    const int32_t *rg = p.ranges + (size_t)utt * kRangeSlots * 2;
-    int off = 0;
-#pragma unroll
-    for (int cls = 0; cls < 5; cls++) {
-      const int slot = cls == 0 ? grp : (cls == 1 ? kRunSlots + 3 : kRunSlots + cls - 2);
-      base_c[cls] = off; off += cc6[cls];
-      lo_c[cls] = rg[2 * slot]; hi_c[cls] = rg[2 * slot + 1];
-    }
-  } else {
-    int off = 0;
-#pragma unroll
-    for (int cls = 0; cls < 5; cls++) {
-      const int cnt_cls = cc6[cls];
-      int cnt = cnt_cls, seg = 0;       // the run searched: the whole class, or (class 0 of a grouped plan) this wavefront's run
-      if (cls == 0 && p.b_split) {
-        const int32_t *gc = p.group_counts + (size_t)utt * p.groups;
-        for (int g = 0; g < grp; g++) seg += gc[g];
-        cnt = gc[grp];
-      }
-      int nh = 0, nl = 0;
-      {
-        // four chunks per trip, every load issued before the first ballot waits (one memory round trip per 256 pdfs, not four)
-        for (int i0 = 0; i0 < cnt; i0 += 256) {
-          int ff[4], ld[4];
-#pragma unroll
-          for (int u = 0; u < 4; u++) {
-            const int i = min(i0 + 64 * u + lane, cnt - 1);
-            ff[u] = p.first_frame[l0 + off + seg + i]; ld[u] = p.last_depth[l0 + off + seg + i];
-          }
-#pragma unroll
-          for (int u = 0; u < 4; u++) {
-            const bool in = i0 + 64 * u + lane < cnt;
-            nh += __popcll(__ballot(in && ff[u] <= bd.hi));
-            nl += __popcll(__ballot(in && ld[u] < bd.lo));
-          }
-        }
-      }
-      lo_c[cls] = seg + min(nl, nh); hi_c[cls] = seg + nh; base_c[cls] = off;
-      off += cnt_cls;
-    }
-  }
-  if (p.b_chunk > 0) {                                 // list passes: this wavefront's share of the band (class 0 in chunks,
-    lo_c[0] += chunk * p.b_chunk;                      // the small-slot classes with chunk 0)
-    hi_c[0] = min(hi_c[0], lo_c[0] + p.b_chunk);
-    if (chunk != 0) { hi_c[2] = lo_c[2]; hi_c[3] = lo_c[3]; hi_c[4] = lo_c[4]; }
-  }
-  if (p.b_split) {
-    // the small-slot classes have no runs: the virtual blocks (32 / slot pdfs each) of their three bands, laid end to end,
-    // are cut into `groups` pieces, one per wavefront of the sub-tile — all of them on run 0's wavefront would be all of
-    // them on one XCD, and a piece of every class on every wavefront (the first version) was three pipelines to fill and
-    // drain per wavefront, three or four blocks each: a piece now lies inside one class, rarely two
-    int nb_c[5], tot = 0;
-#pragma unroll
-    for (int cls = 2; cls < 5; cls++) {
-      const int kp = cls == 2 ? 2 : (cls == 3 ? 4 : 8);
-      nb_c[cls] = (hi_c[cls] + kp - 1) / kp - lo_c[cls] / kp;
-      if (lo_c[cls] >= hi_c[cls]) nb_c[cls] = 0;
-      tot += nb_c[cls];
-    }
-    const int per = (tot + p.groups - 1) / p.groups;
-    const int w0 = grp * per, w1 = min(tot, w0 + per);
-    int pos = 0;
-#pragma unroll
-    for (int cls = 2; cls < 5; cls++) {
-      const int kp = cls == 2 ? 2 : (cls == 3 ? 4 : 8);
-      const int jb0 = lo_c[cls] / kp;
-      const int a = jb0 + max(w0 - pos, 0), b = jb0 + min(w1 - pos, nb_c[cls]);
-      pos += nb_c[cls];
-      if (a >= b) hi_c[cls] = lo_c[cls];
-      else { lo_c[cls] = max(lo_c[cls], a * kp); hi_c[cls] = min(hi_c[cls], b * kp); }
-    }
-  }
-  // class 1 (pdfs of more than 32 Gaussians, few): its band's columns go round the sub-tile's wavefronts one by one
-  const int step1 = p.b_split ? p.groups : (p.b_chunk > 0 ? p.b_nchunk : 1);
-  const int first1 = lo_c[1] + (p.b_split ? grp : (p.b_chunk > 0 ? chunk : 0));
-  const int lo = lo_c[0], hi = hi_c[0];
-  if (lo >= hi && first1 >= hi_c[1] && lo_c[2] >= hi_c[2] && lo_c[3] >= hi_c[3] && lo_c[4] >= hi_c[4]) {
-    if (kHalf && lane == 0) *redo_flag = 0;
-    return;
-  }
-#ifdef GMM_BAND_STAMPS
-  const unsigned long long st1 = wall_clock64();
-#endif
-  if (!presplit) bad = split_features<kSteps, kPieces>(p, f0, T, t_base, col, h, b);
-#ifdef GMM_BAND_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const unsigned long long st2 = wall_clock64();
-#endif
-  if constexpr (kHalf) {
-    const bool any_bad = __ballot(bad) != 0ull;
-    if (lane == 0) *redo_flag = any_bad ? 1 : 0;
-    if (any_bad) return;                                               // a scaled feature left the f16 range: bf16×3 pass
-  }
-  const float inv_s = kHalf ? p.acc_scale_inv : 1.0f;
-  const float l2e_s = 1.44269504088896341f * inv_s;
-  float *out = p.out + p.ll_off[utt];
-  constexpr int kProd = kHalf ? 3 : 6;
-  constexpr int pa[6] = {kHalf ? 1 : 2, kHalf ? 0 : 1, 0, 1, 0, 0}, pb[6] = {0, 1, kHalf ? 0 : 2, 0, 1, 0};
-  // `cnt` staged columns, the first of them score column c0 of the utterance's matrix → HBM as 128-byte row segments
-  auto flush_cols = [&](int c0, int cnt) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll 4
-    for (int i = 0; i < 32; i++) {
-      const int rr = h + 2 * i, t = t_base + rr;
-      if (col < cnt && t < T) __builtin_nontemporal_store(stage[rr * 33 + col], &out[(size_t)t * P + c0 + col]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  };
-
-  // ---------------------------------------------------------------- class 0: one pdf per 32-row block
-  if (lo < hi) {
-    const uint4 *wsrc = (kHalf ? p.wh : p.wb) + lane;
-    const float *gsrc = (kHalf ? p.gch : p.gc) + 4 * h;
-    const int last = hi - 1;
-    // First model row per column, precomputed per batch: ONE load.  The pdf id → row chain it replaces (row0[list[j]]) made
-    // the second load wait for the first — the youngest entry of the in-order vmcnt queue — i.e. drained every outstanding
-    // operand load of the next block at the top of each block.
-    const int32_t *crow = p.col_row0 + l0;
-    auto row0_at = [&](int jj) { return crow[min(jj, last)]; };
-    auto block_at = [&](int jj) {
-      const int blk = __builtin_amdgcn_readfirstlane(row0_at(jj)) >> 5;
-#ifdef BAND_DIAG_BLKMOD   // timing-only builds (-DBAND_DIAG_BLKMOD=8): every block from a cache-resident handful (wrong scores)
-      return blk % BAND_DIAG_BLKMOD;
-#else
-      return blk;
-#endif
-    };
-    op8 a[kSteps][kPieces];
-    f32x4 g[4];
-    {
-      const int blk = block_at(lo);
-      const uint4 *src = wsrc + (size_t)blk * kUnits;
-#pragma unroll
-      for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gsrc + (size_t)blk * 32 + 8 * q);
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++)
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-    }
-    int blk_next = block_at(lo + 1);
-#ifdef GMM_BAND_STAMPS
-    unsigned long long ph[4] = {0, 0, 0, 0};   // shader-clock cycles: MFMA phase (issue + operand waits), lookup wait, log-sum-exp + stage, flush
-#endif
-    for (int j = lo; j < hi; j++) {
-#ifdef GMM_BAND_STAMPS
-      const unsigned long long c0_ = clock64();
-#endif
-      const int x_next2 = row0_at(j + 2);                      // lookup two blocks ahead (oldest entry of the vmcnt queue)
-      f32x16 init, acc[2];
-#pragma unroll
-      for (int rr = 0; rr < 16; rr++) init[rr] = g[rr >> 2][rr & 3];
-      const uint4 *src = wsrc + (size_t)blk_next * kUnits;
-      const float *gn = gsrc + (size_t)blk_next * 32;
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++) {
-#pragma unroll
-        for (int t6 = 0; t6 < kProd; t6++)
-#pragma unroll
-          for (int n = 0; n < 2; n++) {
-            const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
-#ifdef BAND_DIAG_NO_MFMA   // timing-only builds: one product per step instead of six (results wrong by construction)
-            if (t6 > 0) { if (s_ == 0 && t6 == 1) acc[n] = cin; continue; }
-#endif
-            if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-            else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-          }
-        // this step's operand registers (and, after the first step, the gconst registers) are free: next block's rows.
-        // (A second operand set — two blocks in flight per wavefront — was measured: 12.70 vs 12.76 ms per step; the
-        //  kernel is bound by what the fabric delivers, ≈6.5 TB/s of 10 KiB blocks gathered from a 51 MB table.)
-        if (s_ == 0) {
-#pragma unroll
-          for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gn + 8 * q);
-        }
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#ifdef GMM_BAND_STAMPS
-      const unsigned long long c1_ = clock64();
-#endif
-      blk_next = __builtin_amdgcn_readfirstlane(x_next2) >> 5;
-#ifdef BAND_DIAG_BLKMOD
-      blk_next %= BAND_DIAG_BLKMOD;
-#endif
-#ifdef GMM_BAND_STAMPS
-      const unsigned long long c2_ = clock64();
-#endif
-      float mx[2], sum[2];
-#pragma unroll
-      for (int n = 0; n < 2; n++) {
-#ifdef BAND_DIAG_NO_EPI   // timing-only builds: results are wrong by construction
-        mx[n] = acc[n][0] + acc[n][15]; sum[n] = 1.0f;
-#else
-        float m = reg_max<0, 16>(acc[n]);
-        m = fmaxf(m, swap32(m, h));
-        float sv = reg_expsum_fast(acc[n], m, l2e_s);
-        sv += swap32(sv, h);
-        mx[n] = m; sum[n] = sv;
-#endif
-      }
-      const int jj = (j - lo) & 31;
-      stage[(32 * h + col) * 33 + jj] = finish((h ? mx[1] : mx[0]) * inv_s, h ? sum[1] : sum[0]);
-#ifdef GMM_BAND_STAMPS
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const unsigned long long c3_ = clock64();
-#endif
-      if (jj == 31 || j == last) flush_cols(j - jj, jj + 1);
-#ifdef GMM_BAND_STAMPS
-      const unsigned long long c4_ = clock64();
-      ph[0] += c1_ - c0_; ph[1] += c2_ - c1_; ph[2] += c3_ - c2_; ph[3] += c4_ - c3_;
-#endif
-    }
-#ifdef GMM_BAND_STAMPS
-    if (p.trace && lane == 0 && kHalf) { atomicAdd(&p.trace[8], ph[0]); atomicAdd(&p.trace[9], ph[1]); atomicAdd(&p.trace[10], ph[2]); atomicAdd(&p.trace[11], ph[3]); }
-#endif
-  }
-
-  // ---------------------------------------------------------------- class 1: several 32-row blocks per pdf
-  // Online log-sum-exp over the pdf's blocks (running max M and sum S against it, per frame): (M, S) ← (max(M, m_b),
-  // S·2^((M − M')·l2e) + s_b·2^((m_b − M')·l2e)).  Products and per-block reductions are class 0's; pad rows carry gconst
-  // −1e30 and vanish in the sum.  No software pipeline: a trained model has a few such pdfs per band, if any.
-  // Software pipeline as class 0's: the operands of the next block — the pdf's next one, or the first block of this
-  // wavefront's next column — are requested as soon as a step's MFMAs have been issued; the column's (row, blocks) word is
-  // looked up one column ahead.
-  if (first1 < hi_c[1]) {
-    const uint4 *wsrc = (kHalf ? p.wh : p.wb) + lane;
-    const float *gsrc = (kHalf ? p.gch : p.gc) + 4 * h;
-    const int32_t *crow1 = p.col_row0 + l0 + base_c[1];
-    const int last1 = hi_c[1] - 1;
-    auto col_word = [&](int jj) { return crow1[min(jj, last1)]; };     // row | (blocks − 1) when packed
-    auto blocks_of = [&](int word, int jj) {
-      return p.col_nb_packed ? (word & 31) + 1 : __builtin_amdgcn_readfirstlane(p.nblk[list[base_c[1] + min(jj, last1)]]);
-    };
-    int j1 = first1;
-    int word = __builtin_amdgcn_readfirstlane(col_word(j1));
-    int nb = blocks_of(word, j1), blk = word >> 5, bk = 0;
-    int word_n = col_word(j1 + step1);                                 // stays a vector register until its column opens
-    op8 a[kSteps][kPieces];
-    f32x4 g[4];
-    {
-      const uint4 *src = wsrc + (size_t)blk * kUnits;
-#pragma unroll
-      for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gsrc + (size_t)blk * 32 + 8 * q);
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++)
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-    }
-    float M[2] = {0.0f, 0.0f}, S[2] = {0.0f, 0.0f};
-    for (;;) {
-      const bool last_blk = bk + 1 == nb;
-      const bool more_cols = j1 + step1 < hi_c[1];
-      int blk_n = blk + 1;                                             // (past the pdf's last block only when nothing follows:
-      if (last_blk) blk_n = more_cols ? __builtin_amdgcn_readfirstlane(word_n) >> 5 : blk;   //  then the same block again, unused)
-      f32x16 init, acc[2];
-#pragma unroll
-      for (int rr = 0; rr < 16; rr++) init[rr] = g[rr >> 2][rr & 3];
-      const uint4 *src = wsrc + (size_t)blk_n * kUnits;
-      const float *gn = gsrc + (size_t)blk_n * 32;
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++) {
-#pragma unroll
-        for (int t6 = 0; t6 < kProd; t6++)
-#pragma unroll
-          for (int n = 0; n < 2; n++) {
-            const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
-            if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-            else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-          }
-        if (s_ == 0) {
-#pragma unroll
-          for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gn + 8 * q);
-        }
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int n = 0; n < 2; n++) {
-        float m = reg_max<0, 16>(acc[n]);
-        m = fmaxf(m, swap32(m, h));
-        float sv = reg_expsum_fast(acc[n], m, l2e_s);
-        sv += swap32(sv, h);
-        if (bk == 0) { M[n] = m; S[n] = sv; }
-        else {
-          const float mn = fmaxf(M[n], m);
-          S[n] = S[n] * __builtin_amdgcn_exp2f((M[n] - mn) * l2e_s) + sv * __builtin_amdgcn_exp2f((m - mn) * l2e_s);
-          M[n] = mn;
-        }
-      }
-      blk = blk_n;
-      if (!last_blk) { bk++; continue; }
-      const int t = t_base + 32 * h + col;
-      if (t < T) __builtin_nontemporal_store(finish((h ? M[1] : M[0]) * inv_s, h ? S[1] : S[0]), &out[(size_t)t * P + base_c[1] + j1]);
-      if (!more_cols) break;
-      j1 += step1;
-      word = __builtin_amdgcn_readfirstlane(word_n);
-      nb = blocks_of(word, j1); bk = 0;
-      word_n = col_word(j1 + step1);
-    }
-  }
-
-  // ---------------------------------------------------------------- classes 2, 3, 4: 32 / slot pdfs per virtual block
-  // As gmm_split_small_kernel: the pdfs the list puts next to each other are gathered into one 32-row block (lane ↔ row
-  // ρ = lane mod 32 → pdf ρ / slot, its row ρ mod slot; rows past the range come from the model's dummy row), the MFMAs
-  // are those of class 0, the log-sum-exp runs over the slot's rows of each pdf — per pdf the very same expressions, so a
-  // cell scored here carries the dense kernel's bits.  The gather costs nothing extra: every lane loads through its own
-  // row pointer anyway.
-  auto run_small = [&](auto slot_c, int base, int lo_s, int hi_s) {
-    constexpr int kSlot = decltype(slot_c)::value, kPdfs = 32 / kSlot;
-    if (lo_s >= hi_s) return;
-    const uint4 *wsrc = kHalf ? p.wh : p.wb;
-    const float *gsrc = kHalf ? p.gch : p.gc;
-    const int rho = lane & 31, my_k = rho / kSlot, my_r = rho % kSlot;
-    const int jb0 = lo_s / kPdfs, jb1 = (hi_s + kPdfs - 1) / kPdfs;
-    auto row_of = [&](int jb) -> int {                 // this lane's packed row in virtual block jb (two dependent loads)
-      const int idx = min(jb, jb1 - 1) * kPdfs + my_k;
-      return idx < hi_s ? p.col_row0[l0 + base + idx] + my_r : p.num_rows;
-    };
-    auto src_of = [&](int row) { return wsrc + (size_t)(row >> 5) * kUnits + (row & 31) + 32 * h; };
-    op8 a[kSteps][kPieces];
-    int row_cur = row_of(jb0), row_next = row_of(jb0 + 1);
-    float gcv = gsrc[row_cur];
-    {
-      const uint4 *src = src_of(row_cur);
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++)
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-    }
-    const int col0 = base + jb0 * kPdfs;               // score column of the first staged column
-    for (int jb = jb0; jb < jb1; jb++) {
-      const int row_n2 = row_of(jb + 2);               // in flight during this block
-      f32x16 init, acc[2];
-#pragma unroll
-      for (int rr = 0; rr < 16; rr++) init[rr] = __shfl(gcv, acc_row(rr, h));
-      const uint4 *src = src_of(row_next);
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++) {
-#pragma unroll
-        for (int t6 = 0; t6 < kProd; t6++)
-#pragma unroll
-          for (int n = 0; n < 2; n++) {
-            const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
-            if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-            else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-          }
-        if (s_ == 0) gcv = gsrc[row_next];
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      row_next = row_n2;
-      // per-pdf log-sum-exp.  Accumulator register r of half-wave h is row (r & 3) + 8 (r >> 2) + 4 h of the block.
-      auto group_max = [&](const f32x16 &v, int r0, int cnt) {
-        float m = v[r0];
-#pragma unroll
-        for (int rr = 1; rr < cnt; rr++) m = fmaxf(m, v[r0 + rr]);
-        return m;
-      };
-      auto group_expsum = [&](const f32x16 &v, int r0, int cnt, float m) {
-        float e[8];
-#pragma unroll
-        for (int rr = 0; rr < cnt; rr++) e[rr] = __builtin_amdgcn_exp2f((v[r0 + rr] - m) * l2e_s);
-#pragma unroll
-        for (int w = 1; w < cnt; w <<= 1)
-#pragma unroll
-          for (int rr = 0; rr + w < cnt; rr += 2 * w) e[rr] += e[rr + w];
-        return e[0];
-      };
-      const int colbase = ((jb - jb0) * kPdfs) & 31;   // first staging column of this block
-#pragma unroll
-      for (int n = 0; n < 2; n++) {
-        float *srow = stage + (32 * n + col) * 33 + colbase;
-        if constexpr (kSlot == 16) {                   // pdf k: rows 16k..16k+15 = registers [8k, 8k+8) of both halves
-          float ll[2];
-#pragma unroll
-          for (int k2 = 0; k2 < 2; k2++) {
-            float m = group_max(acc[n], 8 * k2, 8);
-            m = fmaxf(m, swap32(m, h));
-            float sv = group_expsum(acc[n], 8 * k2, 8, m);
-            sv += swap32(sv, h);
-            ll[k2] = finish(m * inv_s, sv);
-          }
-          srow[h] = h ? ll[1] : ll[0];
-        } else if constexpr (kSlot == 8) {             // pdf k: rows 8k..8k+7 = registers [4k, 4k+4) of both halves
-          float ll[4];
-#pragma unroll
-          for (int k2 = 0; k2 < 4; k2++) {
-            float m = group_max(acc[n], 4 * k2, 4);
-            m = fmaxf(m, swap32(m, h));
-            float sv = group_expsum(acc[n], 4 * k2, 4, m);
-            sv += swap32(sv, h);
-            ll[k2] = finish(m * inv_s, sv);
-          }
-          srow[h] = h ? ll[1] : ll[0];
-          srow[2 + h] = h ? ll[3] : ll[2];
-        } else {                                       // slot 4: pdf 2i + h: rows 8i + 4h .. +3 = registers [4i, 4i+4)
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            const float m = group_max(acc[n], 4 * i, 4);
-            const float sv = group_expsum(acc[n], 4 * i, 4, m);
-            srow[2 * i + h] = finish(m * inv_s, sv);
-          }
-        }
-      }
-      const int done = (jb - jb0 + 1) * kPdfs;         // staged columns since col0 (whole blocks)
-      if ((done & 31) == 0 || jb == jb1 - 1) {
-        const int first = (done - 1) & ~31;            // first staged column of the open window
-        const int valid = min(done, hi_s - jb0 * kPdfs) - first;   // columns of pdfs inside the class's range
-        flush_cols(col0 + first, valid);
-      }
-    }
-  };
-  run_small(std::integral_constant<int, 16>{}, base_c[2], lo_c[2], hi_c[2]);
-  run_small(std::integral_constant<int, 8>{}, base_c[3], lo_c[3], hi_c[3]);
-  run_small(std::integral_constant<int, 4>{}, base_c[4], lo_c[4], hi_c[4]);
-#ifdef GMM_BAND_STAMPS
-  if (p.trace && lane == 0 && kHalf) {
-    const unsigned long long st3 = wall_clock64();
-    atomicAdd(&p.trace[0], st1 - st0); atomicAdd(&p.trace[1], st2 - st1); atomicAdd(&p.trace[2], st3 - st2);
-    atomicAdd(&p.trace[3], 1ull); atomicAdd(&p.trace[4], (unsigned long long)(hi - lo));
-  }
-#endif
-}
-
-// Band-mode launch of the f32 kernel's tile walk: whatever slot classes gmm_band_kernel does not cover (single-Gaussian
-// pdfs — bit-exact —, the 16/8/4-row classes, pdfs of more than 32 Gaussians; everything under MFA_GMM_BF16=0).
+// Band-mode launch of the f32 kernel's tile walk over the (utterance, 64-frame sub-tile) items of a lazy-scoring window
+// (gmm_band.hip): the classes gmm_band_kernel left (b_skip0: single-Gaussian pdfs, bit-exact), or every class under
+// MFA_GMM_BF16=0.  It stays in this unit, next to score_tile and gmm_kernel: compiled without gmm_kernel beside it, the
+// inlined tile walk gets another register assignment.
 template <int M8>
 __global__ __launch_bounds__(256, 2) void gmm_band_f32_kernel(GmmParams p) {
   __shared__ float stage_all[4][64 * 33];
@@ -2148,14 +1299,6 @@ int slot_of(int g) { return g <= 1 ? 1 : g <= 4 ? 4 : g <= 8 ? 8 : g <= 16 ? 16 
 int class_index(int slot) { return slot == 32 ? 0 : slot == 16 ? 1 : slot == 8 ? 2 : slot == 4 ? 3 : 4; }
 
 }  // namespace
-
-// Block counts of multi-block pdfs ride in the five low bits of their columns' row words when every pdf has at most 32 blocks
-// (MFA_GMM_PACK_NB=0: never — the lookup path, for tests)
-static int col_nb_packed_for(const mfa_ctx *c) {
-  const char *e = getenv("MFA_GMM_PACK_NB");
-  if (e && e[0] == '0') return 0;
-  return c->max_nblk <= 32 ? 1 : 0;
-}
 
 extern "C" {
 
@@ -2311,13 +1454,13 @@ MFA_API int mfa_load_gmm(mfa_ctx *c, int32_t dim, int32_t num_pdfs, const int32_
   for (int p = 0; p < num_pdfs; p++) c->h_ngauss[p] = h_pdf_offsets[p + 1] - h_pdf_offsets[p];
   if (c->d_w_stats) { (void)hipFree(c->d_w_stats); c->d_w_stats = nullptr; }   // belonged to the previous model's layout
   if (c->d_nrows) { (void)hipFree(c->d_nrows); c->d_nrows = nullptr; }
-  c->all_single_block = true;   // (name kept: "all pdfs are 32-row pdfs", single- or multi-block)
+  c->all_pdfs_32row = true;
   c->has_multi_block = false;
   c->max_nblk = 1;
   for (int q = 0; q < 5; q++) c->has_slot_class[q] = false;
   c->has_single32 = false;
   for (int p = 0; p < num_pdfs; p++) {
-    if (slot[p] != 32) c->all_single_block = false;
+    if (slot[p] != 32) c->all_pdfs_32row = false;
     if (nblk[p] > 1) c->has_multi_block = true;
     c->max_nblk = std::max(c->max_nblk, nblk[p]);
     if (slot[p] == 32 && nblk[p] == 1) c->has_single32 = true;
@@ -2369,244 +1512,6 @@ MFA_API int mfa_gmm_sort_pdf_list_keyed(mfa_ctx *c, int32_t *h_pdfs, int32_t *h_
   return 0;
 }
 
-MFA_API int mfa_fst_first_frames(int32_t n_states, const int32_t *h_arc_off, const int32_t *h_arc_next, int32_t start,
-                                 int32_t *h_depth) {
-  if (n_states <= 0 || start < 0 || start >= n_states) return -1;
-  for (int s = 0; s < n_states; s++) h_depth[s] = INT32_MAX;
-  std::vector<int32_t> queue;
-  queue.reserve(n_states);
-  queue.push_back(start);
-  h_depth[start] = 0;
-  for (size_t q = 0; q < queue.size(); q++) {  // breadth-first: unit arc lengths
-    const int s = queue[q];
-    for (int a = h_arc_off[s]; a < h_arc_off[s + 1]; a++) {
-      const int d = h_arc_next[a];
-      if (d < 0 || d >= n_states) return -1;
-      if (h_depth[d] == INT32_MAX) { h_depth[d] = h_depth[s] + 1; queue.push_back(d); }
-    }
-  }
-  return 0;
-}
-
-// The same with epsilon input arcs (h_arc_pdf[a] < 0) counting for nothing: depth = fewest EMITTING arcs from the start state —
-// the first frame a token can sit on the state, FasterDecoder's ProcessNonemitting moving tokens along epsilon arcs within a
-// frame.  0-1 breadth-first search.
-static int fst_first_frames_eps(int32_t n_states, const int32_t *h_arc_off, const int32_t *h_arc_next, const int32_t *h_arc_pdf,
-                                int32_t start, int32_t *h_depth) {
-  if (n_states <= 0 || start < 0 || start >= n_states) return -1;
-  for (int s = 0; s < n_states; s++) h_depth[s] = INT32_MAX;
-  std::vector<int32_t> cur, nxt;
-  cur.push_back(start);
-  h_depth[start] = 0;
-  int32_t level = 0;
-  while (!cur.empty()) {
-    for (size_t q = 0; q < cur.size(); q++) {            // (cur grows while epsilon arcs are followed)
-      const int s = cur[q];
-      if (h_depth[s] != level) continue;                 // reached more cheaply in the meantime
-      for (int a = h_arc_off[s]; a < h_arc_off[s + 1]; a++) {
-        const int d = h_arc_next[a];
-        if (d < 0 || d >= n_states) return -1;
-        const int32_t nd = level + (h_arc_pdf[a] < 0 ? 0 : 1);
-        if (nd < h_depth[d]) { h_depth[d] = nd; (nd == level ? cur : nxt).push_back(d); }
-      }
-    }
-    cur.swap(nxt); nxt.clear();
-    level++;
-  }
-  return 0;
-}
-
-MFA_API int mfa_fst_last_depths(int32_t n_states, const int32_t *h_arc_off, const int32_t *h_arc_next, int32_t start,
-                                const int32_t *h_bfs_depth, int32_t *h_depth) {
-  if (n_states <= 0 || start < 0 || start >= n_states) return -1;
-  for (int a = 0; a < h_arc_off[n_states]; a++)
-    if (h_arc_next[a] < 0 || h_arc_next[a] >= n_states) return -1;
-  // h_depth[s] = the smallest BFS depth among the states reachable from s (s included).  Computed over the graph's
-  // condensation: strongly connected components (self-loops, the small cycles of an ergodic silence topology) come out of
-  // Tarjan's algorithm (iterative) in reverse topological order, i.e. sinks first — exactly the order this needs.
-  std::vector<int32_t> index(n_states, -1), low(n_states, 0), comp(n_states, -1), stack, next_arc(n_states, 0);
-  std::vector<char> on_stack(n_states, 0);
-  std::vector<int32_t> call;   // DFS stack of states
-  int32_t counter = 0, n_comp = 0;
-  call.push_back(start);
-  index[start] = low[start] = counter++;
-  stack.push_back(start); on_stack[start] = 1;
-  next_arc[start] = h_arc_off[start];
-  std::vector<int32_t> comp_first;   // members of component k: comp_members[comp_first[k] .. comp_first[k+1])
-  std::vector<int32_t> comp_members;
-  while (!call.empty()) {
-    const int s = call.back();
-    if (next_arc[s] < h_arc_off[s + 1]) {
-      const int d = h_arc_next[next_arc[s]++];
-      if (index[d] < 0) {
-        index[d] = low[d] = counter++;
-        stack.push_back(d); on_stack[d] = 1;
-        next_arc[d] = h_arc_off[d];
-        call.push_back(d);
-      } else if (on_stack[d]) {
-        low[s] = std::min(low[s], index[d]);
-      }
-    } else {
-      call.pop_back();
-      if (!call.empty()) low[call.back()] = std::min(low[call.back()], low[s]);
-      if (low[s] == index[s]) {
-        comp_first.push_back((int32_t)comp_members.size());
-        for (;;) {
-          const int v = stack.back(); stack.pop_back(); on_stack[v] = 0;
-          comp[v] = n_comp;
-          comp_members.push_back(v);
-          if (v == s) break;
-        }
-        n_comp++;
-      }
-    }
-  }
-  comp_first.push_back((int32_t)comp_members.size());
-  // an arc s -> d between different components has comp[d] < comp[s]: ascending component order visits successors first
-  std::vector<int32_t> cmin(n_comp, INT32_MAX);
-  bool cyclic = false;
-  for (int k = 0; k < n_comp; k++) {
-    if (comp_first[k + 1] - comp_first[k] > 1) cyclic = true;
-    int32_t m = INT32_MAX;
-    for (int i = comp_first[k]; i < comp_first[k + 1]; i++) {
-      const int s = comp_members[i];
-      m = std::min(m, h_bfs_depth[s]);
-      for (int a = h_arc_off[s]; a < h_arc_off[s + 1]; a++) {
-        const int cd = comp[h_arc_next[a]];
-        if (cd != k) m = std::min(m, cmin[cd]);
-      }
-    }
-    cmin[k] = m;
-  }
-  for (int s = 0; s < n_states; s++) h_depth[s] = comp[s] >= 0 ? cmin[comp[s]] : 0;
-  return cyclic ? 1 : 0;
-}
-
-// Score columns of one utterance for mfa_align_features_batch / mfa_gmm_score_batch — see include/mfa_hip.h.
-MFA_API int mfa_build_score_plan(int32_t n_states, const int32_t *h_arc_off, const int32_t *h_arc_next,
-                                 const int32_t *h_arc_pdf, int32_t start, int32_t num_pdfs, const int32_t *h_pdf_class,
-                                 int32_t cluster_span, int32_t *h_state_depth, int32_t *h_arc_col, int32_t *h_col_pdf,
-                                 int32_t *h_col_first, int32_t *h_col_last, int32_t *h_class_counts, int32_t *h_n_cols) {
-  return mfa_build_score_plan_grouped(n_states, h_arc_off, h_arc_next, h_arc_pdf, start, num_pdfs, h_pdf_class, cluster_span,
-                                      1, h_state_depth, h_arc_col, h_col_pdf, h_col_first, h_col_last, h_class_counts, nullptr,
-                                      h_n_cols);
-}
-
-MFA_API int mfa_build_score_plans_batch(int32_t n_utt, const int64_t *h_state_off, const int64_t *h_arc_base,
-                                        const int32_t *h_arc_off, const int32_t *h_arc_next, const int32_t *h_arc_pdf,
-                                        const int32_t *h_start, int32_t num_pdfs, const int32_t *h_pdf_class,
-                                        int32_t cluster_span, int32_t groups, int32_t n_threads, int32_t *h_state_depth,
-                                        int32_t *h_arc_col, int32_t *h_col_pdf, int32_t *h_col_first, int32_t *h_col_last,
-                                        int32_t *h_class_counts, int32_t *h_group_counts, int32_t *h_n_cols,
-                                        int32_t *h_bad_utt) {
-  if (n_utt < 0) return -1;
-  std::atomic<int> next(0), first_bad(INT32_MAX);
-  std::vector<int> codes((size_t)std::max(n_utt, 1), 0);
-  auto work = [&]() {
-    for (;;) {
-      const int u = next.fetch_add(1);
-      if (u >= n_utt) break;
-      const int64_t s0 = h_state_off[u], a0 = h_arc_base[u];
-      const int32_t ns = (int32_t)(h_state_off[u + 1] - s0);
-      const int rc = mfa_build_score_plan_grouped(ns, h_arc_off + s0 + u, h_arc_next + a0, h_arc_pdf + a0, h_start[u], num_pdfs,
-                                                  h_pdf_class, cluster_span, groups, h_state_depth + 2 * s0, h_arc_col + a0,
-                                                  h_col_pdf + a0, h_col_first + a0, h_col_last + a0, h_class_counts + 6 * (size_t)u,
-                                                  groups > 1 ? h_group_counts + (size_t)groups * u : nullptr, h_n_cols + u);
-      codes[u] = rc;
-      if (rc != 0) { int cur = first_bad.load(); while (u < cur && !first_bad.compare_exchange_weak(cur, u)) {} }
-    }
-  };
-  const int nt = std::max(1, std::min(n_threads, n_utt));
-  if (nt == 1) work();
-  else {
-    std::vector<std::thread> ts;
-    for (int t = 0; t < nt; t++) ts.emplace_back(work);
-    for (auto &t : ts) t.join();
-  }
-  const int bad = first_bad.load();
-  if (bad != INT32_MAX) { if (h_bad_utt) *h_bad_utt = bad; return codes[bad]; }
-  return 0;
-}
-
-MFA_API int mfa_build_score_plan_grouped(int32_t n_states, const int32_t *h_arc_off, const int32_t *h_arc_next,
-                                         const int32_t *h_arc_pdf, int32_t start, int32_t num_pdfs, const int32_t *h_pdf_class,
-                                         int32_t cluster_span, int32_t groups, int32_t *h_state_depth, int32_t *h_arc_col,
-                                         int32_t *h_col_pdf, int32_t *h_col_first, int32_t *h_col_last, int32_t *h_class_counts,
-                                         int32_t *h_group_counts, int32_t *h_n_cols) {
-  if (groups < 1 || groups > MFA_PLAN_MAX_GROUPS || (groups > 1 && !h_group_counts)) return -3;
-  if (n_states <= 0 || start < 0 || start >= n_states) return -1;
-  const int n_arcs = h_arc_off[n_states];
-  std::vector<int32_t> bfs(n_states), low(n_states);
-  bool has_eps = false;
-  for (int a = 0; a < n_arcs; a++) if (h_arc_pdf[a] < 0) { has_eps = true; break; }
-  // (an arc with pdf -1 is an epsilon input arc: no score column, no frame consumed)
-  if ((has_eps ? fst_first_frames_eps(n_states, h_arc_off, h_arc_next, h_arc_pdf, start, bfs.data())
-               : mfa_fst_first_frames(n_states, h_arc_off, h_arc_next, start, bfs.data())) != 0) return -1;
-  if (mfa_fst_last_depths(n_states, h_arc_off, h_arc_next, start, bfs.data(), low.data()) < 0) return -1;
-  for (int s = 0; s < n_states; s++) {
-    h_state_depth[2 * s] = bfs[s] == INT32_MAX ? 0 : bfs[s];
-    h_state_depth[2 * s + 1] = bfs[s] == INT32_MAX ? 0 : low[s];
-  }
-  // arcs by (pdf, BFS depth of the source state); a column = a run of one pdf's arcs whose depths stay within
-  // cluster_span of the run's first (cluster_span <= 0: one column per pdf)
-  std::vector<int32_t> src(n_arcs), order(n_arcs);
-  for (int s = 0; s < n_states; s++)
-    for (int a = h_arc_off[s]; a < h_arc_off[s + 1]; a++) src[a] = s;
-  order.clear();
-  for (int a = 0; a < n_arcs; a++) {
-    if (h_arc_pdf[a] == -1) continue;                    // epsilon input arc
-    if (h_arc_pdf[a] < 0 || h_arc_pdf[a] >= num_pdfs) return -2;
-    if (h_pdf_class[h_arc_pdf[a]] < 0 || h_pdf_class[h_arc_pdf[a]] > 5) return -2;
-    order.push_back(a);
-  }
-  const int n_emit = (int)order.size();
-  std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
-    if (h_arc_pdf[x] != h_arc_pdf[y]) return h_arc_pdf[x] < h_arc_pdf[y];
-    return bfs[src[x]] < bfs[src[y]];
-  });
-  struct Col { int32_t pdf, first, last, cls; };
-  std::vector<Col> cols;
-  std::vector<int32_t> col_of_arc(n_arcs, -1);
-  for (int i = 0; i < n_emit; i++) {
-    const int a = order[i], pdf = h_arc_pdf[a], d = bfs[src[a]];
-    const bool fresh = cols.empty() || cols.back().pdf != pdf ||
-                       (cluster_span > 0 && ((int64_t)d - cols.back().first > cluster_span));
-    if (fresh) cols.push_back({pdf, d, d, h_pdf_class[pdf]});
-    cols.back().last = std::max(cols.back().last, d);
-    col_of_arc[a] = (int32_t)cols.size() - 1;
-  }
-  // kernel order: slot class, (class 0 only: pdf id mod `groups` — the XCD whose L2 keeps that part of the model), then
-  // ascending first depth (ties: pdf id, then depth — the creation order)
-  const int n_cols = (int)cols.size();
-  std::vector<int32_t> perm(n_cols), rank(n_cols);
-  for (int i = 0; i < n_cols; i++) perm[i] = i;
-  auto group_of = [&](const Col &c) { return c.cls == 0 ? c.pdf % groups : 0; };
-  std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) {
-    if (cols[x].cls != cols[y].cls) return cols[x].cls < cols[y].cls;
-    const int gx = group_of(cols[x]), gy = group_of(cols[y]);
-    if (gx != gy) return gx < gy;
-    return cols[x].first < cols[y].first;
-  });
-  for (int k = 0; k < 6; k++) h_class_counts[k] = 0;
-  if (h_group_counts) for (int k = 0; k < groups; k++) h_group_counts[k] = 0;
-  int32_t run_cls = -1, run_grp = -1, run_max = 0;
-  for (int i = 0; i < n_cols; i++) {
-    const Col &cl = cols[perm[i]];
-    const int grp = group_of(cl);
-    rank[perm[i]] = i;
-    h_col_pdf[i] = cl.pdf;
-    h_col_first[i] = cl.first;
-    if (cl.cls != run_cls || grp != run_grp) { run_cls = cl.cls; run_grp = grp; run_max = cl.last; }
-    run_max = std::max(run_max, cl.last);
-    h_col_last[i] = run_max;            // running max inside the class (class 0: inside the group): non-decreasing along it
-    h_class_counts[cl.cls]++;
-    if (h_group_counts && cl.cls == 0) h_group_counts[grp]++;
-  }
-  for (int a = 0; a < n_arcs; a++) h_arc_col[a] = col_of_arc[a] >= 0 ? rank[col_of_arc[a]] : 0;
-  *h_n_cols = n_cols;
-  return 0;
-}
-
 MFA_API int mfa_debug_gmm_trace(mfa_ctx *c, void *d_trace) {
   c->gmm_trace = d_trace;
   return 0;
@@ -2628,11 +1533,9 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *c, const float *d_feats, const int64_t 
   p.min_log_diff = logf(1.1920928955078125e-07f);
   p.first_frame = d_pdf_first_frame;
   p.trace = (unsigned long long *)c->gmm_trace;
-  { const char *fb = getenv("MFA_GMM_FF_BIAS"); p.ff_bias = fb ? atoi(fb) : 0; }
   const char *naive = getenv("MFA_GMM_NAIVE");
-  const int m8 = c->kpad / 8;
   KernelTimer kt(c, MFA_K_GMM);
-  if ((naive && naive[0] == '1') || m8 > 12) {
+  if ((naive && naive[0] == '1') || c->kpad > 96) {
     // worst-case P is not known on the host side of this call: cover max_frames * num_pdfs threads per utterance
     int64_t per_utt = (int64_t)max_frames * c->num_pdfs;
     dim3 grid((unsigned)((per_utt + 255) / 256), n_utt);
@@ -2661,15 +1564,16 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *c, const float *d_feats, const int64_t 
     const int64_t items = (int64_t)n_utt * p.tiles;
     const int64_t wgs = std::min<int64_t>((int64_t)c->num_cus * 2, items);
     dim3 grid((unsigned)std::max<int64_t>(wgs, 1));
-    const char *bf = getenv("MFA_GMM_BF16");
+    const GmmSplitPasses passes = gmm_split_passes(c);
+    // one launch of a kernel template whose first parameter is the model's 16-k step count
+    auto launch = [&](auto kernel_of) { gmm_with_steps(c->kpad, [&](auto steps) { hipLaunchKernelGGL(kernel_of(steps), grid, dim3(256), 0, c->stream, p); }); };
     p.wb = (const uint4 *)c->d_wb;
     p.wh = nullptr; p.gch = nullptr; p.fscale = nullptr; p.acc_scale_inv = 1.0f; p.redo = nullptr; p.redo_mode = 0; p.redo_count = nullptr; p.skip_cc0 = 0;
     p.skip_single = 0;
-    if (!(bf && bf[0] == '0') && c->d_wb) {   // default on; MFA_GMM_BF16=0 keeps every class on the f32 kernel
+    if (passes.bf16) {   // default on; MFA_GMM_BF16=0 keeps every class on the f32 kernel
       // class 0 on the bf16×3 kernel, then the f32 kernel for whatever other slot classes the lists hold (second set of
       // queue counters; an item with nothing left returns at once)
-      const char *hf = getenv("MFA_GMM_F16");
-      const bool f16_ok = !(hf && hf[0] == '0') && c->d_wh;
+      const bool f16_ok = passes.f16;
       const bool use_f16 = f16_ok && c->has_single32;   // single-block 32-row class on the lean f16 kernel
       p.skip_cc0 = 0;
       if (f16_ok) {
@@ -2686,61 +1590,48 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *c, const float *d_feats, const int64_t 
         p.redo = c->d_gmm_redo; p.redo_mode = 0; p.redo_count = c->d_gmm_queue + 51;
       }
       if (use_f16) {
-        if (m8 == 10) hipLaunchKernelGGL((gmm_split_single_kernel<5, 2>), grid, dim3(256), 0, c->stream, p);
-        else hipLaunchKernelGGL((gmm_split_single_kernel<6, 2>), grid, dim3(256), 0, c->stream, p);
+        launch([](auto steps) { return gmm_split_single_kernel<steps(), 2>; });
         p.redo_mode = 2;
         p.queue = c->d_gmm_queue + 34;
-        if (m8 == 10) hipLaunchKernelGGL((gmm_split_single_kernel<5, 3>), grid, dim3(256), 0, c->stream, p);
-        else hipLaunchKernelGGL((gmm_split_single_kernel<6, 3>), grid, dim3(256), 0, c->stream, p);
+        launch([](auto steps) { return gmm_split_single_kernel<steps(), 3>; });
         p.redo_mode = 0;
         p.skip_cc0 = 1;
         p.queue = c->d_gmm_queue + 64 + 6 * 16;
       }
       if (c->has_multi_block) {                           // pdfs of more than 32 Gaussians (and, without f16, the whole 32-row class)
         if (f16_ok) {                                     // f16×2 pass, then the bf16×3 pass over the tiles it declined
-          if (m8 == 10) hipLaunchKernelGGL((gmm_bf16_kernel<5, 2>), grid, dim3(256), 0, c->stream, p);
-          else hipLaunchKernelGGL((gmm_bf16_kernel<6, 2>), grid, dim3(256), 0, c->stream, p);
+          launch([](auto steps) { return gmm_bf16_kernel<steps(), 2>; });
           p.redo_mode = 2;
           p.queue = c->d_gmm_queue + 64 + 7 * 16;
         }
-        if (m8 == 10) hipLaunchKernelGGL((gmm_bf16_kernel<5, 3>), grid, dim3(256), 0, c->stream, p);
-        else hipLaunchKernelGGL((gmm_bf16_kernel<6, 3>), grid, dim3(256), 0, c->stream, p);
+        launch([](auto steps) { return gmm_bf16_kernel<steps(), 3>; });
         p.redo_mode = 0;
       } else if (!use_f16 && c->has_single32) {
-        if (m8 == 10) hipLaunchKernelGGL((gmm_split_single_kernel<5, 3>), grid, dim3(256), 0, c->stream, p);
-        else hipLaunchKernelGGL((gmm_split_single_kernel<6, 3>), grid, dim3(256), 0, c->stream, p);
+        launch([](auto steps) { return gmm_split_single_kernel<steps(), 3>; });
       }
       p.skip_single = 1;
       {
         // the 16- / 8- / 4-row classes on the same pipe (f16×2 pass, then the bf16×3 pass over declined tiles), each launch
         // with its own queue counters; classes the model does not have are not launched
         int qbase = 64;
-        auto small = [&](int slot_rows, int cls_idx) {
+        auto small = [&](auto slot_rows, int cls_idx) {
           if (!c->has_slot_class[cls_idx]) return;
           for (int pass = f16_ok ? 0 : 1; pass < 2; pass++) {
             p.redo_mode = f16_ok ? (pass == 0 ? 0 : 2) : 0;
             p.queue = c->d_gmm_queue + qbase; qbase += 16;
-#define MFA_LAUNCH_SMALL(STEPS, PIECES)                                                                                   \
-            do {                                                                                                        \
-              if (slot_rows == 16) hipLaunchKernelGGL((gmm_split_small_kernel<STEPS, PIECES, 16>), grid, dim3(256), 0, c->stream, p); \
-              else if (slot_rows == 8) hipLaunchKernelGGL((gmm_split_small_kernel<STEPS, PIECES, 8>), grid, dim3(256), 0, c->stream, p); \
-              else hipLaunchKernelGGL((gmm_split_small_kernel<STEPS, PIECES, 4>), grid, dim3(256), 0, c->stream, p); \
-            } while (0)
-            if (pass == 0) { if (m8 == 10) MFA_LAUNCH_SMALL(5, 2); else MFA_LAUNCH_SMALL(6, 2); }
-            else { if (m8 == 10) MFA_LAUNCH_SMALL(5, 3); else MFA_LAUNCH_SMALL(6, 3); }
-#undef MFA_LAUNCH_SMALL
+            if (pass == 0) launch([=](auto steps) { return gmm_split_small_kernel<steps(), 2, slot_rows()>; });
+            else launch([=](auto steps) { return gmm_split_small_kernel<steps(), 3, slot_rows()>; });
           }
         };
-        small(16, 1); small(8, 2); small(4, 3);
+        small(std::integral_constant<int, 16>{}, 1); small(std::integral_constant<int, 8>{}, 2); small(std::integral_constant<int, 4>{}, 3);
         p.skip_single = 2;
       }
       p.queue = c->d_gmm_queue + 17;
     }
     const bool only_split_classes = !c->has_slot_class[4] && p.skip_single == 2;   // no single-Gaussian pdfs left over
-    if (p.skip_single && (c->all_single_block || only_split_classes)) {
-      // every pdf of the model is a single 32-row block: nothing is left for the f32 kernel
-    } else if (m8 <= 10) hipLaunchKernelGGL((gmm_kernel<10, 2, 2, 4>), grid, dim3(256), 0, c->stream, p);
-    else hipLaunchKernelGGL((gmm_kernel<12, 2, 2, 4>), grid, dim3(256), 0, c->stream, p);
+    if (p.skip_single && (c->all_pdfs_32row || only_split_classes)) {
+      // every pdf of the model went to the split-operand kernels: nothing is left for the f32 kernel
+    } else launch([](auto steps) { return gmm_kernel<2 * steps(), 2, 2, 4>; });
   }
   MFA_HIP_CHECK(c, hipGetLastError());
   MFA_DEBUG_POINT(c, "dense scoring of %d utterances", n_utt);
@@ -2749,138 +1640,7 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *c, const float *d_feats, const int64_t 
 
 }  // extern "C"
 
-int mfa_gmm_lazy_supported(mfa_ctx *c) { return c->gmm_ready && (c->kpad == 80 || c->kpad == 96); }
-
-// Pre-split f16 operands of the whole batch (see gmm_presplit_kernel); mfa_gmm_score_window then hands them to the band kernel.
-int mfa_gmm_presplit(mfa_ctx *c, const MfaLazyScoring *lazy, const int64_t *d_frame_off, int n_utt, int64_t total_frames) {
-  c->xsplit_ready = false;
-  {   // first model row of every score column of the batch (the band kernels read nothing else to find a block)
-    const int64_t cols_cap = (int64_t)n_utt * std::max(1, lazy->plan.max_cols);
-    if (c->col_row0_cap < cols_cap) {
-      MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-      if (c->d_col_row0) (void)hipFree(c->d_col_row0);
-      c->d_col_row0 = nullptr; c->col_row0_cap = 0;
-      MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_col_row0, (size_t)cols_cap * sizeof(int32_t)));
-      c->col_row0_cap = cols_cap;
-    }
-    GmmParams q;
-    memset(&q, 0, sizeof(q));
-    q.row0 = c->d_row0; q.pdf_list = lazy->plan.d_pdf_list; q.pdf_off = lazy->plan.d_pdf_off; q.n_utt = n_utt;
-    q.nblk = c->d_nblk; q.col_nb_packed = col_nb_packed_for(c);
-    hipLaunchKernelGGL(gmm_col_rows_kernel, dim3(n_utt), dim3(256), 0, c->stream, q, c->d_col_row0);
-    MFA_HIP_CHECK(c, hipGetLastError());
-  }
-  const char *bf = getenv("MFA_GMM_BF16");
-  const char *hf = getenv("MFA_GMM_F16");
-  const char *ps = getenv("MFA_GMM_PRESPLIT");
-  if ((bf && bf[0] == '0') || (hf && hf[0] == '0') || (ps && ps[0] == '0') || !c->d_wh || !c->d_wb) return 0;   // no f16 pass: nothing to prepare
-  const int ksteps = c->kpad / 16;
-  if (ksteps != 5 && ksteps != 6) return 0;
-  const int64_t tiles = (total_frames >> 6) + n_utt + 1;
-  if (c->xsplit_tiles < tiles) {
-    MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    if (c->d_xsplit) (void)hipFree(c->d_xsplit);
-    if (c->d_xsplit_bad) (void)hipFree(c->d_xsplit_bad);
-    c->d_xsplit = nullptr; c->d_xsplit_bad = nullptr; c->xsplit_tiles = 0;
-    MFA_HIP_CHECK(c, hipMalloc(&c->d_xsplit, (size_t)tiles * 2 * 6 * 2 * 64 * 16));
-    MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_xsplit_bad, (size_t)tiles * sizeof(int)));
-    c->xsplit_tiles = tiles;
-  }
-  GmmParams p;
-  memset(&p, 0, sizeof(p));
-  p.dim = c->dim; p.kpad = c->kpad; p.feats = lazy->d_feats; p.frame_off = d_frame_off; p.n_utt = n_utt; p.fscale = c->d_fscale;
-  const int tiles_per_utt = (lazy->max_frames + 63) / 64;
-  const int64_t waves = (int64_t)n_utt * tiles_per_utt;
-  const dim3 grid((unsigned)((waves + 3) / 4));
-  KernelTimer kt(c, MFA_K_GMM);
-  if (ksteps == 5) hipLaunchKernelGGL((gmm_presplit_kernel<5>), grid, dim3(256), 0, c->stream, p, (uint4 *)c->d_xsplit, c->d_xsplit_bad, tiles_per_utt);
-  else hipLaunchKernelGGL((gmm_presplit_kernel<6>), grid, dim3(256), 0, c->stream, p, (uint4 *)c->d_xsplit, c->d_xsplit_bad, tiles_per_utt);
-  MFA_HIP_CHECK(c, hipGetLastError());
-  c->xsplit_ready = true;
-  return 0;
-}
-
-const int32_t *mfa_band_ranges(mfa_ctx *c) { return c->d_band_ranges; }
-
-int mfa_gmm_score_window(mfa_ctx *c, const MfaLazyScoring *lazy, const MfaWindowScore *ws, const int64_t *d_frame_off,
-                         int n_utt, const int64_t *d_ll_off, float *d_loglikes) {
-  if (!c->gmm_ready) return c->fail("mfa_load_gmm has not been called");
-  if (!mfa_gmm_lazy_supported(c)) return c->fail("lazy scoring needs a model of at most 48 dimensions");
-  if (ws->window <= 0 || ws->window % 64 != 0) return c->fail("scoring window must be a multiple of 64 frames");
-  GmmParams p;
-  memset(&p, 0, sizeof(p));
-  p.dim = c->dim; p.kpad = c->kpad; p.num_rows = c->num_rows;
-  p.w = c->d_w; p.gc = c->d_gc; p.row0 = c->d_row0; p.nblk = c->d_nblk; p.slot = c->d_slot;
-  p.feats = lazy->d_feats; p.frame_off = d_frame_off; p.pdf_list = lazy->plan.d_pdf_list; p.pdf_off = lazy->plan.d_pdf_off;
-  p.class_counts = lazy->plan.d_class_counts; p.ll_off = d_ll_off; p.out = d_loglikes;
-  p.min_log_diff = logf(1.1920928955078125e-07f);
-  p.first_frame = lazy->plan.d_pdf_first_frame; p.last_depth = lazy->plan.d_pdf_last_depth;
-  p.n_utt = n_utt; p.tiles = 0;
-  p.acc_scale_inv = 1.0f;
-  p.trace = (unsigned long long *)c->gmm_trace;
-  p.b_hi_slack = ws->hi_slack > 0 ? ws->hi_slack : 0;
-  p.b_mode = 1; p.b_t_begin = ws->t_begin; p.b_sub = ws->window / 64; p.b_band = ws->band;
-  p.b_utt_list = ws->utt_list; p.b_n_list = ws->n_list;
-  p.b_done = ws->done; p.b_done_stride = ws->done_stride; p.b_done_word = ws->done_word;
-  p.b_lag = ws->lag; p.b_lag_stride = ws->lag_stride; p.b_lag_word = ws->lag_word; p.b_lag_frames = ws->window;
-  const int64_t waves = (int64_t)n_utt * p.b_sub;
-  const dim3 grid((unsigned)((waves + 3) / 4));
-  p.groups = lazy->plan.groups > 1 && lazy->plan.d_group_counts ? lazy->plan.groups : 0;
-  p.group_counts = p.groups ? lazy->plan.d_group_counts : nullptr;
-  p.b_chunk = (ws->cols_per_wave > 0 && !p.groups) ? ws->cols_per_wave : 0;   // (a grouped plan already spreads the band over `groups` wavefronts)
-  p.b_nchunk = p.b_chunk > 0 ? (lazy->plan.max_cols + p.b_chunk - 1) / p.b_chunk : 1;
-  const int64_t split_waves = waves * p.b_nchunk;
-  p.b_split = p.groups > 1 ? 1 : 0;
-  const dim3 split_grid((unsigned)((split_waves + 3) / 4) * (unsigned)(p.b_split ? p.groups : 1));
-  const int m8 = c->kpad / 8;
-  const char *bf = getenv("MFA_GMM_BF16");
-  const char *hf = getenv("MFA_GMM_F16");
-  KernelTimer kt(c, MFA_K_GMM);
-  {   // the band's index ranges, once per utterance (instead of once per scoring wavefront)
-    const int64_t need = (int64_t)n_utt * kRangeSlots * 2;
-    if (c->band_ranges_cap < need) {
-      MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-      if (c->d_band_ranges) (void)hipFree(c->d_band_ranges);
-      c->d_band_ranges = nullptr; c->band_ranges_cap = 0;
-      MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_band_ranges, (size_t)need * sizeof(int32_t)));
-      c->band_ranges_cap = need;
-    }
-    p.ranges = c->d_band_ranges;
-    hipLaunchKernelGGL(gmm_band_ranges_kernel, dim3((unsigned)((n_utt + 3) / 4)), dim3(256), 0, c->stream, p);
-  }
-  const bool split_classes = c->has_single32 || c->has_multi_block || c->has_slot_class[1] || c->has_slot_class[2] || c->has_slot_class[3];
-  if (!(bf && bf[0] == '0') && c->d_wb && split_classes) {
-    const bool f16_ok = !(hf && hf[0] == '0') && c->d_wh;
-    if (c->gmm_redo_cap < split_waves) {
-      if (c->d_gmm_redo) { MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_gmm_redo); }
-      c->d_gmm_redo = nullptr; c->gmm_redo_cap = 0;
-      MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_gmm_redo, split_waves * sizeof(int)));
-      c->gmm_redo_cap = split_waves;
-    }
-    p.redo = c->d_gmm_redo;
-    p.wb = (const uint4 *)c->d_wb;
-    p.col_row0 = c->d_col_row0;
-    p.col_nb_packed = col_nb_packed_for(c);
-    if (f16_ok) {
-      p.wh = (const uint4 *)c->d_wh; p.gch = c->d_gch; p.fscale = c->d_fscale;
-      p.acc_scale_inv = 1.0f / c->gmm_acc_scale;
-      p.redo_mode = 0;
-      if (c->xsplit_ready) { p.xsplit = (const uint4 *)c->d_xsplit; p.xsplit_bad = c->d_xsplit_bad; }
-      if (m8 == 10) hipLaunchKernelGGL((gmm_band_kernel<5, 2>), split_grid, dim3(256), 0, c->stream, p);
-      else hipLaunchKernelGGL((gmm_band_kernel<6, 2>), split_grid, dim3(256), 0, c->stream, p);
-      p.redo_mode = 2;   // the sub-tiles the f16 pass flagged
-    }
-    if (m8 == 10) hipLaunchKernelGGL((gmm_band_kernel<5, 3>), split_grid, dim3(256), 0, c->stream, p);
-    else hipLaunchKernelGGL((gmm_band_kernel<6, 3>), split_grid, dim3(256), 0, c->stream, p);
-    p.redo_mode = 0;
-    p.b_skip0 = 1;
-  }
-  p.b_split = 0;   // (the f32 band kernel keeps one wavefront per sub-tile and walks the runs of class 0 itself)
-  const bool f32_classes = c->has_slot_class[4];   // single Gaussians stay on the f32 pipe (bit-exact); everything else was scored above
-  if (!p.b_skip0 || f32_classes) {
-    if (m8 <= 10) hipLaunchKernelGGL((gmm_band_f32_kernel<10>), grid, dim3(256), 0, c->stream, p);
-    else hipLaunchKernelGGL((gmm_band_f32_kernel<12>), grid, dim3(256), 0, c->stream, p);
-  }
-  MFA_HIP_CHECK(c, hipGetLastError());
-  return 0;
+void mfa_gmm_launch_band_f32(mfa_ctx *c, const void *params, dim3 grid) {
+  const GmmParams &p = *static_cast<const GmmParams *>(params);
+  gmm_with_steps(c->kpad, [&](auto steps) { hipLaunchKernelGGL((gmm_band_f32_kernel<2 * steps()>), grid, dim3(256), 0, c->stream, p); });
 }

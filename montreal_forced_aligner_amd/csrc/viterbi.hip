@@ -604,23 +604,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     // The frame's score row moves registers → LDS right before its first use, not here: on this target stores count in
     // vmcnt like loads and retire in order, so a wait for the row (requested during the previous frame) at the top of the
     // frame would also sit out the previous frame's back-pointer stores.  By the arc gather's wait they have long landed
-    // (5.91 → 5.80 ms per 2 048 utterances; -DVIT_STAGE_ROW_AT_TOP restores the old place).
+    // (measured against staging the row at the top of the frame: 5.91 → 5.80 ms per 2 048 utterances).
     auto stage_row = [&]() {
-#ifndef VIT_STAGE_ROW_AT_TOP
       if (row_cached) {
 #pragma unroll
         for (int r = 0; r < kPre; r++) if (lane + 64 * r < P) ll_row[lane + 64 * r] = pre[r];
         WSYNC();
       }
-#endif
     };
-#ifdef VIT_STAGE_ROW_AT_TOP
-    if (row_cached) {
-#pragma unroll
-      for (int r = 0; r < kPre; r++) if (lane + 64 * r < P) ll_row[lane + 64 * r] = pre[r];
-      WSYNC();
-    }
-#endif
 #ifdef VIT_STAMPS
     stamp_acc[10] += (unsigned long long)n;   // tokens entering the frame
     stamp_acc[11] += 1;                       // frames

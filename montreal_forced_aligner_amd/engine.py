@@ -32,6 +32,13 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _split_passes(mono: bool, gauss_per_pdf: int) -> Tuple[bool, bool]:
+    """(split-operand scoring at all, its f16x2 pass) for a model, as MFA_GMM_BF16 / MFA_GMM_F16 say right now (tests and the
+    benchmark flip them inside one process, so nothing is cached)."""
+    split = os.environ.get("MFA_GMM_BF16", "1") != "0" and not mono and gauss_per_pdf != 1
+    return split, split and os.environ.get("MFA_GMM_F16", "1") != "0"
+
+
 def _host_threads(share: float = 1.0, cap: int = 32) -> int:
     from . import hostcpu
     return hostcpu.threads(share, cap)
@@ -831,9 +838,7 @@ class Pipeline:
         return "reachable cells only (pdf j from its first possible frame on)" if self.reachability else "dense T x P"
 
     def dtype_string(self, mono: bool, gauss_per_pdf: int) -> str:
-        import os
-        split = os.environ.get("MFA_GMM_BF16", "1") != "0" and not mono and gauss_per_pdf != 1
-        f16 = split and os.environ.get("MFA_GMM_F16", "1") != "0"
+        split, f16 = _split_passes(mono, gauss_per_pdf)
         if f16:
             return "f32 scores from 2-way f16-split products (3*2^-22 per term worst case), f64 path costs"
         if split:
@@ -901,13 +906,11 @@ class Pipeline:
         priced here is work the kernels EXECUTE: scoring = the cells the lazy path wrote (``measure_scored_cells``), the
         decoder's score bytes = the cells it read (``score_cells_read`` when the oracle counted them on a sample, else the
         cells written — an upper bound)."""
-        import os
         ms = ktimes[dominant]["ms"] / max(1, steps)
         launches = ktimes[dominant]["launches"] / max(1, steps)
         lazy_measured = self.lazy and getattr(self, "scored_flops", None) is not None
         if dominant == "gmm":
-            split = os.environ.get("MFA_GMM_BF16", "1") != "0" and not mono and gauss_per_pdf != 1
-            f16 = split and os.environ.get("MFA_GMM_F16", "1") != "0"
+            split, f16 = _split_passes(mono, gauss_per_pdf)
             mult = 3.0 if f16 else (6.0 if split else 1.0)
             peak = 2500.0 if split else 157.3
             flops = self.scored_flops if lazy_measured else self.gmm_flops
