@@ -50,6 +50,8 @@ struct mfa_ctx {
   float *d_dct = nullptr;      // [nceps][nbins] with lifter folded separately
   float *d_lifter = nullptr;   // [nceps]
 
+  bool delta_uploaded = false; // feats.hip: this context has written the delta scales to its device's constant memory
+
   // GMM model (device)
   bool gmm_ready = false;
   int dim = 0, kpad = 0, num_pdfs = 0, num_rows = 0;

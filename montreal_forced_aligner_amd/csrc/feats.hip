@@ -15,6 +15,7 @@ namespace {
 constexpr int kTile = 64;       // frames per block
 constexpr int kMaxDim = 16;     // base feature dim (13 MFCC; 16 with pitch)
 constexpr int kMaxOut = 64;     // LDA rows
+constexpr size_t kMaxLdsBytes = 64 << 10;   // dynamic LDS of a launch that sets no function attribute
 
 // ---- CMVN statistics -------------------------------------------------------------------------------------------
 // One block per utterance: thread (stripe s = tid/16, dim d = tid%16) sums frames s, s+16, … in double; the 16
@@ -279,9 +280,9 @@ __global__ __launch_bounds__(256) void feats_lda_kernel(FeatParams p) {
   }
 }
 
-bool g_delta_uploaded = false;
-
+// __constant__ data lives once per device: every context uploads for its own device (mfa_ctx::delta_uploaded).
 int upload_delta_scales(mfa_ctx *c) {
+  MFA_HIP_CHECK(c, hipSetDevice(c->device));
   // Kaldi DeltaFeatures::DeltaFeatures, order 2, window 2, float arithmetic
   float s0[1] = {1.0f}, s1[5] = {0}, s2[9] = {0};
   {
@@ -335,11 +336,15 @@ MFA_API int mfa_feats_batch(mfa_ctx *c, const float *d_mfcc, const int64_t *d_fr
   if (n_utt > 65535) return c->fail("at most 65535 utterances per feature launch (got %d)", n_utt);
   if (mode != 0 && mode != 1) return c->fail("feats: bad mode %d", mode);
   if (d_cmvn && !d_utt2spk) return c->fail("feats: CMVN given without utt2spk");
-  if (!g_delta_uploaded) { if (upload_delta_scales(c)) return -1; g_delta_uploaded = true; }
+  if (!c->delta_uploaded) { if (upload_delta_scales(c)) return -1; c->delta_uploaded = true; }
   FeatParams p;
   p.dim = dim; p.mode = mode; p.ctx = splice_ctx; p.lda_rows = lda_rows; p.lda_cols = lda_cols;
   p.mfcc = d_mfcc; p.frame_off = d_frame_off; p.utt2spk = d_utt2spk; p.cmvn = d_cmvn; p.lda = d_lda; p.fmllr = d_fmllr;
   p.out = d_out;
+  // register-row kernel for MFA's standard shape (13 MFCCs spliced ±3 → 91, LDA to 40); other shapes take the generic kernel
+  constexpr int kDim = 13, kCtx = 3, kR = 40;
+  const char *generic = getenv("MFA_FEATS_GENERIC");
+  const bool register_rows = mode == 1 && dim == kDim && splice_ctx == kCtx && lda_rows == kR && !(generic && generic[0] == '1');
   size_t lds = 0;
   if (mode == 0) {
     lds = (size_t)(kTile + 8) * dim * 4;
@@ -349,13 +354,14 @@ MFA_API int mfa_feats_batch(mfa_ctx *c, const float *d_mfcc, const int64_t *d_fr
       return c->fail("feats: LDA %dx%d does not match spliced dim %d", lda_rows, lda_cols, sdim);
     lds = ((size_t)(kTile + 2 * splice_ctx) * dim + (size_t)lda_rows * lda_cols + (size_t)lda_rows * (lda_rows + 1) +
            (size_t)kTile * lda_rows) * 4;
+    // kMaxDim × kMaxOut admit shapes whose tile does not fit a launch (16 dims, ±3, 64 rows: 66 KB)
+    if (lds > kMaxLdsBytes && !register_rows)
+      return c->fail("feats: base dim %d, splice ±%d, LDA %dx%d needs %zu bytes of LDS (a launch may ask for %zu)", dim,
+                     splice_ctx, lda_rows, lda_cols, lds, kMaxLdsBytes);
   }
   dim3 grid((max_frames + kTile - 1) / kTile, n_utt);
   KernelTimer kt(c, MFA_K_FEATS);
-  // register-row kernel for MFA's standard shape (13 MFCCs spliced ±3 → 91, LDA to 40); other shapes take the generic kernel
-  constexpr int kDim = 13, kCtx = 3, kR = 40;
-  const char *generic = getenv("MFA_FEATS_GENERIC");
-  if (mode == 1 && dim == kDim && splice_ctx == kCtx && lda_rows == kR && !(generic && generic[0] == '1')) {
+  if (register_rows) {
     const int rows = kTileLda + 2 * splice_ctx;
     size_t x_floats = std::max((size_t)rows * ((kDim + 3) & ~3), (size_t)lda_rows * (lda_rows + 1));
     size_t y_floats = std::max((size_t)kTileLda * lda_rows, (size_t)lda_rows * lda_cols);

@@ -227,10 +227,25 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 4) void mfcc_kernel(MfccParams
 #pragma unroll
     for (int j = 0; j < kJ; j++) a[j] = (v2f){(float)(short)(nxt[j] & 0xFFFFu), (float)(short)(nxt[j] >> 16)};
     if (it + 1 < npass) load_frame(frame_of(it + 1), nxt);   // in flight while this pass is processed
-    // ---- DC removal (int16-valued samples: the sum is an exact integer < 2^24 in any order)
-    const bool ok_e = 2 * (16 * (kJ - 1) + i) < p.win, ok_o = 2 * (16 * (kJ - 1) + i) + 1 < p.win;   // only the last pair can lie beyond the window
-    if (!ok_e) a[kJ - 1].x = 0.0f;
-    if (!ok_o) a[kJ - 1].y = 0.0f;
+    // ---- samples at and beyond the window's end are zero.  load_frame's fast path brings 32·kJ samples whatever the window:
+    // at 385–416 (kJ 13) and 481–512 (kJ 16) samples only the last pair can lie beyond it, but a shorter window of the same
+    // instantiation (257–383, 417–479) leaves real audio in whole registers before that one.  The window weights are 0
+    // there, so the FFT never sees it — the DC sum and the raw energy would.  (Pairs below j = 8 lie inside every window
+    // the 512-point FFT admits; the branch is uniform and not taken at 400 samples.)
+    const bool ok_e = 2 * (16 * (kJ - 1) + i) < p.win, ok_o = 2 * (16 * (kJ - 1) + i) + 1 < p.win;
+    auto clear_tail = [&]() {
+      if (p.win < 32 * (kJ - 1)) {
+#pragma unroll
+        for (int j = 8; j < kJ - 1; j++) {
+          if (2 * (16 * j + i) >= p.win) a[j].x = 0.0f;
+          if (2 * (16 * j + i) + 1 >= p.win) a[j].y = 0.0f;
+        }
+      }
+      if (!ok_e) a[kJ - 1].x = 0.0f;
+      if (!ok_o) a[kJ - 1].y = 0.0f;
+    };
+    clear_tail();
+    // ---- DC removal (int16-valued samples: the sum is an exact integer ≤ 2^24 in any order)
     float sum = 0.0f;
 #pragma unroll
     for (int j = 0; j < kJ; j++) sum += a[j].x + a[j].y;
@@ -238,8 +253,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 4) void mfcc_kernel(MfccParams
     const float off = p.remove_dc ? (-sum / (float)p.win) : 0.0f;
 #pragma unroll
     for (int j = 0; j < kJ; j++) a[j] += splat(off);
-    if (!ok_e) a[kJ - 1].x = 0.0f;
-    if (!ok_o) a[kJ - 1].y = 0.0f;
+    clear_tail();
     // ---- use_energy: Kaldi's ProcessWindow takes the log energy here when raw_energy (default), after the window otherwise
     // (VecVec over the frame, floored at FLT_EPSILON; the sum's order is this kernel's, the result agrees to float rounding)
     float log_energy = 0.0f;

@@ -241,9 +241,10 @@ class AlignmentEngine:
             d[k] = v
         for k in ("num_mel_bins", "num_coefficients", "snip_edges", "remove_dc_offset", "use_energy", "raw_energy"):
             d[k] = int(d[k])
-        self.mfcc_opts = MfccOpts(**d)
+        opts = MfccOpts(**d)
+        check(self.ctx, self.lib.mfa_mfcc_configure(self.ctx, C.byref(opts)), "mfa_mfcc_configure")
+        self.mfcc_opts = opts            # (a refused option set leaves the library, and so this object, at the previous one)
         self.num_ceps = d["num_coefficients"]
-        check(self.ctx, self.lib.mfa_mfcc_configure(self.ctx, C.byref(self.mfcc_opts)), "mfa_mfcc_configure")
 
     def load_gmm(self, gmm: DiagGmmModel) -> None:
         po = np.ascontiguousarray(gmm.pdf_offsets, dtype=np.int32)

@@ -11,8 +11,10 @@ import numpy as np
 
 
 def mfcc(wave, samp_freq=16000.0, frame_length_ms=25.0, frame_shift_ms=10.0, preemph=0.97, low_freq=20.0,
-         high_freq=7800.0, num_mel_bins=23, num_ceps=13, cepstral_lifter=22.0, snip_edges=False, remove_dc_offset=True):
-    """SURVEY Appendix A.1 (Kaldi compute-mfcc-feats with MFA's options, dither 0, use_energy False)."""
+         high_freq=7800.0, num_mel_bins=23, num_ceps=13, cepstral_lifter=22.0, snip_edges=False, remove_dc_offset=True,
+         use_energy=False, raw_energy=True, energy_floor=0.0):
+    """SURVEY Appendix A.1 (Kaldi compute-mfcc-feats with MFA's options, dither 0; use_energy: C0 is the frame's log
+    energy, before pre-emphasis and window with raw_energy, after them without)."""
     wave = np.asarray(wave, dtype=np.float64)
     n = wave.shape[0]
     win = int(samp_freq * 0.001 * frame_length_ms)
@@ -33,10 +35,14 @@ def mfcc(wave, samp_freq=16000.0, frame_length_ms=25.0, frame_shift_ms=10.0, pre
     fr = wave[idx]
     if remove_dc_offset:
         fr = fr - fr.mean(axis=1, keepdims=True)
+    eps = np.finfo(np.float32).eps
+    log_energy = np.log(np.maximum((fr * fr).sum(axis=1), eps))
     pre = fr.copy()
     pre[:, 1:] = fr[:, 1:] - preemph * fr[:, :-1]
     pre[:, 0] = fr[:, 0] - preemph * fr[:, 0]
     window = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(win) / (win - 1))) ** 0.85
+    if not raw_energy:
+        log_energy = np.log(np.maximum(((pre * window) ** 2).sum(axis=1), eps))
     spec = np.fft.rfft(pre * window, nfft, axis=1)
     power = spec.real ** 2 + spec.imag ** 2  # [T, nfft/2+1]
 
@@ -56,7 +62,7 @@ def mfcc(wave, samp_freq=16000.0, frame_length_ms=25.0, frame_shift_ms=10.0, pre
         w = np.where(binf <= center, up, down)
         W[b] = np.where((binf > left) & (binf < right), w, 0.0)
     melE = power[:, : nfft // 2] @ W.T
-    melE = np.log(np.maximum(melE, np.finfo(np.float32).eps))
+    melE = np.log(np.maximum(melE, eps))
     k = np.arange(num_ceps)[:, None]
     nn = np.arange(num_mel_bins)[None, :]
     dct = np.sqrt(2.0 / num_mel_bins) * np.cos(np.pi / num_mel_bins * (nn + 0.5) * k)
@@ -64,6 +70,8 @@ def mfcc(wave, samp_freq=16000.0, frame_length_ms=25.0, frame_shift_ms=10.0, pre
     c = melE @ dct.T
     if cepstral_lifter != 0:
         c = c * (1.0 + 0.5 * cepstral_lifter * np.sin(np.pi * np.arange(num_ceps) / cepstral_lifter))
+    if use_energy:
+        c[:, 0] = np.maximum(log_energy, np.log(energy_floor)) if energy_floor > 0 else log_energy
     return c
 
 

@@ -209,3 +209,108 @@ class PoolOwnership:
 
 def _batch_name(batch) -> str:
     return "no batch" if batch is None else f"the batch of utterances {batch[0]} … {batch[-1]} ({len(batch)})"
+
+
+# ---- front-end inputs: tests/test_gpu_frontend_options.py, tests/test_oracle_cpu.py and tools/frontend_fuzz.py ----------------
+_ORACLE_NAME = {"sample_frequency": "samp_freq", "preemphasis": "preemph", "low_frequency": "low_freq",
+                "high_frequency": "high_freq", "num_coefficients": "num_ceps"}
+
+
+def oracle_mfcc_opts(**dev_opts):
+    """The oracle's options for a set of the library's (``engine.configure_mfcc`` / ``mfa_mfcc_opts`` names)."""
+    return O.default_mfcc_opts(**{_ORACLE_NAME.get(k, k): v for k, v in dev_opts.items()})
+
+
+def np_mfcc(wave, **dev_opts):
+    """oracle.np_oracle.mfcc (float64) under the library's option names."""
+    from oracle import np_oracle as N
+    kw = {_ORACLE_NAME.get(k, k): v for k, v in dev_opts.items()}
+    kw["snip_edges"] = bool(kw.get("snip_edges", 0))
+    kw["remove_dc_offset"] = bool(kw.get("remove_dc_offset", 1))
+    return N.mfcc(wave, **kw)
+
+
+def mfcc_window_samples(**dev_opts):
+    """(window, shift) in samples, float32 arithmetic as in mfa_mfcc_configure and the oracle."""
+    f32 = np.float32
+    ms = f32(f32(dev_opts.get("sample_frequency", 16000.0)) * f32(0.001))
+    return int(ms * f32(dev_opts.get("frame_length_ms", 25.0))), int(ms * f32(dev_opts.get("frame_shift_ms", 10.0)))
+
+
+# Window lengths at 16 kHz, in samples: every class boundary of the two kernel instantiations (13 and 16 register pairs a
+# lane) and of the zero padding inside each: up to 384 / 480 whole registers lie beyond the window, from 385 / 481 on only
+# part of the last one.  400 is MFA's.
+MFCC_WINDOWS = (257, 320, 383, 384, 385, 400, 415, 416, 417, 448, 479, 480, 481, 511, 512)
+
+
+def mfcc_option_grid(energy=True):
+    """[(name, options)] in the library's option names, without snip_edges: the operating points of the MFCC kernel other
+    than MFA's default.  ``energy=False`` leaves out the use_energy rows (np_oracle has no log-energy coefficient)."""
+    g = [(f"win{w}", dict(frame_length_ms=w / 16.0)) for w in MFCC_WINDOWS]
+    g += [("shift5ms", dict(frame_shift_ms=5.0)), ("shift1ms", dict(frame_shift_ms=1.0)),
+          ("shift30ms", dict(frame_shift_ms=30.0)),                 # longer than the window: samples are skipped
+          ("shift161", dict(frame_shift_ms=10.0625))]               # odd shift: frame starts alternate in parity
+    g += [("22050Hz", dict(sample_frequency=22050.0, frame_length_ms=20.0, high_frequency=0.0)),
+          ("11025Hz", dict(sample_frequency=11025.0, frame_length_ms=25.0, high_frequency=0.0)),
+          ("32000Hz", dict(sample_frequency=32000.0, frame_length_ms=16.0, frame_shift_ms=5.0, high_frequency=0.0)),
+          ("44100Hz", dict(sample_frequency=44100.0, frame_length_ms=10.0, frame_shift_ms=5.0, high_frequency=0.0))]
+    g += [("preemph0", dict(preemphasis=0.0)), ("keep_dc", dict(remove_dc_offset=0)), ("lifter0", dict(cepstral_lifter=0.0)),
+          ("band0_nyquist", dict(low_frequency=0.0, high_frequency=0.0)),
+          ("band100_-400", dict(low_frequency=100.0, high_frequency=-400.0))]
+    g += [(f"bins{b}x{c}", dict(num_mel_bins=b, num_coefficients=c)) for b, c in ((32, 12), (16, 16), (30, 8), (13, 13))]
+    if energy:
+        g += [(f"win{w}_energy_raw{r}", dict(frame_length_ms=w / 16.0, use_energy=1, raw_energy=r))
+              for w in (320, 448) for r in (1, 0)]
+    return g
+
+
+def clipped_noise(rng, n):
+    """Gaussian noise far over full scale, clipped to int16 (the "heavy clipping" signal of the front-end fuzzer)."""
+    return np.clip(rng.normal(0, 40000, n), -32768, 32767).astype(np.int16)
+
+
+def mfcc_like(rng, T, dim):
+    """A seeded [T, dim] float32 matrix N(0, 10²): the scale of MFCCs, uploaded straight to the feature kernels."""
+    return rng.normal(0.0, 10.0, size=(T, dim)).astype(np.float32)
+
+
+def random_affine(rng, rows, cols):
+    """A seeded [rows, cols] float32 matrix N(0, 0.2²) (an LDA or fMLLR matrix, offset column included in ``cols``)."""
+    return rng.normal(0.0, 0.2, size=(rows, cols)).astype(np.float32)
+
+
+FUZZ_TONE = "tone + noise"
+
+
+def frontend_fuzz_case(seed, win=400, shift=160):
+    """One batch of the front-end fuzzer: utterance lengths around every framing boundary of (win, shift) — fewer samples
+    than half a shift, than a window, than a window plus one and two shifts — and a random one; digital silence, constants,
+    heavy clipping and a tone over a noise floor; a random speaker for every utterance (every speaker row used).
+    Returns dict(snip_edges, segs, kinds, n_spk, rows)."""
+    rng = np.random.default_rng(64000 + seed)
+    snip = bool(rng.random() < 0.3)
+    n = int(rng.integers(1, 30))
+    h = shift // 2
+    segs, kinds = [], []
+    for _ in range(n):
+        L = int(rng.choice([1, h - 1, h, h + 1, shift - 1, shift, shift + 1, shift + h - 1, shift + h, win - 1, win, win + 1,
+                            win + shift - 1, win + shift, win + shift + 1, win + 2 * shift - 1, 1000, int(rng.integers(2, 70000))]))
+        kind = rng.random()
+        if kind < 0.1:
+            s = np.zeros(L, np.int16)
+        elif kind < 0.2:
+            s = np.full(L, int(rng.integers(-32768, 32768)), np.int16)
+        elif kind < 0.4:
+            s = clipped_noise(rng, L)
+        else:
+            t = np.arange(L) / 16000.0
+            # (a noise floor of a few LSB under a full-scale tone puts most mel bins below the float32 rounding noise of ANY 512-point FFT —
+            #  two implementations then differ by 1e-2 in the cepstra; measured with std 3: up to 0.027.  Speech is not like that.)
+            s = (rng.normal(0, float(rng.choice([30, 300, 3000])), L) + 8000 * np.sin(2 * np.pi * float(rng.integers(60, 4000)) * t)
+                 + float(rng.integers(-2000, 2000))).clip(-32768, 32767).astype(np.int16)
+        segs.append(s)
+        kinds.append("zeros" if kind < 0.1 else "constant" if kind < 0.2 else "clipped noise" if kind < 0.4 else FUZZ_TONE)
+    n_spk = int(rng.integers(1, 4))
+    rows = rng.integers(0, n_spk, size=n).astype(np.int32)
+    rows[: min(n, n_spk)] = np.arange(min(n, n_spk))          # every speaker row is used
+    return dict(snip_edges=snip, segs=segs, kinds=kinds, n_spk=n_spk, rows=rows)
