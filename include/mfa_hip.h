@@ -315,7 +315,11 @@ MFA_API int mfa_build_score_plans_batch(int32_t n_utt, const int64_t *h_state_of
  * d_ali_pdf [total_frames]: pdf-id of the first-pass alignment per frame (<0 = skip); d_weight [total_frames]: frame
  * weights (0 for silence frames: silence_weight 0.0, MFA/corpus/features.py:759-766).  Outputs per speaker, float64,
  * deterministic: d_beta[n_spk], d_K[n_spk][dim][dim+1], d_G[n_spk][dim][dim+1][dim+1].  The per-speaker solve
- * (Kaldi ComputeFmllrMatrixDiagGmmFull) is host-side: montreal_forced_aligner_amd/fmllr.py. */
+ * (Kaldi ComputeFmllrMatrixDiagGmmFull) is host-side: montreal_forced_aligner_amd/fmllr.py.
+ * Limits (refused with a message, the context stays usable): dim <= 41 — a block of the speaker kernel holds the
+ * (dim+1)^2 <= 7*256 entries of a G_d in registers — and at most 128 Gaussians in a pdf.  n_utt, n_spk or total_frames of
+ * 0 is no error: nothing is written.  A speaker without a weighted frame gets beta, K and G exactly 0.  A speaker's sums
+ * depend on its own utterances in d_spk_utt order only: never on the other speakers of the batch. */
 MFA_API int mfa_fmllr_acc_batch(mfa_ctx *ctx, const float *d_feats, const int64_t *d_frame_off, int32_t n_utt,
                                 int64_t total_frames, const int32_t *d_ali_pdf, const float *d_weight,
                                 const int32_t *d_spk_utt_off, const int32_t *d_spk_utt, int32_t n_spk, double *d_beta,

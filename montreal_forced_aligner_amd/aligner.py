@@ -151,6 +151,9 @@ class CorpusAligner:
         self.fallback_first_pass: List[str] = []
         self.ctm_failed: List[str] = []          # aligned, but the interval stage raised (alignment kept, ctm None)
         self.transforms: Optional[np.ndarray] = None
+        # speakers whose fMLLR estimate was dropped for degenerate statistics (a muted channel: constant features); they keep
+        # the transform they came with (identity, or their previous one)
+        self.fmllr_rejected: List[str] = []
         self._mfcc_cache: Dict[tuple, tuple] = {}
         self._mfcc_cache_bytes = 0
         self._mfcc_cache_on = False
@@ -491,6 +494,7 @@ class CorpusAligner:
 
         utts = list(utterances)
         self.failed, self.failure_reasons, self.fallback_first_pass, self.ctm_failed = [], {}, [], []
+        self.fmllr_rejected = []
         self._mfcc_cache, self._mfcc_cache_bytes, self._mfcc_cache_on = {}, 0, True
         try:
             return self._align(utts, speaker_adapted, make_ctm, previous_transforms)
@@ -520,8 +524,11 @@ class CorpusAligner:
                                                 self.opt.silence_weight, stats_model=two_model)
                 beta[ids] += b; K[ids] += k; G[ids] += g
             W = np.tile(np.eye(D, D + 1, dtype=np.float32), (len(spk_ids), 1, 1))
+            names = {row: name for name, row in spk_ids.items()}
             for s in range(len(spk_ids)):
-                W[s], _impr = _fmllr.compute_fmllr(beta[s], K[s], G[s], min_count=self.opt.fmllr_min_count)
+                W[s], _impr, why = _fmllr.estimate_fmllr(beta[s], K[s], G[s], min_count=self.opt.fmllr_min_count)
+                if why == _fmllr.DEGENERATE:
+                    self.fmllr_rejected.append(names[s])
                 if previous_transforms is not None:
                     W[s] = _fmllr.compose_transforms(W[s], previous_transforms[s])
             self.transforms = W

@@ -15,8 +15,13 @@
 
 namespace {
 
-constexpr int kMaxD = 48;
+// Largest feature dim: a block's 256 threads own 7 (e,f) pairs each of the (D+1)² matrix, and 42² = 1764 ≤ 7·256 = 1792 < 43².
+// (The 2·256 K entries of a row group, 8·(D+1), allow more.)  Stated in include/mfa_hip.h.
+constexpr int kMaxD = 41;
+constexpr int kXiStride = 49;  // LDS row of ξ: ≥ kMaxD + 1, odd
 constexpr int kChunk = 64;
+static_assert((kMaxD + 1) * (kMaxD + 1) <= 7 * 256 && (kMaxD + 2) * (kMaxD + 2) > 7 * 256 && 8 * (kMaxD + 1) <= 2 * 256 &&
+              kMaxD + 1 <= kXiStride && kMaxD <= 64, "fmllr_spk_kernel tiling");
 
 struct FmllrFrameParams {
   int D, kpad;
@@ -93,7 +98,7 @@ struct FmllrSpkParams {
 
 // grid (speaker, row group of 8); 256 threads.  Thread owns (e,f) pairs p = tid + 256 i (i < 7) of the (D+1)² matrix.
 __global__ __launch_bounds__(256) void fmllr_spk_kernel(FmllrSpkParams p) {
-  __shared__ float xi[kChunk][kMaxD + 1];
+  __shared__ float xi[kChunk][kXiStride];
   __shared__ float bs[kChunk][8], as[kChunk][8];
   const int spk = blockIdx.x, d0 = blockIdx.y * 8;
   const int D = p.D, D1 = D + 1, npairs = D1 * D1;
@@ -173,8 +178,7 @@ MFA_API int mfa_fmllr_acc_batch(mfa_ctx *c, const float *d_feats, const int64_t 
   MFA_HIP_CHECK(c, hipSetDevice(c->device));
   if (!c->gmm_ready) return c->fail("mfa_load_gmm has not been called");
   const int D = c->dim;
-  if (D > kMaxD) return c->fail("fMLLR statistics: feature dim %d > %d", D, kMaxD);
-  if ((D + 1) * (D + 1) > 7 * 256 || 8 * (D + 1) > 512) return c->fail("fMLLR statistics: dim %d too large for the tiling", D);
+  if (D > kMaxD) return c->fail("fMLLR statistics: feature dim %d > %d (the speaker kernel tiles (dim+1)^2 <= 1792 entries)", D, kMaxD);
   if (n_utt <= 0 || n_spk <= 0 || total_frames <= 0) return 0;
   size_t need = (size_t)total_frames * (2 * D + 1) * sizeof(float);
   if (c->ws_bytes < need) {

@@ -26,35 +26,68 @@ def fmllr_aux(W: np.ndarray, beta: float, K: np.ndarray, G: np.ndarray) -> float
 
 def compute_fmllr(beta: float, K: np.ndarray, G: np.ndarray, num_iters: int = 40, min_count: float = 500.0,
                   init: Optional[np.ndarray] = None) -> Tuple[np.ndarray, float]:
+    """``estimate_fmllr`` without the reason."""
+    W, impr, _why = estimate_fmllr(beta, K, G, num_iters, min_count, init)
+    return W, impr
+
+
+COUNT, DEGENERATE, OBJECTIVE = "count below min_count", "degenerate statistics", "objective would decrease"
+
+
+def estimate_fmllr(beta: float, K: np.ndarray, G: np.ndarray, num_iters: int = 40, min_count: float = 500.0,
+                   init: Optional[np.ndarray] = None) -> Tuple[np.ndarray, float, Optional[str]]:
     """ComputeFmllrMatrixDiagGmmFull.  K: [D, D+1], G: [D, D+1, D+1] (float64).  Returns (W [D, D+1] float32,
-    auxiliary-function improvement); identity and 0.0 when β < min_count or the objective would not increase."""
+    auxiliary-function improvement); the starting transform (identity, or ``init``) and 0.0 when β < min_count, when the
+    objective would not increase, or when the statistics are degenerate: a G_d or an A that cannot be inverted, or anything
+    non-finite on the way (digital silence gives constant features, i.e. G_d of rank 1; a NaN in the statistics).  Never
+    raises and never returns a non-finite matrix: one speaker's statistics must not stop a corpus.  The third value says why
+    the starting transform came back (COUNT, DEGENERATE, OBJECTIVE), None for an estimate."""
     D = K.shape[0]
     W0 = np.concatenate([np.eye(D), np.zeros((D, 1))], axis=1) if init is None else np.asarray(init, dtype=np.float64)
-    if beta < min_count:
-        return W0.astype(np.float32), 0.0
+    if not beta >= min_count:          # (a NaN count is no count)
+        return W0.astype(np.float32), 0.0, COUNT
+    rejected = (W0.astype(np.float32), 0.0, DEGENERATE)
     K = np.asarray(K, dtype=np.float64)
     G = np.asarray(G, dtype=np.float64)
-    inv_G = np.linalg.inv(G)
-    W = W0.copy()
-    old = fmllr_aux(W0, beta, K, G)
-    for _ in range(num_iters):
-        for d in range(D):
-            cof = np.zeros(D + 1)
-            cof[:D] = np.linalg.inv(W[:, :D].T)[d]          # row d of the cofactor matrix (up to the determinant)
-            cg = inv_G[d] @ cof
-            e1 = float(cg @ cof)
-            e2 = float(cg @ K[d])
-            discr = np.sqrt(e2 * e2 + 4.0 * e1 * beta)
-            a1, a2 = (-e2 + discr) / (2 * e1), (-e2 - discr) / (2 * e1)
-            f1 = beta * np.log(abs(a1 * e1 + e2)) - 0.5 * a1 * a1 * e1
-            f2 = beta * np.log(abs(a2 * e1 + e2)) - 0.5 * a2 * a2 * e1
-            alpha = a1 if f1 > f2 else a2
-            W[d] = inv_G[d] @ (alpha * cof + K[d])
-    new = fmllr_aux(W, beta, K, G)
+    if not (np.isfinite(beta) and np.isfinite(K).all() and np.isfinite(G).all()):
+        return rejected
+    with np.errstate(all="ignore"):
+        try:
+            inv_G = np.linalg.inv(G)
+            if not np.isfinite(inv_G).all():
+                return rejected
+            W = W0.copy()
+            old = fmllr_aux(W0, beta, K, G)
+            for _ in range(num_iters):
+                for d in range(D):
+                    cof = np.zeros(D + 1)
+                    cof[:D] = np.linalg.inv(W[:, :D].T)[d]          # row d of the cofactor matrix (up to the determinant)
+                    cg = inv_G[d] @ cof
+                    e1 = float(cg @ cof)
+                    e2 = float(cg @ K[d])
+                    discr = np.sqrt(e2 * e2 + 4.0 * e1 * beta)
+                    if not (np.isfinite(e1) and np.isfinite(discr)) or e1 == 0.0:
+                        return rejected
+                    a1, a2 = (-e2 + discr) / (2 * e1), (-e2 - discr) / (2 * e1)
+                    f1 = beta * np.log(abs(a1 * e1 + e2)) - 0.5 * a1 * a1 * e1
+                    f2 = beta * np.log(abs(a2 * e1 + e2)) - 0.5 * a2 * a2 * e1
+                    alpha = a1 if f1 > f2 else a2
+                    W[d] = inv_G[d] @ (alpha * cof + K[d])
+                    if not np.isfinite(W[d]).all():
+                        return rejected
+            new = fmllr_aux(W, beta, K, G)
+        except np.linalg.LinAlgError:
+            return rejected
     impr = new - old
+    if not (np.isfinite(old) and np.isfinite(new)):
+        return rejected
     if impr < 0.0 and not abs(new - old) <= 0.001 * (abs(new) + abs(old)):
-        return W0.astype(np.float32), 0.0
-    return W.astype(np.float32), float(impr)
+        # an inverse of a G_d that is singular up to rounding can be finite and meaningless: that is degenerate
+        # statistics too, not an honest estimate that happened to lose
+        with np.errstate(all="ignore"):
+            singular = bool((np.linalg.cond(G) > 1.0 / np.finfo(np.float64).eps).any())
+        return W0.astype(np.float32), 0.0, DEGENERATE if singular else OBJECTIVE
+    return W.astype(np.float32), float(impr), None
 
 
 def compose_transforms(new: np.ndarray, previous: np.ndarray) -> np.ndarray:

@@ -930,7 +930,11 @@ static double fmllr_auxf(const std::vector<double> &W, int D, double beta, const
   return obj;
 }
 
-// Returns the auxiliary-function improvement (0 and identity transform when beta < min_count or no improvement).
+static bool all_finite(const double *v, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(v[i])) return false; return true; }
+
+// Returns the auxiliary-function improvement (0 and identity transform when beta < min_count or no improvement, and for
+// degenerate statistics: a G_d or an A with a zero pivot, or anything non-finite in an inverse, e1, the discriminant, a row
+// of W or the objective — the estimate is dropped, never returned).
 ORC_API double orc_fmllr_solve(int32_t D, double beta, const double *K, const double *G, int32_t num_iters, double min_count,
                                float *out /*[D][D+1]*/) {
   const int D1 = D + 1;
@@ -938,11 +942,12 @@ ORC_API double orc_fmllr_solve(int32_t D, double beta, const double *K, const do
   for (int i = 0; i < D; i++) W[(size_t)i * D1 + i] = 1.0;
   auto store = [&](const std::vector<double> &M) { for (size_t i = 0; i < M.size(); i++) out[i] = (float)M[i]; };
   store(W);
-  if (beta < min_count) return 0.0;
+  if (!(beta >= min_count) || !std::isfinite(beta)) return 0.0;
+  if (!all_finite(K, (size_t)D * D1) || !all_finite(G, (size_t)D * D1 * D1)) return 0.0;
   std::vector<std::vector<double> > invG(D);
   for (int d = 0; d < D; d++) {
     invG[d].assign(G + (size_t)d * D1 * D1, G + (size_t)(d + 1) * D1 * D1);
-    if (!invert_spd(invG[d], D1)) return 0.0;
+    if (!invert_spd(invG[d], D1) || !all_finite(invG[d].data(), invG[d].size())) return 0.0;
   }
   std::vector<double> Wn(W);
   double old_obj = fmllr_auxf(W, D, beta, K, G);
@@ -952,7 +957,7 @@ ORC_API double orc_fmllr_solve(int32_t D, double beta, const double *K, const do
       // cofactor row = row of inverse(A^T)
       for (int i = 0; i < D; i++) for (int j = 0; j < D; j++) At[(size_t)i * D + j] = Wn[(size_t)j * D1 + i];
       std::vector<double> inv(At);
-      if (!invert_spd(inv, D)) return 0.0;
+      if (!invert_spd(inv, D) || !all_finite(inv.data(), inv.size())) return 0.0;
       for (int j = 0; j < D; j++) cof[j] = inv[(size_t)row * D + j];
       cof[D] = 0.0;
       const std::vector<double> &iG = invG[row];
@@ -961,16 +966,19 @@ ORC_API double orc_fmllr_solve(int32_t D, double beta, const double *K, const do
       double e1 = 0.0, e2 = 0.0;
       for (int e = 0; e < D1; e++) { e1 += cg[e] * cof[e]; e2 += cg[e] * k[e]; }
       double discr = std::sqrt(e2 * e2 + 4 * e1 * beta);
+      if (!std::isfinite(e1) || !std::isfinite(discr) || e1 == 0.0) return 0.0;
       double alpha1 = (-e2 + discr) / (2 * e1), alpha2 = (-e2 - discr) / (2 * e1);
       double auxf1 = beta * std::log(std::fabs(alpha1 * e1 + e2)) - 0.5 * alpha1 * alpha1 * e1;
       double auxf2 = beta * std::log(std::fabs(alpha2 * e1 + e2)) - 0.5 * alpha2 * alpha2 * e1;
       double alpha = auxf1 > auxf2 ? alpha1 : alpha2;
       for (int e = 0; e < D1; e++) cof[e] = alpha * cof[e] + k[e];
       for (int e = 0; e < D1; e++) { double r = 0.0; for (int f = 0; f < D1; f++) r += iG[(size_t)e * D1 + f] * cof[f]; Wn[(size_t)row * D1 + e] = r; }
+      if (!all_finite(&Wn[(size_t)row * D1], D1)) return 0.0;
     }
   }
   double new_obj = fmllr_auxf(Wn, D, beta, K, G);
   double impr = new_obj - old_obj;
+  if (!std::isfinite(old_obj) || !std::isfinite(new_obj)) return 0.0;
   if (impr < 0.0 && !(std::fabs(new_obj - old_obj) <= 0.001 * (std::fabs(new_obj) + std::fabs(old_obj)))) return 0.0;
   store(Wn);
   return impr;

@@ -156,3 +156,87 @@ def viterbi_exact(num_states, start, arc_offsets, arcs, final, neg_scaled_loglik
         ali[t] = il[a]
         s = src[a]
     return best, ali
+
+
+# ---- fMLLR: statistics and the row-by-row solve, float64 ------------------------------------------------------
+def fmllr_acc(feats, ali_pdf, weight, gconsts, means_invvars, inv_vars, pdf_offsets, stat_means_invvars=None,
+              stat_inv_vars=None, chunk=4096):
+    """fMLLR statistics of one speaker's frames, everything in float64 (log-likelihoods, posteriors, a, b and the sums):
+    β = Σ_t Σ_g γ_tg,  K = Σ_t a_t ξ_tᵀ,  G_d = Σ_t b_t[d] ξ_t ξ_tᵀ  with ξ = [x; 1], γ_t = w_t · softmax over the aligned pdf,
+    a_t = Σ_g γ_tg mi_g, b_t = Σ_g γ_tg iv_g.  With ``stat_*`` the posteriors come from (gconsts, means_invvars, inv_vars) and
+    mi, iv from the stat_* arrays (the two-model form).  Frames of weight 0 or pdf < 0 contribute nothing.
+
+    Returns dict(beta, K, G) and the absolute-sum scales of the same sums, the unit a float32 pipeline's error is measured in:
+    S_beta = Σ_t w_t,  SK[d,e] = Σ_t (Σ_g γ_tg |mi_g[d]|) |ξ_t[e]|,  SG[d,e,f] = Σ_t (Σ_g γ_tg iv_g[d]) |ξ_t[e] ξ_t[f]|."""
+    x_all = np.asarray(feats, np.float64)
+    T, D = x_all.shape
+    D1 = D + 1
+    ali_pdf = np.asarray(ali_pdf, np.int64)
+    w_all = np.asarray(weight, np.float64)
+    gc, mi, iv = (np.asarray(v, np.float64) for v in (gconsts, means_invvars, inv_vars))
+    smi = mi if stat_means_invvars is None else np.asarray(stat_means_invvars, np.float64)
+    siv = iv if stat_inv_vars is None else np.asarray(stat_inv_vars, np.float64)
+    a, b, aa = np.zeros((T, D)), np.zeros((T, D)), np.zeros((T, D))
+    beta = 0.0
+    live = (w_all != 0) & (ali_pdf >= 0)
+    for p in np.unique(ali_pdf[live]):
+        rows = np.nonzero(live & (ali_pdf == p))[0]
+        g0, g1 = int(pdf_offsets[p]), int(pdf_offsets[p + 1])
+        x = x_all[rows]
+        ll = gc[None, g0:g1] + x @ mi[g0:g1].T - 0.5 * (x * x) @ iv[g0:g1].T
+        post = np.exp(ll - ll.max(axis=1, keepdims=True))
+        post *= (w_all[rows] / post.sum(axis=1))[:, None]
+        beta += float(post.sum())
+        a[rows], b[rows], aa[rows] = post @ smi[g0:g1], post @ siv[g0:g1], post @ np.abs(smi[g0:g1])
+    xi = np.concatenate([x_all, np.ones((T, 1))], axis=1)
+    xi[~live] = 0.0
+    K, SK = a.T @ xi, aa.T @ np.abs(xi)
+    G, SG = np.zeros((D, D1 * D1)), np.zeros((D, D1 * D1))
+    for t0 in range(0, T, chunk):
+        xc = xi[t0:t0 + chunk]
+        ef = (xc[:, :, None] * xc[:, None, :]).reshape(xc.shape[0], D1 * D1)
+        G += b[t0:t0 + chunk].T @ ef
+        SG += b[t0:t0 + chunk].T @ np.abs(ef)
+    return dict(beta=beta, K=K, G=G.reshape(D, D1, D1), S_beta=float(w_all[live].sum()), SK=SK, SG=SG.reshape(D, D1, D1))
+
+
+def fmllr_aux(W, beta, K, G):
+    """β log|det A| + Σ_d w_d·k_d − ½ Σ_d w_d G_d w_dᵀ  (W = [A b])."""
+    D = W.shape[0]
+    quad = sum(float(W[d] @ G[d] @ W[d]) for d in range(D))
+    return beta * np.linalg.slogdet(W[:, :D])[1] + float(np.sum(W * K)) - 0.5 * quad
+
+
+def fmllr_solve(beta, K, G, num_iters=40, min_count=500.0, init=None, trace=None):
+    """The row update of Kaldi's ComputeFmllrMatrixDiagGmmFull, from its description: for ``num_iters`` sweeps and each row
+    d, with c = [row d of (A⁻¹)ᵀ; 0] (the cofactor row up to det A): e1 = cᵀ G_d⁻¹ c, e2 = cᵀ G_d⁻¹ k_d, α = the root of
+    e1 α² + e2 α − β = 0 that maximises β log|α e1 + e2| − ½ α² e1, and w_d = G_d⁻¹ (α c + k_d).  Linear systems with
+    np.linalg.solve (no explicit inverse of G).  The estimate is dropped for the starting transform when β < min_count or the
+    auxiliary function fell by more than rounding.  Returns (W [D, D+1] float64, improvement); ``trace`` (a list) receives the
+    auxiliary function before the first and after every sweep."""
+    K, G = np.asarray(K, np.float64), np.asarray(G, np.float64)
+    D = K.shape[0]
+    W0 = np.eye(D, D + 1) if init is None else np.array(init, dtype=np.float64)
+    if beta < min_count:
+        return W0, 0.0
+    W = W0.copy()
+    old = fmllr_aux(W0, beta, K, G)
+    if trace is not None:
+        trace.append(old)
+    for _ in range(num_iters):
+        for d in range(D):
+            e_d = np.zeros(D)
+            e_d[d] = 1.0
+            c = np.append(np.linalg.solve(W[:, :D], e_d), 0.0)      # A⁻¹ e_d = column d of A⁻¹ = row d of (A⁻¹)ᵀ
+            gc_, gk = np.linalg.solve(G[d], np.stack([c, K[d]], axis=1)).T
+            e1, e2 = float(c @ gc_), float(c @ gk)
+            root = np.sqrt(e2 * e2 + 4.0 * e1 * beta)
+            a1, a2 = (-e2 + root) / (2.0 * e1), (-e2 - root) / (2.0 * e1)
+            f1, f2 = (beta * np.log(abs(al * e1 + e2)) - 0.5 * al * al * e1 for al in (a1, a2))
+            W[d] = (a1 if f1 > f2 else a2) * gc_ + gk
+        if trace is not None:
+            trace.append(fmllr_aux(W, beta, K, G))
+    new = fmllr_aux(W, beta, K, G)
+    if new < old and abs(new - old) > 0.001 * (abs(new) + abs(old)):
+        return W0, 0.0
+    return W, new - old

@@ -314,3 +314,219 @@ def frontend_fuzz_case(seed, win=400, shift=160):
     rows = rng.integers(0, n_spk, size=n).astype(np.int32)
     rows[: min(n, n_spk)] = np.arange(min(n, n_spk))          # every speaker row is used
     return dict(snip_edges=snip, segs=segs, kinds=kinds, n_spk=n_spk, rows=rows)
+
+
+# ---- fMLLR statistics: tests/test_fmllr_cpu.py (oracle against float64) and tests/test_gpu_fmllr_stats.py (device) ---------
+FMLLR_DIMS = (8, 13, 39, 40, 41)
+FMLLR_SIZES = (1, 2, 3, 4, 5, 8, 9, 16, 17, 26, 32, 33, 64, 65, 100, 128)     # Gaussians per pdf: every packing class
+FMLLR_LENGTHS = (0, 1, 63, 64, 65, 128, 129, 1000)                            # frames per utterance: the 64-frame chunks
+EPS32 = float(np.finfo(np.float32).eps)
+# The oracle's worst distance from the float64 restatement over fmllr_case_names() and the two fixture cases, in units of
+# ε32·S (β, K, G), and through the solver in ulp of max|W|: measured by tests/test_fmllr_cpu.py, which fails when a figure
+# moves by more than half a percent.  tests/test_gpu_fmllr_stats.py says what the device is held to.
+FMLLR_ORACLE_BETA, FMLLR_ORACLE_K, FMLLR_ORACLE_G, FMLLR_ORACLE_W = 3.00, 219.60, 148.37, 44.69
+
+
+def fmllr_tm(num_pdfs):
+    """What fmllr_statistics reads of a transition model: transition-ids 2p+1 and 2p+2 belong to pdf p of phone p+1
+    (id 0 is no id).  The largest valid id is 2·num_pdfs."""
+    from types import SimpleNamespace
+    return SimpleNamespace(id2pdf=np.concatenate([[-1], np.repeat(np.arange(num_pdfs), 2)]).astype(np.int32),
+                           id2phone=np.concatenate([[0], np.repeat(np.arange(num_pdfs) + 1, 2)]).astype(np.int32),
+                           num_transition_ids=2 * num_pdfs)
+
+
+def fmllr_draw(rng, am, pdfs):
+    """A frame for every entry of ``pdfs``: a draw from a random Gaussian of that pdf."""
+    x = np.zeros((len(pdfs), am.dim), np.float32)
+    for t, p in enumerate(pdfs):
+        g = rng.integers(am.pdf_offsets[p], am.pdf_offsets[p + 1])
+        var = 1.0 / am.inv_vars[g].astype(np.float64)
+        x[t] = am.means_invvars[g] * var + np.sqrt(var) * rng.normal(size=am.dim)
+    return x
+
+
+def fmllr_second_model(rng, am):
+    """A statistics model with the layout of ``am``: other means and variances (the two-model form)."""
+    import copy
+    st = copy.copy(am)
+    st.means_invvars = (am.means_invvars * (1.0 + 0.05 * rng.normal(size=am.means_invvars.shape))).astype(np.float32)
+    st.inv_vars = (am.inv_vars * rng.uniform(0.8, 1.25, size=am.inv_vars.shape)).astype(np.float32)
+    return st
+
+
+def _fmllr_pdfs(rng, n_frames, sizes, big_share=60, small_share=6):
+    """Pdf of every frame: pdfs of more than 64 Gaussians ``big_share`` times, the others ``small_share`` times (fewer when
+    the frames do not suffice), the rest uniform; shuffled."""
+    P = len(sizes)
+    fixed = np.concatenate([np.full(big_share if sizes[p] > 64 else small_share, p) for p in range(P)])
+    if len(fixed) > n_frames:
+        fixed = rng.permutation(fixed)[:n_frames]
+    return rng.permutation(np.concatenate([fixed, rng.integers(0, P, size=n_frames - len(fixed))])).astype(np.int32)
+
+
+def fmllr_case(name):
+    """One case of the fMLLR statistics grid, seeded by its name: dict(name, am, stats_am | None, tm, sil_phones,
+    silence_weight, feats [T, D] float32, frame_off, ali [T] int32 transition-ids, utt2spk)."""
+    import zlib
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    kind, _, arg = name.partition("-")
+    D, sizes, lengths, two, sw = 40, list(FMLLR_SIZES), list(FMLLR_LENGTHS), False, 0.0
+    utt2spk = None
+    if kind == "shape":                    # shape-D39-two
+        d, form = arg.split("-")
+        D, two = int(d[1:]), form == "two"
+        utt2spk = [0, 1, 0, 1, 2, 2, 1, 0]
+    elif kind == "spk" and arg == "one":
+        lengths, utt2spk = [64, 0, 130, 7, 1000], [5] * 5
+    elif kind == "spk" and arg == "300":
+        lengths = rng.integers(1, 12, size=300).tolist()
+        utt2spk = rng.permutation(300).tolist()
+    elif kind == "spk" and arg == "mixed":  # scrambled ids; 44: only empty utterances; 3: silence and unaligned frames only
+        lengths = [200, 90, 64, 0, 300, 129, 0, 77, 150, 65, 31]
+        utt2spk = [907, 12, 907, 44, 5000, 12, 44, 3, 5000, 3, 907]
+    elif kind == "weights":                # weights-0.5
+        D, sw, lengths, utt2spk = 39, float(arg), [200, 65, 300, 128], [1, 0, 1, 0]
+    elif kind == "long":
+        lengths, utt2spk = rng.integers(900, 1100, size=60).tolist() + [100], [0] * 60 + [1]
+    elif kind == "hard":
+        lengths, utt2spk = [129, 500, 64, 700], [0, 1, 0, 1]
+        if arg == "ties":
+            sizes = [2, 4, 8, 64, 66, 128]
+    else:
+        raise ValueError(name)
+    am = random_gmm(rng, D, sizes)
+    # random_gmm's means are N(0, 3²) a dimension: at D ≥ 13 every frame would belong to one Gaussian outright and the
+    # softmax would never be seen.  Pull the means in to a few σ of each other, so that a frame's posteriors are spread.
+    var = 1.0 / am.inv_vars.astype(np.float64)
+    mean = am.means_invvars * var
+    mean2 = mean * (1.07 / np.sqrt(D))
+    am.means_invvars = (mean2 / var).astype(np.float32)
+    am.gconsts = (am.gconsts + 0.5 * ((mean * mean - mean2 * mean2) / var).sum(axis=1)).astype(np.float32)
+    if name == "hard-ties":                # the second half of every pdf repeats the first: exact ties in the softmax
+        for p, n in enumerate(sizes):
+            g0, h = int(am.pdf_offsets[p]), n // 2
+            for v in (am.gconsts, am.means_invvars, am.inv_vars):
+                v[g0 + h: g0 + 2 * h] = v[g0: g0 + h]
+    if name == "hard-weights":             # mixture weights from 1 down to 1e-30 inside every pdf
+        for p, n in enumerate(sizes):
+            g0 = int(am.pdf_offsets[p])
+            am.gconsts[g0: g0 + n] += (np.log(10.0) * np.linspace(0.0, -30.0, n)).astype(np.float32) if n > 1 else 0.0
+    P = len(sizes)
+    tm = fmllr_tm(P)
+    sil_pdfs = [2, 9] if P > 9 else [0]
+    T = int(np.sum(lengths))
+    pdfs = _fmllr_pdfs(rng, T, sizes)
+    feats = fmllr_draw(rng, am, pdfs)
+    ali = (2 * pdfs + 1 + rng.integers(0, 2, size=T)).astype(np.int32)
+    frame_off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    utt2spk = np.asarray(utt2spk)
+    if name == "spk-mixed":
+        for u in np.nonzero(utt2spk == 3)[0]:
+            a, b = frame_off[u], frame_off[u + 1]
+            ali[a:b] = np.where(rng.random(b - a) < 0.5, 0, 2 * sil_pdfs[0] + 1)
+    if kind == "weights":                  # ids the lookup must give weight 0, and the largest valid one
+        bad = rng.choice(T, size=60, replace=False)
+        ali[bad] = np.resize(np.array([0, -1, -7, 2 * P + 1, 2 * P + 6, 2 ** 30, np.iinfo(np.int32).min], np.int32), 60)
+        ali[np.setdiff1d(np.arange(T), bad)[:3]] = 2 * P
+    if name == "hard-far":
+        # ×30 and 50 σ (σ ≤ 2) off every mean: log-likelihoods near −1e5, where float32 resolves 1e-2.  Only frames whose
+        # best Gaussian leads by 40 in float64 are kept aligned, so one Gaussian takes everything in any float32 pipeline.
+        # The ambiguous frames are dropped on purpose: there float32 and float64 posteriors differ by tens of percent and no
+        # bound in ε32·S can hold for either pipeline; what this case checks is that nothing overflows or turns NaN.
+        feats = (30.0 * feats + 100.0).astype(np.float32)
+        x = feats.astype(np.float64)
+        ll = am.gconsts[None, :] + x @ am.means_invvars.T.astype(np.float64) - 0.5 * (x * x) @ am.inv_vars.T.astype(np.float64)
+        for t in range(T):
+            v = np.sort(ll[t, am.pdf_offsets[pdfs[t]]: am.pdf_offsets[pdfs[t] + 1]])
+            if len(v) > 1 and v[-1] - v[-2] < 40.0:
+                ali[t] = 0
+    stats_am = fmllr_second_model(rng, am) if two else None
+    return dict(name=name, am=am, stats_am=stats_am, tm=tm, sil_phones=[p + 1 for p in sil_pdfs], silence_weight=sw,
+                feats=feats, frame_off=frame_off, ali=ali, utt2spk=utt2spk, sizes=sizes)
+
+
+def fmllr_case_names():
+    return ([f"shape-D{d}-{form}" for d in FMLLR_DIMS for form in ("one", "two")] + ["spk-one", "spk-300", "spk-mixed"] +
+            ["weights-0.0", "weights-0.5", "weights-1.0", "long", "hard-far", "hard-ties", "hard-weights"])
+
+
+def fmllr_fixture_case(fx, two_model):
+    """The inputs of test_fmllr_statistics_match_oracle (tests/test_gpu_parity.py) and of its two-model twin
+    (tests/test_gpu_alimdl_flow.py): three cuts of the fixture recording through the oracle's LDA front end, random
+    transition-ids of acoustic_g2p_output_model as the alignment."""
+    import copy
+    from montreal_forced_aligner_amd import model as M
+    tm, am = fx.g2p_tm, fx.g2p_am
+    rng = np.random.default_rng(4 if two_model else 3)
+    stats_am = None
+    if two_model:
+        tm_a, am_a = M.load_model_bytes(fx.g2p_archive["final.alimdl"])
+        assert np.array_equal(am_a.pdf_offsets, am.pdf_offsets) and tm_a.num_transition_ids == tm.num_transition_ids
+        stats_am = am
+        if np.array_equal(am_a.means_invvars, am.means_invvars):     # the fixture's two models may coincide: force a difference
+            stats_am = copy.copy(am)
+            stats_am.means_invvars = (am.means_invvars * (1.0 + 0.05 * rng.normal(size=am.means_invvars.shape))).astype(np.float32)
+            stats_am.inv_vars = (am.inv_vars * rng.uniform(0.8, 1.25, size=am.inv_vars.shape)).astype(np.float32)
+        am = am_a
+    sr = 16000
+    segs = [fx.pcm[int(a * sr): int(b * sr)] for a, b in ((0.0, 3.0), (3.0, 3.21), (5.0, 12.5))]
+    mf = [O.mfcc(s.astype(np.float32), O.default_mfcc_opts(snip_edges=1)) for s in segs]
+    feats = [O.affine(O.splice(O.cmvn_apply(O.cmvn_stats([m]), m)), fx.g2p_lda) for m in mf]
+    alis = [rng.integers(1, tm.num_transition_ids + 1, size=f.shape[0]).astype(np.int32) for f in feats]
+    if two_model:
+        alis[2][-7:] = 0
+    else:
+        alis[1][:5] = 0              # unaligned frames carry no weight
+    return dict(name="fixture-two" if two_model else "fixture-one", am=am, stats_am=stats_am, tm=tm, sil_phones=[1, 2],
+                silence_weight=0.0, feats=np.concatenate(feats), ali=np.concatenate(alis),
+                frame_off=np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int64),
+                utt2spk=np.array([1, 0, 1] if two_model else [7, 3, 7]))
+
+
+def fmllr_frame_weights(case):
+    """(pdf, weight) of every frame as the device's lookup defines them: ids ≤ 0 or beyond the table weigh 0 (pdf −1)."""
+    tm, ali = case["tm"], case["ali"].astype(np.int64)
+    ok = (ali > 0) & (ali < tm.id2pdf.shape[0])
+    tid = np.where(ok, ali, 0)
+    sil = np.isin(tm.id2phone[tid], case["sil_phones"])
+    w = np.where(ok, np.where(sil, np.float32(case["silence_weight"]), np.float32(1.0)), np.float32(0.0)).astype(np.float32)
+    return np.where(ok, np.maximum(tm.id2pdf[tid], 0), -1).astype(np.int32), w
+
+
+def fmllr_expected(case):
+    """Per speaker (ascending id, the order fmllr_statistics returns): the oracle's statistics, utterances accumulated in
+    ascending order as on the device, and the float64 restatement with its scales.  Returns (ids, [oracle (β, K, G)], [N dict])."""
+    from oracle import np_oracle as N
+    am, st = case["am"], case["stats_am"]
+    pdf, w = fmllr_frame_weights(case)
+    fo, x = case["frame_off"], case["feats"]
+    D = x.shape[1]
+    kw = {} if st is None else dict(stat_means_invvars=st.means_invvars, stat_inv_vars=st.inv_vars)
+    ids = np.unique(case["utt2spk"])
+    orc, ref = [], []
+    for s in ids:
+        stats = (np.zeros(1), np.zeros((D, D + 1)), np.zeros((D, D + 1, D + 1)))
+        rows = []
+        for u in np.nonzero(case["utt2spk"] == s)[0]:
+            a, b = int(fo[u]), int(fo[u + 1])
+            rows.append(np.arange(a, b))
+            if b > a:
+                O.fmllr_acc(x[a:b], np.maximum(pdf[a:b], 0), w[a:b], am.gconsts, am.means_invvars, am.inv_vars, am.pdf_offsets,
+                            stats, **kw)
+        rows = np.concatenate(rows)
+        orc.append((float(stats[0][0]), stats[1], stats[2]))
+        ref.append(N.fmllr_acc(x[rows], pdf[rows], w[rows], am.gconsts, am.means_invvars, am.inv_vars, am.pdf_offsets, **kw))
+    return ids, orc, ref
+
+
+def fmllr_distance(got, ref):
+    """Worst distance of statistics (β, K, G) from the float64 restatement ``ref``, in units of ε32·S for β, K and G.
+    Where the scale is zero nothing was summed: the statistic must be exactly zero (inf otherwise)."""
+    out = []
+    for g, r, s in ((np.asarray(got[0]), ref["beta"], ref["S_beta"]), (got[1], ref["K"], ref["SK"]), (got[2], ref["G"], ref["SG"])):
+        err, s = np.abs(np.asarray(g, np.float64) - r), np.asarray(s, np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            q = np.where(s > 0, err / (EPS32 * s), np.where(err == 0, 0.0, np.inf))
+        out.append(float(np.max(q)) if not np.isnan(q).any() else float("inf"))
+    return tuple(out)

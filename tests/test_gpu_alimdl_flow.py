@@ -15,50 +15,31 @@ from montreal_forced_aligner_amd.aligner import AlignOptions, CorpusAligner, Cor
 from montreal_forced_aligner_amd.engine import fmllr_statistics
 from oracle import oracle as O
 from tests import synth
-from tests.test_gpu_parity import _dev, _segments
+from tests.test_gpu_parity import _dev
 
 pytestmark = pytest.mark.gpu
 
 
 def test_two_model_fmllr_statistics_match_oracle(engine, fx):
     """acoustic_g2p_output_model.zip ships both final.mdl and final.alimdl (same Gaussian layout): device statistics with
-    the alignment model loaded and final.mdl as the statistics model vs the oracle's two-model accumulation."""
-    tm, am = fx.g2p_tm, fx.g2p_am
-    tm_a, am_a = M.load_model_bytes(fx.g2p_archive["final.alimdl"])
-    assert np.array_equal(am_a.pdf_offsets, am.pdf_offsets) and tm_a.num_transition_ids == tm.num_transition_ids
-    rng = np.random.default_rng(4)
-    if np.array_equal(am_a.means_invvars, am.means_invvars):     # the fixture's two models may coincide: force a difference
-        am = copy.copy(am)
-        am.means_invvars = (am.means_invvars * (1.0 + 0.05 * rng.normal(size=am.means_invvars.shape))).astype(np.float32)
-        am.inv_vars = (am.inv_vars * rng.uniform(0.8, 1.25, size=am.inv_vars.shape)).astype(np.float32)
-    mf = [O.mfcc(s.astype(np.float32), O.default_mfcc_opts(snip_edges=1)) for s in _segments(fx)[:3]]
-    feats = [O.affine(O.splice(O.cmvn_apply(O.cmvn_stats([m]), m)), fx.g2p_lda) for m in mf]
-    frame_off = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int64)
-    alis = [rng.integers(1, tm.num_transition_ids + 1, size=f.shape[0]).astype(np.int32) for f in feats]
-    alis[2][-7:] = 0
-    utt2spk = np.array([1, 0, 1])
-    sil_phones = [1, 2]
-    engine.load_gmm(am_a)                       # posteriors: the alignment model
-    ids, beta, K, G = fmllr_statistics(engine, _dev(engine, np.concatenate(feats)), frame_off, _dev(engine, np.concatenate(alis)),
-                                       tm, utt2spk, sil_phones, stats_model=am)
-    one, b1, K1, G1 = fmllr_statistics(engine, _dev(engine, np.concatenate(feats)), frame_off, _dev(engine, np.concatenate(alis)),
-                                       tm, utt2spk, sil_phones)          # back to the single-model form
+    the alignment model loaded and final.mdl as the statistics model vs the oracle's two-model accumulation and the float64
+    restatement, under the bound of tests/test_gpu_fmllr_stats.py; then the single-model form on the same engine."""
+    from tests import helpers
+    from tests.test_gpu_fmllr_stats import check_statistics, device_statistics
+
+    two = helpers.fmllr_fixture_case(fx, two_model=True)
+    one = dict(two, stats_am=None)
+    assert (two["ali"][-7:] == 0).all()
+    ids, beta, K, G = got2 = device_statistics(engine, two)          # posteriors: the alignment model
+    _, b1, K1, G1 = got1 = device_statistics(engine, one, load=False)          # back to the single-model form
     assert not np.allclose(K, K1)               # the statistics model really is used
-    for k, spk in enumerate(ids):
-        st2, st1 = None, None
-        for u in range(3):
-            if utt2spk[u] != spk:
-                continue
-            ali = alis[u]
-            w = np.where((ali == 0) | np.isin(tm.id2phone[ali], sil_phones), 0.0, 1.0).astype(np.float32)
-            pdf = np.maximum(tm.id2pdf[ali], 0)
-            st2 = O.fmllr_acc(feats[u], pdf, w, am_a.gconsts, am_a.means_invvars, am_a.inv_vars, am_a.pdf_offsets, st2,
-                              stat_means_invvars=am.means_invvars, stat_inv_vars=am.inv_vars)
-            st1 = O.fmllr_acc(feats[u], pdf, w, am_a.gconsts, am_a.means_invvars, am_a.inv_vars, am_a.pdf_offsets, st1)
-        for (rb, rK, rG), (db, dK, dG) in (((st2[0][0], st2[1], st2[2]), (beta[k], K[k], G[k])),
-                                           ((st1[0][0], st1[1], st1[2]), (b1[k], K1[k], G1[k]))):
-            assert abs(db - rb) < 1e-3 * max(1.0, rb)
-            assert np.allclose(dK, rK, rtol=1e-4, atol=1e-2) and np.allclose(dG, rG, rtol=1e-4, atol=1e-2)
+    for case, got, what in ((two, got2, "two-model form"), (one, got1, "single-model form after it")):
+        expected = helpers.fmllr_expected(case)
+        check_statistics(case, got, expected, what=what)
+        for k in range(len(ids)):
+            rb, rK, rG = expected[1][k]
+            assert abs(got[1][k] - rb) < 1e-3 * max(1.0, rb)
+            assert np.allclose(got[2][k], rK, rtol=1e-4, atol=1e-2) and np.allclose(got[3][k], rG, rtol=1e-4, atol=1e-2)
 
 
 @pytest.fixture(scope="module")
