@@ -95,9 +95,12 @@ MFA_API int mfa_cmvn_stats(mfa_ctx *ctx, const float *d_feats, const int64_t *d_
 
 /* ---- Final features: replaces FeatureArchive(..., cmvn, deltas | lda_mat, transform) iteration / the explicit chain at
  *      MFA/alignment/multiprocessing.py:1287-1304: ApplyCmvn → compute_deltas | splice_frames+LDA → fMLLR.
- * mode 0: CMVN + Δ+ΔΔ (order 2, window 2): out dim = 3*dim.
+ * mode 0: CMVN + Δ+ΔΔ (order 2, window 2): out dim = 3*dim; with d_fmllr non-NULL the per-speaker transform follows the
+ *         deltas in the same launch: d_fmllr[n_spk][3*dim][3*dim+1], out[t][o] = Σ_d W[o][d]·y[t][d] + W[o][3*dim] with
+ *         y the Δ+ΔΔ vector (fmaf over ascending d, offset last).  d_lda / lda_rows / lda_cols are not read.
  * mode 1: CMVN + splice(±ctx) + LDA d_lda[lda_rows][lda_cols] (+ fMLLR d_fmllr[n_spk][lda_rows][lda_rows+1] if non-NULL).
- * d_utt2spk[n_utt]; d_cmvn may be NULL (no CMVN). */
+ * d_utt2spk[n_utt] indexes d_cmvn and d_fmllr (NULL: every utterance takes row 0 of d_fmllr; d_cmvn then must be NULL);
+ * d_cmvn may be NULL (no CMVN).  The caller vouches for n_spk: the rows are indexed by d_utt2spk alone. */
 MFA_API int mfa_feats_batch(mfa_ctx *ctx, const float *d_mfcc, const int64_t *d_frame_off, int32_t n_utt, int32_t max_frames,
                             int32_t dim, const int32_t *d_utt2spk, const double *d_cmvn, int32_t mode, int32_t splice_ctx,
                             const float *d_lda, int32_t lda_rows, int32_t lda_cols, const float *d_fmllr, float *d_out);

@@ -514,9 +514,8 @@ class CorpusAligner:
         results, kept = self._pass(utts, spk_ids, cmvn, prev, want_feats=speaker_adapted, first_compile=first_compile)
         self.transforms = None if previous_transforms is None else np.asarray(previous_transforms, dtype=np.float32)
         if speaker_adapted:
-            if self.lda is None:
-                raise NotImplementedError("speaker adaptation needs the LDA feature path")
-            D = self.lda.shape[0]
+            # the transform follows either feature branch: the LDA's rows, or Δ+ΔΔ of the cepstra (MFA/db.py:2101-2136)
+            D = self.lda.shape[0] if self.lda is not None else 3 * self.engine.num_ceps
             beta = np.zeros(len(spk_ids)); K = np.zeros((len(spk_ids), D, D + 1)); G = np.zeros((len(spk_ids), D, D + 1, D + 1))
             two_model = self.am if self.ali_am is not None else None
             for idx, feats, ali, fo, rows in kept:

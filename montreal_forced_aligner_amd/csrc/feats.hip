@@ -1,6 +1,6 @@
 // CMVN statistics and final-feature kernels for gfx950.
 //   mfa_cmvn_stats : per-speaker Σx, Σx², count in float64 (Kaldi AccCmvnStats), deterministic order.
-//   mfa_feats_batch: ApplyCmvn → Δ+ΔΔ (Kaldi DeltaFeatures order 2 window 2) or splice(±ctx)+LDA(+fMLLR)
+//   mfa_feats_batch: ApplyCmvn → Δ+ΔΔ (Kaldi DeltaFeatures order 2 window 2) (+fMLLR) or splice(±ctx)+LDA(+fMLLR)
 //                    (Kaldi SpliceFrames / ApplyAffineTransform; Appendix A.3) — the chain of
 //                    MFA/alignment/multiprocessing.py:1287-1304 / MFA/db.py:2101-2136.
 // HBM-bound streaming stages: each input row is read once per tile (+halo) and each output row written once.
@@ -82,7 +82,10 @@ __global__ __launch_bounds__(256) void feats_kernel(FeatParams p) {
   const int rows = kTile + 2 * halo;
   float *x = smem;                       // [rows][dim] CMVN-applied base features (frame t0-halo+r, clamped)
   float *mat = x + rows * p.dim;         // mode 1: LDA [lda_rows][lda_cols] then fMLLR [lda_rows][lda_rows+1]
-  float *y = mat + (p.mode == 1 ? p.lda_rows * p.lda_cols + p.lda_rows * (p.lda_rows + 1) : 0);  // [kTile][lda_rows]
+                                         // mode 0 with fMLLR: the speaker's matrix [3·dim][3·dim+1]
+  const int od0 = 3 * p.dim;
+  float *y = mat + (p.mode == 1 ? p.lda_rows * p.lda_cols + p.lda_rows * (p.lda_rows + 1)
+                                : (p.fmllr ? od0 * (od0 + 1) : 0));  // [kTile][lda_rows] | [kTile][3·dim] Δ rows before fMLLR
   // CMVN offsets (Kaldi ApplyCmvn without variance normalisation): offset = (float)(-mean)
   const int spk = p.utt2spk ? p.utt2spk[utt] : 0;
   for (int i = threadIdx.x; i < rows * p.dim; i += blockDim.x) {
@@ -104,6 +107,9 @@ __global__ __launch_bounds__(256) void feats_kernel(FeatParams p) {
       float *fdst = mat + p.lda_rows * p.lda_cols;
       for (int i = threadIdx.x; i < p.lda_rows * (p.lda_rows + 1); i += blockDim.x) fdst[i] = fm[i];
     }
+  } else if (p.fmllr) {
+    const float *fm = p.fmllr + (size_t)spk * od0 * (od0 + 1);
+    for (int i = threadIdx.x; i < od0 * (od0 + 1); i += blockDim.x) mat[i] = fm[i];
   }
   __syncthreads();
   if (p.mode == 0) {
@@ -130,7 +136,20 @@ __global__ __launch_bounds__(256) void feats_kernel(FeatParams p) {
           if (s != 0.0f) acc = fmaf(s, xc[(tf - t) * p.dim], acc);
         }
       }
-      p.out[(f0 + t) * od + c] = acc;
+      if (p.fmllr) y[r * od + c] = acc;
+      else p.out[(f0 + t) * od + c] = acc;
+    }
+    if (!p.fmllr) return;
+    // per-speaker fMLLR on the Δ rows: acc = 0, fmaf over ascending d, offset column last (the oracle's affine chain)
+    __syncthreads();
+    for (int i = threadIdx.x; i < kTile * od; i += blockDim.x) {
+      int r = i / od, o = i % od, t = t0 + r;
+      if (t >= T) continue;
+      const float *m = mat + o * (od + 1);
+      float acc = 0.0f;
+      for (int d = 0; d < od; d++) acc = fmaf(m[d], y[r * od + d], acc);
+      acc += m[od];
+      p.out[(f0 + t) * od + o] = acc;
     }
     return;
   }
@@ -344,10 +363,18 @@ MFA_API int mfa_feats_batch(mfa_ctx *c, const float *d_mfcc, const int64_t *d_fr
   // register-row kernel for MFA's standard shape (13 MFCCs spliced ±3 → 91, LDA to 40); other shapes take the generic kernel
   constexpr int kDim = 13, kCtx = 3, kR = 40;
   const char *generic = getenv("MFA_FEATS_GENERIC");
-  const bool register_rows = mode == 1 && dim == kDim && splice_ctx == kCtx && lda_rows == kR && !(generic && generic[0] == '1');
+  const bool force_generic = generic && generic[0] == '1';
+  const bool register_rows = mode == 1 && dim == kDim && splice_ctx == kCtx && lda_rows == kR && !force_generic;
   size_t lds = 0;
   if (mode == 0) {
     lds = (size_t)(kTile + 8) * dim * 4;
+    if (d_fmllr) {
+      const size_t od = 3 * (size_t)dim;
+      lds += (od * (od + 1) + (size_t)kTile * od) * 4;
+      if (lds > kMaxLdsBytes)
+        return c->fail("feats: base dim %d with a %zux%zu fMLLR needs %zu bytes of LDS (a launch may ask for %zu)", dim, od,
+                       od + 1, lds, kMaxLdsBytes);
+    }
   } else {
     int sdim = (2 * splice_ctx + 1) * dim;
     if (!d_lda || lda_rows <= 0 || lda_rows > kMaxOut || (lda_cols != sdim && lda_cols != sdim + 1))

@@ -355,17 +355,20 @@ class AlignmentEngine:
     def features(self, mfcc: torch.Tensor, frame_off: np.ndarray, utt2spk: Optional[np.ndarray] = None,
                  cmvn: Optional[torch.Tensor] = None, lda: Optional[torch.Tensor] = None,
                  fmllr: Optional[torch.Tensor] = None, splice_context: int = 3) -> torch.Tensor:
-        """CMVN → Δ+ΔΔ (no ``lda``) or splice+LDA(+fMLLR).  Mirrors FeatureArchive's chain (MFA/db.py:2101-2136)."""
+        """CMVN → Δ+ΔΔ (no ``lda``) or splice+LDA, then per-speaker fMLLR when ``fmllr`` is given: [n_spk, D, D+1] with
+        D = 3·dim after the deltas, the LDA's rows after the LDA.  Mirrors FeatureArchive's chain (MFA/db.py:2101-2136)."""
         n_utt = len(frame_off) - 1
         dim = mfcc.shape[1]
         total = int(frame_off[-1])
+        if lda is None and fmllr is not None:
+            check_delta_fmllr(fmllr, dim, utt2spk)
         d_fo = self._dev(frame_off)
         d_u2s = self._dev(np.asarray(utt2spk, dtype=np.int32)) if utt2spk is not None else None
         max_frames = int(np.diff(frame_off).max()) if n_utt else 0
         if lda is None:
             out = torch.empty((total, 3 * dim), dtype=torch.float32, device=self.device)
             rc = self.lib.mfa_feats_batch(self.ctx, _ptr(mfcc), _ptr(d_fo), n_utt, max_frames, dim, _ptr(d_u2s), _ptr(cmvn), 0, 0,
-                                          None, 0, 0, None, _ptr(out))
+                                          None, 0, 0, _ptr(fmllr), _ptr(out))
         else:
             rows, cols = lda.shape
             out = torch.empty((total, rows), dtype=torch.float32, device=self.device)
@@ -774,6 +777,8 @@ class Pipeline:
         self.d_ll_off, self.d_ll_cols = d(self.ll_off), d(P.astype(np.int32))
         self.num_ceps = e.num_ceps
         self.feat_dim = 3 * self.num_ceps if lda is None else int(lda.shape[0])
+        if lda is None and fmllr is not None:
+            check_delta_fmllr(fmllr, self.num_ceps, inv)
         f32, i32 = torch.float32, torch.int32
         self.mfcc = torch.empty((self.total_frames, self.num_ceps), dtype=f32, device=dev)
         self.cmvn = torch.empty((self.n_spk, 2, self.num_ceps + 1), dtype=torch.float64, device=dev)
@@ -949,7 +954,7 @@ class Pipeline:
                                   _ptr(self.d_spk_utt), self.n_spk, _ptr(self.cmvn)), "mfa_cmvn_stats")
         if self.lda is None:
             rc = L.mfa_feats_batch(c, _ptr(self.mfcc), _ptr(self.d_frame_off), self.n_utt, self.max_frames, self.num_ceps,
-                                   _ptr(self.d_utt2spk), _ptr(self.cmvn), 0, 0, None, 0, 0, None, _ptr(self.feats))
+                                   _ptr(self.d_utt2spk), _ptr(self.cmvn), 0, 0, None, 0, 0, _ptr(self.fmllr), _ptr(self.feats))
         else:
             rc = L.mfa_feats_batch(c, _ptr(self.mfcc), _ptr(self.d_frame_off), self.n_utt, self.max_frames, self.num_ceps,
                                    _ptr(self.d_utt2spk), _ptr(self.cmvn), 1, self.ctx_frames, _ptr(self.lda),
@@ -971,6 +976,28 @@ class Pipeline:
                                    _ptr(self.d_frame_off), self.total_frames, g.total_arcs, g.max_states, g.max_arcs, C.byref(self.opts), _ptr(self.ali),
                                    _ptr(self.words), _ptr(self.n_words), _ptr(self.like), None, _ptr(self.status)),
               "mfa_align_batch")
+
+
+def check_delta_fmllr(fmllr, dim: int, utt2spk) -> None:
+    """Host check of the per-speaker transforms of the Δ+ΔΔ path before a launch: float32, contiguous, on the device,
+    [n_spk, 3·dim, 3·dim+1], a row for every speaker ``utt2spk`` names (row 0 without ``utt2spk``).  The kernel indexes the
+    array by these numbers alone."""
+    D = 3 * int(dim)
+    if not isinstance(fmllr, torch.Tensor) or fmllr.dtype != torch.float32:
+        raise _lib.MfaHipError(f"features: fMLLR transforms must be a float32 tensor (got {getattr(fmllr, 'dtype', type(fmllr))})")
+    if fmllr.dim() != 3 or tuple(fmllr.shape[1:]) != (D, D + 1):
+        raise _lib.MfaHipError(f"features: fMLLR transforms of shape {tuple(fmllr.shape)} do not fit Δ+ΔΔ features of dimension {D}: "
+                               f"expected [n_spk, {D}, {D + 1}]")
+    if not fmllr.is_contiguous():
+        raise _lib.MfaHipError("features: fMLLR transforms must be contiguous")
+    u2s = None if utt2spk is None else np.asarray(utt2spk)
+    if u2s is not None and u2s.size and int(u2s.min()) < 0:
+        raise _lib.MfaHipError("features: negative speaker row in utt2spk")
+    need = 1 if u2s is None or u2s.size == 0 else int(u2s.max()) + 1
+    if fmllr.shape[0] < need:
+        raise _lib.MfaHipError(f"features: {fmllr.shape[0]} fMLLR transforms for speaker rows up to {need - 1}")
+    if not fmllr.is_cuda:
+        raise _lib.MfaHipError("features: fMLLR transforms must be on the device")
 
 
 def fmllr_statistics(engine: "AlignmentEngine", feats: torch.Tensor, frame_off: np.ndarray, ali: torch.Tensor,

@@ -189,6 +189,9 @@ class FeatureArchive:
         self._cmvn = self._read_table(cmvn_file_name)
         self._trans = self._read_table(transform_file_name)
         self._lda = None if lda_mat_file_name is None else kaldi_io.read_matrix_file(Path(lda_mat_file_name).read_bytes())
+        if self._trans is not None and self._lda is None and not self.use_deltas:
+            # CMVN-only features are not final features: the reference transforms after the deltas or the LDA (MFA/db.py:2101-2136)
+            raise NotImplementedError("transform_file_name needs deltas=True or an LDA matrix: nothing here applies it to CMVN-only features")
 
     @staticmethod
     def _read_map(m):
@@ -232,8 +235,8 @@ class FeatureArchive:
                 cm = torch.from_numpy(st).to(eng.device)
             lda = None if self._lda is None else torch.from_numpy(self._lda.astype(np.float32)).to(eng.device)
             fm = None
-            if self._trans is not None and lda is not None:
-                R = lda.shape[0]
+            if self._trans is not None and (lda is not None or self.use_deltas):
+                R = lda.shape[0] if lda is not None else 3 * dim   # the transform follows the LDA or the deltas
                 ft = np.tile(np.eye(R, R + 1, dtype=np.float32), (len(ids), 1, 1))
                 for s, i in ids.items():
                     if s in self._trans:
@@ -307,7 +310,8 @@ class Utterance:
 
     def generate_features(self, mfcc_computer: MfccComputer, pitch_computer=None, lda_mat: Optional[np.ndarray] = None,
                           fmllr_trans: Optional[np.ndarray] = None, splice_context: int = 3) -> np.ndarray:
-        """CMVN → Δ+ΔΔ, or splice+LDA (→ fMLLR) when ``lda_mat`` is given (MFA/alignment/multiprocessing.py:1287-1304)."""
+        """CMVN → Δ+ΔΔ, or splice+LDA when ``lda_mat`` is given, then fMLLR when there is a transform
+        (MFA/alignment/multiprocessing.py:1287-1304)."""
         import torch
 
         if pitch_computer is not None:
@@ -323,8 +327,6 @@ class Utterance:
         lda = None if lda_mat is None else torch.from_numpy(np.asarray(lda_mat, dtype=np.float32)).to(dev)
         fm = fmllr_trans if fmllr_trans is not None else self.fmllr
         fm = None if fm is None else torch.from_numpy(np.asarray(fm, dtype=np.float32)[None].copy()).to(dev)
-        if fm is not None and lda is None:
-            raise NotImplementedError("fMLLR without LDA is not supported by the feature kernel")
         return eng.features(d, frame_off, u2s, cm, lda=lda, fmllr=fm, splice_context=splice_context).cpu().numpy()
 
 

@@ -1,6 +1,6 @@
 """Randomised check of the front end against the oracle: MFCC (random utterance lengths around every framing boundary, odd
 sample offsets inside the batch buffer, silence, DC offsets, clipping, both snip_edges settings), per-speaker CMVN, the
-delta and the splice+LDA+fMLLR feature kernels.  GPU.  python tools/frontend_fuzz.py [n_seeds] [first_seed]"""
+delta, delta+fMLLR and splice+LDA+fMLLR feature kernels.  GPU.  python tools/frontend_fuzz.py [n_seeds] [first_seed]"""
 import sys
 sys.path.insert(0, ".")
 import numpy as np
@@ -9,12 +9,14 @@ import synth_workload as synth
 from montreal_forced_aligner_amd.engine import AlignmentEngine
 from oracle import oracle as O
 from tests import helpers
+from tests.delta_fmllr_helpers import seeded_delta_fmllr
 
 n_seeds = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 eng = AlignmentEngine(0)
 lda = synth.seeded_lda()
 fm = synth.seeded_fmllr(16)
+fm_delta = seeded_delta_fmllr(16)                                  # 39×40: the transforms of the Δ+ΔΔ path
 bad = 0
 for seed in range(seed0, seed0 + n_seeds):
     case = helpers.frontend_fuzz_case(seed)
@@ -49,9 +51,10 @@ for seed in range(seed0, seed0 + n_seeds):
                 assert np.allclose(st[s_], ref_st, rtol=1e-12, atol=1e-9), ("cmvn", s_)
         d_mfcc = torch.from_numpy(out).to(eng.device)
         f_delta = eng.features(d_mfcc, fo, rows, stats).cpu().numpy()
+        f_dfm = eng.features(d_mfcc, fo, rows, stats, fmllr=torch.from_numpy(fm_delta[:n_spk]).to(eng.device)).cpu().numpy()
         spk_fm = torch.from_numpy(fm[:n_spk]).to(eng.device)       # one transform per speaker row
         f_lda = eng.features(d_mfcc, fo, rows, stats, lda=torch.from_numpy(lda).to(eng.device), fmllr=spk_fm).cpu().numpy()
-        wd = wl = 0.0
+        wd = wf = wl = 0.0
         for u in range(n):
             if mf[u].shape[0] == 0:
                 continue
@@ -59,9 +62,10 @@ for seed in range(seed0, seed0 + n_seeds):
             rd = O.deltas(base)
             rl = O.affine(O.affine(O.splice(base), lda), fm[rows[u]])
             wd = max(wd, float(np.abs(f_delta[fo[u]: fo[u + 1]] - rd).max()))
+            wf = max(wf, float(np.abs(f_dfm[fo[u]: fo[u + 1]] - O.affine(rd, fm_delta[rows[u]])).max()))
             wl = max(wl, float(np.abs(f_lda[fo[u]: fo[u + 1]] - rl).max()))
-        assert wd < 1e-3 and wl < 1e-3, ("features", wd, wl)
-        print(seed, f"snip_edges {snip}, {n} utterances, mfcc worst {worst:.2e}, deltas {wd:.1e}, lda+fmllr {wl:.1e}", flush=True)
+        assert wd < 1e-3 and wf < 1e-3 and wl < 1e-3, ("features", wd, wf, wl)
+        print(seed, f"snip_edges {snip}, {n} utterances, mfcc worst {worst:.2e}, deltas {wd:.1e}, deltas+fmllr {wf:.1e}, lda+fmllr {wl:.1e}", flush=True)
     except AssertionError as e:
         bad += 1
         print(seed, "MISMATCH", str(e)[:300], flush=True)
