@@ -129,6 +129,26 @@ inline bool mfa_debug_sync_enabled() {
     }                                                                                                     \
   } while (0)
 
+// Workgroups of a strided launch: the list passes' scoring launches and the redo sweeps walk their items on a small fixed
+// grid (gmm_band_kernel<…, true>, gmm_band_f32_strided_kernel).  Four workgroups per CU: two rounds of what a CU holds of
+// the band kernel (two workgroups at its 256 VGPRs), so that a wavefront which meets real work holds up one item of the
+// walk, not a whole share of it — and still 64 times fewer workgroups than a list launch over a batch of 8 192 had.  A
+// launch never gets more workgroups than its full grid would have.  MFA_LIST_GRID=<workgroups> overrides (tests: 1 or 3
+// make every wavefront walk many items); launches over a grouped plan round up to a multiple of its runs, so there every
+// value up to the run count gives one workgroup per run.  Read at every call, as MFA_GMM_BF16 / MFA_GMM_F16 are (tests
+// flip it inside one process).  Returns 0 when the device cannot be queried.
+inline int mfa_list_grid(mfa_ctx *c) {
+  const char *e = getenv("MFA_LIST_GRID");
+  const int forced = e ? atoi(e) : 0;
+  if (forced > 0) return forced;
+  if (c->num_cus <= 0) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return 0;
+    c->num_cus = prop.multiProcessorCount;
+  }
+  return 4 * c->num_cus;
+}
+
 // Scoped per-kernel timing (HIP events on the ctx stream, resolved lazily).
 struct KernelTimer {
   mfa_ctx *c; int which; hipEvent_t a = nullptr, b = nullptr;

@@ -1254,6 +1254,23 @@ __global__ __launch_bounds__(256, 2) void gmm_band_f32_kernel(GmmParams p) {
   score_tile<M8, 2>(p, utt, band_t_begin(p, utt) + 64 * r, lane, stage_all[wave], 0);
 }
 
+// The list passes' launch of the same walk: a small fixed grid, every wavefront taking the items first, first + stride, …
+// (band_walk) — a list holds a handful of utterances, a full grid one wavefront per sub-tile of the whole batch.
+template <int M8>
+__global__ __launch_bounds__(256, 2) void gmm_band_f32_strided_kernel(GmmParams p) {
+  __shared__ float stage_all[4][64 * 33];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const BandWalk w = band_walk(p, wave, false);
+  for (int witem = w.first; witem < w.n_witems; witem += w.stride) {
+    int utt, r;
+    if (!band_witem(p, witem, utt, r)) continue;
+    score_tile<M8, 2>(p, utt, band_t_begin(p, utt) + 64 * r, lane, stage_all[wave], 0);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");         // the stage goes to the next item
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+}
+
 // max over the batch of the pdfs' first possible frames → *max_ff (the persistent kernel derives its phase split from it)
 __global__ void gmm_max_first_frame_kernel(const int32_t *first_frame, const int64_t *pdf_off, int n_utt, int *out) {
   const int64_t n = pdf_off[n_utt];
@@ -1640,7 +1657,10 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *c, const float *d_feats, const int64_t 
 
 }  // extern "C"
 
-void mfa_gmm_launch_band_f32(mfa_ctx *c, const void *params, dim3 grid) {
+void mfa_gmm_launch_band_f32(mfa_ctx *c, const void *params, dim3 grid, bool strided) {
   const GmmParams &p = *static_cast<const GmmParams *>(params);
-  gmm_with_steps(c->kpad, [&](auto steps) { hipLaunchKernelGGL((gmm_band_f32_kernel<2 * steps()>), grid, dim3(256), 0, c->stream, p); });
+  gmm_with_steps(c->kpad, [&](auto steps) {
+    if (strided) hipLaunchKernelGGL((gmm_band_f32_strided_kernel<2 * steps()>), grid, dim3(256), 0, c->stream, p);
+    else hipLaunchKernelGGL((gmm_band_f32_kernel<2 * steps()>), grid, dim3(256), 0, c->stream, p);
+  });
 }

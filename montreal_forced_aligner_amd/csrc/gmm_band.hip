@@ -171,7 +171,14 @@ struct BandStamps {
 #endif
 
 // The band kernel: see the head of this file.  One wavefront per (utterance, 64-frame sub-tile[, run of class 0 | chunk]).
-template <int kSteps, int kPieces>
+// kStrided = false, the per-window launches of the first tier: a full grid, the wavefront's one item follows from its
+// workgroup (band_item).  kStrided = true, every scoring launch of a list pass and every window's bf16×3 redo sweep —
+// launches that find work for a handful of wavefronts, or for none: a small fixed grid (mfa_list_grid) whose wavefronts
+// walk the items first, first + stride, … (band_walk).  A full grid there is workgroups that claim four wavefronts of
+// ≈200 VGPRs and 33 KB of LDS to read one word and leave.  Same items, same arithmetic; the wavefront's stage passes from
+// one item to the next behind the flush's wavefront-scope fences.  The body is one `do` block, left with `continue`:
+// for kStrided = false it runs once and compiles to the code the kernel had before it could walk.
+template <int kSteps, int kPieces, bool kStrided = false>
 __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
   constexpr bool kHalf = kPieces == 2;
   using op8 = std::conditional_t<kHalf, f16x8, bf16x8>;
@@ -179,403 +186,430 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
   __shared__ float stage_all[4][64 * 33];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float *stage = stage_all[wave];
-  const int grp = p.b_split ? band_split_block(p).y : 0;                          // the run of class 0 this wavefront scores
-  BandStamps stamps;
-  stamps.mark(0);
-  int utt, r, chunk = 0;
-  if (!band_item(p, wave, utt, r, &chunk)) return;
-  const int64_t f0 = p.frame_off[utt];
-  const int T = (int)(p.frame_off[utt + 1] - f0);
-  const int t_base = band_t_begin(p, utt) + 64 * r;
-  if (t_base >= T) return;
-  int *redo_flag = p.redo + ((size_t)utt * p.b_sub + r) * p.b_nchunk + chunk;
-  if (!kHalf && p.redo_mode == 2 && *redo_flag == 0) return;          // only what the f16 pass declined
-  const int col = lane & 31, h = lane >> 5;
-  const int64_t l0 = p.pdf_off[utt];
-  const int P = (int)(p.pdf_off[utt + 1] - l0);
-  const int32_t *list = p.pdf_list + l0;
-  const int32_t *cc6 = p.class_counts + (size_t)utt * 6;
-  // The pre-split operands depend on nothing but the sub-tile: requested first, they travel while the band is looked up
-  // (volatile: the loads stay here instead of sinking below the early exit).
-  op8 b[2][kSteps][kPieces];
-  bool bad = false;
-  const bool presplit = kHalf && p.xsplit != nullptr;
-  if (presplit) {
-    const int64_t ti = xsplit_tile_index(f0, utt, t_base >> 6);
-    const uint4 *src = p.xsplit + ti * (2 * kSteps * 2 * 64) + lane;
-#pragma unroll
-    for (int n = 0; n < 2; n++)
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++)
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) {
-          // (measured: non-temporal loads here keep more of the model in L2 — FETCH_SIZE 30 → 24.5 GB per step — but the
-          // kernel is 3 % slower, the throughput unchanged)
-          uint4 v;
-          const volatile uint4 *a4 = src + ((n * kSteps + s_) * 2 + (q & 1)) * 64;
-          v.x = a4->x; v.y = a4->y; v.z = a4->z; v.w = a4->w;
-          b[n][s_][q] = __builtin_bit_cast(op8, v);
-        }
-    bad = p.xsplit_bad[ti] != 0;
-  }
-  // band range [lo, hi) of every class this kernel scores: 0 (one 32-row block per pdf), 1 (several blocks per pdf) and 2, 3, 4
-  // (16-, 8-, 4-row slots); class 5 (single Gaussians) is the f32 band kernel's
-  int lo_c[5], hi_c[5], base_c[5];
-  {   // looked up once per utterance and window by gmm_band_ranges_kernel
-    const int32_t *rg = p.ranges + (size_t)utt * kRangeSlots * 2;
-    int off = 0;
-#pragma unroll
-    for (int cls = 0; cls < 5; cls++) {
-      const int slot = cls == 0 ? grp : (cls == 1 ? kRunSlots + 3 : kRunSlots + cls - 2);
-      base_c[cls] = off; off += cc6[cls];
-      lo_c[cls] = rg[2 * slot]; hi_c[cls] = rg[2 * slot + 1];
+  BandWalk walk = {0, 0, 0, 0};
+  if constexpr (kStrided) walk = band_walk(p, wave, true);
+  const int grp = kStrided ? walk.grp : (p.b_split ? band_split_block(p).y : 0);   // the run of class 0 this wavefront scores
+  // The walk.  A redo sweep without a list (utterance = item: the item's flag is redo[witem]) reads the flags of 64 items
+  // at a time, one per lane, and visits only the flagged ones — one memory trip per 64 items instead of three dependent
+  // ones per item (done word, frame offsets, flag).  A visited item still passes every exit below, its flag among them.
+  const bool sweep = kStrided && !kHalf && p.redo_mode == 2 && p.b_utt_list == nullptr;
+  int witem = walk.first - walk.stride, blk = (walk.first - walk.stride) * 64;
+  unsigned long long flagged = 0ull;
+  auto next_item = [&]() -> bool {
+    if (!sweep) { witem += walk.stride; return witem < walk.n_witems; }
+    while (flagged == 0ull) {
+      blk += walk.stride * 64;
+      if (blk >= walk.n_witems) return false;
+      flagged = __ballot(blk + lane < walk.n_witems && p.redo[blk + lane] != 0);
     }
-  }
-  if (p.b_chunk > 0) {                                 // list passes: this wavefront's share of the band (class 0 in chunks,
-    lo_c[0] += chunk * p.b_chunk;                      // the small-slot classes with chunk 0)
-    hi_c[0] = min(hi_c[0], lo_c[0] + p.b_chunk);
-    if (chunk != 0) { hi_c[2] = lo_c[2]; hi_c[3] = lo_c[3]; hi_c[4] = lo_c[4]; }
-  }
-  if (p.b_split) {
-    // the small-slot classes have no runs: the virtual blocks (32 / slot pdfs each) of their three bands, laid end to end,
-    // are cut into `groups` pieces, one per wavefront of the sub-tile — all of them on run 0's wavefront would be all of
-    // them on one XCD, and a piece of every class on every wavefront (the first version) was three pipelines to fill and
-    // drain per wavefront, three or four blocks each: a piece now lies inside one class, rarely two
-    int nb_c[5], tot = 0;
+    witem = blk + __ffsll((long long)flagged) - 1;
+    flagged &= flagged - 1ull;
+    return true;
+  };
+  if (kStrided && !next_item()) return;
+  do {
+    BandStamps stamps;
+    stamps.mark(0);
+    int utt, r, chunk = 0;
+    if (!(kStrided ? band_witem(p, witem, utt, r, &chunk) : band_item(p, wave, utt, r, &chunk))) continue;
+    const int64_t f0 = p.frame_off[utt];
+    const int T = (int)(p.frame_off[utt + 1] - f0);
+    const int t_base = band_t_begin(p, utt) + 64 * r;
+    if (t_base >= T) continue;
+    int *redo_flag = p.redo + ((size_t)utt * p.b_sub + r) * p.b_nchunk + chunk;
+    if (!kHalf && p.redo_mode == 2 && *redo_flag == 0) continue;        // only what the f16 pass declined
+    const int col = lane & 31, h = lane >> 5;
+    const int64_t l0 = p.pdf_off[utt];
+    const int P = (int)(p.pdf_off[utt + 1] - l0);
+    const int32_t *list = p.pdf_list + l0;
+    const int32_t *cc6 = p.class_counts + (size_t)utt * 6;
+    // The pre-split operands depend on nothing but the sub-tile: requested first, they travel while the band is looked up
+    // (volatile: the loads stay here instead of sinking below the early exit).
+    op8 b[2][kSteps][kPieces];
+    bool bad = false;
+    const bool presplit = kHalf && p.xsplit != nullptr;
+    if (presplit) {
+      const int64_t ti = xsplit_tile_index(f0, utt, t_base >> 6);
+      const uint4 *src = p.xsplit + ti * (2 * kSteps * 2 * 64) + lane;
 #pragma unroll
-    for (int cls = 2; cls < 5; cls++) {
-      const int kp = cls == 2 ? 2 : (cls == 3 ? 4 : 8);
-      nb_c[cls] = (hi_c[cls] + kp - 1) / kp - lo_c[cls] / kp;
-      if (lo_c[cls] >= hi_c[cls]) nb_c[cls] = 0;
-      tot += nb_c[cls];
-    }
-    const int per = (tot + p.groups - 1) / p.groups;
-    const int w0 = grp * per, w1 = min(tot, w0 + per);
-    int pos = 0;
+      for (int n = 0; n < 2; n++)
 #pragma unroll
-    for (int cls = 2; cls < 5; cls++) {
-      const int kp = cls == 2 ? 2 : (cls == 3 ? 4 : 8);
-      const int jb0 = lo_c[cls] / kp;
-      const int a = jb0 + max(w0 - pos, 0), b = jb0 + min(w1 - pos, nb_c[cls]);
-      pos += nb_c[cls];
-      if (a >= b) hi_c[cls] = lo_c[cls];
-      else { lo_c[cls] = max(lo_c[cls], a * kp); hi_c[cls] = min(hi_c[cls], b * kp); }
+        for (int s_ = 0; s_ < kSteps; s_++)
+#pragma unroll
+          for (int q = 0; q < kPieces; q++) {
+            // (measured: non-temporal loads here keep more of the model in L2 — FETCH_SIZE 30 → 24.5 GB per step — but the
+            // kernel is 3 % slower, the throughput unchanged)
+            uint4 v;
+            const volatile uint4 *a4 = src + ((n * kSteps + s_) * 2 + (q & 1)) * 64;
+            v.x = a4->x; v.y = a4->y; v.z = a4->z; v.w = a4->w;
+            b[n][s_][q] = __builtin_bit_cast(op8, v);
+          }
+      bad = p.xsplit_bad[ti] != 0;
     }
-  }
-  // class 1 (pdfs of more than 32 Gaussians, few): its band's columns go round the sub-tile's wavefronts one by one
-  const int step1 = p.b_split ? p.groups : (p.b_chunk > 0 ? p.b_nchunk : 1);
-  const int first1 = lo_c[1] + (p.b_split ? grp : (p.b_chunk > 0 ? chunk : 0));
-  const int lo = lo_c[0], hi = hi_c[0];
-  if (lo >= hi && first1 >= hi_c[1] && lo_c[2] >= hi_c[2] && lo_c[3] >= hi_c[3] && lo_c[4] >= hi_c[4]) {
-    if (kHalf && lane == 0) *redo_flag = 0;
-    return;
-  }
-  stamps.mark(1);
-  if (!presplit) bad = split_features<kSteps, kPieces>(p, f0, T, t_base, col, h, b);
-  stamps.mark_loads_landed(2);
-  if constexpr (kHalf) {
-    const bool any_bad = __ballot(bad) != 0ull;
-    if (lane == 0) *redo_flag = any_bad ? 1 : 0;
-    if (any_bad) return;                                               // a scaled feature left the f16 range: bf16×3 pass
-  }
-  const float inv_s = kHalf ? p.acc_scale_inv : 1.0f;
-  const float l2e_s = 1.44269504088896341f * inv_s;
-  float *out = p.out + p.ll_off[utt];
-  constexpr int kProd = kHalf ? 3 : 6;
-  constexpr int pa[6] = {kHalf ? 1 : 2, kHalf ? 0 : 1, 0, 1, 0, 0}, pb[6] = {0, 1, kHalf ? 0 : 2, 0, 1, 0};
-  // `cnt` staged columns, the first of them score column c0 of the utterance's matrix → HBM as 128-byte row segments
-  auto flush_cols = [&](int c0, int cnt) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // band range [lo, hi) of every class this kernel scores: 0 (one 32-row block per pdf), 1 (several blocks per pdf) and 2, 3, 4
+    // (16-, 8-, 4-row slots); class 5 (single Gaussians) is the f32 band kernel's
+    int lo_c[5], hi_c[5], base_c[5];
+    {   // looked up once per utterance and window by gmm_band_ranges_kernel
+      const int32_t *rg = p.ranges + (size_t)utt * kRangeSlots * 2;
+      int off = 0;
+#pragma unroll
+      for (int cls = 0; cls < 5; cls++) {
+        const int slot = cls == 0 ? grp : (cls == 1 ? kRunSlots + 3 : kRunSlots + cls - 2);
+        base_c[cls] = off; off += cc6[cls];
+        lo_c[cls] = rg[2 * slot]; hi_c[cls] = rg[2 * slot + 1];
+      }
+    }
+    if (p.b_chunk > 0) {                                 // list passes: this wavefront's share of the band (class 0 in chunks,
+      lo_c[0] += chunk * p.b_chunk;                      // the small-slot classes with chunk 0)
+      hi_c[0] = min(hi_c[0], lo_c[0] + p.b_chunk);
+      if (chunk != 0) { hi_c[2] = lo_c[2]; hi_c[3] = lo_c[3]; hi_c[4] = lo_c[4]; }
+    }
+    if (p.b_split) {
+      // the small-slot classes have no runs: the virtual blocks (32 / slot pdfs each) of their three bands, laid end to end,
+      // are cut into `groups` pieces, one per wavefront of the sub-tile — all of them on run 0's wavefront would be all of
+      // them on one XCD, and a piece of every class on every wavefront (the first version) was three pipelines to fill and
+      // drain per wavefront, three or four blocks each: a piece now lies inside one class, rarely two
+      int nb_c[5], tot = 0;
+#pragma unroll
+      for (int cls = 2; cls < 5; cls++) {
+        const int kp = cls == 2 ? 2 : (cls == 3 ? 4 : 8);
+        nb_c[cls] = (hi_c[cls] + kp - 1) / kp - lo_c[cls] / kp;
+        if (lo_c[cls] >= hi_c[cls]) nb_c[cls] = 0;
+        tot += nb_c[cls];
+      }
+      const int per = (tot + p.groups - 1) / p.groups;
+      const int w0 = grp * per, w1 = min(tot, w0 + per);
+      int pos = 0;
+#pragma unroll
+      for (int cls = 2; cls < 5; cls++) {
+        const int kp = cls == 2 ? 2 : (cls == 3 ? 4 : 8);
+        const int jb0 = lo_c[cls] / kp;
+        const int a = jb0 + max(w0 - pos, 0), b = jb0 + min(w1 - pos, nb_c[cls]);
+        pos += nb_c[cls];
+        if (a >= b) hi_c[cls] = lo_c[cls];
+        else { lo_c[cls] = max(lo_c[cls], a * kp); hi_c[cls] = min(hi_c[cls], b * kp); }
+      }
+    }
+    // class 1 (pdfs of more than 32 Gaussians, few): its band's columns go round the sub-tile's wavefronts one by one
+    const int step1 = p.b_split ? p.groups : (p.b_chunk > 0 ? p.b_nchunk : 1);
+    const int first1 = lo_c[1] + (p.b_split ? grp : (p.b_chunk > 0 ? chunk : 0));
+    const int lo = lo_c[0], hi = hi_c[0];
+    if (lo >= hi && first1 >= hi_c[1] && lo_c[2] >= hi_c[2] && lo_c[3] >= hi_c[3] && lo_c[4] >= hi_c[4]) {
+      if (kHalf && lane == 0) *redo_flag = 0;
+      continue;
+    }
+    stamps.mark(1);
+    if (!presplit) bad = split_features<kSteps, kPieces>(p, f0, T, t_base, col, h, b);
+    stamps.mark_loads_landed(2);
+    if constexpr (kHalf) {
+      const bool any_bad = __ballot(bad) != 0ull;
+      if (lane == 0) *redo_flag = any_bad ? 1 : 0;
+      if (any_bad) continue;                                             // a scaled feature left the f16 range: bf16×3 pass
+    }
+    const float inv_s = kHalf ? p.acc_scale_inv : 1.0f;
+    const float l2e_s = 1.44269504088896341f * inv_s;
+    float *out = p.out + p.ll_off[utt];
+    constexpr int kProd = kHalf ? 3 : 6;
+    constexpr int pa[6] = {kHalf ? 1 : 2, kHalf ? 0 : 1, 0, 1, 0, 0}, pb[6] = {0, 1, kHalf ? 0 : 2, 0, 1, 0};
+    // `cnt` staged columns, the first of them score column c0 of the utterance's matrix → HBM as 128-byte row segments
+    auto flush_cols = [&](int c0, int cnt) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll 4
-    for (int i = 0; i < 32; i++) {
-      const int rr = h + 2 * i, t = t_base + rr;
-      if (col < cnt && t < T) __builtin_nontemporal_store(stage[rr * 33 + col], &out[(size_t)t * P + c0 + col]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  };
-
-  // ---------------------------------------------------------------- class 0: one pdf per 32-row block
-  if (lo < hi) {
-    const uint4 *wsrc = (kHalf ? p.wh : p.wb) + lane;
-    const float *gsrc = (kHalf ? p.gch : p.gc) + 4 * h;
-    const int last = hi - 1;
-    // First model row per column, precomputed per batch: ONE load.  The pdf id → row chain it replaces (row0[list[j]]) made
-    // the second load wait for the first — the youngest entry of the in-order vmcnt queue — i.e. drained every outstanding
-    // operand load of the next block at the top of each block.
-    const int32_t *crow = p.col_row0 + l0;
-    auto row0_at = [&](int jj) { return crow[min(jj, last)]; };
-    auto block_at = [&](int jj) {
-      const int blk = __builtin_amdgcn_readfirstlane(row0_at(jj)) >> 5;
-      return blk;
+      for (int i = 0; i < 32; i++) {
+        const int rr = h + 2 * i, t = t_base + rr;
+        if (col < cnt && t < T) __builtin_nontemporal_store(stage[rr * 33 + col], &out[(size_t)t * P + c0 + col]);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
     };
-    op8 a[kSteps][kPieces];
-    f32x4 g[4];
-    {
-      const int blk = block_at(lo);
-      const uint4 *src = wsrc + (size_t)blk * kUnits;
-#pragma unroll
-      for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gsrc + (size_t)blk * 32 + 8 * q);
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++)
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-    }
-    int blk_next = block_at(lo + 1);
-    for (int j = lo; j < hi; j++) {
-      stamps.cycle(0);
-      const int x_next2 = row0_at(j + 2);                      // lookup two blocks ahead (oldest entry of the vmcnt queue)
-      f32x16 init, acc[2];
-#pragma unroll
-      for (int rr = 0; rr < 16; rr++) init[rr] = g[rr >> 2][rr & 3];
-      const uint4 *src = wsrc + (size_t)blk_next * kUnits;
-      const float *gn = gsrc + (size_t)blk_next * 32;
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++) {
-#pragma unroll
-        for (int t6 = 0; t6 < kProd; t6++)
-#pragma unroll
-          for (int n = 0; n < 2; n++) {
-            const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
-            if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-            else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-          }
-        // this step's operand registers (and, after the first step, the gconst registers) are free: next block's rows.
-        // (A second operand set — two blocks in flight per wavefront — was measured: 12.70 vs 12.76 ms per step; the
-        //  kernel is bound by what the fabric delivers, ≈6.5 TB/s of 10 KiB blocks gathered from a 51 MB table.)
-        if (s_ == 0) {
-#pragma unroll
-          for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gn + 8 * q);
-        }
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      stamps.cycle(1);
-      blk_next = __builtin_amdgcn_readfirstlane(x_next2) >> 5;
-      stamps.cycle(2);
-      float mx[2], sum[2];
-#pragma unroll
-      for (int n = 0; n < 2; n++) {
-        float m = reg_max<0, 16>(acc[n]);
-        m = fmaxf(m, swap32(m, h));
-        float sv = reg_expsum_fast(acc[n], m, l2e_s);
-        sv += swap32(sv, h);
-        mx[n] = m; sum[n] = sv;
-      }
-      const int jj = (j - lo) & 31;
-      stage[(32 * h + col) * 33 + jj] = finish((h ? mx[1] : mx[0]) * inv_s, h ? sum[1] : sum[0]);
-      stamps.cycle_lds_landed(3);
-      if (jj == 31 || j == last) flush_cols(j - jj, jj + 1);
-      stamps.cycle(4);
-      stamps.block_done();
-    }
-    stamps.add_block_phases(p, lane == 0 && kHalf);
-  }
 
-  // ---------------------------------------------------------------- class 1: several 32-row blocks per pdf
-  // Online log-sum-exp over the pdf's blocks (running max M and sum S against it, per frame): (M, S) ← (max(M, m_b),
-  // S·2^((M − M')·l2e) + s_b·2^((m_b − M')·l2e)).  Products and per-block reductions are class 0's; pad rows carry gconst
-  // −1e30 and vanish in the sum.  No software pipeline: a trained model has a few such pdfs per band, if any.
-  // Software pipeline as class 0's: the operands of the next block — the pdf's next one, or the first block of this
-  // wavefront's next column — are requested as soon as a step's MFMAs have been issued; the column's (row, blocks) word is
-  // looked up one column ahead.
-  if (first1 < hi_c[1]) {
-    const uint4 *wsrc = (kHalf ? p.wh : p.wb) + lane;
-    const float *gsrc = (kHalf ? p.gch : p.gc) + 4 * h;
-    const int32_t *crow1 = p.col_row0 + l0 + base_c[1];
-    const int last1 = hi_c[1] - 1;
-    auto col_word = [&](int jj) { return crow1[min(jj, last1)]; };     // row | (blocks − 1) when packed
-    auto blocks_of = [&](int word, int jj) {
-      return p.col_nb_packed ? (word & 31) + 1 : __builtin_amdgcn_readfirstlane(p.nblk[list[base_c[1] + min(jj, last1)]]);
-    };
-    int j1 = first1;
-    int word = __builtin_amdgcn_readfirstlane(col_word(j1));
-    int nb = blocks_of(word, j1), blk = word >> 5, bk = 0;
-    int word_n = col_word(j1 + step1);                                 // stays a vector register until its column opens
-    op8 a[kSteps][kPieces];
-    f32x4 g[4];
-    {
-      const uint4 *src = wsrc + (size_t)blk * kUnits;
-#pragma unroll
-      for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gsrc + (size_t)blk * 32 + 8 * q);
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++)
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-    }
-    float M[2] = {0.0f, 0.0f}, S[2] = {0.0f, 0.0f};
-    for (;;) {
-      const bool last_blk = bk + 1 == nb;
-      const bool more_cols = j1 + step1 < hi_c[1];
-      int blk_n = blk + 1;                                             // (past the pdf's last block only when nothing follows:
-      if (last_blk) blk_n = more_cols ? __builtin_amdgcn_readfirstlane(word_n) >> 5 : blk;   //  then the same block again, unused)
-      f32x16 init, acc[2];
-#pragma unroll
-      for (int rr = 0; rr < 16; rr++) init[rr] = g[rr >> 2][rr & 3];
-      const uint4 *src = wsrc + (size_t)blk_n * kUnits;
-      const float *gn = gsrc + (size_t)blk_n * 32;
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++) {
-#pragma unroll
-        for (int t6 = 0; t6 < kProd; t6++)
-#pragma unroll
-          for (int n = 0; n < 2; n++) {
-            const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
-            if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-            else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-          }
-        if (s_ == 0) {
-#pragma unroll
-          for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gn + 8 * q);
-        }
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int n = 0; n < 2; n++) {
-        float m = reg_max<0, 16>(acc[n]);
-        m = fmaxf(m, swap32(m, h));
-        float sv = reg_expsum_fast(acc[n], m, l2e_s);
-        sv += swap32(sv, h);
-        if (bk == 0) { M[n] = m; S[n] = sv; }
-        else {
-          const float mn = fmaxf(M[n], m);
-          S[n] = S[n] * __builtin_amdgcn_exp2f((M[n] - mn) * l2e_s) + sv * __builtin_amdgcn_exp2f((m - mn) * l2e_s);
-          M[n] = mn;
-        }
-      }
-      blk = blk_n;
-      if (!last_blk) { bk++; continue; }
-      const int t = t_base + 32 * h + col;
-      if (t < T) __builtin_nontemporal_store(finish((h ? M[1] : M[0]) * inv_s, h ? S[1] : S[0]), &out[(size_t)t * P + base_c[1] + j1]);
-      if (!more_cols) break;
-      j1 += step1;
-      word = __builtin_amdgcn_readfirstlane(word_n);
-      nb = blocks_of(word, j1); bk = 0;
-      word_n = col_word(j1 + step1);
-    }
-  }
-
-  // ---------------------------------------------------------------- classes 2, 3, 4: 32 / slot pdfs per virtual block
-  // As gmm_split_small_kernel: the pdfs the list puts next to each other are gathered into one 32-row block (lane ↔ row
-  // ρ = lane mod 32 → pdf ρ / slot, its row ρ mod slot; rows past the range come from the model's dummy row), the MFMAs
-  // are those of class 0, the log-sum-exp runs over the slot's rows of each pdf — per pdf the very same expressions, so a
-  // cell scored here carries the dense kernel's bits.  The gather costs nothing extra: every lane loads through its own
-  // row pointer anyway.
-  auto run_small = [&](auto slot_c, int base, int lo_s, int hi_s) {
-    constexpr int kSlot = decltype(slot_c)::value, kPdfs = 32 / kSlot;
-    if (lo_s >= hi_s) return;
-    const uint4 *wsrc = kHalf ? p.wh : p.wb;
-    const float *gsrc = kHalf ? p.gch : p.gc;
-    const int rho = lane & 31, my_k = rho / kSlot, my_r = rho % kSlot;
-    const int jb0 = lo_s / kPdfs, jb1 = (hi_s + kPdfs - 1) / kPdfs;
-    auto row_of = [&](int jb) -> int {                 // this lane's packed row in virtual block jb (two dependent loads)
-      const int idx = min(jb, jb1 - 1) * kPdfs + my_k;
-      return idx < hi_s ? p.col_row0[l0 + base + idx] + my_r : p.num_rows;
-    };
-    auto src_of = [&](int row) { return wsrc + (size_t)(row >> 5) * kUnits + (row & 31) + 32 * h; };
-    op8 a[kSteps][kPieces];
-    int row_cur = row_of(jb0), row_next = row_of(jb0 + 1);
-    float gcv = gsrc[row_cur];
-    {
-      const uint4 *src = src_of(row_cur);
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++)
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-    }
-    const int col0 = base + jb0 * kPdfs;               // score column of the first staged column
-    for (int jb = jb0; jb < jb1; jb++) {
-      const int row_n2 = row_of(jb + 2);               // in flight during this block
-      f32x16 init, acc[2];
-#pragma unroll
-      for (int rr = 0; rr < 16; rr++) init[rr] = __shfl(gcv, acc_row(rr, h));
-      const uint4 *src = src_of(row_next);
-#pragma unroll
-      for (int s_ = 0; s_ < kSteps; s_++) {
-#pragma unroll
-        for (int t6 = 0; t6 < kProd; t6++)
-#pragma unroll
-          for (int n = 0; n < 2; n++) {
-            const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
-            if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-            else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-          }
-        if (s_ == 0) gcv = gsrc[row_next];
-#pragma unroll
-        for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      row_next = row_n2;
-      // per-pdf log-sum-exp.  Accumulator register r of half-wave h is row (r & 3) + 8 (r >> 2) + 4 h of the block.
-      auto group_max = [&](const f32x16 &v, int r0, int cnt) {
-        float m = v[r0];
-#pragma unroll
-        for (int rr = 1; rr < cnt; rr++) m = fmaxf(m, v[r0 + rr]);
-        return m;
+    // ---------------------------------------------------------------- class 0: one pdf per 32-row block
+    if (lo < hi) {
+      const uint4 *wsrc = (kHalf ? p.wh : p.wb) + lane;
+      const float *gsrc = (kHalf ? p.gch : p.gc) + 4 * h;
+      const int last = hi - 1;
+      // First model row per column, precomputed per batch: ONE load.  The pdf id → row chain it replaces (row0[list[j]]) made
+      // the second load wait for the first — the youngest entry of the in-order vmcnt queue — i.e. drained every outstanding
+      // operand load of the next block at the top of each block.
+      const int32_t *crow = p.col_row0 + l0;
+      auto row0_at = [&](int jj) { return crow[min(jj, last)]; };
+      auto block_at = [&](int jj) {
+        const int blk = __builtin_amdgcn_readfirstlane(row0_at(jj)) >> 5;
+        return blk;
       };
-      auto group_expsum = [&](const f32x16 &v, int r0, int cnt, float m) {
-        float e[8];
+      op8 a[kSteps][kPieces];
+      f32x4 g[4];
+      {
+        const int blk = block_at(lo);
+        const uint4 *src = wsrc + (size_t)blk * kUnits;
 #pragma unroll
-        for (int rr = 0; rr < cnt; rr++) e[rr] = __builtin_amdgcn_exp2f((v[r0 + rr] - m) * l2e_s);
+        for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gsrc + (size_t)blk * 32 + 8 * q);
 #pragma unroll
-        for (int w = 1; w < cnt; w <<= 1)
+        for (int s_ = 0; s_ < kSteps; s_++)
 #pragma unroll
-          for (int rr = 0; rr + w < cnt; rr += 2 * w) e[rr] += e[rr + w];
-        return e[0];
+          for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
+      }
+      int blk_next = block_at(lo + 1);
+      for (int j = lo; j < hi; j++) {
+        stamps.cycle(0);
+        const int x_next2 = row0_at(j + 2);                      // lookup two blocks ahead (oldest entry of the vmcnt queue)
+        f32x16 init, acc[2];
+#pragma unroll
+        for (int rr = 0; rr < 16; rr++) init[rr] = g[rr >> 2][rr & 3];
+        const uint4 *src = wsrc + (size_t)blk_next * kUnits;
+        const float *gn = gsrc + (size_t)blk_next * 32;
+#pragma unroll
+        for (int s_ = 0; s_ < kSteps; s_++) {
+#pragma unroll
+          for (int t6 = 0; t6 < kProd; t6++)
+#pragma unroll
+            for (int n = 0; n < 2; n++) {
+              const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
+              if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
+              else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
+            }
+          // this step's operand registers (and, after the first step, the gconst registers) are free: next block's rows.
+          // (A second operand set — two blocks in flight per wavefront — was measured: 12.70 vs 12.76 ms per step; the
+          //  kernel is bound by what the fabric delivers, ≈6.5 TB/s of 10 KiB blocks gathered from a 51 MB table.)
+          if (s_ == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gn + 8 * q);
+          }
+#pragma unroll
+          for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        stamps.cycle(1);
+        blk_next = __builtin_amdgcn_readfirstlane(x_next2) >> 5;
+        stamps.cycle(2);
+        float mx[2], sum[2];
+#pragma unroll
+        for (int n = 0; n < 2; n++) {
+          float m = reg_max<0, 16>(acc[n]);
+          m = fmaxf(m, swap32(m, h));
+          float sv = reg_expsum_fast(acc[n], m, l2e_s);
+          sv += swap32(sv, h);
+          mx[n] = m; sum[n] = sv;
+        }
+        const int jj = (j - lo) & 31;
+        stage[(32 * h + col) * 33 + jj] = finish((h ? mx[1] : mx[0]) * inv_s, h ? sum[1] : sum[0]);
+        stamps.cycle_lds_landed(3);
+        if (jj == 31 || j == last) flush_cols(j - jj, jj + 1);
+        stamps.cycle(4);
+        stamps.block_done();
+      }
+      stamps.add_block_phases(p, lane == 0 && kHalf);
+    }
+
+    // ---------------------------------------------------------------- class 1: several 32-row blocks per pdf
+    // Online log-sum-exp over the pdf's blocks (running max M and sum S against it, per frame): (M, S) ← (max(M, m_b),
+    // S·2^((M − M')·l2e) + s_b·2^((m_b − M')·l2e)).  Products and per-block reductions are class 0's; pad rows carry gconst
+    // −1e30 and vanish in the sum.  No software pipeline: a trained model has a few such pdfs per band, if any.
+    // Software pipeline as class 0's: the operands of the next block — the pdf's next one, or the first block of this
+    // wavefront's next column — are requested as soon as a step's MFMAs have been issued; the column's (row, blocks) word is
+    // looked up one column ahead.
+    if (first1 < hi_c[1]) {
+      const uint4 *wsrc = (kHalf ? p.wh : p.wb) + lane;
+      const float *gsrc = (kHalf ? p.gch : p.gc) + 4 * h;
+      const int32_t *crow1 = p.col_row0 + l0 + base_c[1];
+      const int last1 = hi_c[1] - 1;
+      auto col_word = [&](int jj) { return crow1[min(jj, last1)]; };     // row | (blocks − 1) when packed
+      auto blocks_of = [&](int word, int jj) {
+        return p.col_nb_packed ? (word & 31) + 1 : __builtin_amdgcn_readfirstlane(p.nblk[list[base_c[1] + min(jj, last1)]]);
       };
-      const int colbase = ((jb - jb0) * kPdfs) & 31;   // first staging column of this block
+      int j1 = first1;
+      int word = __builtin_amdgcn_readfirstlane(col_word(j1));
+      int nb = blocks_of(word, j1), blk = word >> 5, bk = 0;
+      int word_n = col_word(j1 + step1);                                 // stays a vector register until its column opens
+      op8 a[kSteps][kPieces];
+      f32x4 g[4];
+      {
+        const uint4 *src = wsrc + (size_t)blk * kUnits;
 #pragma unroll
-      for (int n = 0; n < 2; n++) {
-        float *srow = stage + (32 * n + col) * 33 + colbase;
-        if constexpr (kSlot == 16) {                   // pdf k: rows 16k..16k+15 = registers [8k, 8k+8) of both halves
-          float ll[2];
+        for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gsrc + (size_t)blk * 32 + 8 * q);
 #pragma unroll
-          for (int k2 = 0; k2 < 2; k2++) {
-            float m = group_max(acc[n], 8 * k2, 8);
-            m = fmaxf(m, swap32(m, h));
-            float sv = group_expsum(acc[n], 8 * k2, 8, m);
-            sv += swap32(sv, h);
-            ll[k2] = finish(m * inv_s, sv);
+        for (int s_ = 0; s_ < kSteps; s_++)
+#pragma unroll
+          for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
+      }
+      float M[2] = {0.0f, 0.0f}, S[2] = {0.0f, 0.0f};
+      for (;;) {
+        const bool last_blk = bk + 1 == nb;
+        const bool more_cols = j1 + step1 < hi_c[1];
+        int blk_n = blk + 1;                                             // (past the pdf's last block only when nothing follows:
+        if (last_blk) blk_n = more_cols ? __builtin_amdgcn_readfirstlane(word_n) >> 5 : blk;   //  then the same block again, unused)
+        f32x16 init, acc[2];
+#pragma unroll
+        for (int rr = 0; rr < 16; rr++) init[rr] = g[rr >> 2][rr & 3];
+        const uint4 *src = wsrc + (size_t)blk_n * kUnits;
+        const float *gn = gsrc + (size_t)blk_n * 32;
+#pragma unroll
+        for (int s_ = 0; s_ < kSteps; s_++) {
+#pragma unroll
+          for (int t6 = 0; t6 < kProd; t6++)
+#pragma unroll
+            for (int n = 0; n < 2; n++) {
+              const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
+              if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
+              else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
+            }
+          if (s_ == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gn + 8 * q);
           }
-          srow[h] = h ? ll[1] : ll[0];
-        } else if constexpr (kSlot == 8) {             // pdf k: rows 8k..8k+7 = registers [4k, 4k+4) of both halves
-          float ll[4];
 #pragma unroll
-          for (int k2 = 0; k2 < 4; k2++) {
-            float m = group_max(acc[n], 4 * k2, 4);
-            m = fmaxf(m, swap32(m, h));
-            float sv = group_expsum(acc[n], 4 * k2, 4, m);
-            sv += swap32(sv, h);
-            ll[k2] = finish(m * inv_s, sv);
-          }
-          srow[h] = h ? ll[1] : ll[0];
-          srow[2 + h] = h ? ll[3] : ll[2];
-        } else {                                       // slot 4: pdf 2i + h: rows 8i + 4h .. +3 = registers [4i, 4i+4)
+          for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
 #pragma unroll
-          for (int i = 0; i < 4; i++) {
-            const float m = group_max(acc[n], 4 * i, 4);
-            const float sv = group_expsum(acc[n], 4 * i, 4, m);
-            srow[2 * i + h] = finish(m * inv_s, sv);
+        for (int n = 0; n < 2; n++) {
+          float m = reg_max<0, 16>(acc[n]);
+          m = fmaxf(m, swap32(m, h));
+          float sv = reg_expsum_fast(acc[n], m, l2e_s);
+          sv += swap32(sv, h);
+          if (bk == 0) { M[n] = m; S[n] = sv; }
+          else {
+            const float mn = fmaxf(M[n], m);
+            S[n] = S[n] * __builtin_amdgcn_exp2f((M[n] - mn) * l2e_s) + sv * __builtin_amdgcn_exp2f((m - mn) * l2e_s);
+            M[n] = mn;
           }
         }
-      }
-      const int done = (jb - jb0 + 1) * kPdfs;         // staged columns since col0 (whole blocks)
-      if ((done & 31) == 0 || jb == jb1 - 1) {
-        const int first = (done - 1) & ~31;            // first staged column of the open window
-        const int valid = min(done, hi_s - jb0 * kPdfs) - first;   // columns of pdfs inside the class's range
-        flush_cols(col0 + first, valid);
+        blk = blk_n;
+        if (!last_blk) { bk++; continue; }
+        const int t = t_base + 32 * h + col;
+        if (t < T) __builtin_nontemporal_store(finish((h ? M[1] : M[0]) * inv_s, h ? S[1] : S[0]), &out[(size_t)t * P + base_c[1] + j1]);
+        if (!more_cols) break;
+        j1 += step1;
+        word = __builtin_amdgcn_readfirstlane(word_n);
+        nb = blocks_of(word, j1); bk = 0;
+        word_n = col_word(j1 + step1);
       }
     }
-  };
-  run_small(std::integral_constant<int, 16>{}, base_c[2], lo_c[2], hi_c[2]);
-  run_small(std::integral_constant<int, 8>{}, base_c[3], lo_c[3], hi_c[3]);
-  run_small(std::integral_constant<int, 4>{}, base_c[4], lo_c[4], hi_c[4]);
-  stamps.add_kernel_phases(p, lane == 0 && kHalf, hi - lo);
+
+    // ---------------------------------------------------------------- classes 2, 3, 4: 32 / slot pdfs per virtual block
+    // As gmm_split_small_kernel: the pdfs the list puts next to each other are gathered into one 32-row block (lane ↔ row
+    // ρ = lane mod 32 → pdf ρ / slot, its row ρ mod slot; rows past the range come from the model's dummy row), the MFMAs
+    // are those of class 0, the log-sum-exp runs over the slot's rows of each pdf — per pdf the very same expressions, so a
+    // cell scored here carries the dense kernel's bits.  The gather costs nothing extra: every lane loads through its own
+    // row pointer anyway.
+    auto run_small = [&](auto slot_c, int base, int lo_s, int hi_s) {
+      constexpr int kSlot = decltype(slot_c)::value, kPdfs = 32 / kSlot;
+      if (lo_s >= hi_s) return;
+      const uint4 *wsrc = kHalf ? p.wh : p.wb;
+      const float *gsrc = kHalf ? p.gch : p.gc;
+      const int rho = lane & 31, my_k = rho / kSlot, my_r = rho % kSlot;
+      const int jb0 = lo_s / kPdfs, jb1 = (hi_s + kPdfs - 1) / kPdfs;
+      auto row_of = [&](int jb) -> int {                 // this lane's packed row in virtual block jb (two dependent loads)
+        const int idx = min(jb, jb1 - 1) * kPdfs + my_k;
+        return idx < hi_s ? p.col_row0[l0 + base + idx] + my_r : p.num_rows;
+      };
+      auto src_of = [&](int row) { return wsrc + (size_t)(row >> 5) * kUnits + (row & 31) + 32 * h; };
+      op8 a[kSteps][kPieces];
+      int row_cur = row_of(jb0), row_next = row_of(jb0 + 1);
+      float gcv = gsrc[row_cur];
+      {
+        const uint4 *src = src_of(row_cur);
+#pragma unroll
+        for (int s_ = 0; s_ < kSteps; s_++)
+#pragma unroll
+          for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
+      }
+      const int col0 = base + jb0 * kPdfs;               // score column of the first staged column
+      for (int jb = jb0; jb < jb1; jb++) {
+        const int row_n2 = row_of(jb + 2);               // in flight during this block
+        f32x16 init, acc[2];
+#pragma unroll
+        for (int rr = 0; rr < 16; rr++) init[rr] = __shfl(gcv, acc_row(rr, h));
+        const uint4 *src = src_of(row_next);
+#pragma unroll
+        for (int s_ = 0; s_ < kSteps; s_++) {
+#pragma unroll
+          for (int t6 = 0; t6 < kProd; t6++)
+#pragma unroll
+            for (int n = 0; n < 2; n++) {
+              const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
+              if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
+              else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
+            }
+          if (s_ == 0) gcv = gsrc[row_next];
+#pragma unroll
+          for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        row_next = row_n2;
+        // per-pdf log-sum-exp.  Accumulator register r of half-wave h is row (r & 3) + 8 (r >> 2) + 4 h of the block.
+        auto group_max = [&](const f32x16 &v, int r0, int cnt) {
+          float m = v[r0];
+#pragma unroll
+          for (int rr = 1; rr < cnt; rr++) m = fmaxf(m, v[r0 + rr]);
+          return m;
+        };
+        auto group_expsum = [&](const f32x16 &v, int r0, int cnt, float m) {
+          float e[8];
+#pragma unroll
+          for (int rr = 0; rr < cnt; rr++) e[rr] = __builtin_amdgcn_exp2f((v[r0 + rr] - m) * l2e_s);
+#pragma unroll
+          for (int w = 1; w < cnt; w <<= 1)
+#pragma unroll
+            for (int rr = 0; rr + w < cnt; rr += 2 * w) e[rr] += e[rr + w];
+          return e[0];
+        };
+        const int colbase = ((jb - jb0) * kPdfs) & 31;   // first staging column of this block
+#pragma unroll
+        for (int n = 0; n < 2; n++) {
+          float *srow = stage + (32 * n + col) * 33 + colbase;
+          if constexpr (kSlot == 16) {                   // pdf k: rows 16k..16k+15 = registers [8k, 8k+8) of both halves
+            float ll[2];
+#pragma unroll
+            for (int k2 = 0; k2 < 2; k2++) {
+              float m = group_max(acc[n], 8 * k2, 8);
+              m = fmaxf(m, swap32(m, h));
+              float sv = group_expsum(acc[n], 8 * k2, 8, m);
+              sv += swap32(sv, h);
+              ll[k2] = finish(m * inv_s, sv);
+            }
+            srow[h] = h ? ll[1] : ll[0];
+          } else if constexpr (kSlot == 8) {             // pdf k: rows 8k..8k+7 = registers [4k, 4k+4) of both halves
+            float ll[4];
+#pragma unroll
+            for (int k2 = 0; k2 < 4; k2++) {
+              float m = group_max(acc[n], 4 * k2, 4);
+              m = fmaxf(m, swap32(m, h));
+              float sv = group_expsum(acc[n], 4 * k2, 4, m);
+              sv += swap32(sv, h);
+              ll[k2] = finish(m * inv_s, sv);
+            }
+            srow[h] = h ? ll[1] : ll[0];
+            srow[2 + h] = h ? ll[3] : ll[2];
+          } else {                                       // slot 4: pdf 2i + h: rows 8i + 4h .. +3 = registers [4i, 4i+4)
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+              const float m = group_max(acc[n], 4 * i, 4);
+              const float sv = group_expsum(acc[n], 4 * i, 4, m);
+              srow[2 * i + h] = finish(m * inv_s, sv);
+            }
+          }
+        }
+        const int done = (jb - jb0 + 1) * kPdfs;         // staged columns since col0 (whole blocks)
+        if ((done & 31) == 0 || jb == jb1 - 1) {
+          const int first = (done - 1) & ~31;            // first staged column of the open window
+          const int valid = min(done, hi_s - jb0 * kPdfs) - first;   // columns of pdfs inside the class's range
+          flush_cols(col0 + first, valid);
+        }
+      }
+    };
+    run_small(std::integral_constant<int, 16>{}, base_c[2], lo_c[2], hi_c[2]);
+    run_small(std::integral_constant<int, 8>{}, base_c[3], lo_c[3], hi_c[3]);
+    run_small(std::integral_constant<int, 4>{}, base_c[4], lo_c[4], hi_c[4]);
+    stamps.add_kernel_phases(p, lane == 0 && kHalf, hi - lo);
+    if constexpr (kStrided) {                            // the stage goes to the wavefront's next item
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+  } while (kStrided && next_item());
 }
 
 }  // namespace
@@ -668,6 +702,15 @@ int mfa_gmm_score_window(mfa_ctx *c, const MfaLazyScoring *lazy, const MfaWindow
   p.b_split = p.groups > 1 ? 1 : 0;
   const dim3 split_grid((unsigned)((split_waves + 3) / 4) * (unsigned)(p.b_split ? p.groups : 1));
   const GmmSplitPasses passes = gmm_split_passes(c);
+  // Launches that find work for a handful of wavefronts or for none — everything a list pass scores, and each window's
+  // redo sweep — walk their items on a small fixed grid (mfa_list_grid) instead of asking for one wavefront per item.
+  const bool list_pass = ws->utt_list != nullptr;
+  const int walk = mfa_list_grid(c);
+  if (walk <= 0) return c->fail("cannot size the list-pass grid: device properties unavailable");
+  const unsigned runs = p.b_split ? (unsigned)p.groups : 1u;
+  const unsigned full_per_run = std::max(1u, (unsigned)((split_waves + 3) / 4));
+  const dim3 walk_grid(std::min(((unsigned)walk + runs - 1) / runs, full_per_run) * runs);
+  const dim3 walk_grid_f32(std::min((unsigned)walk, std::max(1u, grid.x)));
   KernelTimer kt(c, MFA_K_GMM);
   {   // the band's index ranges, once per utterance (instead of once per scoring wavefront)
     const int64_t need = (int64_t)n_utt * kRangeSlots * 2;
@@ -698,16 +741,22 @@ int mfa_gmm_score_window(mfa_ctx *c, const MfaLazyScoring *lazy, const MfaWindow
       p.acc_scale_inv = 1.0f / c->gmm_acc_scale;
       p.redo_mode = 0;
       if (c->xsplit_ready) { p.xsplit = (const uint4 *)c->d_xsplit; p.xsplit_bad = c->d_xsplit_bad; }
-      gmm_with_steps(c->kpad, [&](auto steps) { hipLaunchKernelGGL((gmm_band_kernel<steps(), 2>), split_grid, dim3(256), 0, c->stream, p); });
+      gmm_with_steps(c->kpad, [&](auto steps) {
+        if (list_pass) hipLaunchKernelGGL((gmm_band_kernel<steps(), 2, true>), walk_grid, dim3(256), 0, c->stream, p);
+        else hipLaunchKernelGGL((gmm_band_kernel<steps(), 2>), split_grid, dim3(256), 0, c->stream, p);
+      });
       p.redo_mode = 2;   // the sub-tiles the f16 pass flagged
     }
-    gmm_with_steps(c->kpad, [&](auto steps) { hipLaunchKernelGGL((gmm_band_kernel<steps(), 3>), split_grid, dim3(256), 0, c->stream, p); });
+    gmm_with_steps(c->kpad, [&](auto steps) {
+      if (list_pass || p.redo_mode == 2) hipLaunchKernelGGL((gmm_band_kernel<steps(), 3, true>), walk_grid, dim3(256), 0, c->stream, p);
+      else hipLaunchKernelGGL((gmm_band_kernel<steps(), 3>), split_grid, dim3(256), 0, c->stream, p);
+    });
     p.redo_mode = 0;
     p.b_skip0 = 1;
   }
   p.b_split = 0;   // (the f32 band kernel keeps one wavefront per sub-tile and walks the runs of class 0 itself)
   const bool f32_classes = c->has_slot_class[4];   // single Gaussians stay on the f32 pipe (bit-exact); everything else was scored above
-  if (!p.b_skip0 || f32_classes) mfa_gmm_launch_band_f32(c, &p, grid);
+  if (!p.b_skip0 || f32_classes) mfa_gmm_launch_band_f32(c, &p, list_pass ? walk_grid_f32 : grid, list_pass);
   MFA_HIP_CHECK(c, hipGetLastError());
   return 0;
 }

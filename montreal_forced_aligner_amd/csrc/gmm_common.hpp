@@ -95,9 +95,8 @@ __device__ __forceinline__ int2 band_split_block(const GmmParams &p) {
   const unsigned half = gridDim.x >> 1, phase = blockIdx.x >= half ? 1u : 0u, rem = blockIdx.x - phase * half;
   return make_int2((int)(rem >> 3), (int)(phase * 8u + (rem & 7u)));
 }
-// wavefront → (utterance, 64-frame sub-tile) of a band-mode launch; false: nothing to do
-__device__ __forceinline__ bool band_item(const GmmParams &p, int wave, int &utt, int &r, int *chunk = nullptr) {
-  int witem = (p.b_split ? band_split_block(p).x : (int)blockIdx.x) * 4 + wave;
+// wavefront item → (utterance, 64-frame sub-tile[, chunk]) of a band-mode launch; false: nothing to do
+__device__ __forceinline__ bool band_witem(const GmmParams &p, int witem, int &utt, int &r, int *chunk = nullptr) {
   if (chunk) { const int q = witem / p.b_nchunk; *chunk = witem - q * p.b_nchunk; witem = q; }
   const int item = witem / p.b_sub;
   r = witem - item * p.b_sub;
@@ -106,6 +105,26 @@ __device__ __forceinline__ bool band_item(const GmmParams &p, int wave, int &utt
   utt = p.b_utt_list ? p.b_utt_list[item] : item;
   if (p.b_t_begin > 0 && p.b_done && p.b_done[(size_t)utt * p.b_done_stride + p.b_done_word] != 0) return false;
   return true;
+}
+// full grids (one wavefront per item): the item follows from the workgroup
+__device__ __forceinline__ bool band_item(const GmmParams &p, int wave, int &utt, int &r, int *chunk = nullptr) {
+  return band_witem(p, (p.b_split ? band_split_block(p).x : (int)blockIdx.x) * 4 + wave, utt, r, chunk);
+}
+// Strided grids (list passes, redo sweeps: launches that find work for a handful of wavefronts, or none): a small fixed
+// grid whose wavefronts walk the items first, first + stride, … < n_witems — the items of a full grid, counted on the
+// device.  Grouped plans keep their rule: workgroup b scores run b % groups (the grid is a multiple of `groups`), so run
+// x still meets XCD x only.  (With 16 runs an XCD serves x and x + 8 at the same time here; the full grid runs them one
+// after the other, band_split_block, so that its L2 sees a sixteenth of the model at a time.  Eight runs is the default.)
+struct BandWalk { int first, stride, n_witems, grp; };
+__device__ __forceinline__ BandWalk band_walk(const GmmParams &p, int wave, bool chunks) {
+  BandWalk w;
+  const unsigned runs = p.b_split ? (unsigned)p.groups : 1u;
+  w.grp = (int)(blockIdx.x % runs);
+  w.first = (int)(blockIdx.x / runs) * 4 + wave;
+  w.stride = (int)(gridDim.x / runs) * 4;
+  const int n_items = p.b_n_list ? *p.b_n_list : p.n_utt;
+  w.n_witems = n_items * p.b_sub * (chunks ? p.b_nchunk : 1);
+  return w;
 }
 
 // row index (within a 32-row MFMA block) held by accumulator register r of a lane in half h
@@ -241,5 +260,5 @@ inline void gmm_with_steps(int kpad, F &&f) {
 
 // Band-mode launch of the f32 tile walk (gmm_band_f32_kernel, gmm.hip) for mfa_gmm_score_window (gmm_band.hip).  `params`
 // points to the launch's GmmParams: the type lives in each unit's unnamed namespace (the kernels' symbol names carry it),
-// so a function that crosses units cannot name it.
-void mfa_gmm_launch_band_f32(mfa_ctx *c, const void *params, dim3 grid);
+// so a function that crosses units cannot name it.  `strided`: `grid` is a small fixed grid whose wavefronts walk the items.
+void mfa_gmm_launch_band_f32(mfa_ctx *c, const void *params, dim3 grid, bool strided);

@@ -12,8 +12,8 @@ rows = list(csv.DictReader(open(path)))
 
 
 def cls(n, dur):
-    if "gmm_band_kernel<5, 2>" in n or "gmm_band_kernel<6, 2>" in n:
-        return "band" if dur > 60_000 else None          # (the flagged-list launches are thin)
+    if any(k in n for k in ("gmm_band_kernel<5, 2>", "gmm_band_kernel<6, 2>", "gmm_band_kernel<5, 2, false>", "gmm_band_kernel<6, 2, false>")):
+        return "band" if dur > 60_000 else None          # (the flagged-list launches are thin; so is every <…, true> launch)
     if "viterbi_small_kernel" in n: return "tier1"
     if "mfcc_kernel" in n: return "mfcc"
     if "feats_lda" in n or "feats_kernel" in n: return "lda"

@@ -19,10 +19,12 @@ def rows(sub, suffix):
 
 
 def short(name):
+    if "gmm_band_f32_strided_kernel" in name:
+        return "gmm_band_f32_strided_kernel"
     if "gmm_band_f32_kernel" in name:
         return "gmm_band_f32_kernel"
-    if "gmm_band_kernel" in name:            # <steps, pieces>: 2 = f16×2 pass, 3 = bf16×3 pass (its redo sweep when f16 is on)
-        pieces = name.split("gmm_band_kernel<")[-1].split(">")[0].replace(" ", "").split(",")[-1] if "<" in name else "?"
+    if "gmm_band_kernel" in name:            # <steps, pieces[, strided]>: 2 = f16×2 pass, 3 = bf16×3 pass (its redo sweep when f16 is on)
+        pieces = name.split("gmm_band_kernel<")[-1].split(">")[0].replace(" ", "").split(",")[1] if "<" in name else "?"
         return {"2": "gmm_band_kernel_f16", "3": "gmm_band_kernel_bf16"}.get(pieces, "gmm_band_kernel")
     if "gmm_split_single_kernel" in name:   # <steps, pieces>: 2 = f16×2 pass, 3 = bf16×3 pass (or its redo sweep)
         pieces = name.split("gmm_split_single_kernel<")[-1].split(">")[0].replace(" ", "").split(",")[-1] if "<" in name else "?"
