@@ -18,14 +18,9 @@
 #include <algorithm>
 #include <vector>
 
-#include "ctx.hpp"
+#include "viterbi_common.hpp"
 
 namespace {
-
-enum { G_OK = 0, G_RETRIED = 1, G_FAILED = 2, G_TOKEN_OVERFLOW = 3, G_BP_OVERFLOW = 4, G_INTERNAL = 6, G_WORDS = 7 };
-constexpr int kMinActive = 20;
-constexpr float kBeamDelta = 0.5f;
-constexpr float kHashRatio = 2.0f;
 
 struct GenParams {
   mfa_graph_batch g;
@@ -84,7 +79,7 @@ struct Decoder {
     bk_prev = p.bk_prev + (size_t)w * p.hcap; bk_last = p.bk_last + (size_t)w * p.hcap;
     queue = p.queue + (size_t)w * p.qcap; tmp = p.tmp + (size_t)w * p.ncap;
     hash_size = 1000 < p.hcap ? 1000 : p.hcap;
-    status = G_OK;
+    status = ST_OK;
   }
 
   // ---- HashList (util/hash-list-inl.h): list order = buckets by first occupancy, within a bucket by insertion
@@ -100,7 +95,7 @@ struct Decoder {
       const int tail = el_tail[bk_last[index]];
       for (int e = head; e != tail; e = el_tail[e]) if (el_key[e] == key) { *inserted = false; return e; }
     }
-    if (el_n >= p.ncap) { status = G_TOKEN_OVERFLOW; *inserted = false; return -1; }
+    if (el_n >= p.ncap) { status = ST_TOKEN_OVERFLOW; *inserted = false; return -1; }
     const int ei = el_base + el_n++;
     el_key[ei] = key; el_val[ei] = val; el_tail[ei] = -1;
     *inserted = true;
@@ -120,7 +115,7 @@ struct Decoder {
 
   // NewToken: cost = prev.cost + arc.weight (+ ac_cost): Kaldi's double + float arithmetic (left to right)
   __device__ int NewToken(int arc, double cost, int prev) {
-    if (pool_n >= pool_cap) { status = G_BP_OVERFLOW; return -1; }
+    if (pool_n >= pool_cap) { status = ST_BP_OVERFLOW; return -1; }
     const int t = (int)pool_n++;
     tok_arc[t] = arc; tok_prev[t] = prev; tok_cost[t] = cost;
     return t;
@@ -129,10 +124,10 @@ struct Decoder {
   __device__ void ProcessNonemitting(double cutoff) {
     int qn = 0;
     for (int e = list_head; e != -1; e = el_tail[e]) {
-      if (qn >= p.qcap) { status = G_INTERNAL; return; }
+      if (qn >= p.qcap) { status = ST_INTERNAL; return; }
       queue[qn++] = e;
     }
-    while (qn > 0 && status == G_OK) {
+    while (qn > 0 && status == ST_OK) {
       const int e = queue[--qn];
       const int state = el_key[e], tok = el_val[e];
       if (tok_cost[tok] > cutoff) continue;
@@ -156,13 +151,13 @@ struct Decoder {
           if (nt < 0) return;
           const int ef = Insert(key, nt, &ins);
           if (ef < 0) return;
-          if (qn >= p.qcap) { status = G_INTERNAL; return; }
+          if (qn >= p.qcap) { status = ST_INTERNAL; return; }
           queue[qn++] = ef;
         } else if (tok_cost[el_val[found]] > nc) {
           const int nt = NewToken(a, nc, tok);
           if (nt < 0) return;
           el_val[found] = nt;
-          if (qn >= p.qcap) { status = G_INTERNAL; return; }
+          if (qn >= p.qcap) { status = ST_INTERNAL; return; }
           queue[qn++] = found;
         }
       }
@@ -234,7 +229,7 @@ struct Decoder {
         }
       }
     }
-    for (int e = last_toks; e != -1 && status == G_OK; e = el_tail[e]) {
+    for (int e = last_toks; e != -1 && status == ST_OK; e = el_tail[e]) {
       const int state = el_key[e], tok = el_val[e];
       if (tok_cost[tok] < weight_cutoff) {
         for (int a = arc_off[state]; a < arc_off[state + 1]; a++) {
@@ -271,9 +266,9 @@ struct Decoder {
 
   __device__ void Decode(float beam) {
     InitDecoding();
-    for (int t = 0; t < T && status == G_OK; t++) {
+    for (int t = 0; t < T && status == ST_OK; t++) {
       const double c = ProcessEmitting(t, beam);
-      if (status != G_OK) break;
+      if (status != ST_OK) break;
       ProcessNonemitting(c);
     }
   }
@@ -294,28 +289,28 @@ __global__ __launch_bounds__(64) void viterbi_general_kernel(GenParams p) {
   int32_t *ali = p.ali + f0, *words = p.words + f0;
   float *flike = p.frame_like ? p.frame_like + f0 : nullptr;
   auto fail = [&](int st) { p.status[utt] = st; p.n_words[utt] = 0; p.like[utt] = 0.0f; };
-  if (d.S <= 0 || d.start < 0 || d.start >= d.S || d.T <= 0) { fail(G_FAILED); return; }
+  if (d.S <= 0 || d.start < 0 || d.start >= d.S || d.T <= 0) { fail(ST_FAILED); return; }
   d.Decode(p.beam);
-  int status = G_OK;
-  bool ans = d.status == G_OK && d.ReachedFinal();
-  if (d.status == G_OK && !ans && p.retry_beam != 0.0f) {
-    status = G_RETRIED;
+  int status = ST_OK;
+  bool ans = d.status == ST_OK && d.ReachedFinal();
+  if (d.status == ST_OK && !ans && p.retry_beam != 0.0f) {
+    status = ST_RETRIED;
     d.Decode(p.retry_beam);
-    ans = d.status == G_OK && d.ReachedFinal();
+    ans = d.status == ST_OK && d.ReachedFinal();
   }
-  if (d.status != G_OK) { fail(d.status); return; }
-  if (!ans) { fail(G_FAILED); return; }
+  if (d.status != ST_OK) { fail(d.status); return; }
+  if (!ans) { fail(ST_FAILED); return; }
   // ---- best final token (first in list order on ties), path back through the token pool
   int best_tok = -1; double best_cost = INFINITY;
   for (int e = d.list_head; e != -1; e = d.el_tail[e]) {
     const double c = d.tok_cost[d.el_val[e]] + (double)d.final_w[d.el_key[e]];
     if (c < best_cost && c != INFINITY) { best_cost = c; best_tok = d.el_val[e]; }
   }
-  if (best_tok < 0) { fail(G_FAILED); return; }
+  if (best_tok < 0) { fail(ST_FAILED); return; }
   int32_t *rev = p.rev + (size_t)(item - p.item_base) * p.rev_cap;
   int n_rev = 0;
   for (int tok = best_tok; tok != -1; tok = d.tok_prev[tok]) {
-    if (n_rev >= p.rev_cap) { fail(G_INTERNAL); return; }
+    if (n_rev >= p.rev_cap) { fail(ST_INTERNAL); return; }
     rev[n_rev++] = tok;
   }
   n_rev--;   // the start token carries no arc
@@ -334,8 +329,8 @@ __global__ __launch_bounds__(64) void viterbi_general_kernel(GenParams p) {
     }
     if (d.a_ol[a] != 0) { if (n_w < d.T) words[n_w] = d.a_ol[a]; n_w++; }
   }
-  if (n_ali != d.T) { fail(G_INTERNAL); return; }
-  if (n_w > d.T) { fail(G_WORDS); return; }   // more word labels than frames: d_words holds one per frame (mfa_hip.h, status 7)
+  if (n_ali != d.T) { fail(ST_INTERNAL); return; }
+  if (n_w > d.T) { fail(ST_WORDS); return; }   // more word labels than frames: d_words holds one per frame (mfa_hip.h, status 7)
   w1 += d.final_w[d.a_next[d.tok_arc[best_tok]]];
   p.like[utt] = -(w1 + w2) / p.scale;
   p.n_words[utt] = n_w;
@@ -439,7 +434,7 @@ MFA_API int mfa_align_general_batch(mfa_ctx *c, const mfa_graph_batch *g, const 
     MFA_HIP_CHECK(c, hipMemcpyAsync(st.data(), d_status, (size_t)n_utt * 4, hipMemcpyDeviceToHost, c->stream));
     MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     std::vector<int32_t> again;
-    for (int u = 0; u < n_utt; u++) if (st[u] == G_BP_OVERFLOW) again.push_back(u);
+    for (int u = 0; u < n_utt; u++) if (st[u] == ST_BP_OVERFLOW) again.push_back(u);
     n_second = (int)again.size();
     if (n_second > 0) {
       if (c->gen_list_cap < (size_t)n_second) {

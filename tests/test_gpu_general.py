@@ -359,3 +359,77 @@ def test_wavefront_decoder_fuzz_with_epsilon_arcs(engine, fx, seed):
     seen, n = _check_fast(engine, tm, am, fsts, feats, beam, retry)
     assert n == 24 and seen & {0, 1}
     _check_fast(engine, tm, am, fsts, feats, beam, retry, dense=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The seams of the epsilon closures the two frame-loop kernels share (csrc/viterbi_eps.hpp).
+def _wide_initial_closure_graph(tm, rejoin=False):
+    """Start state 0 with 40 epsilon arcs to states 1..40, each of those with one epsilon arc to a state of its own (41..80):
+    81 tokens before frame 0, more than a wavefront.  Every leaf has an emitting arc into a common chain of six states, the
+    last one final.  Weights repeat every four arcs, so many closure tokens and every leaf's candidate tie exactly.
+    rejoin: states 1 and 2, popped last, get a second epsilon arc each, into leaves 45 and 46 — by then tokens number 76 and
+    75 of the closure: state 1's path is cheaper (0.125 against 0.25, the token is replaced), state 2's ties (0.75, it stays)."""
+    tids = np.flatnonzero(tm.id2pdf >= 0)[:3].astype(np.int64)
+    rows, off = [], [0]
+    for k in range(40):
+        rows.append((0, 0, 0.25 * (k % 4), 1 + k))                       # state 0
+    off.append(len(rows))
+    for k in range(40):
+        rows.append((0, 0, 0.25 * ((k + 1) % 4), 41 + k))                # states 1..40
+        if rejoin and k < 2:
+            rows.append((0, 0, (0.125, 0.5)[k], 45 + k))
+        off.append(len(rows))
+    for k in range(40):
+        rows.append((int(tids[k % 3]), 0, 0.5, 81)); off.append(len(rows))            # leaves 41..80 → chain
+    for c in range(5):
+        rows.append((int(tids[c % 3]), 7 if c == 2 else 0, 0.125, 82 + c)); off.append(len(rows))   # chain 81..85
+    off.append(len(rows))                                                             # 86: final, no arcs
+    arcs = np.array(rows, dtype=K.ARC_DTYPE)
+    final = np.full(87, np.inf, dtype=np.float32); final[86] = 0.0
+    return K.Fst(0, np.array(off, dtype=np.int64), arcs, final)
+
+
+def test_initial_closure_wider_than_a_wavefront(engine, fx):
+    """81 tokens in InitDecoding's closure: the 64-token first tier's closure gives up and hands the utterance over, the list
+    pass looks destinations up in chunks of 64 tokens.  Lazy and dense both equal the oracle bit for bit."""
+    tm, am = fx.mono_tm, fx.mono_am
+    f = _wide_initial_closure_graph(tm)
+    assert f.num_states == 87 and int(np.diff(f.arc_offsets)[0]) == 40 and not engine.needs_general_decoder(f)
+    x = fx.mono_feats(fx.pcm[: 16000 // 2])[:6]
+    assert x.shape[0] == 6
+    assert _oracle(tm, am, f, x, 50.0, 0.0)["status"] == 0
+    for dense in (False, True):
+        seen, n = _check_fast(engine, tm, am, [f], [x], 50.0, 0.0, dense=dense, max_tokens=f.num_states)
+        assert n == 1 and seen == {0}
+
+
+def test_initial_closure_finds_tokens_past_the_first_64(engine, fx):
+    """The same closure with two destinations reached a second time once they are tokens number 75 and 76: the chunked lookup
+    of the list pass has to find them (a token created twice would make 83), once to replace the token and once on a tie."""
+    tm, am = fx.mono_tm, fx.mono_am
+    f = _wide_initial_closure_graph(tm, rejoin=True)
+    assert f.num_states == 87 and f.arcs.shape[0] == 127 and not engine.needs_general_decoder(f)
+    x = fx.mono_feats(fx.pcm[: 16000 // 2])[:6]
+    assert _oracle(tm, am, f, x, 50.0, 0.0)["status"] == 0
+    for dense in (False, True):
+        seen, n = _check_fast(engine, tm, am, [f], [x], 50.0, 0.0, dense=dense, max_tokens=f.num_states)
+        assert n == 1 and seen == {0}
+
+
+def test_state_with_65_epsilon_arcs_is_refused_when_packing(engine, fx):
+    """A hub with 65 epsilon arcs, reached at frame 1.  The device contract gives status 5 for it (include/mfa_hip.h,
+    _lib.STATUS_REASONS[5]); pack_graphs does not let it get that far: it refuses the graph, and the host layers route it to
+    the general decoder (needs_general_decoder)."""
+    from montreal_forced_aligner_amd import _lib
+
+    tm = fx.mono_tm
+    tid = int(np.flatnonzero(tm.id2pdf >= 0)[0])
+    rows, off = [(tid, 0, 0.0, 1)], [0, 1]                                # start → hub
+    rows += [(0, 0, 0.25 * (k % 4), 2 + k) for k in range(65)]; off.append(len(rows))     # hub: 65 epsilon arcs
+    for k in range(65):
+        rows.append((tid, 0, 0.5, 2 + k)); off.append(len(rows))          # leaves: emitting self-loop, final
+    final = np.array([np.inf, np.inf] + [0.0] * 65, dtype=np.float32)
+    f = K.Fst(0, np.array(off, dtype=np.int64), np.array(rows, dtype=K.ARC_DTYPE), final)
+    assert engine.needs_general_decoder(f)
+    with pytest.raises(_lib.MfaHipError, match="more than 64 arcs of a kind"):
+        engine.pack_graphs([f], tm)

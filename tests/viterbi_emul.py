@@ -1,4 +1,4 @@
-"""Pure-numpy emulation of the device Viterbi kernel's PARALLEL formulation (montreal_forced_aligner_amd/csrc/viterbi.hip):
+"""Pure-numpy emulation of the device Viterbi kernel's PARALLEL formulation (viterbi_kernel, montreal_forced_aligner_amd/csrc/viterbi_wave.hpp):
 prefix-min cutoffs, per-state winners, Kaldi list order via first-creator ordinals and hash buckets.  Lets the
 formulation be checked against the sequential oracle on a machine without a GPU.  Test infrastructure only."""
 import numpy as np
