@@ -155,6 +155,20 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *ctx, const float *d_feats, const int64_
  * it scores, four uint64 words {start, end (100 MHz wall clock), hardware id (HW_ID | XCC_ID << 32), 32-row blocks
  * walked} at d_trace[((u * tiles) * 4 + r) * 4], tiles = ceil(max_frames / 256).  NULL turns it off. */
 MFA_API int mfa_debug_gmm_trace(mfa_ctx *ctx, void *d_trace);
+/* Test aid, no context and no device: packs a model as mfa_load_gmm does and copies out what it would upload.  h_info[13] =
+ * {kpad, rows, blocks, split tables present, has_slot_class[5] (32, 16, 8, 4, 1 rows), has_single32, has_multi_block,
+ * max_nblk, all_pdfs_32row}; *h_acc_scale = S.  Every array pointer may be NULL (call once for the sizes): h_row0
+ * [num_pdfs + 1], h_nblk / h_slot [num_pdfs], h_w [blocks * 32 * kpad], h_gc / h_gch [blocks * 32], h_wb [blocks * 32 *
+ * kpad * 3] bf16 bits, h_wh [blocks * 32 * kpad * 2] f16 bits, h_fscale [kpad]; h_wb, h_wh and h_gch are written only when
+ * the split tables are present (kpad 80 or 96).  h_sort_pdfs[n_sort] (may be NULL) is sorted in place as by
+ * mfa_gmm_sort_pdf_list_keyed with the keys h_sort_keys[n_sort] — or, h_sort_keys NULL, as by mfa_gmm_sort_pdf_list — and
+ * h_sort_counts[6] receives the class counts.  Returns 0, -1 for a model without pdfs or with an empty pdf, -2 for a pdf id
+ * out of range in h_sort_pdfs. */
+MFA_API int mfa_debug_gmm_pack(int32_t dim, int32_t num_pdfs, const int32_t *h_pdf_offsets, const float *h_gconsts,
+                               const float *h_means_invvars, const float *h_inv_vars, int32_t *h_info, float *h_acc_scale,
+                               int32_t *h_row0, int32_t *h_nblk, int32_t *h_slot, float *h_w, float *h_gc, uint16_t *h_wb,
+                               uint16_t *h_wh, float *h_gch, float *h_fscale, int32_t *h_sort_pdfs, int32_t *h_sort_keys,
+                               int32_t n_sort, int32_t *h_sort_counts);
 /* Profiling aid, effective only in a library built with -DVIT_STAMPS (tools/viterbi_phases.py): the first-beam decoder
  * launch leaves, per utterance, twelve uint64 shader-clock totals (one per phase of its frame loop) at d_stamps[u * 12]. */
 MFA_API int mfa_debug_viterbi_stamps(mfa_ctx *ctx, void *d_stamps);

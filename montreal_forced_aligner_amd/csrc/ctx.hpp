@@ -10,15 +10,7 @@
 
 #include "../../include/mfa_hip.h"
 
-// Packed model layout (built by mfa_load_gmm, read by gmm.hip, gmm_band.hip and fmllr.hip).  Rows (Gaussians) are grouped in blocks of
-// 32; a block is stored operand-major: for every group m of 8 k-values and half h, the 32 rows' 4-float pieces lie side
-// by side —  float offset of (row, logical k = 8m + 2c + h):
-//     (row >> 5) · 32·kpad  +  ((2m + h) · 32 + (row & 31)) · 4  +  c
-// so the 16-byte A-operand loads of the 32 lanes of a half-wavefront (one row each) read 512 contiguous bytes.
-__host__ __device__ inline size_t mfa_packed_offset(int row, int k, int kpad) {
-  const int m = k >> 3, o = k & 7, h = o & 1, c = o >> 1;
-  return (size_t)(row >> 5) * 32 * kpad + (size_t)(((2 * m + h) * 32 + (row & 31)) * 4 + c);
-}
+#include "gmm_pack.hpp"   // mfa_packed_offset: the packed model layout
 
 enum { MFA_K_MFCC = 0, MFA_K_CMVN = 1, MFA_K_FEATS = 2, MFA_K_GMM = 3, MFA_K_VITERBI = 4, MFA_K_COUNT = 5 };
 
@@ -56,7 +48,7 @@ struct mfa_ctx {
   bool gmm_ready = false;
   int dim = 0, kpad = 0, num_pdfs = 0, num_rows = 0;
   float *d_w = nullptr;        // [num_rows][kpad] permuted weights
-  void *d_wb = nullptr;        // bf16×3 split of d_w for gmm_bf16_kernel (see gmm.hip), or NULL
+  void *d_wb = nullptr;        // bf16×3 split of d_w for the bf16×3 kernels (gmm_pack.cpp), or NULL
   void *d_wh = nullptr;        // f16×2 split of the column-scaled d_w for gmm_split_single_kernel<…, 2>, or NULL
   float *d_gch = nullptr;      // gconsts × gmm_acc_scale
   float *d_fscale = nullptr;   // [kpad] feature column scales of the f16 path
@@ -80,10 +72,10 @@ struct mfa_ctx {
   bool has_slot_class[5] = {false, false, false, false, false};   // model has pdfs of slot 32 / 16 / 8 / 4 / 1 rows
   bool has_single32 = false;       // some pdf is one 32-row block (17–32 Gaussians): gmm_split_single_kernel has work
   int max_nblk = 1;                // most 32-row blocks of any pdf
-  bool has_multi_block = false;    // some pdf has more than 32 Gaussians (several blocks, merged by gmm_bf16_kernel<…, true>)
+  bool has_multi_block = false;    // some pdf has more than 32 Gaussians (several blocks, merged by gmm_bf16_kernel)
   bool all_pdfs_32row = false;     // every pdf is a 32-row pdf, of one block or several (no work for the f32 kernel in bf16 mode)
   int32_t *d_nrows = nullptr;  // [num_pdfs] packed rows per pdf (fmllr.hip)
-  int *d_gmm_queue = nullptr;  // [8] per-XCD work-item counters of the persistent scoring kernel
+  int *d_gmm_queue = nullptr;  // work-item counters of the dense scoring launches (layout: kQueue… in mfa_gmm_score_batch), zeroed per call
   int num_cus = 0;
   void *vit_stamps = nullptr;  // debug: per-utterance phase cycle counters of the decoder (-DVIT_STAMPS builds)
   void *gmm_trace = nullptr;   // debug: per-wavefront timeline records of the scoring kernel (mfa_debug_gmm_trace)

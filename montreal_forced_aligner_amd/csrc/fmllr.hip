@@ -25,7 +25,7 @@ static_assert((kMaxD + 1) * (kMaxD + 1) <= 7 * 256 && (kMaxD + 2) * (kMaxD + 2) 
 
 struct FmllrFrameParams {
   int D, kpad;
-  const float *w; const float *gc; const int32_t *row0; const int32_t *nrows;  // packed model (gmm.hip layout)
+  const float *w; const float *gc; const int32_t *row0; const int32_t *nrows;  // packed model (gmm_pack.hpp layout)
   const float *ws;   // packed rows of the model the statistics are formed with (two-model form) — same layout; == w otherwise
   const float *feats; const int32_t *ali_pdf; const float *weight; int64_t total_frames;
   float *a; float *b; float *cnt;
@@ -242,14 +242,7 @@ MFA_API int mfa_fmllr_stats_model(mfa_ctx *c, int32_t dim, int32_t num_pdfs, con
       return c->fail("fMLLR statistics model: pdf %d has %d Gaussians, the loaded (alignment) model %d — the two models must share their Gaussian layout", p, h_pdf_offsets[p + 1] - h_pdf_offsets[p], c->h_ngauss[p]);
   const int blocks = (c->num_rows + 1 + 31) / 32;
   std::vector<float> w((size_t)blocks * 32 * c->kpad, 0.0f);
-  for (int p = 0; p < num_pdfs; p++) {
-    const int g0 = h_pdf_offsets[p], g = h_pdf_offsets[p + 1] - g0;
-    for (int i = 0; i < g; i++) {
-      const float *mi = h_means_invvars + (size_t)(g0 + i) * dim, *iv = h_inv_vars + (size_t)(g0 + i) * dim;
-      for (int k = 0; k < 2 * dim; k++)
-        w[mfa_packed_offset(c->h_row0[p] + i, k, c->kpad)] = k < dim ? mi[k] : -0.5f * iv[k - dim];
-    }
-  }
+  gmm_pack_rows(dim, num_pdfs, h_pdf_offsets, c->h_row0.data(), c->kpad, h_means_invvars, h_inv_vars, w);
   MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_w_stats, w.size() * 4));
   MFA_HIP_CHECK(c, hipMemcpy(c->d_w_stats, w.data(), w.size() * 4, hipMemcpyHostToDevice));
   return 0;

@@ -5,7 +5,7 @@
 //   gmm_col_rows_kernel     once per batch: the first packed model row of every score column;
 //   gmm_band_ranges_kernel  once per window: the band's index range in every class (and run of class 0) of every utterance.
 // Single-Gaussian pdfs (and everything under MFA_GMM_BF16=0) go to gmm_band_f32_kernel, the exact-f32 tile walk, which lives
-// next to its score_tile in gmm.hip and is reached through mfa_gmm_launch_band_f32.  mfa_gmm_score_window (end of file)
+// next to its score_tile in gmm.hip's unit (gmm_f32.hpp) and is reached through mfa_gmm_launch_band_f32.  mfa_gmm_score_window (end of file)
 // decides the launches; mfa_gmm_presplit prepares a batch.  Shared pieces: gmm_common.hpp.
 //
 // Kaldi evaluates its decodable lazily: a score exists only if a live token's arc asked for it.  The dense kernels (gmm.hip)
@@ -19,7 +19,8 @@
 // blocks straight from L2 / Infinity Cache into its A registers — 10 coalesced 1 KiB loads per 32-row block, each operand
 // register re-loaded for the next block as soon as the MFMAs that read it have been issued.  Per block: 30 (60) MFMAs,
 // the log-sum-exp, one staged score column.  Arithmetic per cell is that of gmm_split_single_kernel exactly (same operand
-// split, same product order, same epilogue expressions): a cell scored here is bit-identical to the dense kernel's.
+// split, same product order, same epilogue expressions — gmm_common.hpp's, bar the copies this kernel names in its body):
+// a cell scored here is bit-identical to the dense kernel's.
 // Bound: the 10 KiB (15 KiB) of operands per block and 64 frames — fabric bandwidth, not the matrix pipe.
 #include <algorithm>
 #include <cmath>
@@ -180,8 +181,9 @@ struct BandStamps {
 // for kStrided = false it runs once and compiles to the code the kernel had before it could walk.
 template <int kSteps, int kPieces, bool kStrided = false>
 __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
-  constexpr bool kHalf = kPieces == 2;
-  using op8 = std::conditional_t<kHalf, f16x8, bf16x8>;
+  using Ops = SplitOps<kPieces>;
+  using op8 = typename Ops::op8;
+  constexpr bool kHalf = Ops::kHalf;
   constexpr int kUnits = kSteps * kPieces * 2 * 32;    // 16-byte units per block
   __shared__ float stage_all[4][64 * 33];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -309,8 +311,11 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
     const float inv_s = kHalf ? p.acc_scale_inv : 1.0f;
     const float l2e_s = 1.44269504088896341f * inv_s;
     float *out = p.out + p.ll_off[utt];
-    constexpr int kProd = kHalf ? 3 : 6;
-    constexpr int pa[6] = {kHalf ? 1 : 2, kHalf ? 0 : 1, 0, 1, 0, 0}, pb[6] = {0, 1, kHalf ? 0 : 2, 0, 1, 0};
+    // Three pieces this kernel keeps in its own words, because the instruction text of its hot instantiations (<5, 2> and
+    // <6, 2>, full grid) changes — by a scalar instruction's place or two — when it calls the shared ones: the product loop of
+    // a step (SplitOps::mfma_step; the order table is the shared one), the accumulator seed from the gconst registers
+    // (init_from_gconst) and this flush (flush_staged), all in gmm_common.hpp.  Change them together.
+    constexpr int kProd = Ops::kProd;
     // `cnt` staged columns, the first of them score column c0 of the utterance's matrix → HBM as 128-byte row segments
     auto flush_cols = [&](int c0, int cnt) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -367,8 +372,8 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
 #pragma unroll
             for (int n = 0; n < 2; n++) {
               const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
-              if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-              else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
+              if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][Ops::pa(t6)], b[n][s_][Ops::pb(t6)], cin, 0, 0, 0);
+              else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][Ops::pa(t6)], b[n][s_][Ops::pb(t6)], cin, 0, 0, 0);
             }
           // this step's operand registers (and, after the first step, the gconst registers) are free: next block's rows.
           // (A second operand set — two blocks in flight per wavefront — was measured: 12.70 vs 12.76 ms per step; the
@@ -384,17 +389,9 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
         stamps.cycle(1);
         blk_next = __builtin_amdgcn_readfirstlane(x_next2) >> 5;
         stamps.cycle(2);
-        float mx[2], sum[2];
-#pragma unroll
-        for (int n = 0; n < 2; n++) {
-          float m = reg_max<0, 16>(acc[n]);
-          m = fmaxf(m, swap32(m, h));
-          float sv = reg_expsum_fast(acc[n], m, l2e_s);
-          sv += swap32(sv, h);
-          mx[n] = m; sum[n] = sv;
-        }
+        const Lse lse0 = block_lse(acc[0], h, l2e_s), lse1 = block_lse(acc[1], h, l2e_s);
         const int jj = (j - lo) & 31;
-        stage[(32 * h + col) * 33 + jj] = finish((h ? mx[1] : mx[0]) * inv_s, h ? sum[1] : sum[0]);
+        stage[(32 * h + col) * 33 + jj] = finish((h ? lse1.m : lse0.m) * inv_s, h ? lse1.s : lse0.s);
         stamps.cycle_lds_landed(3);
         if (jj == 31 || j == last) flush_cols(j - jj, jj + 1);
         stamps.cycle(4);
@@ -452,8 +449,8 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
 #pragma unroll
             for (int n = 0; n < 2; n++) {
               const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
-              if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-              else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
+              if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][Ops::pa(t6)], b[n][s_][Ops::pb(t6)], cin, 0, 0, 0);
+              else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][Ops::pa(t6)], b[n][s_][Ops::pb(t6)], cin, 0, 0, 0);
             }
           if (s_ == 0) {
 #pragma unroll
@@ -465,16 +462,9 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
         }
 #pragma unroll
         for (int n = 0; n < 2; n++) {
-          float m = reg_max<0, 16>(acc[n]);
-          m = fmaxf(m, swap32(m, h));
-          float sv = reg_expsum_fast(acc[n], m, l2e_s);
-          sv += swap32(sv, h);
-          if (bk == 0) { M[n] = m; S[n] = sv; }
-          else {
-            const float mn = fmaxf(M[n], m);
-            S[n] = S[n] * __builtin_amdgcn_exp2f((M[n] - mn) * l2e_s) + sv * __builtin_amdgcn_exp2f((m - mn) * l2e_s);
-            M[n] = mn;
-          }
+          const Lse l = block_lse(acc[n], h, l2e_s);
+          if (bk == 0) { M[n] = l.m; S[n] = l.s; }
+          else lse_merge(M[n], S[n], l.m, l.s, l2e_s);
         }
         blk = blk_n;
         if (!last_blk) { bk++; continue; }
@@ -530,8 +520,8 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
 #pragma unroll
             for (int n = 0; n < 2; n++) {
               const f32x16 &cin = (s_ == 0 && t6 == 0) ? init : acc[n];
-              if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
-              else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][pa[t6]], b[n][s_][pb[t6]], cin, 0, 0, 0);
+              if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s_][Ops::pa(t6)], b[n][s_][Ops::pb(t6)], cin, 0, 0, 0);
+              else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s_][Ops::pa(t6)], b[n][s_][Ops::pb(t6)], cin, 0, 0, 0);
             }
           if (s_ == 0) gcv = gsrc[row_next];
 #pragma unroll
@@ -539,59 +529,7 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
           __builtin_amdgcn_sched_barrier(0);
         }
         row_next = row_n2;
-        // per-pdf log-sum-exp.  Accumulator register r of half-wave h is row (r & 3) + 8 (r >> 2) + 4 h of the block.
-        auto group_max = [&](const f32x16 &v, int r0, int cnt) {
-          float m = v[r0];
-#pragma unroll
-          for (int rr = 1; rr < cnt; rr++) m = fmaxf(m, v[r0 + rr]);
-          return m;
-        };
-        auto group_expsum = [&](const f32x16 &v, int r0, int cnt, float m) {
-          float e[8];
-#pragma unroll
-          for (int rr = 0; rr < cnt; rr++) e[rr] = __builtin_amdgcn_exp2f((v[r0 + rr] - m) * l2e_s);
-#pragma unroll
-          for (int w = 1; w < cnt; w <<= 1)
-#pragma unroll
-            for (int rr = 0; rr + w < cnt; rr += 2 * w) e[rr] += e[rr + w];
-          return e[0];
-        };
-        const int colbase = ((jb - jb0) * kPdfs) & 31;   // first staging column of this block
-#pragma unroll
-        for (int n = 0; n < 2; n++) {
-          float *srow = stage + (32 * n + col) * 33 + colbase;
-          if constexpr (kSlot == 16) {                   // pdf k: rows 16k..16k+15 = registers [8k, 8k+8) of both halves
-            float ll[2];
-#pragma unroll
-            for (int k2 = 0; k2 < 2; k2++) {
-              float m = group_max(acc[n], 8 * k2, 8);
-              m = fmaxf(m, swap32(m, h));
-              float sv = group_expsum(acc[n], 8 * k2, 8, m);
-              sv += swap32(sv, h);
-              ll[k2] = finish(m * inv_s, sv);
-            }
-            srow[h] = h ? ll[1] : ll[0];
-          } else if constexpr (kSlot == 8) {             // pdf k: rows 8k..8k+7 = registers [4k, 4k+4) of both halves
-            float ll[4];
-#pragma unroll
-            for (int k2 = 0; k2 < 4; k2++) {
-              float m = group_max(acc[n], 4 * k2, 4);
-              m = fmaxf(m, swap32(m, h));
-              float sv = group_expsum(acc[n], 4 * k2, 4, m);
-              sv += swap32(sv, h);
-              ll[k2] = finish(m * inv_s, sv);
-            }
-            srow[h] = h ? ll[1] : ll[0];
-            srow[2 + h] = h ? ll[3] : ll[2];
-          } else {                                       // slot 4: pdf 2i + h: rows 8i + 4h .. +3 = registers [4i, 4i+4)
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-              const float m = group_max(acc[n], 4 * i, 4);
-              const float sv = group_expsum(acc[n], 4 * i, 4, m);
-              srow[2 * i + h] = finish(m * inv_s, sv);
-            }
-          }
-        }
+        small_slot_scores<kSlot>(acc, stage, col, ((jb - jb0) * kPdfs) & 31, h, inv_s, l2e_s);
         const int done = (jb - jb0 + 1) * kPdfs;         // staged columns since col0 (whole blocks)
         if ((done & 31) == 0 || jb == jb1 - 1) {
           const int first = (done - 1) & ~31;            // first staged column of the open window

@@ -1,7 +1,8 @@
-// What the two scoring units share: gmm.hip (dense scoring, the f32 tile walk, the model packer) and gmm_band.hip (lazy,
-// windowed scoring).  The kernel parameter block, the band arithmetic of a windowed launch, the register reductions of the
-// log-sum-exp, the feature split of the f16 / bf16 operand paths, and the two host helpers every dispatcher uses.
-// Everything device-side sits in an unnamed namespace, as the kernels do: each unit compiles its own copy.
+// What the two scoring units share: gmm.hip (dense scoring and the f32 tile walk: gmm_f32.hpp, gmm_split.hpp) and
+// gmm_band.hip (lazy, windowed scoring).  The kernel parameter block, the band arithmetic of a windowed launch, the register
+// reductions of the log-sum-exp, the split-operand scoring pieces (product order, block log-sum-exp, online merge,
+// small-slot epilogue, staged flush), the feature split of the f16 / bf16 operand paths, and the two host helpers every
+// dispatcher uses.  Everything device-side sits in an unnamed namespace, as the kernels do: each unit compiles its own copy.
 #pragma once
 #include <climits>
 #include <cstdint>
@@ -37,7 +38,7 @@ struct GmmParams {
   float *out;
   float min_log_diff;  // logf(FLT_EPSILON), computed on the host so device and oracle use the same constant
   int n_utt, tiles;    // tiles = 256-frame tiles per utterance (ceil(max_frames / 256)); items = (utterance, tile)
-  int *queue;          // [0..8) phase-1 and [8..16) phase-2 per-XCD item counters; zeroed per launch
+  int *queue;          // this launch's per-XCD item counters: [0..8), gmm_kernel also [8..16) for its second phase; zeroed per call
   const int *max_ff;   // largest first_frame of the batch (device scalar)
   // ---- lazy (windowed) scoring, mfa_gmm_score_window: one wavefront scores the 64 frames [b_t_begin + 64 r, +64) of one
   // utterance for the pdfs inside the band the decoder published for this window
@@ -127,6 +128,9 @@ __device__ __forceinline__ BandWalk band_walk(const GmmParams &p, int wave, bool
   return w;
 }
 
+// one past the last index (i0 + lane) whose bit is set in a 64-lane ballot, 0 if none
+__device__ __forceinline__ int prefix_end(unsigned long long mask, int i0) { return mask ? i0 + 64 - __clzll((long long)mask) : 0; }
+
 // row index (within a 32-row MFMA block) held by accumulator register r of a lane in half h
 __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
@@ -177,6 +181,148 @@ __device__ __forceinline__ float reg_expsum_fast(const f32x16 &v, float mx, floa
 // LL = max + ln(sum) with the hardware log2 (1 ulp on a value ≤ 7, i.e. ≲4e-7 absolute).
 __device__ __forceinline__ float finish(float mx, float sum) {
   return fmaf(__builtin_amdgcn_logf(sum), 0.693147180559945309f, mx);
+}
+
+// ---- the split-operand scoring pieces: ONE definition of the arithmetic the dense kernels (gmm_split.hpp) and the band
+// kernel (gmm_band.hip) promise to agree on to the bit — product order, block log-sum-exp, online merge, small-slot
+// epilogue — and of the staged-column flush.  A kernel that keeps a copy of its own says so at the copy.
+template <int kPieces>   // 3: bf16 triples; 2: column-scaled f16 pairs
+struct SplitOps {
+  static constexpr bool kHalf = kPieces == 2;
+  using op8 = std::conditional_t<kHalf, f16x8, bf16x8>;
+  // six (three) products per 16 k-values, smallest terms first: product t multiplies A piece pa(t) by B piece pb(t)
+  static constexpr int kProd = kHalf ? 3 : 6;
+  static constexpr int pa(int t) { constexpr int v[6] = {kHalf ? 1 : 2, kHalf ? 0 : 1, 0, 1, 0, 0}; return v[t]; }
+  static constexpr int pb(int t) { constexpr int v[6] = {0, 1, kHalf ? 0 : 2, 0, 1, 0}; return v[t]; }
+  // The products of 16-k step s for both frame tiles: a = the block's pieces of that step, b = the wavefront's x̃ operands.
+  // The two tiles alternate so that consecutive MFMAs never wait on each other's accumulator; the first product of step 0
+  // takes `init` (the gconsts) as its addend.  after(t, n) runs behind each MFMA (gmm_split_single_kernel's epilogue chunks).
+  // gmm_band_kernel spells this loop out itself (see the note there): the table above is what the two must share.
+  template <int kSteps, typename After>
+  __device__ __forceinline__ static void mfma_step(const op8 (&a)[kPieces], const op8 (&b)[2][kSteps][kPieces], f32x16 (&acc)[2],
+                                                   const f32x16 &init, int s, After &&after) {
+#pragma unroll
+    for (int t6 = 0; t6 < kProd; t6++)
+#pragma unroll
+      for (int n = 0; n < 2; n++) {
+        const f32x16 &cin = (s == 0 && t6 == 0) ? init : acc[n];
+        if constexpr (kHalf) acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[pa(t6)], b[n][s][pb(t6)], cin, 0, 0, 0);
+        else acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[pa(t6)], b[n][s][pb(t6)], cin, 0, 0, 0);
+        after(t6, n);
+      }
+  }
+  template <int kSteps>
+  __device__ __forceinline__ static void mfma_step(const op8 (&a)[kPieces], const op8 (&b)[2][kSteps][kPieces], f32x16 (&acc)[2],
+                                                   const f32x16 &init, int s) {
+    mfma_step(a, b, acc, init, s, [](int, int) {});
+  }
+};
+
+// The accumulator seed of a 32-row block, gconst of row acc_row(r, h) in register r, from the block's 32 gconsts in LDS
+// (four aligned 16-byte loads per lane).  gmm_band_kernel seeds from registers it loaded a block earlier, in its own words.
+__device__ __forceinline__ f32x16 init_from_gconst(const float *gc_blk, int h) {
+  f32x16 init;
+#pragma unroll
+  for (int qq = 0; qq < 4; qq++) {
+    const float4 gq = *reinterpret_cast<const float4 *>(&gc_blk[8 * qq + 4 * h]);
+    init[4 * qq] = gq.x; init[4 * qq + 1] = gq.y; init[4 * qq + 2] = gq.z; init[4 * qq + 3] = gq.w;
+  }
+  return init;
+}
+
+// (max, Σ exp(x − max)) over the 32 rows of a block for this lane's frame, in accumulator units (× S: l2e_s = log2 e / S)
+struct Lse { float m, s; };
+__device__ __forceinline__ Lse block_lse(const f32x16 &acc, int h, float l2e_s) {
+  float m = reg_max<0, 16>(acc);
+  m = fmaxf(m, swap32(m, h));
+  float sv = reg_expsum_fast(acc, m, l2e_s);
+  sv += swap32(sv, h);
+  return {m, sv};
+}
+// online log-sum-exp of a pdf of several blocks: folds a block's (m, s) into the running pair (M, S)
+__device__ __forceinline__ void lse_merge(float &M, float &S, float m, float s, float l2e_s) {
+  const float mn = fmaxf(M, m);
+  S = S * __builtin_amdgcn_exp2f((M - mn) * l2e_s) + s * __builtin_amdgcn_exp2f((m - mn) * l2e_s);
+  M = mn;
+}
+
+// The small-slot classes: 32 / kSlot pdfs share a (gathered) 32-row block, the log-sum-exp runs over the kSlot rows of each
+// pdf and the block yields 32 / kSlot score columns, staged from column colbase on in the rows of this lane's two frames.
+// Accumulator register r of half-wave h is row (r & 3) + 8 (r >> 2) + 4 h of the block.
+template <int kSlot>
+__device__ __forceinline__ void small_slot_scores(const f32x16 (&acc)[2], float *stage, int col, int colbase, int h, float inv_s,
+                                                  float l2e_s) {
+  auto group_max = [&](const f32x16 &v, int r0, int cnt) {
+    float m = v[r0];
+#pragma unroll
+    for (int rr = 1; rr < cnt; rr++) m = fmaxf(m, v[r0 + rr]);
+    return m;
+  };
+  // Σ exp(x − m) over `cnt` registers from r0, pairwise; m: their maximum
+  auto group_expsum = [&](const f32x16 &v, int r0, int cnt, float m) {
+    float e[8];
+#pragma unroll
+    for (int rr = 0; rr < cnt; rr++) e[rr] = __builtin_amdgcn_exp2f((v[r0 + rr] - m) * l2e_s);
+#pragma unroll
+    for (int w = 1; w < cnt; w <<= 1)
+#pragma unroll
+      for (int rr = 0; rr + w < cnt; rr += 2 * w) e[rr] += e[rr + w];
+    return e[0];
+  };
+#pragma unroll
+  for (int n = 0; n < 2; n++) {
+    float *srow = stage + (32 * n + col) * 33 + colbase;
+    if constexpr (kSlot == 16) {                   // pdf k: rows 16k..16k+15 = registers [8k, 8k+8) of both halves
+      float ll[2];
+#pragma unroll
+      for (int k2 = 0; k2 < 2; k2++) {
+        float m = group_max(acc[n], 8 * k2, 8);
+        m = fmaxf(m, swap32(m, h));
+        float sv = group_expsum(acc[n], 8 * k2, 8, m);
+        sv += swap32(sv, h);
+        ll[k2] = finish(m * inv_s, sv);
+      }
+      srow[h] = h ? ll[1] : ll[0];                 // each half-wave stores one of the two columns
+    } else if constexpr (kSlot == 8) {             // pdf k: rows 8k..8k+7 = registers [4k, 4k+4) of both halves
+      float ll[4];
+#pragma unroll
+      for (int k2 = 0; k2 < 4; k2++) {
+        float m = group_max(acc[n], 4 * k2, 4);
+        m = fmaxf(m, swap32(m, h));
+        float sv = group_expsum(acc[n], 4 * k2, 4, m);
+        sv += swap32(sv, h);
+        ll[k2] = finish(m * inv_s, sv);
+      }
+      srow[h] = h ? ll[1] : ll[0];
+      srow[2 + h] = h ? ll[3] : ll[2];
+    } else {                                       // kSlot 4: pdf 2i + h: rows 8i + 4h .. +3 = registers [4i, 4i+4)
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const float m = group_max(acc[n], 4 * i, 4);
+        const float sv = group_expsum(acc[n], 4 * i, 4, m);
+        srow[2 * i + h] = finish(m * inv_s, sv);
+      }
+    }
+  }
+}
+
+// `count` staged columns of a wavefront's [64 frames][33] staging tile, the first of them score column first_col of the
+// utterance's [T][P] matrix → HBM as 128-byte row segments (a lane-per-frame store would touch 64 lines per instruction).
+// Streaming stores: the scores are written once and read once by the decoder; keeping them out of the Infinity Cache
+// leaves room for the model rows.  Wavefront-scope fences on both sides: the stage is the wavefront's own.
+// (gmm_band_kernel's flush_cols is a copy of this body: see the note there.)
+__device__ __forceinline__ void flush_staged(const float *stage, float *out, int P, int t_base, int T, int first_col, int count,
+                                             int col, int h) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll 4
+  for (int i = 0; i < 32; i++) {
+    const int r = h + 2 * i, t = t_base + r;
+    if (col < count && t < T) __builtin_nontemporal_store(stage[r * 33 + col], &out[(size_t)t * P + first_col + col]);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
 }
 
 // x̃ = [x, x²] of a wavefront's two 32-frame tiles (frames t_base + 32 n + col, clamped into the utterance), split into
@@ -258,7 +404,7 @@ inline void gmm_with_steps(int kpad, F &&f) {
   else f(std::integral_constant<int, 6>{});
 }
 
-// Band-mode launch of the f32 tile walk (gmm_band_f32_kernel, gmm.hip) for mfa_gmm_score_window (gmm_band.hip).  `params`
+// Band-mode launch of the f32 tile walk (gmm_band_f32_kernel, gmm_f32.hpp in gmm.hip's unit) for mfa_gmm_score_window (gmm_band.hip).  `params`
 // points to the launch's GmmParams: the type lives in each unit's unnamed namespace (the kernels' symbol names carry it),
 // so a function that crosses units cannot name it.  `strided`: `grid` is a small fixed grid whose wavefronts walk the items.
 void mfa_gmm_launch_band_f32(mfa_ctx *c, const void *params, dim3 grid, bool strided);
