@@ -46,7 +46,8 @@ MFA_API int mfa_memcpy_d2h(mfa_ctx *ctx, void *h_dst, const void *d_src, size_t 
 /* HIP-event timing of everything enqueued between begin and end on the ctx stream (bench.py's roofline leg). */
 MFA_API int mfa_timer_begin(mfa_ctx *ctx);
 MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
-/* Per-kernel accumulated HIP-event times since the last reset.  which: 0 mfcc, 1 cmvn, 2 feats, 3 gmm, 4 viterbi.
+/* Per-kernel accumulated HIP-event times since the last reset.  which: 0 mfcc, 1 cmvn, 2 feats, 3 gmm, 4 viterbi,
+ * 5 resample.
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -85,6 +86,34 @@ MFA_API int mfa_mfcc_batch(mfa_ctx *ctx, const int16_t *d_pcm, const int64_t *d_
  * (MFA/corpus/features.py:223-235); a batch of 4 096 ten-second utterances is 1.3 GB of samples. */
 MFA_API int mfa_gather_pcm(int32_t n_utt, const int16_t *const *h_src, const int64_t *h_sample_off, int16_t *h_dst,
                            int32_t n_threads);
+
+/* ---- Sample-rate conversion ahead of the MFCC: what OfflineFeatureTpl::ComputeFeatures does with a wave whose rate is
+ *      not sample_frequency when allow_downsample / allow_upsample are set (MFA passes both as True,
+ *      MFA/corpus/features.py:605-607) — Kaldi's LinearResample: a Hann-windowed sinc low-pass at 0.99 x the lower Nyquist
+ *      frequency, 6 zero crossings a side, one filter per output phase of a unit of 1/gcd(in_hz, out_hz) seconds.
+ * The plan is computed in double precision and each weight is rounded once to float32; the device sums
+ * acc = fmaf(w, (float)x, acc) over a phase's taps in ascending order from 0.0f (taps outside the utterance dropped) and
+ * stores acc rounded to nearest-even and clamped to int16 — so the MFCC that follows sees exactly what it would see had
+ * the file been converted to 16-bit PCM at the model's rate beforehand.  Rates: 1 000 - 384 000 Hz. */
+/* Output samples for n input samples (Kaldi GetNumOutputSamples with flush): host arithmetic, < 0 on bad arguments. */
+MFA_API int64_t mfa_resample_num_samples(int32_t in_hz, int32_t out_hz, int64_t n);
+/* The filter bank the kernel uses, on the host (no context): phases = out_hz/gcd, in_per_unit = in_hz/gcd, and per phase i
+ * h_first[i] (first input of output i of a unit, relative to the unit's first input; may be negative), h_taps[i] and the
+ * row h_weights[i][0 .. max_taps) (zero beyond h_taps[i]).  Output k = u*phases + i is
+ * sum_j h_weights[i][j] * x[h_first[i] + u*in_per_unit + j].  Any of the pointers may be NULL: call once with NULL arrays
+ * for the sizes.  < 0: rates outside the limits, or equal. */
+MFA_API int mfa_resample_plan(int32_t in_hz, int32_t out_hz, int32_t *phases, int32_t *in_per_unit, int32_t *max_taps,
+                              int32_t *h_first, int32_t *h_taps, float *h_weights);
+/* Consecutive output samples one workgroup of the kernel produces (tests place utterance lengths around it). */
+MFA_API int32_t mfa_resample_block_outputs(void);
+/* Resamples the n_sel utterances d_utt[0 .. n_sel) — all recorded at in_hz — of a ragged batch: utterance u's samples are
+ * d_in[d_in_off[u] .. d_in_off[u+1]) and its output goes to d_out[d_out_off[u] .. d_out_off[u+1]), whose length the caller
+ * computed with mfa_resample_num_samples.  Both offset arrays span the whole batch (which may hold several rates: one call
+ * per distinct rate, all writing the same d_out); max_out = longest output among the selected utterances.  The plan of a
+ * pair of rates is built on first use and kept in the context.  Errors: rates outside the limits, in_hz == out_hz, more
+ * than 65 535 selected utterances. */
+MFA_API int mfa_resample_batch(mfa_ctx *ctx, int32_t in_hz, int32_t out_hz, const int16_t *d_in, const int64_t *d_in_off,
+                               int16_t *d_out, const int64_t *d_out_off, const int32_t *d_utt, int32_t n_sel, int64_t max_out);
 
 /* ---- CMVN statistics: replaces CmvnComputer().compute_cmvn_from_features / export_cmvn
  *      (MFA/corpus/acoustic_corpus.py:1315-1367; MFA/online/alignment.py:86-88).

@@ -13,7 +13,7 @@ from pathlib import Path
 _PKG = Path(__file__).resolve().parent
 _SO = Path(os.environ["MFA_HIP_SO"]).resolve() if os.environ.get("MFA_HIP_SO") else _PKG / "libmfa_hip.so"   # (override: A/B builds)
 _SOURCES = ["api.hip", "mfcc.hip", "feats.hip", "gmm.hip", "gmm_band.hip", "gmm_pack.cpp", "score_plan.cpp", "viterbi.hip", "viterbi_general.hip",
-            "fmllr.hip"]
+            "fmllr.hip", "resample.hip", "resample_plan.cpp"]
 _LIB = None
 
 
@@ -74,7 +74,8 @@ def build_native(force: bool = False, verbose: bool = False) -> Path:
     """Compile the HIP sources for gfx950 into libmfa_hip.so next to this file (hipcc cross-compiles without a GPU)."""
     src_dir = _PKG / "csrc"
     srcs = [src_dir / s for s in _SOURCES]
-    headers = ("ctx.hpp", "gmm_common.hpp", "gmm_f32.hpp", "gmm_split.hpp", "gmm_pack.hpp", "viterbi_common.hpp", "viterbi_eps.hpp", "viterbi_wave.hpp", "viterbi_small.hpp")
+    headers = ("ctx.hpp", "gmm_common.hpp", "gmm_f32.hpp", "gmm_split.hpp", "gmm_pack.hpp", "viterbi_common.hpp", "viterbi_eps.hpp", "viterbi_wave.hpp", "viterbi_small.hpp",
+               "resample_plan.hpp")
     deps = srcs + [src_dir / h for h in headers] + [_PKG.parent / "include" / "mfa_hip.h"]
     if not force and _SO.exists() and all(_SO.stat().st_mtime >= d.stat().st_mtime for d in deps if d.exists()):
         return _SO
@@ -109,6 +110,10 @@ SIGNATURES = {
     "mfa_mfcc_num_frames": (_i32, [_vp, _i64]),
     "mfa_mfcc_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "mfa_gather_pcm": (C.c_int, [_i32, _vp, _vp, _vp, _i32]),
+    "mfa_resample_num_samples": (_i64, [_i32, _i32, _i64]),
+    "mfa_resample_plan": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mfa_resample_block_outputs": (_i32, []),
+    "mfa_resample_batch": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64]),
     "mfa_cmvn_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp]),
     "mfa_feats_batch": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
     "mfa_load_gmm": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -32,11 +32,12 @@ from .model import DiagGmmModel, TransitionModel
 class CorpusUtterance:
     utt_id: str
     speaker: str
-    pcm: np.ndarray                 # int16 mono at the model's sample rate
+    pcm: np.ndarray                 # int16 mono at ``sample_rate``
     text: str
     begin: float = 0.0              # position inside its sound file (for TextGrid export)
     file_name: Optional[str] = None
     file_duration: Optional[float] = None
+    sample_rate: Optional[int] = None   # Hz of ``pcm``; None: the model's rate.  Other rates are converted on the device
 
 
 class UtteranceResult:
@@ -181,14 +182,32 @@ class CorpusAligner:
             self._loaded = am
 
     # ------------------------------------------------------------------ helpers
+    def _model_rate(self) -> float:
+        return float(self.mfcc_options.get("sample_frequency", 16000.0))
+
+    def _rates(self, utts: Sequence[CorpusUtterance]) -> Optional[List[int]]:
+        """Per-utterance sample rates when some utterance is not at the model's rate, else None (nothing to convert)."""
+        model = self._model_rate()
+        if all(getattr(u, "sample_rate", None) is None or u.sample_rate == model for u in utts):
+            return None
+        return [int(model) if getattr(u, "sample_rate", None) is None else int(u.sample_rate) for u in utts]
+
+    def audio_seconds(self, u: CorpusUtterance) -> float:
+        """Duration of an utterance's audio, by its own rate."""
+        rate = getattr(u, "sample_rate", None)
+        return len(u.pcm) / (self._model_rate() if rate is None else float(rate))
+
     def _batches(self, utts: Sequence[CorpusUtterance]) -> List[List[int]]:
         """Length-bucketed batches (BASELINE configs[4]): sort by duration, cut at ``batch_frames``.  Computed once per run
         (``align`` asks three times: graph compilation ahead, the CMVN pass, the alignment passes)."""
         lens = np.fromiter((len(u.pcm) for u in utts), dtype=np.int64, count=len(utts))
+        rates = self._rates(utts)
         # (keyed on what the batches are a function of: not the list's identity, which a refilled or a new list can share)
-        key = (int(self.opt.batch_frames), lens.tobytes())
+        key = (int(self.opt.batch_frames), lens.tobytes(), None if rates is None else np.asarray(rates, dtype=np.int64).tobytes())
         if getattr(self, "_batches_key", None) == key:
             return self._batches_val
+        if rates is not None:          # frames are counted from the lengths the resampler will hand the MFCC
+            lens = self.engine.num_resampled_array(lens, rates)
         order = np.argsort(lens, kind="stable")
         frames = self.engine.num_frames_array(lens) if hasattr(self.engine, "num_frames_array") else \
             np.array([self.engine.num_frames(int(n)) for n in lens], dtype=np.int64)
@@ -213,6 +232,9 @@ class CorpusAligner:
             return hit
         # PCM gathered by host threads straight into pinned staging memory, then one asynchronous H2D copy (mfa_gather_pcm)
         pcm, so = self.engine.gather_pcm([utts[i].pcm for i in idx])
+        rates = self._rates([utts[i] for i in idx])
+        if rates is not None:          # native-rate PCM travels; the conversion to the model's rate runs on the device
+            pcm, so = self.engine.resample(pcm, so, rates)
         mfcc, fo = self.engine.mfcc(pcm, so)
         if self.opt.corpus_compression:      # feats.*.ark of MfccFunction: compute_mfccs_for_export(seg, compress=True)
             from . import kaldi_io as _kio
@@ -557,7 +579,6 @@ class CorpusAligner:
         runs once per batch over the arrays (intervals_native); the ``HierarchicalCtm`` objects are built when a caller asks
         an ``UtteranceResult`` for its ``ctm``.  Per utterance, as the reference's extraction loop: an alignment the stage
         cannot take concerns this utterance only (:1739-1770 catches, logs and continues)."""
-        sr = float(self.mfcc_options.get("sample_frequency", 16000.0))
         if make_ctm:
             ex = self._extractor()
             for bo in {id(r[0]): r[0] for r in results if r is not None}.values():
@@ -574,7 +595,7 @@ class CorpusAligner:
             a, b = int(bo.frame_off[k]), int(bo.frame_off[k + 1])
             ur = UtteranceResult(u.utt_id, u.speaker, bo.ali[a:b], bo.words[a: a + int(bo.n_words[k])], float(bo.like[k]), b - a)
             if make_ctm:
-                end = u.begin + len(u.pcm) / sr
+                end = u.begin + self.audio_seconds(u)
                 if bo.intervals.err[k] == 0:
                     ur._lazy = (bo.intervals, k, u.text, u.begin, end)
                 else:
@@ -596,7 +617,6 @@ class CorpusAligner:
         Python objects."""
         out_dir = Path(output_directory)
         out_dir.mkdir(parents=True, exist_ok=True)
-        sr = float(self.mfcc_options.get("sample_frequency", 16000.0))
         ext = {"long_textgrid": ".TextGrid", "short_textgrid": ".TextGrid", "json": ".json", "csv": ".csv"}[output_format]
         per_file: Dict[str, dict] = {}
         for n, (u, r) in enumerate(zip(utterances, results)):
@@ -606,7 +626,7 @@ class CorpusAligner:
             f = per_file.get(name)
             if f is None:
                 f = per_file[name] = dict(name=name, duration=0.0, speakers={}, native=True)
-            end = u.begin + len(u.pcm) / sr
+            end = u.begin + self.audio_seconds(u)
             f["duration"] = max(f["duration"], u.file_duration or end)
             f["speakers"].setdefault(u.speaker, []).append(n)
             if r._lazy is None:
@@ -675,10 +695,14 @@ def align_sharded(aligner_factory, utterances: Sequence[CorpusUtterance], rank: 
     """One process per GPU: this rank aligns the speakers ``sharding.assign_speakers`` gives it (weights = audio seconds)
     and every rank receives all results (host-side object gather; no collective on the data path)."""
     spk_index = {s: k for k, s in enumerate(dict.fromkeys(u.speaker for u in utterances))}
-    rank_of = sharding.assign_speakers([spk_index[u.speaker] for u in utterances], world_size,
-                                       weights=[len(u.pcm) for u in utterances])
-    mine = sharding.local_indices(rank_of, rank)
     aligner = aligner_factory()
+    # (samples weigh the same as seconds while every utterance is at the model's rate; with rates of their own, seconds)
+    if all(getattr(u, "sample_rate", None) is None for u in utterances):
+        weights = [len(u.pcm) for u in utterances]
+    else:
+        weights = [aligner.audio_seconds(u) for u in utterances]
+    rank_of = sharding.assign_speakers([spk_index[u.speaker] for u in utterances], world_size, weights=weights)
+    mine = sharding.local_indices(rank_of, rank)
     local = aligner.align([utterances[i] for i in mine], **kw)
     gathered = sharding.gather_results({int(i): r for i, r in zip(mine, local)}, world_size)
     return [gathered.get(i) for i in range(len(utterances))]

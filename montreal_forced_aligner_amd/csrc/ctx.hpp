@@ -12,7 +12,20 @@
 
 #include "gmm_pack.hpp"   // mfa_packed_offset: the packed model layout
 
-enum { MFA_K_MFCC = 0, MFA_K_CMVN = 1, MFA_K_FEATS = 2, MFA_K_GMM = 3, MFA_K_VITERBI = 4, MFA_K_COUNT = 5 };
+enum { MFA_K_MFCC = 0, MFA_K_CMVN = 1, MFA_K_FEATS = 2, MFA_K_GMM = 3, MFA_K_VITERBI = 4, MFA_K_RESAMPLE = 5, MFA_K_COUNT = 6 };
+
+// Resampler plan of one pair of rates on the device (resample.hip; the host plan is resample_plan.cpp's)
+struct MfaResampleDevicePlan {
+  int32_t in_hz = 0, out_hz = 0;
+  int phases = 0, in_per_unit = 0, max_taps = 0;
+  int taps4 = 0;               // max_taps rounded up to a multiple of 4: taps the kernel runs per output
+  int stride = 0;              // floats per row of d_w: taps4 + 1 (odd)
+  int back = 0;                // most inputs a phase's first tap lies before its output's position
+  int chunk = 0, span = 0;     // outputs per staged run of a workgroup and the inputs staged for it
+  bool table_in_lds = false;   // the phase table fits the workgroup's LDS beside the span
+  int32_t *d_first = nullptr;  // [phases] first input of the phase, relative to its unit
+  float *d_w = nullptr;        // [phases][stride], rows zero padded
+};
 
 struct mfa_ctx {
   int device = 0;
@@ -25,8 +38,8 @@ struct mfa_ctx {
   bool kernel_timing = false;
   struct Pending { int which; hipEvent_t a, b; };
   std::vector<Pending> pending;
-  double k_ms[MFA_K_COUNT] = {0, 0, 0, 0, 0};
-  int k_n[MFA_K_COUNT] = {0, 0, 0, 0, 0};
+  double k_ms[MFA_K_COUNT] = {};
+  int k_n[MFA_K_COUNT] = {};
   std::vector<hipEvent_t> event_pool;
 
   // MFCC tables (device)
@@ -41,6 +54,8 @@ struct mfa_ctx {
   int mel_np_max = 1;
   float *d_dct = nullptr;      // [nceps][nbins] with lifter folded separately
   float *d_lifter = nullptr;   // [nceps]
+
+  std::vector<MfaResampleDevicePlan> resample_plans;   // one per (in_hz, out_hz) this context has resampled
 
   bool delta_uploaded = false; // feats.hip: this context has written the delta scales to its device's constant memory
 

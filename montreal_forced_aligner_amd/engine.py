@@ -320,6 +320,83 @@ class AlignmentEngine:
         with torch.cuda.device(self.device):
             return torch.from_numpy(view).to(self.device, non_blocking=True)
 
+    # ------------------------------------------------------------------ sample-rate conversion (ahead of the MFCC)
+    def model_rate(self) -> int:
+        """The rate the MFCC is configured for (``sample_frequency``), in whole Hz: what every utterance is brought to."""
+        if self.mfcc_opts is None:
+            self.configure_mfcc()
+        f = float(self.mfcc_opts.sample_frequency)
+        if f != int(f):
+            raise _lib.MfaHipError(f"the resampler takes whole rates in Hz (sample_frequency is {f})")
+        return int(f)
+
+    def resample_block_outputs(self) -> int:
+        """Consecutive output samples per workgroup of the resampling kernel (mfa_resample_block_outputs)."""
+        return int(self.lib.mfa_resample_block_outputs())
+
+    def num_resampled(self, n: int, rate: Optional[int]) -> int:
+        """Samples at the model's rate that ``n`` samples at ``rate`` become (Kaldi GetNumOutputSamples with flush)."""
+        target = self.model_rate()
+        if rate is None or int(rate) == target:
+            return int(n)
+        out = int(self.lib.mfa_resample_num_samples(int(rate), target, int(n)))
+        if out < 0:
+            raise _lib.MfaHipError(f"mfa_resample_num_samples({int(rate)} Hz -> {target} Hz, {int(n)}): rates must lie in 1000 - 384000 Hz")
+        return out
+
+    def num_resampled_array(self, num_samples: np.ndarray, rates: Sequence[Optional[int]]) -> np.ndarray:
+        """``num_resampled`` for a batch: the same integer arithmetic per distinct rate, checked against the library on the
+        longest utterance of each."""
+        n = np.asarray(num_samples, dtype=np.int64)
+        target = self.model_rate()
+        r = np.fromiter((target if x is None else int(x) for x in rates), dtype=np.int64, count=n.shape[0])
+        out = n.copy()
+        for rate in np.unique(r[r != target]).tolist():
+            sel = r == rate
+            g = int(np.gcd(rate, target))
+            per_in, per_out = target // g, rate // g                  # ticks of 1 / lcm seconds per input / output sample
+            length = n[sel] * per_in
+            last = length // per_out
+            last -= (last * per_out == length)
+            cnt = np.where(length <= 0, 0, last + 1)
+            probe = int(np.argmax(n[sel]))
+            if int(cnt[probe]) != self.num_resampled(int(n[sel][probe]), rate):
+                raise _lib.MfaHipError("num_resampled_array disagrees with mfa_resample_num_samples")
+            out[sel] = cnt
+        return out
+
+    def resample(self, pcm: torch.Tensor, sample_off: np.ndarray, rates: Sequence[Optional[int]]):
+        """pcm: int16 [ΣN] on device, utterance u recorded at ``rates[u]`` Hz (None: the model's rate).  Returns
+        (pcm at the model's rate, its sample offsets): utterances already at that rate are copied, the others converted on
+        the device, one launch per distinct rate (mfa_resample_batch).  A batch with nothing to convert comes back as it
+        is, without a device call."""
+        assert pcm.dtype == torch.int16 and pcm.is_cuda
+        target = self.model_rate()
+        so = np.ascontiguousarray(sample_off, dtype=np.int64)
+        n_utt = so.shape[0] - 1
+        r = np.fromiter((target if x is None else int(x) for x in rates), dtype=np.int64, count=n_utt)
+        if not np.any(r != target):
+            return pcm, so
+        out_len = self.num_resampled_array(np.diff(so), r)
+        oo = np.zeros(n_utt + 1, dtype=np.int64)
+        np.cumsum(out_len, out=oo[1:])
+        out = torch.empty(int(oo[-1]), dtype=torch.int16, device=self.device)
+        # utterances at the model's rate: device-to-device copies of their contiguous runs
+        same = r == target
+        edges = np.flatnonzero(np.diff(np.concatenate([[False], same, [False]]).astype(np.int8)))
+        for a, b in zip(edges[::2].tolist(), edges[1::2].tolist()):
+            if so[b] > so[a]:
+                out[int(oo[a]): int(oo[b])].copy_(pcm[int(so[a]): int(so[b])])
+        d_so, d_oo = self._dev(so), self._dev(oo)
+        for rate in np.unique(r[~same]).tolist():
+            sel = np.flatnonzero(r == rate).astype(np.int32)
+            max_out = int(out_len[sel].max())
+            for a in range(0, sel.shape[0], 65535):           # (the kernel indexes the selected utterances in blockIdx.y)
+                d_sel = self._dev(sel[a: a + 65535])
+                check(self.ctx, self.lib.mfa_resample_batch(self.ctx, int(rate), target, _ptr(pcm), _ptr(d_so), _ptr(out), _ptr(d_oo),
+                                                            _ptr(d_sel), int(d_sel.shape[0]), max_out), "mfa_resample_batch")
+        return out, oo
+
     def frame_offsets(self, sample_off: np.ndarray) -> np.ndarray:
         frames = self.num_frames_array(np.diff(sample_off))
         return np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
@@ -729,6 +806,13 @@ class AlignmentEngine:
             check(self.ctx, self.lib.mfa_kernel_time_ms(self.ctx, i, C.byref(ms), C.byref(n)), "mfa_kernel_time_ms")
             out[name] = dict(ms=float(ms.value), launches=int(n.value))
         return out
+
+    def resample_time(self) -> Dict[str, float]:
+        """Accumulated time and launches of the resampling kernel under ``kernel_timing`` (kept out of ``kernel_times``: the
+        benchmark's stage table lists the five stages of its step)."""
+        ms, n = C.c_float(0), C.c_int(0)
+        check(self.ctx, self.lib.mfa_kernel_time_ms(self.ctx, 5, C.byref(ms), C.byref(n)), "mfa_kernel_time_ms")
+        return dict(ms=float(ms.value), launches=int(n.value))
 
     def reset_kernel_times(self) -> None:
         check(self.ctx, self.lib.mfa_kernel_time_reset(self.ctx), "mfa_kernel_time_reset")

@@ -654,8 +654,9 @@ def load_acoustic_model_archive(path) -> Dict[str, bytes]:
 def read_wav_pcm16(path) -> Tuple[np.ndarray, int]:
     """PCM16 RIFF reader (stdlib only).  Returns (int16 [channels, N], sample_rate).
 
-    The reference goes through librosa/soundfile with resampling; the parity domain of this
-    engine is native 16 kHz PCM16, so other encodings are rejected loudly rather than approximated.
+    The reference goes through librosa/soundfile.  Any sample rate is read as it is — the conversion to the
+    model's rate happens on the device (engine.resample) — but other sample encodings are rejected loudly rather than
+    approximated.
     """
     import wave
 

@@ -47,26 +47,55 @@ def get_engine(device: int = 0):
 
 
 # ------------------------------------------------------------------------------------------------ audio / features
+def _model_rate() -> int:
+    """The rate audio is brought to: the engine's configured ``sample_frequency``, or the default before an engine exists."""
+    if _ENGINE is not None and _ENGINE.mfcc_opts is not None:
+        return _ENGINE.model_rate()
+    from .engine import DEFAULT_MFCC
+
+    return int(DEFAULT_MFCC["sample_frequency"])
+
+
+def _to_model_rate(eng, pcm: np.ndarray, rate: int) -> np.ndarray:
+    import torch
+
+    d = torch.from_numpy(np.ascontiguousarray(pcm, dtype=np.int16).copy()).to(eng.device)
+    out, _ = eng.resample(d, np.array([0, pcm.shape[0]], dtype=np.int64), [rate])
+    return out.cpu().numpy()
+
+
 class Segment:
-    """``Segment(path, begin, end, channel)`` — PCM16 16 kHz wav only (resampling is outside the parity domain)."""
+    """``Segment(path, begin, end, channel)`` — PCM16 wav at any rate from 1 to 384 kHz.  ``sample_rate`` is the file's rate
+    (known once the file has been read)."""
 
     def __init__(self, file_path, begin: Optional[float] = None, end: Optional[float] = None, channel: int = 0):
         self.file_path = str(file_path)
         self.begin, self.end, self.channel = begin, end, channel or 0
+        self.sample_rate: Optional[int] = None
 
-    def load_audio(self) -> np.ndarray:
+    def load_native(self) -> Tuple[np.ndarray, int]:
+        """(samples of the segment at the file's own rate, that rate): ``begin`` / ``end`` cut at the native rate."""
         pcm, sr = kaldi_io.read_wav_pcm16(self.file_path)
-        if sr != 16000:
-            raise kaldi_io.KaldiFormatError(f"{self.file_path}: {sr} Hz audio; only native 16 kHz PCM16 is supported")
+        self.sample_rate = int(sr)
         x = pcm[min(self.channel, pcm.shape[0] - 1)]
         b = 0 if self.begin is None else int(round(self.begin * sr))
         e = x.shape[0] if self.end is None else int(round(self.end * sr))
-        return np.ascontiguousarray(x[b:e])
+        return np.ascontiguousarray(x[b:e]), int(sr)
+
+    def load_audio(self) -> np.ndarray:
+        """The segment at the model's rate, as the reference's ``librosa.load(sr=16000)`` hands it over
+        (MFA/db_polars.py:1992): a file at another rate is cut at its own rate, then converted on the device
+        (Kaldi's LinearResample, include/mfa_hip.h — not librosa's resampler, which is outside the parity domain)."""
+        x, sr = self.load_native()
+        if sr == _model_rate():
+            return x
+        return _to_model_rate(get_engine(), x, sr)
 
 
 class MfccComputer:
     """``MfccComputer(**mfcc_options)`` with MFA's option names (MFA/corpus/features.py:780-820)."""
 
+    # (allow_downsample / allow_upsample are options of this object, not of the kernel: see ``_load``)
     _MAP = dict(sample_frequency="sample_frequency", frame_length="frame_length_ms", frame_shift="frame_shift_ms",
                 preemphasis_coefficient="preemphasis", low_frequency="low_frequency", high_frequency="high_frequency",
                 cepstral_lifter="cepstral_lifter", energy_floor="energy_floor", num_mel_bins="num_mel_bins",
@@ -80,18 +109,41 @@ class MfccComputer:
             raise ValueError("dither must be 0: dithered features are random and outside the parity domain")
         self._opts = {self._MAP[k]: v for k, v in options.items() if k in self._MAP and v is not None}
         self.frame_shift = float(options.get("frame_shift", 10)) / 1000.0
+        # Kaldi's defaults are False (a wave at another rate is an error); MFA passes True for both (MFA/corpus/features.py:605-607)
+        self.allow_downsample = bool(options.get("allow_downsample", False))
+        self.allow_upsample = bool(options.get("allow_upsample", False))
 
     def _configure(self):
         eng = get_engine()
         eng.configure_mfcc(**{k: (int(v) if isinstance(v, bool) else v) for k, v in self._opts.items()})
         return eng
 
+    def _load(self, segment: Union[Segment, np.ndarray]) -> Tuple[np.ndarray, Optional[int]]:
+        """(samples, their rate or None for an array, which is taken to be at the model's rate).  A file the options do not
+        allow to be converted is refused here, on the host (Kaldi: "Waveform and config sample Frequency mismatch")."""
+        if not isinstance(segment, Segment):
+            return np.ascontiguousarray(segment, dtype=np.int16), None
+        pcm, sr = segment.load_native()
+        from .engine import DEFAULT_MFCC
+
+        target = float(self._opts.get("sample_frequency", DEFAULT_MFCC["sample_frequency"]))
+        if sr > target and not self.allow_downsample:
+            raise kaldi_io.KaldiFormatError(f"{segment.file_path}: {sr} Hz audio, the features are configured for "
+                                            f"{target:g} Hz and allow_downsample is False")
+        if sr < target and not self.allow_upsample:
+            raise kaldi_io.KaldiFormatError(f"{segment.file_path}: {sr} Hz audio, the features are configured for "
+                                            f"{target:g} Hz and allow_upsample is False")
+        return pcm, (None if sr == target else sr)
+
     def compute_mfccs(self, segment: Union[Segment, np.ndarray]) -> np.ndarray:
         import torch
 
+        pcm, rate = self._load(segment)          # (refusals come before any device work)
         eng = self._configure()
-        pcm = segment.load_audio() if isinstance(segment, Segment) else np.asarray(segment, dtype=np.int16)
-        out, _ = eng.mfcc(torch.from_numpy(pcm.copy()).to(eng.device), np.array([0, pcm.shape[0]], dtype=np.int64))
+        d, so = torch.from_numpy(pcm.copy()).to(eng.device), np.array([0, pcm.shape[0]], dtype=np.int64)
+        if rate is not None:
+            d, so = eng.resample(d, so, [rate])
+        out, _ = eng.mfcc(d, so)
         return out.cpu().numpy()
 
     def compute_mfccs_for_export(self, segment, compress: bool = True):
@@ -105,27 +157,32 @@ class MfccComputer:
         """``feats.*.ark`` (+ ``.scp``) for (key, segment) pairs, MFCCs computed in device batches (MfccFunction._run)."""
         import torch
 
-        eng = self._configure()
         ark = Path(file_name)
         scp = ark.with_suffix(".scp") if write_scp else None
         lines = []
+        eng = None
         with open(ark, "wb") as f:
-            batch: List[Tuple[str, np.ndarray]] = []
+            batch: List[Tuple[str, np.ndarray, Optional[int]]] = []
 
             def flush():
+                nonlocal eng
                 if not batch:
                     return
-                so = np.concatenate([[0], np.cumsum([len(x) for _, x in batch])]).astype(np.int64)
-                out, fo = eng.mfcc(torch.from_numpy(np.concatenate([x for _, x in batch])).to(eng.device), so)
+                if eng is None:
+                    eng = self._configure()
+                so = np.concatenate([[0], np.cumsum([len(x) for _, x, _ in batch])]).astype(np.int64)
+                d = torch.from_numpy(np.concatenate([x for _, x, _ in batch])).to(eng.device)
+                d, so = eng.resample(d, so, [r for _, _, r in batch])       # the whole batch in one call (a launch per rate)
+                out, fo = eng.mfcc(d, so)
                 out = out.cpu().numpy()
-                for i, (key, _) in enumerate(batch):
+                for i, (key, _, _) in enumerate(batch):
                     off = kaldi_io.write_ark_entry(f, key, out[fo[i]: fo[i + 1]], "compressed_matrix" if compress else "matrix")
                     lines.append(f"{key} {ark}:{off}\n")
                 batch.clear()
 
             for key, seg in segments:
-                pcm = seg.load_audio() if isinstance(seg, Segment) else np.asarray(seg, dtype=np.int16)
-                batch.append((key, np.ascontiguousarray(pcm, dtype=np.int16)))
+                pcm, rate = self._load(seg)
+                batch.append((key, pcm, rate))
                 if len(batch) >= batch_size:
                     flush()
             flush()
