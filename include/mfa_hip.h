@@ -47,7 +47,7 @@ MFA_API int mfa_memcpy_d2h(mfa_ctx *ctx, void *h_dst, const void *d_src, size_t 
 MFA_API int mfa_timer_begin(mfa_ctx *ctx);
 MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
 /* Per-kernel accumulated HIP-event times since the last reset.  which: 0 mfcc, 1 cmvn, 2 feats, 3 gmm, 4 viterbi,
- * 5 resample.
+ * 5 resample, 6 pitch.
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -104,6 +104,13 @@ MFA_API int64_t mfa_resample_num_samples(int32_t in_hz, int32_t out_hz, int64_t 
  * for the sizes.  < 0: rates outside the limits, or equal. */
 MFA_API int mfa_resample_plan(int32_t in_hz, int32_t out_hz, int32_t *phases, int32_t *in_per_unit, int32_t *max_taps,
                               int32_t *h_first, int32_t *h_taps, float *h_weights);
+/* The same bank with the low-pass cutoff (Hz; 0 < 2 * cutoff_hz < both rates) and the zero crossings kept on each side (1 - 64)
+ * chosen by the caller, and equal rates allowed (one phase: a plain low-pass): Kaldi's LinearResample(in, out, cutoff, zeros).
+ * mfa_resample_plan is this with (0.99 x the lower Nyquist frequency, 6), bit for bit; the pitch tracker's down-sampler
+ * (mfa_pitch_batch) is (sample_frequency -> resample_frequency, lowpass_cutoff, lowpass_filter_width). */
+MFA_API int mfa_resample_plan_general(int32_t in_hz, int32_t out_hz, double cutoff_hz, int32_t zeros, int32_t *phases,
+                                      int32_t *in_per_unit, int32_t *max_taps, int32_t *h_first, int32_t *h_taps,
+                                      float *h_weights);
 /* Consecutive output samples one workgroup of the kernel produces (tests place utterance lengths around it). */
 MFA_API int32_t mfa_resample_block_outputs(void);
 /* Resamples the n_sel utterances d_utt[0 .. n_sel) — all recorded at in_hz — of a ragged batch: utterance u's samples are
@@ -114,6 +121,97 @@ MFA_API int32_t mfa_resample_block_outputs(void);
  * than 65 535 selected utterances. */
 MFA_API int mfa_resample_batch(mfa_ctx *ctx, int32_t in_hz, int32_t out_hz, const int16_t *d_in, const int64_t *d_in_off,
                                int16_t *d_out, const int64_t *d_out_off, const int32_t *d_utt, int32_t n_sel, int64_t max_out);
+
+/* ---- Pitch and voicing: replaces kalpy.feat.pitch.PitchComputer(**pitch_options).compute_pitch[_for_export]
+ *      (MFA/corpus/features.py:687-688, :340-355; pasted after CMVN, MFA/alignment/multiprocessing.py:1290-1294; options
+ *      MFA/models.py:551-576) = Kaldi ComputeKaldiPitch (offline, whole utterance) followed by ProcessPitch.
+ * Kaldi's source is not among this project's references: the algorithm is RESTATED ("Pitch"; tests/pitch_ref.py)
+ * and pinned by what a pitch tracker has to do, not by parity with Kaldi's arithmetic.
+ *  1. down-sample: LinearResample(sample_frequency -> resample_frequency, lowpass_cutoff, lowpass_filter_width) to float32
+ *     (acc = fmaf(w, (float)x, acc) over a phase's taps in ascending order from 0.0f, no rounding to int16);
+ *  2. per frame a window of N + last_lag resampled samples (zeros outside the utterance), minus the mean of its first N;
+ *     per measured integer lag l: inner = sum_k w[k] w[k+l], norm = (sum_k w[k]^2)(sum_k w[k+l]^2) (fmaf chains over
+ *     ascending k < N from 0.0f) and two NCCFs inner / sqrtf(norm + ballast) (0 where the denominator is 0): ballast
+ *     (mean_square * N)^2 * nccf_ballast for the pitch NCCF, 0 for the voicing (POV) NCCF;
+ *  3. both NCCFs up-sampled onto the state lags lag_i = (1 + delta_pitch)^i / max_f0 <= 1 / min_f0 by a Hann-windowed sinc
+ *     (cutoff resample_frequency / 2, upsample_filter_width zero crossings; fmaf over ascending taps from 0.0f);
+ *  4. Viterbi over the states: local_i = fmaf(soft_min_f0 * lag_i, n_i, 1 - n_i), fwd_t[i] = min_j (fwd_{t-1}[j] +
+ *     c * (i-j)^2) + local_i with c = delta_pitch^2 * penalty_factor, the frame's minimum subtracted after every frame;
+ *     ties take the SMALLEST j and the final state is the smallest argmin (Kaldi's tie order is not reproduced);
+ *     raw output per frame: (POV NCCF at the state, 1 / lag_state Hz);
+ *  5. ProcessPitch: POV feature, normalised log-pitch (POV-weighted mean over +-normalization_context frames), raw log-pitch.
+ * Stages 1-4 are exact float32 contracts (a float32 numpy restatement is bit-identical); stage 5 uses the device's logf /
+ * expf / powf and is checked under a tolerance. */
+typedef struct {
+  float sample_frequency;        /* 16000 */
+  float frame_length_ms;         /* 25 */
+  float frame_shift_ms;          /* 10 */
+  float min_f0;                  /* 50 */
+  float max_f0;                  /* MFA: 800 (Kaldi: 400) */
+  float soft_min_f0;             /* 10 */
+  float penalty_factor;          /* 0.1 */
+  float lowpass_cutoff;          /* 1000 */
+  float resample_frequency;      /* 4000 */
+  float delta_pitch;             /* 0.005 */
+  float nccf_ballast;            /* 7000 */
+  float preemphasis;             /* 0 (anything else is refused) */
+  float pov_scale;               /* 2 */
+  float pov_offset;              /* 0 */
+  float pitch_scale;             /* 2 */
+  int32_t lowpass_filter_width;  /* 1 */
+  int32_t upsample_filter_width; /* 5 */
+  int32_t snip_edges;            /* MFA's model default 1 */
+  int32_t normalization_context; /* 75 frames on each side */
+  int32_t add_pov_feature;       /* use_voicing */
+  int32_t add_normalized_log_pitch; /* use_pitch and normalize_pitch */
+  int32_t add_raw_log_pitch;     /* use_pitch and not normalize_pitch */
+  int32_t add_delta_pitch;       /* refused: Kaldi adds Gaussian noise to it, so like dither it has no parity domain */
+} mfa_pitch_opts;
+
+/* Refused with a message, the context keeping its previous options and staying usable: add_delta_pitch, preemphasis != 0,
+ * min_f0 >= max_f0 or min_f0 <= 0, max_f0 >= resample_frequency / 2 - 100 Hz (no room for the up-sampling filter below the
+ * Nyquist lag: one measured lag at least must lie under 1 / max_f0), 2 * lowpass_cutoff >= either rate, non-integer rates,
+ * more than 2 048 states, 1 024 measured lags or 2 048 window samples (what a workgroup's LDS holds), no column asked for. */
+MFA_API int mfa_pitch_configure(mfa_ctx *ctx, const mfa_pitch_opts *opts);
+/* Frames the tracker gives for num_samples samples (host arithmetic): with n the resampled length
+ * (mfa_resample_num_samples) and N, shift the window and shift in resampled samples, 0 when n < N; otherwise
+ * (n - N) / shift + 1 with snip_edges, (int)(n / shift + 0.5) without.  The MFCC's count may differ by one: a caller pastes
+ * min(mfcc, pitch) frames when they differ by at most 1 (paste-feats, length tolerance 1) and refuses the utterance otherwise. */
+MFA_API int32_t mfa_pitch_num_frames(mfa_ctx *ctx, int64_t num_samples);
+MFA_API int32_t mfa_pitch_num_states(mfa_ctx *ctx);
+/* Columns mfa_pitch_process_batch writes under the configured options (1 - 3). */
+MFA_API int32_t mfa_pitch_num_columns(mfa_ctx *ctx);
+/* Device workspace mfa_pitch_batch will hold for a batch of this shape: back-pointers uint16 [frames][states], the POV NCCF
+ * [frames][lags] and the resampled signal, for as many utterances as fit the workspace budget at a time — 2 GiB, or
+ * environment MFA_PITCH_WORKSPACE_MB (read at every call) — and never less than the largest single utterance needs
+ * (max_samples, max_frames).  The utterances of a batch are tracked in sub-launches that fit it. */
+MFA_API size_t mfa_pitch_workspace_bytes(mfa_ctx *ctx, int32_t n_utt, int64_t total_samples, int64_t total_frames,
+                                         int64_t max_samples, int32_t max_frames);
+/* d_pcm / d_sample_off as for mfa_mfcc_batch (samples at sample_frequency); d_frame_off[n_utt+1]: rows of every utterance
+ * in d_raw, float32 [total_frames][2] = (POV NCCF, pitch in Hz), exactly mfa_pitch_num_frames rows each (the trace-back
+ * starts at the utterance's last frame: a row the paste rule drops is dropped afterwards, as paste-feats does).  h_sample_off / h_frame_off: host copies of the two
+ * offset arrays (workspace sizing and sub-launches without a synchronisation on device data). */
+MFA_API int mfa_pitch_batch(mfa_ctx *ctx, const int16_t *d_pcm, const int64_t *d_sample_off, const int64_t *d_frame_off,
+                            const int64_t *h_sample_off, const int64_t *h_frame_off, int32_t n_utt, int32_t max_frames,
+                            float *d_raw);
+/* ProcessPitch on the raw output: the configured columns of frame r go to d_out[r * out_stride + out_col0 ...] (float32; a
+ * wider base-feature matrix whose first columns hold the MFCCs, or a matrix of its own with out_stride = columns). */
+MFA_API int mfa_pitch_process_batch(mfa_ctx *ctx, const float *d_raw, const int64_t *d_frame_off, int32_t n_utt,
+                                    int32_t max_frames, float *d_out, int32_t out_stride, int32_t out_col0);
+/* Test aid.  Host tables, no device: with ctx NULL the tables of *opts (otherwise of the configured options).  h_sizes[8] =
+ * {states, first measured lag, last measured lag, up-sampler max taps, N, shift, down-sampler phases, down-sampler max
+ * taps}; h_lags / h_soft_min_lag / h_penalty [states]; h_up_first / h_up_taps [states], h_up_weights [states][max taps].
+ * Every array pointer may be NULL (call once for the sizes).  Device stages (ctx and d_pcm non-NULL): tracks the batch as
+ * mfa_pitch_batch does, in ONE sub-launch whatever the budget, and copies out what the caller gave room for: d_resampled
+ * (float32, utterance u at d_rs_off[u], length mfa_resample_num_samples), d_nccf_pitch / d_nccf_pov [total_frames][states]
+ * (the up-sampled NCCFs), d_path [total_frames] (state per frame), d_raw [total_frames][2].  Returns 0, < 0 on refusal
+ * (ctx NULL: no message is kept). */
+MFA_API int mfa_debug_pitch_stages(mfa_ctx *ctx, const mfa_pitch_opts *opts, int32_t *h_sizes, float *h_lags,
+                                   float *h_soft_min_lag, float *h_penalty, int32_t *h_up_first, int32_t *h_up_taps,
+                                   float *h_up_weights, const int16_t *d_pcm, const int64_t *d_sample_off,
+                                   const int64_t *d_frame_off, const int64_t *h_sample_off, const int64_t *h_frame_off,
+                                   int32_t n_utt, int32_t max_frames, float *d_resampled, const int64_t *d_rs_off,
+                                   float *d_nccf_pitch, float *d_nccf_pov, int32_t *d_path, float *d_raw);
 
 /* ---- CMVN statistics: replaces CmvnComputer().compute_cmvn_from_features / export_cmvn
  *      (MFA/corpus/acoustic_corpus.py:1315-1367; MFA/online/alignment.py:86-88).

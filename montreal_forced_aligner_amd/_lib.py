@@ -13,7 +13,7 @@ from pathlib import Path
 _PKG = Path(__file__).resolve().parent
 _SO = Path(os.environ["MFA_HIP_SO"]).resolve() if os.environ.get("MFA_HIP_SO") else _PKG / "libmfa_hip.so"   # (override: A/B builds)
 _SOURCES = ["api.hip", "mfcc.hip", "feats.hip", "gmm.hip", "gmm_band.hip", "gmm_pack.cpp", "score_plan.cpp", "viterbi.hip", "viterbi_general.hip",
-            "fmllr.hip", "resample.hip", "resample_plan.cpp"]
+            "fmllr.hip", "resample.hip", "resample_plan.cpp", "pitch.hip", "pitch_plan.cpp"]
 _LIB = None
 
 
@@ -46,6 +46,19 @@ class MfccOpts(C.Structure):
     ]
 
 
+class PitchOpts(C.Structure):
+    _fields_ = [
+        ("sample_frequency", C.c_float), ("frame_length_ms", C.c_float), ("frame_shift_ms", C.c_float),
+        ("min_f0", C.c_float), ("max_f0", C.c_float), ("soft_min_f0", C.c_float), ("penalty_factor", C.c_float),
+        ("lowpass_cutoff", C.c_float), ("resample_frequency", C.c_float), ("delta_pitch", C.c_float),
+        ("nccf_ballast", C.c_float), ("preemphasis", C.c_float), ("pov_scale", C.c_float), ("pov_offset", C.c_float),
+        ("pitch_scale", C.c_float),
+        ("lowpass_filter_width", C.c_int32), ("upsample_filter_width", C.c_int32), ("snip_edges", C.c_int32),
+        ("normalization_context", C.c_int32), ("add_pov_feature", C.c_int32), ("add_normalized_log_pitch", C.c_int32),
+        ("add_raw_log_pitch", C.c_int32), ("add_delta_pitch", C.c_int32),
+    ]
+
+
 class GraphBatch(C.Structure):
     _fields_ = [
         ("n_utt", C.c_int32),
@@ -75,7 +88,7 @@ def build_native(force: bool = False, verbose: bool = False) -> Path:
     src_dir = _PKG / "csrc"
     srcs = [src_dir / s for s in _SOURCES]
     headers = ("ctx.hpp", "gmm_common.hpp", "gmm_f32.hpp", "gmm_split.hpp", "gmm_pack.hpp", "viterbi_common.hpp", "viterbi_eps.hpp", "viterbi_wave.hpp", "viterbi_small.hpp",
-               "resample_plan.hpp")
+               "resample_plan.hpp", "pitch_plan.hpp")
     deps = srcs + [src_dir / h for h in headers] + [_PKG.parent / "include" / "mfa_hip.h"]
     if not force and _SO.exists() and all(_SO.stat().st_mtime >= d.stat().st_mtime for d in deps if d.exists()):
         return _SO
@@ -112,8 +125,18 @@ SIGNATURES = {
     "mfa_gather_pcm": (C.c_int, [_i32, _vp, _vp, _vp, _i32]),
     "mfa_resample_num_samples": (_i64, [_i32, _i32, _i64]),
     "mfa_resample_plan": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mfa_resample_plan_general": (C.c_int, [_i32, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mfa_resample_block_outputs": (_i32, []),
     "mfa_resample_batch": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64]),
+    "mfa_pitch_configure": (C.c_int, [_vp, C.POINTER(PitchOpts)]),
+    "mfa_pitch_num_frames": (_i32, [_vp, _i64]),
+    "mfa_pitch_num_states": (_i32, [_vp]),
+    "mfa_pitch_num_columns": (_i32, [_vp]),
+    "mfa_pitch_workspace_bytes": (C.c_size_t, [_vp, _i32, _i64, _i64, _i64, _i32]),
+    "mfa_pitch_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "mfa_pitch_process_batch": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32]),
+    "mfa_debug_pitch_stages": (C.c_int, [_vp, C.POINTER(PitchOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mfa_cmvn_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp]),
     "mfa_feats_batch": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
     "mfa_load_gmm": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),

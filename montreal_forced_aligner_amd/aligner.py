@@ -127,13 +127,22 @@ class CorpusAligner:
     def __init__(self, tm: TransitionModel, am: DiagGmmModel, tree, lexicon, lda: Optional[np.ndarray] = None,
                  options: Optional[AlignOptions] = None, device: int = 0, engine: Optional[AlignmentEngine] = None,
                  mfcc_options: Optional[dict] = None, silence_phones: Sequence[int] = (),
-                 ali_am: Optional[DiagGmmModel] = None, lazy: bool = True):
+                 ali_am: Optional[DiagGmmModel] = None, lazy: bool = True, pitch_options: Optional[dict] = None):
         self.tm, self.tree, self.lexicon = tm, tree, lexicon
         self.lda = None if lda is None else np.asarray(lda, dtype=np.float32)
         self.opt = options or AlignOptions()
         self.engine = engine or AlignmentEngine(device)
         self.mfcc_options = dict(mfcc_options or {})
         self.engine.configure_mfcc(**self.mfcc_options)
+        # a use_pitch / use_voicing model (model.pitch_options(meta)): pitch columns are pasted after the MFCCs' CMVN in every
+        # pass (MFA/alignment/multiprocessing.py:1290-1294).  None: no pitch, the path below is the one without this keyword.
+        self.pitch_options = None if pitch_options is None else {k: v for k, v in pitch_options.items() if v is not None}
+        self.n_pitch = 0
+        if self.pitch_options is not None:
+            if float(self.pitch_options.get("sample_frequency", 16000.0)) != self._model_rate():
+                raise ValueError("pitch_options and mfcc_options must name the same sample_frequency: pitch runs on the PCM at the model's rate")
+            self.engine.configure_pitch(**self.pitch_options)        # (add_delta_pitch and bad f0 bounds are refused here)
+            self.n_pitch = self.engine.num_pitch_cols
         self.silence_phones = list(silence_phones)
         self.lazy = bool(lazy)
         # boost_silence scales the weights of the silence pdfs (GmmAligner.boost_silence, MFA/alignment/multiprocessing.py:
@@ -235,14 +244,21 @@ class CorpusAligner:
         rates = self._rates([utts[i] for i in idx])
         if rates is not None:          # native-rate PCM travels; the conversion to the model's rate runs on the device
             pcm, so = self.engine.resample(pcm, so, rates)
-        mfcc, fo = self.engine.mfcc(pcm, so)
+        if self.n_pitch:                     # the base matrix: MFCC columns, then the pitch columns (same rows: the paste rule)
+            mfcc, fo = self.engine.base_features(pcm, so)
+        else:
+            mfcc, fo = self.engine.mfcc(pcm, so)
         if self.opt.corpus_compression:      # feats.*.ark of MfccFunction: compute_mfccs_for_export(seg, compress=True)
             from . import kaldi_io as _kio
             host = mfcc.cpu().numpy()
+            nc = self.engine.num_ceps
             for k in range(len(idx)):
                 a, b = int(fo[k]), int(fo[k + 1])
-                if b > a:
+                if b > a and not self.n_pitch:
                     host[a:b] = _kio.compress_round_trip(host[a:b])
+                elif b > a:                  # two tables: the MFCCs', and compute_pitch_for_export(seg, compress=True)'s
+                    host[a:b, :nc] = _kio.compress_round_trip(np.ascontiguousarray(host[a:b, :nc]))
+                    host[a:b, nc:] = _kio.compress_round_trip(np.ascontiguousarray(host[a:b, nc:]))
             mfcc = torch.from_numpy(host).to(self.engine.device)
         size = mfcc.numel() * mfcc.element_size()
         if self._mfcc_cache_on and self._mfcc_cache_bytes + size <= self.opt.mfcc_cache_bytes:   # 52 KB per 10 s utterance: HBM holds millions
@@ -252,7 +268,8 @@ class CorpusAligner:
 
     def _final_features(self, mfcc, fo, rows, cmvn, d_lda, fmllr):
         """CMVN → Δ+ΔΔ | splice+LDA(+fMLLR).  With ``corpus_compression`` the CMVN-applied MFCCs take the second trip
-        through the 8-bit codec first (FinalFeatureFunction, MFA/corpus/features.py:323-365), on the host."""
+        through the 8-bit codec first (FinalFeatureFunction, MFA/corpus/features.py:323-365), on the host; pitch columns,
+        pasted after CMVN, have been through the codec once (``_mfcc``) and stay as they are."""
         import torch
 
         eng = self.engine
@@ -261,17 +278,21 @@ class CorpusAligner:
         from . import kaldi_io as _kio
         host = mfcc.cpu().numpy()
         stats = cmvn.cpu().numpy()
-        dim = host.shape[1]
+        dim = host.shape[1] - self.n_pitch
         for k in range(len(fo) - 1):
             a, b = int(fo[k]), int(fo[k + 1])
             if b > a:
                 st = stats[rows[k]]
-                mean = (st[0, :dim] / st[0, dim]).astype(np.float32)       # ApplyCmvn, no variance normalisation
-                host[a:b] = _kio.compress_round_trip(host[a:b] - mean)
+                mean = (st[0, :dim] / st[0, -1]).astype(np.float32)        # ApplyCmvn, no variance normalisation
+                if self.n_pitch:
+                    host[a:b, :dim] = _kio.compress_round_trip(host[a:b, :dim] - mean)
+                else:
+                    host[a:b] = _kio.compress_round_trip(host[a:b] - mean)
         return eng.features(torch.from_numpy(host).to(eng.device), fo, rows, None, lda=d_lda, fmllr=fmllr)
 
     def speaker_cmvn(self, utts: Sequence[CorpusUtterance]) -> Tuple[Dict[str, int], "object"]:
-        """calc_cmvn: float64 [n_spk, 2, dim+1] on the device, and the speaker → row map."""
+        """calc_cmvn: float64 [n_spk, 2, dim+1] on the device, and the speaker → row map.  With pitch the statistics are
+        those of the MFCC columns alone, zero-padded in the pitch columns (the feature kernel then leaves those untouched)."""
         import torch
 
         spk_ids = {s: k for k, s in enumerate(dict.fromkeys(u.speaker for u in utts))}
@@ -283,11 +304,14 @@ class CorpusAligner:
             mfcc, fo = self._mfcc(utts, idx)
             rows = np.array([spk_ids[utts[i].speaker] for i in idx], dtype=np.int32)
             local, inv = np.unique(rows, return_inverse=True)
+            if self.n_pitch:
+                mfcc = mfcc[:, : self.engine.num_ceps].contiguous()
             pending.append((local, self.engine.cmvn_stats(mfcc, fo, inv.astype(np.int32), len(local))))
         # read back after the last batch is queued: the next batch's PCM is gathered while this one's copy is on the bus
         for local, st in pending:
             total[local] += st.cpu().numpy()
-        return spk_ids, torch.from_numpy(total).to(self.engine.device)
+        stats = torch.from_numpy(total).to(self.engine.device)
+        return spk_ids, (self.engine.pad_cmvn_stats(stats, self.n_pitch) if self.n_pitch else stats)
 
     def _decode(self, graphs, feats, fo, max_tokens, bp_tokens):
         """One device call: scores evaluated lazily for the cells live tokens can reach (default), or the dense matrix."""
@@ -537,7 +561,7 @@ class CorpusAligner:
         self.transforms = None if previous_transforms is None else np.asarray(previous_transforms, dtype=np.float32)
         if speaker_adapted:
             # the transform follows either feature branch: the LDA's rows, or Δ+ΔΔ of the cepstra (MFA/db.py:2101-2136)
-            D = self.lda.shape[0] if self.lda is not None else 3 * self.engine.num_ceps
+            D = self.lda.shape[0] if self.lda is not None else 3 * (self.engine.num_ceps + self.n_pitch)
             beta = np.zeros(len(spk_ids)); K = np.zeros((len(spk_ids), D, D + 1)); G = np.zeros((len(spk_ids), D, D + 1, D + 1))
             two_model = self.am if self.ali_am is not None else None
             for idx, feats, ali, fo, rows in kept:

@@ -8,7 +8,7 @@
 
 extern "C" {
 
-MFA_API int mfa_version(void) { return 1; }
+MFA_API int mfa_version(void) { return 2; }
 
 MFA_API mfa_ctx *mfa_create(int device_id) {
   int n = 0;
@@ -31,7 +31,8 @@ MFA_API void mfa_destroy(mfa_ctx *c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   void *ptrs[] = {c->d_window, c->d_twiddle, c->d_melw, c->d_melidx, c->d_dct, c->d_lifter, c->d_w, c->d_gc,
-                  c->d_row0, c->d_nblk, c->d_slot, c->d_ws, c->d_nrows, c->d_gmm_queue, c->d_wb, c->d_wh, c->d_gch, c->d_fscale, c->d_gmm_redo, c->d_w_stats, c->d_gen_ws, c->d_gen_list, c->d_xsplit, c->d_xsplit_bad, c->d_col_row0, c->d_band_ranges};
+                  c->d_row0, c->d_nblk, c->d_slot, c->d_ws, c->d_nrows, c->d_gmm_queue, c->d_wb, c->d_wh, c->d_gch, c->d_fscale, c->d_gmm_redo, c->d_w_stats, c->d_gen_ws, c->d_gen_list, c->d_xsplit, c->d_xsplit_bad, c->d_col_row0, c->d_band_ranges,
+                  c->d_pitch_f, c->d_pitch_i, c->d_pitch_ws};
   // teardown: nothing useful can be done with a failure here
   for (void *p : ptrs) if (p) (void)hipFree(p);
   for (auto &q : c->resample_plans) { (void)hipFree(q.d_first); (void)hipFree(q.d_w); }

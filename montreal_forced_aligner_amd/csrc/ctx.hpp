@@ -11,8 +11,9 @@
 #include "../../include/mfa_hip.h"
 
 #include "gmm_pack.hpp"   // mfa_packed_offset: the packed model layout
+#include "pitch_plan.hpp" // MfaPitchHostPlan: the pitch tracker's host tables
 
-enum { MFA_K_MFCC = 0, MFA_K_CMVN = 1, MFA_K_FEATS = 2, MFA_K_GMM = 3, MFA_K_VITERBI = 4, MFA_K_RESAMPLE = 5, MFA_K_COUNT = 6 };
+enum { MFA_K_MFCC = 0, MFA_K_CMVN = 1, MFA_K_FEATS = 2, MFA_K_GMM = 3, MFA_K_VITERBI = 4, MFA_K_RESAMPLE = 5, MFA_K_PITCH = 6, MFA_K_COUNT = 7 };
 
 // Resampler plan of one pair of rates on the device (resample.hip; the host plan is resample_plan.cpp's)
 struct MfaResampleDevicePlan {
@@ -56,6 +57,14 @@ struct mfa_ctx {
   float *d_lifter = nullptr;   // [nceps]
 
   std::vector<MfaResampleDevicePlan> resample_plans;   // one per (in_hz, out_hz) this context has resampled
+
+  // pitch tracker (pitch.hip): the accepted options with their host tables, and the same tables on the device
+  bool pitch_ready = false;
+  MfaPitchHostPlan pitch;
+  float *d_pitch_f = nullptr;      // lags [S] | soft_min_f0 * lag [S] | penalties [S] | up-sampler rows [S][taps] | down-sampler rows
+  int32_t *d_pitch_i = nullptr;    // up-sampler first [S] | taps [S] | down-sampler first [phases] | taps [phases]
+  void *d_pitch_ws = nullptr;      // one sub-launch's resampled signals, POV NCCF rows and back-pointers
+  size_t pitch_ws_bytes = 0;
 
   bool delta_uploaded = false; // feats.hip: this context has written the delta scales to its device's constant memory
 

@@ -10,16 +10,18 @@
 #include "../../include/mfa_hip.h"
 #include "resample_plan.hpp"
 
-namespace {
-constexpr double kZeros = 6.0;   // zeros of the sinc kept on each side
+void mfa_resample_host_plan(int32_t in_hz, int32_t out_hz, bool fill_weights, MfaResampleHostPlan *p) {
+  // the MFCC front end's filter: 0.99 x the lower Nyquist frequency, six zeros of the sinc on each side
+  mfa_resample_host_plan_general(in_hz, out_hz, 0.99 * 0.5 * (double)(in_hz < out_hz ? in_hz : out_hz), 6, fill_weights, p);
 }
 
-void mfa_resample_host_plan(int32_t in_hz, int32_t out_hz, bool fill_weights, MfaResampleHostPlan *p) {
+void mfa_resample_host_plan_general(int32_t in_hz, int32_t out_hz, double fc, int zeros, bool fill_weights,
+                                    MfaResampleHostPlan *p) {
   const int g = std::gcd(in_hz, out_hz);
   const int O = out_hz / g, I = in_hz / g;
   const double fin = (double)in_hz, fout = (double)out_hz;
-  const double fc = 0.99 * 0.5 * (double)(in_hz < out_hz ? in_hz : out_hz);   // low-pass cutoff
-  const double ww = kZeros / (2.0 * fc);                                      // half window, seconds
+  const double kZeros = (double)zeros;    // zeros of the sinc kept on each side
+  const double ww = kZeros / (2.0 * fc);  // half window, seconds
   p->phases = O; p->in_per_unit = I; p->max_taps = 0;
   p->first.assign(O, 0); p->taps.assign(O, 0);
   for (int i = 0; i < O; i++) {
@@ -64,6 +66,23 @@ MFA_API int mfa_resample_plan(int32_t in_hz, int32_t out_hz, int32_t *phases, in
   if (!mfa_resample_rates_ok(in_hz, out_hz) || in_hz == out_hz) return -1;
   MfaResampleHostPlan p;
   mfa_resample_host_plan(in_hz, out_hz, h_weights != nullptr, &p);
+  if (phases) *phases = p.phases;
+  if (in_per_unit) *in_per_unit = p.in_per_unit;
+  if (max_taps) *max_taps = p.max_taps;
+  for (int i = 0; i < p.phases; i++) {
+    if (h_first) h_first[i] = p.first[i];
+    if (h_taps) h_taps[i] = p.taps[i];
+  }
+  if (h_weights) std::copy(p.weights.begin(), p.weights.end(), h_weights);
+  return 0;
+}
+
+MFA_API int mfa_resample_plan_general(int32_t in_hz, int32_t out_hz, double cutoff_hz, int32_t zeros, int32_t *phases,
+                                      int32_t *in_per_unit, int32_t *max_taps, int32_t *h_first, int32_t *h_taps,
+                                      float *h_weights) {
+  if (!mfa_resample_rates_ok(in_hz, out_hz) || !mfa_resample_filter_ok(in_hz, out_hz, cutoff_hz, zeros)) return -1;
+  MfaResampleHostPlan p;
+  mfa_resample_host_plan_general(in_hz, out_hz, cutoff_hz, zeros, h_weights != nullptr, &p);
   if (phases) *phases = p.phases;
   if (in_per_unit) *in_per_unit = p.in_per_unit;
   if (max_taps) *max_taps = p.max_taps;

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import AlignOpts, GraphBatch, MfccOpts, ScorePlan, check
+from ._lib import AlignOpts, GraphBatch, MfccOpts, PitchOpts, ScorePlan, check
 from .kaldi_io import Fst
 from .model import DiagGmmModel, TransitionModel
 
@@ -26,6 +26,17 @@ STATUS_OK, STATUS_RETRIED, STATUS_FAILED, STATUS_TOKEN_OVERFLOW, STATUS_BP_OVERF
 DEFAULT_MFCC = dict(sample_frequency=16000.0, frame_length_ms=25.0, frame_shift_ms=10.0, preemphasis=0.97,
                     low_frequency=20.0, high_frequency=7800.0, cepstral_lifter=22.0, energy_floor=0.0,
                     num_mel_bins=23, num_coefficients=13, snip_edges=0, remove_dc_offset=1, use_energy=0, raw_energy=1)
+
+# Kaldi's PitchExtractionOptions / ProcessPitchOptions at MFA's values (MFA/models.py:551-576 sets max_f0 800 and
+# snip_edges True; Kaldi's own max_f0 is 400)
+DEFAULT_PITCH = dict(sample_frequency=16000.0, frame_length_ms=25.0, frame_shift_ms=10.0, min_f0=50.0, max_f0=800.0,
+                     soft_min_f0=10.0, penalty_factor=0.1, lowpass_cutoff=1000.0, resample_frequency=4000.0, delta_pitch=0.005,
+                     nccf_ballast=7000.0, preemphasis=0.0, pov_scale=2.0, pov_offset=0.0, pitch_scale=2.0,
+                     lowpass_filter_width=1, upsample_filter_width=5, snip_edges=1, normalization_context=75,
+                     add_pov_feature=1, add_normalized_log_pitch=1, add_raw_log_pitch=0, add_delta_pitch=0)
+_PITCH_INT = ("lowpass_filter_width", "upsample_filter_width", "snip_edges", "normalization_context", "add_pov_feature",
+              "add_normalized_log_pitch", "add_raw_log_pitch", "add_delta_pitch")
+_PITCH_ALIAS = {"frame_length": "frame_length_ms", "frame_shift": "frame_shift_ms"}    # kalpy's names (milliseconds)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -396,6 +407,135 @@ class AlignmentEngine:
                 check(self.ctx, self.lib.mfa_resample_batch(self.ctx, int(rate), target, _ptr(pcm), _ptr(d_so), _ptr(out), _ptr(d_oo),
                                                             _ptr(d_sel), int(d_sel.shape[0]), max_out), "mfa_resample_batch")
         return out, oo
+
+    # ------------------------------------------------------------------ pitch and voicing (pasted after CMVN)
+    def configure_pitch(self, **kw) -> None:
+        """Options of kalpy's PitchComputer (``frame_length`` / ``frame_shift`` in milliseconds are accepted under kalpy's
+        names).  A refused set — add_delta_pitch, bad f0 bounds — raises and leaves the previous one in force; the set in force
+        is called for again at no cost.  The options are state of the ENGINE: whoever shares it (a CorpusAligner and a kalpy
+        PitchComputer on the process's engine) shares them, as they share the MFCC options."""
+        d = dict(DEFAULT_PITCH)
+        for k, v in kw.items():
+            k = _PITCH_ALIAS.get(k, k)
+            if k not in d:
+                raise KeyError(f"unknown pitch option {k!r}")
+            d[k] = v
+        for k in _PITCH_INT:
+            d[k] = int(d[k])
+        opts = PitchOpts(**d)
+        if getattr(self, "pitch_opts", None) is not None and bytes(opts) == bytes(self.pitch_opts):
+            return                       # already in force: no tables to rebuild and upload
+        check(self.ctx, self.lib.mfa_pitch_configure(self.ctx, C.byref(opts)), "mfa_pitch_configure")
+        self.pitch_opts = opts
+        self.num_pitch_cols = int(self.lib.mfa_pitch_num_columns(self.ctx))
+
+    def _need_pitch(self) -> None:
+        if getattr(self, "pitch_opts", None) is None:
+            raise _lib.MfaHipError("configure_pitch has not been called")
+
+    def pitch_num_frames(self, num_samples: int) -> int:
+        self._need_pitch()
+        n = int(self.lib.mfa_pitch_num_frames(self.ctx, int(num_samples)))
+        if n < 0:
+            check(self.ctx, -1, "mfa_pitch_num_frames")
+        return n
+
+    def pitch_frame_offsets(self, sample_off: np.ndarray) -> np.ndarray:
+        """Frame offsets of a batch's pitch features (the tracker's own frame counts, mfa_pitch_num_frames)."""
+        self._need_pitch()
+        frames = np.fromiter((self.pitch_num_frames(int(n)) for n in np.diff(sample_off)), dtype=np.int64, count=len(sample_off) - 1)
+        return np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+
+    @staticmethod
+    def paste_frame_offsets(mfcc_frame_off: np.ndarray, pitch_frame_off: np.ndarray) -> np.ndarray:
+        """The paste rule: an utterance gets min(mfcc, pitch) frames when the two counts differ by at most 1 (paste-feats,
+        length tolerance 1); a larger difference is refused — on the host, before anything is launched."""
+        mf, pf = np.diff(np.asarray(mfcc_frame_off, dtype=np.int64)), np.diff(np.asarray(pitch_frame_off, dtype=np.int64))
+        bad = np.flatnonzero(np.abs(mf - pf) > 1)
+        if bad.size:
+            u = int(bad[0])
+            raise _lib.MfaHipError(f"utterance {u}: {int(mf[u])} MFCC frames and {int(pf[u])} pitch frames differ by more than 1 "
+                                   "(the two option sets must share frame shift, length and snip_edges)")
+        return np.concatenate([[0], np.cumsum(np.minimum(mf, pf))]).astype(np.int64)
+
+    def pitch_workspace_bytes(self, sample_off: np.ndarray, frame_off: np.ndarray) -> int:
+        self._need_pitch()
+        ns, nf = np.diff(sample_off), np.diff(frame_off)
+        return int(self.lib.mfa_pitch_workspace_bytes(self.ctx, len(ns), int(ns.sum()), int(nf.sum()), int(ns.max()) if len(ns) else 0,
+                                                      int(nf.max()) if len(nf) else 0))
+
+    def pitch_raw(self, pcm: torch.Tensor, sample_off: np.ndarray, frame_off: Optional[np.ndarray] = None):
+        """pcm: int16 [ΣN] on device at the pitch options' sample_frequency.  Returns (raw float32 [ΣT, 2] = (POV NCCF, pitch in
+        Hz) per frame, frame_off): the tracker's output before ProcessPitch (mfa_pitch_batch).  ``frame_off``, when given,
+        must hold the tracker's own frame counts."""
+        self._need_pitch()
+        assert pcm.dtype == torch.int16 and pcm.is_cuda
+        so = np.ascontiguousarray(sample_off, dtype=np.int64)
+        fo = self.pitch_frame_offsets(so) if frame_off is None else np.ascontiguousarray(frame_off, dtype=np.int64)
+        n_utt = so.shape[0] - 1
+        raw = torch.empty((int(fo[-1]), 2), dtype=torch.float32, device=self.device)
+        max_frames = int(np.diff(fo).max()) if n_utt else 0
+        d_so, d_fo = self._dev(so), self._dev(fo)
+        check(self.ctx, self.lib.mfa_pitch_batch(self.ctx, _ptr(pcm), _ptr(d_so), _ptr(d_fo), so.ctypes.data, fo.ctypes.data, n_utt,
+                                                 max_frames, _ptr(raw)), "mfa_pitch_batch")
+        return raw, fo
+
+    def pitch_process(self, raw: torch.Tensor, frame_off: np.ndarray, out: Optional[torch.Tensor] = None, col0: int = 0) -> torch.Tensor:
+        """ProcessPitch on the raw output: [ΣT, n_pitch_cols], or written into columns col0 … of ``out`` (a wider matrix)."""
+        self._need_pitch()
+        fo = np.ascontiguousarray(frame_off, dtype=np.int64)
+        n_utt = fo.shape[0] - 1
+        if out is None:
+            out = torch.empty((int(fo[-1]), self.num_pitch_cols), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] == int(fo[-1])
+        max_frames = int(np.diff(fo).max()) if n_utt else 0
+        check(self.ctx, self.lib.mfa_pitch_process_batch(self.ctx, _ptr(raw), _ptr(self._dev(fo)), n_utt, max_frames, _ptr(out),
+                                                         int(out.shape[1]), int(col0)), "mfa_pitch_process_batch")
+        return out
+
+    def pitch(self, pcm: torch.Tensor, sample_off: np.ndarray, frame_off: Optional[np.ndarray] = None) -> torch.Tensor:
+        """kalpy PitchComputer.compute_pitch for a batch: [ΣT, n_pitch_cols] (POV feature, normalised log-pitch, raw
+        log-pitch, each if configured)."""
+        raw, fo = self.pitch_raw(pcm, sample_off, frame_off)
+        return self.pitch_process(raw, fo)
+
+    def base_features(self, pcm: torch.Tensor, sample_off: np.ndarray):
+        """The base matrix of a use_pitch model: (float32 [ΣT, num_ceps + n_pitch_cols] = MFCC columns followed by the pitch
+        columns, frame_off), rows by the paste rule of ``paste_frame_offsets``.  The tracker always runs over its own frame
+        count (its trace-back starts at its last frame); a row the paste drops is dropped afterwards, as paste-feats does."""
+        self._need_pitch()
+        if self.mfcc_opts is None:
+            self.configure_mfcc()
+        so = np.ascontiguousarray(sample_off, dtype=np.int64)
+        pfo = self.pitch_frame_offsets(so)
+        fo = self.paste_frame_offsets(self.frame_offsets(so), pfo)
+        mfcc, _ = self.mfcc(pcm, so, fo)        # (fewer rows than the MFCC has: its frames do not depend on each other)
+        nc = self.num_ceps
+        base = torch.empty((int(fo[-1]), nc + self.num_pitch_cols), dtype=torch.float32, device=self.device)
+        base[:, :nc] = mfcc
+        raw, _ = self.pitch_raw(pcm, so, pfo)
+        if np.array_equal(pfo, fo):
+            self.pitch_process(raw, pfo, base, nc)
+        else:
+            rows = np.repeat(pfo[:-1] - fo[:-1], np.diff(fo)) + np.arange(int(fo[-1]), dtype=np.int64)
+            base[:, nc:] = self.pitch_process(raw, pfo)[self._dev(rows)]
+        return base, fo
+
+    def pad_cmvn_stats(self, stats: torch.Tensor, n_extra: int) -> torch.Tensor:
+        """Speaker CMVN statistics [n_spk, 2, dim + 1] of the MFCC columns → [n_spk, 2, dim + n_extra + 1] with zero sums in
+        the pitch columns (the count stays last): the feature kernel's offset −(0 / count) leaves those columns as they are —
+        pitch is pasted AFTER CMVN in the reference (MFA/alignment/multiprocessing.py:1290-1294)."""
+        n_spk, _, d1 = stats.shape
+        out = torch.zeros((n_spk, 2, d1 + n_extra), dtype=stats.dtype, device=stats.device)
+        out[:, :, : d1 - 1] = stats[:, :, : d1 - 1]
+        out[:, :, -1] = stats[:, :, -1]
+        return out
+
+    def pitch_time(self) -> Dict[str, float]:
+        """Accumulated time and launch groups of the pitch kernels under ``kernel_timing`` (slot 6)."""
+        ms, n = C.c_float(0), C.c_int(0)
+        check(self.ctx, self.lib.mfa_kernel_time_ms(self.ctx, 6, C.byref(ms), C.byref(n)), "mfa_kernel_time_ms")
+        return dict(ms=float(ms.value), launches=int(n.value))
 
     def frame_offsets(self, sample_off: np.ndarray) -> np.ndarray:
         frames = self.num_frames_array(np.diff(sample_off))

@@ -190,6 +190,77 @@ class MfccComputer:
             scp.write_text("".join(lines), encoding="utf8")
 
 
+class PitchComputer:
+    """``PitchComputer(**pitch_options)`` with kalpy's option names (MFA/corpus/features.py:687-688; MFA/models.py:551-576):
+    Kaldi's ComputeKaldiPitch + ProcessPitch on the device (include/mfa_hip.h, "Pitch and voicing").  Options not given take
+    Kaldi's defaults (max_f0 400, snip_edges True, POV and normalised log-pitch and DELTA-pitch on) — MFA names every flag;
+    ``add_delta_pitch=True`` is refused: Kaldi adds Gaussian noise to delta-pitch, which has no parity domain.
+    Like MfccComputer, every call puts this object's options in force on the process's engine (``get_engine()``; nothing is
+    rebuilt when they already are): an aligner that shares that engine must use the same pitch options."""
+
+    _KALDI = dict(max_f0=400.0, snip_edges=True, add_pov_feature=True, add_normalized_log_pitch=True, add_delta_pitch=True,
+                  add_raw_log_pitch=False)
+
+    def __init__(self, **options):
+        from .engine import DEFAULT_PITCH, _PITCH_ALIAS
+
+        self.parameters = dict(options)
+        opts = dict(self._KALDI)
+        for k, v in options.items():
+            if v is None:
+                continue
+            if _PITCH_ALIAS.get(k, k) not in DEFAULT_PITCH:
+                raise KeyError(f"unknown pitch option {k!r}")
+            opts[k] = v
+        if opts["add_delta_pitch"]:
+            raise ValueError("add_delta_pitch must be False: Kaldi adds Gaussian noise to delta-pitch, which is outside the parity domain")
+        self._opts = {k: (int(v) if isinstance(v, bool) else v) for k, v in opts.items()}
+        self.frame_shift = float(options.get("frame_shift", 10)) / 1000.0
+        self.sample_frequency = float(options.get("sample_frequency", DEFAULT_PITCH["sample_frequency"]))
+
+    def _configure(self):
+        eng = get_engine()
+        eng.configure_pitch(**self._opts)
+        return eng
+
+    def _pcm(self, eng, segment: Union[Segment, np.ndarray]):
+        """(device int16 samples at the options' rate, sample offsets): a file at another rate goes through the device
+        resampler first, as it does ahead of the MFCC — which the engine must then be configured for at the same rate."""
+        import torch
+
+        if not isinstance(segment, Segment):
+            pcm, rate = np.ascontiguousarray(segment, dtype=np.int16), None
+        else:
+            pcm, sr = segment.load_native()
+            rate = None if sr == self.sample_frequency else sr
+        d, so = torch.from_numpy(pcm.copy()).to(eng.device), np.array([0, pcm.shape[0]], dtype=np.int64)
+        if rate is not None:
+            if float(eng.model_rate()) != self.sample_frequency:
+                raise kaldi_io.KaldiFormatError(f"{segment.file_path}: {rate} Hz audio would be converted to the MFCC's "
+                                                f"{eng.model_rate()} Hz, the pitch options name {self.sample_frequency:g} Hz")
+            d, so = eng.resample(d, so, [rate])
+        return d, so
+
+    def compute_pitch(self, segment: Union[Segment, np.ndarray]) -> np.ndarray:
+        """float32 [T, columns]: POV feature, normalised log-pitch, raw log-pitch, each if its flag is set."""
+        eng = self._configure()
+        d, so = self._pcm(eng, segment)
+        return eng.pitch(d, so).cpu().numpy()
+
+    def compute_pitch_for_export(self, segment, compress: bool = True):
+        m = self.compute_pitch(segment)
+        return CompressedFeatures(m) if compress else m
+
+
+def paste_feats(mats: Sequence[np.ndarray], tolerance: int = 0) -> np.ndarray:
+    """Kaldi paste-feats: the matrices side by side, cut to the shortest when their row counts differ by at most
+    ``tolerance``; a larger difference raises."""
+    rows = [int(m.shape[0]) for m in mats]
+    if max(rows) - min(rows) > tolerance:
+        raise kaldi_io.KaldiFormatError(f"paste_feats: row counts {rows} differ by more than {tolerance}")
+    return np.concatenate([np.asarray(m, dtype=np.float32)[: min(rows)] for m in mats], axis=1)
+
+
 class CompressedFeatures(np.ndarray):
     """A float32 matrix tagged for 8-bit storage: ``FeatureArchive``/``write_features`` write it as Kaldi "CM"."""
 
@@ -367,19 +438,25 @@ class Utterance:
 
     def generate_features(self, mfcc_computer: MfccComputer, pitch_computer=None, lda_mat: Optional[np.ndarray] = None,
                           fmllr_trans: Optional[np.ndarray] = None, splice_context: int = 3) -> np.ndarray:
-        """CMVN → Δ+ΔΔ, or splice+LDA when ``lda_mat`` is given, then fMLLR when there is a transform
-        (MFA/alignment/multiprocessing.py:1287-1304)."""
+        """CMVN → (pitch pasted, when a ``pitch_computer`` is given) → Δ+ΔΔ, or splice+LDA when ``lda_mat`` is given, then
+        fMLLR when there is a transform (MFA/alignment/multiprocessing.py:1287-1304).  The CMVN statistics are those of the
+        MFCC columns; the pitch columns get zero sums, which the feature kernel's offset −(0 / count) leaves untouched."""
         import torch
 
-        if pitch_computer is not None:
-            raise NotImplementedError("pitch features are not part of this engine")
         if self.mfccs is None:
             self.generate_mfccs(mfcc_computer)
         eng = get_engine()
         dev = eng.device
-        frame_off = np.array([0, self.mfccs.shape[0]], dtype=np.int64)
-        d = torch.from_numpy(self.mfccs.astype(np.float32)).to(dev)
-        cm = None if self.cmvn is None else torch.from_numpy(self.cmvn[None].copy()).to(dev)
+        base, cmvn = self.mfccs.astype(np.float32), self.cmvn
+        if pitch_computer is not None:
+            pitch = pitch_computer.compute_pitch_for_export(self.segment, compress=False)
+            base = paste_feats([base, pitch], 1)
+            if cmvn is not None:
+                dim = self.mfccs.shape[1]
+                cmvn = np.concatenate([cmvn[:, :dim], np.zeros((2, pitch.shape[1])), cmvn[:, dim:]], axis=1)
+        frame_off = np.array([0, base.shape[0]], dtype=np.int64)
+        d = torch.from_numpy(base).to(dev)
+        cm = None if cmvn is None else torch.from_numpy(np.ascontiguousarray(cmvn)[None].copy()).to(dev)
         u2s = np.zeros(1, dtype=np.int32)
         lda = None if lda_mat is None else torch.from_numpy(np.asarray(lda_mat, dtype=np.float32)).to(dev)
         fm = fmllr_trans if fmllr_trans is not None else self.fmllr

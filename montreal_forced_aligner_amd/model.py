@@ -173,6 +173,26 @@ class DiagGmmModel:
             self.gconsts[a:b] += lf
 
 
+# kalpy PitchComputer option → (key of meta.json's "features", the reference's default)
+_PITCH_META = {"frame_shift": ("frame_shift", 10), "frame_length": ("frame_length", 25), "min_f0": ("min_f0", 50),
+               "max_f0": ("max_f0", 800), "sample_frequency": ("sample_frequency", 16000), "penalty_factor": ("penalty_factor", 0.1),
+               "delta_pitch": ("delta_pitch", 0.005), "snip_edges": ("snip_edges", True)}
+
+
+def pitch_options(meta: dict) -> dict:
+    """kalpy PitchComputer options of an acoustic model's ``meta.json`` (a dict with a ``features`` entry) — the mapping of
+    the reference's AcousticModel.pitch_options (MFA/models.py:551-576): ``use_pitch`` adds the normalised log-pitch, or the
+    raw one when ``normalize_pitch`` is off; ``use_voicing`` adds the POV feature; ``use_delta_pitch`` the delta-pitch."""
+    feats = meta.get("features", {})
+    pitch, normalize = bool(feats.get("use_pitch", False)), feats.get("normalize_pitch", True)
+    options = {name: feats.get(key, default) for name, (key, default) in _PITCH_META.items()}
+    options.update(add_pov_feature=feats.get("use_voicing", False), add_normalized_log_pitch=normalize if pitch else False,
+                   add_delta_pitch=feats.get("use_delta_pitch", False))
+    if pitch:                       # (the reference names this flag only for a use_pitch model)
+        options["add_raw_log_pitch"] = not normalize
+    return options
+
+
 def pdfs_of_phones(tm: TransitionModel, phones: Iterable[int]) -> List[int]:
     """Kaldi ``GetPdfsForPhones``: every pdf reachable from the given phone ids."""
     ph = set(int(p) for p in phones)
