@@ -5,15 +5,28 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "../../include/mfa_hip.h"
 
+#include "dev_buf.hpp"    // DevBuf, dev_upload_commit: the device memory a context owns
 #include "gmm_pack.hpp"   // mfa_packed_offset: the packed model layout
 #include "pitch_plan.hpp" // MfaPitchHostPlan: the pitch tracker's host tables
 
 enum { MFA_K_MFCC = 0, MFA_K_CMVN = 1, MFA_K_FEATS = 2, MFA_K_GMM = 3, MFA_K_VITERBI = 4, MFA_K_RESAMPLE = 5, MFA_K_PITCH = 6, MFA_K_COUNT = 7 };
+
+// The device operations of dev_buf.hpp as HIP calls.  Every device pointer a context owns is an MfaBuf: freed with the
+// context, grown with reserve(), tables replaced as a set with dev_upload_commit<MfaHipDev>().
+struct MfaHipDev {
+  static int alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+  static void free(void *p) { (void)hipFree(p); }   // nothing useful can be done with a failure here
+  static int copy_h2d(void *dst, const void *src, size_t bytes) { return (int)hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+  static int sync(hipStream_t s) { return (int)hipStreamSynchronize(s); }
+  static const char *describe(int code) { return hipGetErrorString((hipError_t)code); }
+};
+using MfaBuf = DevBuf<MfaHipDev>;
 
 // Resampler plan of one pair of rates on the device (resample.hip; the host plan is resample_plan.cpp's)
 struct MfaResampleDevicePlan {
@@ -24,8 +37,8 @@ struct MfaResampleDevicePlan {
   int back = 0;                // most inputs a phase's first tap lies before its output's position
   int chunk = 0, span = 0;     // outputs per staged run of a workgroup and the inputs staged for it
   bool table_in_lds = false;   // the phase table fits the workgroup's LDS beside the span
-  int32_t *d_first = nullptr;  // [phases] first input of the phase, relative to its unit
-  float *d_w = nullptr;        // [phases][stride], rows zero padded
+  MfaBuf d_first;              // int32 [phases] first input of the phase, relative to its unit
+  MfaBuf d_w;                  // float [phases][stride], rows zero padded
 };
 
 struct mfa_ctx {
@@ -47,70 +60,69 @@ struct mfa_ctx {
   mfa_mfcc_opts mfcc{};
   bool mfcc_ready = false;
   int win = 0, shift = 0, nfft = 0;
-  float *d_window = nullptr;   // [16][16][2] window pairs in lane order, see mfcc.hip
-  float *d_twiddle = nullptr;  // [2][16][16][2] W256^(i k1), W512^(i + 16 k2) in lane order, see mfcc.hip
-  float *d_melw = nullptr;     // [pieces][taps] filterbank piece weights, see mfcc.hip
-  int32_t *d_melidx = nullptr;  // [96] first FFT bin per piece + [32] (first piece | pieces << 8) per mel bin
+  MfaBuf d_window;             // float [16][16][2] window pairs in lane order, see mfcc.hip
+  MfaBuf d_twiddle;            // float [2][16][16][2] W256^(i k1), W512^(i + 16 k2) in lane order, see mfcc.hip
+  MfaBuf d_melw;               // float [pieces][taps] filterbank piece weights, see mfcc.hip
+  MfaBuf d_melidx;             // int32 [96] first FFT bin per piece + [32] (first piece | pieces << 8) per mel bin
   int n_melw = 0;              // filterbank pieces
   int mel_np_max = 1;
-  float *d_dct = nullptr;      // [nceps][nbins] with lifter folded separately
-  float *d_lifter = nullptr;   // [nceps]
+  MfaBuf d_dct;                // float [nceps][nbins] with lifter folded separately
+  MfaBuf d_lifter;             // float [nceps]
 
   std::vector<MfaResampleDevicePlan> resample_plans;   // one per (in_hz, out_hz) this context has resampled
 
   // pitch tracker (pitch.hip): the accepted options with their host tables, and the same tables on the device
   bool pitch_ready = false;
   MfaPitchHostPlan pitch;
-  float *d_pitch_f = nullptr;      // lags [S] | soft_min_f0 * lag [S] | penalties [S] | up-sampler rows [S][taps] | down-sampler rows
-  int32_t *d_pitch_i = nullptr;    // up-sampler first [S] | taps [S] | down-sampler first [phases] | taps [phases]
-  void *d_pitch_ws = nullptr;      // one sub-launch's resampled signals, POV NCCF rows and back-pointers
-  size_t pitch_ws_bytes = 0;
+  MfaBuf d_pitch_f;            // float lags [S] | soft_min_f0 * lag [S] | penalties [S] | up-sampler rows [S][taps] | down-sampler rows
+  MfaBuf d_pitch_i;            // int32 up-sampler first [S] | taps [S] | down-sampler first [phases] | taps [phases]
+  MfaBuf d_pitch_ws;           // one sub-launch's resampled signals, POV NCCF rows and back-pointers
 
   bool delta_uploaded = false; // feats.hip: this context has written the delta scales to its device's constant memory
 
-  // GMM model (device)
+  // GMM model (device).  mfa_load_gmm replaces all of it in one step, the buffers and the fields that describe them.
   bool gmm_ready = false;
   int dim = 0, kpad = 0, num_pdfs = 0, num_rows = 0;
-  float *d_w = nullptr;        // [num_rows][kpad] permuted weights
-  void *d_wb = nullptr;        // bf16×3 split of d_w for the bf16×3 kernels (gmm_pack.cpp), or NULL
-  void *d_wh = nullptr;        // f16×2 split of the column-scaled d_w for gmm_split_single_kernel<…, 2>, or NULL
-  float *d_gch = nullptr;      // gconsts × gmm_acc_scale
-  float *d_fscale = nullptr;   // [kpad] feature column scales of the f16 path
+  MfaBuf d_w;                  // float [num_rows][kpad] permuted weights
+  MfaBuf d_wb;                 // bf16×3 split of d_w for the bf16×3 kernels (gmm_pack.cpp), or empty
+  MfaBuf d_wh;                 // f16×2 split of the column-scaled d_w for gmm_split_single_kernel<…, 2>, or empty
+  MfaBuf d_gch;                // float gconsts × gmm_acc_scale
+  MfaBuf d_fscale;             // float [kpad] feature column scales of the f16 path
   float gmm_acc_scale = 1.0f;  // S: the f16 path's accumulators are S × the log-likelihood terms (power of two)
-  int *d_gmm_redo = nullptr;   // tiles the f16 pass handed to the bf16×3 pass
-  int64_t gmm_redo_cap = 0;
-  void *d_xsplit = nullptr;    // lazy scoring: f16 hi/lo operands of every 64-frame tile in register layout (gmm_presplit_kernel)
-  int *d_xsplit_bad = nullptr; // … and the tile's "a scaled feature left the f16 range" flag
-  int64_t xsplit_tiles = 0;
-  int32_t *d_col_row0 = nullptr;   // lazy scoring: first packed model row of every score column of the batch (row0[pdf_list[j]])
-  int64_t col_row0_cap = 0;
-  int32_t *d_band_ranges = nullptr; // [n_utt][11][2]: per window, the band's index range in each run of class 0 and in classes 2..4
-  int64_t band_ranges_cap = 0;
-  bool xsplit_ready = false;   // d_xsplit holds the operands of the batch mfa_align_features_batch is working on
-  float *d_gc = nullptr;       // [num_rows]
-  int32_t *d_row0 = nullptr;   // [num_pdfs] first packed row
-  int32_t *d_nblk = nullptr;   // [num_pdfs] number of 32-row blocks (slot 32) else 1
-  int32_t *d_slot = nullptr;   // [num_pdfs] slot class rows (1,4,8,16,32)
+  MfaBuf d_gc;                 // float [num_rows]
+  MfaBuf d_row0;               // int32 [num_pdfs] first packed row
+  MfaBuf d_nblk;               // int32 [num_pdfs] number of 32-row blocks (slot 32) else 1
+  MfaBuf d_slot;               // int32 [num_pdfs] slot class rows (1,4,8,16,32)
   std::vector<int32_t> h_slot, h_nblk, h_row0, h_ngauss;
-  float *d_w_stats = nullptr;  // packed rows of the fMLLR statistics model (two-model form; mfa_fmllr_stats_model) or NULL
+  MfaBuf d_w_stats;            // float packed rows of the fMLLR statistics model (two-model form; mfa_fmllr_stats_model) or empty
+  MfaBuf d_nrows;              // int32 [num_pdfs] packed rows per pdf (fmllr.hip builds it on first use)
   bool has_slot_class[5] = {false, false, false, false, false};   // model has pdfs of slot 32 / 16 / 8 / 4 / 1 rows
   bool has_single32 = false;       // some pdf is one 32-row block (17–32 Gaussians): gmm_split_single_kernel has work
   int max_nblk = 1;                // most 32-row blocks of any pdf
   bool has_multi_block = false;    // some pdf has more than 32 Gaussians (several blocks, merged by gmm_bf16_kernel)
   bool all_pdfs_32row = false;     // every pdf is a 32-row pdf, of one block or several (no work for the f32 kernel in bf16 mode)
-  int32_t *d_nrows = nullptr;  // [num_pdfs] packed rows per pdf (fmllr.hip)
-  int *d_gmm_queue = nullptr;  // work-item counters of the dense scoring launches (layout: kQueue… in mfa_gmm_score_batch), zeroed per call
-  int num_cus = 0;
-  void *vit_stamps = nullptr;  // debug: per-utterance phase cycle counters of the decoder (-DVIT_STAMPS builds)
-  void *gmm_trace = nullptr;   // debug: per-wavefront timeline records of the scoring kernel (mfa_debug_gmm_trace)
 
-  // Viterbi workspace
-  void *d_ws = nullptr;
-  size_t ws_bytes = 0;
-  void *d_gen_ws = nullptr;    // workspace of the general-graph decoder (viterbi_general.hip)
-  size_t gen_ws_bytes = 0;
-  int32_t *d_gen_list = nullptr;   // utterances of the general decoder's second tier (full token pool)
-  size_t gen_list_cap = 0;
+  // scoring scratch, grown on demand
+  // d_gmm_redo is shared by the dense scorer (gmm.hip) and the band scorer (gmm_band.hip): each call sizes and zeroes it
+  // for itself, and the calls are kept apart by the order of ctx->stream alone.
+  MfaBuf d_gmm_redo;           // int tiles the f16 pass handed to the bf16×3 pass
+  MfaBuf d_gmm_queue;          // int work-item counters of the dense scoring launches (layout: kQueue… in mfa_gmm_score_batch), zeroed per call
+  MfaBuf d_xsplit;             // lazy scoring: f16 hi/lo operands of every 64-frame tile in register layout (gmm_presplit_kernel)
+  MfaBuf d_xsplit_bad;         // int … and the tile's "a scaled feature left the f16 range" flag
+  bool xsplit_ready = false;   // d_xsplit holds the operands of the batch mfa_align_features_batch is working on
+  MfaBuf d_col_row0;           // int32 lazy scoring: first packed model row of every score column of the batch (row0[pdf_list[j]])
+  MfaBuf d_band_ranges;        // int32 [n_utt][11][2]: per window, the band's index range in each run of class 0 and in classes 2..4
+  int num_cus = 0;             // mfa_num_cus
+  // caller-owned debug buffers: not owned, never freed here
+  void *vit_stamps = nullptr;  // per-utterance phase cycle counters of the decoder (-DVIT_STAMPS builds)
+  void *gmm_trace = nullptr;   // per-wavefront timeline records of the scoring kernel (mfa_debug_gmm_trace)
+
+  // d_ws is one scratch buffer shared by the CMVN (feats.hip), Viterbi (viterbi.hip) and fMLLR statistics (fmllr.hip)
+  // stages: each lays its own workspace over it for the length of one call, and the order of ctx->stream is all that
+  // keeps them apart.
+  MfaBuf d_ws;
+  MfaBuf d_gen_ws;             // workspace of the general-graph decoder (viterbi_general.hip)
+  MfaBuf d_gen_list;           // int32 utterances of the general decoder's second tier (full token pool)
 
   int fail(const char *fmt, ...) {
     char buf[1024];
@@ -130,7 +142,6 @@ struct mfa_ctx {
   } while (0)
 
 // Debug aid (environment MFA_DEBUG_SYNC=1): name every launch on stderr, wait for it and report the first failing one.
-#include <cstdlib>
 inline bool mfa_debug_sync_enabled() {
   static const bool on = [] { const char *e = getenv("MFA_DEBUG_SYNC"); return e && e[0] == '1'; }();
   return on;
@@ -145,6 +156,17 @@ inline bool mfa_debug_sync_enabled() {
     }                                                                                                     \
   } while (0)
 
+// Compute units of the context's device, queried once.  Returns 0, with the context's error set, when the query fails.
+inline int mfa_num_cus(mfa_ctx *c) {
+  if (c->num_cus <= 0) {
+    hipDeviceProp_t prop;
+    const hipError_t e = hipGetDeviceProperties(&prop, c->device);
+    if (e != hipSuccess) { c->fail("hipGetDeviceProperties failed: %s", hipGetErrorString(e)); return 0; }
+    c->num_cus = prop.multiProcessorCount;
+  }
+  return c->num_cus;
+}
+
 // Workgroups of a strided launch: the list passes' scoring launches and the redo sweeps walk their items on a small fixed
 // grid (gmm_band_kernel<…, true>, gmm_band_f32_strided_kernel).  Four workgroups per CU: two rounds of what a CU holds of
 // the band kernel (two workgroups at its 256 VGPRs), so that a wavefront which meets real work holds up one item of the
@@ -152,17 +174,11 @@ inline bool mfa_debug_sync_enabled() {
 // launch never gets more workgroups than its full grid would have.  MFA_LIST_GRID=<workgroups> overrides (tests: 1 or 3
 // make every wavefront walk many items); launches over a grouped plan round up to a multiple of its runs, so there every
 // value up to the run count gives one workgroup per run.  Read at every call, as MFA_GMM_BF16 / MFA_GMM_F16 are (tests
-// flip it inside one process).  Returns 0 when the device cannot be queried.
+// flip it inside one process).  Returns 0, with the context's error set, when the device cannot be queried.
 inline int mfa_list_grid(mfa_ctx *c) {
   const char *e = getenv("MFA_LIST_GRID");
   const int forced = e ? atoi(e) : 0;
-  if (forced > 0) return forced;
-  if (c->num_cus <= 0) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return 0;
-    c->num_cus = prop.multiProcessorCount;
-  }
-  return 4 * c->num_cus;
+  return forced > 0 ? forced : 4 * mfa_num_cus(c);
 }
 
 // Scoped per-kernel timing (HIP events on the ctx stream, resolved lazily).

@@ -333,15 +333,11 @@ MFA_API int mfa_cmvn_stats(mfa_ctx *c, const float *d_feats, const int64_t *d_fr
   if (dim > kMaxDim) return c->fail("CMVN: feature dim %d > %d", dim, kMaxDim);
   if (n_utt <= 0 || n_spk <= 0) return 0;
   size_t need = (size_t)n_utt * 2 * (dim + 1) * sizeof(double);
-  if (c->ws_bytes < need) {
-    if (c->d_ws) { MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_ws); c->d_ws = nullptr; c->ws_bytes = 0; }
-    MFA_HIP_CHECK(c, hipMalloc(&c->d_ws, need));
-    c->ws_bytes = need;
-  }
+  if (c->d_ws.reserve(c, need, "the CMVN workspace")) return -1;
   KernelTimer kt(c, MFA_K_CMVN);
-  hipLaunchKernelGGL(cmvn_utt_kernel, dim3(n_utt), dim3(256), 0, c->stream, d_feats, d_frame_off, dim, (double *)c->d_ws);
+  hipLaunchKernelGGL(cmvn_utt_kernel, dim3(n_utt), dim3(256), 0, c->stream, d_feats, d_frame_off, dim, c->d_ws.ptr<double>());
   int total = n_spk * 2 * (dim + 1);
-  hipLaunchKernelGGL(cmvn_spk_kernel, dim3((total + 255) / 256), dim3(256), 0, c->stream, (const double *)c->d_ws,
+  hipLaunchKernelGGL(cmvn_spk_kernel, dim3((total + 255) / 256), dim3(256), 0, c->stream, c->d_ws.ptr<const double>(),
                      d_spk_utt_off, d_spk_utt, n_spk, dim, d_stats);
   MFA_HIP_CHECK(c, hipGetLastError());
   return 0;

@@ -181,22 +181,18 @@ MFA_API int mfa_fmllr_acc_batch(mfa_ctx *c, const float *d_feats, const int64_t 
   if (D > kMaxD) return c->fail("fMLLR statistics: feature dim %d > %d (the speaker kernel tiles (dim+1)^2 <= 1792 entries)", D, kMaxD);
   if (n_utt <= 0 || n_spk <= 0 || total_frames <= 0) return 0;
   size_t need = (size_t)total_frames * (2 * D + 1) * sizeof(float);
-  if (c->ws_bytes < need) {
-    if (c->d_ws) { MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_ws); c->d_ws = nullptr; c->ws_bytes = 0; }
-    MFA_HIP_CHECK(c, hipMalloc(&c->d_ws, need));
-    c->ws_bytes = need;
-  }
-  float *a = (float *)c->d_ws, *b = a + (size_t)total_frames * D, *cnt = b + (size_t)total_frames * D;
+  if (c->d_ws.reserve(c, need, "the fMLLR statistics workspace")) return -1;
+  float *a = c->d_ws.ptr<float>(), *b = a + (size_t)total_frames * D, *cnt = b + (size_t)total_frames * D;
   // rows per pdf (slot, or 32·nblk): derive on the fly from the slot/nblk tables kept by mfa_load_gmm
   if (!c->d_nrows) {
     std::vector<int32_t> nrows(c->num_pdfs);
     for (int p = 0; p < c->num_pdfs; p++) nrows[p] = c->h_slot[p] == 32 ? 32 * c->h_nblk[p] : c->h_slot[p];
     for (int p = 0; p < c->num_pdfs; p++)
       if (nrows[p] > 128) return c->fail("fMLLR statistics: pdf %d has more than 128 Gaussians", p);
-    MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_nrows, nrows.size() * 4));
-    MFA_HIP_CHECK(c, hipMemcpy(c->d_nrows, nrows.data(), nrows.size() * 4, hipMemcpyHostToDevice));
+    if (dev_upload_commit<MfaHipDev>(c, "the pdfs' row counts", {{&c->d_nrows, nrows.data(), nrows.size() * 4}})) return -1;
   }
-  FmllrFrameParams fp{D, c->kpad, c->d_w, c->d_gc, c->d_row0, c->d_nrows, c->d_w_stats ? c->d_w_stats : c->d_w,
+  FmllrFrameParams fp{D, c->kpad, c->d_w.ptr<float>(), c->d_gc.ptr<float>(), c->d_row0.ptr<int32_t>(), c->d_nrows.ptr<int32_t>(),
+                      (c->d_w_stats ? c->d_w_stats : c->d_w).ptr<float>(),
                       d_feats, d_ali_pdf, d_weight, total_frames, a, b, cnt};
   hipLaunchKernelGGL(fmllr_frame_kernel, dim3((unsigned)((total_frames + 3) / 4)), dim3(256), 0, c->stream, fp);
   FmllrSpkParams sp{D, d_feats, a, b, cnt, d_frame_off, d_spk_utt_off, d_spk_utt, d_beta, d_K, d_G};
@@ -233,8 +229,8 @@ MFA_API int mfa_fmllr_acc_ali_batch(mfa_ctx *c, const float *d_feats, const int6
 MFA_API int mfa_fmllr_stats_model(mfa_ctx *c, int32_t dim, int32_t num_pdfs, const int32_t *h_pdf_offsets,
                                   const float *h_means_invvars, const float *h_inv_vars) {
   MFA_HIP_CHECK(c, hipSetDevice(c->device));
-  if (c->d_w_stats) { MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_w_stats); c->d_w_stats = nullptr; }
-  if (!h_means_invvars) return 0;   // back to the single-model form
+  if (!h_means_invvars)   // back to the single-model form
+    return dev_upload_commit<MfaHipDev>(c, "the fMLLR statistics model", {{&c->d_w_stats, nullptr, 0}});
   if (!c->gmm_ready) return c->fail("mfa_load_gmm has not been called");
   if (dim != c->dim || num_pdfs != c->num_pdfs) return c->fail("fMLLR statistics model: %d pdfs of dim %d, loaded model has %d of dim %d", num_pdfs, dim, c->num_pdfs, c->dim);
   for (int p = 0; p < num_pdfs; p++)
@@ -243,9 +239,8 @@ MFA_API int mfa_fmllr_stats_model(mfa_ctx *c, int32_t dim, int32_t num_pdfs, con
   const int blocks = (c->num_rows + 1 + 31) / 32;
   std::vector<float> w((size_t)blocks * 32 * c->kpad, 0.0f);
   gmm_pack_rows(dim, num_pdfs, h_pdf_offsets, c->h_row0.data(), c->kpad, h_means_invvars, h_inv_vars, w);
-  MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_w_stats, w.size() * 4));
-  MFA_HIP_CHECK(c, hipMemcpy(c->d_w_stats, w.data(), w.size() * 4, hipMemcpyHostToDevice));
-  return 0;
+  // nothing was dropped above: a refused or failed statistics model leaves the previous one in force
+  return dev_upload_commit<MfaHipDev>(c, "the fMLLR statistics model", {{&c->d_w_stats, w.data(), w.size() * 4}});
 }
 
 }  // extern "C"

@@ -101,34 +101,33 @@ MFA_API int mfa_load_gmm(mfa_ctx *c, int32_t dim, int32_t num_pdfs, const int32_
   GmmPacked m;
   const int bad = gmm_pack_model(dim, num_pdfs, h_pdf_offsets, h_gconsts, h_means_invvars, h_inv_vars, m);
   if (bad) return c->fail("mfa_load_gmm: pdf %d has no Gaussians", -bad - 1);
-  // the previous model's arrays (d_w_stats and d_nrows belonged to its layout: fmllr.hip builds them on demand)
-  void **old[] = {(void **)&c->d_w, (void **)&c->d_gc, (void **)&c->d_row0, (void **)&c->d_nblk, (void **)&c->d_slot,
-                  (void **)&c->d_nrows, &c->d_wb, &c->d_wh, (void **)&c->d_gch, (void **)&c->d_fscale, (void **)&c->d_w_stats};
-  for (void **q : old) { if (*q) (void)hipFree(*q); *q = nullptr; }
-  auto upload = [&](auto &dst, const auto &v) -> int {
-    MFA_HIP_CHECK(c, hipMalloc((void **)&dst, v.size() * sizeof(v[0])));
-    MFA_HIP_CHECK(c, hipMemcpy(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-    return 0;
-  };
-  if (upload(c->d_w, m.w) || upload(c->d_gc, m.gc) || upload(c->d_row0, m.row0) || upload(c->d_nblk, m.nblk) ||
-      upload(c->d_slot, m.slot)) return -1;
-  if (m.split()) {
-    if (upload(c->d_wb, m.wb) || upload(c->d_wh, m.wh) || upload(c->d_gch, m.gch) || upload(c->d_fscale, m.fscale)) return -1;
-    c->gmm_acc_scale = m.acc_scale;
-  }
-  c->dim = dim; c->kpad = m.kpad; c->num_pdfs = num_pdfs; c->num_rows = m.rows;
-  c->h_slot = m.slot;
-  c->h_nblk = m.nblk;
-  c->h_row0.assign(m.row0.begin(), m.row0.begin() + num_pdfs);
-  c->h_ngauss.resize(num_pdfs);
-  for (int p = 0; p < num_pdfs; p++) c->h_ngauss[p] = h_pdf_offsets[p + 1] - h_pdf_offsets[p];
-  c->all_pdfs_32row = m.all_pdfs_32row;
-  c->has_multi_block = m.has_multi_block;
-  c->max_nblk = m.max_nblk;
-  for (int q = 0; q < 5; q++) c->has_slot_class[q] = m.has_slot_class[q];
-  c->has_single32 = m.has_single32;
-  c->gmm_ready = true;
-  return 0;
+  std::vector<int32_t> ngauss(num_pdfs);
+  for (int p = 0; p < num_pdfs; p++) ngauss[p] = h_pdf_offsets[p + 1] - h_pdf_offsets[p];
+  const bool split = m.split();
+  auto up = [](MfaBuf &dst, const auto &v) { return DevUpload<MfaHipDev>{&dst, v.data(), v.size() * sizeof(v[0])}; };
+  // An empty array empties its buffer: the split operands of a model that has none (gmm_pack_model leaves them empty, all
+  // but fscale), and d_w_stats and d_nrows, which belonged to the previous layout (fmllr.hip builds them on demand).
+  const std::vector<float> none;
+  return dev_upload_commit<MfaHipDev>(
+      c, "the acoustic model",
+      {up(c->d_w, m.w), up(c->d_gc, m.gc), up(c->d_row0, m.row0), up(c->d_nblk, m.nblk), up(c->d_slot, m.slot),
+       up(c->d_wb, m.wb), up(c->d_wh, m.wh), up(c->d_gch, m.gch), up(c->d_fscale, split ? m.fscale : none),
+       up(c->d_w_stats, none), up(c->d_nrows, none)},
+      [&] {
+        c->dim = dim; c->kpad = m.kpad; c->num_pdfs = num_pdfs; c->num_rows = m.rows;
+        if (split) c->gmm_acc_scale = m.acc_scale;
+        c->h_row0.assign(m.row0.begin(), m.row0.begin() + num_pdfs);
+        c->h_slot = std::move(m.slot);
+        c->h_nblk = std::move(m.nblk);
+        c->h_ngauss = std::move(ngauss);
+        c->all_pdfs_32row = m.all_pdfs_32row;
+        c->has_multi_block = m.has_multi_block;
+        c->max_nblk = m.max_nblk;
+        for (int q = 0; q < 5; q++) c->has_slot_class[q] = m.has_slot_class[q];
+        c->has_single32 = m.has_single32;
+        c->xsplit_ready = false;   // d_xsplit was scaled with the previous model's d_fscale
+        c->gmm_ready = true;
+      });
 }
 
 MFA_API int mfa_debug_gmm_trace(mfa_ctx *c, void *d_trace) {
@@ -146,7 +145,7 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *c, const float *d_feats, const int64_t 
   GmmParams p;
   memset(&p, 0, sizeof(p));   // every field this function does not set (the band-mode ones) must read as "off"
   p.dim = c->dim; p.kpad = c->kpad; p.num_rows = c->num_rows;
-  p.w = c->d_w; p.gc = c->d_gc; p.row0 = c->d_row0; p.nblk = c->d_nblk; p.slot = c->d_slot;
+  p.w = c->d_w.ptr<float>(); p.gc = c->d_gc.ptr<float>(); p.row0 = c->d_row0.ptr<int32_t>(); p.nblk = c->d_nblk.ptr<int32_t>(); p.slot = c->d_slot.ptr<int32_t>();
   p.feats = d_feats; p.frame_off = d_frame_off; p.pdf_list = d_pdf_list; p.pdf_off = d_pdf_off;
   p.class_counts = d_class_counts; p.ll_off = d_ll_off; p.out = d_loglikes;
   p.min_log_diff = logf(1.1920928955078125e-07f);
@@ -178,25 +177,23 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *c, const float *d_feats, const int64_t 
     constexpr int kQueueMulti = kQueueSmall + 6 * kQueueStride;        // gmm_bf16_kernel after gmm_split_single_kernel
     constexpr int kQueueMultiRedo = kQueueSmall + 7 * kQueueStride;    // … and its bf16×3 pass over declined tiles
     constexpr int kQueueInts = kQueueSmall + 8 * kQueueStride;
-    if (!c->d_gmm_queue) MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_gmm_queue, kQueueInts * sizeof(int)));
-    MFA_HIP_CHECK(c, hipMemsetAsync(c->d_gmm_queue, 0, kQueueInts * sizeof(int), c->stream));
-    p.queue = c->d_gmm_queue + kQueueFirst;
-    p.max_ff = c->d_gmm_queue + kQueueMaxFf;
+    if (c->d_gmm_queue.reserve(c, kQueueInts * sizeof(int), "the scoring launches' work counters")) return -1;
+    int *const queue = c->d_gmm_queue.ptr<int>();
+    MFA_HIP_CHECK(c, hipMemsetAsync(queue, 0, kQueueInts * sizeof(int), c->stream));
+    p.queue = queue + kQueueFirst;
+    p.max_ff = queue + kQueueMaxFf;
     if (d_pdf_first_frame)
       hipLaunchKernelGGL(gmm_max_first_frame_kernel, dim3(64), dim3(256), 0, c->stream, d_pdf_first_frame, d_pdf_off, n_utt,
-                         c->d_gmm_queue + kQueueMaxFf);
-    if (c->num_cus <= 0) {
-      hipDeviceProp_t prop;
-      MFA_HIP_CHECK(c, hipGetDeviceProperties(&prop, c->device));
-      c->num_cus = prop.multiProcessorCount;
-    }
+                         queue + kQueueMaxFf);
+    const int num_cus = mfa_num_cus(c);
+    if (num_cus <= 0) return -1;
     const int64_t items = (int64_t)n_utt * p.tiles;
-    const int64_t wgs = std::min<int64_t>((int64_t)c->num_cus * 2, items);
+    const int64_t wgs = std::min<int64_t>((int64_t)num_cus * 2, items);
     dim3 grid((unsigned)std::max<int64_t>(wgs, 1));
     const GmmSplitPasses passes = gmm_split_passes(c);
     // one launch of a kernel template whose first parameter is the model's 16-k step count
     auto launch = [&](auto kernel_of) { gmm_with_steps(c->kpad, [&](auto steps) { hipLaunchKernelGGL(kernel_of(steps), grid, dim3(256), 0, c->stream, p); }); };
-    p.wb = (const uint4 *)c->d_wb;
+    p.wb = c->d_wb.ptr<const uint4>();
     p.wh = nullptr; p.gch = nullptr; p.fscale = nullptr; p.acc_scale_inv = 1.0f; p.redo = nullptr; p.redo_mode = 0; p.redo_count = nullptr; p.skip_cc0 = 0;
     p.skip_single = 0;
     if (passes.bf16) {   // default on; MFA_GMM_BF16=0 keeps every class on the f32 kernel
@@ -207,31 +204,26 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *c, const float *d_feats, const int64_t 
       p.skip_cc0 = 0;
       if (f16_ok) {
         // an f16×2 pass scores every tile it can and flags the others for the bf16×3 pass that follows it
-        if (c->gmm_redo_cap < items) {
-          if (c->d_gmm_redo) (void)hipFree(c->d_gmm_redo);
-          c->d_gmm_redo = nullptr; c->gmm_redo_cap = 0;
-          MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_gmm_redo, items * sizeof(int)));
-          c->gmm_redo_cap = items;
-        }
-        MFA_HIP_CHECK(c, hipMemsetAsync(c->d_gmm_redo, 0, items * sizeof(int), c->stream));
-        p.wh = (const uint4 *)c->d_wh; p.gch = c->d_gch; p.fscale = c->d_fscale;
+        if (c->d_gmm_redo.reserve(c, (size_t)items * sizeof(int), "the scoring redo list")) return -1;
+        MFA_HIP_CHECK(c, hipMemsetAsync(c->d_gmm_redo.ptr(), 0, items * sizeof(int), c->stream));
+        p.wh = c->d_wh.ptr<const uint4>(); p.gch = c->d_gch.ptr<float>(); p.fscale = c->d_fscale.ptr<float>();
         p.acc_scale_inv = 1.0f / c->gmm_acc_scale;
-        p.redo = c->d_gmm_redo; p.redo_mode = 0; p.redo_count = c->d_gmm_queue + kQueueRedoCount;
+        p.redo = c->d_gmm_redo.ptr<int>(); p.redo_mode = 0; p.redo_count = queue + kQueueRedoCount;
       }
       if (use_f16) {
         launch([](auto steps) { return gmm_split_single_kernel<steps(), 2>; });
         p.redo_mode = 2;
-        p.queue = c->d_gmm_queue + kQueueSingleRedo;
+        p.queue = queue + kQueueSingleRedo;
         launch([](auto steps) { return gmm_split_single_kernel<steps(), 3>; });
         p.redo_mode = 0;
         p.skip_cc0 = 1;
-        p.queue = c->d_gmm_queue + kQueueMulti;
+        p.queue = queue + kQueueMulti;
       }
       if (c->has_multi_block) {                           // pdfs of more than 32 Gaussians (and, without f16, the whole 32-row class)
         if (f16_ok) {                                     // f16×2 pass, then the bf16×3 pass over the tiles it declined
           launch([](auto steps) { return gmm_bf16_kernel<steps(), 2>; });
           p.redo_mode = 2;
-          p.queue = c->d_gmm_queue + kQueueMultiRedo;
+          p.queue = queue + kQueueMultiRedo;
         }
         launch([](auto steps) { return gmm_bf16_kernel<steps(), 3>; });
         p.redo_mode = 0;
@@ -247,7 +239,7 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *c, const float *d_feats, const int64_t 
           if (!c->has_slot_class[cls_idx]) return;
           for (int pass = f16_ok ? 0 : 1; pass < 2; pass++) {
             p.redo_mode = f16_ok ? (pass == 0 ? 0 : 2) : 0;
-            p.queue = c->d_gmm_queue + qbase; qbase += kQueueStride;
+            p.queue = queue + qbase; qbase += kQueueStride;
             if (pass == 0) launch([=](auto steps) { return gmm_split_small_kernel<steps(), 2, slot_rows()>; });
             else launch([=](auto steps) { return gmm_split_small_kernel<steps(), 3, slot_rows()>; });
           }
@@ -255,7 +247,7 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *c, const float *d_feats, const int64_t 
         small(std::integral_constant<int, 16>{}, 1); small(std::integral_constant<int, 8>{}, 2); small(std::integral_constant<int, 4>{}, 3);
         p.skip_single = 2;
       }
-      p.queue = c->d_gmm_queue + kQueueF32;
+      p.queue = queue + kQueueF32;
     }
     const bool only_split_classes = !c->has_slot_class[4] && p.skip_single == 2;   // no single-Gaussian pdfs left over
     if (p.skip_single && (c->all_pdfs_32row || only_split_classes)) {

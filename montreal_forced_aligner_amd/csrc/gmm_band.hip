@@ -567,47 +567,34 @@ int mfa_gmm_presplit(mfa_ctx *c, const MfaLazyScoring *lazy, const int64_t *d_fr
   c->xsplit_ready = false;
   {   // first model row of every score column of the batch (the band kernels read nothing else to find a block)
     const int64_t cols_cap = (int64_t)n_utt * std::max(1, lazy->plan.max_cols);
-    if (c->col_row0_cap < cols_cap) {
-      MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-      if (c->d_col_row0) (void)hipFree(c->d_col_row0);
-      c->d_col_row0 = nullptr; c->col_row0_cap = 0;
-      MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_col_row0, (size_t)cols_cap * sizeof(int32_t)));
-      c->col_row0_cap = cols_cap;
-    }
+    if (c->d_col_row0.reserve(c, (size_t)cols_cap * sizeof(int32_t), "the score columns' row table")) return -1;
     GmmParams q;
     memset(&q, 0, sizeof(q));
-    q.row0 = c->d_row0; q.pdf_list = lazy->plan.d_pdf_list; q.pdf_off = lazy->plan.d_pdf_off; q.n_utt = n_utt;
-    q.nblk = c->d_nblk; q.col_nb_packed = col_nb_packed_for(c);
-    hipLaunchKernelGGL(gmm_col_rows_kernel, dim3(n_utt), dim3(256), 0, c->stream, q, c->d_col_row0);
+    q.row0 = c->d_row0.ptr<int32_t>(); q.pdf_list = lazy->plan.d_pdf_list; q.pdf_off = lazy->plan.d_pdf_off; q.n_utt = n_utt;
+    q.nblk = c->d_nblk.ptr<int32_t>(); q.col_nb_packed = col_nb_packed_for(c);
+    hipLaunchKernelGGL(gmm_col_rows_kernel, dim3(n_utt), dim3(256), 0, c->stream, q, c->d_col_row0.ptr<int32_t>());
     MFA_HIP_CHECK(c, hipGetLastError());
   }
   if (!gmm_split_passes(c).f16) return 0;   // no f16 pass (its operands exist for rows of 80 or 96 floats only): nothing to prepare
   const int64_t tiles = (total_frames >> 6) + n_utt + 1;
-  if (c->xsplit_tiles < tiles) {
-    MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    if (c->d_xsplit) (void)hipFree(c->d_xsplit);
-    if (c->d_xsplit_bad) (void)hipFree(c->d_xsplit_bad);
-    c->d_xsplit = nullptr; c->d_xsplit_bad = nullptr; c->xsplit_tiles = 0;
-    MFA_HIP_CHECK(c, hipMalloc(&c->d_xsplit, (size_t)tiles * 2 * 6 * 2 * 64 * 16));
-    MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_xsplit_bad, (size_t)tiles * sizeof(int)));
-    c->xsplit_tiles = tiles;
-  }
+  if (c->d_xsplit.reserve(c, (size_t)tiles * 2 * 6 * 2 * 64 * 16, "the pre-split feature operands") ||
+      c->d_xsplit_bad.reserve(c, (size_t)tiles * sizeof(int), "the pre-split tiles' range flags")) return -1;
   GmmParams p;
   memset(&p, 0, sizeof(p));
-  p.dim = c->dim; p.kpad = c->kpad; p.feats = lazy->d_feats; p.frame_off = d_frame_off; p.n_utt = n_utt; p.fscale = c->d_fscale;
+  p.dim = c->dim; p.kpad = c->kpad; p.feats = lazy->d_feats; p.frame_off = d_frame_off; p.n_utt = n_utt; p.fscale = c->d_fscale.ptr<float>();
   const int tiles_per_utt = (lazy->max_frames + 63) / 64;
   const int64_t waves = (int64_t)n_utt * tiles_per_utt;
   const dim3 grid((unsigned)((waves + 3) / 4));
   KernelTimer kt(c, MFA_K_GMM);
   gmm_with_steps(c->kpad, [&](auto steps) {
-    hipLaunchKernelGGL((gmm_presplit_kernel<steps()>), grid, dim3(256), 0, c->stream, p, (uint4 *)c->d_xsplit, c->d_xsplit_bad, tiles_per_utt);
+    hipLaunchKernelGGL((gmm_presplit_kernel<steps()>), grid, dim3(256), 0, c->stream, p, c->d_xsplit.ptr<uint4>(), c->d_xsplit_bad.ptr<int>(), tiles_per_utt);
   });
   MFA_HIP_CHECK(c, hipGetLastError());
   c->xsplit_ready = true;
   return 0;
 }
 
-const int32_t *mfa_band_ranges(mfa_ctx *c) { return c->d_band_ranges; }
+const int32_t *mfa_band_ranges(mfa_ctx *c) { return c->d_band_ranges.ptr<int32_t>(); }
 
 int mfa_gmm_score_window(mfa_ctx *c, const MfaLazyScoring *lazy, const MfaWindowScore *ws, const int64_t *d_frame_off,
                          int n_utt, const int64_t *d_ll_off, float *d_loglikes) {
@@ -617,7 +604,7 @@ int mfa_gmm_score_window(mfa_ctx *c, const MfaLazyScoring *lazy, const MfaWindow
   GmmParams p;
   memset(&p, 0, sizeof(p));
   p.dim = c->dim; p.kpad = c->kpad; p.num_rows = c->num_rows;
-  p.w = c->d_w; p.gc = c->d_gc; p.row0 = c->d_row0; p.nblk = c->d_nblk; p.slot = c->d_slot;
+  p.w = c->d_w.ptr<float>(); p.gc = c->d_gc.ptr<float>(); p.row0 = c->d_row0.ptr<int32_t>(); p.nblk = c->d_nblk.ptr<int32_t>(); p.slot = c->d_slot.ptr<int32_t>();
   p.feats = lazy->d_feats; p.frame_off = d_frame_off; p.pdf_list = lazy->plan.d_pdf_list; p.pdf_off = lazy->plan.d_pdf_off;
   p.class_counts = lazy->plan.d_class_counts; p.ll_off = d_ll_off; p.out = d_loglikes;
   p.min_log_diff = logf(1.1920928955078125e-07f);
@@ -644,41 +631,29 @@ int mfa_gmm_score_window(mfa_ctx *c, const MfaLazyScoring *lazy, const MfaWindow
   // redo sweep — walk their items on a small fixed grid (mfa_list_grid) instead of asking for one wavefront per item.
   const bool list_pass = ws->utt_list != nullptr;
   const int walk = mfa_list_grid(c);
-  if (walk <= 0) return c->fail("cannot size the list-pass grid: device properties unavailable");
+  if (walk <= 0) return -1;
   const unsigned runs = p.b_split ? (unsigned)p.groups : 1u;
   const unsigned full_per_run = std::max(1u, (unsigned)((split_waves + 3) / 4));
   const dim3 walk_grid(std::min(((unsigned)walk + runs - 1) / runs, full_per_run) * runs);
   const dim3 walk_grid_f32(std::min((unsigned)walk, std::max(1u, grid.x)));
   KernelTimer kt(c, MFA_K_GMM);
   {   // the band's index ranges, once per utterance (instead of once per scoring wavefront)
-    const int64_t need = (int64_t)n_utt * kRangeSlots * 2;
-    if (c->band_ranges_cap < need) {
-      MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-      if (c->d_band_ranges) (void)hipFree(c->d_band_ranges);
-      c->d_band_ranges = nullptr; c->band_ranges_cap = 0;
-      MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_band_ranges, (size_t)need * sizeof(int32_t)));
-      c->band_ranges_cap = need;
-    }
-    p.ranges = c->d_band_ranges;
+    if (c->d_band_ranges.reserve(c, (size_t)n_utt * kRangeSlots * 2 * sizeof(int32_t), "the band's index ranges")) return -1;
+    p.ranges = c->d_band_ranges.ptr<int32_t>();
     hipLaunchKernelGGL(gmm_band_ranges_kernel, dim3((unsigned)((n_utt + 3) / 4)), dim3(256), 0, c->stream, p);
   }
   const bool split_classes = c->has_single32 || c->has_multi_block || c->has_slot_class[1] || c->has_slot_class[2] || c->has_slot_class[3];
   if (passes.bf16 && split_classes) {
-    if (c->gmm_redo_cap < split_waves) {
-      if (c->d_gmm_redo) { MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_gmm_redo); }
-      c->d_gmm_redo = nullptr; c->gmm_redo_cap = 0;
-      MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_gmm_redo, split_waves * sizeof(int)));
-      c->gmm_redo_cap = split_waves;
-    }
-    p.redo = c->d_gmm_redo;
-    p.wb = (const uint4 *)c->d_wb;
-    p.col_row0 = c->d_col_row0;
+    if (c->d_gmm_redo.reserve(c, (size_t)split_waves * sizeof(int), "the scoring redo list")) return -1;
+    p.redo = c->d_gmm_redo.ptr<int>();
+    p.wb = c->d_wb.ptr<const uint4>();
+    p.col_row0 = c->d_col_row0.ptr<int32_t>();
     p.col_nb_packed = col_nb_packed_for(c);
     if (passes.f16) {
-      p.wh = (const uint4 *)c->d_wh; p.gch = c->d_gch; p.fscale = c->d_fscale;
+      p.wh = c->d_wh.ptr<const uint4>(); p.gch = c->d_gch.ptr<float>(); p.fscale = c->d_fscale.ptr<float>();
       p.acc_scale_inv = 1.0f / c->gmm_acc_scale;
       p.redo_mode = 0;
-      if (c->xsplit_ready) { p.xsplit = (const uint4 *)c->d_xsplit; p.xsplit_bad = c->d_xsplit_bad; }
+      if (c->xsplit_ready) { p.xsplit = c->d_xsplit.ptr<const uint4>(); p.xsplit_bad = c->d_xsplit_bad.ptr<int>(); }
       gmm_with_steps(c->kpad, [&](auto steps) {
         if (list_pass) hipLaunchKernelGGL((gmm_band_kernel<steps(), 2, true>), walk_grid, dim3(256), 0, c->stream, p);
         else hipLaunchKernelGGL((gmm_band_kernel<steps(), 2>), split_grid, dim3(256), 0, c->stream, p);

@@ -447,23 +447,18 @@ MFA_API int mfa_mfcc_configure(mfa_ctx *c, const mfa_mfcc_opts *o) {
   for (int i = 0; i < nc; i++)
     lifter[i] = o->cepstral_lifter != 0.0f ? (float)(1.0 + 0.5 * o->cepstral_lifter * sin(M_PI * i / o->cepstral_lifter)) : 1.0f;
 
-  auto upload = [&](void **dptr, const void *h, size_t bytes) -> int {
-    if (*dptr) { (void)hipFree(*dptr); *dptr = nullptr; }
-    MFA_HIP_CHECK(c, hipMalloc(dptr, bytes));
-    MFA_HIP_CHECK(c, hipMemcpy(*dptr, h, bytes, hipMemcpyHostToDevice));
-    return 0;
-  };
-  if (upload((void **)&c->d_window, wpairs.data(), wpairs.size() * 4)) return -1;
-  if (upload((void **)&c->d_twiddle, tw.data(), tw.size() * 4)) return -1;
-  if (upload((void **)&c->d_melw, piecew.data(), piecew.size() * 4)) return -1;
-  if (upload((void **)&c->d_melidx, melinfo.data(), melinfo.size() * 4)) return -1;
-  c->n_melw = n_pieces; c->mel_np_max = np_max;
-  if (upload((void **)&c->d_dct, dct.data(), dct.size() * 4)) return -1;
-  if (upload((void **)&c->d_lifter, lifter.data(), lifter.size() * 4)) return -1;
-  c->mfcc = *o;
-  c->win = win; c->shift = shift; c->nfft = nfft;
-  c->mfcc_ready = true;
-  return 0;
+  // a refused option set or a failed upload leaves the previous options and tables in force
+  return dev_upload_commit<MfaHipDev>(
+      c, "the MFCC tables",
+      {{&c->d_window, wpairs.data(), wpairs.size() * 4}, {&c->d_twiddle, tw.data(), tw.size() * 4},
+       {&c->d_melw, piecew.data(), piecew.size() * 4}, {&c->d_melidx, melinfo.data(), melinfo.size() * 4},
+       {&c->d_dct, dct.data(), dct.size() * 4}, {&c->d_lifter, lifter.data(), lifter.size() * 4}},
+      [&] {
+        c->n_melw = n_pieces; c->mel_np_max = np_max;
+        c->mfcc = *o;
+        c->win = win; c->shift = shift; c->nfft = nfft;
+        c->mfcc_ready = true;
+      });
 }
 
 MFA_API int32_t mfa_mfcc_num_frames(mfa_ctx *c, int64_t n) {
@@ -482,8 +477,8 @@ MFA_API int mfa_mfcc_batch(mfa_ctx *c, const int16_t *d_pcm, const int64_t *d_sa
   p.snip_edges = c->mfcc.snip_edges; p.remove_dc = c->mfcc.remove_dc_offset; p.preemph = c->mfcc.preemphasis;
   p.raw_energy = c->mfcc.raw_energy;
   p.log_energy_floor = c->mfcc.energy_floor > 0.0f ? logf(c->mfcc.energy_floor) : -INFINITY;
-  p.window = c->d_window; p.tw256 = c->d_twiddle; p.tw512 = c->d_twiddle + 512;
-  p.melw = c->d_melw; p.melinfo = c->d_melidx; p.dct = c->d_dct; p.lifter = c->d_lifter;
+  p.window = c->d_window.ptr<float>(); p.tw256 = c->d_twiddle.ptr<float>(); p.tw512 = p.tw256 + 512;
+  p.melw = c->d_melw.ptr<float>(); p.melinfo = c->d_melidx.ptr<int32_t>(); p.dct = c->d_dct.ptr<float>(); p.lifter = c->d_lifter.ptr<float>();
   p.n_pieces = c->n_melw; p.n_rounds = (c->n_melw + 15) / 16; p.np_max = c->mel_np_max;
   dim3 grid((max_frames + kFramesPerBlock - 1) / kFramesPerBlock, n_utt);
   KernelTimer kt(c, MFA_K_MFCC);

@@ -298,8 +298,8 @@ PitchParams params_of(mfa_ctx *c) {
   p.O = h.rs.phases; p.I = h.rs.in_per_unit; p.rs_max_taps = h.rs.max_taps;
   p.nccf_ballast = h.o.nccf_ballast;
   const size_t S = h.n_states;
-  p.lags = c->d_pitch_f; p.sml = p.lags + S; p.pen = p.sml + S; p.up_w = p.pen + S; p.rs_w = p.up_w + S * h.up_max_taps;
-  p.up_first = c->d_pitch_i; p.up_taps = p.up_first + S; p.rs_first = p.up_taps + S; p.rs_taps = p.rs_first + h.rs.phases;
+  p.lags = c->d_pitch_f.ptr<float>(); p.sml = p.lags + S; p.pen = p.sml + S; p.up_w = p.pen + S; p.rs_w = p.up_w + S * h.up_max_taps;
+  p.up_first = c->d_pitch_i.ptr<int32_t>(); p.up_taps = p.up_first + S; p.rs_first = p.up_taps + S; p.rs_taps = p.rs_first + h.rs.phases;
   p.pov_scale = h.o.pov_scale; p.pov_offset = h.o.pov_offset; p.pitch_scale = h.o.pitch_scale;
   p.norm_ctx = h.o.normalization_context;
   p.add_pov = h.o.add_pov_feature != 0; p.add_norm = h.o.add_normalized_log_pitch != 0; p.add_raw = h.o.add_raw_log_pitch != 0;
@@ -338,19 +338,15 @@ int track_batch(mfa_ctx *c, const int16_t *d_pcm, const int64_t *d_sample_off, c
     cuts.push_back(u1);
     u0 = u1;
   }
-  if (need > c->pitch_ws_bytes) {
-    if (c->d_pitch_ws) { MFA_HIP_CHECK(c, hipFree(c->d_pitch_ws)); c->d_pitch_ws = nullptr; c->pitch_ws_bytes = 0; }
-    if (hipMalloc(&c->d_pitch_ws, need) != hipSuccess) return c->fail("hipMalloc of the pitch workspace (%zu bytes) failed", need);
-    c->pitch_ws_bytes = need;
-  }
+  if (c->d_pitch_ws.reserve(c, need, "the pitch workspace")) return -1;
   KernelTimer kt(c, MFA_K_PITCH);
   for (size_t g = 0; g + 1 < cuts.size(); g++) {
     const int u0 = cuts[g], u1 = cuts[g + 1];
     const WsLayout l = ws_layout(h, u1 - u0, h_sample_off[u1] - h_sample_off[u0], h_frame_off[u1] - h_frame_off[u0]);
     int64_t max_rs = 0;
     for (int u = u0; u < u1; u++) max_rs = std::max(max_rs, rs_count(h_sample_off[u + 1] - h_sample_off[u], p.O, p.I));
-    float *ws_rs = (float *)c->d_pitch_ws, *ws_pov = ws_rs + l.rs_floats;
-    uint16_t *ws_bp = (uint16_t *)((char *)c->d_pitch_ws + l.bp_off);
+    float *ws_rs = c->d_pitch_ws.ptr<float>(), *ws_pov = ws_rs + l.rs_floats;
+    uint16_t *ws_bp = (uint16_t *)(c->d_pitch_ws.ptr<char>() + l.bp_off);
     const int64_t blocks = (max_rs + kRsPerBlock - 1) / kRsPerBlock;
     if (blocks > 0x7FFFFFFF) return c->fail("pitch: %lld resampled samples in one utterance", (long long)max_rs);
     if (blocks > 0) {
@@ -404,26 +400,9 @@ MFA_API int mfa_pitch_configure(mfa_ctx *c, const mfa_pitch_opts *opts) {
   iv.insert(iv.end(), h.up_taps.begin(), h.up_taps.end());
   iv.insert(iv.end(), h.rs.first.begin(), h.rs.first.end());
   iv.insert(iv.end(), h.rs.taps.begin(), h.rs.taps.end());
-  float *d_f = nullptr;
-  int32_t *d_i = nullptr;
-  MFA_HIP_CHECK(c, hipMalloc((void **)&d_f, f.size() * sizeof(float)));
-  hipError_t e = hipMalloc((void **)&d_i, iv.size() * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMemcpy(d_f, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_i, iv.data(), iv.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d_f); (void)hipFree(d_i);
-    return c->fail("upload of the pitch tables failed: %s", hipGetErrorString(e));
-  }
-  e = hipStreamSynchronize(c->stream);   // launches that read the previous tables are done
-  if (e != hipSuccess) {
-    (void)hipFree(d_f); (void)hipFree(d_i);
-    return c->fail("hipStreamSynchronize failed: %s", hipGetErrorString(e));
-  }
-  (void)hipFree(c->d_pitch_f); (void)hipFree(c->d_pitch_i);
-  c->d_pitch_f = d_f; c->d_pitch_i = d_i;
-  c->pitch = std::move(h);
-  c->pitch_ready = true;
-  return 0;
+  return dev_upload_commit<MfaHipDev>(c, "the pitch tables",
+                           {{&c->d_pitch_f, f.data(), f.size() * sizeof(float)}, {&c->d_pitch_i, iv.data(), iv.size() * sizeof(int32_t)}},
+                           [&] { c->pitch = std::move(h); c->pitch_ready = true; });
 }
 
 MFA_API int32_t mfa_pitch_num_frames(mfa_ctx *c, int64_t num_samples) {

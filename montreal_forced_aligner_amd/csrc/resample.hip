@@ -127,18 +127,10 @@ int plan_for(mfa_ctx *c, int32_t in_hz, int32_t out_hz, MfaResampleDevicePlan **
   std::vector<float> rows((size_t)h.phases * d.stride, 0.0f);
   for (int i = 0; i < h.phases; i++)
     std::copy(h.weights.begin() + (size_t)i * h.max_taps, h.weights.begin() + (size_t)(i + 1) * h.max_taps, rows.begin() + (size_t)i * d.stride);
-  MFA_HIP_CHECK(c, hipMalloc((void **)&d.d_first, h.first.size() * sizeof(int32_t)));
-  if (hipMalloc((void **)&d.d_w, rows.size() * sizeof(float)) != hipSuccess) {
-    (void)hipFree(d.d_first);
-    return c->fail("hipMalloc of the resampler's phase table (%zu bytes) failed", rows.size() * sizeof(float));
-  }
-  hipError_t e = hipMemcpy(d.d_first, h.first.data(), h.first.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d.d_w, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d.d_first); (void)hipFree(d.d_w);
-    return c->fail("upload of the resampler's phase table failed: %s", hipGetErrorString(e));
-  }
-  c->resample_plans.push_back(d);
+  if (dev_upload_commit<MfaHipDev>(c, "the resampler's phase table",
+                        {{&d.d_first, h.first.data(), h.first.size() * sizeof(int32_t)}, {&d.d_w, rows.data(), rows.size() * sizeof(float)}}))
+    return -1;
+  c->resample_plans.push_back(std::move(d));
   *out = &c->resample_plans.back();
   return 0;
 }
@@ -165,7 +157,7 @@ MFA_API int mfa_resample_batch(mfa_ctx *c, int32_t in_hz, int32_t out_hz, const 
   ResampleParams p;
   p.phases = d->phases; p.in_per_unit = d->in_per_unit; p.taps4 = d->taps4; p.stride = d->stride;
   p.back = d->back; p.chunk = d->chunk; p.span = d->span;
-  p.first = d->d_first; p.w = d->d_w;
+  p.first = d->d_first.ptr<int32_t>(); p.w = d->d_w.ptr<float>();
   dim3 grid((unsigned)blocks, (unsigned)n_sel);
   KernelTimer kt(c, MFA_K_RESAMPLE);
   if (d->table_in_lds) {

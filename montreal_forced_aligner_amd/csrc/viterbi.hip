@@ -171,12 +171,8 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
   if (eps && max_arcs >= (1 << 24)) return c->fail("graphs with epsilon arcs and more than 2^24 arcs are not supported");
   const int64_t eps_states = eps ? (int64_t)n_utt * max_states : 0;
   WsLayout w = ws_layout(n_utt, total_frames, Nw, Cw, bpf, total_arcs, eps_states);
-  if (c->ws_bytes < w.total) {
-    if (c->d_ws) { MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_ws); c->d_ws = nullptr; c->ws_bytes = 0; }
-    MFA_HIP_CHECK(c, hipMalloc(&c->d_ws, w.total));
-    c->ws_bytes = w.total;
-  }
-  unsigned char *base = (unsigned char *)c->d_ws;
+  if (c->d_ws.reserve(c, w.total, "the decoder workspace")) return -1;
+  unsigned char *base = c->d_ws.ptr<unsigned char>();
   hipLaunchKernelGGL(arcnext_kernel, dim3(n_utt), dim3(256), 0, c->stream, *g, (uint4 *)(base + w.arcnext),
                      eps ? (u32 *)(base + w.eps) : (u32 *)nullptr, max_states);
   // Launch plan.  The decoder is latency-bound (one wavefront walks one utterance frame by frame), so throughput is the

@@ -403,12 +403,8 @@ MFA_API int mfa_align_general_batch(mfa_ctx *c, const mfa_graph_batch *g, const 
       const size_t o_bp = take((size_t)nc * p.hcap * 4), o_bl = take((size_t)nc * p.hcap * 4);
       const size_t o_q = take((size_t)nc * p.qcap * 4), o_tmp = take((size_t)nc * p.ncap * 8);
       const size_t o_rev = take((size_t)nc * p.rev_cap * 4);
-      if (c->gen_ws_bytes < off) {
-        if (c->d_gen_ws) { MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_gen_ws); c->d_gen_ws = nullptr; c->gen_ws_bytes = 0; }
-        MFA_HIP_CHECK(c, hipMalloc(&c->d_gen_ws, off));
-        c->gen_ws_bytes = off;
-      }
-      unsigned char *base = (unsigned char *)c->d_gen_ws;
+      if (c->d_gen_ws.reserve(c, off, "the general decoder's workspace")) return -1;
+      unsigned char *base = c->d_gen_ws.ptr<unsigned char>();
       p.tok_cost = (double *)(base + o_cost); p.tok_arc = (int32_t *)(base + o_arc); p.tok_prev = (int32_t *)(base + o_prev);
       p.pool_off = (const int64_t *)(base + o_poff);
       p.el_key = (int32_t *)(base + o_ek); p.el_val = (int32_t *)(base + o_ev); p.el_tail = (int32_t *)(base + o_et);
@@ -437,15 +433,10 @@ MFA_API int mfa_align_general_batch(mfa_ctx *c, const mfa_graph_batch *g, const 
     for (int u = 0; u < n_utt; u++) if (st[u] == ST_BP_OVERFLOW) again.push_back(u);
     n_second = (int)again.size();
     if (n_second > 0) {
-      if (c->gen_list_cap < (size_t)n_second) {
-        if (c->d_gen_list) (void)hipFree(c->d_gen_list);
-        c->d_gen_list = nullptr; c->gen_list_cap = 0;
-        MFA_HIP_CHECK(c, hipMalloc((void **)&c->d_gen_list, (size_t)n_second * 4));
-        c->gen_list_cap = (size_t)n_second;
-      }
-      MFA_HIP_CHECK(c, hipMemcpyAsync(c->d_gen_list, again.data(), (size_t)n_second * 4, hipMemcpyHostToDevice, c->stream));
+      if (c->d_gen_list.reserve(c, (size_t)n_second * 4, "the general decoder's second-tier list")) return -1;
+      MFA_HIP_CHECK(c, hipMemcpyAsync(c->d_gen_list.ptr(), again.data(), (size_t)n_second * 4, hipMemcpyHostToDevice, c->stream));
       MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-      if (run_tier(n_second, &again, c->d_gen_list, ppf) != 0) return -1;
+      if (run_tier(n_second, &again, c->d_gen_list.ptr<int32_t>(), ppf) != 0) return -1;
     }
   }
   MFA_DEBUG_POINT(c, "general decoder: %d utterances in %d launches (%d again with the full pool), ncap %d hcap %d ppf %d", n_utt,
