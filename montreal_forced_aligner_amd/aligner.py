@@ -24,7 +24,7 @@ from . import _lib
 from . import fmllr as _fmllr
 from . import graph as _graph
 from . import sharding
-from .engine import AlignmentEngine, fmllr_statistics
+from .engine import AlignmentEngine, fmllr_statistics, redo_capacity
 from .model import DiagGmmModel, TransitionModel
 
 
@@ -437,40 +437,11 @@ class CorpusAligner:
         h = launched["host"]          # (pinned staging views: copied out, the buffers are reused two batches later)
         status, ali, words = h["status"].copy(), h["ali"].copy(), h["words"].copy()
         n_words, like = h["n_words"].copy(), h["like"].copy()
-        # Capacity overflows (status 3 tokens / 4 back-pointers) are not alignment failures: those utterances are decoded
-        # again on their own with the hard upper bounds (one token per graph state), which cannot overflow — and what still
-        # reports a capacity status then (the epsilon closure's pop budget on a pathological epsilon sub-graph) goes to the
-        # general decoder, which runs Kaldi's loops as they are.
-        over = np.flatnonzero((status == 3) | (status == 4)).tolist()
-        if over:
-            def take(ks):
-                fo_s = np.concatenate([[0], np.cumsum([fo[k + 1] - fo[k] for k in ks])]).astype(np.int64)
-                sel = np.concatenate([np.arange(fo[k], fo[k + 1]) for k in ks])
-                return fo_s, eng.gather_rows(feats, sel)
-
-            def merge(ks, fo_s, r):
-                st_, ali_, w_ = r["status"].cpu().numpy(), r["ali"].cpu().numpy(), r["words"].cpu().numpy()
-                nw_, like_ = r["n_words"].cpu().numpy(), r["like"].cpu().numpy()
-                for j, k in enumerate(ks):
-                    status[k] = st_[j]
-                    a, b = int(fo[k]), int(fo[k + 1])
-                    ali[a:b] = ali_[fo_s[j]: fo_s[j + 1]]
-                    n_words[k] = nw_[j]
-                    words[a: a + int(nw_[j])] = w_[fo_s[j]: fo_s[j] + int(nw_[j])]
-                    like[k] = like_[j]
-
-            sub = eng.pack_graphs([fsts[k] for k in over], self.tm)
-            fo2, f2 = take(over)
-            mt, bp = sub.hard_bounds()
-            merge(over, fo2, self._decode(sub, f2, fo2, mt, bp))
-            still = [k for k in over if status[k] in (3, 4)]
-            if still:
-                gg = eng.pack_graphs_general([fsts[k] for k in still], self.tm)
-                fo3, f3 = take(still)
-                merge(still, fo3, eng.align_general(gg, f3, fo3, beam=o.beam, retry_beam=o.retry_beam,
-                                                    acoustic_scale=o.acoustic_scale, bp_tokens_per_frame=2 * gg.max_states + 64))
-            if want_feats:
-                res["ali"] = torch.from_numpy(ali).to(eng.device)
+        # capacity overflows (status 3 tokens / 4 back-pointers) are decoded again: the merged alignments replace the
+        # device's copy when the fMLLR pass will read it
+        host = dict(status=status, ali=ali, words=words, n_words=n_words, like=like)
+        if redo_capacity(eng, fsts, self.tm, feats, fo, host, self._decode, o.beam, o.retry_beam, o.acoustic_scale) and want_feats:
+            res["ali"] = torch.from_numpy(ali).to(eng.device)
         out = _BatchOut(idx, fo, ali, words, n_words, like, status)
         ok = (status == 0) | (status == 1)
         for k in np.flatnonzero(ok).tolist():

@@ -43,6 +43,11 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _out_ptrs(out: Dict[str, Optional[torch.Tensor]]):
+    """The decoders' six output arguments, in the order all three entry points take them, from an ``_align_outputs`` dict."""
+    return [_ptr(out[k]) for k in ("ali", "words", "n_words", "like", "frame_like", "status")]
+
+
 def _split_passes(mono: bool, gauss_per_pdf: int) -> Tuple[bool, bool]:
     """(split-operand scoring at all, its f16x2 pass) for a model, as MFA_GMM_BF16 / MFA_GMM_F16 say right now (tests and the
     benchmark flip them inside one process, so nothing is cached)."""
@@ -53,6 +58,32 @@ def _split_passes(mono: bool, gauss_per_pdf: int) -> Tuple[bool, bool]:
 def _host_threads(share: float = 1.0, cap: int = 32) -> int:
     from . import hostcpu
     return hostcpu.threads(share, cap)
+
+
+def offsets(lengths, dtype=np.int64) -> np.ndarray:
+    """Lengths of n pieces laid end to end → where each starts, and the total last: [0, l0, l0 + l1, …], ``dtype`` [n + 1]."""
+    return np.concatenate([[0], np.cumsum(lengths)]).astype(dtype)
+
+
+def _rows_by_group(rows: np.ndarray, n_groups: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Utterances listed group by group (stable) and each group's range in that list, as the per-speaker kernels take them:
+    int32 [n], int32 [n_groups + 1].  A group may be empty."""
+    return np.argsort(rows, kind="stable").astype(np.int32), offsets(np.bincount(rows, minlength=n_groups), np.int32)
+
+
+def _speaker_groups(utt2spk) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """Speaker labels of any kind → (sorted distinct labels, each utterance's row among them, ``_rows_by_group`` of the rows)."""
+    spk_ids, inv = np.unique(np.asarray(utt2spk), return_inverse=True)
+    return (spk_ids, inv) + _rows_by_group(inv, len(spk_ids))
+
+
+def _flatten_fsts(fsts: Sequence[Fst]):
+    """A list of graphs end to end: (S [n], A [n], state_off, arc_base, arc_off int32 [ΣS + n], final float32 [ΣS], arcs)."""
+    S = np.array([f.num_states for f in fsts], dtype=np.int64)
+    A = np.array([f.num_arcs for f in fsts], dtype=np.int64)
+    arc_off = np.concatenate([f.arc_offsets.astype(np.int32) for f in fsts]) if len(fsts) else np.zeros(0, np.int32)
+    final = np.concatenate([f.final for f in fsts]).astype(np.float32)
+    return S, A, offsets(S), offsets(A), arc_off, final, np.concatenate([f.arcs for f in fsts])
 
 
 class RaggedView:
@@ -196,6 +227,10 @@ class AlignmentEngine:
         self._staging_turn = 0
         self._pcm_staging = [StagingPool(self.device), StagingPool(self.device)]   # PCM has its own pair: gathered while graphs compile
         self._pcm_turn = 0
+        self.pitch_opts: Optional[PitchOpts] = None      # configure_pitch
+        self.num_pitch_cols = 0
+        self._nf_checked: Optional[tuple] = None         # (window, shift, snip_edges) num_frames_array was checked for
+        self._slab, self._slab_off = None, 0             # _dev: pinned memory once asked for (False once refused), bump offset
 
     def next_staging(self) -> StagingPool:
         """The staging pool to fill next (round robin; waits until the copies last started from it are done)."""
@@ -290,7 +325,7 @@ class AlignmentEngine:
         snip = int(o.snip_edges)
         out = np.where(n < win, 0, 1 + (n - win) // shift) if snip else (n + shift // 2) // shift
         key = (win, shift, snip)
-        if getattr(self, "_nf_checked", None) != key:
+        if self._nf_checked != key:
             for probe in (0, 1, win - 1, win, win + shift - 1, win + shift, 159999, 160000, 160001, 1 << 20):
                 ref = (0 if probe < win else 1 + (probe - win) // shift) if snip else (probe + shift // 2) // shift
                 if self.num_frames(probe) != ref:
@@ -311,14 +346,13 @@ class AlignmentEngine:
         nbytes = a.nbytes
         if nbytes == 0 or nbytes > self._SLAB_BYTES // 4:
             return torch.from_numpy(a).to(self.device)
-        slab = getattr(self, "_slab", None)
+        slab = self._slab
         if slab is None:
             try:
                 slab = self._slab = torch.empty(self._SLAB_BYTES, dtype=torch.uint8, pin_memory=True)
             except RuntimeError:
                 self._slab = False
                 return torch.from_numpy(a).to(self.device)
-            self._slab_off = 0
         elif slab is False:
             return torch.from_numpy(a).to(self.device)
         off = (self._slab_off + 255) & ~255
@@ -330,6 +364,52 @@ class AlignmentEngine:
         view[...] = a
         with torch.cuda.device(self.device):
             return torch.from_numpy(view).to(self.device, non_blocking=True)
+
+    # ------------------------------------------------------------------ the hot path's entry points, each called from here alone
+    # Device tensors and offsets already on the device in, nothing allocated or uploaded: the stage methods below and
+    # ``Pipeline`` (persistent tensors) both launch through these.  ``out`` of the decoders: the dict of ``_align_outputs``.
+    def _launch_mfcc(self, pcm, d_sample_off, d_frame_off, n_utt: int, max_frames: int, out) -> None:
+        check(self.ctx, self.lib.mfa_mfcc_batch(self.ctx, _ptr(pcm), _ptr(d_sample_off), _ptr(d_frame_off), n_utt, max_frames,
+                                                _ptr(out)), "mfa_mfcc_batch")
+
+    def _launch_cmvn_stats(self, feats, d_frame_off, n_utt: int, dim: int, d_spk_off, d_spk_utt, n_spk: int, stats) -> None:
+        check(self.ctx, self.lib.mfa_cmvn_stats(self.ctx, _ptr(feats), _ptr(d_frame_off), n_utt, dim, _ptr(d_spk_off),
+                                                _ptr(d_spk_utt), n_spk, _ptr(stats)), "mfa_cmvn_stats")
+
+    def _launch_feats(self, mfcc, d_frame_off, n_utt: int, max_frames: int, dim: int, d_utt2spk, cmvn, lda, splice_context: int,
+                      fmllr, out) -> None:
+        """Δ+ΔΔ without ``lda``, splice + LDA with it."""
+        transform = (0, 0, None, 0, 0) if lda is None else (1, splice_context, _ptr(lda), int(lda.shape[0]), int(lda.shape[1]))
+        check(self.ctx, self.lib.mfa_feats_batch(self.ctx, _ptr(mfcc), _ptr(d_frame_off), n_utt, max_frames, dim, _ptr(d_utt2spk),
+                                                 _ptr(cmvn), *transform, _ptr(fmllr), _ptr(out)), "mfa_feats_batch")
+
+    def _launch_score(self, feats, d_frame_off, n_utt: int, max_frames: int, pdf_list, d_pdf_off, class_counts, pdf_first_frame,
+                      d_ll_off, out) -> None:
+        check(self.ctx, self.lib.mfa_gmm_score_batch(self.ctx, _ptr(feats), _ptr(d_frame_off), n_utt, max_frames, _ptr(pdf_list),
+                                                     _ptr(d_pdf_off), _ptr(class_counts), _ptr(pdf_first_frame), _ptr(d_ll_off),
+                                                     _ptr(out)), "mfa_gmm_score_batch")
+
+    def _launch_align(self, graphs: PackedGraphs, gstruct: GraphBatch, loglikes, d_ll_off, d_ll_cols, d_frame_off, total: int,
+                      opts: AlignOpts, out: Dict[str, Optional[torch.Tensor]]) -> None:
+        check(self.ctx, self.lib.mfa_align_batch(
+            self.ctx, C.byref(gstruct), _ptr(loglikes), _ptr(d_ll_off), _ptr(d_ll_cols), _ptr(d_frame_off), total,
+            graphs.total_arcs, graphs.max_states, graphs.max_arcs, C.byref(opts), *_out_ptrs(out)), "mfa_align_batch")
+
+    def _launch_align_features(self, graphs: PackedGraphs, gstruct: GraphBatch, plan: ScorePlan, feats, d_frame_off,
+                               max_frames: int, total: int, opts: AlignOpts, window: int, loglikes, d_ll_off, d_ll_cols,
+                               out: Dict[str, Optional[torch.Tensor]]) -> None:
+        check(self.ctx, self.lib.mfa_align_features_batch(
+            self.ctx, C.byref(gstruct), C.byref(plan), _ptr(feats), _ptr(d_frame_off), max_frames, total, graphs.total_arcs,
+            graphs.max_states, graphs.max_arcs, C.byref(opts), window, _ptr(loglikes), _ptr(d_ll_off), _ptr(d_ll_cols),
+            *_out_ptrs(out)), "mfa_align_features_batch")
+
+    def _align_outputs(self, n: int, total: int, want_frame_likes: bool) -> Dict[str, Optional[torch.Tensor]]:
+        """What a decoder writes: ali, words, frame_like (or None) [total]; n_words, like, status (−1: not decoded) [n]."""
+        dev, i32, f32 = self.device, torch.int32, torch.float32
+        return dict(ali=torch.zeros(total, dtype=i32, device=dev), words=torch.zeros(total, dtype=i32, device=dev),
+                    n_words=torch.zeros(n, dtype=i32, device=dev), like=torch.zeros(n, dtype=f32, device=dev),
+                    status=torch.full((n,), -1, dtype=i32, device=dev),
+                    frame_like=torch.zeros(total, dtype=f32, device=dev) if want_frame_likes else None)
 
     # ------------------------------------------------------------------ sample-rate conversion (ahead of the MFCC)
     def model_rate(self) -> int:
@@ -423,14 +503,14 @@ class AlignmentEngine:
         for k in _PITCH_INT:
             d[k] = int(d[k])
         opts = PitchOpts(**d)
-        if getattr(self, "pitch_opts", None) is not None and bytes(opts) == bytes(self.pitch_opts):
+        if self.pitch_opts is not None and bytes(opts) == bytes(self.pitch_opts):
             return                       # already in force: no tables to rebuild and upload
         check(self.ctx, self.lib.mfa_pitch_configure(self.ctx, C.byref(opts)), "mfa_pitch_configure")
         self.pitch_opts = opts
         self.num_pitch_cols = int(self.lib.mfa_pitch_num_columns(self.ctx))
 
     def _need_pitch(self) -> None:
-        if getattr(self, "pitch_opts", None) is None:
+        if self.pitch_opts is None:
             raise _lib.MfaHipError("configure_pitch has not been called")
 
     def pitch_num_frames(self, num_samples: int) -> int:
@@ -444,7 +524,7 @@ class AlignmentEngine:
         """Frame offsets of a batch's pitch features (the tracker's own frame counts, mfa_pitch_num_frames)."""
         self._need_pitch()
         frames = np.fromiter((self.pitch_num_frames(int(n)) for n in np.diff(sample_off)), dtype=np.int64, count=len(sample_off) - 1)
-        return np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+        return offsets(frames)
 
     @staticmethod
     def paste_frame_offsets(mfcc_frame_off: np.ndarray, pitch_frame_off: np.ndarray) -> np.ndarray:
@@ -456,7 +536,7 @@ class AlignmentEngine:
             u = int(bad[0])
             raise _lib.MfaHipError(f"utterance {u}: {int(mf[u])} MFCC frames and {int(pf[u])} pitch frames differ by more than 1 "
                                    "(the two option sets must share frame shift, length and snip_edges)")
-        return np.concatenate([[0], np.cumsum(np.minimum(mf, pf))]).astype(np.int64)
+        return offsets(np.minimum(mf, pf))
 
     def pitch_workspace_bytes(self, sample_off: np.ndarray, frame_off: np.ndarray) -> int:
         self._need_pitch()
@@ -533,13 +613,11 @@ class AlignmentEngine:
 
     def pitch_time(self) -> Dict[str, float]:
         """Accumulated time and launch groups of the pitch kernels under ``kernel_timing`` (slot 6)."""
-        ms, n = C.c_float(0), C.c_int(0)
-        check(self.ctx, self.lib.mfa_kernel_time_ms(self.ctx, 6, C.byref(ms), C.byref(n)), "mfa_kernel_time_ms")
-        return dict(ms=float(ms.value), launches=int(n.value))
+        return self._kernel_time(6)
 
     def frame_offsets(self, sample_off: np.ndarray) -> np.ndarray:
         frames = self.num_frames_array(np.diff(sample_off))
-        return np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+        return offsets(frames)
 
     def mfcc(self, pcm: torch.Tensor, sample_off: np.ndarray, frame_off: Optional[np.ndarray] = None):
         """pcm: int16 [ΣN] on device.  Returns (mfcc float32 [ΣT, num_ceps], frame_off host int64 [n+1])."""
@@ -553,20 +631,16 @@ class AlignmentEngine:
         out = torch.empty((total, self.num_ceps), dtype=torch.float32, device=self.device)
         d_so, d_fo = self._dev(sample_off.astype(np.int64)), self._dev(frame_off)
         max_frames = int(np.diff(frame_off).max()) if n_utt else 0
-        check(self.ctx, self.lib.mfa_mfcc_batch(self.ctx, _ptr(pcm), _ptr(d_so), _ptr(d_fo), n_utt, max_frames, _ptr(out)),
-              "mfa_mfcc_batch")
+        self._launch_mfcc(pcm, d_so, d_fo, n_utt, max_frames, out)
         return out, frame_off
 
     def cmvn_stats(self, feats: torch.Tensor, frame_off: np.ndarray, utt2spk: np.ndarray, n_spk: int) -> torch.Tensor:
         n_utt = len(frame_off) - 1
-        order = np.argsort(utt2spk, kind="stable").astype(np.int32)
-        counts = np.bincount(utt2spk, minlength=n_spk)
-        spk_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        order, spk_off = _rows_by_group(utt2spk, n_spk)
         dim = feats.shape[1]
         stats = torch.empty((n_spk, 2, dim + 1), dtype=torch.float64, device=self.device)
         d_fo, d_so, d_su = self._dev(frame_off), self._dev(spk_off), self._dev(order)
-        check(self.ctx, self.lib.mfa_cmvn_stats(self.ctx, _ptr(feats), _ptr(d_fo), n_utt, dim, _ptr(d_so), _ptr(d_su), n_spk,
-                                                _ptr(stats)), "mfa_cmvn_stats")
+        self._launch_cmvn_stats(feats, d_fo, n_utt, dim, d_so, d_su, n_spk, stats)
         return stats
 
     def features(self, mfcc: torch.Tensor, frame_off: np.ndarray, utt2spk: Optional[np.ndarray] = None,
@@ -582,16 +656,8 @@ class AlignmentEngine:
         d_fo = self._dev(frame_off)
         d_u2s = self._dev(np.asarray(utt2spk, dtype=np.int32)) if utt2spk is not None else None
         max_frames = int(np.diff(frame_off).max()) if n_utt else 0
-        if lda is None:
-            out = torch.empty((total, 3 * dim), dtype=torch.float32, device=self.device)
-            rc = self.lib.mfa_feats_batch(self.ctx, _ptr(mfcc), _ptr(d_fo), n_utt, max_frames, dim, _ptr(d_u2s), _ptr(cmvn), 0, 0,
-                                          None, 0, 0, _ptr(fmllr), _ptr(out))
-        else:
-            rows, cols = lda.shape
-            out = torch.empty((total, rows), dtype=torch.float32, device=self.device)
-            rc = self.lib.mfa_feats_batch(self.ctx, _ptr(mfcc), _ptr(d_fo), n_utt, max_frames, dim, _ptr(d_u2s), _ptr(cmvn), 1,
-                                          splice_context, _ptr(lda), rows, cols, _ptr(fmllr), _ptr(out))
-        check(self.ctx, rc, "mfa_feats_batch")
+        out = torch.empty((total, 3 * dim if lda is None else lda.shape[0]), dtype=torch.float32, device=self.device)
+        self._launch_feats(mfcc, d_fo, n_utt, max_frames, dim, d_u2s, cmvn, lda, splice_context, fmllr, out)
         return out
 
     def sort_pdf_list(self, pdfs: np.ndarray, first_frame: Optional[np.ndarray] = None):
@@ -638,27 +704,19 @@ class AlignmentEngine:
         n_utt = len(frame_off) - 1
         T = np.diff(frame_off)
         P = np.diff(pdf_off_host)
-        ll_off = np.concatenate([[0], np.cumsum(T * P)]).astype(np.int64)
+        ll_off = offsets(T * P)
         alloc = torch.empty if pdf_first_frame is None else torch.zeros
         out = alloc(int(ll_off[-1]), dtype=torch.float32, device=self.device)
         d_fo, d_po, d_lo = self._dev(frame_off), self._dev(pdf_off_host.astype(np.int64)), self._dev(ll_off)
         max_frames = int(T.max()) if n_utt else 0
-        check(self.ctx, self.lib.mfa_gmm_score_batch(self.ctx, _ptr(feats), _ptr(d_fo), n_utt, max_frames, _ptr(pdf_list),
-                                                     _ptr(d_po), _ptr(class_counts), _ptr(pdf_first_frame), _ptr(d_lo),
-                                                     _ptr(out)), "mfa_gmm_score_batch")
+        self._launch_score(feats, d_fo, n_utt, max_frames, pdf_list, d_po, class_counts, pdf_first_frame, d_lo, out)
         return out, ll_off, self._dev(P.astype(np.int32))
 
     def pack_graphs_general(self, fsts: Sequence[Fst], tm: TransitionModel) -> PackedGraphs:
         """Device layout for the general-graph decoder (mfa_align_general_batch): graphs may hold epsilon input arcs
         (ilabel 0) and states of any out-degree.  One score column per pdf, no depth keys (scores are computed densely)."""
         n = len(fsts)
-        S = np.array([f.num_states for f in fsts], dtype=np.int64)
-        A = np.array([f.num_arcs for f in fsts], dtype=np.int64)
-        state_off = np.concatenate([[0], np.cumsum(S)]).astype(np.int64)
-        arc_base = np.concatenate([[0], np.cumsum(A)]).astype(np.int64)
-        arc_off = np.concatenate([f.arc_offsets.astype(np.int32) for f in fsts]) if n else np.zeros(0, np.int32)
-        final = np.concatenate([f.final for f in fsts]).astype(np.float32)
-        arcs = np.concatenate([f.arcs for f in fsts])
+        S, A, state_off, arc_base, arc_off, final, arcs = _flatten_fsts(fsts)
         if np.any(arcs["ilabel"] < 0) or np.any(arcs["ilabel"] > tm.num_transition_ids):
             raise _lib.MfaHipError("a graph arc carries an input label outside the model's transition-ids")
         pdf_of_arc = tm.id2pdf[arcs["ilabel"]]            # -1 for epsilon arcs
@@ -674,43 +732,39 @@ class AlignmentEngine:
             cols[a0:a1] = np.where(emit, lut[np.maximum(pa, 0)], 0)
             pdf_lists.append(pl)
             counts.append(cc)
-        pdf_off = np.concatenate([[0], np.cumsum([len(p) for p in pdf_lists])]).astype(np.int64)
-        t = dict(
-            state_off=self._dev(state_off), arc_base=self._dev(arc_base),
-            start=self._dev(np.array([f.start for f in fsts], dtype=np.int32)),
-            arc_off=self._dev(arc_off), final=self._dev(final),
-            arc_next=self._dev(arcs["nextstate"].astype(np.int32)), arc_weight=self._dev(arcs["weight"].astype(np.float32)),
-            arc_col=self._dev(cols), arc_ilabel=self._dev(arcs["ilabel"].astype(np.int32)),
-            arc_olabel=self._dev(arcs["olabel"].astype(np.int32)),
-        )
+        pdf_off = offsets([len(p) for p in pdf_lists])
+        t = self._arc_tensors(state_off, arc_base, np.array([f.start for f in fsts], dtype=np.int32), arc_off, final, arcs,
+                              self._dev(cols))
         return PackedGraphs(n, int(S.max()) if n else 0, int(A.max()) if n else 0, int(A.sum()), t,
                             self._dev(np.concatenate(pdf_lists).astype(np.int32) if n else np.zeros(0, np.int32)),
                             self._dev(pdf_off), self._dev(np.stack(counts).astype(np.int32)), pdf_off, pdf_lists)
+
+    def _arc_tensors(self, state_off, arc_base, starts, arc_off, final, arcs, arc_col: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """mfa_graph_batch's arrays on the device from host arc records, one plain upload per column (``arc_col``: uploaded
+        by the caller, whose staging differs)."""
+        return dict(
+            state_off=self._dev(state_off), arc_base=self._dev(arc_base), start=self._dev(starts),
+            arc_off=self._dev(arc_off), final=self._dev(final),
+            arc_next=self._dev(arcs["nextstate"].astype(np.int32)), arc_weight=self._dev(arcs["weight"].astype(np.float32)),
+            arc_col=arc_col, arc_ilabel=self._dev(arcs["ilabel"].astype(np.int32)),
+            arc_olabel=self._dev(arcs["olabel"].astype(np.int32)),
+        )
 
     def align_general(self, graphs: PackedGraphs, feats: torch.Tensor, frame_off: np.ndarray, beam: float = 10.0,
                       retry_beam: float = 40.0, acoustic_scale: float = 0.1, bp_tokens_per_frame: int = 512,
                       want_frame_likes: bool = False):
         """Alignment over graphs with epsilon input arcs / wide states: dense scores, then FasterDecoder as Kaldi runs it
         (ProcessNonemitting included), one GPU thread per utterance — mfa_align_general_batch."""
-        n = graphs.n_utt
-        total = int(frame_off[-1])
-        dev = self.device
         ll, ll_off, ll_cols = self.score(feats, frame_off, graphs.pdf_list, graphs.pdf_off_host, graphs.class_counts)
-        ali = torch.zeros(total, dtype=torch.int32, device=dev)
-        words = torch.zeros(total, dtype=torch.int32, device=dev)
-        n_words = torch.zeros(n, dtype=torch.int32, device=dev)
-        like = torch.zeros(n, dtype=torch.float32, device=dev)
-        status = torch.full((n,), -1, dtype=torch.int32, device=dev)
-        flike = torch.zeros(total, dtype=torch.float32, device=dev) if want_frame_likes else None
+        out = self._align_outputs(graphs.n_utt, int(frame_off[-1]), want_frame_likes)
         opts = AlignOpts(beam, retry_beam, acoustic_scale, 0, bp_tokens_per_frame)
         gs = graphs.struct()
         d_lo, d_fo = self._dev(ll_off), self._dev(frame_off)
         h_fo = np.ascontiguousarray(frame_off, dtype=np.int64)
         check(self.ctx, self.lib.mfa_align_general_batch(self.ctx, C.byref(gs), _ptr(ll), _ptr(d_lo), _ptr(ll_cols), _ptr(d_fo),
                                                          h_fo.ctypes.data, graphs.max_states, graphs.max_arcs, C.byref(opts),
-                                                         _ptr(ali), _ptr(words), _ptr(n_words), _ptr(like), _ptr(flike),
-                                                         _ptr(status)), "mfa_align_general_batch")
-        return dict(ali=ali, words=words, n_words=n_words, like=like, status=status, frame_like=flike)
+                                                         *_out_ptrs(out)), "mfa_align_general_batch")
+        return out
 
     @staticmethod
     def needs_general_decoder(fst: Fst) -> bool:
@@ -755,13 +809,7 @@ class AlignmentEngine:
             arc_off = fsts.arc_off32 if columns else fsts.arc_off.astype(np.int32)
             final, arcs = np.ascontiguousarray(fsts.final, dtype=np.float32), fsts.arcs
         else:
-            S = np.array([f.num_states for f in fsts], dtype=np.int64)
-            A = np.array([f.num_arcs for f in fsts], dtype=np.int64)
-            state_off = np.concatenate([[0], np.cumsum(S)]).astype(np.int64)
-            arc_base = np.concatenate([[0], np.cumsum(A)]).astype(np.int64)
-            arc_off = np.concatenate([f.arc_offsets.astype(np.int32) for f in fsts]) if n else np.zeros(0, np.int32)
-            final = np.concatenate([f.final for f in fsts]).astype(np.float32)
-            arcs = np.concatenate([f.arcs for f in fsts])
+            S, A, state_off, arc_base, arc_off, final, arcs = _flatten_fsts(fsts)
         if self.slot_class is None:
             raise _lib.MfaHipError("pack_graphs needs the acoustic model's slot classes: call load_gmm first")
         nemit = None          # emitting arcs per state, for graphs with epsilon input arcs
@@ -828,7 +876,7 @@ class AlignmentEngine:
                                     "unsupported number of plan groups" if rc == -3 else "malformed graph"))
         cols = cols[:total_a]
         n_cols = n_cols[:n].astype(np.int64)
-        pdf_off = np.concatenate([[0], np.cumsum(n_cols)]).astype(np.int64)
+        pdf_off = offsets(n_cols)
         # utterance u's columns sit at [arc_base[u], arc_base[u] + n_cols[u]) of the column arrays: compact them
         take = np.repeat(arc_base[:-1] - pdf_off[:-1], n_cols) + np.arange(int(pdf_off[-1]), dtype=np.int64)
         pdf_all, first_all, last_all = cp[take], cf[take], cl[take]
@@ -852,14 +900,7 @@ class AlignmentEngine:
             )
             del rec
         else:
-            t = dict(
-                state_off=self._dev(state_off), arc_base=self._dev(arc_base),
-                start=self._dev(starts),
-                arc_off=self._dev(arc_off), final=self._dev(final),
-                arc_next=self._dev(arcs["nextstate"].astype(np.int32)), arc_weight=self._dev(arcs["weight"].astype(np.float32)),
-                arc_col=up(cols), arc_ilabel=self._dev(arcs["ilabel"].astype(np.int32)),
-                arc_olabel=self._dev(arcs["olabel"].astype(np.int32)),
-            )
+            t = self._arc_tensors(state_off, arc_base, starts, arc_off, final, arcs, up(cols))
         if nemit is not None:
             t["state_nemit"] = self._dev(nemit)
         sd_dev = up(sd_all[:total_s].reshape(-1)).view(-1, 2)
@@ -873,22 +914,12 @@ class AlignmentEngine:
               frame_off: np.ndarray, beam: float = 10.0, retry_beam: float = 40.0, acoustic_scale: float = 0.1,
               max_tokens: int = 1024, bp_tokens_per_frame: int = 512, want_frame_likes: bool = False):
         """Returns device tensors: ali [ΣT], words [ΣT] (+ n_words [n]), like [n], status [n], frame_like or None."""
-        n = graphs.n_utt
         total = int(frame_off[-1])
-        dev = self.device
-        ali = torch.zeros(total, dtype=torch.int32, device=dev)
-        words = torch.zeros(total, dtype=torch.int32, device=dev)
-        n_words = torch.zeros(n, dtype=torch.int32, device=dev)
-        like = torch.zeros(n, dtype=torch.float32, device=dev)
-        status = torch.full((n,), -1, dtype=torch.int32, device=dev)
-        flike = torch.zeros(total, dtype=torch.float32, device=dev) if want_frame_likes else None
+        out = self._align_outputs(graphs.n_utt, total, want_frame_likes)
         opts = AlignOpts(beam, retry_beam, acoustic_scale, max_tokens, bp_tokens_per_frame)
-        gs = graphs.struct()
         d_lo, d_fo = self._dev(ll_off), self._dev(frame_off)
-        check(self.ctx, self.lib.mfa_align_batch(self.ctx, C.byref(gs), _ptr(loglikes), _ptr(d_lo), _ptr(ll_cols), _ptr(d_fo),
-                                                 total, graphs.total_arcs, graphs.max_states, graphs.max_arcs, C.byref(opts), _ptr(ali), _ptr(words),
-                                                 _ptr(n_words), _ptr(like), _ptr(flike), _ptr(status)), "mfa_align_batch")
-        return dict(ali=ali, words=words, n_words=n_words, like=like, status=status, frame_like=flike)
+        self._launch_align(graphs, graphs.struct(), loglikes, d_lo, ll_cols, d_fo, total, opts, out)
+        return out
 
     def gather_rows(self, feats: torch.Tensor, rows: np.ndarray) -> torch.Tensor:
         """Rows ``rows`` of a device matrix as a new contiguous device matrix (device-to-device copies of the contiguous
@@ -913,46 +944,35 @@ class AlignmentEngine:
         [Σ T·P] (zero-filled here when omitted, so tests can see which cells were written)."""
         n = graphs.n_utt
         total = int(frame_off[-1])
-        dev = self.device
         T = np.diff(frame_off)
         P = np.diff(graphs.pdf_off_host)
-        ll_off = np.concatenate([[0], np.cumsum(T * P)]).astype(np.int64)
+        ll_off = offsets(T * P)
         if loglikes is None:
-            loglikes = torch.zeros(int(ll_off[-1]), dtype=torch.float32, device=dev)
-        ali = torch.zeros(total, dtype=torch.int32, device=dev)
-        words = torch.zeros(total, dtype=torch.int32, device=dev)
-        n_words = torch.zeros(n, dtype=torch.int32, device=dev)
-        like = torch.zeros(n, dtype=torch.float32, device=dev)
-        status = torch.full((n,), -1, dtype=torch.int32, device=dev)
-        flike = torch.zeros(total, dtype=torch.float32, device=dev) if want_frame_likes else None
+            loglikes = torch.zeros(int(ll_off[-1]), dtype=torch.float32, device=self.device)
+        out = self._align_outputs(n, total, want_frame_likes)
         opts = AlignOpts(beam, retry_beam, acoustic_scale, max_tokens, bp_tokens_per_frame)
         gs, plan = graphs.struct(), graphs.plan()
         d_lo, d_fo, d_cols = self._dev(ll_off), self._dev(frame_off), self._dev(P.astype(np.int32))
-        check(self.ctx, self.lib.mfa_align_features_batch(
-            self.ctx, C.byref(gs), C.byref(plan), _ptr(feats), _ptr(d_fo), int(T.max()) if n else 0, total, graphs.total_arcs,
-            graphs.max_states, graphs.max_arcs, C.byref(opts), int(window), _ptr(loglikes), _ptr(d_lo), _ptr(d_cols), _ptr(ali),
-            _ptr(words), _ptr(n_words), _ptr(like), _ptr(flike), _ptr(status)), "mfa_align_features_batch")
-        return dict(ali=ali, words=words, n_words=n_words, like=like, status=status, frame_like=flike, loglikes=loglikes,
-                    ll_off=ll_off)
+        self._launch_align_features(graphs, gs, plan, feats, d_fo, int(T.max()) if n else 0, total, opts, int(window), loglikes,
+                                    d_lo, d_cols, out)
+        return dict(out, loglikes=loglikes, ll_off=ll_off)
 
     # ------------------------------------------------------------------ timing helpers (bench.py)
     def kernel_timing(self, enable: bool) -> None:
         check(self.ctx, self.lib.mfa_kernel_timing(self.ctx, int(enable)), "mfa_kernel_timing")
 
+    def _kernel_time(self, slot: int) -> Dict[str, float]:
+        ms, n = C.c_float(0), C.c_int(0)
+        check(self.ctx, self.lib.mfa_kernel_time_ms(self.ctx, slot, C.byref(ms), C.byref(n)), "mfa_kernel_time_ms")
+        return dict(ms=float(ms.value), launches=int(n.value))
+
     def kernel_times(self) -> Dict[str, Dict[str, float]]:
-        out = {}
-        for i, name in enumerate(("mfcc", "cmvn", "feats", "gmm", "viterbi")):
-            ms, n = C.c_float(0), C.c_int(0)
-            check(self.ctx, self.lib.mfa_kernel_time_ms(self.ctx, i, C.byref(ms), C.byref(n)), "mfa_kernel_time_ms")
-            out[name] = dict(ms=float(ms.value), launches=int(n.value))
-        return out
+        return {name: self._kernel_time(i) for i, name in enumerate(("mfcc", "cmvn", "feats", "gmm", "viterbi"))}
 
     def resample_time(self) -> Dict[str, float]:
         """Accumulated time and launches of the resampling kernel under ``kernel_timing`` (kept out of ``kernel_times``: the
         benchmark's stage table lists the five stages of its step)."""
-        ms, n = C.c_float(0), C.c_int(0)
-        check(self.ctx, self.lib.mfa_kernel_time_ms(self.ctx, 5, C.byref(ms), C.byref(n)), "mfa_kernel_time_ms")
-        return dict(ms=float(ms.value), launches=int(n.value))
+        return self._kernel_time(5)
 
     def reset_kernel_times(self) -> None:
         check(self.ctx, self.lib.mfa_kernel_time_reset(self.ctx), "mfa_kernel_time_reset")
@@ -989,12 +1009,9 @@ class Pipeline:
         self.total_frames = int(self.frame_off[-1])
         self.max_frames = int(T.max())
         P = np.diff(graphs.pdf_off_host)
-        self.ll_off = np.concatenate([[0], np.cumsum(T * P)]).astype(np.int64)
-        utt2spk = np.asarray(utt2spk, dtype=np.int32)
-        spk_ids, inv = np.unique(utt2spk, return_inverse=True)
+        self.ll_off = offsets(T * P)
+        spk_ids, inv, order, spk_off = _speaker_groups(np.asarray(utt2spk, dtype=np.int32))
         self.n_spk = len(spk_ids)
-        order = np.argsort(inv, kind="stable").astype(np.int32)
-        spk_off = np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=self.n_spk))]).astype(np.int32)
         d = e._dev
         self.d_sample_off, self.d_frame_off = d(sample_off.astype(np.int64)), d(self.frame_off)
         self.d_utt2spk, self.d_spk_off, self.d_spk_utt = d(inv.astype(np.int32)), d(spk_off), d(order)
@@ -1003,18 +1020,19 @@ class Pipeline:
         self.feat_dim = 3 * self.num_ceps if lda is None else int(lda.shape[0])
         if lda is None and fmllr is not None:
             check_delta_fmllr(fmllr, self.num_ceps, inv)
-        f32, i32 = torch.float32, torch.int32
+        f32 = torch.float32
         self.mfcc = torch.empty((self.total_frames, self.num_ceps), dtype=f32, device=dev)
         self.cmvn = torch.empty((self.n_spk, 2, self.num_ceps + 1), dtype=torch.float64, device=dev)
         self.feats = torch.empty((self.total_frames, self.feat_dim), dtype=f32, device=dev)
         self.loglikes = torch.empty(int(self.ll_off[-1]), dtype=f32, device=dev)
-        self.ali = torch.zeros(self.total_frames, dtype=i32, device=dev)
-        self.words = torch.zeros(self.total_frames, dtype=i32, device=dev)
-        self.n_words = torch.zeros(self.n_utt, dtype=i32, device=dev)
-        self.like = torch.zeros(self.n_utt, dtype=f32, device=dev)
-        self.status = torch.full((self.n_utt,), -1, dtype=i32, device=dev)
+        self._out = e._align_outputs(self.n_utt, self.total_frames, False)     # (persistent: every step decodes into these)
+        self.ali, self.words, self.n_words, self.like, self.status = (self._out[k] for k in ("ali", "words", "n_words", "like", "status"))
         self.opts = AlignOpts(beam, retry_beam, acoustic_scale, max_tokens, bp_tokens_per_frame)
         self.gstruct = graphs.struct()
+        self._plan: Optional[ScorePlan] = None          # graphs.plan(), made by the first lazy step
+        self._states_times_frames: Optional[float] = None
+        # measure_scored_cells (bench.py hands one pipeline's figures to the others of the same shape)
+        self.cells_scored = self.cells_scored_fraction = self.scored_flops = None
         # algorithmic work of one step: GMM flops 4·D·g·P·T summed over utterances
         # With reachability a (frame, pdf) cell is algorithmically needed only from the pdf's first possible frame on.
         g_of_pdf = np.diff(e.gmm.pdf_offsets).astype(np.float64)
@@ -1038,14 +1056,11 @@ class Pipeline:
 
     def score_and_decode(self) -> None:
         """features + graphs → alignments, scores evaluated lazily per window (mfa_align_features_batch)."""
-        L, c, g = self.e.lib, self.e.ctx, self.graphs
-        if not hasattr(self, "_plan"):
-            self._plan = g.plan()
-        check(c, L.mfa_align_features_batch(
-            c, C.byref(self.gstruct), C.byref(self._plan), _ptr(self.feats), _ptr(self.d_frame_off), self.max_frames,
-            self.total_frames, g.total_arcs, g.max_states, g.max_arcs, C.byref(self.opts), self.window, _ptr(self.loglikes),
-            _ptr(self.d_ll_off), _ptr(self.d_ll_cols), _ptr(self.ali), _ptr(self.words), _ptr(self.n_words), _ptr(self.like),
-            None, _ptr(self.status)), "mfa_align_features_batch")
+        if self._plan is None:
+            self._plan = self.graphs.plan()
+        self.e._launch_align_features(self.graphs, self.gstruct, self._plan, self.feats, self.d_frame_off, self.max_frames,
+                                      self.total_frames, self.opts, self.window, self.loglikes, self.d_ll_off, self.d_ll_cols,
+                                      self._out)
 
     # ---- host side of the boundary: alignments land in (pinned) host memory
     def host_output_buffers(self, pinned: bool = True) -> Dict[str, torch.Tensor]:
@@ -1087,14 +1102,14 @@ class Pipeline:
         S = float(self.graphs.tensors["final"].numel())
         D = float(self.feat_dim)
         tot = float(T.sum())
-        written = getattr(self, "cells_scored", None) if self.lazy else None
+        written = self.cells_scored if self.lazy else None
         if written is None:
             written = float((P * T).sum())
         if score_cells_read is not None:
             read, how = float(score_cells_read), "4 B x cells the decoder read (oracle's lazy-decodable count on the CPU sample, scaled to the batch)"
         else:
             read, how = written, "4 B x cells the scoring stage wrote (upper bound of the cells the decoder read)"
-        if not hasattr(self, "_states_times_frames"):
+        if self._states_times_frames is None:
             self._states_times_frames = float((T * np.diff(self.graphs.tensors["state_off"].cpu().numpy())).sum())
         return {
             "mfcc": 2.0 * n_samples + 4.0 * self.num_ceps * tot,
@@ -1138,7 +1153,7 @@ class Pipeline:
         cells written — an upper bound)."""
         ms = ktimes[dominant]["ms"] / max(1, steps)
         launches = ktimes[dominant]["launches"] / max(1, steps)
-        lazy_measured = self.lazy and getattr(self, "scored_flops", None) is not None
+        lazy_measured = self.lazy and self.scored_flops is not None
         if dominant == "gmm":
             split, f16 = _split_passes(mono, gauss_per_pdf)
             mult = 3.0 if f16 else (6.0 if split else 1.0)
@@ -1151,7 +1166,7 @@ class Pipeline:
                     "frac": round(ach / peak, 4), "traffic": None,
                     "executed_flops_per_step": flops, "mfma_flops_per_algorithmic_flop": int(mult),
                     "executed_mfma_tflops": round(mult * ach, 3), "executed_mfma_frac_of_peak": round(mult * ach / peak, 4),
-                    "cells_scored_fraction": getattr(self, "cells_scored_fraction", None),
+                    "cells_scored_fraction": self.cells_scored_fraction,
                     "algorithmic_equivalent_tflops": round(equiv, 3), "ms_per_step": round(ms, 4), "launches_per_step": launches,
                     "note": "achieved = 4*D*g flops of the (frame, pdf) cells the scoring kernels actually computed / stage time; "
                             "executed_mfma_* = the same times the split-operand products per term; algorithmic_equivalent_tflops "
@@ -1171,35 +1186,71 @@ class Pipeline:
 
     def front(self) -> None:
         """PCM → MFCC → CMVN statistics → final features (three launches on the engine's stream)."""
-        L, c = self.e.lib, self.e.ctx
-        check(c, L.mfa_mfcc_batch(c, _ptr(self.pcm), _ptr(self.d_sample_off), _ptr(self.d_frame_off), self.n_utt,
-                                  self.max_frames, _ptr(self.mfcc)), "mfa_mfcc_batch")
-        check(c, L.mfa_cmvn_stats(c, _ptr(self.mfcc), _ptr(self.d_frame_off), self.n_utt, self.num_ceps, _ptr(self.d_spk_off),
-                                  _ptr(self.d_spk_utt), self.n_spk, _ptr(self.cmvn)), "mfa_cmvn_stats")
-        if self.lda is None:
-            rc = L.mfa_feats_batch(c, _ptr(self.mfcc), _ptr(self.d_frame_off), self.n_utt, self.max_frames, self.num_ceps,
-                                   _ptr(self.d_utt2spk), _ptr(self.cmvn), 0, 0, None, 0, 0, _ptr(self.fmllr), _ptr(self.feats))
-        else:
-            rc = L.mfa_feats_batch(c, _ptr(self.mfcc), _ptr(self.d_frame_off), self.n_utt, self.max_frames, self.num_ceps,
-                                   _ptr(self.d_utt2spk), _ptr(self.cmvn), 1, self.ctx_frames, _ptr(self.lda),
-                                   int(self.lda.shape[0]), int(self.lda.shape[1]), _ptr(self.fmllr), _ptr(self.feats))
-        check(c, rc, "mfa_feats_batch")
+        e = self.e
+        e._launch_mfcc(self.pcm, self.d_sample_off, self.d_frame_off, self.n_utt, self.max_frames, self.mfcc)
+        e._launch_cmvn_stats(self.mfcc, self.d_frame_off, self.n_utt, self.num_ceps, self.d_spk_off, self.d_spk_utt, self.n_spk,
+                             self.cmvn)
+        e._launch_feats(self.mfcc, self.d_frame_off, self.n_utt, self.max_frames, self.num_ceps, self.d_utt2spk, self.cmvn,
+                        self.lda, self.ctx_frames, self.fmllr, self.feats)
 
     def score(self) -> None:
         """features → GMM log-likelihoods of every utterance's pdf list."""
-        L, c, g = self.e.lib, self.e.ctx, self.graphs
-        check(c, L.mfa_gmm_score_batch(c, _ptr(self.feats), _ptr(self.d_frame_off), self.n_utt, self.max_frames,
-                                       _ptr(g.pdf_list), _ptr(g.pdf_off), _ptr(g.class_counts),
-                                       _ptr(g.pdf_first_frame) if self.reachability else None, _ptr(self.d_ll_off),
-                                       _ptr(self.loglikes)), "mfa_gmm_score_batch")
+        g = self.graphs
+        self.e._launch_score(self.feats, self.d_frame_off, self.n_utt, self.max_frames, g.pdf_list, g.pdf_off, g.class_counts,
+                             g.pdf_first_frame if self.reachability else None, self.d_ll_off, self.loglikes)
 
     def decode(self) -> None:
         """log-likelihoods + graphs → alignments (beam Viterbi, retry beam for the utterances that need it)."""
-        L, c, g = self.e.lib, self.e.ctx, self.graphs
-        check(c, L.mfa_align_batch(c, C.byref(self.gstruct), _ptr(self.loglikes), _ptr(self.d_ll_off), _ptr(self.d_ll_cols),
-                                   _ptr(self.d_frame_off), self.total_frames, g.total_arcs, g.max_states, g.max_arcs, C.byref(self.opts), _ptr(self.ali),
-                                   _ptr(self.words), _ptr(self.n_words), _ptr(self.like), None, _ptr(self.status)),
-              "mfa_align_batch")
+        self.e._launch_align(self.graphs, self.gstruct, self.loglikes, self.d_ll_off, self.d_ll_cols, self.d_frame_off,
+                             self.total_frames, self.opts, self._out)
+
+
+_PER_FRAME = ("ali", "words", "frame_like")          # decoder outputs over an utterance's frames; the others are one per utterance
+
+
+def _decode_again(eng, ks: List[int], feats, frame_off: np.ndarray, host: Dict[str, np.ndarray], run) -> None:
+    """Utterances ``ks`` of a batch as a batch of their own (their feature rows gathered) through ``run(feats, frame_off)``,
+    and what it returns merged over their entries of ``host``."""
+    fo_s = offsets([frame_off[k + 1] - frame_off[k] for k in ks])
+    r = run(eng.gather_rows(feats, np.concatenate([np.arange(frame_off[k], frame_off[k + 1]) for k in ks])), fo_s)
+    r = {key: r[key].cpu().numpy() for key in host}
+    for j, k in enumerate(ks):
+        a, b, a2, b2 = int(frame_off[k]), int(frame_off[k + 1]), int(fo_s[j]), int(fo_s[j + 1])
+        for key, dst in host.items():
+            if key in _PER_FRAME:
+                dst[a:b] = r[key][a2:b2]
+            else:
+                dst[k] = r[key][j]
+
+
+def redo_capacity(eng, fsts: Sequence[Fst], tm: TransitionModel, feats: torch.Tensor, frame_off: np.ndarray,
+                  host: Dict[str, np.ndarray], decode, beam: float, retry_beam: float, acoustic_scale: float) -> List[int]:
+    """The capacity ladder of a decoded batch.  Token / back-pointer overflows (status 3 / 4) are not alignment failures —
+    FasterDecoder has no such limits: those utterances are decoded again on their own with ``PackedGraphs.hard_bounds()``
+    (one token per graph state), which cannot overflow; what still reports a capacity status then (the epsilon closure's pop
+    budget on a pathological epsilon sub-graph) goes to the general decoder, which runs Kaldi's loops as they are, with
+    ``bp_tokens_per_frame = 2 * max_states + 64``.
+
+    ``fsts``: the batch's graphs with transition probabilities applied, by position; ``feats`` / ``frame_off``: its features
+    on the device and frame offsets on the host; ``host``: the first decode's results as host arrays, updated in place — its
+    keys say what is merged (``frame_like`` only when the caller brings it); ``decode(graphs, feats, frame_off, max_tokens,
+    bp_tokens_per_frame)``: the caller's decoder for the hard-bounds step.  Merging: per-utterance values by position,
+    per-frame arrays over the utterance's whole frame range — of ``words`` only the first ``n_words`` entries mean
+    anything, to the decoder and to every consumer.  Returns the positions decoded again; with none there is no device call
+    and nothing is packed."""
+    status = host["status"]
+    over = np.flatnonzero((status == 3) | (status == 4)).tolist()
+    if not over:
+        return over
+    sub = eng.pack_graphs([fsts[k] for k in over], tm)
+    _decode_again(eng, over, feats, frame_off, host, lambda f, fo: decode(sub, f, fo, *sub.hard_bounds()))
+    still = [k for k in over if status[k] in (3, 4)]
+    if still:
+        gg = eng.pack_graphs_general([fsts[k] for k in still], tm)
+        _decode_again(eng, still, feats, frame_off, host, lambda f, fo: eng.align_general(
+            gg, f, fo, beam=beam, retry_beam=retry_beam, acoustic_scale=acoustic_scale,
+            bp_tokens_per_frame=2 * gg.max_states + 64, want_frame_likes="frame_like" in host))
+    return over
 
 
 def check_delta_fmllr(fmllr, dim: int, utt2spk) -> None:
@@ -1253,10 +1304,8 @@ def fmllr_statistics(engine: "AlignmentEngine", feats: torch.Tensor, frame_off: 
     ali = ali.to(torch.int32).contiguous() if ali.dtype != torch.int32 else ali.contiguous()
     pdf = torch.empty(ali.shape[0], dtype=torch.int32, device=dev)       # scratch: the lookup runs inside the library
     weight = torch.empty(ali.shape[0], dtype=torch.float32, device=dev)
-    spk_ids, inv = np.unique(np.asarray(utt2spk), return_inverse=True)
+    spk_ids, _inv, order, spk_off = _speaker_groups(utt2spk)
     n_spk = len(spk_ids)
-    order = np.argsort(inv, kind="stable").astype(np.int32)
-    spk_off = np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=n_spk))]).astype(np.int32)
     D = feats.shape[1]
     beta = torch.zeros(n_spk, dtype=torch.float64, device=dev)
     K = torch.zeros((n_spk, D, D + 1), dtype=torch.float64, device=dev)

@@ -95,6 +95,7 @@ def fine_tune_boundaries(aligner, compiler: _graph.TrainingGraphCompiler, pcm: S
     utterance's begin).  ``intervals``: per utterance, phone CtmIntervals with ``symbol`` = phone id, sorted by begin.
     ``cmvn``: device tensor [n_spk, 2, dim+1] (the speakers' 10 ms statistics) or None; ``utt2spk`` indexes it."""
     import torch
+    from .engine import offsets
 
     eng = aligner._engine()
     tm = aligner.transition_model
@@ -110,7 +111,7 @@ def fine_tune_boundaries(aligner, compiler: _graph.TrainingGraphCompiler, pcm: S
     for w in windows:
         a, b = int(round(w.feature_begin * sample_rate)), int(round(w.feature_end * sample_rate))
         cuts.append(np.ascontiguousarray(pcm[w.utt][a:b], dtype=np.int16))
-    sample_off = np.concatenate([[0], np.cumsum([len(c) for c in cuts])]).astype(np.int64)
+    sample_off = offsets([len(c) for c in cuts])
     saved = dict(mfcc_options or {})
     eng.configure_mfcc(**{**saved, "frame_shift_ms": NEW_FRAME_SHIFT * 1000.0})
     try:
@@ -144,7 +145,7 @@ def fine_tune_boundaries(aligner, compiler: _graph.TrainingGraphCompiler, pcm: S
         if not sel:
             return {}
         graphs = eng.pack_graphs([fsts[k] for k in sel], tm)
-        fo = np.concatenate([[0], np.cumsum([new_off[k + 1] - new_off[k] for k in sel])]).astype(np.int64)
+        fo = offsets([new_off[k + 1] - new_off[k] for k in sel])
         idx = np.concatenate([np.arange(new_off[k], new_off[k + 1]) for k in sel])
         x = eng.gather_rows(sub, idx)
         ll, ll_off, ll_cols = eng.score(x, fo, graphs.pdf_list, graphs.pdf_off_host, graphs.class_counts,

@@ -156,6 +156,7 @@ class MfccComputer:
                      compress: bool = True, batch_size: int = 256) -> None:
         """``feats.*.ark`` (+ ``.scp``) for (key, segment) pairs, MFCCs computed in device batches (MfccFunction._run)."""
         import torch
+        from .engine import offsets
 
         ark = Path(file_name)
         scp = ark.with_suffix(".scp") if write_scp else None
@@ -170,7 +171,7 @@ class MfccComputer:
                     return
                 if eng is None:
                     eng = self._configure()
-                so = np.concatenate([[0], np.cumsum([len(x) for _, x, _ in batch])]).astype(np.int64)
+                so = offsets([len(x) for _, x, _ in batch])
                 d = torch.from_numpy(np.concatenate([x for _, x, _ in batch])).to(eng.device)
                 d, so = eng.resample(d, so, [r for _, _, r in batch])       # the whole batch in one call (a launch per rate)
                 out, fo = eng.mfcc(d, so)
@@ -272,9 +273,10 @@ class CmvnComputer:
     def compute_cmvn_from_features(self, feats: Sequence[np.ndarray]) -> np.ndarray:
         """Kaldi layout float64 [2, dim+1]: sums + count / sums of squares."""
         import torch
+        from .engine import offsets
 
         eng = get_engine()
-        frame_off = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int64)
+        frame_off = offsets([f.shape[0] for f in feats])
         d = torch.from_numpy(np.concatenate(feats).astype(np.float32)).to(eng.device)
         return eng.cmvn_stats(d, frame_off, np.zeros(len(feats), dtype=np.int32), 1).cpu().numpy()[0]
 
@@ -344,6 +346,7 @@ class FeatureArchive:
 
     def __iter__(self) -> Iterator[Tuple[str, np.ndarray]]:
         import torch
+        from .engine import offsets
 
         eng = get_engine()
         batch: List[Tuple[str, np.ndarray]] = []
@@ -370,7 +373,7 @@ class FeatureArchive:
                     if s in self._trans:
                         ft[i] = self._trans[s]
                 fm = torch.from_numpy(ft).to(eng.device)
-            fo = np.concatenate([[0], np.cumsum([m.shape[0] for _, m in batch])]).astype(np.int64)
+            fo = offsets([m.shape[0] for _, m in batch])
             d = torch.from_numpy(np.concatenate([m for _, m in batch]).astype(np.float32)).to(eng.device)
             if self.use_splices and lda is None:
                 raise NotImplementedError("spliced features without an LDA matrix")
@@ -586,6 +589,7 @@ class GmmAligner:
     def align_utterances(self, fsts: Sequence[kaldi_io.Fst], feats: Sequence[np.ndarray], utterance_ids=None) -> List[Optional[Alignment]]:
         """Batched form of ``align_utterance``: one device launch per stage for the whole list."""
         import torch
+        from .engine import offsets, redo_capacity
 
         eng = self._engine()
         general = [k for k, f in enumerate(fsts) if eng.needs_general_decoder(f)]
@@ -597,7 +601,7 @@ class GmmAligner:
                 for k, r in zip(part, self.align_utterances([fsts[k] for k in part], [feats[k] for k in part], ids)):
                     out[k] = r
             return out
-        frame_off = np.concatenate([[0], np.cumsum([x.shape[0] for x in feats])]).astype(np.int64)
+        frame_off = offsets([x.shape[0] for x in feats])
         d_feats = torch.from_numpy(np.concatenate(feats).astype(np.float32)).to(eng.device)
         if general:
             # graphs with epsilon input arcs (kalpy-compiled fsts.*.ark) or very wide states: FasterDecoder as Kaldi runs
@@ -614,39 +618,12 @@ class GmmAligner:
         res = eng.align_features(graphs, d_feats, frame_off, beam=self.beam, retry_beam=self.retry_beam,
                                  acoustic_scale=self.acoustic_scale, want_frame_likes=True)
         res = {k: res[k].cpu().numpy() for k in self._RESULT_KEYS}      # (not the score scratch: ΣT·P floats)
-        # Token / back-pointer capacity overflows (status 3 / 4) are not alignment failures — FasterDecoder has no such
-        # limit: those utterances are decoded again with the hard bounds (one token per graph state), which cannot
-        # overflow, exactly as CorpusAligner._pass does.
-        over = [u for u in range(len(fsts)) if int(res["status"][u]) in (3, 4)]
-        if over:
-            def take(us):
-                fo_s = np.concatenate([[0], np.cumsum([frame_off[u + 1] - frame_off[u] for u in us])]).astype(np.int64)
-                return fo_s, eng.gather_rows(d_feats, np.concatenate([np.arange(frame_off[u], frame_off[u + 1]) for u in us]))
-
-            def merge(us, fo_s, r):
-                r = {k: r[k].cpu().numpy() for k in self._RESULT_KEYS}
-                for j, u in enumerate(us):
-                    a, b, a2, b2 = int(frame_off[u]), int(frame_off[u + 1]), int(fo_s[j]), int(fo_s[j + 1])
-                    for k in ("ali", "words", "frame_like"):
-                        res[k][a:b] = r[k][a2:b2]
-                    for k in ("n_words", "like", "status"):
-                        res[k][u] = r[k][j]
-
-            sub = eng.pack_graphs([scaled_fsts[u] for u in over], self.transition_model)
-            fo2, f2 = take(over)
-            mt, bp = sub.hard_bounds()
-            merge(over, fo2, eng.align_features(sub, f2, fo2, beam=self.beam, retry_beam=self.retry_beam,
-                                                acoustic_scale=self.acoustic_scale, max_tokens=mt, bp_tokens_per_frame=bp,
-                                                want_frame_likes=True))
-            # what still reports a capacity status (the epsilon closure's pop budget on a pathological epsilon sub-graph)
-            # goes to the general decoder: Kaldi's loops as they are, no budget
-            still = [u for u in over if int(res["status"][u]) in (3, 4)]
-            if still:
-                gg = eng.pack_graphs_general([scaled_fsts[u] for u in still], self.transition_model)
-                fo3, f3 = take(still)
-                merge(still, fo3, eng.align_general(gg, f3, fo3, beam=self.beam, retry_beam=self.retry_beam,
-                                                    acoustic_scale=self.acoustic_scale, bp_tokens_per_frame=2 * gg.max_states + 64,
-                                                    want_frame_likes=True))
+        # token / back-pointer capacity overflows (status 3 / 4) are decoded again, as in the corpus pipeline
+        redo_capacity(eng, scaled_fsts, self.transition_model, d_feats, frame_off, res,
+                      lambda g, f, fo, mt, bp: eng.align_features(g, f, fo, beam=self.beam, retry_beam=self.retry_beam,
+                                                                  acoustic_scale=self.acoustic_scale, max_tokens=mt,
+                                                                  bp_tokens_per_frame=bp, want_frame_likes=True),
+                      self.beam, self.retry_beam, self.acoustic_scale)
         return self._collect(res, frame_off, len(fsts), utterance_ids)
 
     _RESULT_KEYS = ("ali", "words", "n_words", "like", "status", "frame_like")

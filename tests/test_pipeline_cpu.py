@@ -1,7 +1,7 @@
 """The corpus driver's software pipeline on the host: ``CorpusAligner._pass`` over several batches — graphs of batch b + 1
 compiled on the worker thread into rotating staging pools while batch b is packed, launched and collected — with the
-capacity redo of ``_collect`` (status 3/4 → hard bounds → general decoder, merged back by index) and the mixed-batch path of
-``_prepare``.  The native graph compiler, the staging pools and their rotation, ``_prepare``, ``_collect`` and its merge are
+capacity redo of ``_collect`` (``engine.redo_capacity``: status 3/4 → hard bounds → general decoder, merged back by index; also
+driven directly, with ``frame_like`` among the arrays) and the mixed-batch path of ``_prepare``.  The native graph compiler, the staging pools and their rotation, ``_prepare``, ``_collect`` and its merge are
 the real ones; the device (features, packing, the decoders) is a scripted stub whose "alignment" of an utterance names the
 utterance it was decoded for, so a graph read from a reused pool or a result merged into the wrong slot shows.
 
@@ -12,7 +12,7 @@ import torch
 from montreal_forced_aligner_amd import _lib
 from montreal_forced_aligner_amd import kaldi_io as K
 from montreal_forced_aligner_amd.aligner import AlignOptions, CorpusAligner, CorpusUtterance
-from montreal_forced_aligner_amd.engine import AlignmentEngine, StagingPool
+from montreal_forced_aligner_amd.engine import AlignmentEngine, StagingPool, _speaker_groups, offsets, redo_capacity
 from tests import helpers
 
 T = 50                      # frames per utterance (the stub's 160 samples per frame)
@@ -93,6 +93,7 @@ class StubEngine:
         n, total = graphs.n_utt, int(fo[-1])
         status, n_words = np.zeros(n, np.int32), np.zeros(n, np.int32)
         ali, words, like = np.zeros(total, np.int32), np.zeros(total, np.int32), np.zeros(n, np.float32)
+        frame_like = np.zeros(total, np.float32)
         for j, u in enumerate(graphs.utts):
             a, b = int(fo[j]), int(fo[j + 1])
             self.calls.append((stage, u))
@@ -102,7 +103,9 @@ class StubEngine:
             ali[a:b] = _ali_code(u, stage)
             words[a], words[a + 1], n_words[j] = u, STAGE[stage], 2
             like[j] = _like(u, stage)
-        return {k: torch.from_numpy(v) for k, v in dict(status=status, ali=ali, words=words, n_words=n_words, like=like).items()}
+            frame_like[a:b] = _frame_like(u, stage)
+        return {k: torch.from_numpy(v) for k, v in dict(status=status, ali=ali, words=words, n_words=n_words, like=like,
+                                                        frame_like=frame_like).items()}
 
 
 def _ali_code(u, stage):
@@ -111,6 +114,10 @@ def _ali_code(u, stage):
 
 def _like(u, stage):
     return np.float32(-u - 0.25 * STAGE[stage])
+
+
+def _frame_like(u, stage):
+    return np.float32(-0.5 * u - 0.125 * STAGE[stage])
 
 
 def _texts(n):
@@ -308,6 +315,62 @@ def test_two_passes_in_a_row(fx, monkeypatch):
     _run_and_check(al, eng, utts, own, SCRIPT_CONSECUTIVE, passes=2)
 
 
+# ------------------------------------------------------------------------------------------- the shared ladder, directly
+RESULT_KEYS = ("ali", "words", "n_words", "like", "status", "frame_like")
+
+
+def _ladder(fx, script, n=5):
+    """One batch of ``n`` utterances of T frames through the stub's first decode, then ``redo_capacity`` on the host copy
+    of its results (``frame_like`` among them).  Returns the stub, the arrays before and after, and the positions redone."""
+    texts = _texts(n)
+    eng = StubEngine(script)
+    al = CorpusAligner(fx.mono_tm, fx.mono_am, fx.mono_tree, fx.mono_lex, engine=eng)
+    fsts = [al.compiler.compile_fsts([t], al.scaled, columns=True)[0] for t in texts]
+    for u, f in enumerate(fsts):
+        eng.expected[_key(f)] = u
+    feats, fo = _feats(range(n)), _fo(n)
+    first = eng._decode(_Graphs(list(range(n))), feats, fo, "first")
+    host = {k: first[k].numpy().copy() for k in RESULT_KEYS}
+    before = {k: v.copy() for k, v in host.items()}
+    eng.calls.clear()
+
+    def decode(graphs, f, o, max_tokens, bp_tokens_per_frame):
+        assert (max_tokens, bp_tokens_per_frame) == graphs.hard_bounds()
+        return eng.align_features(graphs, f, o, max_tokens=max_tokens, bp_tokens_per_frame=bp_tokens_per_frame)
+
+    redone = redo_capacity(eng, fsts, fx.mono_tm, feats, fo, host, decode, 10.0, 40.0, 0.1)
+    return eng, before, host, redone
+
+
+def test_ladder_merges_every_array_of_every_stage(fx):
+    """Statuses 0, 3, 4, 2, 3 at the first decode; utterance 2 still 4 with the hard bounds (on to the general decoder),
+    utterance 4 fails (2) there: each utterance's ali, words[:n_words], n_words, like, status and frame_like are those of
+    the last stage it went through, and utterances 0 and 3 — no capacity status — keep every byte of theirs."""
+    script = {1: {"first": 3}, 2: {"first": 4, "hard": 4}, 3: {"first": 2}, 4: {"first": 3, "hard": 2}}
+    eng, before, host, redone = _ladder(fx, script)
+    assert redone == [1, 2, 4]
+    assert sorted(eng.calls) == sorted([("hard", 1), ("hard", 2), ("hard", 4), ("general", 2)])
+    assert eng.packed == [("pack_graphs", [1, 2, 4]), ("pack_graphs_general", [2])]
+    assert eng.bad_rows == []
+    final = {0: ("first", 0), 1: ("hard", 0), 2: ("general", 0), 3: ("first", 2), 4: ("hard", 2)}
+    for u, (stage, status) in final.items():
+        a, b = u * T, (u + 1) * T
+        assert np.all(host["ali"][a:b] == _ali_code(u, stage)), u
+        assert int(host["n_words"][u]) == 2 and list(host["words"][a: a + 2]) == [u, STAGE[stage]], u
+        assert host["like"][u] == _like(u, stage) and int(host["status"][u]) == status, u
+        assert np.all(host["frame_like"][a:b] == _frame_like(u, stage)), u
+    for u in (0, 3):
+        for k in RESULT_KEYS:
+            sl = slice(u * T, (u + 1) * T) if k in ("ali", "words", "frame_like") else u
+            assert np.array_equal(host[k][sl], before[k][sl]), (u, k)
+
+
+def test_ladder_without_capacity_status_touches_nothing(fx):
+    eng, before, host, redone = _ladder(fx, {1: {"first": 2}, 3: {"first": 1}})
+    assert redone == [] and eng.packed == [] and eng.calls == []
+    assert all(np.array_equal(host[k], before[k]) for k in RESULT_KEYS)
+
+
 # ---------------------------------------------------------------------------------------------------------- small pieces
 class _HostPool(StagingPool):
     def to_device(self, view, stream=None):
@@ -348,3 +411,21 @@ def test_batches_are_never_another_runs(fx):
     assert al._batches(utts) == fresh(utts) == [[5, 3, 2, 4], [1], [0]]
     al.opt.batch_frames = 1000
     assert al._batches(utts) == fresh(utts) == [[5, 3, 2, 4, 1, 0]]
+
+
+def test_offsets_and_speaker_groups_are_the_expressions_they_replace():
+    def same(got, want):
+        assert got.dtype == want.dtype and np.array_equal(got, want), (got, want)
+
+    for lengths in ([], [7], [3, 0, 5], np.array([4, 4, 1], dtype=np.int32), np.zeros(0, dtype=np.int64), (2, 9)):
+        same(offsets(lengths), np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64))
+        same(offsets(lengths, np.int32), np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32))
+    # empty, one utterance, speakers first seen out of order with gaps between their numbers, labels that are not numbers
+    for utt2spk in (np.zeros(0, dtype=np.int32), np.array([5], dtype=np.int32), np.array([9, 2, 9, 40, 2, 2, 7], dtype=np.int32),
+                    np.array([3, 3, 0], dtype=np.int64), ["zoe", "al", "zoe", "mo"]):
+        spk_ids, inv, order, spk_off = _speaker_groups(utt2spk)
+        want_ids, want_inv = np.unique(np.asarray(utt2spk), return_inverse=True)
+        same(spk_ids, want_ids)
+        same(inv, want_inv)
+        same(order, np.argsort(want_inv, kind="stable").astype(np.int32))
+        same(spk_off, np.concatenate([[0], np.cumsum(np.bincount(want_inv, minlength=len(want_ids)))]).astype(np.int32))
