@@ -259,7 +259,10 @@ MFA_API int mfa_fst_first_frames(int32_t n_states, const int32_t *h_arc_off, con
 /* ---- Acoustic scoring: replaces DecodableAmDiagGmmScaled::LogLikelihood inside GmmAligner.align_utterance and
  *      gmm_compute_likes (MFA/alignment/multiprocessing.py:846-853, :1415).
  * Per utterance u: pdf list d_pdf_list[pdf_off[u]..pdf_off[u+1]) (sorted as above) with d_class_counts[u][6];
- * output d_loglikes + ll_off[u]: float32 [T_u][P_u] row-major (UNSCALED log-likelihoods). */
+ * output d_loglikes + ll_off[u]: float32 [T_u][P_u] row-major (UNSCALED log-likelihoods).
+ * A list is a list of score COLUMNS: it may hold a pdf more than once (mfa_build_score_plan gives a pdf that recurs in a
+ * transcript one column per cluster of occurrences), so P_u may exceed the model's number of pdfs; every entry gets its
+ * column, on every kernel. */
 /* d_pdf_first_frame (may be NULL): int32 parallel to d_pdf_list, ascending inside every class of every utterance
  * (mfa_gmm_sort_pdf_list_keyed).  When given, cell (t, j) is only guaranteed to be written if
  * d_pdf_first_frame[j] <= t rounded up to the end of its 64-frame tile: Kaldi's decodable is evaluated lazily, for the

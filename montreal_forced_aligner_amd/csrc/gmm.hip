@@ -7,7 +7,7 @@
 //                  gmm_split_single_kernel (pdfs that are one 32-row block, 17–32 Gaussians), gmm_split_small_kernel (the
 //                  16-, 8- and 4-row slot classes as gathered virtual blocks), gmm_bf16_kernel (pdfs of more than 32
 //                  Gaussians: runs of blocks merged by an online log-sum-exp);
-//   this file      gmm_naive_kernel, one thread per (frame, pdf): feature dims beyond 48, and MFA_GMM_NAIVE=1 as a
+//   this file      gmm_naive_kernel, a thread per (frame, column) cell: feature dims beyond 48, and MFA_GMM_NAIVE=1 as a
 //                  cross-check; gmm_max_first_frame_kernel, the batch's largest first-reachable frame, for gmm_kernel's
 //                  phase split; mfa_load_gmm (uploads what gmm_pack.cpp packed); mfa_gmm_score_batch, which decides the
 //                  launches a model and the environment call for; mfa_gmm_launch_band_f32 (for gmm_band.hip).
@@ -59,35 +59,38 @@ __global__ void gmm_max_first_frame_kernel(const int32_t *first_frame, const int
   if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(out, m);
 }
 
-// Straightforward one-thread-per-(frame,pdf) kernel: used for feature dims the MFMA kernel is not instantiated for and,
-// with MFA_GMM_NAIVE=1, as an on-device cross-check of the MFMA path.  Same fmaf chain, same log-sum-exp.
+// Straightforward kernel, a thread per (frame, column) cell: used for feature dims the MFMA kernel is not instantiated for
+// and, with MFA_GMM_NAIVE=1, as an on-device cross-check of the MFMA path.  Same fmaf chain, same log-sum-exp.  The threads
+// of blockIdx.y's utterance stride over its T × P cells: a list may hold a pdf more than once (a column per cluster of
+// occurrences), so P is bounded by nothing the launch knows and the grid is sized for a typical utterance only.
 __global__ void gmm_naive_kernel(GmmParams p) {
   const int utt = blockIdx.y;
   const int64_t f0 = p.frame_off[utt];
   const int T = (int)(p.frame_off[utt + 1] - f0);
   const int64_t l0 = p.pdf_off[utt];
   const int P = (int)(p.pdf_off[utt + 1] - l0);
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (int64_t)T * P) return;
-  const int t = (int)(idx / P), j = (int)(idx % P);
-  const int pdf = p.pdf_list[l0 + j];
-  const int r0 = p.row0[pdf];
-  const int rows = p.slot[pdf] == 32 ? 32 * p.nblk[pdf] : p.slot[pdf];  // pad rows carry gconst -1e30
-  const float *x = p.feats + (f0 + t) * p.dim;
-  float mx = -INFINITY;
-  double sum = 0.0;
-  for (int pass = 0; pass < 2; pass++) {
-    for (int r = 0; r < rows; r++) {
-      float acc = p.gc[r0 + r];
-      for (int k = 0; k < 2 * p.dim; k++) {
-        float xv = k < p.dim ? x[k] : x[k - p.dim] * x[k - p.dim];
-        acc = fmaf(p.w[mfa_packed_offset(r0 + r, k, p.kpad)], xv, acc);
+  const int64_t cells = (int64_t)T * P, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < cells; idx += stride) {
+    const int t = (int)(idx / P), j = (int)(idx % P);
+    const int pdf = p.pdf_list[l0 + j];
+    const int r0 = p.row0[pdf];
+    const int rows = p.slot[pdf] == 32 ? 32 * p.nblk[pdf] : p.slot[pdf];  // pad rows carry gconst -1e30
+    const float *x = p.feats + (f0 + t) * p.dim;
+    float mx = -INFINITY;
+    double sum = 0.0;
+    for (int pass = 0; pass < 2; pass++) {
+      for (int r = 0; r < rows; r++) {
+        float acc = p.gc[r0 + r];
+        for (int k = 0; k < 2 * p.dim; k++) {
+          float xv = k < p.dim ? x[k] : x[k - p.dim] * x[k - p.dim];
+          acc = fmaf(p.w[mfa_packed_offset(r0 + r, k, p.kpad)], xv, acc);
+        }
+        if (pass == 0) mx = fmaxf(mx, acc);
+        else if (acc >= mx + p.min_log_diff) sum += (double)expf(acc - mx);
       }
-      if (pass == 0) mx = fmaxf(mx, acc);
-      else if (acc >= mx + p.min_log_diff) sum += (double)expf(acc - mx);
     }
+    p.out[p.ll_off[utt] + (size_t)idx] = (float)((double)mx + log(sum));
   }
-  p.out[p.ll_off[utt] + (size_t)t * P + j] = (float)((double)mx + log(sum));
 }
 
 }  // namespace
@@ -154,9 +157,10 @@ MFA_API int mfa_gmm_score_batch(mfa_ctx *c, const float *d_feats, const int64_t 
   const char *naive = getenv("MFA_GMM_NAIVE");
   KernelTimer kt(c, MFA_K_GMM);
   if ((naive && naive[0] == '1') || c->kpad > 96) {
-    // worst-case P is not known on the host side of this call: cover max_frames * num_pdfs threads per utterance
-    int64_t per_utt = (int64_t)max_frames * c->num_pdfs;
-    dim3 grid((unsigned)((per_utt + 255) / 256), n_utt);
+    // the longest list is not known on the host side of this call (a list may repeat pdfs): max_frames * num_pdfs threads
+    // per utterance, which stride over whatever cells the utterance has
+    const int64_t per_utt = (int64_t)max_frames * c->num_pdfs;
+    dim3 grid((unsigned)std::min<int64_t>((per_utt + 255) / 256, 1 << 20), n_utt);
     hipLaunchKernelGGL(gmm_naive_kernel, grid, dim3(256), 0, c->stream, p);
   } else {
     // 4 wavefronts per workgroup, 2 frame tiles (64 frames) per wavefront, two workgroups resident per CU (206 VGPRs).

@@ -107,28 +107,33 @@ __device__ __forceinline__ int64_t xsplit_tile_index(int64_t frame_off_u, int ut
 // Lazy scoring pre-pass: the f16 hi/lo operands [x, x²]·scale of every 64-frame tile, in the register layout the band
 // kernel's MFMAs read (b[n][step][piece] of lane l at ((n·kSteps + step)·2 + piece)·64 + l), so that a wavefront starts
 // a window with twenty coalesced 1 KiB loads instead of 160 strided 4-byte loads and the split arithmetic — the values are
-// those of split_features bit for bit.  One wavefront per tile.
+// those of split_features bit for bit.  One wavefront per tile; tiles_per_utt is a multiple of four, so a workgroup's four
+// wavefronts hold the sub-tiles of one 256-frame tile of one utterance, and the range flag is that tile's: a scaled feature
+// out of the f16 range hands all four sub-tiles to the bf16×3 pass, as the dense kernels' 256-frame items do — a cell
+// then carries the same bits whichever path scored it.
 template <int kSteps>
 __global__ __launch_bounds__(256) void gmm_presplit_kernel(GmmParams p, uint4 *out, int *bad_out, int tiles_per_utt) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t item = (int64_t)blockIdx.x * 4 + wave;
   const int utt = (int)(item / tiles_per_utt), tile = (int)(item - (int64_t)utt * tiles_per_utt);
-  if (utt >= p.n_utt) return;
-  const int64_t f0 = p.frame_off[utt];
-  const int T = (int)(p.frame_off[utt + 1] - f0);
-  if (tile * 64 >= T) return;
-  f16x8 b[2][kSteps][2];
-  const bool bad = split_features<kSteps, 2>(p, f0, T, tile * 64, lane & 31, lane >> 5, b);
+  const int64_t f0 = utt < p.n_utt ? p.frame_off[utt] : 0;
+  const int T = utt < p.n_utt ? (int)(p.frame_off[utt + 1] - f0) : 0;
+  const bool live = tile * 64 < T;
   const int64_t ti = xsplit_tile_index(f0, utt, tile);
-  uint4 *dst = out + ti * (2 * kSteps * 2 * 64) + lane;
+  bool bad = false;
+  if (live) {
+    f16x8 b[2][kSteps][2];
+    bad = split_features<kSteps, 2>(p, f0, T, tile * 64, lane & 31, lane >> 5, b);
+    uint4 *dst = out + ti * (2 * kSteps * 2 * 64) + lane;
 #pragma unroll
-  for (int n = 0; n < 2; n++)
+    for (int n = 0; n < 2; n++)
 #pragma unroll
-    for (int s_ = 0; s_ < kSteps; s_++)
+      for (int s_ = 0; s_ < kSteps; s_++)
 #pragma unroll
-      for (int q = 0; q < 2; q++) dst[((n * kSteps + s_) * 2 + q) * 64] = __builtin_bit_cast(uint4, b[n][s_][q]);
-  const bool any_bad = __ballot(bad) != 0ull;
-  if (lane == 0) bad_out[ti] = any_bad ? 1 : 0;
+        for (int q = 0; q < 2; q++) dst[((n * kSteps + s_) * 2 + q) * 64] = __builtin_bit_cast(uint4, b[n][s_][q]);
+  }
+  const int any_bad = __syncthreads_or(bad ? 1 : 0);
+  if (live && lane == 0) bad_out[ti] = any_bad ? 1 : 0;
 }
 
 // Phase accounting of gmm_band_kernel for -DGMM_BAND_STAMPS builds (buffer from mfa_debug_gmm_trace, summed over the f16
@@ -582,7 +587,7 @@ int mfa_gmm_presplit(mfa_ctx *c, const MfaLazyScoring *lazy, const int64_t *d_fr
   GmmParams p;
   memset(&p, 0, sizeof(p));
   p.dim = c->dim; p.kpad = c->kpad; p.feats = lazy->d_feats; p.frame_off = d_frame_off; p.n_utt = n_utt; p.fscale = c->d_fscale.ptr<float>();
-  const int tiles_per_utt = (lazy->max_frames + 63) / 64;
+  const int tiles_per_utt = ((lazy->max_frames + 255) / 256) * 4;   // whole 256-frame tiles: a workgroup each (gmm_presplit_kernel)
   const int64_t waves = (int64_t)n_utt * tiles_per_utt;
   const dim3 grid((unsigned)((waves + 3) / 4));
   KernelTimer kt(c, MFA_K_GMM);

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from montreal_forced_aligner_amd import _lib
-from tests import helpers
+from tests import gmm_ref, helpers
 
 SIZES = [1, 2, 3, 4, 5, 8, 9, 12, 16, 17, 26, 32, 33, 40, 70]
 DIMS = [39, 40, 45, 48, 50]
@@ -73,15 +73,26 @@ def _slot(g):
     return 1 if g <= 1 else 4 if g <= 4 else 8 if g <= 8 else 16 if g <= 16 else 32
 
 
-@pytest.fixture(scope="module", params=DIMS)
+SKEWED_DIMS = [39, 40, 45]
+
+
+@pytest.fixture(scope="module", params=DIMS + [("skewed", d) for d in SKEWED_DIMS], ids=str)
 def packed(request):
+    """(model, packed arrays, the column of means·inv_vars the fixture zeroed or None): helpers.random_gmm models at DIMS, and
+    models with the column spread of a trained one (tests/gmm_ref.py) at SKEWED_DIMS."""
+    if isinstance(request.param, tuple):
+        dim = request.param[1]
+        rng = np.random.default_rng(200 + dim)
+        am = gmm_ref.skewed_gmm(rng, dim, [int(g) for g in rng.permutation(SIZES)]).am
+        return am, _pack(am), None
     dim = request.param
-    am = _model(dim, 100 + dim, zero_column=3 if dim == 40 else None)
-    return am, _pack(am)
+    zero_column = 3 if dim == 40 else None
+    am = _model(dim, 100 + dim, zero_column=zero_column)
+    return am, _pack(am), zero_column
 
 
 def test_layout(packed):
-    am, pk = packed
+    am, pk, _ = packed
     dim, kpad, rows = am.dim, pk["kpad"], pk["rows"]
     assert kpad == (80 if 2 * dim <= 80 else 96 if 2 * dim <= 96 else (2 * dim + 7) // 8 * 8)
     g = np.diff(am.pdf_offsets)
@@ -132,7 +143,7 @@ def _bf16_to_f64(bits):
 
 
 def test_split_tables(packed):
-    am, pk = packed
+    am, pk, zero_column = packed
     dim, kpad, rows = am.dim, pk["kpad"], pk["rows"]
     if dim > 48:
         assert not pk["split"] and kpad > 96 and pk["acc_scale"] == 1.0   # above 48 dims: no split tables
@@ -149,8 +160,8 @@ def test_split_tables(packed):
     assert np.log2(s) == np.round(np.log2(s)) and 2.0 ** -20 <= s <= 2.0 ** 12
     nonzero = np.any(w[:rows] != 0.0, axis=0)
     want_nonzero = np.arange(kpad) < 2 * dim
-    if dim == 40:
-        want_nonzero[3] = False                                           # the fixture zeroed this column of means·inv_vars
+    if zero_column is not None:
+        want_nonzero[zero_column] = False                                          # the fixture zeroed this column of means·inv_vars
     assert np.array_equal(nonzero, want_nonzero)
     assert np.all(fscale[~nonzero] == 0.0) and np.all(fscale[nonzero] > 0.0)
     e = np.zeros(kpad)
