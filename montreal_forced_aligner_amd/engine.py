@@ -697,10 +697,18 @@ class AlignmentEngine:
             raise _lib.MfaHipError("mfa_fst_last_depths: malformed graph")
         return depth
 
+    def _check_width(self, feats: torch.Tensor, what: str) -> None:
+        """The scoring kernels read ``feats`` by pointer, at the loaded model's width: a matrix of another width is refused
+        here, on the host."""
+        if self.gmm is not None and (feats.dim() != 2 or int(feats.shape[1]) != int(self.gmm.dim)):
+            raise _lib.MfaHipError(f"{what}: the features have {int(feats.shape[1]) if feats.dim() == 2 else tuple(feats.shape)} "
+                                   f"columns, the loaded acoustic model has {int(self.gmm.dim)} dimensions")
+
     def score(self, feats: torch.Tensor, frame_off: np.ndarray, pdf_list: torch.Tensor, pdf_off_host: np.ndarray,
               class_counts: torch.Tensor, pdf_first_frame: Optional[torch.Tensor] = None):
         """Returns (loglikes float32 flat, ll_off host int64 [n+1], ll_cols int32 tensor).  With ``pdf_first_frame``
         (PackedGraphs.pdf_first_frame) cells no decoder token can ask for are left unwritten (zero here)."""
+        self._check_width(feats, "score")
         n_utt = len(frame_off) - 1
         T = np.diff(frame_off)
         P = np.diff(pdf_off_host)
@@ -755,6 +763,7 @@ class AlignmentEngine:
                       want_frame_likes: bool = False):
         """Alignment over graphs with epsilon input arcs / wide states: dense scores, then FasterDecoder as Kaldi runs it
         (ProcessNonemitting included), one GPU thread per utterance — mfa_align_general_batch."""
+        self._check_width(feats, "align_general")
         ll, ll_off, ll_cols = self.score(feats, frame_off, graphs.pdf_list, graphs.pdf_off_host, graphs.class_counts)
         out = self._align_outputs(graphs.n_utt, int(frame_off[-1]), want_frame_likes)
         opts = AlignOpts(beam, retry_beam, acoustic_scale, 0, bp_tokens_per_frame)
@@ -942,6 +951,7 @@ class AlignmentEngine:
         can reach (mfa_align_features_batch) — the shape of GmmAligner.align_utterance(fst, feats)
         (MFA/alignment/multiprocessing.py:846-853).  Same results as ``score`` + ``align``.  ``loglikes``: optional scratch
         [Σ T·P] (zero-filled here when omitted, so tests can see which cells were written)."""
+        self._check_width(feats, "align_features")
         n = graphs.n_utt
         total = int(frame_off[-1])
         T = np.diff(frame_off)

@@ -6,7 +6,7 @@ kernels on tiny windows and on all-pdf score matrices.
   shift, against the two-phone graph "previous phone group → phone group" (the phone-group lexicon of
   MFA/dictionary/multispeaker.py:2078-2111 is a single-state transducer phone → group, i.e. a free choice among the
   group's phones, no silence insertion).  The reference does this one boundary at a time in a worker process; here all
-  boundaries of a batch of utterances are one ragged device batch (≈120 windows per 10 s utterance).
+  boundaries of a batch of utterances are ragged device batches (≈120 windows per 10 s utterance, ``max_windows`` at a time).
 * ``phone_confidence`` mirrors PhoneConfidenceFunction._run (:1353-1447): all-pdf log-likelihoods
   (``gmm_compute_likes``), phone scores as count-weighted sums over each phone's pdfs, and per interval the mean margin
   by which the best phone beats the aligned phone ("phone_goodness").
@@ -24,6 +24,8 @@ from . import graph as _graph
 
 NEW_FRAME_SHIFT = 0.001          # FineTuneFunction.new_frame_shift_seconds
 FEATURE_PADDING_FACTOR = 3       # FineTuneFunction.feature_padding_factor
+MAX_UTTERANCES_PER_LAUNCH = 65535   # the MFCC, feature and scoring kernels put the utterance on a grid axis
+MAX_WINDOWS = 32768              # default chunk of fine_tune_boundaries
 
 
 @dataclass
@@ -87,13 +89,29 @@ def fine_tune_boundaries(aligner, compiler: _graph.TrainingGraphCompiler, pcm: S
                          intervals: Sequence[Sequence[_ctm.CtmInterval]], utt2spk: Optional[Sequence[int]] = None,
                          cmvn=None, lda=None, fmllr=None, phone_group: Optional[Callable[[int], Sequence[int]]] = None,
                          frame_shift: float = 0.01, sample_rate: int = 16000, mfcc_options: Optional[dict] = None,
-                         splice_context: int = 3):
+                         splice_context: int = 3, phone_table=None, max_windows: int = MAX_WINDOWS,
+                         trace: Optional[dict] = None):
     """Returns (new interval lists, deletions per utterance).
 
     ``aligner``: a kalpy_api.GmmAligner (its beams and transition scales are used; the acoustic scale is 1.0, falling
     back to 0.1 for a window that fails, as the reference does).  ``pcm``: one int16 array per utterance (time 0 = the
     utterance's begin).  ``intervals``: per utterance, phone CtmIntervals with ``symbol`` = phone id, sorted by begin.
-    ``cmvn``: device tensor [n_spk, 2, dim+1] (the speakers' 10 ms statistics) or None; ``utt2spk`` indexes it."""
+    ``cmvn``: device tensor [n_spk, 2, dim+1] (the speakers' 10 ms statistics) or None; ``utt2spk`` indexes it.
+
+    ``phone_table``: the phone symbol table (``find(id)`` → name); the tuned intervals' labels come from it, as in the
+    reference (:1329) — with a phone group of several phones the decoder may choose a phone that occurs nowhere else in the
+    utterance.  Without it a label is taken from an interval of the same utterance that carries the phone id, and a phone id
+    none of them carries stays an id (an ``int`` label).
+
+    ``max_windows``: the windows are decoded in chunks of at most this many — a chunk is one ragged batch of the MFCC,
+    feature and scoring kernels, each of which takes at most 65 535 utterances.  The results do not depend on it.
+
+    ``trace``: a dict that receives what every stage produced, for tests (no launch or copy is made for it):
+    ``windows`` (the planned ``_Window`` list), ``scale`` (per window, the acoustic scale its alignment was found at; None:
+    no rows, or failed at both) and ``chunks``, one dict per chunk: ``first`` (index of its first window), ``mfcc`` /
+    ``frame_off`` (the 1 ms MFCCs of the cuts), ``spk``, ``feats``, ``sub`` / ``new_off`` (the decoded rows), ``fsts`` and
+    ``attempts``: per decode, ``scale``, ``windows`` (global indices), ``frame_off``, ``x`` (their rows), ``pdf_lists_host``,
+    ``pdf_first_frame`` (host, per window), ``ll`` / ``ll_off`` (device scores) and the ``status`` / ``ali`` that came back."""
     import torch
     from .engine import offsets
 
@@ -102,66 +120,98 @@ def fine_tune_boundaries(aligner, compiler: _graph.TrainingGraphCompiler, pcm: S
     group_of = phone_group or (lambda p: [p])
     utt_ends = [len(x) / sample_rate for x in pcm]
     windows = plan_windows(intervals, utt_ends, frame_shift)
-    result = [[{"id": (u, 0), "begin": ivs[0].begin, "end": ivs[0].end, "label": int(ivs[0].symbol)}] if ivs else []
-              for u, ivs in enumerate(intervals)]
+    if trace is not None:
+        trace.update(windows=windows, scale=[None] * len(windows), chunks=[])
     if not windows:
         return [list(ivs) for ivs in intervals], [[] for _ in intervals]
-    # ---- 1 ms features of every window (one batch)
-    cuts = []
-    for w in windows:
-        a, b = int(round(w.feature_begin * sample_rate)), int(round(w.feature_end * sample_rate))
-        cuts.append(np.ascontiguousarray(pcm[w.utt][a:b], dtype=np.int16))
-    sample_off = offsets([len(c) for c in cuts])
+    if not 1 <= int(max_windows) <= MAX_UTTERANCES_PER_LAUNCH:
+        raise ValueError(f"max_windows must be between 1 and {MAX_UTTERANCES_PER_LAUNCH}, got {max_windows}")
     saved = dict(mfcc_options or {})
-    eng.configure_mfcc(**{**saved, "frame_shift_ms": NEW_FRAME_SHIFT * 1000.0})
-    try:
-        d_pcm = torch.from_numpy(np.concatenate(cuts)).to(eng.device)
-        mfcc, frame_off = eng.mfcc(d_pcm, sample_off)
-    finally:
-        eng.configure_mfcc(**saved)
-    spk = np.asarray([0 if utt2spk is None else utt2spk[w.utt] for w in windows], dtype=np.int32)
-    feats = eng.features(mfcc, frame_off, spk if cmvn is not None or fmllr is not None else None, cmvn, lda, fmllr, splice_context)
-    # ---- rows [begin_offset, end_offset) of every window (FloatSubMatrix in the reference, :1300-1304)
-    rows, new_off = [], [0]
-    for k, w in enumerate(windows):
-        T = int(frame_off[k + 1] - frame_off[k])
-        a = min(max(int(round(w.begin_offset * 1000)), 0), T)
-        b = min(max(int(round(w.end_offset * 1000)), a), T)
-        rows.append(np.arange(frame_off[k] + a, frame_off[k] + b, dtype=np.int64))
-        new_off.append(new_off[-1] + (b - a))
-    new_off = np.asarray(new_off, dtype=np.int64)
-    sub = eng.gather_rows(feats, np.concatenate(rows)) if new_off[-1] else feats[:0]   # device-to-device copies of the windows
-    # ---- two-phone graphs (cached per group pair)
-    cache: Dict[Tuple[Tuple[int, ...], Tuple[int, ...]], object] = {}
-    fsts = []
-    for w in windows:
-        key = (tuple(group_of(w.prev_phone)), tuple(group_of(w.phone)))
-        if key not in cache:
-            cache[key] = _graph.add_transition_probs(two_phone_graph(compiler, *key), aligner._scaled)
-        fsts.append(cache[key])
-    ok = [k for k in range(len(windows)) if new_off[k + 1] > new_off[k]]
+    cache: Dict[Tuple[Tuple[int, ...], Tuple[int, ...]], object] = {}     # two-phone graphs per group pair
 
-    def run(sel: List[int], acoustic_scale: float):
-        if not sel:
-            return {}
-        graphs = eng.pack_graphs([fsts[k] for k in sel], tm)
-        fo = offsets([new_off[k + 1] - new_off[k] for k in sel])
-        idx = np.concatenate([np.arange(new_off[k], new_off[k + 1]) for k in sel])
-        x = eng.gather_rows(sub, idx)
-        ll, ll_off, ll_cols = eng.score(x, fo, graphs.pdf_list, graphs.pdf_off_host, graphs.class_counts,
-                                        pdf_first_frame=graphs.pdf_first_frame)
-        res = eng.align(graphs, ll, ll_off, ll_cols, fo, beam=aligner.beam, retry_beam=aligner.retry_beam,
-                        acoustic_scale=acoustic_scale)
-        status, ali = res["status"].cpu().numpy(), res["ali"].cpu().numpy()
-        return {k: ali[fo[i]: fo[i + 1]] for i, k in enumerate(sel) if status[i] in (0, 1)}
+    def tune(first: int, chunk: List[_Window]) -> Dict[int, np.ndarray]:
+        """One chunk of windows through the device: {window index in the chunk: its alignment}."""
+        # ---- 1 ms features of every window (one batch)
+        cuts = []
+        for w in chunk:
+            a, b = int(round(w.feature_begin * sample_rate)), int(round(w.feature_end * sample_rate))
+            cuts.append(np.ascontiguousarray(pcm[w.utt][a:b], dtype=np.int16))
+        sample_off = offsets([len(c) for c in cuts])
+        eng.configure_mfcc(**{**saved, "frame_shift_ms": NEW_FRAME_SHIFT * 1000.0})
+        try:
+            d_pcm = torch.from_numpy(np.concatenate(cuts)).to(eng.device)
+            mfcc, frame_off = eng.mfcc(d_pcm, sample_off)
+        finally:
+            eng.configure_mfcc(**saved)
+        spk = np.asarray([0 if utt2spk is None else utt2spk[w.utt] for w in chunk], dtype=np.int32)
+        feats = eng.features(mfcc, frame_off, spk if cmvn is not None or fmllr is not None else None, cmvn, lda, fmllr, splice_context)
+        # ---- rows [begin_offset, end_offset) of every window (FloatSubMatrix in the reference, :1300-1304)
+        rows, new_off = [], [0]
+        for k, w in enumerate(chunk):
+            T = int(frame_off[k + 1] - frame_off[k])
+            a = min(max(int(round(w.begin_offset * 1000)), 0), T)
+            b = min(max(int(round(w.end_offset * 1000)), a), T)
+            rows.append(np.arange(frame_off[k] + a, frame_off[k] + b, dtype=np.int64))
+            new_off.append(new_off[-1] + (b - a))
+        new_off = np.asarray(new_off, dtype=np.int64)
+        sub = eng.gather_rows(feats, np.concatenate(rows)) if new_off[-1] else feats[:0]   # device-to-device copies of the windows
+        fsts = []
+        for w in chunk:
+            key = (tuple(group_of(w.prev_phone)), tuple(group_of(w.phone)))
+            if key not in cache:
+                cache[key] = _graph.add_transition_probs(two_phone_graph(compiler, *key), aligner._scaled)
+            fsts.append(cache[key])
+        ok = [k for k in range(len(chunk)) if new_off[k + 1] > new_off[k]]
+        attempts: List[dict] = []
+        if trace is not None:
+            trace["chunks"].append(dict(first=first, mfcc=mfcc, frame_off=frame_off, spk=spk, feats=feats, sub=sub,
+                                        new_off=new_off, fsts=fsts, attempts=attempts))
 
-    done = run(ok, 1.0)
-    done.update(run([k for k in ok if k not in done], 0.1))   # :1306-1309
+        def run(sel: List[int], acoustic_scale: float):
+            if not sel:
+                return {}
+            graphs = eng.pack_graphs([fsts[k] for k in sel], tm)
+            fo = offsets([new_off[k + 1] - new_off[k] for k in sel])
+            idx = np.concatenate([np.arange(new_off[k], new_off[k + 1]) for k in sel])
+            x = eng.gather_rows(sub, idx)
+            ll, ll_off, ll_cols = eng.score(x, fo, graphs.pdf_list, graphs.pdf_off_host, graphs.class_counts,
+                                            pdf_first_frame=graphs.pdf_first_frame)
+            res = eng.align(graphs, ll, ll_off, ll_cols, fo, beam=aligner.beam, retry_beam=aligner.retry_beam,
+                            acoustic_scale=acoustic_scale)
+            status, ali = res["status"].cpu().numpy(), res["ali"].cpu().numpy()
+            if trace is not None:
+                attempts.append(dict(scale=acoustic_scale, windows=[first + k for k in sel], frame_off=fo, x=x,
+                                     pdf_lists_host=[np.array(p) for p in graphs.pdf_lists_host],
+                                     pdf_first_frame=[np.array(p) for p in graphs.pdf_first_frame_host],
+                                     ll=ll, ll_off=ll_off, status=status, ali=ali))
+                for i, k in enumerate(sel):
+                    if status[i] in (0, 1):
+                        trace["scale"][first + k] = acoustic_scale
+            return {k: ali[fo[i]: fo[i + 1]] for i, k in enumerate(sel) if status[i] in (0, 1)}
+
+        got = run(ok, 1.0)
+        got.update(run([k for k in ok if k not in got], 0.1))   # :1306-1309
+        return got
+
+    done: Dict[int, np.ndarray] = {}
+    for first in range(0, len(windows), int(max_windows)):
+        for k, a in tune(first, windows[first: first + int(max_windows)]).items():
+            done[first + k] = a
+    return assemble(windows, intervals, done, tm, phone_table)
+
+
+def assemble(windows: Sequence[_Window], intervals: Sequence[Sequence[_ctm.CtmInterval]], alis: Dict[int, np.ndarray], tm,
+             phone_table=None):
+    """Intervals and deletions from the windows' alignments (``alis``: window index → transition-ids; a window without one
+    keeps its boundary and phone): the second phone's begin and id replace the interval's (:1310-1326), then the repair
+    loop.  Labels as ``fine_tune_boundaries`` documents them."""
+    result = [[{"id": (u, 0), "begin": ivs[0].begin, "end": ivs[0].end, "label": int(ivs[0].symbol)}] if ivs else []
+              for u, ivs in enumerate(intervals)]
     for k, w in enumerate(windows):
         iv = intervals[w.utt][w.index]
         begin, label = iv.begin, int(iv.symbol)
-        if k in done:
-            ctm = _ctm.generate_ctm(done[k], tm, None, NEW_FRAME_SHIFT)
+        if k in alis:
+            ctm = _ctm.generate_ctm(alis[k], tm, None, NEW_FRAME_SHIFT)
             if len(ctm) > 1:
                 begin = round(ctm[1].begin + w.feature_begin + w.begin_offset, 4)
                 label = int(ctm[1].symbol)
@@ -169,8 +219,12 @@ def fine_tune_boundaries(aligner, compiler: _graph.TrainingGraphCompiler, pcm: S
     out_iv, out_del = [], []
     for u, mapping in enumerate(result):
         mapping, deleted = repair_intervals(mapping) if mapping else ([], [])
-        labels = {int(iv.symbol): iv.label for iv in intervals[u]}
-        out_iv.append([_ctm.CtmInterval(m["begin"], m["end"], labels.get(m["label"], m["label"]), m["label"]) for m in mapping])
+        if phone_table is not None:
+            name = phone_table.find
+        else:
+            labels = {int(iv.symbol): iv.label for iv in intervals[u]}
+            name = lambda p: labels.get(p, p)      # noqa: E731
+        out_iv.append([_ctm.CtmInterval(m["begin"], m["end"], name(m["label"]), m["label"]) for m in mapping])
         out_del.append([i for (_u, i) in deleted])
     return out_iv, out_del
 

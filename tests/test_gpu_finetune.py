@@ -88,7 +88,7 @@ def test_fine_tune_boundaries_matches_oracle_windows(fx, tmp_path):
             got = new_ivs[kept.index(w.index)].begin
             assert abs(got - want) <= 0.0011, (w.index, got, want)   # 1 ms grid; device MFCC vs oracle MFCC differ by ~1e-4
             checked += 1
-    assert checked >= 5 or deleted
+    assert checked >= 5          # (nothing is deleted here, on the device as on the oracle: every sampled window was compared)
 
 
 def test_repair_intervals_restates_reference_loop():
