@@ -47,7 +47,7 @@ MFA_API int mfa_memcpy_d2h(mfa_ctx *ctx, void *h_dst, const void *d_src, size_t 
 MFA_API int mfa_timer_begin(mfa_ctx *ctx);
 MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
 /* Per-kernel accumulated HIP-event times since the last reset.  which: 0 mfcc, 1 cmvn, 2 feats, 3 gmm, 4 viterbi,
- * 5 resample, 6 pitch.
+ * 5 resample, 6 pitch, 7 feature codec.
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -231,6 +231,31 @@ MFA_API int mfa_cmvn_stats(mfa_ctx *ctx, const float *d_feats, const int64_t *d_
 MFA_API int mfa_feats_batch(mfa_ctx *ctx, const float *d_mfcc, const int64_t *d_frame_off, int32_t n_utt, int32_t max_frames,
                             int32_t dim, const int32_t *d_utt2spk, const double *d_cmvn, int32_t mode, int32_t splice_ctx,
                             const float *d_lda, int32_t lda_rows, int32_t lda_cols, const float *d_fmllr, float *d_out);
+
+/* ---- Feature codec: Kaldi CompressedMatrix, method kOneByteWithColHeaders ("CM") — what compute_mfccs_for_export /
+ *      compute_pitch_for_export (compress=True) and FinalFeatureFunction store (MFA/corpus/features.py:235, :356-365).
+ * d_feats: float32 [total_frames][stride]; for every utterance with rows, columns [c0, c1) of its rows are one table.
+ * Bit-identical to kaldi_io.write_compressed_matrix / _read_compressed (the specification):
+ *   d_global  float  [n_utt][2]            min, range of the table                                   (or NULL)
+ *   d_colhdr  uint16 [n_utt][c1-c0][4]     the columns' 0/25/75/100-th percentile codes             (or NULL)
+ *   d_bytes   uint8, utterance k at d_frame_off[k]*(c1-c0), column-major [c1-c0][rows]               (or NULL)
+ *   d_out     float32 [total_frames][stride]: what a reader makes of those headers and bytes; only columns [c0, c1) are
+ *             written (or NULL).  It may not be d_feats.
+ * d_cmvn float64 [n_spk][2][cmvn_dim+1] with d_utt2spk [n_utt] (both or neither): the speaker's mean
+ * (float)(sum[c] / count) is subtracted in float32 before the table is compressed (ApplyCmvn without variance
+ * normalisation, then the second trip); cmvn_dim >= c1.  An utterance without rows has no table: nothing of it is written.
+ * Any number of rows (a table of at most mfa_compress_resident_values() values is held in LDS, a longer one is read
+ * from memory by the same passes) and of utterances.  Non-finite input has no defined result.  Asynchronous on the
+ * context's stream. */
+MFA_API int32_t mfa_compress_resident_values(void);
+MFA_API int mfa_compress_batch(mfa_ctx *ctx, const float *d_feats, const int64_t *d_frame_off, int32_t n_utt, int32_t stride,
+                               int32_t c0, int32_t c1, const double *d_cmvn, const int32_t *d_utt2spk, int32_t cmvn_dim,
+                               float *d_out, float *d_global, uint16_t *d_colhdr, uint8_t *d_bytes);
+/* Debug/test: the codec's arithmetic (the functions the kernel runs, compiled for the host) on one host table
+ * h_table [rows][cols], order statistics by a sort: h_global [2], h_colhdr [cols][4], h_bytes [cols][rows],
+ * h_out [rows][cols], each or NULL.  No context, no device.  < 0: an empty table. */
+MFA_API int mfa_debug_compress_host(const float *h_table, int32_t rows, int32_t cols, float *h_global, uint16_t *h_colhdr,
+                                    uint8_t *h_bytes, float *h_out);
 
 /* ---- Acoustic model: replaces GmmAligner.__init__'s model load (+ .boost_silence, applied by the host to gconsts)
  *      (MFA/alignment/multiprocessing.py:814-815).  Host arrays, SoA over all Gaussians:

@@ -97,7 +97,7 @@ class AlignOptions:
     silence_weight: float = 0.0
     # `mfa align` (the corpus path) stores raw MFCCs and the CMVN-applied features as 8-bit Kaldi CompressedMatrix tables
     # (MFA/corpus/features.py:235, :356-365) and therefore aligns features quantised twice; `align_one` / the online path
-    # keep float32 (the default here).  True reproduces the corpus path's two quantisations (host-side codec).
+    # keep float32 (the default here).  True reproduces the corpus path's two quantisations (device codec).
     corpus_compression: bool = False
     # raw MFCCs of a run stay on the device between the CMVN pass and the alignment passes up to this many bytes
     mfcc_cache_bytes: int = 64 << 30
@@ -233,8 +233,6 @@ class CorpusAligner:
         return out
 
     def _mfcc(self, utts: Sequence[CorpusUtterance], idx: Sequence[int]):
-        import torch
-
         key = (id(utts), tuple(idx))          # (the list object of the run in progress; the cache only lives inside align())
         hit = self._mfcc_cache.get(key) if self._mfcc_cache_on else None
         if hit is not None:          # the CMVN pass computed them already (and a second alignment pass asks a third time)
@@ -249,17 +247,12 @@ class CorpusAligner:
         else:
             mfcc, fo = self.engine.mfcc(pcm, so)
         if self.opt.corpus_compression:      # feats.*.ark of MfccFunction: compute_mfccs_for_export(seg, compress=True)
-            from . import kaldi_io as _kio
-            host = mfcc.cpu().numpy()
             nc = self.engine.num_ceps
-            for k in range(len(idx)):
-                a, b = int(fo[k]), int(fo[k + 1])
-                if b > a and not self.n_pitch:
-                    host[a:b] = _kio.compress_round_trip(host[a:b])
-                elif b > a:                  # two tables: the MFCCs', and compute_pitch_for_export(seg, compress=True)'s
-                    host[a:b, :nc] = _kio.compress_round_trip(np.ascontiguousarray(host[a:b, :nc]))
-                    host[a:b, nc:] = _kio.compress_round_trip(np.ascontiguousarray(host[a:b, nc:]))
-            mfcc = torch.from_numpy(host).to(self.engine.device)
+            if not self.n_pitch:
+                mfcc = self.engine.compress_round_trip(mfcc, fo)
+            else:                            # two tables: the MFCCs', and compute_pitch_for_export(seg, compress=True)'s
+                once = self.engine.compress_round_trip(mfcc, fo, cols=(0, nc))
+                mfcc = self.engine.compress_round_trip(mfcc, fo, cols=(nc, nc + self.n_pitch), out=once)
         size = mfcc.numel() * mfcc.element_size()
         if self._mfcc_cache_on and self._mfcc_cache_bytes + size <= self.opt.mfcc_cache_bytes:   # 52 KB per 10 s utterance: HBM holds millions
             self._mfcc_cache[key] = (mfcc, fo)
@@ -268,27 +261,16 @@ class CorpusAligner:
 
     def _final_features(self, mfcc, fo, rows, cmvn, d_lda, fmllr):
         """CMVN → Δ+ΔΔ | splice+LDA(+fMLLR).  With ``corpus_compression`` the CMVN-applied MFCCs take the second trip
-        through the 8-bit codec first (FinalFeatureFunction, MFA/corpus/features.py:323-365), on the host; pitch columns,
+        through the 8-bit codec first (FinalFeatureFunction, MFA/corpus/features.py:323-365), on the device; pitch columns,
         pasted after CMVN, have been through the codec once (``_mfcc``) and stay as they are."""
-        import torch
-
         eng = self.engine
         if not self.opt.corpus_compression:
             return eng.features(mfcc, fo, rows, cmvn, lda=d_lda, fmllr=fmllr)
-        from . import kaldi_io as _kio
-        host = mfcc.cpu().numpy()
-        stats = cmvn.cpu().numpy()
-        dim = host.shape[1] - self.n_pitch
-        for k in range(len(fo) - 1):
-            a, b = int(fo[k]), int(fo[k + 1])
-            if b > a:
-                st = stats[rows[k]]
-                mean = (st[0, :dim] / st[0, -1]).astype(np.float32)        # ApplyCmvn, no variance normalisation
-                if self.n_pitch:
-                    host[a:b, :dim] = _kio.compress_round_trip(host[a:b, :dim] - mean)
-                else:
-                    host[a:b] = _kio.compress_round_trip(host[a:b] - mean)
-        return eng.features(torch.from_numpy(host).to(eng.device), fo, rows, None, lda=d_lda, fmllr=fmllr)
+        # ApplyCmvn (no variance normalisation) fused into the codec launch; with pitch the statistics are zero-padded to
+        # the base matrix's width and only the MFCC columns make the trip
+        dim = mfcc.shape[1] - self.n_pitch
+        twice = eng.compress_round_trip(mfcc, fo, cols=(0, dim), cmvn=cmvn, utt2spk=rows)
+        return eng.features(twice, fo, rows, None, lda=d_lda, fmllr=fmllr)
 
     def speaker_cmvn(self, utts: Sequence[CorpusUtterance]) -> Tuple[Dict[str, int], "object"]:
         """calc_cmvn: float64 [n_spk, 2, dim+1] on the device, and the speaker → row map.  With pitch the statistics are

@@ -383,6 +383,11 @@ class AlignmentEngine:
         check(self.ctx, self.lib.mfa_feats_batch(self.ctx, _ptr(mfcc), _ptr(d_frame_off), n_utt, max_frames, dim, _ptr(d_utt2spk),
                                                  _ptr(cmvn), *transform, _ptr(fmllr), _ptr(out)), "mfa_feats_batch")
 
+    def _launch_compress(self, feats, d_frame_off, n_utt: int, c0: int, c1: int, cmvn, d_utt2spk, out, glob, colhdr, data) -> None:
+        check(self.ctx, self.lib.mfa_compress_batch(self.ctx, _ptr(feats), _ptr(d_frame_off), n_utt, int(feats.shape[1]), c0, c1,
+                                                    _ptr(cmvn), _ptr(d_utt2spk), int(cmvn.shape[2]) - 1 if cmvn is not None else 0,
+                                                    _ptr(out), _ptr(glob), _ptr(colhdr), _ptr(data)), "mfa_compress_batch")
+
     def _launch_score(self, feats, d_frame_off, n_utt: int, max_frames: int, pdf_list, d_pdf_off, class_counts, pdf_first_frame,
                       d_ll_off, out) -> None:
         check(self.ctx, self.lib.mfa_gmm_score_batch(self.ctx, _ptr(feats), _ptr(d_frame_off), n_utt, max_frames, _ptr(pdf_list),
@@ -610,6 +615,63 @@ class AlignmentEngine:
         out[:, :, : d1 - 1] = stats[:, :, : d1 - 1]
         out[:, :, -1] = stats[:, :, -1]
         return out
+
+    # ------------------------------------------------------------------ feature codec (Kaldi CompressedMatrix, "CM")
+    def compress_resident_values(self) -> int:
+        """Values of the largest table the codec kernel holds in LDS; a larger one runs the same passes from memory."""
+        return int(self.lib.mfa_compress_resident_values())
+
+    def _codec_input(self, feats: torch.Tensor, frame_off, cols):
+        if not (feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2 and feats.is_contiguous()):
+            raise _lib.MfaHipError("compress: the features must be a contiguous float32 [frames, dim] tensor on the device")
+        fo = np.ascontiguousarray(frame_off, dtype=np.int64)
+        if fo.ndim != 1 or fo.shape[0] < 1 or fo[0] < 0 or (np.diff(fo) < 0).any() or fo[-1] > feats.shape[0]:
+            raise _lib.MfaHipError(f"compress: frame offsets do not lie inside the {feats.shape[0]} rows of the features")
+        c0, c1 = (0, int(feats.shape[1])) if cols is None else (int(cols[0]), int(cols[1]))
+        return fo, fo.shape[0] - 1, c0, c1
+
+    def compress_round_trip(self, feats: torch.Tensor, frame_off: np.ndarray, cols: Optional[Tuple[int, int]] = None,
+                            cmvn: Optional[torch.Tensor] = None, utt2spk: Optional[np.ndarray] = None,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """What a reader gets back after every utterance's columns ``cols`` = [c0, c1) (default: all) were written as one
+        Kaldi CompressedMatrix table — ``kaldi_io.compress_round_trip`` per utterance, bit for bit, on the device.  Returns a
+        new tensor (or ``out``, which may not be ``feats``); columns outside ``cols`` are copied through.  With ``cmvn``
+        (float64 [n_spk, 2, d + 1], d >= c1) and ``utt2spk`` the speaker's mean is subtracted before the table is compressed:
+        ApplyCmvn, then FinalFeatureFunction's trip through the codec."""
+        fo, n_utt, c0, c1 = self._codec_input(feats, frame_off, cols)
+        d_u2s = None
+        if cmvn is not None:
+            if utt2spk is None or len(utt2spk) != n_utt:
+                raise _lib.MfaHipError("compress: CMVN statistics need one speaker row per utterance")
+            if not (cmvn.is_cuda and cmvn.dtype == torch.float64 and cmvn.dim() == 3 and cmvn.shape[1] == 2 and cmvn.is_contiguous()):
+                raise _lib.MfaHipError("compress: CMVN statistics must be a contiguous float64 [n_spk, 2, dim + 1] tensor on the device")
+            u2s = np.ascontiguousarray(utt2spk, dtype=np.int32)
+            if n_utt and (u2s.min() < 0 or u2s.max() >= cmvn.shape[0]):
+                raise _lib.MfaHipError(f"compress: utt2spk names a speaker outside the {cmvn.shape[0]} rows of the CMVN statistics")
+            d_u2s = self._dev(u2s)
+        if out is None:
+            out = torch.empty_like(feats) if (c0, c1) == (0, feats.shape[1]) and int(fo[0]) == 0 and int(fo[-1]) == feats.shape[0] \
+                else feats.clone()
+        elif out.shape != feats.shape or out.dtype != feats.dtype or not out.is_cuda or not out.is_contiguous():
+            raise _lib.MfaHipError("compress: the output must match the features' shape and type")
+        self._launch_compress(feats, self._dev(fo), n_utt, c0, c1, cmvn, d_u2s, out, None, None, None)
+        return out
+
+    def compress(self, feats: torch.Tensor, frame_off: np.ndarray, cols: Optional[Tuple[int, int]] = None):
+        """The parts of every utterance's "CM" table for the writers (``kaldi_io.write_compressed_parts``), on the device:
+        (global float32 [n_utt, 2] = min, range; colhdr uint16 [n_utt, c1 - c0, 4]; bytes uint8 [frames · (c1 - c0)], utterance
+        k at frame_off[k] · (c1 - c0), column after column).  An utterance without rows has no table: its headers stay zero."""
+        fo, n_utt, c0, c1 = self._codec_input(feats, frame_off, cols)
+        nc = max(c1 - c0, 0)
+        glob = torch.zeros((n_utt, 2), dtype=torch.float32, device=self.device)
+        colhdr = torch.zeros((n_utt, nc, 4), dtype=torch.int16, device=self.device).view(torch.uint16)
+        data = torch.empty(int(fo[-1]) * nc, dtype=torch.uint8, device=self.device)
+        self._launch_compress(feats, self._dev(fo), n_utt, c0, c1, None, None, None, glob, colhdr, data)
+        return glob, colhdr, data
+
+    def compress_time(self) -> Dict[str, float]:
+        """Accumulated time and launches of the codec kernel under ``kernel_timing`` (slot 7)."""
+        return self._kernel_time(7)
 
     def pitch_time(self) -> Dict[str, float]:
         """Accumulated time and launch groups of the pitch kernels under ``kernel_timing`` (slot 6)."""

@@ -194,6 +194,25 @@ def write_compressed_matrix(f: BinaryIO, m: np.ndarray) -> None:
     f.write(data.tobytes())
 
 
+def write_compressed_parts(f: BinaryIO, global_header, colhdr, data, rows: int, cols: int) -> None:
+    """The "CM" record of ``write_compressed_matrix`` from parts computed elsewhere (``AlignmentEngine.compress``):
+    ``global_header`` float32 (min, range), ``colhdr`` uint16 [cols, 4] percentile codes, ``data`` uint8 [cols, rows]
+    (column after column)."""
+    rows, cols = int(rows), int(cols)
+    if rows <= 0 or cols <= 0:
+        raise ValueError("cannot compress an empty matrix")
+    g = np.ascontiguousarray(global_header, dtype="<f4").reshape(-1)
+    h = np.ascontiguousarray(colhdr)
+    d = np.ascontiguousarray(data)
+    if g.shape != (2,) or h.dtype != np.uint16 or h.size != 4 * cols or d.dtype != np.uint8 or d.size != rows * cols:
+        raise ValueError(f"compressed parts do not describe a {rows} x {cols} table")
+    _w_token(f, "CM")
+    f.write(g.tobytes())
+    f.write(struct.pack("<ii", rows, cols))
+    f.write(h.astype("<u2").tobytes())
+    f.write(d.tobytes())
+
+
 def compress_round_trip(m: np.ndarray) -> np.ndarray:
     """What a feature matrix looks like after it has been written to and read back from a Kaldi CompressedMatrix table
     (8-bit, per-column headers) — the corpus path of the reference stores raw MFCCs and the CMVN-applied features this way

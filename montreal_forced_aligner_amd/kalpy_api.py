@@ -175,10 +175,21 @@ class MfccComputer:
                 d = torch.from_numpy(np.concatenate([x for _, x, _ in batch])).to(eng.device)
                 d, so = eng.resample(d, so, [r for _, _, r in batch])       # the whole batch in one call (a launch per rate)
                 out, fo = eng.mfcc(d, so)
-                out = out.cpu().numpy()
-                for i, (key, _, _) in enumerate(batch):
-                    off = kaldi_io.write_ark_entry(f, key, out[fo[i]: fo[i + 1]], "compressed_matrix" if compress else "matrix")
-                    lines.append(f"{key} {ark}:{off}\n")
+                if compress:          # headers and bytes from the device codec: a quarter of the float bytes come back
+                    nc = int(out.shape[1])
+                    glob, colhdr, data = (t.cpu().numpy() for t in eng.compress(out, fo))
+                    for i, (key, _, _) in enumerate(batch):
+                        f.write(key.encode("utf8") + b" ")
+                        off = f.tell()
+                        f.write(b"\0B")
+                        rows = int(fo[i + 1] - fo[i])
+                        kaldi_io.write_compressed_parts(f, glob[i], colhdr[i], data[fo[i] * nc: fo[i + 1] * nc], rows, nc)
+                        lines.append(f"{key} {ark}:{off}\n")
+                else:
+                    out = out.cpu().numpy()
+                    for i, (key, _, _) in enumerate(batch):
+                        off = kaldi_io.write_ark_entry(f, key, out[fo[i]: fo[i + 1]], "matrix")
+                        lines.append(f"{key} {ark}:{off}\n")
                 batch.clear()
 
             for key, seg in segments:
