@@ -47,7 +47,7 @@ MFA_API int mfa_memcpy_d2h(mfa_ctx *ctx, void *h_dst, const void *d_src, size_t 
 MFA_API int mfa_timer_begin(mfa_ctx *ctx);
 MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
 /* Per-kernel accumulated HIP-event times since the last reset.  which: 0 mfcc, 1 cmvn, 2 feats, 3 gmm, 4 viterbi,
- * 5 resample, 6 pitch, 7 feature codec.
+ * 5 resample, 6 pitch, 7 feature codec, 8-11 GMM statistics (lookup, ordering, sums, reduction).
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -513,6 +513,51 @@ MFA_API int mfa_fmllr_acc_ali_batch(mfa_ctx *ctx, const float *d_feats, const in
  * Gaussians in every pdf.  Stays in force until the next mfa_load_gmm, or until called with NULL arrays. */
 MFA_API int mfa_fmllr_stats_model(mfa_ctx *ctx, int32_t dim, int32_t num_pdfs, const int32_t *h_pdf_offsets,
                                   const float *h_means_invvars, const float *h_inv_vars);
+
+/* ---- GMM statistics: replaces the accumulation of AccStatsFunction / kalpy GmmStatsAccumulator.accumulate_stats
+ *      (MFA/alignment/adapting.py, MFA/alignment/multiprocessing.py:40; Kaldi gmm-acc-stats-ali =
+ *      AccumAmDiagGmm::AccumulateForGmm, restated here from the algorithm's description — Kaldi's source is not among this
+ *      project's references: parity unpinned).  The E-step of `mfa adapt` and of every training stage.
+ *
+ * Arithmetic contract.  A frame t takes no part when its transition-id d_ali[t] is outside the table (< 0 or >= n_tids), is
+ * 0, or has weight 0 (or names a pdf the loaded model does not have).  Otherwise p = d_tid2pdf[d_ali[t]],
+ * w = d_tid_weight[d_ali[t]], and for every Gaussian g of pdf p, in model order:
+ *   log-likelihood   ll_g: the float32 fmaf chain of the fMLLR statistics — from gconst_g, then means_invvars_g[k] * x[k]
+ *                    over ascending k, then (-0.5f * inv_vars_g[k]) * (x[k] * x[k]) over ascending k;
+ *   softmax          m = max ll, e_g = expf(ll_g - m), s = sum of e_g, gamma_g = e_g * (1 / s) * w, all float32; the frame's
+ *                    log-likelihood is m + logf(s);
+ *   sums (double, explicit fma)
+ *                    occ[g] += gamma_g;  mean[g][k] = fma(gamma_g, x_k, mean[g][k]);
+ *                    var[g][k] = fma(gamma_g, x_k * x_k, var[g][k]) with the square formed in double;
+ *                    tot[0] = fma(w, loglike, tot[0]);  tot[1] += w;
+ *   counts           tid_count[d_ali[t]] += 1 (int64).
+ * The accumulators are indexed by MODEL Gaussian (pdf_offsets of mfa_load_gmm, not packed rows): d_occ [G], d_mean / d_var
+ * [G][dim], d_tot [2], d_tid_count [n_tids] (may be NULL).  They are added to, never overwritten.
+ * Order of the double sums on the device: the frames of a pdf in ascending frame index, cut into chunks of
+ * mfa_gmm_acc_chunk_frames() consecutive frames of that pdf; a chunk is summed from zero in frame order, the chunks are
+ * added in order onto the caller's value; tot sums the chunks' totals in (pdf, chunk) order.  The result is therefore a
+ * function of the input alone: two calls on the same input give the same bits.  No floating-point atomics.
+ * mfa_debug_gmm_acc_host is the same contract on host arrays, frames in ascending index, expf / logf from libm: the
+ * log-likelihood bits are the device's by construction (both run csrc/gmm_acc_math.hpp); only expf / logf, the order in
+ * which the e_g are added and the order of the double sums may differ.
+ * Runs on the model loaded with mfa_load_gmm, asynchronously on the ctx stream.  Limits (refused with a message, the
+ * context stays usable): no model loaded; a pdf of more than 128 Gaussians; dim > mfa_gmm_acc_max_dim() = 48 (a thread of
+ * the sum kernel owns 3 of 48 columns); 2^31 frames or more in one call.  total_frames == 0 is no error and writes nothing. */
+MFA_API int32_t mfa_gmm_acc_chunk_frames(void);
+MFA_API int32_t mfa_gmm_acc_max_dim(void);
+MFA_API int mfa_gmm_acc_batch(mfa_ctx *ctx, const float *d_feats, int64_t total_frames, const int32_t *d_ali,
+                              const int32_t *d_tid2pdf, const float *d_tid_weight, int32_t n_tids, double *d_occ, double *d_mean,
+                              double *d_var, double *d_tot, int64_t *d_tid_count);
+/* Host twin, no context and no device.  The model as mfa_load_gmm takes it; h_feats [total_frames][dim]; per frame
+ * h_pdf (< 0 or >= num_pdfs: the frame takes no part) and h_weight (0: no part); h_tid [total_frames] with n_tids (both
+ * optional: NULL / 0) feed h_tid_count (may be NULL).  h_post (may be NULL): [total_frames][post_stride] receives every
+ * frame's gamma (0 beyond the pdf's Gaussians and for frames that take no part); post_stride >= the largest pdf.
+ * Returns 0, -1 for bad arguments or an empty pdf, -2 for a pdf of more than 128 Gaussians. */
+MFA_API int mfa_debug_gmm_acc_host(int32_t dim, int32_t num_pdfs, const int32_t *h_pdf_offsets, const float *h_gconsts,
+                                   const float *h_means_invvars, const float *h_inv_vars, const float *h_feats,
+                                   int64_t total_frames, const int32_t *h_pdf, const float *h_weight, const int32_t *h_tid,
+                                   int32_t n_tids, double *h_occ, double *h_mean, double *h_var, double *h_tot,
+                                   int64_t *h_tid_count, float *h_post, int32_t post_stride);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,9 @@ from . import _lib
 from . import fmllr as _fmllr
 from . import graph as _graph
 from . import sharding
-from .engine import AlignmentEngine, fmllr_statistics, redo_capacity
+from . import adapt as _adapt
+from . import kaldi_io
+from .engine import AlignmentEngine, GmmStats, fmllr_statistics, gmm_statistics, redo_capacity
 from .model import DiagGmmModel, TransitionModel
 
 
@@ -127,8 +129,17 @@ class CorpusAligner:
     def __init__(self, tm: TransitionModel, am: DiagGmmModel, tree, lexicon, lda: Optional[np.ndarray] = None,
                  options: Optional[AlignOptions] = None, device: int = 0, engine: Optional[AlignmentEngine] = None,
                  mfcc_options: Optional[dict] = None, silence_phones: Sequence[int] = (),
-                 ali_am: Optional[DiagGmmModel] = None, lazy: bool = True, pitch_options: Optional[dict] = None):
+                 ali_am: Optional[DiagGmmModel] = None, lazy: bool = True, pitch_options: Optional[dict] = None,
+                 raw_tm: Optional[kaldi_io.RawTransitionModel] = None, raw_am: Optional[kaldi_io.RawAmDiagGmm] = None,
+                 raw_ali_am: Optional[kaldi_io.RawAmDiagGmm] = None):
         self.tm, self.tree, self.lexicon = tm, tree, lexicon
+        # the models as their files hold them (kaldi_io.read_model): what ``adapt`` updates and ``write_adapted`` writes
+        self.raw_tm, self.raw_am, self.raw_ali_am = raw_tm, raw_am, raw_ali_am
+        self.adapted: Optional[tuple] = None             # (raw tm, raw am, raw ali_am | None) of the last ``adapt``
+        self.adapt_stats: Optional[GmmStats] = None      # its statistics on ``am`` (``adapt_ali_stats``: on ``ali_am``)
+        self.adapt_ali_stats: Optional[GmmStats] = None
+        self.adapt_loglike: Dict[str, Optional[float]] = {}   # average log-likelihood per frame the reference logs, per model
+        self.adapt_counts: Dict[str, tuple] = {}         # Gaussians (updated, kept) per model
         self.lda = None if lda is None else np.asarray(lda, dtype=np.float32)
         self.opt = options or AlignOptions()
         self.engine = engine or AlignmentEngine(device)
@@ -496,12 +507,14 @@ class CorpusAligner:
         self.fmllr_rejected = []
         self._mfcc_cache, self._mfcc_cache_bytes, self._mfcc_cache_on = {}, 0, True
         try:
-            return self._align(utts, speaker_adapted, make_ctm, previous_transforms)
+            return self._align(utts, speaker_adapted, make_ctm, previous_transforms)[0]
         finally:
             self._mfcc_cache, self._mfcc_cache_bytes, self._mfcc_cache_on = {}, 0, False
             self._batches_key = None
 
-    def _align(self, utts, speaker_adapted, make_ctm, previous_transforms):
+    def _align(self, utts, speaker_adapted, make_ctm, previous_transforms, keep_last=False):
+        """Returns (results, kept): ``kept`` — with ``keep_last`` — is what the LAST pass left on the device per batch,
+        (utterance indices, final features, alignments with failed utterances zeroed, frame offsets, speaker rows)."""
         import torch
 
         batches = self._batches(utts)
@@ -510,7 +523,7 @@ class CorpusAligner:
         first_model = self.ali_am if self.ali_am is not None else self.am
         self._load(first_model)
         prev = None if previous_transforms is None else torch.from_numpy(np.asarray(previous_transforms, dtype=np.float32)).to(self.engine.device)
-        results, kept = self._pass(utts, spk_ids, cmvn, prev, want_feats=speaker_adapted, first_compile=first_compile)
+        results, kept = self._pass(utts, spk_ids, cmvn, prev, want_feats=speaker_adapted or keep_last, first_compile=first_compile)
         self.transforms = None if previous_transforms is None else np.asarray(previous_transforms, dtype=np.float32)
         if speaker_adapted:
             # the transform follows either feature branch: the LDA's rows, or Δ+ΔΔ of the cepstra (MFA/db.py:2101-2136)
@@ -533,7 +546,7 @@ class CorpusAligner:
             self._load(self.am)
             first = results
             self.failure_reasons = {}
-            results, _ = self._pass(utts, spk_ids, cmvn, torch.from_numpy(W).to(self.engine.device))
+            results, kept = self._pass(utts, spk_ids, cmvn, torch.from_numpy(W).to(self.engine.device), want_feats=keep_last)
             if self.ali_am is not None:
                 # an utterance the second pass lost keeps its first-pass (alignment-model) result:
                 # ali_first_pass / words_first_pass / likelihoods_first_pass, MFA/alignment/multiprocessing.py:1784-1860
@@ -542,7 +555,91 @@ class CorpusAligner:
                         results[i] = r1
                         self.fallback_first_pass.append(utts[i].utt_id)
                         self.failure_reasons.pop(utts[i].utt_id, None)
-        return self._results(utts, results, make_ctm)
+        return self._results(utts, results, make_ctm), (kept if keep_last else [])
+
+    # ------------------------------------------------------------------ model adaptation
+    def adapt(self, utterances: Sequence[CorpusUtterance], speaker_adapted: bool = False, mapping_tau: float = 20.0,
+              update_transitions: bool = True, make_ctm: bool = True) -> List[Optional[UtteranceResult]]:
+        """``mfa adapt`` (MFA/alignment/adapting.py): align the corpus as ``align`` does, accumulate GMM statistics from the
+        alignments of the last pass on the device (``engine.gmm_statistics``), smooth them towards the old model with
+        ``mapping_tau`` frames, re-estimate the means and — with ``update_transitions`` — the transition probabilities, and
+        load the new model.  Returns the results of the alignment (made with the OLD model).
+
+        Statistics are formed with the model as its file holds it (``raw_am``, no silence boost: the reference reads
+        ``unadapted.mdl`` from disk), on the final features of the last pass — with ``speaker_adapted`` the fMLLR-transformed
+        ones.  With ``speaker_adapted`` and an ``ali_am`` the alignment model is adapted from the SAME features and
+        alignments: the reference's AccStatsFunction builds its feature archive with Job.construct_feature_archive
+        (MFA/db.py:2101-2136), which picks up the ``trans`` table whenever one exists, for either model.  Utterances that
+        failed contribute nothing.  Needs the raw models (``raw_tm=``, ``raw_am=`` and, for the alignment model,
+        ``raw_ali_am=`` of the constructor).  Afterwards: ``adapted`` (raw tm, am, ali_am), ``adapt_stats`` /
+        ``adapt_ali_stats``, ``adapt_loglike`` and ``adapt_counts``; ``write_adapted`` writes the files."""
+        if self.raw_tm is None or self.raw_am is None:
+            raise ValueError("adapt needs the models as read from their files: CorpusAligner(..., raw_tm=, raw_am=[, raw_ali_am=])")
+        both = bool(speaker_adapted) and self.ali_am is not None
+        if both and self.raw_ali_am is None:
+            raise ValueError("adapt with an alignment model needs raw_ali_am= as well")
+        utts = list(utterances)
+        self.failed, self.failure_reasons, self.fallback_first_pass, self.ctm_failed = [], {}, [], []
+        self.fmllr_rejected = []
+        self._mfcc_cache, self._mfcc_cache_bytes, self._mfcc_cache_on = {}, 0, True
+        try:
+            results, kept = self._align(utts, speaker_adapted, make_ctm, None, keep_last=True)
+        finally:
+            self._mfcc_cache, self._mfcc_cache_bytes, self._mfcc_cache_on = {}, 0, False
+            self._batches_key = None
+        n_tids = self.tm.num_transition_ids + 1
+
+        def accumulate(raw):
+            model = DiagGmmModel.from_raw(raw)
+            self.engine.load_gmm(model)
+            self._loaded = model
+            st = GmmStats.zeros(model.num_gauss, model.dim, n_tids)
+            for _idx, feats, ali, _fo, _rows in kept:
+                gmm_statistics(self.engine, feats, ali, self.tm, into=st)
+            return st
+
+        self.adapt_stats = accumulate(self.raw_am)
+        new_am, up, keep = _adapt.adapt_model(self.raw_am, self.adapt_stats, mapping_tau)
+        self.adapt_counts = {"mdl": (up, keep)}
+        self.adapt_loglike = {"mdl": self.adapt_stats.loglike_per_frame, "alimdl": None}
+        new_ali, self.adapt_ali_stats = None, None
+        if both:
+            self.adapt_ali_stats = accumulate(self.raw_ali_am)
+            new_ali, up, keep = _adapt.adapt_model(self.raw_ali_am, self.adapt_ali_stats, mapping_tau)
+            self.adapt_counts["alimdl"] = (up, keep)
+            self.adapt_loglike["alimdl"] = self.adapt_ali_stats.loglike_per_frame
+        new_tm = _adapt.transition_update(self.raw_tm, self.adapt_stats.tid_count) if update_transitions else self.raw_tm
+        self.adapted = (new_tm, new_am, new_ali)
+        self._reload(new_tm, new_am, new_ali)
+        return results
+
+    def _reload(self, raw_tm, raw_am, raw_ali_am) -> None:
+        """Make the adapted models the aligner's own: transition model (graphs, scaled probabilities), boosted copies, device."""
+        self.raw_tm, self.raw_am = raw_tm, raw_am
+        self.tm = TransitionModel(raw_tm)
+        self.am = self._boosted(DiagGmmModel.from_raw(raw_am))
+        if raw_ali_am is not None:
+            self.raw_ali_am = raw_ali_am
+            self.ali_am = self._boosted(DiagGmmModel.from_raw(raw_ali_am))
+        self.compiler = _graph.TrainingGraphCompiler(self.tm, self.tree, self.lexicon)
+        self.scaled = self.tm.scaled_log_probs(self.opt.transition_scale, self.opt.self_loop_scale)
+        self._intervals = None
+        self._load(self.am)
+
+    def write_adapted(self, directory) -> List[Path]:
+        """``final.mdl`` and, when the alignment model was adapted, ``final.alimdl`` of the last ``adapt``."""
+        if self.adapted is None:
+            raise ValueError("write_adapted: adapt has not been run")
+        out_dir = Path(directory)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        tm, am, ali = self.adapted
+        written = []
+        for name, model in (("final.mdl", am), ("final.alimdl", ali)):
+            if model is not None:
+                with open(out_dir / name, "wb") as f:
+                    kaldi_io.write_model(f, tm, model)
+                written.append(out_dir / name)
+        return written
 
     def _extractor(self):
         if self._intervals is None:

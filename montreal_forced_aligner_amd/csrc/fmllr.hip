@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "tid_lookup.hpp"   // fmllr_tid_lookup_kernel, shared with gmm_acc.hip
 
 namespace {
 
@@ -201,17 +202,6 @@ MFA_API int mfa_fmllr_acc_batch(mfa_ctx *c, const float *d_feats, const int64_t 
   return 0;
 }
 
-// alignment (transition-ids) → per-frame pdf and weight through the host-built tables (0 / unknown ids: weight 0)
-__global__ void fmllr_tid_lookup_kernel(const int32_t *ali, int64_t n, const int32_t *tid2pdf, const float *tid_weight,
-                                        int32_t n_tids, int32_t *pdf, float *weight) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const int tid = ali[t];
-  const bool ok = tid > 0 && tid < n_tids;
-  pdf[t] = ok ? tid2pdf[tid] : -1;
-  weight[t] = ok ? tid_weight[tid] : 0.0f;
-}
-
 MFA_API int mfa_fmllr_acc_ali_batch(mfa_ctx *c, const float *d_feats, const int64_t *d_frame_off, int32_t n_utt,
                                     int64_t total_frames, const int32_t *d_ali, const int32_t *d_tid2pdf,
                                     const float *d_tid_weight, int32_t n_tids, int32_t *d_pdf_scratch, float *d_weight_scratch,
@@ -220,7 +210,7 @@ MFA_API int mfa_fmllr_acc_ali_batch(mfa_ctx *c, const float *d_feats, const int6
   MFA_HIP_CHECK(c, hipSetDevice(c->device));
   if (n_utt <= 0 || n_spk <= 0 || total_frames <= 0) return 0;
   hipLaunchKernelGGL(fmllr_tid_lookup_kernel, dim3((unsigned)((total_frames + 255) / 256)), dim3(256), 0, c->stream, d_ali,
-                     total_frames, d_tid2pdf, d_tid_weight, n_tids, d_pdf_scratch, d_weight_scratch);
+                     total_frames, d_tid2pdf, d_tid_weight, n_tids, d_pdf_scratch, d_weight_scratch, TidLookupSort{});
   MFA_HIP_CHECK(c, hipGetLastError());
   return mfa_fmllr_acc_batch(c, d_feats, d_frame_off, n_utt, total_frames, d_pdf_scratch, d_weight_scratch, d_spk_utt_off,
                              d_spk_utt, n_spk, d_beta, d_K, d_G);

@@ -109,13 +109,14 @@ MFA_API int mfa_load_gmm(mfa_ctx *c, int32_t dim, int32_t num_pdfs, const int32_
   const bool split = m.split();
   auto up = [](MfaBuf &dst, const auto &v) { return DevUpload<MfaHipDev>{&dst, v.data(), v.size() * sizeof(v[0])}; };
   // An empty array empties its buffer: the split operands of a model that has none (gmm_pack_model leaves them empty, all
-  // but fscale), and d_w_stats and d_nrows, which belonged to the previous layout (fmllr.hip builds them on demand).
+  // but fscale), and d_w_stats, d_nrows and d_acc_tabs, which belonged to the previous layout (fmllr.hip and gmm_acc.hip
+  // build them on demand).
   const std::vector<float> none;
   return dev_upload_commit<MfaHipDev>(
       c, "the acoustic model",
       {up(c->d_w, m.w), up(c->d_gc, m.gc), up(c->d_row0, m.row0), up(c->d_nblk, m.nblk), up(c->d_slot, m.slot),
        up(c->d_wb, m.wb), up(c->d_wh, m.wh), up(c->d_gch, m.gch), up(c->d_fscale, split ? m.fscale : none),
-       up(c->d_w_stats, none), up(c->d_nrows, none)},
+       up(c->d_w_stats, none), up(c->d_nrows, none), up(c->d_acc_tabs, none)},
       [&] {
         c->dim = dim; c->kpad = m.kpad; c->num_pdfs = num_pdfs; c->num_rows = m.rows;
         if (split) c->gmm_acc_scale = m.acc_scale;

@@ -1388,3 +1388,125 @@ def fmllr_statistics(engine: "AlignmentEngine", feats: torch.Tensor, frame_off: 
                                                           int(id2pdf.shape[0]), _ptr(pdf), _ptr(weight), _ptr(d_so), _ptr(d_su),
                                                           n_spk, _ptr(beta), _ptr(K), _ptr(G)), "mfa_fmllr_acc_ali_batch")
     return spk_ids, beta.cpu().numpy(), K.cpu().numpy(), G.cpu().numpy()
+
+
+@dataclass
+class GmmStats:
+    """GMM sufficient statistics, indexed by model Gaussian (``DiagGmmModel.pdf_offsets``): float64 ``occ`` [G], ``mean_acc`` /
+    ``var_acc`` [G, dim], ``tot_like`` = Σ w·loglike, ``tot_count`` = Σ w, int64 ``tid_count`` [transition-ids + 1].  Additive:
+    ``a += b`` (AccumAmDiagGmm::Add); what a sum over batches, or later over ranks, needs."""
+
+    occ: np.ndarray
+    mean_acc: np.ndarray
+    var_acc: np.ndarray
+    tot_like: float
+    tot_count: float
+    tid_count: np.ndarray
+
+    @classmethod
+    def zeros(cls, num_gauss: int, dim: int, n_tids: int) -> "GmmStats":
+        return cls(np.zeros(num_gauss), np.zeros((num_gauss, dim)), np.zeros((num_gauss, dim)), 0.0, 0.0, np.zeros(n_tids, dtype=np.int64))
+
+    def copy(self) -> "GmmStats":
+        return GmmStats(self.occ.copy(), self.mean_acc.copy(), self.var_acc.copy(), self.tot_like, self.tot_count, self.tid_count.copy())
+
+    def __iadd__(self, other: "GmmStats") -> "GmmStats":
+        if self.mean_acc.shape != other.mean_acc.shape or self.tid_count.shape != other.tid_count.shape:
+            raise ValueError("GmmStats of different models cannot be added")
+        self.occ += other.occ
+        self.mean_acc += other.mean_acc
+        self.var_acc += other.var_acc
+        self.tot_like += other.tot_like
+        self.tot_count += other.tot_count
+        self.tid_count += other.tid_count
+        return self
+
+    @property
+    def loglike_per_frame(self) -> float:
+        """What the reference logs after accumulation: total log-likelihood over total weight."""
+        return self.tot_like / self.tot_count if self.tot_count else 0.0
+
+
+def tid_tables(tm: TransitionModel, weights: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The two host-built tables of mfa_gmm_acc_batch: pdf of every transition-id (int32; index 0 unused) and its frame
+    weight (float32; 1 for every id but 0 unless ``weights`` [transition-ids + 1] is given)."""
+    id2pdf = np.maximum(tm.id2pdf, 0).astype(np.int32)
+    w = np.ones(id2pdf.shape[0], dtype=np.float32) if weights is None else np.ascontiguousarray(weights, dtype=np.float32).copy()
+    if w.shape != id2pdf.shape:
+        raise ValueError(f"weights: {w.shape[0]} entries for {id2pdf.shape[0] - 1} transition-ids (+ 1)")
+    w[0] = 0.0
+    return id2pdf, w
+
+
+def gmm_statistics(engine: "AlignmentEngine", feats: torch.Tensor, ali: torch.Tensor, tm: TransitionModel,
+                   weights: Optional[np.ndarray] = None, into: Optional[GmmStats] = None) -> GmmStats:
+    """GMM statistics of one batch from its alignments (mfa_gmm_acc_batch; the contract is in include/mfa_hip.h), with the
+    model loaded in the engine.
+
+    ``feats`` float32 [ΣT, dim] and ``ali`` int32 [ΣT] transition-ids on the device (0 where an utterance failed: those frames
+    take no part); ``weights``: per transition-id frame weights (default 1).  ``into``: statistics to add to — the device sums
+    start from its values, so a corpus accumulated batch by batch is one chain of additions — and the object returned."""
+    if engine.gmm is None:
+        raise _lib.MfaHipError("gmm_statistics: no acoustic model loaded (AlignmentEngine.load_gmm)")
+    dev = engine.device
+    gmm = engine.gmm
+    G, D = gmm.num_gauss, gmm.dim
+    id2pdf, w = tid_tables(tm, weights)
+    n_tids = int(id2pdf.shape[0])
+    st = into if into is not None else GmmStats.zeros(G, D, n_tids)
+    if st.mean_acc.shape != (G, D) or st.tid_count.shape != (n_tids,):
+        raise ValueError("gmm_statistics: `into` does not fit the loaded model")
+    total = int(ali.shape[0])
+    if feats.shape[0] != total or (total and feats.shape[1] != D):
+        raise _lib.MfaHipError(f"gmm_statistics: features {tuple(feats.shape)} for {total} frames of a model of dim {D}")
+    if feats.dtype != torch.float32 or not feats.is_cuda or not ali.is_cuda:
+        raise _lib.MfaHipError("gmm_statistics: features must be float32 and, like the alignments, on the device")
+    feats = feats.contiguous()
+    ali = ali.to(torch.int32).contiguous()
+    occ = torch.from_numpy(st.occ).to(dev)
+    mean = torch.from_numpy(np.ascontiguousarray(st.mean_acc)).to(dev)
+    var = torch.from_numpy(np.ascontiguousarray(st.var_acc)).to(dev)
+    tot = torch.tensor([st.tot_like, st.tot_count], dtype=torch.float64, device=dev)
+    cnt = torch.from_numpy(st.tid_count).to(dev)
+    d_pdf, d_w = torch.from_numpy(id2pdf).to(dev), torch.from_numpy(w).to(dev)
+    check(engine.ctx, engine.lib.mfa_gmm_acc_batch(engine.ctx, _ptr(feats), total, _ptr(ali), _ptr(d_pdf), _ptr(d_w), n_tids,
+                                                    _ptr(occ), _ptr(mean), _ptr(var), _ptr(tot), _ptr(cnt)), "mfa_gmm_acc_batch")
+    st.occ, st.mean_acc, st.var_acc, st.tid_count = occ.cpu().numpy(), mean.cpu().numpy(), var.cpu().numpy(), cnt.cpu().numpy()
+    t = tot.cpu().numpy()
+    st.tot_like, st.tot_count = float(t[0]), float(t[1])
+    return st
+
+
+def gmm_statistics_host(gmm: DiagGmmModel, feats: np.ndarray, ali: np.ndarray, tm: TransitionModel,
+                        weights: Optional[np.ndarray] = None, into: Optional[GmmStats] = None, want_post: bool = False):
+    """The same call on the host twin (mfa_debug_gmm_acc_host: no device, frames in ascending index): the specification the
+    device is held to.  numpy arrays in; with ``want_post`` also returns every frame's posteriors [ΣT, largest pdf]."""
+    lib = _lib.lib()
+    id2pdf, w = tid_tables(tm, weights)
+    n_tids = int(id2pdf.shape[0])
+    G, D = gmm.num_gauss, gmm.dim
+    st = into if into is not None else GmmStats.zeros(G, D, n_tids)
+    feats = np.ascontiguousarray(feats, dtype=np.float32)
+    ali = np.ascontiguousarray(ali, dtype=np.int32)
+    ok = (ali > 0) & (ali < n_tids)
+    safe = np.where(ok, ali, 0)
+    pdf = np.where(ok, id2pdf[safe], -1).astype(np.int32)
+    fw = np.where(ok, w[safe], np.float32(0)).astype(np.float32)
+    po = np.ascontiguousarray(gmm.pdf_offsets, dtype=np.int32)
+    gc = np.ascontiguousarray(gmm.gconsts, dtype=np.float32)
+    mi = np.ascontiguousarray(gmm.means_invvars, dtype=np.float32)
+    iv = np.ascontiguousarray(gmm.inv_vars, dtype=np.float32)
+    occ, mean, var = (np.ascontiguousarray(a, dtype=np.float64) for a in (st.occ, st.mean_acc, st.var_acc))
+    tot = np.array([st.tot_like, st.tot_count], dtype=np.float64)
+    cnt = np.ascontiguousarray(st.tid_count, dtype=np.int64)
+    stride = int(np.diff(po).max())
+    post = np.zeros((ali.shape[0], stride), dtype=np.float32) if want_post else None
+    rc = lib.mfa_debug_gmm_acc_host(D, gmm.num_pdfs, po.ctypes.data, gc.ctypes.data, mi.ctypes.data, iv.ctypes.data,
+                                    feats.ctypes.data, int(ali.shape[0]), pdf.ctypes.data, fw.ctypes.data, ali.ctypes.data, n_tids,
+                                    occ.ctypes.data, mean.ctypes.data, var.ctypes.data, tot.ctypes.data, cnt.ctypes.data,
+                                    None if post is None else post.ctypes.data, stride)
+    if rc != 0:
+        raise _lib.MfaHipError(f"mfa_debug_gmm_acc_host: {'a pdf of more than 128 Gaussians' if rc == -2 else 'bad arguments'}")
+    st.occ, st.mean_acc, st.var_acc, st.tid_count = occ, mean, var, cnt
+    st.tot_like, st.tot_count = float(tot[0]), float(tot[1])
+    return (st, post) if want_post else st

@@ -700,6 +700,101 @@ class GmmAligner:
                     f.close()
 
 
+# ------------------------------------------------------------------------------------------------ statistics / adaptation
+class AccumAmDiagGmm:
+    """``_kalpy.gmm.AccumAmDiagGmm`` as MFA/alignment/adapting.py uses it: ``init(acoustic_model)``, ``Add(scale, other)``,
+    ``TotLogLike()``, ``TotCount()``.  ``stats`` is the ``engine.GmmStats`` behind it (its transition-id counts are the
+    accumulator's ``transition_accs``)."""
+
+    def __init__(self):
+        self.stats = None
+
+    def init(self, acoustic_model, n_tids: int = 1) -> None:
+        from .engine import GmmStats
+        self.stats = GmmStats.zeros(acoustic_model.num_gauss, acoustic_model.dim, n_tids)
+
+    def Add(self, scale: float, other: "AccumAmDiagGmm") -> None:
+        if float(scale) != 1.0:
+            raise NotImplementedError("AccumAmDiagGmm.Add: only scale 1.0")
+        o = other.stats
+        if self.stats.tid_count.shape != o.tid_count.shape:          # (init() does not know the transition model)
+            self.stats.tid_count = np.zeros_like(o.tid_count)
+        self.stats += o
+
+    def TotLogLike(self) -> float:
+        return float(self.stats.tot_like)
+
+    def TotCount(self) -> float:
+        return float(self.stats.tot_count)
+
+
+def IsmoothStatsAmDiagGmmFromModel(acoustic_model, tau: float, gmm_accs: AccumAmDiagGmm) -> None:
+    """In place, as the reference calls it (MFA/alignment/adapting.py:117)."""
+    from . import adapt
+    gmm_accs.stats = adapt.ismooth_from_model(adapt.raw_from_soa(acoustic_model), gmm_accs.stats, tau)
+
+
+class GmmStatsAccumulator:
+    """``kalpy.gmm.train.GmmStatsAccumulator(model_path)``: ``accumulate_stats(feature_archive, alignment_archive,
+    callback=None)`` over (key, matrix) features and ``Alignment`` objects, then ``gmm_accs`` / ``transition_accs``
+    (MFA/alignment/multiprocessing.py:40, :652-666).  Utterances are batched onto the device (``engine.gmm_statistics``)."""
+
+    def __init__(self, acoustic_model_path, batch_frames: int = 500_000):
+        self.acoustic_model_path = acoustic_model_path
+        self.transition_model, self.acoustic_model = _read_model(acoustic_model_path)
+        self.gmm_accs = AccumAmDiagGmm()
+        self.gmm_accs.init(self.acoustic_model, self.transition_model.num_transition_ids + 1)
+        self.batch_frames = int(batch_frames)
+
+    @property
+    def transition_accs(self) -> np.ndarray:
+        """Counts per transition-id as float64 (kalpy: a DoubleVector), index 0 unused."""
+        return self.gmm_accs.stats.tid_count.astype(np.float64)
+
+    def accumulate_stats(self, feature_archive, alignment_archive, callback=None) -> None:
+        import torch
+        from .engine import gmm_statistics
+
+        eng = get_engine()
+        if eng.gmm is not self.acoustic_model:
+            eng.load_gmm(self.acoustic_model)
+        feats = dict(feature_archive) if not isinstance(feature_archive, dict) else feature_archive
+        rows, alis, total = [], [], 0
+
+        def flush():
+            nonlocal rows, alis, total
+            if rows:
+                gmm_statistics(eng, torch.from_numpy(np.concatenate(rows).astype(np.float32)).to(eng.device),
+                               torch.from_numpy(np.concatenate(alis).astype(np.int32)).to(eng.device), self.transition_model,
+                               into=self.gmm_accs.stats)
+            rows, alis, total = [], [], 0
+
+        for al in alignment_archive:
+            x = feats.get(al.utterance_id)
+            if x is None:
+                continue
+            a = np.asarray(al.alignment, dtype=np.int32)
+            if a.shape[0] != x.shape[0]:
+                logger.warning("utterance %s: %d alignment entries for %d frames, skipped", al.utterance_id, a.shape[0], x.shape[0])
+                continue
+            rows.append(np.asarray(x)); alis.append(a); total += a.shape[0]
+            if callback:
+                callback(al.utterance_id)
+            if total >= self.batch_frames:
+                flush()
+        flush()
+
+
+def write_gmm_model(path, transition_model, acoustic_model) -> None:
+    """``kalpy.gmm.utils.write_gmm_model(path, transition_model, acoustic_model)`` for the objects ``read_gmm_model``
+    returns (the mixture weights are the model's own when it was read from a file)."""
+    from . import adapt
+    raw_tm = kaldi_io.RawTransitionModel(transition_model.raw.topo, transition_model.raw.tuples,
+                                         transition_model.log_probs.astype(np.float32))
+    with open(path, "wb") as f:
+        kaldi_io.write_model(f, raw_tm, adapt.raw_from_soa(acoustic_model))
+
+
 HierarchicalCtm = _ctm.HierarchicalCtm
 CtmInterval = _ctm.CtmInterval
 WordCtmInterval = _ctm.WordCtmInterval

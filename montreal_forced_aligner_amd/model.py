@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes
 import ctypes.util
 from dataclasses import dataclass
-from typing import Iterable, List
+from typing import Iterable, List, Optional
 
 import numpy as np
 
@@ -105,6 +105,21 @@ class TransitionModel:
     def transition_id(self, ts: int, index: int) -> int:
         return int(self.state2id[ts]) + index
 
+    def mle_update(self, transition_accs):
+        """kalpy's ``transition_model.mle_update(transition_accs)``: new transition probabilities from the counts
+        (``adapt.transition_update``), in place.  Returns (log-likelihood improvement, count) over the states updated."""
+        from . import adapt
+
+        cnt = np.asarray(transition_accs, dtype=np.float64)
+        new = adapt.transition_update(self.raw, cnt)
+        moved = new.log_probs != self.log_probs
+        states = np.unique(self.id2state[moved])
+        touched = np.isin(self.id2state, states[states > 0])
+        impr = float(np.sum(cnt[touched] * (new.log_probs[touched].astype(np.float64) - self.log_probs[touched])))
+        self.raw = new
+        self.log_probs = new.log_probs.astype(np.float32)
+        return impr, float(cnt[touched].sum())
+
     def flat_topology(self):
         """Flattened topology arrays in the layout the oracle's orc_tm_derive takes (tests use this)."""
         phone2entry = self.topo.phone2idx.astype(np.int32)
@@ -129,7 +144,8 @@ class TransitionModel:
 class DiagGmmModel:
     """All Gaussians of an AmDiagGmm, concatenated (struct of arrays).
 
-    gconsts [G], means_invvars [G, D], inv_vars [G, D], pdf_offsets [P+1] (Gaussian range per pdf).
+    gconsts [G], means_invvars [G, D], inv_vars [G, D], pdf_offsets [P+1] (Gaussian range per pdf); weights [G] (optional:
+    the mixture weights, already folded into the gconsts — kept for model adaptation, which writes models back).
     """
 
     dim: int
@@ -137,6 +153,7 @@ class DiagGmmModel:
     means_invvars: np.ndarray
     inv_vars: np.ndarray
     pdf_offsets: np.ndarray
+    weights: Optional[np.ndarray] = None
 
     @property
     def num_pdfs(self) -> int:
@@ -157,7 +174,29 @@ class DiagGmmModel:
             np.concatenate(am.means_invvars, axis=0).astype(np.float32),
             np.concatenate(am.inv_vars, axis=0).astype(np.float32),
             offs,
+            np.concatenate(am.weights).astype(np.float32),
         )
+
+    def mle_update(self, gmm_accs, update_flags_str: str = "m", remove_low_count_gaussians: bool = False):
+        """kalpy's ``acoustic_model.mle_update(gmm_accs, update_flags_str="m", remove_low_count_gaussians=False)``: the mean
+        update of ``adapt.map_update``, in place.  Only that form exists here.  Returns (auxiliary-function improvement,
+        count): Σ_i Σ_k inv_var·[(μ' − μ)·mean_acc − ½·occ·(μ'² − μ²)] and Σ occ."""
+        from . import adapt
+
+        if update_flags_str != "m" or remove_low_count_gaussians:
+            raise NotImplementedError("mle_update: only update_flags_str='m' with remove_low_count_gaussians=False (means only)")
+        stats = getattr(gmm_accs, "stats", gmm_accs)
+        raw = adapt.raw_from_soa(self)
+        new, _updated, _kept = adapt.map_update(raw, stats)
+        iv = self.inv_vars.astype(np.float64)
+        mu0 = self.means_invvars.astype(np.float64) / iv
+        mi1 = np.concatenate(new.means_invvars)
+        mu1 = mi1.astype(np.float64) / iv
+        impr = float(np.sum(iv * ((mu1 - mu0) * stats.mean_acc - 0.5 * stats.occ[:, None] * (mu1 * mu1 - mu0 * mu0))))
+        self.means_invvars = mi1
+        self.gconsts = np.concatenate(new.gconsts)
+        self.weights = np.concatenate(new.weights)
+        return impr, float(stats.occ.sum())
 
     def boost_silence(self, factor: float, pdf_ids: Iterable[int]) -> None:
         """Scale the weights of the given pdfs by ``factor`` without renormalising ⇒ gconst += ln(factor).
