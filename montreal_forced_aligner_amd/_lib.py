@@ -83,6 +83,18 @@ class AlignOpts(C.Structure):
     ]
 
 
+def options(struct, defaults: dict, given: dict, what: str, alias: dict = {}):
+    """``struct`` filled from ``defaults`` with ``given`` laid over them: a name that is no option is refused (KeyError),
+    the integer fields are made integers."""
+    d = dict(defaults)
+    for k, v in given.items():
+        k = alias.get(k, k)
+        if k not in d:
+            raise KeyError(f"unknown {what} option {k!r}")
+        d[k] = v
+    return struct(**{k: int(d[k]) if t is C.c_int32 else d[k] for k, t in struct._fields_})
+
+
 def build_native(force: bool = False, verbose: bool = False) -> Path:
     """Compile the HIP sources for gfx950 into libmfa_hip.so next to this file (hipcc cross-compiles without a GPU)."""
     src_dir = _PKG / "csrc"
@@ -203,3 +215,8 @@ def check(ctx, rc: int, what: str) -> None:
     if rc != 0:
         msg = lib().mfa_last_error(ctx)
         raise MfaHipError(f"{what}: {msg.decode() if msg else 'error'}")
+
+
+def _ptr(t):
+    """A torch tensor (or None) as the pointer argument of a library call."""
+    return None if t is None else C.c_void_p(t.data_ptr())

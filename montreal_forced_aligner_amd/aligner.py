@@ -13,11 +13,13 @@ A failed utterance yields ``None`` and is counted, never raised (MFA/alignment/m
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
+import torch
 
 from . import ctm as _ctm
 from . import _lib
@@ -28,6 +30,7 @@ from . import adapt as _adapt
 from . import kaldi_io
 from .engine import AlignmentEngine, GmmStats, fmllr_statistics, gmm_statistics, redo_capacity
 from .model import DiagGmmModel, TransitionModel
+from .staging import StagingRing
 
 
 @dataclass
@@ -180,10 +183,8 @@ class CorpusAligner:
         self._mfcc_cache_on = False
         self._intervals = None          # intervals_native.IntervalExtractor, built on first use
         self._worker = None             # one worker thread: the next batch's graphs compile under the current batch
-        self._graph_pools = None        # staging the batches' graphs compile into (three sets, this pipeline's alone)
-        self._graph_turn = 0
-        self._out_pools = None          # pinned staging for the batches' outputs on their way back (two sets)
-        self._out_turn = 0
+        self._graph_pools = StagingRing(self.engine.device, 3)   # staging the batches' graphs compile into (this pipeline's alone)
+        self._out_pools = StagingRing(self.engine.device, 3)     # pinned staging for the batches' outputs on their way back
 
     def _boosted(self, am: DiagGmmModel) -> DiagGmmModel:
         import copy
@@ -286,8 +287,6 @@ class CorpusAligner:
     def speaker_cmvn(self, utts: Sequence[CorpusUtterance]) -> Tuple[Dict[str, int], "object"]:
         """calc_cmvn: float64 [n_spk, 2, dim+1] on the device, and the speaker → row map.  With pitch the statistics are
         those of the MFCC columns alone, zero-padded in the pitch columns (the feature kernel then leaves those untouched)."""
-        import torch
-
         spk_ids = {s: k for k, s in enumerate(dict.fromkeys(u.speaker for u in utts))}
         # per-batch statistics come from the device kernel (float64, fixed order); batches are added up on the host, in
         # batch order — a few hundred bytes per speaker, and no framework arithmetic on the path
@@ -330,13 +329,7 @@ class CorpusAligner:
         draws from — batch b + 1 compiles while batch b is launched from its pool and batch b - 1 is still collected from
         its own (the capacity redo packs its graphs again).  The engine's ``next_staging``, which every other packing call
         takes from, cannot move this turn.  Waits until the copies last started from the pool are done (main thread)."""
-        if self._graph_pools is None:
-            from .engine import StagingPool
-            self._graph_pools = [StagingPool(self.engine.device) for _ in range(3)]
-        self._graph_turn = (self._graph_turn + 1) % len(self._graph_pools)
-        pool = self._graph_pools[self._graph_turn]
-        pool.wait()
-        return pool
+        return self._graph_pools.next()
 
     def _submit_compile(self, utts, idx_all):
         from concurrent.futures import ThreadPoolExecutor
@@ -372,16 +365,13 @@ class CorpusAligner:
         enqueued, not waited for."""
         if not prep["idx"]:
             return None
-        idx = prep["idx"]
-        mfcc, fo = self._mfcc(utts, idx)
-        rows = np.array([spk_ids[utts[i].speaker] for i in idx], dtype=np.int32)
-        feats = self._final_features(mfcc, fo, rows, cmvn, d_lda, fmllr)
+        feats, fo, rows = self._batch_features(utts, prep["idx"], spk_ids, cmvn, d_lda, fmllr)
         res = self._decode(prep["graphs"], feats, fo, self.opt.max_tokens, self.opt.bp_tokens_per_frame)
         # outputs start their way back right behind the kernels (asynchronous copies into pinned staging memory, one event):
-        # _collect waits for THIS batch only, while the next batch's kernels are already queued behind it
-        import torch
-        pool = self._out_pools[self._out_turn]
-        self._out_turn = (self._out_turn + 1) % len(self._out_pools)
+        # _collect waits for THIS batch only, while the next batch's kernels are already queued behind it.  (No copy to
+        # the device starts from these pools, so the ring's wait has nothing to wait for: a set is free once _collect has
+        # copied its views out, which happens right after the next batch's launch.)
+        pool = self._out_pools.next()
         host = {}
         with torch.cuda.device(self.engine.device):
             for k in ("status", "ali", "words", "n_words", "like"):
@@ -398,9 +388,7 @@ class CorpusAligner:
         graphs with epsilon input arcs or very wide states."""
         eng, o = self.engine, self.opt
         gidx, gfsts = prep["gidx"], prep["gfsts"]
-        mfcc, fo = self._mfcc(utts, gidx)
-        rows = np.array([spk_ids[utts[i].speaker] for i in gidx], dtype=np.int32)
-        feats = self._final_features(mfcc, fo, rows, cmvn, d_lda, fmllr)
+        feats, fo, rows = self._batch_features(utts, gidx, spk_ids, cmvn, d_lda, fmllr)
         gg = eng.pack_graphs_general(gfsts, self.tm)
         rg = eng.align_general(gg, feats, fo, beam=o.beam, retry_beam=o.retry_beam, acoustic_scale=o.acoustic_scale,
                                bp_tokens_per_frame=max(o.bp_tokens_per_frame, 512))
@@ -412,30 +400,39 @@ class CorpusAligner:
             else:
                 self.failure_reasons[utts[i].utt_id] = _lib.status_reason(out.status[k])
         if want_feats:
-            import torch
-            ali_dev = rg["ali"].clone()
-            for k in range(len(gidx)):
-                if out.status[k] not in (0, 1):
-                    ali_dev[int(fo[k]): int(fo[k + 1])] = 0
-            kept.append((gidx, feats, ali_dev, fo, rows))
+            kept.append((gidx, feats, self._zero_failed(rg["ali"], fo, out.status), fo, rows))
+
+    def _batch_features(self, utts, idx, spk_ids, cmvn, d_lda, fmllr):
+        """(final features, frame offsets, speaker rows) of the utterances ``idx`` of a batch."""
+        mfcc, fo = self._mfcc(utts, idx)
+        rows = np.array([spk_ids[utts[i].speaker] for i in idx], dtype=np.int32)
+        return self._final_features(mfcc, fo, rows, cmvn, d_lda, fmllr), fo, rows
+
+    @staticmethod
+    def _zero_failed(ali_dev, fo, status):
+        """A batch's alignments on the device with the frames of failed utterances zeroed (in a copy): they must not vote in
+        the statistics made from them."""
+        bad = np.flatnonzero((status != 0) & (status != 1)).tolist()
+        if bad:
+            ali_dev = ali_dev.clone()
+            for k in bad:
+                ali_dev[int(fo[k]): int(fo[k + 1])] = 0
+        return ali_dev
 
     def _collect(self, utts, prep, launched, results, kept, want_feats):
         """Results of a launched batch back on the host (this is where the host waits for the device)."""
-        import torch
-
         eng, o = self.engine, self.opt
         idx, fsts = prep["idx"], prep["fsts"]
         res, feats, fo, rows = launched["res"], launched["feats"], launched["fo"], launched["rows"]
         launched["event"].synchronize()
-        h = launched["host"]          # (pinned staging views: copied out, the buffers are reused two batches later)
-        status, ali, words = h["status"].copy(), h["ali"].copy(), h["words"].copy()
-        n_words, like = h["n_words"].copy(), h["like"].copy()
+        # (pinned staging views: copied out here, before the ring of output pools comes round to their set again)
+        host = {k: v.copy() for k, v in launched["host"].items()}
+        status, ali = host["status"], host["ali"]
         # capacity overflows (status 3 tokens / 4 back-pointers) are decoded again: the merged alignments replace the
         # device's copy when the fMLLR pass will read it
-        host = dict(status=status, ali=ali, words=words, n_words=n_words, like=like)
         if redo_capacity(eng, fsts, self.tm, feats, fo, host, self._decode, o.beam, o.retry_beam, o.acoustic_scale) and want_feats:
             res["ali"] = torch.from_numpy(ali).to(eng.device)
-        out = _BatchOut(idx, fo, ali, words, n_words, like, status)
+        out = _BatchOut(idx, fo, ali, host["words"], host["n_words"], host["like"], status)
         ok = (status == 0) | (status == 1)
         for k in np.flatnonzero(ok).tolist():
             results[idx[k]] = (out, k)
@@ -445,13 +442,7 @@ class CorpusAligner:
             else:
                 self.failure_reasons[utts[idx[k]].utt_id] = _lib.status_reason(status[k])
         if want_feats:
-            bad = np.flatnonzero(~ok).tolist()
-            if bad:   # frames of utterances that failed must not vote in the fMLLR statistics
-                ali_dev = res["ali"].clone()
-                for k in bad:
-                    ali_dev[int(fo[k]): int(fo[k + 1])] = 0
-                res["ali"] = ali_dev
-            kept.append((idx, feats, res["ali"], fo, rows))
+            kept.append((idx, feats, self._zero_failed(res["ali"], fo, status), fo, rows))
 
     def _pass(self, utts, spk_ids, cmvn, fmllr, want_feats=False, first_compile=None):
         """One alignment pass over all batches.  Returns per utterance ``(batch output, index)`` (None where alignment
@@ -462,12 +453,7 @@ class CorpusAligner:
         Software pipeline over batches: the graphs of batch b + 1 compile on a worker thread while the main thread packs,
         launches and collects batch b.  ``first_compile``: the future of batch 0's compilation when the caller started it
         earlier (``_align`` does, under the CMVN pass)."""
-        import torch
-
         eng = self.engine
-        if self._out_pools is None:
-            from .engine import StagingPool
-            self._out_pools = [StagingPool(eng.device), StagingPool(eng.device), StagingPool(eng.device)]
         d_lda = None if self.lda is None else torch.from_numpy(self.lda).to(eng.device)
         results: List[Optional[tuple]] = [None] * len(utts)
         kept: List[tuple] = []
@@ -500,14 +486,18 @@ class CorpusAligner:
         in MFA) per-speaker fMLLR is estimated from it and a second pass is run with the transforms on ``am``.
         ``previous_transforms`` [n_spk, D, D+1] (speaker rows in first-appearance order): transforms the features already
         carry in the first pass; the new estimate is composed onto them (CalcFmllrFunction's previous_transform_archive)."""
-        import torch
+        with self._run():
+            return self._align(list(utterances), speaker_adapted, make_ctm, previous_transforms)[0]
 
-        utts = list(utterances)
+    @contextmanager
+    def _run(self):
+        """The state of one run of ``align`` / ``adapt``: empty failure lists on entry; the cache of raw MFCCs (and of the
+        batches) lives inside it and is dropped on the way out, however the run ends."""
         self.failed, self.failure_reasons, self.fallback_first_pass, self.ctm_failed = [], {}, [], []
         self.fmllr_rejected = []
         self._mfcc_cache, self._mfcc_cache_bytes, self._mfcc_cache_on = {}, 0, True
         try:
-            return self._align(utts, speaker_adapted, make_ctm, previous_transforms)[0]
+            yield
         finally:
             self._mfcc_cache, self._mfcc_cache_bytes, self._mfcc_cache_on = {}, 0, False
             self._batches_key = None
@@ -515,8 +505,6 @@ class CorpusAligner:
     def _align(self, utts, speaker_adapted, make_ctm, previous_transforms, keep_last=False):
         """Returns (results, kept): ``kept`` — with ``keep_last`` — is what the LAST pass left on the device per batch,
         (utterance indices, final features, alignments with failed utterances zeroed, frame offsets, speaker rows)."""
-        import torch
-
         batches = self._batches(utts)
         first_compile = self._submit_compile(utts, batches[0]) if batches else None     # graphs compile under the CMVN pass
         spk_ids, cmvn = self.speaker_cmvn(utts)
@@ -578,15 +566,8 @@ class CorpusAligner:
         both = bool(speaker_adapted) and self.ali_am is not None
         if both and self.raw_ali_am is None:
             raise ValueError("adapt with an alignment model needs raw_ali_am= as well")
-        utts = list(utterances)
-        self.failed, self.failure_reasons, self.fallback_first_pass, self.ctm_failed = [], {}, [], []
-        self.fmllr_rejected = []
-        self._mfcc_cache, self._mfcc_cache_bytes, self._mfcc_cache_on = {}, 0, True
-        try:
-            results, kept = self._align(utts, speaker_adapted, make_ctm, None, keep_last=True)
-        finally:
-            self._mfcc_cache, self._mfcc_cache_bytes, self._mfcc_cache_on = {}, 0, False
-            self._batches_key = None
+        with self._run():
+            results, kept = self._align(list(utterances), speaker_adapted, make_ctm, None, keep_last=True)
         n_tids = self.tm.num_transition_ids + 1
 
         def accumulate(raw):

@@ -21,6 +21,7 @@ import numpy as np
 
 from . import ctm as _ctm
 from . import graph as _graph
+from .ragged import offsets
 
 NEW_FRAME_SHIFT = 0.001          # FineTuneFunction.new_frame_shift_seconds
 FEATURE_PADDING_FACTOR = 3       # FineTuneFunction.feature_padding_factor
@@ -113,7 +114,6 @@ def fine_tune_boundaries(aligner, compiler: _graph.TrainingGraphCompiler, pcm: S
     ``attempts``: per decode, ``scale``, ``windows`` (global indices), ``frame_off``, ``x`` (their rows), ``pdf_lists_host``,
     ``pdf_first_frame`` (host, per window), ``ll`` / ``ll_off`` (device scores) and the ``status`` / ``ali`` that came back."""
     import torch
-    from .engine import offsets
 
     eng = aligner._engine()
     tm = aligner.transition_model

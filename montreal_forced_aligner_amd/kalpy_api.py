@@ -30,6 +30,7 @@ from . import kaldi_io
 from . import model as _model
 from .graph import LexiconCompiler as _LexiconCompiler
 from .graph import Pronunciation as KalpyPronunciation  # noqa: F401  (name used by the reference)
+from .ragged import offsets
 
 logger = logging.getLogger("kalpy.align")      # the reference's per-job logger name (MFA/utils.py:1435-1476)
 
@@ -156,7 +157,6 @@ class MfccComputer:
                      compress: bool = True, batch_size: int = 256) -> None:
         """``feats.*.ark`` (+ ``.scp``) for (key, segment) pairs, MFCCs computed in device batches (MfccFunction._run)."""
         import torch
-        from .engine import offsets
 
         ark = Path(file_name)
         scp = ark.with_suffix(".scp") if write_scp else None
@@ -284,7 +284,6 @@ class CmvnComputer:
     def compute_cmvn_from_features(self, feats: Sequence[np.ndarray]) -> np.ndarray:
         """Kaldi layout float64 [2, dim+1]: sums + count / sums of squares."""
         import torch
-        from .engine import offsets
 
         eng = get_engine()
         frame_off = offsets([f.shape[0] for f in feats])
@@ -357,7 +356,6 @@ class FeatureArchive:
 
     def __iter__(self) -> Iterator[Tuple[str, np.ndarray]]:
         import torch
-        from .engine import offsets
 
         eng = get_engine()
         batch: List[Tuple[str, np.ndarray]] = []
@@ -600,7 +598,7 @@ class GmmAligner:
     def align_utterances(self, fsts: Sequence[kaldi_io.Fst], feats: Sequence[np.ndarray], utterance_ids=None) -> List[Optional[Alignment]]:
         """Batched form of ``align_utterance``: one device launch per stage for the whole list."""
         import torch
-        from .engine import offsets, redo_capacity
+        from .engine import redo_capacity
 
         eng = self._engine()
         general = [k for k, f in enumerate(fsts) if eng.needs_general_decoder(f)]

@@ -1,0 +1,207 @@
+"""Statistics from alignments: per-speaker fMLLR statistics and GMM sufficient statistics (device call and host twin), with
+the host-built tables they share.  Functions of an engine, not methods: they use its ``lib``, ``ctx``, ``device``, ``_dev``
+and the loaded ``gmm``.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import _ptr, check
+from .model import DiagGmmModel, TransitionModel
+from .ragged import _speaker_groups
+
+
+def model_arrays(gmm: DiagGmmModel) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """A model as the library takes it: contiguous (pdf_offsets int32, gconsts, means_invvars, inv_vars float32).  The caller
+    keeps them alive across the call it passes their addresses to."""
+    return (np.ascontiguousarray(gmm.pdf_offsets, dtype=np.int32), np.ascontiguousarray(gmm.gconsts, dtype=np.float32),
+            np.ascontiguousarray(gmm.means_invvars, dtype=np.float32), np.ascontiguousarray(gmm.inv_vars, dtype=np.float32))
+
+
+def check_delta_fmllr(fmllr, dim: int, utt2spk) -> None:
+    """Host check of the per-speaker transforms of the Δ+ΔΔ path before a launch: float32, contiguous, on the device,
+    [n_spk, 3·dim, 3·dim+1], a row for every speaker ``utt2spk`` names (row 0 without ``utt2spk``).  The kernel indexes the
+    array by these numbers alone."""
+    D = 3 * int(dim)
+    if not isinstance(fmllr, torch.Tensor) or fmllr.dtype != torch.float32:
+        raise _lib.MfaHipError(f"features: fMLLR transforms must be a float32 tensor (got {getattr(fmllr, 'dtype', type(fmllr))})")
+    if fmllr.dim() != 3 or tuple(fmllr.shape[1:]) != (D, D + 1):
+        raise _lib.MfaHipError(f"features: fMLLR transforms of shape {tuple(fmllr.shape)} do not fit Δ+ΔΔ features of dimension {D}: "
+                               f"expected [n_spk, {D}, {D + 1}]")
+    if not fmllr.is_contiguous():
+        raise _lib.MfaHipError("features: fMLLR transforms must be contiguous")
+    u2s = None if utt2spk is None else np.asarray(utt2spk)
+    if u2s is not None and u2s.size and int(u2s.min()) < 0:
+        raise _lib.MfaHipError("features: negative speaker row in utt2spk")
+    need = 1 if u2s is None or u2s.size == 0 else int(u2s.max()) + 1
+    if fmllr.shape[0] < need:
+        raise _lib.MfaHipError(f"features: {fmllr.shape[0]} fMLLR transforms for speaker rows up to {need - 1}")
+    if not fmllr.is_cuda:
+        raise _lib.MfaHipError("features: fMLLR transforms must be on the device")
+
+
+def tid_tables(tm: TransitionModel, weights: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The two host-built tables of the statistics calls: pdf of every transition-id (int32; index 0 unused) and its frame
+    weight (float32; 1 for every id but 0 unless ``weights`` [transition-ids + 1] is given)."""
+    id2pdf = np.maximum(tm.id2pdf, 0).astype(np.int32)
+    w = np.ones(id2pdf.shape[0], dtype=np.float32) if weights is None else np.ascontiguousarray(weights, dtype=np.float32).copy()
+    if w.shape != id2pdf.shape:
+        raise ValueError(f"weights: {w.shape[0]} entries for {id2pdf.shape[0] - 1} transition-ids (+ 1)")
+    w[0] = 0.0
+    return id2pdf, w
+
+
+def silence_weights(tm: TransitionModel, silence_phones: Sequence[int], silence_weight: float) -> np.ndarray:
+    """Frame weight of every transition-id for fMLLR statistics: ``silence_weight`` for the silence phones' ids, 1 elsewhere."""
+    sil = np.isin(tm.id2phone, np.asarray(list(silence_phones), dtype=np.int64))
+    return np.where(sil, np.float32(silence_weight), np.float32(1.0))
+
+
+def fmllr_statistics(engine, feats: torch.Tensor, frame_off: np.ndarray, ali: torch.Tensor,
+                     tm: TransitionModel, utt2spk: np.ndarray, silence_phones: Sequence[int], silence_weight: float = 0.0,
+                     stats_model: Optional[DiagGmmModel] = None):
+    """Per-speaker fMLLR statistics from first-pass alignments (mfa_fmllr_acc_batch).
+
+    ``ali``: int32 [ΣT] transition-ids (0 where an utterance failed: those frames get weight 0).  Returns
+    (speaker ids, beta [S], K [S,D,D+1], G [S,D,D+1,D+1]) as float64 numpy arrays.
+
+    ``stats_model``: the two-model form the reference runs for models that ship ``final.alimdl``
+    (FmllrComputer(ali_model_path, model_path, …), MFA/corpus/features.py:503-511): posteriors from the model loaded in the
+    engine (the alignment model), statistics with ``stats_model``'s means and variances (``final.mdl``)."""
+    dev = engine.device
+    if stats_model is not None:
+        po, _gc, mi, iv = model_arrays(stats_model)
+        check(engine.ctx, engine.lib.mfa_fmllr_stats_model(engine.ctx, stats_model.dim, stats_model.num_pdfs, po.ctypes.data,
+                                                           mi.ctypes.data, iv.ctypes.data), "mfa_fmllr_stats_model")
+    else:
+        check(engine.ctx, engine.lib.mfa_fmllr_stats_model(engine.ctx, 0, 0, None, None, None), "mfa_fmllr_stats_model")
+    id2pdf, w = tid_tables(tm, silence_weights(tm, silence_phones, silence_weight))
+    id2pdf, w_of_tid = torch.from_numpy(id2pdf).to(dev), torch.from_numpy(w).to(dev)
+    ali = ali.to(torch.int32).contiguous() if ali.dtype != torch.int32 else ali.contiguous()
+    pdf = torch.empty(ali.shape[0], dtype=torch.int32, device=dev)       # scratch: the lookup runs inside the library
+    weight = torch.empty(ali.shape[0], dtype=torch.float32, device=dev)
+    spk_ids, _inv, order, spk_off = _speaker_groups(utt2spk)
+    n_spk = len(spk_ids)
+    D = feats.shape[1]
+    beta = torch.zeros(n_spk, dtype=torch.float64, device=dev)
+    K = torch.zeros((n_spk, D, D + 1), dtype=torch.float64, device=dev)
+    G = torch.zeros((n_spk, D, D + 1, D + 1), dtype=torch.float64, device=dev)
+    d_fo, d_so, d_su = engine._dev(frame_off), engine._dev(spk_off), engine._dev(order)
+    check(engine.ctx, engine.lib.mfa_fmllr_acc_ali_batch(engine.ctx, _ptr(feats), _ptr(d_fo), len(frame_off) - 1,
+                                                          int(frame_off[-1]), _ptr(ali), _ptr(id2pdf), _ptr(w_of_tid),
+                                                          int(id2pdf.shape[0]), _ptr(pdf), _ptr(weight), _ptr(d_so), _ptr(d_su),
+                                                          n_spk, _ptr(beta), _ptr(K), _ptr(G)), "mfa_fmllr_acc_ali_batch")
+    return spk_ids, beta.cpu().numpy(), K.cpu().numpy(), G.cpu().numpy()
+
+
+@dataclass
+class GmmStats:
+    """GMM sufficient statistics, indexed by model Gaussian (``DiagGmmModel.pdf_offsets``): float64 ``occ`` [G], ``mean_acc`` /
+    ``var_acc`` [G, dim], ``tot_like`` = Σ w·loglike, ``tot_count`` = Σ w, int64 ``tid_count`` [transition-ids + 1].  Additive:
+    ``a += b`` (AccumAmDiagGmm::Add); what a sum over batches, or later over ranks, needs."""
+
+    occ: np.ndarray
+    mean_acc: np.ndarray
+    var_acc: np.ndarray
+    tot_like: float
+    tot_count: float
+    tid_count: np.ndarray
+
+    @classmethod
+    def zeros(cls, num_gauss: int, dim: int, n_tids: int) -> "GmmStats":
+        return cls(np.zeros(num_gauss), np.zeros((num_gauss, dim)), np.zeros((num_gauss, dim)), 0.0, 0.0, np.zeros(n_tids, dtype=np.int64))
+
+    def copy(self) -> "GmmStats":
+        return GmmStats(self.occ.copy(), self.mean_acc.copy(), self.var_acc.copy(), self.tot_like, self.tot_count, self.tid_count.copy())
+
+    def __iadd__(self, other: "GmmStats") -> "GmmStats":
+        if self.mean_acc.shape != other.mean_acc.shape or self.tid_count.shape != other.tid_count.shape:
+            raise ValueError("GmmStats of different models cannot be added")
+        self.occ += other.occ
+        self.mean_acc += other.mean_acc
+        self.var_acc += other.var_acc
+        self.tot_like += other.tot_like
+        self.tot_count += other.tot_count
+        self.tid_count += other.tid_count
+        return self
+
+    @property
+    def loglike_per_frame(self) -> float:
+        """What the reference logs after accumulation: total log-likelihood over total weight."""
+        return self.tot_like / self.tot_count if self.tot_count else 0.0
+
+
+def gmm_statistics(engine, feats: torch.Tensor, ali: torch.Tensor, tm: TransitionModel,
+                   weights: Optional[np.ndarray] = None, into: Optional[GmmStats] = None) -> GmmStats:
+    """GMM statistics of one batch from its alignments (mfa_gmm_acc_batch; the contract is in include/mfa_hip.h), with the
+    model loaded in the engine.
+
+    ``feats`` float32 [ΣT, dim] and ``ali`` int32 [ΣT] transition-ids on the device (0 where an utterance failed: those frames
+    take no part); ``weights``: per transition-id frame weights (default 1).  ``into``: statistics to add to — the device sums
+    start from its values, so a corpus accumulated batch by batch is one chain of additions — and the object returned."""
+    if engine.gmm is None:
+        raise _lib.MfaHipError("gmm_statistics: no acoustic model loaded (AlignmentEngine.load_gmm)")
+    dev = engine.device
+    gmm = engine.gmm
+    G, D = gmm.num_gauss, gmm.dim
+    id2pdf, w = tid_tables(tm, weights)
+    n_tids = int(id2pdf.shape[0])
+    st = into if into is not None else GmmStats.zeros(G, D, n_tids)
+    if st.mean_acc.shape != (G, D) or st.tid_count.shape != (n_tids,):
+        raise ValueError("gmm_statistics: `into` does not fit the loaded model")
+    total = int(ali.shape[0])
+    if feats.shape[0] != total or (total and feats.shape[1] != D):
+        raise _lib.MfaHipError(f"gmm_statistics: features {tuple(feats.shape)} for {total} frames of a model of dim {D}")
+    if feats.dtype != torch.float32 or not feats.is_cuda or not ali.is_cuda:
+        raise _lib.MfaHipError("gmm_statistics: features must be float32 and, like the alignments, on the device")
+    feats = feats.contiguous()
+    ali = ali.to(torch.int32).contiguous()
+    occ = torch.from_numpy(st.occ).to(dev)
+    mean = torch.from_numpy(np.ascontiguousarray(st.mean_acc)).to(dev)
+    var = torch.from_numpy(np.ascontiguousarray(st.var_acc)).to(dev)
+    tot = torch.tensor([st.tot_like, st.tot_count], dtype=torch.float64, device=dev)
+    cnt = torch.from_numpy(st.tid_count).to(dev)
+    d_pdf, d_w = torch.from_numpy(id2pdf).to(dev), torch.from_numpy(w).to(dev)
+    check(engine.ctx, engine.lib.mfa_gmm_acc_batch(engine.ctx, _ptr(feats), total, _ptr(ali), _ptr(d_pdf), _ptr(d_w), n_tids,
+                                                    _ptr(occ), _ptr(mean), _ptr(var), _ptr(tot), _ptr(cnt)), "mfa_gmm_acc_batch")
+    st.occ, st.mean_acc, st.var_acc, st.tid_count = occ.cpu().numpy(), mean.cpu().numpy(), var.cpu().numpy(), cnt.cpu().numpy()
+    t = tot.cpu().numpy()
+    st.tot_like, st.tot_count = float(t[0]), float(t[1])
+    return st
+
+
+def gmm_statistics_host(gmm: DiagGmmModel, feats: np.ndarray, ali: np.ndarray, tm: TransitionModel,
+                        weights: Optional[np.ndarray] = None, into: Optional[GmmStats] = None, want_post: bool = False):
+    """The same call on the host twin (mfa_debug_gmm_acc_host: no device, frames in ascending index): the specification the
+    device is held to.  numpy arrays in; with ``want_post`` also returns every frame's posteriors [ΣT, largest pdf]."""
+    lib = _lib.lib()
+    id2pdf, w = tid_tables(tm, weights)
+    n_tids = int(id2pdf.shape[0])
+    G, D = gmm.num_gauss, gmm.dim
+    st = into if into is not None else GmmStats.zeros(G, D, n_tids)
+    feats = np.ascontiguousarray(feats, dtype=np.float32)
+    ali = np.ascontiguousarray(ali, dtype=np.int32)
+    ok = (ali > 0) & (ali < n_tids)
+    safe = np.where(ok, ali, 0)
+    pdf = np.where(ok, id2pdf[safe], -1).astype(np.int32)
+    fw = np.where(ok, w[safe], np.float32(0)).astype(np.float32)
+    po, gc, mi, iv = model_arrays(gmm)
+    occ, mean, var = (np.ascontiguousarray(a, dtype=np.float64) for a in (st.occ, st.mean_acc, st.var_acc))
+    tot = np.array([st.tot_like, st.tot_count], dtype=np.float64)
+    cnt = np.ascontiguousarray(st.tid_count, dtype=np.int64)
+    stride = int(np.diff(po).max())
+    post = np.zeros((ali.shape[0], stride), dtype=np.float32) if want_post else None
+    rc = lib.mfa_debug_gmm_acc_host(D, gmm.num_pdfs, po.ctypes.data, gc.ctypes.data, mi.ctypes.data, iv.ctypes.data,
+                                    feats.ctypes.data, int(ali.shape[0]), pdf.ctypes.data, fw.ctypes.data, ali.ctypes.data, n_tids,
+                                    occ.ctypes.data, mean.ctypes.data, var.ctypes.data, tot.ctypes.data, cnt.ctypes.data,
+                                    None if post is None else post.ctypes.data, stride)
+    if rc != 0:
+        raise _lib.MfaHipError(f"mfa_debug_gmm_acc_host: {'a pdf of more than 128 Gaussians' if rc == -2 else 'bad arguments'}")
+    st.occ, st.mean_acc, st.var_acc, st.tid_count = occ, mean, var, cnt
+    st.tot_like, st.tot_count = float(tot[0]), float(tot[1])
+    return (st, post) if want_post else st

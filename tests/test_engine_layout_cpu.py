@@ -1,0 +1,114 @@
+"""The host layer by role: every name ``engine`` used to define is still importable from it and is the object its new module
+defines; ``ragged`` stays free of torch; the staging ring hands its pools out in a fixed cycle, waiting for the one it
+returns; and the helpers that replaced repeated expressions compute those expressions."""
+import copy
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+from montreal_forced_aligner_amd import _lib, engine, frontend, packing, pipeline, ragged, staging, stats
+
+REEXPORTS = {
+    engine: ("AlignmentEngine", "redo_capacity", "DEFAULT_MFCC"),
+    pipeline: ("Pipeline",),
+    packing: ("PackedGraphs",),
+    staging: ("StagingPool", "StagingRing"),
+    stats: ("GmmStats", "check_delta_fmllr", "fmllr_statistics", "gmm_statistics", "gmm_statistics_host", "tid_tables"),
+    ragged: ("offsets", "_speaker_groups"),
+    frontend: ("DEFAULT_PITCH", "_PITCH_ALIAS"),
+    _lib: ("_ptr",),
+}
+
+
+@pytest.mark.parametrize("name,home", [(n, m) for m, names in REEXPORTS.items() for n in names])
+def test_engine_reexports_the_object_of_the_new_module(name, home):
+    obj = getattr(home, name)
+    assert getattr(engine, name) is obj
+    if hasattr(obj, "__module__"):            # (classes and functions: defined there, not passed through)
+        assert obj.__module__ == home.__name__
+
+
+def test_ragged_imports_without_torch():
+    code = "import sys; import montreal_forced_aligner_amd.ragged; sys.exit(1 if 'torch' in sys.modules else 0)"
+    root = Path(__file__).resolve().parent.parent
+    assert subprocess.run([sys.executable, "-c", code], cwd=root).returncode == 0
+
+
+@pytest.mark.parametrize("n", [1, 2, 3])
+def test_ring_hands_out_every_pool_once_per_round_and_waits_for_it_alone(n, monkeypatch):
+    waited = []
+
+    class Recording(staging.StagingPool):
+        def wait(self):
+            waited.append(self)
+            super().wait()
+
+    monkeypatch.setattr(staging, "StagingPool", Recording)
+    ring = staging.StagingRing(torch.device("cpu"), n, pinned=False)
+    assert len(ring.pools) == n and all(type(p) is Recording and not p.pinned for p in ring.pools)
+    handed = []
+    for _ in range(3 * n):
+        before = len(waited)
+        pool = ring.next()
+        assert waited[before:] == [pool]              # waited for before it is returned, and for no other
+        handed.append(pool)
+    first = handed[:n]
+    assert sorted(map(id, first)) == sorted(map(id, ring.pools))      # every pool once per n calls
+    assert all(p is q for p, q in zip(handed, first * 3))             # and the same cycle again
+
+
+def test_max_len_is_the_expression_it_replaces():
+    for off in ([0], [0, 0], [0, 5], [0, 3, 3, 10], np.array([0, 4, 4, 6, 13], dtype=np.int32), np.array([0], dtype=np.int64)):
+        n = len(off) - 1
+        want = int(np.diff(off).max()) if n else 0
+        got = ragged.max_len(off)
+        assert type(got) is int and got == want, (off, got, want)
+
+
+def _parent_fmllr_tables(tm, silence_phones, silence_weight):
+    """fmllr_statistics' own tables before it called tid_tables."""
+    id2pdf = np.maximum(tm.id2pdf, 0).astype(np.int32)
+    sil = np.zeros(tm.id2phone.shape[0], dtype=np.float32)
+    sil[np.isin(tm.id2phone, np.asarray(list(silence_phones), dtype=np.int64))] = 1.0
+    w_host = np.where(sil > 0, np.float32(silence_weight), np.float32(1.0)).astype(np.float32)
+    w_host[0] = 0.0
+    return id2pdf, w_host
+
+
+@pytest.mark.parametrize("silence_weight", [0.0, 0.25])
+def test_tid_tables_with_silence_weights_is_the_fmllr_pair_it_replaces(fx, silence_weight):
+    tm = fx.mono_tm
+    phones = np.unique(tm.id2phone[1:])
+    absent = int(phones.max()) + 7
+    for silence in ([int(phones[0])], [int(phones[0]), int(phones[-1])], [], [absent], [int(phones[1]), absent]):
+        got = stats.tid_tables(tm, weights=stats.silence_weights(tm, silence, silence_weight))
+        want = _parent_fmllr_tables(tm, silence, silence_weight)
+        for g, w in zip(got, want):
+            assert g.dtype == w.dtype and g.flags.c_contiguous and np.array_equal(g, w), (silence, silence_weight)
+        assert got[1][0] == 0.0
+        if silence_weight != 1.0 and silence and silence != [absent]:
+            assert (got[1][1:] == np.float32(silence_weight)).any()
+
+
+def test_model_arrays_are_the_views_they_replace(fx):
+    am = fx.mono_am
+    f64 = copy.copy(am)
+    f64.pdf_offsets = am.pdf_offsets.astype(np.int64)
+    f64.gconsts, f64.means_invvars, f64.inv_vars = (np.asarray(a, dtype=np.float64) for a in (am.gconsts, am.means_invvars, am.inv_vars))
+    strided = copy.copy(am)
+    strided.pdf_offsets = np.repeat(am.pdf_offsets, 2)[::2]
+    strided.gconsts = np.repeat(am.gconsts, 3)[::3]
+    strided.means_invvars, strided.inv_vars = np.asfortranarray(am.means_invvars), np.repeat(am.inv_vars, 2, axis=1)[:, ::2]
+    assert not strided.gconsts.flags.c_contiguous and not strided.inv_vars.flags.c_contiguous
+    for gmm in (am, f64, strided):
+        want = (np.ascontiguousarray(gmm.pdf_offsets, dtype=np.int32), np.ascontiguousarray(gmm.gconsts, dtype=np.float32),
+                np.ascontiguousarray(gmm.means_invvars, dtype=np.float32), np.ascontiguousarray(gmm.inv_vars, dtype=np.float32))
+        got = stats.model_arrays(gmm)
+        assert len(got) == 4
+        for g, w, orig in zip(got, want, (am.pdf_offsets, am.gconsts, am.means_invvars, am.inv_vars)):
+            assert g.dtype == w.dtype and g.shape == w.shape and g.flags.c_contiguous and np.array_equal(g, w)
+            assert np.array_equal(g, orig)

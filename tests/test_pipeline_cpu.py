@@ -12,7 +12,7 @@ import torch
 from montreal_forced_aligner_amd import _lib
 from montreal_forced_aligner_amd import kaldi_io as K
 from montreal_forced_aligner_amd.aligner import AlignOptions, CorpusAligner, CorpusUtterance
-from montreal_forced_aligner_amd.engine import AlignmentEngine, StagingPool, _speaker_groups, offsets, redo_capacity
+from montreal_forced_aligner_amd.engine import AlignmentEngine, StagingPool, StagingRing, _speaker_groups, offsets, redo_capacity
 from tests import helpers
 
 T = 50                      # frames per utterance (the stub's 160 samples per frame)
@@ -51,8 +51,7 @@ class StubEngine:
     next_staging = AlignmentEngine.next_staging
 
     def __init__(self, script):
-        self._staging = [StagingPool(self.device, pinned=False) for _ in range(3)]
-        self._staging_turn = 0
+        self._staging = StagingRing(self.device, 3, pinned=False)
         self.script = script          # utterance → {stage: status} (0 where not given)
         self.expected = {}            # _key(graph) → utterance
         self.packed = []              # (pack call, [utterance per graph])
