@@ -47,7 +47,7 @@ MFA_API int mfa_memcpy_d2h(mfa_ctx *ctx, void *h_dst, const void *d_src, size_t 
 MFA_API int mfa_timer_begin(mfa_ctx *ctx);
 MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
 /* Per-kernel accumulated HIP-event times since the last reset.  which: 0 mfcc, 1 cmvn, 2 feats, 3 gmm, 4 viterbi,
- * 5 resample, 6 pitch, 7 feature codec, 8-11 GMM statistics (lookup, ordering, sums, reduction).
+ * 5 resample, 6 pitch, 7 feature codec, 8-11 GMM statistics (lookup, ordering, sums, reduction), 12 equal alignment.
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -558,6 +558,49 @@ MFA_API int mfa_debug_gmm_acc_host(int32_t dim, int32_t num_pdfs, const int32_t 
                                    int64_t total_frames, const int32_t *h_pdf, const float *h_weight, const int32_t *h_tid,
                                    int32_t n_tids, double *h_occ, double *h_mean, double *h_var, double *h_tot,
                                    int64_t *h_tid_count, float *h_post, int32_t post_stride);
+
+/* ---- Equal alignment: replaces kalpy gmm_align_equal (MFA/acoustic_modeling/monophone.py:108; Kaldi align-equal =
+ *      EqualAlign, restated here from its description — Kaldi's source is not among this project's references, and its
+ *      random numbers are not reproducible here: parity unpinned by construction).  The first alignment of
+ *      flat-start training: a random path through the utterance's graph with its T_u frames spread evenly over the path's
+ *      self-loops.  No features, no model.
+ *
+ * Graphs: mfa_graph_batch as for mfa_align_batch; read are d_state_off, d_arc_base, d_start, d_arc_off, d_final,
+ * d_arc_next and d_arc_ilabel, in the arc order they are stored in.  d_frame_off [n_utt + 1]; d_utt_key [n_utt]: one
+ * uint32 per utterance, which the host derives from the utterance's position in the CORPUS, not in the batch.
+ * Outputs: d_ali [total_frames] transition-ids at frame_off, d_status [n_utt]: 0 ok, 2 failed.
+ *
+ * Random numbers are counter-based.  With fmix(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35;
+ * h ^= h >> 16 (uint32 arithmetic), draw d of an utterance is
+ *   u = fmix(fmix(fmix(seed ^ 0x9E3779B9) + key * 0x85EBCA6B + 0x165667B1) ^ (d * 0xC2B2AE35 + 0x27D4EB2F))
+ * and picks among m candidates by multiply-high, (u * m) >> 32 in 64 bits.  No state is shared between utterances: an
+ * utterance's result is the same bits alone, in any batch, at any position, on the device and in the host twin (both run
+ * csrc/align_equal_math.hpp; everything is integer arithmetic).
+ * One attempt: from the start state, while the state is not final (d_final = +inf), choose uniformly among its arcs that
+ *   are not self-loops (next != state), in arc order; append the arc; count it if its ilabel != 0.  Stop at the FIRST final
+ *   state.  The attempt fails as soon as the counted ilabels exceed T_u (they only grow: Kaldi's check made early, and it
+ *   bounds the walk), when the steps exceed 2 (T_u + S_u) (epsilon cycles), or at a non-final state without a non-self-loop
+ *   arc.  Up to 10 attempts, the draws numbered on across attempts; after that status 2 and the utterance's frames set to 0.
+ *   A malformed graph (a start state, an arc range or a next state outside it) is status 2 as well.
+ * Spreading: a path state is loopable when it has a self-loop arc with ilabel != 0; the first such arc in arc order is
+ *   the loop's transition-id.  With extra = T_u - ilabels and L loopable path states (a state the path visits twice counts
+ *   twice): L == 0 and extra > 0 is status 2; otherwise every loopable state gets extra / L loops, the first extra % L of
+ *   them in path order one more.  Output per path state, in path order: its loops, then its outgoing path arc's ilabel if
+ *   != 0; the last state's loops go last.  T_u == 0: ok iff the walk reaches a final state with 0 ilabels; nothing is written.
+ * total_frames = frame_off[n_utt] with frame_off[0] = 0 and total_states = state_off[n_utt] - state_off[0] are host copies
+ * (the call never synchronises): they size the path workspace, 2 (2 (total_frames + total_states) + n_utt) int32 laid over
+ * the context's shared workspace; an utterance whose device offsets do not fit them fails (status 2) without a write.
+ * Asynchronous on the ctx stream.  Refused with a message, the context usable afterwards: NULL graph arrays (or offsets,
+ * keys, outputs) with n_utt > 0; 2^31 frames or more.  n_utt == 0 is no error. */
+MFA_API int mfa_align_equal_batch(mfa_ctx *ctx, const mfa_graph_batch *graphs, const int64_t *d_frame_off, int64_t total_frames,
+                                  int64_t total_states, const uint32_t *d_utt_key, uint32_t seed, int32_t *d_ali,
+                                  int32_t *d_status);
+/* Host twin, no context and no device: the same contract on host arrays (the graph batch's arrays by name).  Returns 0,
+ * -1 for bad arguments (a NULL array that would be read or written), -2 for 2^31 frames or more. */
+MFA_API int mfa_debug_align_equal_host(int32_t n_utt, const int64_t *h_state_off, const int64_t *h_arc_base,
+                                       const int32_t *h_start, const int32_t *h_arc_off, const float *h_final,
+                                       const int32_t *h_arc_next, const int32_t *h_arc_ilabel, const int64_t *h_frame_off,
+                                       const uint32_t *h_utt_key, uint32_t seed, int32_t *h_ali, int32_t *h_status);
 
 #ifdef __cplusplus
 }

@@ -38,7 +38,7 @@ DEFAULT_MFCC = dict(sample_frequency=16000.0, frame_length_ms=25.0, frame_shift_
 
 # The kernel-timing slots by name, in the order of the MFA_K_* enum of csrc/ctx.hpp: the two lists go together.
 KERNEL_SLOTS = ("mfcc", "cmvn", "feats", "gmm", "viterbi", "resample", "pitch", "compress",
-                "acc_lookup", "acc_sort", "acc_sums", "acc_reduce")
+                "acc_lookup", "acc_sort", "acc_sums", "acc_reduce", "equal_align")
 
 
 def _out_ptrs(out: Dict[str, Optional[torch.Tensor]]):

@@ -514,6 +514,43 @@ def read_tree(data: bytes) -> ContextDependency:
     return ContextDependency(n, p, em)
 
 
+def _write_event_map(f: BinaryIO, em: Optional[EventMap]) -> None:
+    if em is None:
+        _w_token(f, "NULL")
+    elif em.kind == "CE":
+        _w_token(f, "CE")
+        _w_int32(f, em.answer)
+    elif em.kind == "TE":
+        _w_token(f, "TE")
+        _w_int32(f, em.key)
+        f.write(b"\xfc" + struct.pack("<I", len(em.table)))     # uint32: size marker -4
+        _w_token(f, "(")
+        for t in em.table:
+            _write_event_map(f, t)
+        _w_token(f, ")")
+    elif em.kind == "SE":
+        _w_token(f, "SE")
+        _w_int32(f, em.key)
+        write_int_vector(f, sorted(em.yes_set))
+        _w_token(f, "{")
+        _write_event_map(f, em.yes)
+        _write_event_map(f, em.no)
+        _w_token(f, "}")
+    else:
+        raise KaldiFormatError(f"bad EventMap kind {em.kind!r}")
+
+
+def write_tree(f: BinaryIO, tree: ContextDependency) -> None:
+    """Write a ``tree`` file in Kaldi binary form: the inverse of ``read_tree`` for CE / TE / SE / NULL nodes."""
+    f.write(b"\0B")
+    _w_token(f, "ContextDependency")
+    _w_int32(f, tree.context_width)
+    _w_int32(f, tree.central_position)
+    _w_token(f, "ToPdf")
+    _write_event_map(f, tree.to_pdf)
+    _w_token(f, "EndContextDependency")
+
+
 # --------------------------------------------------------------------------- OpenFst VectorFst<StdArc> (A.13)
 FST_MAGIC = 0x7EB2FDD6
 ARC_DTYPE = np.dtype([("ilabel", "<i4"), ("olabel", "<i4"), ("weight", "<f4"), ("nextstate", "<i4")])

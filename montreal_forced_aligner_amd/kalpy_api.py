@@ -783,6 +783,60 @@ class GmmStatsAccumulator:
         flush()
 
 
+# ------------------------------------------------------------------------------------------------ flat-start training
+def read_topology(path_or_bytes) -> kaldi_io.HmmTopology:
+    """``kalpy.gmm.utils.read_topology``: a binary ``topo`` file."""
+    data = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray)) else Path(path_or_bytes).read_bytes()
+    r = kaldi_io.BinaryReader(bytes(data))
+    r.expect_binary_header()
+    return kaldi_io.read_topology(r)
+
+
+def read_tree(path_or_bytes) -> kaldi_io.ContextDependency:
+    data = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray)) else Path(path_or_bytes).read_bytes()
+    return kaldi_io.read_tree(bytes(data))
+
+
+def gmm_init_mono(topo, feats: Sequence[np.ndarray], shared_phones, model_path, tree_path) -> None:
+    """``_kalpy.gmm.gmm_init_mono(topo, feats, shared_phones, model_path, tree_path)`` (MFA/acoustic_modeling/monophone.py:324):
+    the flat-start model — one Gaussian per (phone set, pdf-class) at the global mean and variance of ``feats``, a list of
+    feature matrices — and its tree, written to the two paths (``mle.init_mono``).  ``shared_phones``: lists of phone ids."""
+    from . import adapt, mle
+
+    feats = [np.asarray(x, dtype=np.float64) for x in feats if len(x)]
+    if not feats:
+        raise ValueError("gmm_init_mono: no features")
+    raw_tm, raw_am, tree = mle.init_mono(topo, feats[0].shape[1], shared_phones)
+    n = sum(x.shape[0] for x in feats)
+    mean = sum(x.sum(axis=0) for x in feats) / n
+    var = np.maximum(sum((x * x).sum(axis=0) for x in feats) / n - mean * mean, mle.MIN_VARIANCE)
+    iv = (1.0 / var).astype(np.float32)[None]
+    mi = mean.astype(np.float32)[None] * iv
+    gc = adapt.gconsts(np.ones(1, np.float32), mi, iv)
+    for p in range(raw_am.num_pdfs):
+        raw_am.gconsts[p], raw_am.means_invvars[p], raw_am.inv_vars[p] = gc.copy(), mi.copy(), iv.copy()
+    with open(model_path, "wb") as f:
+        kaldi_io.write_model(f, raw_tm, raw_am)
+    with open(tree_path, "wb") as f:
+        kaldi_io.write_tree(f, tree)
+
+
+def gmm_align_equal(fst: kaldi_io.Fst, feats: np.ndarray, seed: int = 0, key: int = 0):
+    """``_kalpy.gmm.gmm_align_equal(decode_fst, feats)`` (MFA/acoustic_modeling/monophone.py:108): (alignment, words) of a
+    random path with the frames spread evenly over its self-loops, on the device (mfa_align_equal_batch; the batch entry's
+    result for utterance key ``key``), or (None, None) when the utterance cannot be aligned.  ``words``: the output labels
+    along a path of the graph that spells the alignment."""
+    from . import equal_align as _equal
+
+    eng = get_engine()
+    n_frames = int(np.asarray(feats).shape[0])
+    ali, status = _equal.equal_align(eng, _equal.pack_bare(eng, [fst]), np.array([0, n_frames], dtype=np.int64), [key], seed)
+    if int(status.cpu()[0]) != 0:
+        return None, None
+    ali = ali.cpu().numpy()
+    return ali.tolist(), _equal.path_words(fst, ali)
+
+
 def write_gmm_model(path, transition_model, acoustic_model) -> None:
     """``kalpy.gmm.utils.write_gmm_model(path, transition_model, acoustic_model)`` for the objects ``read_gmm_model``
     returns (the mixture weights are the model's own when it was read from a file)."""

@@ -177,14 +177,29 @@ class DiagGmmModel:
             np.concatenate(am.weights).astype(np.float32),
         )
 
-    def mle_update(self, gmm_accs, update_flags_str: str = "m", remove_low_count_gaussians: bool = False):
-        """kalpy's ``acoustic_model.mle_update(gmm_accs, update_flags_str="m", remove_low_count_gaussians=False)``: the mean
-        update of ``adapt.map_update``, in place.  Only that form exists here.  Returns (auxiliary-function improvement,
-        count): Σ_i Σ_k inv_var·[(μ' − μ)·mean_acc − ½·occ·(μ'² − μ²)] and Σ occ."""
+    def mle_update(self, gmm_accs, update_flags_str: Optional[str] = None, remove_low_count_gaussians: Optional[bool] = None,
+                   mixup: Optional[int] = None, power: float = 0.25, min_gaussian_occupancy: Optional[float] = None,
+                   perturb_factor: float = 0.01, rng=None):
+        """kalpy's ``acoustic_model.mle_update``, in place, in the two forms the reference calls.
+
+        ``mle_update(gmm_accs, update_flags_str="m", remove_low_count_gaussians=False)`` (MFA/alignment/adapting.py; also what
+        a call with ``gmm_accs`` alone gives): the mean update of ``adapt.map_update``; no other form without ``mixup``.  Returns (auxiliary-function
+        improvement, count): Σ_i Σ_k inv_var·[(μ' − μ)·mean_acc − ½·occ·(μ'² − μ²)] and Σ occ.
+
+        ``mle_update(gmm_accs, mixup=, power=[, min_gaussian_occupancy=])`` (MFA/acoustic_modeling/monophone.py:280-285,
+        base.py:788-790): ``mle.mle_update`` — means, variances and weights, low-count Gaussians removed unless told otherwise
+        — then ``mle.mix_up`` to ``mixup`` Gaussians.  Returns (auxiliary-function improvement of the update, before mixing
+        up, over the pdfs that kept all their Gaussians; Σ occ)."""
         from . import adapt
 
-        if update_flags_str != "m" or remove_low_count_gaussians:
-            raise NotImplementedError("mle_update: only update_flags_str='m' with remove_low_count_gaussians=False (means only)")
+        if mixup is not None:
+            return self._mle_update_training(gmm_accs, update_flags_str or "mvw",
+                                             True if remove_low_count_gaussians is None else bool(remove_low_count_gaussians),
+                                             mixup, power, 10.0 if min_gaussian_occupancy is None else float(min_gaussian_occupancy),
+                                             perturb_factor, rng)
+        if update_flags_str not in (None, "m") or remove_low_count_gaussians or min_gaussian_occupancy is not None:
+            raise NotImplementedError("mle_update without mixup=: only update_flags_str='m' with remove_low_count_gaussians=False "
+                                      "(means only); the training form is mle_update(gmm_accs, mixup=, power=)")
         stats = getattr(gmm_accs, "stats", gmm_accs)
         raw = adapt.raw_from_soa(self)
         new, _updated, _kept = adapt.map_update(raw, stats)
@@ -196,6 +211,31 @@ class DiagGmmModel:
         self.means_invvars = mi1
         self.gconsts = np.concatenate(new.gconsts)
         self.weights = np.concatenate(new.weights)
+        return impr, float(stats.occ.sum())
+
+    def _mle_update_training(self, gmm_accs, flags, remove, mixup, power, min_occ, perturb_factor, rng):
+        from . import adapt, mle
+
+        stats = getattr(gmm_accs, "stats", gmm_accs)
+        raw = adapt.raw_from_soa(self)
+        new, _updated, _removed, _floored = mle.mle_update(raw, stats, flags=flags, min_gaussian_occupancy=min_occ,
+                                                           remove_low_count_gaussians=remove)
+
+        def aux(am, p, a, b):          # Σ_g occ·gconst + means_invvars·mean_acc − ½·inv_vars·var_acc over one pdf
+            return float(np.sum(stats.occ[a:b] * am.gconsts[p].astype(np.float64))
+                         + np.sum(am.means_invvars[p].astype(np.float64) * stats.mean_acc[a:b])
+                         - 0.5 * np.sum(am.inv_vars[p].astype(np.float64) * stats.var_acc[a:b]))
+
+        impr = 0.0
+        for p in range(raw.num_pdfs):
+            a, b = int(self.pdf_offsets[p]), int(self.pdf_offsets[p + 1])
+            if new.weights[p].shape[0] == b - a:
+                impr += aux(new, p, a, b) - aux(raw, p, a, b)
+        if mixup is not None and int(mixup) > sum(w.shape[0] for w in new.weights):
+            new, _targets = mle.mix_up(new, mle.pdf_occupancies(raw, stats), int(mixup), power, perturb_factor=perturb_factor, rng=rng)
+        soa = DiagGmmModel.from_raw(new)
+        self.gconsts, self.means_invvars, self.inv_vars = soa.gconsts, soa.means_invvars, soa.inv_vars
+        self.pdf_offsets, self.weights = soa.pdf_offsets, soa.weights
         return impr, float(stats.occ.sum())
 
     def boost_silence(self, factor: float, pdf_ids: Iterable[int]) -> None:
