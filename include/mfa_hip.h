@@ -47,7 +47,8 @@ MFA_API int mfa_memcpy_d2h(mfa_ctx *ctx, void *h_dst, const void *d_src, size_t 
 MFA_API int mfa_timer_begin(mfa_ctx *ctx);
 MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
 /* Per-kernel accumulated HIP-event times since the last reset.  which: 0 mfcc, 1 cmvn, 2 feats, 3 gmm, 4 viterbi,
- * 5 resample, 6 pitch, 7 feature codec, 8-11 GMM statistics (lookup, ordering, sums, reduction), 12 equal alignment.
+ * 5 resample, 6 pitch, 7 feature codec, 8-11 GMM statistics (lookup, ordering, sums, reduction), 12 equal alignment,
+ * 13-16 LDA statistics (lookup, second moment, ordering + class sums, reductions).
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -601,6 +602,64 @@ MFA_API int mfa_debug_align_equal_host(int32_t n_utt, const int64_t *h_state_off
                                        const int32_t *h_start, const int32_t *h_arc_off, const float *h_final,
                                        const int32_t *h_arc_next, const int32_t *h_arc_ilabel, const int64_t *h_frame_off,
                                        const uint32_t *h_utt_key, uint32_t seed, int32_t *h_ali, int32_t *h_status);
+
+/* ---- LDA statistics: replaces the accumulation of LdaAccStatsFunction / kalpy LdaStatsAccumulator.accumulate_stats
+ *      (MFA/acoustic_modeling/lda.py:54-119; Kaldi acc-lda = LdaEstimate::Accumulate with weight-silence-post and
+ *      RandPrune, restated here from the algorithm's description — Kaldi's source is not among this project's references,
+ *      and its random numbers are not reproducible here: parity unpinned).  Class-labelled scatter sums in the
+ *      SPLICED feature space, S = (2 * splice_ctx + 1) * dim; the spliced matrix is never materialised.
+ *
+ * Inputs.  d_mfcc [total_frames][dim], d_frame_off [n_utt + 1], d_utt2spk [n_utt], d_cmvn float64 [n_spk][2][dim + 1] (may
+ * be NULL: no CMVN; the caller vouches for n_spk) and splice_ctx are what mfa_feats_batch mode 1 takes; total_frames =
+ * frame_off[n_utt] is the host's copy (the call never synchronises).  d_ali [total_frames] transition-ids, d_tid2class /
+ * d_tid_weight [n_tids], n_classes = C.  rand_prune (0: off), d_utt_key [n_utt] (uint32, from the utterance's position in
+ * the CORPUS; may be NULL when rand_prune == 0), seed.
+ * Accumulators, float64, added to and never overwritten: d_zero [C], d_first [C][S], d_second [S][S] (the full square, both
+ * triangles written and bit-equal; the caller's value is read from the lower triangle), optional int64 d_tid_count [n_tids].
+ *
+ * Arithmetic contract.
+ *   spliced vector   x_t of frame t of utterance u is what mfa_feats_batch mode 1 multiplies by the LDA matrix: for o in
+ *                    -ctx..ctx the CMVN-applied row of frame clamp(t + o, first, last of u); a column is
+ *                    x - (float)(sum / count) in float32 (pitch columns are zero-padded in the statistics and stay
+ *                    untouched); offsets ascend, columns within an offset.
+ *   taking part      a frame takes no part when its transition-id is outside the table or 0, its weight is 0, or its class
+ *                    is outside [0, C).  Otherwise c = tid2class[ali[t]], w = tid_weight[ali[t]].
+ *   random prune     with rand_prune = theta > 0 and |w| < theta: r = |w| / theta (float32), u = draw (t - first frame of
+ *                    the utterance) of the utterance's stream — the fmix construction of the equal alignment above, keyed
+ *                    by seed and d_utt_key[utt]; if (float)(u >> 8) * 2^-24 < r then w = copysign(theta, w), otherwise the
+ *                    frame takes no part.  Kaldi's RandPrune on a generator whose draws are a function of (seed, corpus
+ *                    position, frame): the kept set does not depend on how batches are cut.
+ *   sums (double)    zero[c] += w;  first[c][i] = fma(w, x_i, first[c][i]);  second[i][j] += (w * x_i) * x_j, where the
+ *                    product (double)w * (double)x_i is exact and the second product and the addition are rounded once (an
+ *                    fma on the f64 matrix pipe: the device) or twice (multiply, add: the host twin);
+ *   counts           tid_count[ali[t]] += 1 for the frames that take part.
+ * Order on the device.  second: the batch's frames in slabs of mfa_lda_acc_slab_frames() consecutive frames; a slab is
+ * summed from zero (4 frames per step of the matrix instruction, in frame order), the slabs are added in order onto the
+ * caller's value.  zero / first: the frames of a class in ascending frame index (stable sort by class), cut into chunks of
+ * mfa_lda_acc_chunk_frames() entries; a chunk is summed from zero in frame order, the chunks are added in order onto the
+ * caller's value.  The result is a function of the input alone: two calls give the same bits.  No floating-point atomics.
+ * mfa_debug_lda_acc_host is the same contract on host arrays, frames in ascending index: spliced vectors, weights and
+ * prune decisions have the device's bits by construction (both run csrc/lda_acc_math.hpp); only the order of the double
+ * sums and the rounding of a second-moment term may differ.
+ * Asynchronous on the ctx stream.  Limits (refused with a message, the context stays usable): S > mfa_lda_acc_max_dim() =
+ * 128; dim <= 0 or splice_ctx < 0; n_classes <= 0; a NULL array that would be read or written (CMVN without utt2spk,
+ * pruning without keys among them); 2^31 frames or more.  total_frames == 0 is no error and writes nothing. */
+MFA_API int32_t mfa_lda_acc_slab_frames(void);
+MFA_API int32_t mfa_lda_acc_chunk_frames(void);
+MFA_API int32_t mfa_lda_acc_max_dim(void);
+MFA_API int mfa_lda_acc_batch(mfa_ctx *ctx, const float *d_mfcc, const int64_t *d_frame_off, int32_t n_utt, int64_t total_frames,
+                              int32_t dim, const int32_t *d_utt2spk, const double *d_cmvn, int32_t splice_ctx,
+                              const int32_t *d_ali, const int32_t *d_tid2class, const float *d_tid_weight, int32_t n_tids,
+                              int32_t n_classes, float rand_prune, const uint32_t *d_utt_key, uint32_t seed, double *d_zero,
+                              double *d_first, double *d_second, int64_t *d_tid_count);
+/* Host twin, no context and no device: the same contract on host arrays (total_frames is h_frame_off[n_utt]).  Returns 0,
+ * -1 for bad arguments (a NULL array that would be read or written, offsets that do not ascend), -2 for S > 128, -3 for
+ * 2^31 frames or more. */
+MFA_API int mfa_debug_lda_acc_host(const float *h_mfcc, const int64_t *h_frame_off, int32_t n_utt, int32_t dim,
+                                   const int32_t *h_utt2spk, const double *h_cmvn, int32_t splice_ctx, const int32_t *h_ali,
+                                   const int32_t *h_tid2class, const float *h_tid_weight, int32_t n_tids, int32_t n_classes,
+                                   float rand_prune, const uint32_t *h_utt_key, uint32_t seed, double *h_zero, double *h_first,
+                                   double *h_second, int64_t *h_tid_count);
 
 #ifdef __cplusplus
 }

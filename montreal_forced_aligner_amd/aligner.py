@@ -30,6 +30,7 @@ from . import adapt as _adapt
 from . import kaldi_io
 from .engine import AlignmentEngine, GmmStats, fmllr_statistics, gmm_statistics, redo_capacity
 from .model import DiagGmmModel, TransitionModel
+from .stats import LdaStats, lda_statistics, silence_weights
 from .staging import StagingRing
 
 
@@ -143,6 +144,7 @@ class CorpusAligner:
         self.adapt_ali_stats: Optional[GmmStats] = None
         self.adapt_loglike: Dict[str, Optional[float]] = {}   # average log-likelihood per frame the reference logs, per model
         self.adapt_counts: Dict[str, tuple] = {}         # Gaussians (updated, kept) per model
+        self.lda_stats: Optional[LdaStats] = None        # the statistics of the last ``estimate_lda``
         self.lda = None if lda is None else np.asarray(lda, dtype=np.float32)
         self.opt = options or AlignOptions()
         self.engine = engine or AlignmentEngine(device)
@@ -593,6 +595,44 @@ class CorpusAligner:
         self.adapted = (new_tm, new_am, new_ali)
         self._reload(new_tm, new_am, new_ali)
         return results
+
+    # ------------------------------------------------------------------ LDA estimation
+    def _lda_accumulate(self, utts, kept, spk_ids, cmvn, splice_context: int, rand_prune: float, seed: int) -> LdaStats:
+        """LDA statistics of the alignments ``kept`` (of ``_align(..., keep_last=True)``, inside the same ``_run``) on the
+        base features as ``_mfcc`` / ``speaker_cmvn`` make them — with ``corpus_compression`` the twice-compressed
+        CMVN-applied rows without CMVN, exactly what ``_final_features`` hands the feature kernel.  Classes are pdfs, silence
+        weighs 0 (weight-silence-post 0.0), utterance keys are corpus positions."""
+        eng = self.engine
+        weights = silence_weights(self.tm, self.silence_phones, 0.0)
+        st = None
+        for idx, _feats, ali, fo, rows in kept:
+            mfcc, fo2 = self._mfcc(utts, idx)
+            assert np.array_equal(fo, fo2)
+            use_cmvn = cmvn
+            if self.opt.corpus_compression:
+                mfcc = eng.compress_round_trip(mfcc, fo, cols=(0, mfcc.shape[1] - self.n_pitch), cmvn=cmvn, utt2spk=rows)
+                use_cmvn = None
+            st = lda_statistics(eng, mfcc, fo, rows, use_cmvn, ali, self.tm, splice_context=splice_context, weights=weights,
+                                rand_prune=rand_prune, utt_keys=np.asarray(idx, dtype=np.uint32), seed=seed, into=st)
+        if st is None:
+            raise ValueError("estimate_lda: no utterances")
+        return st
+
+    def estimate_lda(self, utterances: Sequence[CorpusUtterance], dim: int = 40, splice_context: int = 3, rand_prune: float = 0.0,
+                     seed: int = 0):
+        """The LDA stage's estimate (MFA/acoustic_modeling/lda.py:54-119, 352-373): align with this aligner's model on its
+        own features, accumulate LDA statistics of those alignments in the spliced space of the base features on the device
+        (``lda_statistics``, batch by batch into one ``LdaStats``, kept as ``lda_stats``) and return
+        ``lda.estimate_lda(stats, dim)`` = (lda_mat [dim, S], full [S, S]).  ``rand_prune``: the reference prunes at 4.0
+        because its accumulation is slow; here every frame is affordable and the default is 0 (off)."""
+        from .lda import estimate_lda as _estimate
+
+        utts = list(utterances)
+        with self._run():
+            _results, kept = self._align(utts, False, False, None, keep_last=True)
+            spk_ids, cmvn = self.speaker_cmvn(utts)            # (from the cached MFCCs: the bits of the alignment pass)
+            self.lda_stats = self._lda_accumulate(utts, kept, spk_ids, cmvn, int(splice_context), float(rand_prune), int(seed))
+        return _estimate(self.lda_stats, dim=dim)
 
     def _reload(self, raw_tm, raw_am, raw_ali_am) -> None:
         """Make the adapted models the aligner's own: transition model (graphs, scaled probabilities), boosted copies, device."""

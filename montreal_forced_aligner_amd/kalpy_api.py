@@ -354,6 +354,23 @@ class FeatureArchive:
         else:
             yield from kaldi_io.read_ark(self.file_name.read_bytes(), "matrix")
 
+    def cmvn_rows(self, ids: Dict[str, int], dim: int) -> Optional[np.ndarray]:
+        """The CMVN statistics [len(ids), 2, dim + 1] of the speakers ``ids`` (name → row), or None without a CMVN table."""
+        if self._cmvn is None:
+            return None
+        st = np.zeros((len(ids), 2, dim + 1), dtype=np.float64)
+        st[:, 0, dim] = 1.0   # a speaker without statistics keeps its features (mean 0 over count 1)
+        for s, i in ids.items():
+            if s in self._cmvn:
+                st[i] = self._cmvn[s]
+        return st
+
+    def base_rows(self) -> Iterator[Tuple[str, np.ndarray, str]]:
+        """(utt_id, base feature matrix as stored, speaker name): for a consumer that applies CMVN (``cmvn_rows``) and
+        splices (``splice_frames``) on the device itself — ``LdaStatsAccumulator``."""
+        for key, m in self._base():
+            yield key, m, (self.utt2spk.get(key, key) if self.utt2spk else key)
+
     def __iter__(self) -> Iterator[Tuple[str, np.ndarray]]:
         import torch
 
@@ -365,14 +382,8 @@ class FeatureArchive:
             ids = {s: i for i, s in enumerate(dict.fromkeys(spk_names))}
             u2s = np.array([ids[s] for s in spk_names], dtype=np.int32)
             dim = batch[0][1].shape[1]
-            cm = None
-            if self._cmvn is not None:
-                st = np.zeros((len(ids), 2, dim + 1), dtype=np.float64)
-                st[:, 0, dim] = 1.0   # a speaker without statistics keeps its features (mean 0 over count 1)
-                for s, i in ids.items():
-                    if s in self._cmvn:
-                        st[i] = self._cmvn[s]
-                cm = torch.from_numpy(st).to(eng.device)
+            st = self.cmvn_rows(ids, dim)
+            cm = None if st is None else torch.from_numpy(st).to(eng.device)
             lda = None if self._lda is None else torch.from_numpy(self._lda.astype(np.float32)).to(eng.device)
             fm = None
             if self._trans is not None and (lda is not None or self.use_deltas):
@@ -776,6 +787,94 @@ class GmmStatsAccumulator:
                 logger.warning("utterance %s: %d alignment entries for %d frames, skipped", al.utterance_id, a.shape[0], x.shape[0])
                 continue
             rows.append(np.asarray(x)); alis.append(a); total += a.shape[0]
+            if callback:
+                callback(al.utterance_id)
+            if total >= self.batch_frames:
+                flush()
+        flush()
+
+
+# ------------------------------------------------------------------------------------------------ LDA
+class LdaEstimateOptions:
+    """``_kalpy.transform.LdaEstimateOptions``: ``dim`` 40, ``allow_large_dim`` False, ``remove_offset`` False."""
+
+    def __init__(self, dim: int = 40, allow_large_dim: bool = False, remove_offset: bool = False):
+        self.dim, self.allow_large_dim, self.remove_offset = int(dim), bool(allow_large_dim), bool(remove_offset)
+
+
+class LdaEstimate:
+    """``_kalpy.transform.LdaEstimate`` as MFA/acoustic_modeling/lda.py:340-351 uses it: ``Add(other)`` and
+    ``estimate(options) -> (lda_mat, full_mat)``.  ``stats`` is the ``stats.LdaStats`` behind it (None until frames arrive)."""
+
+    def __init__(self, stats=None):
+        self.stats = stats
+
+    def Add(self, other: "LdaEstimate") -> None:
+        if other.stats is None:
+            return
+        if self.stats is None:
+            self.stats = other.stats.copy()
+        else:
+            self.stats += other.stats
+
+    def estimate(self, options: Optional[LdaEstimateOptions] = None):
+        from .lda import estimate_lda
+        if self.stats is None:
+            raise ValueError("LdaEstimate.estimate: no statistics were accumulated")
+        o = options or LdaEstimateOptions()
+        return estimate_lda(self.stats, dim=o.dim, allow_large_dim=o.allow_large_dim, remove_offset=o.remove_offset)
+
+
+class LdaStatsAccumulator:
+    """``kalpy.feat.lda.LdaStatsAccumulator(model_path, silence_phones, rand_prune=…)``: ``accumulate_stats(feature_archive,
+    alignment_archive, callback=None)`` then ``.lda`` (MFA/acoustic_modeling/lda.py:106-119).  The archive is the reference's
+    ``FeatureArchive(feats, deltas=False, splices=True, splice_frames=…)``: it is not iterated (spliced rows are never made);
+    the accumulator takes its base rows, CMVN table and splice width and the statistics kernel splices
+    (``stats.lda_statistics``).  Classes are the model's pdfs, ``silence_phones`` weigh 0.  ``rand_prune`` defaults to the
+    reference's 4.0; the draws are keyed by ``seed`` and the utterance's position in the alignment archive."""
+
+    def __init__(self, acoustic_model_path, silence_phones: Sequence[int] = (), rand_prune: float = 4.0, seed: int = 0,
+                 batch_frames: int = 500_000):
+        self.acoustic_model_path = acoustic_model_path
+        self.transition_model, self.acoustic_model = _read_model(acoustic_model_path)
+        self.silence_phones, self.rand_prune, self.seed = list(silence_phones), float(rand_prune), int(seed)
+        self.batch_frames = int(batch_frames)
+        self.lda = LdaEstimate()
+
+    def accumulate_stats(self, feature_archive, alignment_archive, callback=None) -> None:
+        import torch
+        from .stats import lda_statistics, silence_weights
+
+        eng = get_engine()
+        tm = self.transition_model
+        weights = silence_weights(tm, self.silence_phones, 0.0)
+        base = {key: (m, spk) for key, m, spk in feature_archive.base_rows()}
+        ctx = int(feature_archive.splice_frames)
+        rows, alis, spks, keys, total = [], [], [], [], 0
+
+        def flush():
+            nonlocal rows, alis, spks, keys, total
+            if rows:
+                ids = {s: i for i, s in enumerate(dict.fromkeys(spks))}
+                u2s = np.array([ids[s] for s in spks], dtype=np.int32)
+                st = feature_archive.cmvn_rows(ids, rows[0].shape[1])
+                self.lda.stats = lda_statistics(
+                    eng, torch.from_numpy(np.concatenate(rows).astype(np.float32)).to(eng.device), offsets([m.shape[0] for m in rows]),
+                    u2s if st is not None else None, None if st is None else torch.from_numpy(st).to(eng.device),
+                    torch.from_numpy(np.concatenate(alis).astype(np.int32)).to(eng.device), tm, splice_context=ctx, weights=weights,
+                    rand_prune=self.rand_prune, utt_keys=np.asarray(keys, dtype=np.uint32), seed=self.seed, into=self.lda.stats)
+            rows, alis, spks, keys, total = [], [], [], [], 0
+
+        for position, al in enumerate(alignment_archive):
+            got = base.get(al.utterance_id)
+            if got is None:
+                continue
+            x, spk = got
+            a = np.asarray(al.alignment, dtype=np.int32)
+            if a.shape[0] != x.shape[0]:
+                logger.warning("utterance %s: %d alignment entries for %d frames, skipped", al.utterance_id, a.shape[0], x.shape[0])
+                continue
+            rows.append(np.asarray(x)); alis.append(a); spks.append(spk); keys.append(position); total += a.shape[0]
             if callback:
                 callback(al.utterance_id)
             if total >= self.batch_frames:

@@ -205,3 +205,154 @@ def gmm_statistics_host(gmm: DiagGmmModel, feats: np.ndarray, ali: np.ndarray, t
     st.occ, st.mean_acc, st.var_acc, st.tid_count = occ, mean, var, cnt
     st.tot_like, st.tot_count = float(tot[0]), float(tot[1])
     return (st, post) if want_post else st
+
+
+@dataclass
+class LdaStats:
+    """LDA scatter statistics in the spliced space (mfa_lda_acc_batch; Kaldi LdaEstimate): float64 ``zero`` [C] = Σ w per
+    class, ``first`` [C, S] = Σ w·x, ``second`` [S, S] = Σ w·x·xᵀ (symmetric, both triangles held).  Additive: ``a += b``."""
+
+    zero: np.ndarray
+    first: np.ndarray
+    second: np.ndarray
+
+    @classmethod
+    def zeros(cls, num_classes: int, dim: int) -> "LdaStats":
+        return cls(np.zeros(num_classes), np.zeros((num_classes, dim)), np.zeros((dim, dim)))
+
+    def copy(self) -> "LdaStats":
+        return LdaStats(self.zero.copy(), self.first.copy(), self.second.copy())
+
+    def __iadd__(self, other: "LdaStats") -> "LdaStats":
+        if self.first.shape != other.first.shape:
+            raise ValueError("LdaStats of different shapes cannot be added")
+        self.zero += other.zero
+        self.first += other.first
+        self.second += other.second
+        return self
+
+    @property
+    def num_classes(self) -> int:
+        return int(self.first.shape[0])
+
+    @property
+    def dim(self) -> int:
+        return int(self.first.shape[1])
+
+
+def _lda_tables(tm, weights, num_classes):
+    """The class and weight of every transition-id: a ``TransitionModel`` (classes are its pdfs, ``tid_tables``) or a ready
+    pair (tid2class int32, tid_weight float32) with ``num_classes``."""
+    if hasattr(tm, "id2pdf"):
+        id2class, w = tid_tables(tm, weights)
+        C = int(num_classes) if num_classes is not None else int(getattr(tm, "num_pdfs", int(id2class.max()) + 1))
+    else:
+        id2class = np.ascontiguousarray(tm[0], dtype=np.int32)
+        w = np.ascontiguousarray(tm[1], dtype=np.float32)
+        if weights is not None:
+            raise ValueError("lda_statistics: `weights` goes with a TransitionModel; a (tid2class, tid_weight) pair carries its own")
+        if num_classes is None:
+            raise ValueError("lda_statistics: a (tid2class, tid_weight) pair needs num_classes")
+        C = int(num_classes)
+    if id2class.shape != w.shape or id2class.ndim != 1:
+        raise ValueError("lda_statistics: tid2class and tid_weight must be vectors of one length")
+    return id2class, w, C
+
+
+def _lda_prune_args(rand_prune, utt_keys, n_utt):
+    rand_prune = float(rand_prune)
+    if rand_prune < 0:
+        raise ValueError("lda_statistics: rand_prune must be >= 0")
+    if rand_prune > 0 and utt_keys is None:
+        raise ValueError("lda_statistics: rand_prune needs utt_keys (the utterances' corpus positions)")
+    keys = None if utt_keys is None else np.ascontiguousarray(utt_keys, dtype=np.uint32)
+    if keys is not None and keys.shape != (n_utt,):
+        raise ValueError(f"lda_statistics: {keys.shape} utterance keys for {n_utt} utterances")
+    return rand_prune, keys
+
+
+def lda_statistics(engine, mfcc: torch.Tensor, frame_off: np.ndarray, utt2spk, cmvn, ali: torch.Tensor, tm,
+                   splice_context: int = 3, weights: Optional[np.ndarray] = None, rand_prune: float = 0.0, utt_keys=None,
+                   seed: int = 0, into: Optional[LdaStats] = None, num_classes: Optional[int] = None,
+                   tid_count: Optional[np.ndarray] = None) -> LdaStats:
+    """LDA statistics of one batch from its alignments (mfa_lda_acc_batch; the contract is in include/mfa_hip.h).
+
+    ``mfcc`` float32 [ΣT, dim] base features and ``ali`` int32 [ΣT] transition-ids on the device; ``utt2spk`` / ``cmvn``
+    (float64 [n_spk, 2, dim+1] on the device, or None) as ``AlignmentEngine.final_features`` takes them.  Classes are the pdfs
+    of ``tm`` with per transition-id ``weights`` (``silence_weights(tm, silence_phones, 0.0)`` is the reference's
+    weight-silence-post 0.0); ``tm`` may also be a ready (tid2class, tid_weight) pair with ``num_classes``.  ``rand_prune``
+    with ``utt_keys`` (corpus positions) and ``seed``: Kaldi's RandPrune on counter-based draws.  ``into``: statistics to add
+    to, and the object returned.  ``tid_count``: optional int64 [transition-ids + 1] counts to add to (returned in place)."""
+    dev = engine.device
+    id2class, w, C = _lda_tables(tm, weights, num_classes)
+    n_tids = int(id2class.shape[0])
+    frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+    n_utt, total = len(frame_off) - 1, int(frame_off[-1])
+    if mfcc.dim() != 2 or mfcc.shape[0] != total or ali.shape[0] != total:
+        raise _lib.MfaHipError(f"lda_statistics: features {tuple(mfcc.shape)} and {ali.shape[0]} alignment frames for {total} frames")
+    if mfcc.dtype != torch.float32 or not mfcc.is_cuda or not ali.is_cuda:
+        raise _lib.MfaHipError("lda_statistics: features must be float32 and, like the alignments, on the device")
+    dim = int(mfcc.shape[1])
+    S = (2 * int(splice_context) + 1) * dim
+    st = into if into is not None else LdaStats.zeros(C, max(S, 0))
+    if st.first.shape != (C, S) or st.second.shape != (S, S):
+        raise ValueError("lda_statistics: `into` does not fit the classes and the spliced dimension")
+    rand_prune, keys = _lda_prune_args(rand_prune, utt_keys, n_utt)
+    mfcc = mfcc.contiguous()
+    ali = ali.to(torch.int32).contiguous()
+    d_u2s = None if utt2spk is None else engine._dev(np.ascontiguousarray(utt2spk, dtype=np.int32))
+    if cmvn is not None and (cmvn.dtype != torch.float64 or not cmvn.is_cuda):
+        raise _lib.MfaHipError("lda_statistics: CMVN statistics must be float64 on the device")
+    d_cmvn = None if cmvn is None else cmvn.contiguous()
+    zero = torch.from_numpy(np.ascontiguousarray(st.zero)).to(dev)
+    first = torch.from_numpy(np.ascontiguousarray(st.first)).to(dev)
+    second = torch.from_numpy(np.ascontiguousarray(st.second)).to(dev)
+    cnt = None if tid_count is None else torch.from_numpy(np.ascontiguousarray(tid_count, dtype=np.int64)).to(dev)
+    d_cls, d_w = torch.from_numpy(id2class).to(dev), torch.from_numpy(w).to(dev)
+    d_keys = None if keys is None else torch.from_numpy(keys.view(np.int32)).to(dev)
+    d_fo = engine._dev(frame_off)
+    check(engine.ctx, engine.lib.mfa_lda_acc_batch(engine.ctx, _ptr(mfcc), _ptr(d_fo), n_utt, total, dim, _ptr(d_u2s), _ptr(d_cmvn),
+                                                    int(splice_context), _ptr(ali), _ptr(d_cls), _ptr(d_w), n_tids, C, rand_prune,
+                                                    _ptr(d_keys), int(seed) & 0xFFFFFFFF, _ptr(zero), _ptr(first), _ptr(second),
+                                                    _ptr(cnt)), "mfa_lda_acc_batch")
+    st.zero, st.first, st.second = zero.cpu().numpy(), first.cpu().numpy(), second.cpu().numpy()
+    if cnt is not None:
+        tid_count[...] = cnt.cpu().numpy()
+    return st
+
+
+def lda_statistics_host(mfcc: np.ndarray, frame_off: np.ndarray, utt2spk, cmvn, ali: np.ndarray, tm, splice_context: int = 3,
+                        weights: Optional[np.ndarray] = None, rand_prune: float = 0.0, utt_keys=None, seed: int = 0,
+                        into: Optional[LdaStats] = None, num_classes: Optional[int] = None,
+                        tid_count: Optional[np.ndarray] = None) -> LdaStats:
+    """The same call on the host twin (mfa_debug_lda_acc_host: no device, frames in ascending index): the specification the
+    device is held to.  numpy arrays in."""
+    lib = _lib.lib()
+    id2class, w, C = _lda_tables(tm, weights, num_classes)
+    n_tids = int(id2class.shape[0])
+    frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+    n_utt, total = len(frame_off) - 1, int(frame_off[-1])
+    mfcc = np.ascontiguousarray(mfcc, dtype=np.float32)
+    ali = np.ascontiguousarray(ali, dtype=np.int32)
+    if mfcc.ndim != 2 or mfcc.shape[0] != total or ali.shape[0] != total:
+        raise _lib.MfaHipError(f"lda_statistics_host: features {mfcc.shape} and {ali.shape[0]} alignment frames for {total} frames")
+    dim = int(mfcc.shape[1])
+    S = (2 * int(splice_context) + 1) * dim
+    st = into if into is not None else LdaStats.zeros(C, max(S, 0))
+    if st.first.shape != (C, S) or st.second.shape != (S, S):
+        raise ValueError("lda_statistics_host: `into` does not fit the classes and the spliced dimension")
+    rand_prune, keys = _lda_prune_args(rand_prune, utt_keys, n_utt)
+    u2s = None if utt2spk is None else np.ascontiguousarray(utt2spk, dtype=np.int32)
+    cm = None if cmvn is None else np.ascontiguousarray(cmvn, dtype=np.float64)
+    zero, first, second = (np.ascontiguousarray(a, dtype=np.float64) for a in (st.zero, st.first, st.second))
+    cnt = None if tid_count is None else np.ascontiguousarray(tid_count, dtype=np.int64)
+    p = lambda a: None if a is None else a.ctypes.data
+    rc = lib.mfa_debug_lda_acc_host(p(mfcc), p(frame_off), n_utt, dim, p(u2s), p(cm), int(splice_context), p(ali), p(id2class), p(w),
+                                    n_tids, C, rand_prune, p(keys), int(seed) & 0xFFFFFFFF, p(zero), p(first), p(second), p(cnt))
+    if rc != 0:
+        why = {-2: "spliced dimension above 128", -3: "2^31 frames or more"}.get(rc, "bad arguments")
+        raise _lib.MfaHipError(f"mfa_debug_lda_acc_host: {why}")
+    st.zero, st.first, st.second = zero, first, second
+    if cnt is not None:
+        tid_count[...] = cnt
+    return st

@@ -9,6 +9,9 @@ labels — ``final.mdl`` and ``tree`` out.
                 ``mle.mle_update`` → ``mle.mix_up`` to the current target; the target grows by ``gaussian_increment`` while
                 i <= ``final_gaussian_iteration``
 
+``LdaTrainer`` (below) is the LDA stage on a fixed tree: the previous model's alignments → LDA statistics and estimate → one
+Gaussian per pdf on the splice + LDA features → the same loop, shared through ``GmmTrainerBase``.
+
 The device is driven through a backend of three calls — ``equal_align``, ``align``, ``accumulate`` — so that the same loop
 runs on the host twins in tests.  ``DeviceBackend`` is ``CorpusAligner``'s machinery: features, CMVN and graphs as ``align``
 makes them, ``_align(..., keep_last=True)`` for features and alignments that stay on the device, ``gmm_statistics(into=)``.
@@ -54,6 +57,7 @@ class DeviceBackend:
         self.mfcc_options, self.silence_phones = dict(mfcc_options or {}), list(silence_phones)
         self.device, self.engine = device, engine
         self.al = None
+        self.lda: Optional[np.ndarray] = None     # LdaDeviceBackend sets it: the aligner's features are then splice + LDA
         self.kept: List[tuple] = []          # per batch (utterance indices, features, alignments, frame offsets, speaker rows)
         self.dim = 3 * int(self.mfcc_options.get("num_coefficients", 13))
 
@@ -61,8 +65,8 @@ class DeviceBackend:
         from .aligner import CorpusAligner
 
         if self.al is None:
-            self.al = CorpusAligner(TransitionModel(raw_tm), DiagGmmModel.from_raw(raw_am), tree, self.lexicon, options=self.opt,
-                                    device=self.device, engine=self.engine, mfcc_options=self.mfcc_options,
+            self.al = CorpusAligner(TransitionModel(raw_tm), DiagGmmModel.from_raw(raw_am), tree, self.lexicon, lda=self.lda,
+                                    options=self.opt, device=self.device, engine=self.engine, mfcc_options=self.mfcc_options,
                                     silence_phones=self.silence_phones, raw_tm=raw_tm, raw_am=raw_am)
             self.engine = self.al.engine
         else:
@@ -121,7 +125,65 @@ class DeviceBackend:
         return out
 
 
-class MonophoneTrainer:
+class GmmTrainerBase:
+    """What the training stages share: the Gaussian schedule, one iteration's update with its ``history`` entry, the loop
+    after iteration 0, and the files.  A stage sets ``backend``, ``raw_tm`` / ``raw_am`` / ``tree``, ``opt``, ``power``,
+    ``rng``, ``num_iterations``, ``max_gaussians``, ``initial_gaussians``, ``final_gaussian_iteration``,
+    ``realignment_iterations`` and ``current_gaussians``, and runs iteration 0 itself."""
+
+    history: List[Dict]
+    iteration = 0
+
+    @property
+    def gaussian_increment(self) -> int:
+        """BaseTrainer.gaussian_increment (MFA/acoustic_modeling/base.py:451-453); 0 when no iteration may add Gaussians."""
+        if self.final_gaussian_iteration <= 0:
+            return 0
+        return int((self.max_gaussians - self.initial_gaussians) / self.final_gaussian_iteration)
+
+    @property
+    def num_gaussians(self) -> int:
+        return int(sum(w.shape[0] for w in self.raw_am.weights))
+
+    def _update(self, stats: GmmStats, failed: int, realigned: bool, **mle_options) -> None:
+        """Transition update, Gaussian update and mix-up to the current target from one iteration's statistics."""
+        loglike, before = stats.loglike_per_frame, self.raw_am
+        self.raw_tm = _adapt.transition_update(self.raw_tm, stats.tid_count)
+        occ = mle.pdf_occupancies(before, stats)
+        self.raw_am, updated, removed, floored = mle.mle_update(before, stats, **mle_options)
+        n = self.num_gaussians
+        if self.current_gaussians > n:
+            self.raw_am, _targets = mle.mix_up(self.raw_am, occ, self.current_gaussians, self.power, rng=self.rng)
+        self.history.append(dict(iteration=self.iteration, loglike=loglike, frames=stats.tot_count, gaussians=self.num_gaussians,
+                                 failed=int(failed), realigned=bool(realigned), mixed_up=self.num_gaussians > n,
+                                 target=self.current_gaussians, updated=updated, removed=removed, floored=floored))
+
+    def _iterate(self, failed: int, first_beam: float) -> None:
+        """Iterations 1 .. num_iterations (MFA/acoustic_modeling/base.py:769-833): realign when scheduled (iteration 1 with
+        ``first_beam``), statistics, update, then the target grows while the iteration is at most ``final_gaussian_iteration``."""
+        b = self.backend
+        for it in range(1, self.num_iterations + 1):
+            self.iteration = it
+            realign = it in self.realignment_iterations
+            if realign:
+                failed = b.align(self.raw_tm, self.raw_am, self.tree, first_beam if it == 1 else self.opt.beam)
+            stats = b.accumulate(self.raw_tm, self.raw_am)
+            self._update(stats, failed, realign)
+            if it <= self.final_gaussian_iteration:
+                self.current_gaussians += self.gaussian_increment
+
+    def write(self, directory) -> List[Path]:
+        """``final.mdl`` and ``tree``."""
+        out = Path(directory)
+        out.mkdir(parents=True, exist_ok=True)
+        with open(out / "final.mdl", "wb") as f:
+            kaldi_io.write_model(f, self.raw_tm, self.raw_am)
+        with open(out / "tree", "wb") as f:
+            kaldi_io.write_tree(f, self.tree)
+        return [out / "final.mdl", out / "tree"]
+
+
+class MonophoneTrainer(GmmTrainerBase):
     """``MonophoneTrainer(utterances, lexicon, topology).train()`` then ``write(directory)`` / ``aligner()``.
 
     Options carry the reference's names and defaults (MFA/acoustic_modeling/monophone.py:160-182): ``num_iterations`` 40,
@@ -159,30 +221,6 @@ class MonophoneTrainer:
         self.initial_stats: Optional[GmmStats] = None      # iteration 0's statistics (of the equal alignments)
         self.iteration = 0
 
-    @property
-    def gaussian_increment(self) -> int:
-        """BaseTrainer.gaussian_increment (MFA/acoustic_modeling/base.py:451-453); 0 when no iteration may add Gaussians."""
-        if self.final_gaussian_iteration <= 0:
-            return 0
-        return int((self.max_gaussians - self.initial_gaussians) / self.final_gaussian_iteration)
-
-    @property
-    def num_gaussians(self) -> int:
-        return int(sum(w.shape[0] for w in self.raw_am.weights))
-
-    def _update(self, stats: GmmStats, failed: int, realigned: bool, **mle_options) -> None:
-        """Transition update, Gaussian update and mix-up to the current target from one iteration's statistics."""
-        loglike, before = stats.loglike_per_frame, self.raw_am
-        self.raw_tm = _adapt.transition_update(self.raw_tm, stats.tid_count)
-        occ = mle.pdf_occupancies(before, stats)
-        self.raw_am, updated, removed, floored = mle.mle_update(before, stats, **mle_options)
-        n = self.num_gaussians
-        if self.current_gaussians > n:
-            self.raw_am, _targets = mle.mix_up(self.raw_am, occ, self.current_gaussians, self.power, rng=self.rng)
-        self.history.append(dict(iteration=self.iteration, loglike=loglike, frames=stats.tot_count, gaussians=self.num_gaussians,
-                                 failed=int(failed), realigned=bool(realigned), mixed_up=self.num_gaussians > n,
-                                 target=self.current_gaussians, updated=updated, removed=removed, floored=floored))
-
     def _flat_start(self, stats: GmmStats) -> kaldi_io.RawAmDiagGmm:
         """gmm-init-mono's model from the statistics of the equal alignments: every pdf at the global mean and variance."""
         n = float(stats.occ.sum())
@@ -207,26 +245,8 @@ class MonophoneTrainer:
         self.initial_stats = stats.copy()
         self.raw_am = self._flat_start(stats)
         self._update(stats, failed, True, min_gaussian_occupancy=3.0)
-        for it in range(1, self.num_iterations + 1):
-            self.iteration = it
-            realign = it in self.realignment_iterations
-            if realign:
-                failed = b.align(self.raw_tm, self.raw_am, self.tree, self.initial_beam if it == 1 else self.opt.beam)
-            stats = b.accumulate(self.raw_tm, self.raw_am)
-            self._update(stats, failed, realign)
-            if it <= self.final_gaussian_iteration:
-                self.current_gaussians += self.gaussian_increment
+        self._iterate(failed, self.initial_beam)
         return self
-
-    def write(self, directory) -> List[Path]:
-        """``final.mdl`` and ``tree``."""
-        out = Path(directory)
-        out.mkdir(parents=True, exist_ok=True)
-        with open(out / "final.mdl", "wb") as f:
-            kaldi_io.write_model(f, self.raw_tm, self.raw_am)
-        with open(out / "tree", "wb") as f:
-            kaldi_io.write_tree(f, self.tree)
-        return [out / "final.mdl", out / "tree"]
 
     def aligner(self, **kw):
         """A ``CorpusAligner`` on the trained model (on the training engine when the device backend ran)."""
@@ -237,3 +257,187 @@ class MonophoneTrainer:
         return CorpusAligner(TransitionModel(self.raw_tm), DiagGmmModel.from_raw(self.raw_am), self.tree, self.lexicon,
                              mfcc_options=self.mfcc_options, silence_phones=self.silence_phones, raw_tm=self.raw_tm,
                              raw_am=self.raw_am, **kw)
+
+
+# ---- the LDA stage on a fixed tree ----------------------------------------------------------------------------------------------
+class LdaDeviceBackend(DeviceBackend):
+    """``LdaTrainer``'s calls on the device: ``DeviceBackend``'s ``align`` / ``accumulate`` / ``alignments`` on splice + LDA
+    features, and before them the previous model's alignments, the LDA statistics of those alignments
+    (``CorpusAligner._lda_accumulate``) and the same alignments on the new features."""
+
+    def __init__(self, utterances, lexicon, options=None, mfcc_options: Optional[dict] = None, silence_phones: Sequence[int] = (),
+                 device: int = 0, engine=None, splice_context: int = 3):
+        super().__init__(utterances, lexicon, options, mfcc_options, silence_phones, device, engine)
+        self.ctx = int(splice_context)
+        self.base_dim = int(self.mfcc_options.get("num_coefficients", 13))
+        self.prev_al = None
+        self.prev_kept: List[tuple] = []
+
+    def align_previous(self, raw_tm, raw_am, tree, previous_lda, beam: float) -> int:
+        from .aligner import CorpusAligner
+
+        al = CorpusAligner(TransitionModel(raw_tm), DiagGmmModel.from_raw(raw_am), tree, self.lexicon, lda=previous_lda,
+                           options=self.opt, device=self.device, engine=self.engine, mfcc_options=self.mfcc_options,
+                           silence_phones=self.silence_phones, raw_tm=raw_tm, raw_am=raw_am)
+        self.prev_al, self.engine = al, al.engine
+        usual = al.opt.beam
+        al.opt.beam = float(beam)
+        try:
+            with al._run():
+                results, self.prev_kept = al._align(self.utts, False, False, None, keep_last=True)
+        finally:
+            al.opt.beam = usual
+        return sum(r is None for r in results)
+
+    def lda_accumulate(self, raw_tm, rand_prune: float, seed: int):
+        al = self.prev_al
+        with al._run():
+            spk_ids, cmvn = al.speaker_cmvn(self.utts)
+            return al._lda_accumulate(self.utts, self.prev_kept, spk_ids, cmvn, self.ctx, float(rand_prune), int(seed))
+
+    def set_lda(self, lda: np.ndarray, raw_tm, raw_am, tree) -> None:
+        """From here on the features are splice + ``lda``: the aligner is built anew on the model given (of the LDA's
+        dimension), and the previous model's alignments stay resident beside their new features."""
+        import torch
+
+        self.lda, self.al = np.ascontiguousarray(lda, dtype=np.float32), None
+        al = self._aligner(raw_tm, raw_am, tree)
+        d_lda = torch.from_numpy(self.lda).to(al.engine.device)
+        with al._run():
+            spk_ids, cmvn = al.speaker_cmvn(self.utts)
+            self.kept = [(idx, al._batch_features(self.utts, idx, spk_ids, cmvn, d_lda, None)[0], ali, fo, rows)
+                         for idx, _feats, ali, fo, rows in self.prev_kept]
+        self.prev_kept, self.prev_al = [], None
+
+
+class LdaTrainer(GmmTrainerBase):
+    """The reference's ``LdaTrainer`` (MFA/acoustic_modeling/lda.py) on the tree it is given — tree building is not in this
+    project, and neither is MLLT (iterations 2, 4, 6, 12 of the reference).  ``LdaTrainer(utterances, lexicon,
+    previous=(raw_tm, raw_am, tree)).train()`` then ``write(directory)`` (``final.mdl``, ``tree``, ``lda.mat``) / ``aligner()``.
+
+      iteration 0   align with ``previous`` on its own features (Δ+ΔΔ, or splice + ``previous_lda``) → LDA statistics of
+                    those alignments (classes are pdfs, silence weighs 0) → ``lda.estimate_lda`` → GMM statistics of the same
+                    alignments on the splice + LDA features under a one-Gaussian-per-pdf model (the posterior is 1 whatever
+                    its parameters) → every pdf at its own mean and variance (floored at ``mle.MIN_VARIANCE``; a pdf not
+                    above ``min_gaussian_occupancy`` takes the global ones) → transition update, ``mle_update``, mix-up
+      iteration i   ``MonophoneTrainer``'s loop (``GmmTrainerBase._iterate``)
+
+    Options carry the reference's names and defaults (MFA/acoustic_modeling/lda.py:218-244, triphone.py:213-234, :318-325):
+    ``num_iterations`` 35, ``max_gaussians`` 15000, ``power`` 0.25, ``lda_dimension`` 40, ``splice_context`` 3 (both sides),
+    ``boost_silence`` 1.0 (in ``align_options``), realignment at every tenth iteration, ``final_gaussian_iteration`` =
+    ``num_iterations`` − 10, ``initial_gaussians`` = the number of pdfs (the reference's ``num_leaves``).  ``random_prune``
+    defaults to 0, not the reference's 4.0: the reference prunes because its accumulation is slow, and on the device every
+    frame is affordable.  ``history`` as ``MonophoneTrainer``'s; ``lda_stats``, ``lda_mat`` [dim, S] and ``lda_full`` [S, S]
+    are kept.  Refused with a message: an LDA dimension above the GMM statistics' (48) and a spliced dimension above 128."""
+
+    def __init__(self, utterances=None, lexicon=None, previous=None, previous_lda: Optional[np.ndarray] = None,
+                 lda_dimension: int = 40, splice_context: int = 3, num_iterations: int = 35, max_gaussians: int = 15000,
+                 power: float = 0.25, random_prune: float = 0.0, align_options=None, seed: int = 1234,
+                 min_gaussian_occupancy: float = 3.0, silence_phones: Sequence[int] = (), mfcc_options: Optional[dict] = None,
+                 device: int = 0, engine=None, backend=None):
+        from . import _lib
+        from .aligner import AlignOptions
+
+        if previous is None or lexicon is None:
+            raise ValueError("LdaTrainer needs a lexicon and the previous stage's (raw_tm, raw_am, tree)")
+        if num_iterations < 1:
+            raise ValueError("num_iterations must be at least 1")
+        lib = _lib.lib()
+        self.lexicon, self.previous = lexicon, tuple(previous)
+        self.previous_lda = None if previous_lda is None else np.asarray(previous_lda, dtype=np.float32)
+        self.lda_dimension, self.splice_context = int(lda_dimension), int(splice_context)
+        if self.lda_dimension < 1 or self.lda_dimension > int(lib.mfa_gmm_acc_max_dim()):
+            raise ValueError(f"LdaTrainer: lda_dimension {self.lda_dimension} outside 1..{int(lib.mfa_gmm_acc_max_dim())} "
+                             "(the GMM statistics' feature dimension)")
+        self.num_iterations, self.max_gaussians, self.power = int(num_iterations), int(max_gaussians), float(power)
+        self.random_prune, self.seed = float(random_prune), int(seed)
+        self.min_gaussian_occupancy = float(min_gaussian_occupancy)
+        self.opt = align_options or AlignOptions(boost_silence=1.0)
+        self.silence_phones, self.mfcc_options = list(silence_phones), dict(mfcc_options or {})
+        self.backend = backend if backend is not None else LdaDeviceBackend(utterances, lexicon, self.opt, self.mfcc_options,
+                                                                             self.silence_phones, device, engine, self.splice_context)
+        spliced = (2 * self.splice_context + 1) * int(self.backend.base_dim)
+        if self.splice_context < 0 or spliced > int(lib.mfa_lda_acc_max_dim()):
+            raise ValueError(f"LdaTrainer: splice context {self.splice_context} on {self.backend.base_dim} base features gives a "
+                             f"spliced dimension of {spliced} (the LDA statistics take at most {int(lib.mfa_lda_acc_max_dim())})")
+        if self.lda_dimension > spliced:
+            raise ValueError(f"LdaTrainer: lda_dimension {self.lda_dimension} above the spliced dimension {spliced}")
+        self.raw_tm, self.raw_am, self.tree = self.previous
+        self.initial_gaussians = self.raw_am.num_pdfs
+        self.final_gaussian_iteration = self.num_iterations - 10
+        self.realignment_iterations = list(range(10, self.num_iterations, 10))
+        self.current_gaussians = self.initial_gaussians
+        self.rng = np.random.default_rng(self.seed)
+        self.history: List[Dict] = []
+        self.initial_stats: Optional[GmmStats] = None      # iteration 0's statistics (of the previous model's alignments)
+        self.lda_stats = None
+        self.lda_mat: Optional[np.ndarray] = None
+        self.lda_full: Optional[np.ndarray] = None
+        self.iteration = 0
+
+    def _unit_model(self, num_pdfs: int) -> kaldi_io.RawAmDiagGmm:
+        """One Gaussian per pdf at mean 0, variance 1: what iteration 0's statistics run under."""
+        D = self.lda_dimension
+        one, mi, iv = np.ones(1, np.float32), np.zeros((1, D), np.float32), np.ones((1, D), np.float32)
+        gc = _adapt.gconsts(one, mi, iv)
+        return kaldi_io.RawAmDiagGmm(D, [gc.copy() for _ in range(num_pdfs)], [one.copy() for _ in range(num_pdfs)],
+                                     [mi.copy() for _ in range(num_pdfs)], [iv.copy() for _ in range(num_pdfs)])
+
+    def _pdf_start(self, stats: GmmStats) -> kaldi_io.RawAmDiagGmm:
+        """Every pdf at the mean and variance of its own frames; one not above ``min_gaussian_occupancy`` at the global ones."""
+        n = float(stats.occ.sum())
+        if not n > 0:
+            raise ValueError("LdaTrainer: the previous model aligned no utterance")
+        gmean = stats.mean_acc.sum(axis=0) / n
+        gvar = np.maximum(stats.var_acc.sum(axis=0) / n - gmean * gmean, mle.MIN_VARIANCE)
+        one = np.ones(1, np.float32)
+        out = kaldi_io.RawAmDiagGmm(self.lda_dimension, [], [], [], [])
+        for p in range(stats.occ.shape[0]):
+            mean, var = gmean, gvar
+            if stats.occ[p] > self.min_gaussian_occupancy:
+                mean = stats.mean_acc[p] / stats.occ[p]
+                var = np.maximum(stats.var_acc[p] / stats.occ[p] - mean * mean, mle.MIN_VARIANCE)
+            iv = (1.0 / var).astype(np.float32)[None]
+            mi = mean.astype(np.float32)[None] * iv
+            out.gconsts.append(_adapt.gconsts(one, mi, iv)); out.weights.append(one.copy())
+            out.means_invvars.append(mi); out.inv_vars.append(iv)
+        return out
+
+    def train(self) -> "LdaTrainer":
+        from .lda import estimate_lda
+
+        b = self.backend
+        prev_tm, prev_am, tree = self.previous
+        self.iteration = 0
+        failed = b.align_previous(prev_tm, prev_am, tree, self.previous_lda, self.opt.beam)
+        self.lda_stats = b.lda_accumulate(prev_tm, self.random_prune, self.seed)
+        self.lda_mat, self.lda_full = estimate_lda(self.lda_stats, dim=self.lda_dimension)
+        self.raw_tm, self.tree = prev_tm, tree
+        self.raw_am = self._unit_model(prev_am.num_pdfs)
+        b.set_lda(self.lda_mat, self.raw_tm, self.raw_am, self.tree)
+        stats = b.accumulate(self.raw_tm, self.raw_am)
+        self.initial_stats = stats.copy()
+        self.raw_am = self._pdf_start(stats)
+        self._update(stats, failed, True, min_gaussian_occupancy=self.min_gaussian_occupancy)
+        self._iterate(failed, self.opt.beam)
+        return self
+
+    def write(self, directory) -> List[Path]:
+        """``final.mdl``, ``tree`` and ``lda.mat``."""
+        files = super().write(directory)
+        if self.lda_mat is None:
+            raise ValueError("LdaTrainer.write: train has not been run")
+        with open(Path(directory) / "lda.mat", "wb") as f:
+            f.write(b"\0B")
+            kaldi_io.write_matrix(f, self.lda_mat)
+        return files + [Path(directory) / "lda.mat"]
+
+    def aligner(self, **kw):
+        """A ``CorpusAligner`` on the trained model and its LDA matrix (on the training engine when the device backend ran)."""
+        from .aligner import CorpusAligner
+
+        kw.setdefault("engine", getattr(self.backend, "engine", None))
+        kw.setdefault("options", self.opt)
+        return CorpusAligner(TransitionModel(self.raw_tm), DiagGmmModel.from_raw(self.raw_am), self.tree, self.lexicon,
+                             lda=self.lda_mat, mfcc_options=self.mfcc_options, silence_phones=self.silence_phones,
+                             raw_tm=self.raw_tm, raw_am=self.raw_am, **kw)
