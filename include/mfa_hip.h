@@ -48,7 +48,8 @@ MFA_API int mfa_timer_begin(mfa_ctx *ctx);
 MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
 /* Per-kernel accumulated HIP-event times since the last reset.  which: 0 mfcc, 1 cmvn, 2 feats, 3 gmm, 4 viterbi,
  * 5 resample, 6 pitch, 7 feature codec, 8-11 GMM statistics (lookup, ordering, sums, reduction), 12 equal alignment,
- * 13-16 LDA statistics (lookup, second moment, ordering + class sums, reductions).
+ * 13-16 LDA statistics (lookup, second moment, ordering + class sums, reductions), 17-20 MLLT statistics (lookup,
+ * ordering, sums, reductions).
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -660,6 +661,53 @@ MFA_API int mfa_debug_lda_acc_host(const float *h_mfcc, const int64_t *h_frame_o
                                    const int32_t *h_tid2class, const float *h_tid_weight, int32_t n_tids, int32_t n_classes,
                                    float rand_prune, const uint32_t *h_utt_key, uint32_t seed, double *h_zero, double *h_first,
                                    double *h_second, int64_t *h_tid_count);
+
+/* ---- MLLT statistics: replaces the accumulation of MlltAccStatsFunction / kalpy MlltStatsAccumulator.accumulate_stats
+ *      (MFA/acoustic_modeling/lda.py:122-180; Kaldi gmm-acc-mllt = MlltAccs::AccumulateFromPosteriors, restated here from
+ *      the algorithm's description — Kaldi's source is not among this project's references: parity unpinned).
+ *      Kaldi keeps, per output dimension j, G_j = sum over (t, g) of gamma_tg * inv_var_g[j] * d_tg d_tg^T with
+ *      d = x - mean_g.  The same G_j is sum over g of inv_var_g[j] * F_g with the per-Gaussian full second moment
+ *      F_g = sum over t of gamma_tg d_tg d_tg^T: this call forms occ and F_g, the contraction is the host's (mllt.py).
+ *
+ * Arithmetic contract.  A frame takes part, and gets its weight w, by the GMM statistics' rule (above).  The posteriors
+ * gamma_g of the frame's pdf are the GMM statistics' bits: the same float32 chain and the same softmax
+ * (csrc/gmm_acc_math.hpp, shared and not restated).  d_means float32 [G][dim], model Gaussian order, comes from the caller
+ * (means_invvars / inv_vars, formed once in float32 and handed to the device and to the twin alike).  For every Gaussian g
+ * of the pdf, in model order:
+ *   d_k = x_k - means[g][k]                         float32, one rounding;
+ *   occ[g] += gamma_g                               double;
+ *   full[g][i][j] = fma((double)gamma_g * (double)d_i, (double)d_j, full[g][i][j])   for j <= i; the first product is
+ *                                                   exact in double (24 + 24 bits);
+ *   the upper triangle of full[g] is a copy of the lower (the caller's value is read from the lower triangle);
+ *   tot[0] = fma(w, loglike, tot[0]);  tot[1] += w  as in the GMM statistics.
+ * Accumulators, float64, indexed by MODEL Gaussian: d_occ [G], d_full [G][dim][dim], d_tot [2].  They are added to, never
+ * overwritten; the Gaussians of a pdf without a frame keep the caller's bits, both triangles.
+ * Order of the double sums on the device: the frames of a pdf in ascending frame index (the GMM statistics' ordering).  full:
+ * cut into chunks of mfa_mllt_acc_chunk_frames() consecutive frames of that pdf; a chunk is summed from zero in frame order
+ * (4 frames per step of the f64 matrix instruction), the chunks are added in order onto the caller's value.  occ and tot:
+ * the same with chunks of mfa_gmm_acc_chunk_frames() — every chunk of full is a whole number of those —, so that occ and
+ * tot are bit-equal to mfa_gmm_acc_batch's on the same input.  The result is a function of the input alone: two calls on
+ * the same input give the same bits.  No floating-point atomics.
+ * mfa_debug_mllt_acc_host is the same contract on host arrays, frames in ascending index, plain loops, expf / logf from
+ * libm: only expf / logf, the order in which a frame's exponentials are added and the order of the double sums may differ.
+ * Runs on the model loaded with mfa_load_gmm, asynchronously on the ctx stream; the partials lie in the context's shared
+ * workspace: (frames / chunk + 1) * largest pdf + G rows of dim * (dim + 1) / 2 doubles at the most.  Limits (refused with
+ * a message, the context stays usable): no model loaded; dim > mfa_mllt_acc_max_dim() = 48 (three 16-wide blocks of the
+ * matrix tiles); a pdf of more than 128 Gaussians; 2^31 frames or more in one call; a NULL array.  total_frames == 0 is no
+ * error and writes nothing. */
+MFA_API int32_t mfa_mllt_acc_chunk_frames(void);
+MFA_API int32_t mfa_mllt_acc_max_dim(void);
+MFA_API int mfa_mllt_acc_batch(mfa_ctx *ctx, const float *d_feats, int64_t total_frames, const int32_t *d_ali,
+                               const int32_t *d_tid2pdf, const float *d_tid_weight, int32_t n_tids, const float *d_means,
+                               double *d_occ, double *d_full, double *d_tot);
+/* Host twin, no context and no device.  The model as mfa_load_gmm takes it plus h_means [G][dim]; h_feats
+ * [total_frames][dim]; per frame h_pdf (< 0 or >= num_pdfs: the frame takes no part) and h_weight (0: no part).  h_post
+ * (may be NULL) as in mfa_debug_gmm_acc_host.  Returns 0, -1 for bad arguments or an empty pdf, -2 for a pdf of more than
+ * 128 Gaussians, -3 for dim > 48. */
+MFA_API int mfa_debug_mllt_acc_host(int32_t dim, int32_t num_pdfs, const int32_t *h_pdf_offsets, const float *h_gconsts,
+                                    const float *h_means_invvars, const float *h_inv_vars, const float *h_means,
+                                    const float *h_feats, int64_t total_frames, const int32_t *h_pdf, const float *h_weight,
+                                    double *h_occ, double *h_full, double *h_tot, float *h_post, int32_t post_stride);
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,7 @@ from . import adapt as _adapt
 from . import kaldi_io
 from .engine import AlignmentEngine, GmmStats, fmllr_statistics, gmm_statistics, redo_capacity
 from .model import DiagGmmModel, TransitionModel
-from .stats import LdaStats, lda_statistics, silence_weights
+from .stats import LdaStats, MlltStats, lda_statistics, mllt_statistics, silence_weights
 from .staging import StagingRing
 
 
@@ -145,6 +145,7 @@ class CorpusAligner:
         self.adapt_loglike: Dict[str, Optional[float]] = {}   # average log-likelihood per frame the reference logs, per model
         self.adapt_counts: Dict[str, tuple] = {}         # Gaussians (updated, kept) per model
         self.lda_stats: Optional[LdaStats] = None        # the statistics of the last ``estimate_lda``
+        self.mllt_stats: Optional[MlltStats] = None      # the statistics of the last ``estimate_mllt``
         self.lda = None if lda is None else np.asarray(lda, dtype=np.float32)
         self.opt = options or AlignOptions()
         self.engine = engine or AlignmentEngine(device)
@@ -633,6 +634,36 @@ class CorpusAligner:
             spk_ids, cmvn = self.speaker_cmvn(utts)            # (from the cached MFCCs: the bits of the alignment pass)
             self.lda_stats = self._lda_accumulate(utts, kept, spk_ids, cmvn, int(splice_context), float(rand_prune), int(seed))
         return _estimate(self.lda_stats, dim=dim)
+
+    # ------------------------------------------------------------------ MLLT estimation
+    def _mllt_accumulate(self, kept, raw_am) -> MlltStats:
+        """MLLT statistics of the resident features and alignments ``kept`` under ``raw_am`` as its file holds it (no silence
+        boost), silence at weight 0.  The accumulators stay on the device over the batches (``MlltStats``)."""
+        model = DiagGmmModel.from_raw(raw_am)
+        self.engine.load_gmm(model)
+        self._loaded = model
+        weights = silence_weights(self.tm, self.silence_phones, 0.0)
+        st = MlltStats.zeros(model.num_gauss, model.dim)
+        for _idx, feats, ali, _fo, _rows in kept:
+            mllt_statistics(self.engine, feats, ali, self.tm, weights, into=st)
+        return st
+
+    def estimate_mllt(self, utterances: Sequence[CorpusUtterance], num_sweeps: int = 200):
+        """The MLLT estimate of the LDA+MLLT stage (MFA/acoustic_modeling/lda.py:122-180, 399-410), the sibling of
+        ``estimate_lda``: align with this aligner's model on its own features, keep features and alignments resident,
+        accumulate MLLT statistics under ``raw_am`` with silence at weight 0 on the device (``mllt_statistics``, kept as
+        ``mllt_stats``) and return ``mllt.estimate_mllt(*mllt.mllt_accs(stats, raw_am))`` = (mat [D, D], objf_impr, count,
+        trace).  Needs ``raw_am=`` of the constructor."""
+        from . import mllt as _mllt
+
+        if self.raw_am is None:
+            raise ValueError("estimate_mllt needs the model as read from its file: CorpusAligner(..., raw_am=)")
+        with self._run():
+            _results, kept = self._align(list(utterances), False, False, None, keep_last=True)
+            self.mllt_stats = self._mllt_accumulate(kept, self.raw_am)
+            self._load(self.am)
+        beta, G = _mllt.mllt_accs(self.mllt_stats, self.raw_am)
+        return _mllt.estimate_mllt(beta, G, num_sweeps=num_sweeps)
 
     def _reload(self, raw_tm, raw_am, raw_ali_am) -> None:
         """Make the adapted models the aligner's own: transition model (graphs, scaled probabilities), boosted copies, device."""

@@ -17,7 +17,8 @@
 
 enum { MFA_K_MFCC = 0, MFA_K_CMVN = 1, MFA_K_FEATS = 2, MFA_K_GMM = 3, MFA_K_VITERBI = 4, MFA_K_RESAMPLE = 5, MFA_K_PITCH = 6, MFA_K_COMPRESS = 7,
        MFA_K_ACC_LOOKUP = 8, MFA_K_ACC_SORT = 9, MFA_K_ACC_SUMS = 10, MFA_K_ACC_REDUCE = 11, MFA_K_EQUAL_ALIGN = 12,
-       MFA_K_LDA_LOOKUP = 13, MFA_K_LDA_SECOND = 14, MFA_K_LDA_CLASS = 15, MFA_K_LDA_REDUCE = 16, MFA_K_COUNT = 17 };
+       MFA_K_LDA_LOOKUP = 13, MFA_K_LDA_SECOND = 14, MFA_K_LDA_CLASS = 15, MFA_K_LDA_REDUCE = 16,
+       MFA_K_MLLT_LOOKUP = 17, MFA_K_MLLT_SORT = 18, MFA_K_MLLT_SUMS = 19, MFA_K_MLLT_REDUCE = 20, MFA_K_COUNT = 21 };
 
 // The device operations of dev_buf.hpp as HIP calls.  Every device pointer a context owns is an MfaBuf: freed with the
 // context, grown with reserve(), tables replaced as a set with dev_upload_commit<MfaHipDev>().
@@ -98,7 +99,7 @@ struct mfa_ctx {
   std::vector<int32_t> h_slot, h_nblk, h_row0, h_ngauss;
   MfaBuf d_w_stats;            // float packed rows of the fMLLR statistics model (two-model form; mfa_fmllr_stats_model) or empty
   MfaBuf d_nrows;              // int32 [num_pdfs] packed rows per pdf (fmllr.hip builds it on first use)
-  MfaBuf d_acc_tabs;           // int32 [num_pdfs] Gaussians per pdf | [num_pdfs + 1] first Gaussian (gmm_acc.hip builds it on first use)
+  MfaBuf d_acc_tabs;           // int32 [num_pdfs] Gaussians per pdf | [num_pdfs + 1] first Gaussian (gmm_acc.hip / mllt_acc.hip build it on first use)
   bool has_slot_class[5] = {false, false, false, false, false};   // model has pdfs of slot 32 / 16 / 8 / 4 / 1 rows
   bool has_single32 = false;       // some pdf is one 32-row block (17–32 Gaussians): gmm_split_single_kernel has work
   int max_nblk = 1;                // most 32-row blocks of any pdf
@@ -121,8 +122,8 @@ struct mfa_ctx {
   void *gmm_trace = nullptr;   // per-wavefront timeline records of the scoring kernel (mfa_debug_gmm_trace)
 
   // d_ws is one scratch buffer shared by the CMVN (feats.hip), Viterbi (viterbi.hip), fMLLR statistics (fmllr.hip), GMM
-  // statistics (gmm_acc.hip), feature codec (compress.hip), equal alignment (align_equal.hip) and LDA statistics (lda_acc.hip)
-  // stages: each lays its own workspace over it for the length of one call, and the order of
+  // statistics (gmm_acc.hip), feature codec (compress.hip), equal alignment (align_equal.hip), LDA statistics (lda_acc.hip)
+  // and MLLT statistics (mllt_acc.hip) stages: each lays its own workspace over it for the length of one call, and the order of
   // ctx->stream is all that keeps them apart.
   MfaBuf d_ws;
   MfaBuf d_gen_ws;             // workspace of the general-graph decoder (viterbi_general.hip)

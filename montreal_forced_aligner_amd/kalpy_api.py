@@ -882,6 +882,90 @@ class LdaStatsAccumulator:
         flush()
 
 
+# ------------------------------------------------------------------------------------------------ MLLT
+class MlltAccs:
+    """``_kalpy.transform.MlltAccs`` as MFA/acoustic_modeling/lda.py:399-410 uses it: ``Add(other)`` and ``update() -> (mat,
+    objf_impr, count)``.  ``stats`` is the ``stats.MlltStats`` behind it (None until frames arrive) — per-Gaussian full second
+    moments, contracted with ``acoustic_model``'s inverse variances at ``update`` (``mllt.mllt_accs``)."""
+
+    def __init__(self, acoustic_model=None, stats=None):
+        self.acoustic_model, self.stats = acoustic_model, stats
+
+    def Add(self, other: "MlltAccs") -> None:
+        if other.stats is None:
+            return
+        if self.acoustic_model is None:
+            self.acoustic_model = other.acoustic_model
+        if self.stats is None:
+            self.stats = other.stats.copy()
+        else:
+            self.stats += other.stats
+
+    def update(self, num_sweeps: int = 200):
+        from . import mllt
+        if self.stats is None:
+            raise ValueError("MlltAccs.update: no statistics were accumulated")
+        mat, objf_impr, count, _trace = mllt.estimate_mllt(*mllt.mllt_accs(self.stats, self.acoustic_model), num_sweeps=num_sweeps)
+        return mat, objf_impr, count
+
+
+class MlltStatsAccumulator:
+    """``kalpy.feat.lda.MlltStatsAccumulator(model_path, silence_phones, rand_prune=…)``: ``accumulate_stats(feature_archive,
+    alignment_archive, callback=None)`` over (key, matrix) final features and ``Alignment`` objects, then ``.mllt_accs``
+    (MFA/acoustic_modeling/lda.py:174-180).  Utterances are batched onto the device (``stats.mllt_statistics``), the
+    accumulators stay there over the batches; ``silence_phones`` weigh 0.  ``rand_prune`` is accepted and ignored: the prune
+    exists to make the reference's D³ accumulation per frame and Gaussian affordable, this formulation (per-Gaussian second
+    moments, D² per pair) does not have that cost, and a nonzero value changes nothing."""
+
+    def __init__(self, acoustic_model_path, silence_phones: Sequence[int] = (), rand_prune: float = 0.0, batch_frames: int = 500_000):
+        self.acoustic_model_path = acoustic_model_path
+        self.transition_model, self.acoustic_model = _read_model(acoustic_model_path)
+        self.silence_phones, self.rand_prune = list(silence_phones), float(rand_prune)
+        self.batch_frames = int(batch_frames)
+        self.mllt_accs = MlltAccs(self.acoustic_model)
+
+    def accumulate_stats(self, feature_archive, alignment_archive, callback=None) -> None:
+        import torch
+        from .stats import mllt_statistics, silence_weights
+
+        eng = get_engine()
+        if eng.gmm is not self.acoustic_model:
+            eng.load_gmm(self.acoustic_model)
+        tm = self.transition_model
+        weights = silence_weights(tm, self.silence_phones, 0.0)
+        feats = dict(feature_archive) if not isinstance(feature_archive, dict) else feature_archive
+        rows, alis, total = [], [], 0
+
+        def flush():
+            nonlocal rows, alis, total
+            if rows:
+                self.mllt_accs.stats = mllt_statistics(
+                    eng, torch.from_numpy(np.concatenate(rows).astype(np.float32)).to(eng.device),
+                    torch.from_numpy(np.concatenate(alis).astype(np.int32)).to(eng.device), tm, weights, into=self.mllt_accs.stats)
+            rows, alis, total = [], [], 0
+
+        for al in alignment_archive:
+            x = feats.get(al.utterance_id)
+            if x is None:
+                continue
+            a = np.asarray(al.alignment, dtype=np.int32)
+            if a.shape[0] != x.shape[0]:
+                logger.warning("utterance %s: %d alignment entries for %d frames, skipped", al.utterance_id, a.shape[0], x.shape[0])
+                continue
+            rows.append(np.asarray(x)); alis.append(a); total += a.shape[0]
+            if callback:
+                callback(al.utterance_id)
+            if total >= self.batch_frames:
+                flush()
+        flush()
+
+
+def compose_transforms(a: np.ndarray, b: np.ndarray, b_is_affine: bool = False) -> np.ndarray:
+    """``_kalpy.transform.compose_transforms(mat, prev, False)`` (MFA/acoustic_modeling/lda.py:420): ``mllt.compose_transforms``."""
+    from . import mllt
+    return mllt.compose_transforms(a, b, b_is_affine)
+
+
 # ------------------------------------------------------------------------------------------------ flat-start training
 def read_topology(path_or_bytes) -> kaldi_io.HmmTopology:
     """``kalpy.gmm.utils.read_topology``: a binary ``topo`` file."""

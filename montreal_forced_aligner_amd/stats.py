@@ -356,3 +356,154 @@ def lda_statistics_host(mfcc: np.ndarray, frame_off: np.ndarray, utt2spk, cmvn, 
     if cnt is not None:
         tid_count[...] = cnt
     return st
+
+
+def gaussian_means(gmm: DiagGmmModel) -> np.ndarray:
+    """The Gaussians' means as the MLLT statistics take them: ``means_invvars / inv_vars`` in float32, formed once and handed
+    to the device and to the host twin alike."""
+    return np.ascontiguousarray(np.asarray(gmm.means_invvars, dtype=np.float32) / np.asarray(gmm.inv_vars, dtype=np.float32))
+
+
+class MlltStats:
+    """MLLT statistics, indexed by model Gaussian (mfa_mllt_acc_batch): float64 ``occ`` [G], ``full`` [G, D, D] = Σ γ·d·dᵀ with
+    d = x − μ_g (symmetric, both triangles held), ``tot_like`` = Σ w·loglike, ``tot_count`` = Σ w.  Additive: ``a += b``.
+
+    ``full`` is hundreds of megabytes for a real model, so during a device pass the accumulators live in device tensors:
+    ``mllt_statistics(into=)`` adds to them in place, batch after batch, and nothing crosses to the host until ``occ``,
+    ``full``, ``tot_like`` or ``tot_count`` is read — once, after the pass.  Host arrays handed in (``zeros``, a copy, the
+    result of ``+=``) go to the device at the next ``mllt_statistics`` call and stay there."""
+
+    def __init__(self, occ: np.ndarray, full: np.ndarray, tot_like: float = 0.0, tot_count: float = 0.0):
+        self._occ = np.ascontiguousarray(occ, dtype=np.float64)
+        self._full = np.ascontiguousarray(full, dtype=np.float64)
+        if self._full.ndim != 3 or self._full.shape[0] != self._occ.shape[0] or self._full.shape[1] != self._full.shape[2]:
+            raise ValueError(f"MlltStats: occ {self._occ.shape} and full {self._full.shape} are not [G] and [G, D, D]")
+        self._tot = np.array([tot_like, tot_count], dtype=np.float64)
+        self._shape = tuple(self._full.shape)
+        self._dev = None          # (occ, full, tot) device tensors, or None
+        self._dev_newer = False   # the device tensors hold sums the host arrays do not
+
+    @classmethod
+    def zeros(cls, num_gauss: int, dim: int) -> "MlltStats":
+        return cls(np.zeros(num_gauss), np.zeros((num_gauss, dim, dim)))
+
+    @property
+    def shape(self) -> Tuple[int, int, int]:
+        return self._shape
+
+    def _host(self) -> None:
+        if self._dev_newer:
+            occ, full, tot = self._dev
+            self._occ, self._full, self._tot = occ.cpu().numpy(), full.cpu().numpy(), tot.cpu().numpy()
+            self._dev_newer = False
+
+    def _device(self, dev):
+        """The accumulators as device tensors to add to; the host copies are stale from here on."""
+        if self._dev is None or self._dev[0].device != torch.device(dev):
+            self._host()
+            self._dev = tuple(torch.from_numpy(a).to(dev) for a in (self._occ, self._full, self._tot))
+        self._dev_newer = True
+        return self._dev
+
+    @property
+    def occ(self) -> np.ndarray:
+        self._host()
+        return self._occ
+
+    @property
+    def full(self) -> np.ndarray:
+        self._host()
+        return self._full
+
+    @property
+    def tot_like(self) -> float:
+        self._host()
+        return float(self._tot[0])
+
+    @property
+    def tot_count(self) -> float:
+        self._host()
+        return float(self._tot[1])
+
+    def copy(self) -> "MlltStats":
+        return MlltStats(self.occ.copy(), self.full.copy(), self.tot_like, self.tot_count)
+
+    def __iadd__(self, other: "MlltStats") -> "MlltStats":
+        if self.shape != other.shape:
+            raise ValueError("MlltStats of different models cannot be added")
+        self._host()
+        self._occ += other.occ
+        self._full += other.full
+        self._tot += np.array([other.tot_like, other.tot_count])
+        self._dev = None          # the host arrays are the value now
+        return self
+
+    @property
+    def loglike_per_frame(self) -> float:
+        return self.tot_like / self.tot_count if self.tot_count else 0.0
+
+
+def mllt_statistics(engine, feats: torch.Tensor, ali: torch.Tensor, tm: TransitionModel,
+                    weights: Optional[np.ndarray] = None, into: Optional[MlltStats] = None) -> MlltStats:
+    """MLLT statistics of one batch from its alignments (mfa_mllt_acc_batch; the contract is in include/mfa_hip.h), with the
+    model loaded in the engine.  Arguments as ``gmm_statistics``.  ``into``: statistics to add to, and the object returned;
+    its accumulators stay on the device between calls (``MlltStats``)."""
+    if engine.gmm is None:
+        raise _lib.MfaHipError("mllt_statistics: no acoustic model loaded (AlignmentEngine.load_gmm)")
+    dev = engine.device
+    gmm = engine.gmm
+    G, D = gmm.num_gauss, gmm.dim
+    id2pdf, w = tid_tables(tm, weights)
+    n_tids = int(id2pdf.shape[0])
+    st = into if into is not None else MlltStats.zeros(G, D)
+    if st.shape != (G, D, D):
+        raise ValueError("mllt_statistics: `into` does not fit the loaded model")
+    total = int(ali.shape[0])
+    if feats.shape[0] != total or (total and feats.shape[1] != D):
+        raise _lib.MfaHipError(f"mllt_statistics: features {tuple(feats.shape)} for {total} frames of a model of dim {D}")
+    if feats.dtype != torch.float32 or not feats.is_cuda or not ali.is_cuda:
+        raise _lib.MfaHipError("mllt_statistics: features must be float32 and, like the alignments, on the device")
+    feats = feats.contiguous()
+    ali = ali.to(torch.int32).contiguous()
+    means = torch.from_numpy(gaussian_means(gmm)).to(dev)
+    d_pdf, d_w = torch.from_numpy(id2pdf).to(dev), torch.from_numpy(w).to(dev)
+    occ, full, tot = st._device(dev)
+    check(engine.ctx, engine.lib.mfa_mllt_acc_batch(engine.ctx, _ptr(feats), total, _ptr(ali), _ptr(d_pdf), _ptr(d_w), n_tids,
+                                                     _ptr(means), _ptr(occ), _ptr(full), _ptr(tot)), "mfa_mllt_acc_batch")
+    return st
+
+
+def mllt_statistics_host(gmm: DiagGmmModel, feats: np.ndarray, ali: np.ndarray, tm: TransitionModel,
+                         weights: Optional[np.ndarray] = None, into: Optional[MlltStats] = None, want_post: bool = False):
+    """The same call on the host twin (mfa_debug_mllt_acc_host: no device, frames in ascending index, plain loops): the
+    specification the device is held to.  numpy arrays in; with ``want_post`` also returns every frame's posteriors."""
+    lib = _lib.lib()
+    id2pdf, w = tid_tables(tm, weights)
+    n_tids = int(id2pdf.shape[0])
+    G, D = gmm.num_gauss, gmm.dim
+    st = into if into is not None else MlltStats.zeros(G, D)
+    if st.shape != (G, D, D):
+        raise ValueError("mllt_statistics_host: `into` does not fit the model")
+    feats = np.ascontiguousarray(feats, dtype=np.float32)
+    ali = np.ascontiguousarray(ali, dtype=np.int32)
+    if feats.ndim != 2 or feats.shape[0] != ali.shape[0] or (ali.shape[0] and feats.shape[1] != D):
+        raise _lib.MfaHipError(f"mllt_statistics_host: features {feats.shape} for {ali.shape[0]} frames of a model of dim {D}")
+    ok = (ali > 0) & (ali < n_tids)
+    safe = np.where(ok, ali, 0)
+    pdf = np.where(ok, id2pdf[safe], -1).astype(np.int32)
+    fw = np.where(ok, w[safe], np.float32(0)).astype(np.float32)
+    po, gc, mi, iv = model_arrays(gmm)
+    means = gaussian_means(gmm)
+    st._host()
+    occ, full, tot = st._occ, st._full, st._tot
+    stride = int(np.diff(po).max())
+    post = np.zeros((ali.shape[0], stride), dtype=np.float32) if want_post else None
+    rc = lib.mfa_debug_mllt_acc_host(D, gmm.num_pdfs, po.ctypes.data, gc.ctypes.data, mi.ctypes.data, iv.ctypes.data,
+                                     means.ctypes.data, feats.ctypes.data, int(ali.shape[0]), pdf.ctypes.data, fw.ctypes.data,
+                                     occ.ctypes.data, full.ctypes.data, tot.ctypes.data,
+                                     None if post is None else post.ctypes.data, stride)
+    if rc != 0:
+        why = {-2: "a pdf of more than 128 Gaussians", -3: "feature dimension above 48"}.get(rc, "bad arguments")
+        raise _lib.MfaHipError(f"mfa_debug_mllt_acc_host: {why}")
+    st._dev = None                # the host arrays are the value now
+    return (st, post) if want_post else st

@@ -167,10 +167,18 @@ class GmmTrainerBase:
             realign = it in self.realignment_iterations
             if realign:
                 failed = b.align(self.raw_tm, self.raw_am, self.tree, first_beam if it == 1 else self.opt.beam)
+            extra = self._before_statistics(it)
             stats = b.accumulate(self.raw_tm, self.raw_am)
             self._update(stats, failed, realign)
+            if extra:
+                self.history[-1].update(extra)
             if it <= self.final_gaussian_iteration:
                 self.current_gaussians += self.gaussian_increment
+
+    def _before_statistics(self, iteration: int) -> Optional[Dict]:
+        """A stage's own step between an iteration's realignment and its statistics; what it returns joins the iteration's
+        ``history`` entry.  Nothing here."""
+        return None
 
     def write(self, directory) -> List[Path]:
         """``final.mdl`` and ``tree``."""
@@ -309,18 +317,52 @@ class LdaDeviceBackend(DeviceBackend):
                          for idx, _feats, ali, fo, rows in self.prev_kept]
         self.prev_kept, self.prev_al = [], None
 
+    def mllt_accumulate(self, raw_tm, raw_am):
+        """MLLT statistics of the resident alignments under the model as its file would hold it, silence at weight 0
+        (``CorpusAligner._mllt_accumulate``: the accumulators stay on the device over the batches)."""
+        return self.al._mllt_accumulate(self.kept, raw_am)
+
+    def set_transform(self, lda: np.ndarray) -> None:
+        """From here on the features are splice + ``lda`` (the composed matrix, of the same shape): the resident features
+        are recomputed from the base features, the alignments stay."""
+        import torch
+
+        al = self.al
+        self.lda = al.lda = np.ascontiguousarray(lda, dtype=np.float32)
+        d_lda = torch.from_numpy(self.lda).to(al.engine.device)
+        with al._run():
+            spk_ids, cmvn = al.speaker_cmvn(self.utts)
+            self.kept = [(idx, al._batch_features(self.utts, idx, spk_ids, cmvn, d_lda, None)[0], ali, fo, rows)
+                         for idx, _feats, ali, fo, rows in self.kept]
+
+
+REFERENCE_MLLT_ITERATIONS = (2, 4, 6, 12)      # LdaTrainer.mllt_iterations of the reference (MFA/acoustic_modeling/lda.py:312)
+
 
 class LdaTrainer(GmmTrainerBase):
-    """The reference's ``LdaTrainer`` (MFA/acoustic_modeling/lda.py) on the tree it is given — tree building is not in this
-    project, and neither is MLLT (iterations 2, 4, 6, 12 of the reference).  ``LdaTrainer(utterances, lexicon,
-    previous=(raw_tm, raw_am, tree)).train()`` then ``write(directory)`` (``final.mdl``, ``tree``, ``lda.mat``) / ``aligner()``.
+    """The reference's LDA+MLLT ``LdaTrainer`` (MFA/acoustic_modeling/lda.py) on the tree it is given — tree building is not
+    in this project.  ``LdaTrainer(utterances, lexicon, previous=(raw_tm, raw_am, tree)).train()`` then ``write(directory)``
+    (``final.mdl``, ``tree``, ``lda.mat``) / ``aligner()``.
 
       iteration 0   align with ``previous`` on its own features (Δ+ΔΔ, or splice + ``previous_lda``) → LDA statistics of
                     those alignments (classes are pdfs, silence weighs 0) → ``lda.estimate_lda`` → GMM statistics of the same
                     alignments on the splice + LDA features under a one-Gaussian-per-pdf model (the posterior is 1 whatever
                     its parameters) → every pdf at its own mean and variance (floored at ``mle.MIN_VARIANCE``; a pdf not
                     above ``min_gaussian_occupancy`` takes the global ones) → transition update, ``mle_update``, mix-up
-      iteration i   ``MonophoneTrainer``'s loop (``GmmTrainerBase._iterate``)
+      iteration i   ``MonophoneTrainer``'s loop (``GmmTrainerBase._iterate``); at an iteration of ``mllt_iterations``, after the
+                    realignment if one is scheduled and before the GMM statistics (MFA/acoustic_modeling/lda.py:372-451):
+                    MLLT statistics of the resident alignments (``backend.mllt_accumulate``: per-Gaussian full second
+                    moments on the device, silence at weight 0) → ``mllt.mllt_accs`` → ``mllt.estimate_mllt`` → the means
+                    moved into the new space (``mllt.transform_means``) → the matrix composed onto ``lda_mat``
+                    (``mllt.compose_transforms``) → ``backend.set_transform``: the resident features recomputed, the
+                    alignments kept.  The iteration's ``history`` entry gains ``mllt`` = {objf_impr_per_frame, logdet, count}.
+
+    ``mllt_iterations`` defaults to EMPTY, not to the reference's schedule ``REFERENCE_MLLT_ITERATIONS`` = (2, 4, 6, 12): the
+    loop without MLLT is what existing callers and tests of this stage run, and an empty schedule reproduces it bit for
+    bit; pass ``mllt_iterations=REFERENCE_MLLT_ITERATIONS`` for the reference's stage.  Entries outside
+    1..``num_iterations`` are refused.  ``mllt_mats`` keeps every estimated matrix, ``logdet_total`` the sum of their
+    log|det|: after an MLLT ``loglike`` is measured in a new space, and only ``loglike + logdet_total`` compares across
+    iterations.  ``write`` writes the composed ``lda.mat``.
 
     Options carry the reference's names and defaults (MFA/acoustic_modeling/lda.py:218-244, triphone.py:213-234, :318-325):
     ``num_iterations`` 35, ``max_gaussians`` 15000, ``power`` 0.25, ``lda_dimension`` 40, ``splice_context`` 3 (both sides),
@@ -334,7 +376,7 @@ class LdaTrainer(GmmTrainerBase):
                  lda_dimension: int = 40, splice_context: int = 3, num_iterations: int = 35, max_gaussians: int = 15000,
                  power: float = 0.25, random_prune: float = 0.0, align_options=None, seed: int = 1234,
                  min_gaussian_occupancy: float = 3.0, silence_phones: Sequence[int] = (), mfcc_options: Optional[dict] = None,
-                 device: int = 0, engine=None, backend=None):
+                 device: int = 0, engine=None, backend=None, mllt_iterations: Sequence[int] = (), mllt_sweeps: int = 200):
         from . import _lib
         from .aligner import AlignOptions
 
@@ -342,6 +384,12 @@ class LdaTrainer(GmmTrainerBase):
             raise ValueError("LdaTrainer needs a lexicon and the previous stage's (raw_tm, raw_am, tree)")
         if num_iterations < 1:
             raise ValueError("num_iterations must be at least 1")
+        self.mllt_iterations = tuple(int(i) for i in mllt_iterations)
+        if any(i < 1 or i > int(num_iterations) for i in self.mllt_iterations):
+            raise ValueError(f"LdaTrainer: mllt_iterations {self.mllt_iterations} outside 1..{int(num_iterations)}")
+        self.mllt_sweeps = int(mllt_sweeps)
+        self.mllt_mats: List[np.ndarray] = []
+        self.logdet_total = 0.0
         lib = _lib.lib()
         self.lexicon, self.previous = lexicon, tuple(previous)
         self.previous_lda = None if previous_lda is None else np.asarray(previous_lda, dtype=np.float32)
@@ -422,8 +470,25 @@ class LdaTrainer(GmmTrainerBase):
         self._iterate(failed, self.opt.beam)
         return self
 
+    def _before_statistics(self, iteration: int) -> Optional[Dict]:
+        if iteration not in self.mllt_iterations:
+            return None
+        from . import mllt
+
+        b = self.backend
+        stats = b.mllt_accumulate(self.raw_tm, self.raw_am)
+        beta, G = mllt.mllt_accs(stats, self.raw_am)
+        mat, impr, count, _trace = mllt.estimate_mllt(beta, G, num_sweeps=self.mllt_sweeps)
+        self.raw_am = mllt.transform_means(self.raw_am, mat)
+        self.lda_mat = mllt.compose_transforms(mat, self.lda_mat)
+        b.set_transform(self.lda_mat)
+        logdet = float(np.linalg.slogdet(mat.astype(np.float64))[1])
+        self.mllt_mats.append(mat)
+        self.logdet_total += logdet
+        return dict(mllt=dict(objf_impr_per_frame=impr / count, logdet=logdet, count=count))
+
     def write(self, directory) -> List[Path]:
-        """``final.mdl``, ``tree`` and ``lda.mat``."""
+        """``final.mdl``, ``tree`` and ``lda.mat`` (with MLLT: the composed matrix)."""
         files = super().write(directory)
         if self.lda_mat is None:
             raise ValueError("LdaTrainer.write: train has not been run")
