@@ -49,7 +49,7 @@ MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
 /* Per-kernel accumulated HIP-event times since the last reset.  which: 0 mfcc, 1 cmvn, 2 feats, 3 gmm, 4 viterbi,
  * 5 resample, 6 pitch, 7 feature codec, 8-11 GMM statistics (lookup, ordering, sums, reduction), 12 equal alignment,
  * 13-16 LDA statistics (lookup, second moment, ordering + class sums, reductions), 17-20 MLLT statistics (lookup,
- * ordering, sums, reductions).
+ * ordering, sums, reductions), 21-23 tree statistics (keys, ordering, sums).
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -708,6 +708,60 @@ MFA_API int mfa_debug_mllt_acc_host(int32_t dim, int32_t num_pdfs, const int32_t
                                     const float *h_means_invvars, const float *h_inv_vars, const float *h_means,
                                     const float *h_feats, int64_t total_frames, const int32_t *h_pdf, const float *h_weight,
                                     double *h_occ, double *h_full, double *h_tot, float *h_post, int32_t post_stride);
+
+/* ---- Tree statistics: replaces the accumulation of TreeStatsFunction / kalpy TreeStatsAccumulator.accumulate_stats
+ *      (MFA/acoustic_modeling/triphone.py; Kaldi acc-tree-stats, restated here from the algorithm's description — Kaldi's
+ *      source is not among this project's references: parity unpinned).  Per event (left phone, centre phone,
+ *      right phone, pdf-class) a count, the sum and the sum of squares of the features.  Context width 3, central position 1.
+ *
+ * Inputs.  d_feats float32 [total_frames][dim], the stage's final features; d_frame_off int64 [n_utt + 1]; total_frames =
+ * frame_off[n_utt] is the host's copy (the call never synchronises).  d_ali [total_frames] transition-ids.  Per
+ * transition-id, int32 [n_tids] each: d_tid_phone, d_tid_class (the pdf-class of the arc: the state's self-loop pdf-class for
+ * a self-loop, its forward pdf-class otherwise), d_tid_flags (bit 0: the arc is final, it enters the topology entry's final
+ * state; bit 1: the arc is a self-loop).  d_phone_ci uint8 [n_phones + 1]: 1 marks a context-independent phone.
+ *
+ * Taking part.  The alignments are those of this project's graphs, which put a state's self-loops AFTER its forward arc
+ * (Kaldi's reorder option; SplitToPhones with reordered = true): a segment is a maximal run of frames that ends at a final
+ * transition-id and the self-loops that follow it directly.  An utterance takes part only if every transition-id is in
+ * (0, n_tids) with a phone in [1, n_phones] and a pdf-class in [0, 256), its last frame ends a segment, and no frame's phone
+ * differs from the phone of the first frame of its segment.  Otherwise none of its frames take part and it is counted in
+ * d_skipped.  An utterance of 0 frames is counted nowhere.
+ * Event key of frame t in a segment of phone c: l = the previous segment's phone (0 at the utterance's start), r = the next
+ * segment's (0 at its end), l = r = 0 if d_phone_ci[c], pc = tid_class[ali[t]];
+ *   key = l << 48 | c << 28 | r << 8 | pc   (uint64; all ones for a frame that takes no part).
+ * The left phone has 16 bits of the key: n_phones of 2^16 or more is refused.
+ *
+ * Outputs, fresh per call (never added to).  d_frame_event int32 [total_frames]: the frame's row in the event list, or -1.
+ * d_n_events int64 [1]: always the true number of distinct keys.  d_skipped int64 [1].  For e < n_events, only if n_events <=
+ * cap: d_ev_key [e] (ascending), d_ev_count int64 [e], d_ev_sum / d_ev_sumsq float64 [e][dim].  If n_events > cap no event
+ * row is written: the host repeats the call with cap >= n_events (cap 0: the event arrays may be NULL).
+ *
+ * Arithmetic.  sum[k] += (double)x_k;  sumsq[k] += (double)x_k * (double)x_k — the product is exact in double, each step
+ * rounds once.  Order: the frames of an event in ascending frame index (stable sort by key), cut into chunks of
+ * mfa_tree_acc_chunk_frames(); a chunk is summed from zero in frame order, the chunks are added in order.  The result is a
+ * function of the input alone: two calls give the same bits.  No floating-point atomics.
+ * mfa_debug_tree_acc_host is the same contract on host arrays: keys, participation and event order are the device's by
+ * construction (both run csrc/tree_acc_math.hpp); every event is one plain loop in ascending frame index, so only the order
+ * of the double additions may differ.
+ * Asynchronous on the ctx stream; scratch in the context's shared workspace (some 36 bytes a frame and the sort's own).  Limits (refused with a
+ * message, the context stays usable): dim <= 0 or dim > mfa_tree_acc_max_dim() = 48 (the GMM statistics' limit: those run
+ * next); n_phones >= 2^16; a NULL array that would be read or written; 2^31 frames or more.  total_frames == 0 is no
+ * error: it writes n_events = 0 and skipped = 0. */
+MFA_API int32_t mfa_tree_acc_chunk_frames(void);
+MFA_API int32_t mfa_tree_acc_max_dim(void);
+MFA_API int mfa_tree_acc_batch(mfa_ctx *ctx, const float *d_feats, const int64_t *d_frame_off, int32_t n_utt, int64_t total_frames,
+                               int32_t dim, const int32_t *d_ali, const int32_t *d_tid_phone, const int32_t *d_tid_class,
+                               const int32_t *d_tid_flags, int32_t n_tids, const uint8_t *d_phone_ci, int32_t n_phones,
+                               int64_t cap, int32_t *d_frame_event, int64_t *d_n_events, int64_t *d_skipped, uint64_t *d_ev_key,
+                               int64_t *d_ev_count, double *d_ev_sum, double *d_ev_sumsq);
+/* Host twin, no context and no device (total_frames is h_frame_off[n_utt]).  Returns 0, -1 for bad arguments (a NULL array
+ * that would be read or written, offsets that do not ascend), -2 for dim > 48, -3 for 2^31 frames or more, -4 for n_phones
+ * >= 2^16. */
+MFA_API int mfa_debug_tree_acc_host(const float *h_feats, const int64_t *h_frame_off, int32_t n_utt, int32_t dim,
+                                    const int32_t *h_ali, const int32_t *h_tid_phone, const int32_t *h_tid_class,
+                                    const int32_t *h_tid_flags, int32_t n_tids, const uint8_t *h_phone_ci, int32_t n_phones,
+                                    int64_t cap, int32_t *h_frame_event, int64_t *h_n_events, int64_t *h_skipped,
+                                    uint64_t *h_ev_key, int64_t *h_ev_count, double *h_ev_sum, double *h_ev_sumsq);
 
 #ifdef __cplusplus
 }

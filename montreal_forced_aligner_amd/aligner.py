@@ -30,7 +30,7 @@ from . import adapt as _adapt
 from . import kaldi_io
 from .engine import AlignmentEngine, GmmStats, fmllr_statistics, gmm_statistics, redo_capacity
 from .model import DiagGmmModel, TransitionModel
-from .stats import LdaStats, MlltStats, lda_statistics, mllt_statistics, silence_weights
+from .stats import LdaStats, MlltStats, TreeStats, lda_statistics, mllt_statistics, silence_weights, tree_statistics
 from .staging import StagingRing
 
 
@@ -146,6 +146,8 @@ class CorpusAligner:
         self.adapt_counts: Dict[str, tuple] = {}         # Gaussians (updated, kept) per model
         self.lda_stats: Optional[LdaStats] = None        # the statistics of the last ``estimate_lda``
         self.mllt_stats: Optional[MlltStats] = None      # the statistics of the last ``estimate_mllt``
+        self.tree_stats: Optional[TreeStats] = None      # the statistics of the last ``tree_statistics``
+        self.tree_skipped = 0                            # ... and the utterances it skipped
         self.lda = None if lda is None else np.asarray(lda, dtype=np.float32)
         self.opt = options or AlignOptions()
         self.engine = engine or AlignmentEngine(device)
@@ -664,6 +666,35 @@ class CorpusAligner:
             self._load(self.am)
         beta, G = _mllt.mllt_accs(self.mllt_stats, self.raw_am)
         return _mllt.estimate_mllt(beta, G, num_sweeps=num_sweeps)
+
+    # ------------------------------------------------------------------ tree statistics
+    def _tree_accumulate(self, kept, ci_phones: Sequence[int]):
+        """Tree statistics of the resident features and alignments ``kept`` (of ``_align(..., keep_last=True)``): the device
+        call per batch (``stats.tree_statistics``), the batches merged on the host in batch order.  Returns (``TreeStats`` of
+        all batches or None, per batch (its ``TreeStats``, ``frame_event`` on the device), utterances skipped)."""
+        total, batches, skipped = None, [], 0
+        for _idx, feats, ali, fo, _rows in kept:
+            st, frame_event, n = tree_statistics(self.engine, feats, fo, ali, self.tm, ci_phones)
+            batches.append((st, frame_event))
+            skipped += n
+            if total is None:
+                total = st.copy()
+            else:
+                total += st
+        return total, batches, skipped
+
+    def tree_statistics(self, utterances: Sequence[CorpusUtterance], ci_phones: Optional[Sequence[int]] = None) -> TreeStats:
+        """The tree statistics of the triphone stage (MFA/acoustic_modeling/triphone.py, ``TreeStatsFunction``): align with this
+        aligner's model on its own features, keep features and alignments resident, accumulate per (left, centre, right,
+        pdf-class) on the device.  ``ci_phones``: the context-independent phones (default: the silence phones).  Kept as
+        ``tree_stats``; ``tree_skipped`` counts the utterances whose alignment did not end a phone."""
+        ci = self.silence_phones if ci_phones is None else list(ci_phones)
+        with self._run():
+            _results, kept = self._align(list(utterances), False, False, None, keep_last=True)
+            self.tree_stats, _batches, self.tree_skipped = self._tree_accumulate(kept, ci)
+        if self.tree_stats is None:
+            raise ValueError("tree_statistics: no utterances")
+        return self.tree_stats
 
     def _reload(self, raw_tm, raw_am, raw_ali_am) -> None:
         """Make the adapted models the aligner's own: transition model (graphs, scaled probabilities), boosted copies, device."""

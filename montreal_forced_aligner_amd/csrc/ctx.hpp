@@ -18,7 +18,8 @@
 enum { MFA_K_MFCC = 0, MFA_K_CMVN = 1, MFA_K_FEATS = 2, MFA_K_GMM = 3, MFA_K_VITERBI = 4, MFA_K_RESAMPLE = 5, MFA_K_PITCH = 6, MFA_K_COMPRESS = 7,
        MFA_K_ACC_LOOKUP = 8, MFA_K_ACC_SORT = 9, MFA_K_ACC_SUMS = 10, MFA_K_ACC_REDUCE = 11, MFA_K_EQUAL_ALIGN = 12,
        MFA_K_LDA_LOOKUP = 13, MFA_K_LDA_SECOND = 14, MFA_K_LDA_CLASS = 15, MFA_K_LDA_REDUCE = 16,
-       MFA_K_MLLT_LOOKUP = 17, MFA_K_MLLT_SORT = 18, MFA_K_MLLT_SUMS = 19, MFA_K_MLLT_REDUCE = 20, MFA_K_COUNT = 21 };
+       MFA_K_MLLT_LOOKUP = 17, MFA_K_MLLT_SORT = 18, MFA_K_MLLT_SUMS = 19, MFA_K_MLLT_REDUCE = 20,
+       MFA_K_TREE_KEYS = 21, MFA_K_TREE_ORDER = 22, MFA_K_TREE_SUMS = 23, MFA_K_COUNT = 24 };
 
 // The device operations of dev_buf.hpp as HIP calls.  Every device pointer a context owns is an MfaBuf: freed with the
 // context, grown with reserve(), tables replaced as a set with dev_upload_commit<MfaHipDev>().
@@ -122,8 +123,8 @@ struct mfa_ctx {
   void *gmm_trace = nullptr;   // per-wavefront timeline records of the scoring kernel (mfa_debug_gmm_trace)
 
   // d_ws is one scratch buffer shared by the CMVN (feats.hip), Viterbi (viterbi.hip), fMLLR statistics (fmllr.hip), GMM
-  // statistics (gmm_acc.hip), feature codec (compress.hip), equal alignment (align_equal.hip), LDA statistics (lda_acc.hip)
-  // and MLLT statistics (mllt_acc.hip) stages: each lays its own workspace over it for the length of one call, and the order of
+  // statistics (gmm_acc.hip), feature codec (compress.hip), equal alignment (align_equal.hip), LDA statistics (lda_acc.hip),
+  // MLLT statistics (mllt_acc.hip) and tree statistics (tree_acc.hip) stages: each lays its own workspace over it for the length of one call, and the order of
   // ctx->stream is all that keeps them apart.
   MfaBuf d_ws;
   MfaBuf d_gen_ws;             // workspace of the general-graph decoder (viterbi_general.hip)

@@ -27,8 +27,8 @@ from .packing import GraphPacking, PackedGraphs
 from .pipeline import Pipeline   # noqa: F401
 from .ragged import _rows_by_group, _speaker_groups, max_len, offsets   # noqa: F401
 from .staging import StagingPool, StagingRing
-from .stats import (GmmStats, LdaStats, MlltStats, check_delta_fmllr, fmllr_statistics, gmm_statistics, gmm_statistics_host,   # noqa: F401
-                    lda_statistics, lda_statistics_host, mllt_statistics, mllt_statistics_host, model_arrays, tid_tables)
+from .stats import (GmmStats, LdaStats, MlltStats, TreeStats, check_delta_fmllr, fmllr_statistics, gmm_statistics, gmm_statistics_host,   # noqa: F401
+                    lda_statistics, lda_statistics_host, mllt_statistics, mllt_statistics_host, model_arrays, tid_tables, tree_statistics, tree_statistics_host)
 
 STATUS_OK, STATUS_RETRIED, STATUS_FAILED, STATUS_TOKEN_OVERFLOW, STATUS_BP_OVERFLOW, STATUS_UNSUPPORTED = 0, 1, 2, 3, 4, 5
 
@@ -40,7 +40,8 @@ DEFAULT_MFCC = dict(sample_frequency=16000.0, frame_length_ms=25.0, frame_shift_
 KERNEL_SLOTS = ("mfcc", "cmvn", "feats", "gmm", "viterbi", "resample", "pitch", "compress",
                 "acc_lookup", "acc_sort", "acc_sums", "acc_reduce", "equal_align",
                 "lda_lookup", "lda_second", "lda_class", "lda_reduce",
-                "mllt_lookup", "mllt_sort", "mllt_sums", "mllt_reduce")
+                "mllt_lookup", "mllt_sort", "mllt_sums", "mllt_reduce",
+                "tree_keys", "tree_order", "tree_sums")
 
 
 def _out_ptrs(out: Dict[str, Optional[torch.Tensor]]):

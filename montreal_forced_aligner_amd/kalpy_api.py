@@ -1020,6 +1020,137 @@ def gmm_align_equal(fst: kaldi_io.Fst, feats: np.ndarray, seed: int = 0, key: in
     return ali.tolist(), _equal.path_words(fst, ali)
 
 
+# ------------------------------------------------------------------------------------------------ the triphone stage
+class TreeStatsAccumulator:
+    """``kalpy.gmm.train.TreeStatsAccumulator(model_path, context_independent_symbols=…)``: ``accumulate_stats(feature_archive,
+    alignment_archive, callback=None)`` over (key, matrix) final features and ``Alignment`` objects, then ``.tree_stats``
+    (MFA/acoustic_modeling/triphone.py:181-187) — a ``stats.TreeStats``, which adds (``+=``) as the reference's per-job
+    dicts are merged.  Utterances are batched onto the device (``stats.tree_statistics``), the batches merged on the host in
+    order.  ``skipped`` counts the utterances whose alignment does not split into phones."""
+
+    def __init__(self, acoustic_model_path, context_independent_symbols: Sequence[int] = (), context_width: int = 3,
+                 central_position: int = 1, batch_frames: int = 500_000):
+        if (int(context_width), int(central_position)) != (3, 1):
+            raise ValueError(f"TreeStatsAccumulator: context width {context_width} with central position {central_position}: only 3 and 1")
+        self.acoustic_model_path = acoustic_model_path
+        self.transition_model, self.acoustic_model = _read_model(acoustic_model_path)
+        self.context_independent_symbols = [int(p) for p in context_independent_symbols]
+        self.batch_frames = int(batch_frames)
+        self.tree_stats = None
+        self.skipped = 0
+
+    def accumulate_stats(self, feature_archive, alignment_archive, callback=None) -> None:
+        import torch
+        from .stats import tree_statistics
+
+        eng = get_engine()
+        tm = self.transition_model
+        feats = dict(feature_archive) if not isinstance(feature_archive, dict) else feature_archive
+        rows, alis, total = [], [], 0
+
+        def flush():
+            nonlocal rows, alis, total
+            if rows:
+                fo = np.concatenate([[0], np.cumsum([a.shape[0] for a in alis])]).astype(np.int64)
+                st, _frame_event, skipped = tree_statistics(
+                    eng, torch.from_numpy(np.concatenate(rows).astype(np.float32)).to(eng.device), fo,
+                    torch.from_numpy(np.concatenate(alis).astype(np.int32)).to(eng.device), tm, self.context_independent_symbols)
+                self.skipped += skipped
+                if self.tree_stats is None:
+                    self.tree_stats = st
+                else:
+                    self.tree_stats += st
+            rows, alis, total = [], [], 0
+
+        for al in alignment_archive:
+            x = feats.get(al.utterance_id)
+            if x is None:
+                continue
+            a = np.asarray(al.alignment, dtype=np.int32)
+            if a.shape[0] != x.shape[0]:
+                logger.warning("utterance %s: %d alignment entries for %d frames, skipped", al.utterance_id, a.shape[0], x.shape[0])
+                continue
+            rows.append(np.asarray(x)); alis.append(a); total += a.shape[0]
+            if callback:
+                callback(al.utterance_id)
+            if total >= self.batch_frames:
+                flush()
+        flush()
+
+
+def automatically_obtain_questions(tree_stats, phone_sets, pdf_classes=(1,), position: int = 1):
+    """``_kalpy.tree.automatically_obtain_questions(tree_stats, phone_sets, [1], 1)`` (MFA/acoustic_modeling/triphone.py:402):
+    ``tree.automatic_questions`` — bottom-up clustering, not Kaldi's seeded top-down one."""
+    from . import tree as _tree
+    return _tree.automatic_questions(tree_stats, phone_sets, tuple(pdf_classes), int(position))
+
+
+def read_roots(path) -> List[Tuple[List[int], bool, bool]]:
+    """The reference's ``roots.int`` (MFA/dictionary/mixins.py:845-879): lines of ``shared|not-shared split|not-split`` and
+    phone ids, as ``tree.build_tree`` takes them."""
+    roots = []
+    for line in Path(path).read_text().splitlines():
+        f = line.split()
+        if not f:
+            continue
+        if f[0] not in ("shared", "not-shared") or len(f) < 3 or f[1] not in ("split", "not-split"):
+            raise ValueError(f"roots file {path}: bad line {line!r}")
+        roots.append(([int(p) for p in f[2:]], f[0] == "shared", f[1] == "split"))
+    return roots
+
+
+def build_tree(topo, questions, tree_stats, roots_path, tree_path, max_leaves: int = 1000, cluster_thresh: float = -1.0):
+    """``_kalpy.tree.build_tree(topo, questions, tree_stats, roots_int_path, tree_path, max_leaves=, cluster_thresh=)``
+    (MFA/acoustic_modeling/triphone.py:417): ``tree.build_tree`` on the roots file, the tree written to ``tree_path``.  Also
+    returns the record of splits and merges."""
+    from . import tree as _tree
+    t, record = _tree.build_tree(topo, questions, tree_stats, read_roots(roots_path), max_leaves=int(max_leaves),
+                                 cluster_thresh=float(cluster_thresh))
+    with open(tree_path, "wb") as f:
+        kaldi_io.write_tree(f, t)
+    return record
+
+
+def gmm_init_model(topo, tree, tree_stats, model_path, mixup: int = 0, mixdown: int = 0, var_floor: float = 0.01) -> None:
+    """``_kalpy.gmm.gmm_init_model(topo, tree, tree_stats, model_path, mixup=, mixdown=)`` (MFA/acoustic_modeling/triphone.py:
+    455): ``tree.init_model`` written to ``model_path``; with ``mixup`` above the number of leaves, ``mle.mix_up`` to that
+    many Gaussians on the leaves' frame counts.  ``mixdown`` is not built."""
+    from . import mle
+    from . import tree as _tree
+
+    if mixdown:
+        raise NotImplementedError("gmm_init_model: mixdown is not built")
+    raw_tm, raw_am = _tree.init_model(topo, tree, tree_stats, var_floor=var_floor)
+    if mixup and int(mixup) > raw_am.num_pdfs:
+        leaf = _tree.event_leaves(tree, tree_stats)
+        occ = np.bincount(leaf[leaf >= 0], weights=tree_stats.count[leaf >= 0].astype(np.float64), minlength=raw_am.num_pdfs)
+        raw_am, _targets = mle.mix_up(raw_am, occ, int(mixup))
+    with open(model_path, "wb") as f:
+        kaldi_io.write_model(f, raw_tm, raw_am)
+
+
+def gmm_init_model_from_previous(*args, **kwargs):
+    """``_kalpy.gmm.gmm_init_model_from_previous`` (two-level trees): not built."""
+    raise NotImplementedError("gmm_init_model_from_previous is not built")
+
+
+def convert_alignments(old_transition_model, new_transition_model, tree, alignment) -> List[int]:
+    """``_kalpy.hmm.convert_alignments(old_transition_model, new_transition_model, tree, alignment)`` (MFA/acoustic_modeling/
+    triphone.py:112): one utterance's transition-ids on the new model and tree — the same phones, states and arcs, the pdfs of
+    the windows the alignment itself spells (``tree.convert_table`` over the host twin of the tree statistics).  Raises when
+    the alignment does not split into phones."""
+    from . import tree as _tree
+    from .stats import tree_statistics_host
+
+    a = np.asarray(alignment, dtype=np.int32)
+    st, frame_event, skipped = tree_statistics_host(np.zeros((a.shape[0], 1), np.float32), np.array([0, a.shape[0]], dtype=np.int64),
+                                                    a, old_transition_model, ())
+    if skipped:
+        raise ValueError("convert_alignments: the alignment does not split into phones")
+    table = _tree.convert_table(old_transition_model, new_transition_model, tree, st)
+    return _tree.convert_alignments(table, _tree.local_of_tid(old_transition_model), frame_event, a).tolist()
+
+
 def write_gmm_model(path, transition_model, acoustic_model) -> None:
     """``kalpy.gmm.utils.write_gmm_model(path, transition_model, acoustic_model)`` for the objects ``read_gmm_model``
     returns (the mixture weights are the model's own when it was read from a file)."""

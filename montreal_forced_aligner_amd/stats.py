@@ -4,6 +4,7 @@ and the loaded ``gmm``.
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
@@ -507,3 +508,195 @@ def mllt_statistics_host(gmm: DiagGmmModel, feats: np.ndarray, ali: np.ndarray, 
         raise _lib.MfaHipError(f"mfa_debug_mllt_acc_host: {why}")
     st._dev = None                # the host arrays are the value now
     return (st, post) if want_post else st
+
+
+TREE_NO_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)
+TREE_MAX_PHONES, TREE_MAX_CLASSES = 1 << 16, 256
+
+
+def tree_key(left, centre, right, pdf_class) -> np.ndarray:
+    """The event key of include/mfa_hip.h ("Tree statistics"): l << 48 | c << 28 | r << 8 | pc, uint64."""
+    l, c, r, pc = (np.asarray(a, dtype=np.uint64) for a in (left, centre, right, pdf_class))
+    return (l << np.uint64(48)) | (c << np.uint64(28)) | (r << np.uint64(8)) | pc
+
+
+@dataclass
+class TreeStats:
+    """Tree statistics (mfa_tree_acc_batch; Kaldi acc-tree-stats): per event — (left, centre, right) phone window and
+    pdf-class, packed in ``keys`` [E] uint64 ascending — int64 ``count`` [E] and float64 ``sum`` / ``sumsq`` [E, dim].
+    Additive: ``a += b`` merges by key, float64 addition in call order."""
+
+    keys: np.ndarray
+    count: np.ndarray
+    sum: np.ndarray
+    sumsq: np.ndarray
+
+    @classmethod
+    def zeros(cls, dim: int) -> "TreeStats":
+        return cls(np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.int64), np.zeros((0, dim)), np.zeros((0, dim)))
+
+    def copy(self) -> "TreeStats":
+        return TreeStats(self.keys.copy(), self.count.copy(), self.sum.copy(), self.sumsq.copy())
+
+    @property
+    def dim(self) -> int:
+        return int(self.sum.shape[1])
+
+    @property
+    def num_events(self) -> int:
+        return int(self.keys.shape[0])
+
+    def windows(self) -> np.ndarray:
+        """[E, 3] int32: left, centre and right phone of every event."""
+        k = self.keys
+        return np.stack([k >> np.uint64(48), (k >> np.uint64(28)) & np.uint64(0xFFFFF), (k >> np.uint64(8)) & np.uint64(0xFFFFF)],
+                        axis=1).astype(np.int32)
+
+    def pdf_classes(self) -> np.ndarray:
+        """[E] int32: the pdf-class of every event."""
+        return (self.keys & np.uint64(0xFF)).astype(np.int32)
+
+    def __iadd__(self, other: "TreeStats") -> "TreeStats":
+        if self.dim != other.dim:
+            raise ValueError("TreeStats of different feature dimensions cannot be added")
+        keys = np.union1d(self.keys, other.keys)
+        a, b = np.searchsorted(keys, self.keys), np.searchsorted(keys, other.keys)
+        count = np.zeros(keys.shape[0], dtype=np.int64)
+        s, q = np.zeros((keys.shape[0], self.dim)), np.zeros((keys.shape[0], self.dim))
+        count[a] = self.count
+        s[a], q[a] = self.sum, self.sumsq
+        count[b] += other.count
+        s[b] += other.sum
+        q[b] += other.sumsq
+        self.keys, self.count, self.sum, self.sumsq = keys, count, s, q
+        return self
+
+
+def tree_tid_tables(tm: TransitionModel, ci_phones: Sequence[int]):
+    """The host-built tables of the tree statistics: per transition-id (int32 [transition-ids + 1]; index 0 unused) its phone,
+    the pdf-class of its arc (the state's self-loop pdf-class for a self-loop, its forward pdf-class otherwise) and its flags
+    (1: final, 2: self-loop); and uint8 [phones + 1] marking the context-independent phones.  Built once per transition
+    model and set of context-independent phones, and kept on the model (it is called for every batch)."""
+    cache = tm.__dict__.setdefault("_tree_tables", {})
+    cache_key = tuple(sorted(int(p) for p in ci_phones))
+    if cache_key in cache:
+        return cache[cache_key]
+    n = int(tm.id2phone.shape[0])
+    phone = np.ascontiguousarray(tm.id2phone, dtype=np.int32)
+    flags = np.ascontiguousarray((tm.is_final != 0) * 1 + (tm.is_self_loop != 0) * 2, dtype=np.int32)
+    # the two pdf-classes of every transition-state (row 0 unused), then one gather over the transition-ids
+    state_cls = np.zeros((tm.tuples.shape[0] + 1, 2), dtype=np.int32)
+    for ts, row in enumerate(tm.tuples, start=1):
+        st = tm.topo.entry_for_phone(int(row[0]))[int(row[1])]
+        state_cls[ts] = (st.forward_pdf_class, st.self_loop_pdf_class)
+    cls = np.ascontiguousarray(state_cls[tm.id2state, (tm.is_self_loop != 0).astype(np.int64)], dtype=np.int32)
+    cls[0] = 0
+    n_phones = int(max(int(phone.max()) if n > 1 else 0, int(np.max(tm.topo.phones)) if len(tm.topo.phones) else 0))
+    if n_phones >= TREE_MAX_PHONES:
+        raise _lib.MfaHipError(f"tree statistics: phone id {n_phones} (the event key holds phone ids below {TREE_MAX_PHONES})")
+    if n > 1 and (int(cls[1:].max()) >= TREE_MAX_CLASSES or int(cls[1:].min()) < 0):
+        raise _lib.MfaHipError(f"tree statistics: pdf-class outside [0, {TREE_MAX_CLASSES})")
+    ci = np.zeros(n_phones + 1, dtype=np.uint8)
+    for p in ci_phones:
+        if not 0 < int(p) <= n_phones:
+            raise _lib.MfaHipError(f"tree statistics: context-independent phone {int(p)} is not a phone of the model")
+        ci[int(p)] = 1
+    cache[cache_key] = (phone, cls, flags, ci)
+    return cache[cache_key]
+
+
+def _tree_device_tables(engine, tm: TransitionModel, ci_phones: Sequence[int]):
+    """``tree_tid_tables`` with their copies on the engine's device, uploaded once per model."""
+    tables = tree_tid_tables(tm, ci_phones)
+    cache = tm.__dict__.setdefault("_tree_device_tables", {})
+    key = (str(engine.device), id(tables))
+    if key not in cache:
+        cache[key] = tuple(torch.from_numpy(a).to(engine.device) for a in tables)
+    return tables, cache[key]
+
+
+def _tree_check(what, feat_shape, frame_off, n_ali, context_width, central_position):
+    if (int(context_width), int(central_position)) != (3, 1):
+        raise _lib.MfaHipError(f"{what}: context width {context_width} with central position {central_position}: only 3 and 1")
+    frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+    if frame_off.ndim != 1 or frame_off.shape[0] < 1 or frame_off[0] != 0 or np.any(np.diff(frame_off) < 0):
+        raise _lib.MfaHipError(f"{what}: frame offsets must start at 0 and ascend")
+    total = int(frame_off[-1])
+    if len(feat_shape) != 2 or feat_shape[0] != total or n_ali != total:
+        raise _lib.MfaHipError(f"{what}: features {tuple(feat_shape)} and {n_ali} alignment frames for {total} frames")
+    return frame_off, len(frame_off) - 1, total
+
+
+def _elem_ptr(t: torch.Tensor, index: int):
+    """Element ``index`` of a 1-D tensor as the pointer argument of a library call."""
+    return ctypes.c_void_p(t.data_ptr() + index * t.element_size())
+
+
+def tree_statistics(engine, feats: torch.Tensor, frame_off: np.ndarray, ali: torch.Tensor, tm: TransitionModel,
+                    ci_phones: Sequence[int] = (), context_width: int = 3, central_position: int = 1, cap: Optional[int] = None):
+    """Tree statistics of one batch from its alignments (mfa_tree_acc_batch; the contract is in include/mfa_hip.h).
+
+    ``feats`` float32 [ΣT, dim] and ``ali`` int32 [ΣT] transition-ids on the device; ``ci_phones``: the context-independent
+    phones (the reference passes silence and OOV phones).  Returns (``TreeStats`` of the batch, ``frame_event`` int32 [ΣT] on
+    the device: every frame's row in ``TreeStats.keys`` or −1, the number of utterances skipped).  ``cap``: event rows to
+    offer first (default: what the engine's last call needed); the call is repeated when the batch has more."""
+    frame_off, n_utt, total = _tree_check("tree_statistics", feats.shape, frame_off, int(ali.shape[0]), context_width, central_position)
+    if feats.dtype != torch.float32 or not feats.is_cuda or not ali.is_cuda:
+        raise _lib.MfaHipError("tree_statistics: features must be float32 and, like the alignments, on the device")
+    dev = engine.device
+    dim = int(feats.shape[1])
+    (phone, cls, flags, ci), (d_phone, d_cls, d_flags, d_ci) = _tree_device_tables(engine, tm, ci_phones)
+    feats = feats.contiguous()
+    ali = ali.to(torch.int32).contiguous()
+    d_fo = engine._dev(frame_off)
+    frame_event = torch.empty(total, dtype=torch.int32, device=dev)
+    scal = torch.zeros(2, dtype=torch.int64, device=dev)               # n_events, skipped
+    cap = int(cap) if cap is not None else int(getattr(engine, "_tree_cap", 4096))
+    while True:
+        key = torch.empty(cap, dtype=torch.int64, device=dev)
+        cnt = torch.empty(cap, dtype=torch.int64, device=dev)
+        s = torch.empty((cap, dim), dtype=torch.float64, device=dev)
+        q = torch.empty((cap, dim), dtype=torch.float64, device=dev)
+        check(engine.ctx, engine.lib.mfa_tree_acc_batch(engine.ctx, _ptr(feats), _ptr(d_fo), n_utt, total, dim, _ptr(ali), _ptr(d_phone),
+                                                         _ptr(d_cls), _ptr(d_flags), int(phone.shape[0]), _ptr(d_ci), int(ci.shape[0]) - 1,
+                                                         cap, _ptr(frame_event), _elem_ptr(scal, 0), _elem_ptr(scal, 1),
+                                                         _ptr(key) if cap else None, _ptr(cnt) if cap else None,
+                                                         _ptr(s) if cap else None, _ptr(q) if cap else None), "mfa_tree_acc_batch")
+        n_events, skipped = (int(v) for v in scal.cpu().numpy())
+        if n_events <= cap:
+            break
+        cap = n_events + n_events // 8
+    engine._tree_cap = max(cap, 4096)
+    st = TreeStats(key[:n_events].cpu().numpy().view(np.uint64), cnt[:n_events].cpu().numpy(), s[:n_events].cpu().numpy(),
+                   q[:n_events].cpu().numpy())
+    return st, frame_event, skipped
+
+
+def tree_statistics_host(feats: np.ndarray, frame_off: np.ndarray, ali: np.ndarray, tm: TransitionModel,
+                         ci_phones: Sequence[int] = (), context_width: int = 3, central_position: int = 1):
+    """The same call on the host twin (mfa_debug_tree_acc_host: no device, every event one loop in ascending frame index): the
+    specification the device is held to.  numpy arrays in; ``frame_event`` comes back as a numpy array."""
+    lib = _lib.lib()
+    feats = np.ascontiguousarray(feats, dtype=np.float32)
+    ali = np.ascontiguousarray(ali, dtype=np.int32)
+    frame_off, n_utt, total = _tree_check("tree_statistics_host", feats.shape, frame_off, int(ali.shape[0]), context_width, central_position)
+    dim = int(feats.shape[1])
+    phone, cls, flags, ci = tree_tid_tables(tm, ci_phones)
+    frame_event = np.empty(total, dtype=np.int32)
+    scal = np.zeros(2, dtype=np.int64)
+    cap = 0
+    while True:
+        key, cnt = np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.int64)
+        s, q = np.empty((cap, dim)), np.empty((cap, dim))
+        p = lambda a: a.ctypes.data if a.size else None
+        rc = lib.mfa_debug_tree_acc_host(p(feats), frame_off.ctypes.data, n_utt, dim, p(ali), phone.ctypes.data, cls.ctypes.data,
+                                         flags.ctypes.data, int(phone.shape[0]), ci.ctypes.data, int(ci.shape[0]) - 1, cap,
+                                         p(frame_event), scal.ctypes.data, scal.ctypes.data + 8, p(key), p(cnt), p(s), p(q))
+        if rc != 0:
+            why = {-2: "feature dimension above 48", -3: "2^31 frames or more", -4: "2^16 phones or more"}.get(rc, "bad arguments")
+            raise _lib.MfaHipError(f"mfa_debug_tree_acc_host: {why}")
+        n_events, skipped = int(scal[0]), int(scal[1])
+        if n_events <= cap:
+            break
+        cap = n_events
+    return TreeStats(key[:n_events], cnt[:n_events], s[:n_events], q[:n_events]), frame_event, skipped

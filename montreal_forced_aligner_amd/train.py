@@ -9,11 +9,13 @@ labels — ``final.mdl`` and ``tree`` out.
                 ``mle.mle_update`` → ``mle.mix_up`` to the current target; the target grows by ``gaussian_increment`` while
                 i <= ``final_gaussian_iteration``
 
-``LdaTrainer`` (below) is the LDA stage on a fixed tree: the previous model's alignments → LDA statistics and estimate → one
+``TriphoneTrainer`` (below) builds a tree from the previous model's alignments — tree statistics on the device, questions, tree
+and initial model on the host (``tree``) — and trains on it.  ``LdaTrainer`` is the LDA stage, on the tree it is given or on
+one it builds the same way: the previous model's alignments → LDA statistics and estimate → one
 Gaussian per pdf on the splice + LDA features → the same loop, shared through ``GmmTrainerBase``.
 
-The device is driven through a backend of three calls — ``equal_align``, ``align``, ``accumulate`` — so that the same loop
-runs on the host twins in tests.  ``DeviceBackend`` is ``CorpusAligner``'s machinery: features, CMVN and graphs as ``align``
+The device is driven through a backend of three calls — ``equal_align``, ``align``, ``accumulate``, and for the tree
+``tree_accumulate`` and ``convert_alignments`` — so that the same loop runs on the host twins in tests.  ``DeviceBackend`` is ``CorpusAligner``'s machinery: features, CMVN and graphs as ``align``
 makes them, ``_align(..., keep_last=True)`` for features and alignments that stay on the device, ``gmm_statistics(into=)``.
 """
 from __future__ import annotations
@@ -59,6 +61,7 @@ class DeviceBackend:
         self.al = None
         self.lda: Optional[np.ndarray] = None     # LdaDeviceBackend sets it: the aligner's features are then splice + LDA
         self.kept: List[tuple] = []          # per batch (utterance indices, features, alignments, frame offsets, speaker rows)
+        self.tree_batches: List[tuple] = []  # per batch (its TreeStats, frame_event) of the last ``tree_accumulate``
         self.dim = 3 * int(self.mfcc_options.get("num_coefficients", 13))
 
     def _aligner(self, raw_tm, raw_am, tree):
@@ -115,6 +118,25 @@ class DeviceBackend:
             gmm_statistics(al.engine, feats, ali, tm, into=st)
         return st
 
+    def tree_accumulate(self, raw_tm, ci_phones: Sequence[int]):
+        """Tree statistics of the resident features and alignments (``CorpusAligner._tree_accumulate``): (``TreeStats`` of the
+        corpus, utterances skipped).  Every batch's own statistics and ``frame_event`` stay for ``convert_alignments``."""
+        stats, self.tree_batches, skipped = self.al._tree_accumulate(self.kept, ci_phones)
+        return stats, skipped
+
+    def convert_alignments(self, old_raw_tm, raw_tm, raw_am, tree) -> None:
+        """The resident alignments moved onto the new model's transition-ids, in place — a gather through
+        ``tree.convert_table`` per batch, on the device — and a new aligner on the new tree; the resident features stay."""
+        from . import tree as _tree
+
+        old_tm, new_tm = TransitionModel(old_raw_tm), TransitionModel(raw_tm)
+        local = _tree.local_of_tid(old_tm)
+        self.kept = [(idx, feats, _tree.convert_alignments(_tree.convert_table(old_tm, new_tm, tree, st), local, fe, ali), fo, rows)
+                     for (idx, feats, ali, fo, rows), (st, fe) in zip(self.kept, self.tree_batches)]
+        self.tree_batches = []
+        self.al = None
+        self._aligner(raw_tm, raw_am, tree)
+
     def alignments(self) -> List[np.ndarray]:
         """The resident alignments on the host, by utterance (zeros where an utterance failed)."""
         out: List[Optional[np.ndarray]] = [None] * len(self.utts)
@@ -123,6 +145,46 @@ class DeviceBackend:
             for k, i in enumerate(idx):
                 out[i] = a[int(fo[k]): int(fo[k + 1])]
         return out
+
+
+def previous_models(previous):
+    """``previous`` of a stage as (raw_tm, raw_am, tree): the tuple itself, or a trained stage."""
+    if hasattr(previous, "raw_tm"):
+        return (previous.raw_tm, previous.raw_am, previous.tree)
+    return tuple(previous)
+
+
+def default_roots(topology: kaldi_io.HmmTopology, shared_phones, silence_phones: Sequence[int]):
+    """The reference's ``roots.int`` (MFA/dictionary/mixins.py:845-879): one root per ``mle.phone_sets`` entry, shared and
+    split — the silence phones' not shared and not split."""
+    sil = set(int(p) for p in silence_phones)
+    return [(s, False, False) if sil & set(s) else (s, True, True) for s in mle.phone_sets(topology, shared_phones)]
+
+
+def tree_stage(backend, prev_tm, topology, roots, shared_phones, ci_phones, extra_questions, num_leaves: int,
+               cluster_threshold: float):
+    """Tree statistics of the resident alignments → questions (the automatic ones, then ``extra_questions``) → tree →
+    ``init_model`` → the alignments converted in place and a new aligner on the new tree.  Returns (raw_tm, raw_am, tree,
+    what the stage's ``history`` entry carries)."""
+    from . import tree as _tree
+
+    stats, skipped = backend.tree_accumulate(prev_tm, ci_phones)
+    if stats is None or stats.num_events == 0:
+        raise ValueError("tree building: the previous model's alignments gave no tree statistics")
+    questions = _tree.automatic_questions(stats, mle.phone_sets(topology, shared_phones))
+    seen = {tuple(q) for q in questions}
+    for q in extra_questions:
+        q = sorted(int(p) for p in q)
+        if tuple(q) not in seen:
+            seen.add(tuple(q))
+            questions.append(q)
+    roots = list(roots) if roots is not None else default_roots(topology, shared_phones, ci_phones)
+    tree, record = _tree.build_tree(topology, questions, stats, roots, max_leaves=num_leaves, cluster_thresh=cluster_threshold)
+    raw_tm, raw_am = _tree.init_model(topology, tree, stats)
+    backend.convert_alignments(prev_tm, raw_tm, raw_am, tree)
+    info = dict(events=stats.num_events, leaves=record["leaves"], skipped=int(skipped), questions=len(questions),
+                tree_gain_per_frame=(record["total_gain"] - record["merge_loss"]) / record["frames"])
+    return raw_tm, raw_am, tree, dict(info, tree_stats=stats, tree_record=record)
 
 
 class GmmTrainerBase:
@@ -267,7 +329,90 @@ class MonophoneTrainer(GmmTrainerBase):
                              raw_am=self.raw_am, **kw)
 
 
-# ---- the LDA stage on a fixed tree ----------------------------------------------------------------------------------------------
+# ---- the triphone stage -----------------------------------------------------------------------------------------------------------
+class TriphoneTrainer(GmmTrainerBase):
+    """The reference's ``TriphoneTrainer`` (MFA/acoustic_modeling/triphone.py): context-dependent models on a tree built here.
+    ``TriphoneTrainer(utterances, lexicon, previous=(raw_tm, raw_am, tree)).train()`` then ``write(directory)`` / ``aligner()``;
+    ``previous`` may also be the trained stage itself.
+
+      iteration 0   align with ``previous`` → tree statistics of those alignments on the device (``stats.tree_statistics``,
+                    context-independent: the silence phones) → ``tree.automatic_questions`` with ``extra_questions`` appended →
+                    ``tree.build_tree`` (``roots``; default ``default_roots``) → ``tree.init_model`` → a new aligner on the new
+                    tree, the resident features kept → the alignments converted in place (``tree.convert_table``, a gather on
+                    the device) → GMM statistics under the initial model, transition update, ``mle_update``
+      iteration i   ``GmmTrainerBase._iterate``
+
+    Options carry the reference's names and defaults (triphone.py:213-234): ``num_iterations`` 35, ``num_leaves`` 1000,
+    ``max_gaussians`` 10000, ``cluster_threshold`` −1, ``boost_silence`` 1.25 (in ``align_options``), ``power`` 0.25;
+    realignment at every tenth iteration, ``final_gaussian_iteration`` = ``num_iterations`` − 10, ``initial_gaussians`` = the
+    number of leaves built.  ``history`` as ``MonophoneTrainer``'s; iteration 0's entry also carries ``events``, ``leaves``,
+    ``questions``, ``tree_gain_per_frame`` and ``skipped``.  ``tree_stats``, ``tree_record`` and ``questions`` are kept."""
+
+    def __init__(self, utterances=None, lexicon=None, previous=None, roots=None, extra_questions: Sequence[Sequence[int]] = (),
+                 num_iterations: int = 35, num_leaves: int = 1000, max_gaussians: int = 10000, cluster_threshold: float = -1.0,
+                 power: float = 0.25, align_options=None, seed: int = 1234, min_gaussian_occupancy: float = 3.0,
+                 shared_phones: Optional[Sequence[Sequence[int]]] = None, silence_phones: Sequence[int] = (),
+                 mfcc_options: Optional[dict] = None, device: int = 0, engine=None, backend=None,
+                 context_width: int = 3, central_position: int = 1):
+        from .aligner import AlignOptions
+
+        if previous is None or lexicon is None:
+            raise ValueError("TriphoneTrainer needs a lexicon and the previous stage's (raw_tm, raw_am, tree)")
+        if num_iterations < 1 or num_leaves < 1:
+            raise ValueError("num_iterations and num_leaves must be at least 1")
+        if (int(context_width), int(central_position)) != (3, 1):
+            raise ValueError(f"TriphoneTrainer: context width {context_width} with central position {central_position}: only 3 and 1")
+        self.lexicon, self.previous = lexicon, previous_models(previous)
+        self.roots, self.extra_questions = roots, [list(q) for q in extra_questions]
+        self.num_iterations, self.num_leaves, self.max_gaussians = int(num_iterations), int(num_leaves), int(max_gaussians)
+        self.cluster_threshold, self.power, self.seed = float(cluster_threshold), float(power), int(seed)
+        self.min_gaussian_occupancy = float(min_gaussian_occupancy)
+        self.shared_phones = shared_phones
+        self.opt = align_options or AlignOptions(boost_silence=1.25)
+        self.silence_phones, self.mfcc_options = list(silence_phones), dict(mfcc_options or {})
+        self.backend = backend if backend is not None else DeviceBackend(utterances, lexicon, self.opt, self.mfcc_options,
+                                                                          self.silence_phones, device, engine)
+        self.raw_tm, self.raw_am, self.tree = self.previous
+        self.initial_gaussians = self.raw_am.num_pdfs           # until the tree is built
+        self.final_gaussian_iteration = self.num_iterations - 10
+        self.realignment_iterations = list(range(10, self.num_iterations, 10))
+        self.current_gaussians = self.initial_gaussians
+        self.rng = np.random.default_rng(self.seed)
+        self.history: List[Dict] = []
+        self.initial_stats: Optional[GmmStats] = None
+        self.tree_stats = None
+        self.tree_record: Optional[Dict] = None
+        self.iteration = 0
+
+    def train(self) -> "TriphoneTrainer":
+        b = self.backend
+        prev_tm, prev_am, prev_tree = self.previous
+        self.iteration = 0
+        failed = b.align(prev_tm, prev_am, prev_tree, self.opt.beam)
+        self.raw_tm, self.raw_am, self.tree, info = tree_stage(b, prev_tm, prev_tm.topo, self.roots, self.shared_phones,
+                                                               self.silence_phones, self.extra_questions, self.num_leaves,
+                                                               self.cluster_threshold)
+        self.tree_stats, self.tree_record = info.pop("tree_stats"), info.pop("tree_record")
+        self.initial_gaussians = self.current_gaussians = self.raw_am.num_pdfs
+        stats = b.accumulate(self.raw_tm, self.raw_am)
+        self.initial_stats = stats.copy()
+        self._update(stats, failed, True, min_gaussian_occupancy=self.min_gaussian_occupancy)
+        self.history[-1].update(info)
+        self._iterate(failed, self.opt.beam)
+        return self
+
+    def aligner(self, **kw):
+        """A ``CorpusAligner`` on the trained model (on the training engine when the device backend ran)."""
+        from .aligner import CorpusAligner
+
+        kw.setdefault("engine", getattr(self.backend, "engine", None))
+        kw.setdefault("options", self.opt)
+        return CorpusAligner(TransitionModel(self.raw_tm), DiagGmmModel.from_raw(self.raw_am), self.tree, self.lexicon,
+                             mfcc_options=self.mfcc_options, silence_phones=self.silence_phones, raw_tm=self.raw_tm,
+                             raw_am=self.raw_am, **kw)
+
+
+# ---- the LDA stage ----------------------------------------------------------------------------------------------------------------
 class LdaDeviceBackend(DeviceBackend):
     """``LdaTrainer``'s calls on the device: ``DeviceBackend``'s ``align`` / ``accumulate`` / ``alignments`` on splice + LDA
     features, and before them the previous model's alignments, the LDA statistics of those alignments
@@ -340,15 +485,21 @@ REFERENCE_MLLT_ITERATIONS = (2, 4, 6, 12)      # LdaTrainer.mllt_iterations of t
 
 
 class LdaTrainer(GmmTrainerBase):
-    """The reference's LDA+MLLT ``LdaTrainer`` (MFA/acoustic_modeling/lda.py) on the tree it is given — tree building is not
-    in this project.  ``LdaTrainer(utterances, lexicon, previous=(raw_tm, raw_am, tree)).train()`` then ``write(directory)``
-    (``final.mdl``, ``tree``, ``lda.mat``) / ``aligner()``.
+    """The reference's LDA+MLLT ``LdaTrainer`` (MFA/acoustic_modeling/lda.py): on the tree it is given, or — with
+    ``num_leaves`` — on a tree it builds itself as the reference's stage does (``_setup_tree``).
+    ``LdaTrainer(utterances, lexicon, previous=(raw_tm, raw_am, tree)).train()`` then ``write(directory)``
+    (``final.mdl``, ``tree``, ``lda.mat``) / ``aligner()``; ``previous`` may also be the trained stage itself.
 
       iteration 0   align with ``previous`` on its own features (Δ+ΔΔ, or splice + ``previous_lda``) → LDA statistics of
                     those alignments (classes are pdfs, silence weighs 0) → ``lda.estimate_lda`` → GMM statistics of the same
                     alignments on the splice + LDA features under a one-Gaussian-per-pdf model (the posterior is 1 whatever
                     its parameters) → every pdf at its own mean and variance (floored at ``mle.MIN_VARIANCE``; a pdf not
                     above ``min_gaussian_occupancy`` takes the global ones) → transition update, ``mle_update``, mix-up
+                    With ``num_leaves``, after the LDA estimate and before those GMM statistics: tree statistics of the same
+                    alignments on the splice + LDA features → questions → tree of at most ``num_leaves`` leaves →
+                    ``tree.init_model`` → the alignments converted (``tree_stage``, as ``TriphoneTrainer``'s iteration 0;
+                    ``roots``, ``extra_questions``, ``cluster_threshold`` as there).  The default ``num_leaves=None`` leaves
+                    the stage exactly as it is without.
       iteration i   ``MonophoneTrainer``'s loop (``GmmTrainerBase._iterate``); at an iteration of ``mllt_iterations``, after the
                     realignment if one is scheduled and before the GMM statistics (MFA/acoustic_modeling/lda.py:372-451):
                     MLLT statistics of the resident alignments (``backend.mllt_accumulate``: per-Gaussian full second
@@ -376,7 +527,9 @@ class LdaTrainer(GmmTrainerBase):
                  lda_dimension: int = 40, splice_context: int = 3, num_iterations: int = 35, max_gaussians: int = 15000,
                  power: float = 0.25, random_prune: float = 0.0, align_options=None, seed: int = 1234,
                  min_gaussian_occupancy: float = 3.0, silence_phones: Sequence[int] = (), mfcc_options: Optional[dict] = None,
-                 device: int = 0, engine=None, backend=None, mllt_iterations: Sequence[int] = (), mllt_sweeps: int = 200):
+                 device: int = 0, engine=None, backend=None, mllt_iterations: Sequence[int] = (), mllt_sweeps: int = 200,
+                 num_leaves: Optional[int] = None, roots=None, extra_questions: Sequence[Sequence[int]] = (),
+                 cluster_threshold: float = -1.0, shared_phones: Optional[Sequence[Sequence[int]]] = None):
         from . import _lib
         from .aligner import AlignOptions
 
@@ -391,7 +544,14 @@ class LdaTrainer(GmmTrainerBase):
         self.mllt_mats: List[np.ndarray] = []
         self.logdet_total = 0.0
         lib = _lib.lib()
-        self.lexicon, self.previous = lexicon, tuple(previous)
+        self.lexicon, self.previous = lexicon, previous_models(previous)
+        self.num_leaves = None if num_leaves is None else int(num_leaves)
+        if self.num_leaves is not None and self.num_leaves < 1:
+            raise ValueError("LdaTrainer: num_leaves must be at least 1")
+        self.roots, self.extra_questions = roots, [list(q) for q in extra_questions]
+        self.cluster_threshold, self.shared_phones = float(cluster_threshold), shared_phones
+        self.tree_stats = None
+        self.tree_record: Optional[Dict] = None
         self.previous_lda = None if previous_lda is None else np.asarray(previous_lda, dtype=np.float32)
         self.lda_dimension, self.splice_context = int(lda_dimension), int(splice_context)
         if self.lda_dimension < 1 or self.lda_dimension > int(lib.mfa_gmm_acc_max_dim()):
@@ -463,10 +623,20 @@ class LdaTrainer(GmmTrainerBase):
         self.raw_tm, self.tree = prev_tm, tree
         self.raw_am = self._unit_model(prev_am.num_pdfs)
         b.set_lda(self.lda_mat, self.raw_tm, self.raw_am, self.tree)
+        info = None
+        if self.num_leaves is not None:
+            self.raw_tm, _init_am, self.tree, info = tree_stage(b, prev_tm, prev_tm.topo, self.roots, self.shared_phones,
+                                                                self.silence_phones, self.extra_questions, self.num_leaves,
+                                                                self.cluster_threshold)
+            self.tree_stats, self.tree_record = info.pop("tree_stats"), info.pop("tree_record")
+            self.raw_am = self._unit_model(_init_am.num_pdfs)
+            self.initial_gaussians = self.current_gaussians = self.raw_am.num_pdfs
         stats = b.accumulate(self.raw_tm, self.raw_am)
         self.initial_stats = stats.copy()
         self.raw_am = self._pdf_start(stats)
         self._update(stats, failed, True, min_gaussian_occupancy=self.min_gaussian_occupancy)
+        if info:
+            self.history[-1].update(info)
         self._iterate(failed, self.opt.beam)
         return self
 
