@@ -143,10 +143,11 @@ ONE_HOT_SIZES = [1, 2, 5, 63, 64, 65, 128]
 
 
 @lru_cache(maxsize=None)
-def one_hot_case(dim, counts):
-    """Pdfs of ONE_HOT_SIZES Gaussians with ``counts`` frames; returns (case, gauss [T]: the Gaussian of every frame)."""
+def one_hot_case(dim, counts, sizes=None):
+    """Pdfs of ``sizes`` Gaussians (a tuple; default ONE_HOT_SIZES) with ``counts`` frames; returns (case, gauss [T]: the
+    Gaussian of every frame)."""
     rng = np.random.default_rng(9100 + dim)
-    sizes = ONE_HOT_SIZES
+    sizes = ONE_HOT_SIZES if sizes is None else list(sizes)
     P = len(sizes)
     assert len(counts) == P
     dev = 2.0 ** rng.integers(-1, 2, size=dim)

@@ -1,6 +1,7 @@
 """GMM statistics on the device (csrc/gmm_acc.hip: the lookup with its histograms, the ordering by pdf, gmm_acc_kernel and
 the two reductions) at the shapes where the kernels can go wrong: pdfs of 0, 1, C − 1, C, C + 1, 2C + 1 frames (C =
-mfa_gmm_acc_chunk_frames()), dims 13 – 48, pdfs of 1 – 128 Gaussians, frames shuffled across the batch.
+mfa_gmm_acc_chunk_frames()), dims 13 – 48, pdfs of 1 – 128 Gaussians, frames shuffled across the batch.  Key counts (hundreds and
+thousands of pdfs), pdfs of eight chunks and more and alignment-shaped frame orders are in tests/test_gpu_stats_scale.py.
 
 Three tiers.
 1. Single-Gaussian pdfs: e = expf(0) = 1, s = 1, 1/s = 1, so γ = w exactly; with weights 1 and ½ every product γ·x and γ·x² is

@@ -6,7 +6,8 @@ in double, so the device must give the restatement's bits whatever its summation
 instruction's operand and result layouts, of the clamped splice and of the tile mirror.  Soft tier: real features with
 per-speaker CMVN under the derived bound (2T + 2)·2⁻⁵³·Σ|terms|.  Shapes: the smallest at which each mechanism can go wrong —
 utterances of 1, 2, ctx, ctx + 1 frames and of slab − 1, slab, slab + 1; spliced widths that are no multiple of 16, one that
-is, and the widest; a class of chunk + 1 frames."""
+is, and the widest; a class of chunk + 1 frames.  Key counts (255 – 600 classes), classes of eight chunks and more and batches
+of nine slabs are in tests/test_gpu_stats_scale.py."""
 import dataclasses
 
 import numpy as np

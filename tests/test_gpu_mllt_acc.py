@@ -8,7 +8,8 @@ moment phases, and the reductions) against the host twin and the float64 restate
    with pdfs of more than one and more than two units: bit-equal to the twin.
 3. Soft posteriors: under the derived bound against the restatement, and against the twin under the two-implementations
    bound (13.5·ε32 per posterior, tests/test_gpu_gmm_acc.py's derivation, propagated through |d_i·d_j|, plus the double sums').
-occ and tot are held to mfa_gmm_acc_batch's bits on the same input."""
+occ and tot are held to mfa_gmm_acc_batch's bits on the same input.  Key counts (hundreds and thousands of pdfs) and pdfs of
+eight units and more are in tests/test_gpu_stats_scale.py."""
 import functools
 
 import numpy as np

@@ -5,7 +5,9 @@ Keys, ``frame_event``, ``n_events``, ``skipped`` and counts are equal outright. 
 every partial sum exact in double, so the device must give the twin's bits whatever its order; real features stay under the
 derived bound (2n + 2)·2⁻⁵³·Σ|terms| per event.  Shapes: the smallest at which each mechanism can go wrong — utterances of 0,
 1, 2, 63, 64, 65 and 129 frames (the 64-frame step of the key pass), one-frame phones, events of chunk − 1, chunk, chunk + 1
-and 2·chunk + 1 frames (the partial rows and their reduction), one event holding every frame, every frame its own event."""
+and 2·chunk + 1 frames (the partial rows and their reduction), one event holding every frame, every frame its own event.  Key
+widths (phone ids up to 65 535, pdf-classes up to 255), events of nine chunks and more and more events and units than the
+kernels have wavefronts are in tests/test_gpu_stats_scale.py."""
 import ctypes
 
 import numpy as np
