@@ -122,7 +122,7 @@ struct mfa_ctx {
   void *vit_stamps = nullptr;  // per-utterance phase cycle counters of the decoder (-DVIT_STAMPS builds)
   void *gmm_trace = nullptr;   // per-wavefront timeline records of the scoring kernel (mfa_debug_gmm_trace)
 
-  // d_ws is one scratch buffer shared by the CMVN (feats.hip), Viterbi (viterbi.hip), fMLLR statistics (fmllr.hip), GMM
+  // d_ws is one scratch buffer shared by the CMVN and feature (feats.hip), Viterbi (viterbi.hip), fMLLR statistics (fmllr.hip), GMM
   // statistics (gmm_acc.hip), feature codec (compress.hip), equal alignment (align_equal.hip), LDA statistics (lda_acc.hip),
   // MLLT statistics (mllt_acc.hip) and tree statistics (tree_acc.hip) stages: each lays its own workspace over it for the length of one call, and the order of
   // ctx->stream is all that keeps them apart.

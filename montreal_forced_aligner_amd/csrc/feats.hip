@@ -184,119 +184,195 @@ __global__ __launch_bounds__(256) void feats_kernel(FeatParams p) {
   }
 }
 
-// splice ±ctx → LDA → optional fMLLR with the matrix rows in REGISTERS.
-// Thread (o, g): output row o, frame group g; it keeps row o of the LDA matrix (kSdim spliced inputs) and of the speaker's
-// fMLLR matrix (kR inputs) in VGPRs for the whole tile, so a multiply-add costs one LDS read (the frame's input, a
-// broadcast to all rows) instead of the generic kernel's two.  The clamped halo rows make the spliced vector of frame r
-// the contiguous floats x[r·dim .. r·dim + sdim).  Same fmaf chains, same order, as feats_kernel and the oracle.
-// Round-1 measurement: 2.05 ms → 0.6 ms per 2M frames (13 → 40 dims, ±3 splice).
-constexpr int kTileLda = 128;   // frames per block of the register-row kernel
-// Round 2: one LDS read per multiply-add made the kernel LDS-issue-bound (91 ds_read_b32 per output and frame, the LDS pipe
-// shared by the CU's four SIMDs).  The base rows are now padded to 16 floats and the LDA outputs to 16-byte alignment, so a
-// spliced vector is read as 7 × (3 × 16 bytes + 4) and the fMLLR input as 10 × 16 bytes: 28 + 10 reads instead of 91 + 40,
-// the multiply-add chains in the same order (results unchanged).
-template <int kDim, int kCtx, int kR>   // exact base dimension, splice context and output rows: no bounds tests inside the unrolled chains
-__global__ __launch_bounds__(256) void feats_lda_kernel(FeatParams p) {
+// splice ±ctx → LDA → optional fMLLR with the FRAME in registers and the matrices as wavefront-uniform operands.
+// A lane owns a frame: it holds the frame's kSdim spliced, CMVN-offset inputs in VGPRs (read once from a coalesced LDS
+// tile; the clamped halo rows make the spliced vector of frame r the contiguous floats X[r·dim .. r·dim + sdim)), runs the
+// kR LDA chains over them, keeps the kR results in registers and runs the kR fMLLR chains over those.  The multipliers
+// are the same for every lane.  Output rows go in pairs (o, o + 1) on the packed FMA — two IEEE fused multiply-adds, so
+// every output keeps the fmaf chain of feats_kernel and the oracle, in the same order — which wants the two rows'
+// multipliers next to each other: both matrices are regrouped as [group of 8 rows][column][8 rows].
+//   LDA   (one per model, 14.7 KB): regrouped by feats_regroup_rows_kernel ahead of the launch, read with scalar loads
+//         into SGPRs — it stays in the 16 KB scalar cache and costs no LDS read at all.
+//   fMLLR (one per speaker, 6.5 KB): regrouped by the block into LDS and read with one address per wavefront, 16 bytes at
+//         a time.  Through the scalar cache as well it pushed the LDA matrix out (every block brings another speaker's):
+//         every scalar load then went to L2 and the kernel took 2.31 ms per 8 192-utterance step against 1.44 ms this way
+//         (DESIGN §4).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+constexpr int kTileRows = 256;  // frames per block of the frame-per-lane kernel: one per thread, 64 per wavefront
+constexpr int kRowGroup = 8;    // output rows whose chains run together: four packed accumulators
+
+// dst[(g·cols + d)·8 + j] = src[(8 g + j)·cols + d]: the columns of a group of eight rows, one after the other
+__global__ __launch_bounds__(256) void feats_regroup_rows_kernel(const float *__restrict__ src, int rows, int cols, float *__restrict__ dst) {
+  for (int i = threadIdx.x; i < rows * cols; i += blockDim.x) {
+    const int j = i % kRowGroup, d = (i / kRowGroup) % cols, g = i / (kRowGroup * cols);
+    dst[i] = src[(g * kRowGroup + j) * cols + d];
+  }
+}
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// a ← m · (x.lo, x.lo) + a, or with x.hi, on both halves: two IEEE fused multiply-adds.  m is a uniform pair of multipliers
+// (rows o, o + 1 at one column) in SGPRs.  Written as the instruction because the compiler, given the vector form, builds
+// every (x, x) pair in registers of its own, keeps them from one row group to the next and spills them.
+template <bool kHi>
+__device__ __forceinline__ void pk_fma_bcast(f32x2 &a, f32x2 m, f32x2 x) {
+  if (kHi) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0]" : "+v"(a) : "s"(m), "v"(x));
+  else asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(a) : "s"(m), "v"(x));
+}
+
+template <bool kHi>                                  // the same with the multipliers in VGPRs
+__device__ __forceinline__ void pk_fma_bcast_v(f32x2 &a, f32x2 m, f32x2 x) {
+  if (kHi) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0]" : "+v"(a) : "v"(m), "v"(x));
+  else asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(a) : "v"(m), "v"(x));
+}
+
+// Four columns of a regrouped matrix: [column][8 rows], 32 floats, two 64-byte scalar loads.
+struct RowSet { f32x16 lo, hi; };
+__device__ __forceinline__ RowSet load_row_set(const float *__restrict__ s, int set) {
+  const f32x16 *q = reinterpret_cast<const f32x16 *>(s + set * 4 * kRowGroup);
+  return RowSet{q[0], q[1]};
+}
+
+// The eight chains of one row group over kN inputs, a[q] = rows (2q, 2q + 1): acc = 0, fma over ascending columns, then the
+// offset column when there is one — feats_kernel's chain.  `s` is the group's [column][8 rows] block; `x` the inputs in
+// pairs (x[c/2] holds inputs c, c + 1).  The multipliers arrive a set of four columns ahead: scalar loads return out of
+// order, so the only wait there is waits for all of them, and the wait for a set is therefore written BEFORE the request
+// for the next one — the next set's latency then lies under this set's packed FMAs (the compiler moves the set's first
+// column across the wait; twelve of the sixteen FMAs remain).  The last set may reach up to three columns past the block:
+// loaded, not used (the workspace is padded for it).
+template <int kN>
+__device__ __forceinline__ void row_group_chains(const float *__restrict__ s, bool offset, const f32x2 *x, f32x2 (&a)[4]) {
+  constexpr int kSets = (kN + 1 + 3) / 4;
+#pragma unroll
+  for (int q = 0; q < 4; q++) a[q] = f32x2{0.0f, 0.0f};
+  RowSet cur = load_row_set(s, 0);
+#pragma unroll
+  for (int i = 0; i < kSets; i++) {
+    __builtin_amdgcn_s_waitcnt(0xc07f);              // lgkmcnt(0): `cur` is here
+    RowSet nxt = cur;
+    if (i + 1 < kSets) nxt = load_row_set(s, i + 1);
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const int col = 4 * i + c;
+      const f32x16 v = c < 2 ? cur.lo : cur.hi;
+      const int e = (c & 1) * kRowGroup;
+      const f32x2 m[4] = {{v[e], v[e + 1]}, {v[e + 2], v[e + 3]}, {v[e + 4], v[e + 5]}, {v[e + 6], v[e + 7]}};
+      if (col < kN) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          if (col & 1) pk_fma_bcast<true>(a[q], m[q], x[col / 2]);
+          else pk_fma_bcast<false>(a[q], m[q], x[col / 2]);
+        }
+      } else if (col == kN) {
+        if (offset)
+#pragma unroll
+          for (int q = 0; q < 4; q++) a[q] += m[q];
+      }
+    }
+    cur = nxt;
+  }
+}
+
+// The same chains with the group's block in LDS, read with one address for the whole wavefront, 16 bytes at a time.
+template <int kN>
+__device__ __forceinline__ void row_group_chains_lds(const float *s, const f32x2 *x, f32x2 (&a)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; q++) a[q] = f32x2{0.0f, 0.0f};
+#pragma unroll
+  for (int col = 0; col <= kN; col++) {
+    const float4 m01 = *reinterpret_cast<const float4 *>(s + col * kRowGroup);
+    const float4 m23 = *reinterpret_cast<const float4 *>(s + col * kRowGroup + 4);
+    const f32x2 m[4] = {{m01.x, m01.y}, {m01.z, m01.w}, {m23.x, m23.y}, {m23.z, m23.w}};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      if (col == kN) a[q] += m[q];
+      else if (col & 1) pk_fma_bcast_v<true>(a[q], m[q], x[col / 2]);
+      else pk_fma_bcast_v<false>(a[q], m[q], x[col / 2]);
+    }
+  }
+}
+
+template <int kDim, int kCtx, int kR>   // exact base dimension, splice context and output rows: the chains are fully unrolled
+__global__ __launch_bounds__(kTileRows, 3) void feats_rows_kernel(FeatParams p, const float *__restrict__ lda_p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int kSdim = (2 * kCtx + 1) * kDim;
-  constexpr int kXS = (kDim + 3) & ~3;               // row stride of the base-feature tile (16-byte aligned rows)
-  static_assert(kR % 4 == 0, "LDA output rows are read 16 bytes at a time");
+  constexpr int kGroups = kR / kRowGroup, kPairs = kRowGroup / 2;
+  static_assert(kR % kRowGroup == 0 && kPairs == 4, "output rows run in groups of eight");
   const int utt = blockIdx.y;
   const int64_t f0 = p.frame_off[utt];
   const int T = (int)(p.frame_off[utt + 1] - f0);
-  const int t0 = blockIdx.x * kTileLda;
+  const int t0 = blockIdx.x * kTileRows;
   if (t0 >= T) return;
-  constexpr int halo = kCtx, rows = kTileLda + 2 * halo;
-  constexpr int R = kR;
-  // X: [rows][kXS] CMVN-applied base features (frame t0-halo+r, clamped); later the staging area of the fMLLR matrix
-  // Y: staging area of the LDA matrix, then [kTileLda][R] LDA outputs (with fMLLR)
-  float *X = smem;
-  constexpr int x_floats = rows * kXS > R * (R + 1) ? rows * kXS : R * (R + 1);
-  float *Y = X + x_floats;
+  constexpr int rows = kTileRows + 2 * kCtx;
+  // X: [rows][kDim] CMVN-applied base features (frame t0-kCtx+r, clamped), then the kDim CMVN offsets.  Once every lane
+  // holds its inputs the whole of LDS is the staging area of the outputs, [wavefront][64 frames][kR].
+  // F: the speaker's fMLLR matrix, regrouped like the LDA matrix, behind the staging area.
+  float *X = smem, *off = smem + rows * kDim, *F = smem + kTileRows * kR;
   const int spk = p.utt2spk ? p.utt2spk[utt] : 0;
-  for (int i = threadIdx.x; i < rows * kDim; i += blockDim.x) {
+  if (p.fmllr) {
+    const float *fm = p.fmllr + (size_t)spk * kR * (kR + 1);
+    for (int i = threadIdx.x; i < kR * (kR + 1); i += kTileRows) {
+      const int j = i % kRowGroup, k = (i / kRowGroup) % (kR + 1), g = i / (kRowGroup * (kR + 1));
+      F[i] = fm[(g * kRowGroup + j) * (kR + 1) + k];
+    }
+  }
+  if (p.cmvn) {
+    if (threadIdx.x < kDim) {
+      const double *st = p.cmvn + (size_t)spk * 2 * (kDim + 1);
+      off[threadIdx.x] = (float)(-(st[threadIdx.x] / st[kDim]));
+    }
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < rows * kDim; i += kTileRows) {
     int r = i / kDim, d = i % kDim;
-    int t = t0 - halo + r;
+    int t = t0 - kCtx + r;
     t = t < 0 ? 0 : (t >= T ? T - 1 : t);
     float v = p.mfcc[(f0 + t) * kDim + d];
-    if (p.cmvn) {
-      const double *st = p.cmvn + (size_t)spk * 2 * (kDim + 1);
-      v += (float)(-(st[d] / st[kDim]));
-    }
-    X[r * kXS + d] = v;
+    if (p.cmvn) v += off[d];
+    X[i] = v;
   }
-  for (int i = threadIdx.x; i < R * p.lda_cols; i += blockDim.x) Y[i] = p.lda[i];   // coalesced; rows go to registers below
   __syncthreads();
-  constexpr int G = 256 / R;                         // frame groups
-  const int o = threadIdx.x % R, g = threadIdx.x / R;
-  const bool active = g < G;
+  f32x2 x[(kSdim + 1) / 2];                         // inputs in pairs: a packed FMA broadcasts either half
+  {
+    const float *xs = X + threadIdx.x * kDim;        // frames t-ctx .. t+ctx: rows r .. r+2·ctx of the tile (a frame past
+#pragma unroll                                       // the utterance's end reads clamped rows and is not stored)
+    for (int k = 0; k < kSdim; k++) x[k / 2][k & 1] = xs[k];
+    if (kSdim & 1) x[kSdim / 2][1] = 0.0f;
+  }
+  __syncthreads();                                   // X is dead
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int tw = t0 + 64 * wave;                     // the wavefront's first frame
+  if (tw >= T) return;
   const bool lda_offset = (p.lda_cols == kSdim + 1);
-  float m[kSdim];
+  f32x2 y[kR / 2];
 #pragma unroll
-  for (int k = 0; k < kSdim; k++) m[k] = Y[o * p.lda_cols + k];   // spare threads (g == G) read a valid row too
-  const float m_off = lda_offset ? Y[o * p.lda_cols + kSdim] : 0.0f;
-  __syncthreads();                                   // Y is free for the outputs
-  if (active) {
-    // two frames per trip (r and r + G): two independent multiply-add chains in flight per thread — each chain is the
-    // same 91 dependent fmaf's in the same order as before (results unchanged), but the VALU no longer waits on one
-    for (int r = g; r < kTileLda; r += 2 * G) {
-      const int t = t0 + r;
-      if (t >= T) break;
-      const int r2 = r + G;
-      const bool two = r2 < kTileLda && t0 + r2 < T;
-      const float *xa = X + r * kXS;                 // frames t-ctx .. t+ctx: rows r .. r+2·ctx of the tile
-      const float *xb = X + (two ? r2 : r) * kXS;
-      float acc = 0.0f, acc2 = 0.0f;
+  for (int g = 0; g < kGroups; g++) {
+    f32x2 a[kPairs];
+    row_group_chains<kSdim>(lda_p + (size_t)g * p.lda_cols * kRowGroup, lda_offset, x, a);
 #pragma unroll
-      for (int j = 0; j < 2 * kCtx + 1; j++) {
-        const float *xr = xa + j * kXS, *xr2 = xb + j * kXS;
-#pragma unroll
-        for (int d4 = 0; d4 + 4 <= kDim; d4 += 4) {
-          const float4 x4 = *reinterpret_cast<const float4 *>(xr + d4);
-          const float4 y4 = *reinterpret_cast<const float4 *>(xr2 + d4);
-          acc = fmaf(m[j * kDim + d4], x4.x, acc);      acc2 = fmaf(m[j * kDim + d4], y4.x, acc2);
-          acc = fmaf(m[j * kDim + d4 + 1], x4.y, acc);  acc2 = fmaf(m[j * kDim + d4 + 1], y4.y, acc2);
-          acc = fmaf(m[j * kDim + d4 + 2], x4.z, acc);  acc2 = fmaf(m[j * kDim + d4 + 2], y4.z, acc2);
-          acc = fmaf(m[j * kDim + d4 + 3], x4.w, acc);  acc2 = fmaf(m[j * kDim + d4 + 3], y4.w, acc2);
-        }
-#pragma unroll
-        for (int d = kDim & ~3; d < kDim; d++) { acc = fmaf(m[j * kDim + d], xr[d], acc); acc2 = fmaf(m[j * kDim + d], xr2[d], acc2); }
-      }
-      if (lda_offset) { acc += m_off; acc2 += m_off; }
-      if (p.fmllr) { Y[r * R + o] = acc; if (two) Y[r2 * R + o] = acc2; }
-      else { p.out[(f0 + t) * R + o] = acc; if (two) p.out[(f0 + t0 + r2) * R + o] = acc2; }
-    }
+    for (int q = 0; q < kPairs; q++) y[g * kPairs + q] = a[q];
   }
-  if (!p.fmllr) return;
-  __syncthreads();                                   // X is dead, Y complete
-  const float *fm = p.fmllr + (size_t)spk * R * (R + 1);
-  for (int i = threadIdx.x; i < R * (R + 1); i += blockDim.x) X[i] = fm[i];
-  __syncthreads();
-  if (!active) return;
-  float f[kR];
+  f32x2 *S = reinterpret_cast<f32x2 *>(smem + wave * 64 * kR) + lane * (kR / 2);
+  if (p.fmllr) {
 #pragma unroll
-  for (int k = 0; k < kR; k++) f[k] = X[o * (R + 1) + k];
-  const float f_off = X[o * (R + 1) + R];
-  for (int r = g; r < kTileLda; r += 2 * G) {        // two frames per trip, as above
-    const int t = t0 + r;
-    if (t >= T) break;
-    const int r2 = r + G;
-    const bool two = r2 < kTileLda && t0 + r2 < T;
-    const float *ys = Y + r * R, *ys2 = Y + (two ? r2 : r) * R;
-    float acc = 0.0f, acc2 = 0.0f;
+    for (int g = 0; g < kGroups; g++) {
+      f32x2 a[kPairs];
+      row_group_chains_lds<kR>(F + g * (kR + 1) * kRowGroup, y, a);
 #pragma unroll
-    for (int k = 0; k < kR; k += 4) {
-      const float4 y4 = *reinterpret_cast<const float4 *>(ys + k);
-      const float4 z4 = *reinterpret_cast<const float4 *>(ys2 + k);
-      acc = fmaf(f[k], y4.x, acc);          acc2 = fmaf(f[k], z4.x, acc2);
-      acc = fmaf(f[k + 1], y4.y, acc);      acc2 = fmaf(f[k + 1], z4.y, acc2);
-      acc = fmaf(f[k + 2], y4.z, acc);      acc2 = fmaf(f[k + 2], z4.z, acc2);
-      acc = fmaf(f[k + 3], y4.w, acc);      acc2 = fmaf(f[k + 3], z4.w, acc2);
+      for (int q = 0; q < kPairs; q++) S[g * kPairs + q] = a[q];
     }
-    acc += f_off; acc2 += f_off;
-    p.out[(f0 + t) * R + o] = acc;
-    if (two) p.out[(f0 + t0 + r2) * R + o] = acc2;
+  } else {
+#pragma unroll
+    for (int q = 0; q < kR / 2; q++) S[q] = y[q];
   }
+  // the wavefront's frames are kR·64 contiguous floats of the output: written as 16-byte segments, lane after lane
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const int nf = T - tw < 64 ? T - tw : 64;
+  const float4 *src = reinterpret_cast<const float4 *>(smem + wave * 64 * kR);
+  float4 *dst = reinterpret_cast<float4 *>(p.out + (f0 + tw) * kR);
+  for (int i = lane; i < nf * (kR / 4); i += 64) dst[i] = src[i];
 }
 
 // __constant__ data lives once per device: every context uploads for its own device (mfa_ctx::delta_uploaded).
@@ -356,11 +432,11 @@ MFA_API int mfa_feats_batch(mfa_ctx *c, const float *d_mfcc, const int64_t *d_fr
   p.dim = dim; p.mode = mode; p.ctx = splice_ctx; p.lda_rows = lda_rows; p.lda_cols = lda_cols;
   p.mfcc = d_mfcc; p.frame_off = d_frame_off; p.utt2spk = d_utt2spk; p.cmvn = d_cmvn; p.lda = d_lda; p.fmllr = d_fmllr;
   p.out = d_out;
-  // register-row kernel for MFA's standard shape (13 MFCCs spliced ±3 → 91, LDA to 40); other shapes take the generic kernel
+  // frame-per-lane kernel for MFA's standard shape (13 MFCCs spliced ±3 → 91, LDA to 40); other shapes take the generic kernel
   constexpr int kDim = 13, kCtx = 3, kR = 40;
   const char *generic = getenv("MFA_FEATS_GENERIC");
   const bool force_generic = generic && generic[0] == '1';
-  const bool register_rows = mode == 1 && dim == kDim && splice_ctx == kCtx && lda_rows == kR && !force_generic;
+  const bool frame_lanes = mode == 1 && dim == kDim && splice_ctx == kCtx && lda_rows == kR && !force_generic;
   size_t lds = 0;
   if (mode == 0) {
     lds = (size_t)(kTile + 8) * dim * 4;
@@ -378,18 +454,22 @@ MFA_API int mfa_feats_batch(mfa_ctx *c, const float *d_mfcc, const int64_t *d_fr
     lds = ((size_t)(kTile + 2 * splice_ctx) * dim + (size_t)lda_rows * lda_cols + (size_t)lda_rows * (lda_rows + 1) +
            (size_t)kTile * lda_rows) * 4;
     // kMaxDim × kMaxOut admit shapes whose tile does not fit a launch (16 dims, ±3, 64 rows: 66 KB)
-    if (lds > kMaxLdsBytes && !register_rows)
+    if (lds > kMaxLdsBytes && !frame_lanes)
       return c->fail("feats: base dim %d, splice ±%d, LDA %dx%d needs %zu bytes of LDS (a launch may ask for %zu)", dim,
                      splice_ctx, lda_rows, lda_cols, lds, kMaxLdsBytes);
   }
   dim3 grid((max_frames + kTile - 1) / kTile, n_utt);
+  // the regrouped LDA matrix of the frame-per-lane kernel, padded for the last set of columns it asks for
+  const size_t lda_p_floats = (size_t)kR * lda_cols + 3 * kRowGroup;
+  if (frame_lanes && c->d_ws.reserve(c, lda_p_floats * sizeof(float), "the regrouped LDA matrix")) return -1;
   KernelTimer kt(c, MFA_K_FEATS);
-  if (register_rows) {
-    const int rows = kTileLda + 2 * splice_ctx;
-    size_t x_floats = std::max((size_t)rows * ((kDim + 3) & ~3), (size_t)lda_rows * (lda_rows + 1));
-    size_t y_floats = std::max((size_t)kTileLda * lda_rows, (size_t)lda_rows * lda_cols);
-    dim3 grid2((max_frames + kTileLda - 1) / kTileLda, n_utt);
-    hipLaunchKernelGGL((feats_lda_kernel<kDim, kCtx, kR>), grid2, dim3(256), (x_floats + y_floats) * 4, c->stream, p);
+  if (frame_lanes) {
+    float *lda_p = c->d_ws.ptr<float>();
+    hipLaunchKernelGGL(feats_regroup_rows_kernel, dim3(1), dim3(256), 0, c->stream, d_lda, kR, lda_cols, lda_p);
+    const size_t lds_rows = ((size_t)kTileRows * kR + (size_t)kR * (kR + 1)) * sizeof(float);   // staging area + fMLLR matrix
+    static_assert((kTileRows + 2 * kCtx) * kDim + kDim <= kTileRows * kR, "the input tile lies inside the staging area");
+    dim3 grid2((max_frames + kTileRows - 1) / kTileRows, n_utt);
+    hipLaunchKernelGGL((feats_rows_kernel<kDim, kCtx, kR>), grid2, dim3(kTileRows), lds_rows, c->stream, p, lda_p);
   } else {
     hipLaunchKernelGGL(feats_kernel, grid, dim3(256), lds, c->stream, p);
   }

@@ -125,7 +125,7 @@ class PipelineReport:
         b = by.get(dominant, 0.0)
         gbs = b / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
         names = {"viterbi": "viterbi kernels (beam Viterbi, one wavefront per utterance)", "mfcc": "mfcc_kernel",
-                 "feats": "feats_lda_kernel / feats_kernel", "cmvn": "cmvn kernels"}
+                 "feats": "feats_rows_kernel / feats_kernel", "cmvn": "cmvn kernels"}
         out = {"kernel": names.get(dominant, dominant), "kernel_key": dominant, "bound": "hbm", "achieved": round(gbs, 2),
                "peak": 8000.0, "unit": "GB/s", "frac": round(gbs / 8000.0, 5), "traffic": None,
                "algorithmic_bytes_per_step": b, "ms_per_step": round(ms, 4), "launches_per_step": launches,

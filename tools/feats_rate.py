@@ -2,7 +2,7 @@
   delta             CMVN → Δ+ΔΔ                                   (the floor: no transform)
   delta_fmllr       CMVN → Δ+ΔΔ → fMLLR, in feats_kernel
   lda_fmllr_gen     CMVN → splice ±3 → LDA → fMLLR, generic kernel (MFA_FEATS_GENERIC=1)
-  lda_fmllr_reg     CMVN → splice ±3 → LDA → fMLLR, register-row  (the yardstick)
+  lda_fmllr_reg     CMVN → splice ±3 → LDA → fMLLR, frame-per-lane kernel (the yardstick)
 Every variant is warmed up, then the variants are launched in turn, ``--rounds`` times; the figure is the median of a
 variant's launches, timed by the library's event pair (mfa_kernel_timing / mfa_kernel_time_ms, which = 2).  GPU.
   python tools/feats_rate.py [--rounds 20] [--only delta] [--out profiles/feats_rate.json | --out '']
