@@ -81,6 +81,10 @@ MFA_API int32_t mfa_mfcc_num_frames(mfa_ctx *ctx, int64_t num_samples);
  * them with mfa_mfcc_num_frames); d_mfcc: float32 [total_frames][num_coefficients].  max_frames = longest utterance. */
 MFA_API int mfa_mfcc_batch(mfa_ctx *ctx, const int16_t *d_pcm, const int64_t *d_sample_off, const int64_t *d_frame_off,
                            int32_t n_utt, int32_t max_frames, float *d_mfcc);
+/* Which kernel tail the next mfa_mfcc_batch launches under the configured options: 1 the specialised one (compile-time
+ * trip counts; every filterbank plan whose bins have at most 8 pieces), 2 the generic one (any other plan, or
+ * MFA_MFCC_GENERIC=1 in the environment, read at every call; the bit reference), 0 before mfa_mfcc_configure. */
+MFA_API int mfa_mfcc_path(mfa_ctx *ctx);
 
 /* Host helper for the call above: utterance u's samples h_src[u][0 .. h_sample_off[u+1] - h_sample_off[u]) copied to
  * h_dst + h_sample_off[u] by n_threads host threads (<= 0: hardware concurrency).  h_dst is the caller's staging buffer

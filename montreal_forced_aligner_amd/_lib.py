@@ -135,6 +135,7 @@ SIGNATURES = {
     "mfa_mfcc_configure": (C.c_int, [_vp, C.POINTER(MfccOpts)]),
     "mfa_mfcc_num_frames": (_i32, [_vp, _i64]),
     "mfa_mfcc_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "mfa_mfcc_path": (C.c_int, [_vp]),
     "mfa_gather_pcm": (C.c_int, [_i32, _vp, _vp, _vp, _i32]),
     "mfa_resample_num_samples": (_i64, [_i32, _i32, _i64]),
     "mfa_resample_plan": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -207,6 +208,10 @@ SIGNATURES = {
 }
 
 
+# entry points that builds loaded through MFA_HIP_SO (older ones, for A/B timing) may lack
+_NEWER = {"mfa_mfcc_path"}
+
+
 def lib() -> C.CDLL:
     global _LIB
     if _LIB is None:
@@ -224,6 +229,8 @@ def lib() -> C.CDLL:
         except OSError as e:  # e.g. no ROCm runtime on this machine
             raise MfaHipError(f"cannot load {_SO}: {e}") from e
         for name, (res, args) in SIGNATURES.items():
+            if name in _NEWER and os.environ.get("MFA_HIP_SO") and not hasattr(handle, name):
+                continue                 # an older build under A/B: calling the entry point raises AttributeError
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -25,6 +25,7 @@
 namespace {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kNfft = 512;
 constexpr int kHalf = 256;
@@ -49,6 +50,24 @@ constexpr int kMelStride = kMaxBins + 8;
 constexpr int kPartOff = 4 * kPStride;  // [4][kPartStride] piece sums
 constexpr int kMelOff = kPartOff + 4 * kPartStride;   // [4][kMelStride] log mel energies
 static_assert(kMelOff + 4 * kMelStride <= kTileFloats, "tile reuse");
+// ---- the specialised tail (kFast): fixed trip counts over zero-padded tables, so that the reads of a stage are issued
+// together and waited for once.  Plans within the bounds take it; anything else (a bin of more than kFastNp pieces) and
+// MFA_MFCC_GENERIC=1 take the generic tail, which is the bit reference.
+constexpr int kFastRounds = kMaxPieces / 16;   // mel rounds: every plan the tables hold
+constexpr int kFastNp = 8;                     // pieces per bin (MFA's 23 bins need 7, 40 bins 4)
+static_assert(kMaxPieces + kFastNp <= kPartStride + 1, "a bin's batch of piece sums stays inside its row");
+static_assert(kMelOff % 4 == 0 && kMelStride % 4 == 0 && kTileFloats % 4 == 0, "16-byte reads of the log energies");
+// a lane's entries of the window / twiddle tables and its DCT row are contiguous; 36 dwords from lane to lane put the sixteen
+// lanes' 16-byte units on the 64 banks exactly once (36 l mod 64 = 0, 36, 8, 44, ...: sixteen distinct multiples of four)
+constexpr int kLaneStride = 36;
+// constant tables in LDS (float offsets).  generic: [e][lane] float2 tables, pieces [piece][tap], DCT [ceps][bins], plan
+constexpr int kGenTw256 = 0, kGenTw512 = 512, kGenWnd = 1024, kGenMelw = 1536, kGenDct = kGenMelw + kMaxMelW,
+              kGenInfo = kGenDct + kMaxDct, kGenConst = kGenInfo + kMaxPieces + kMaxBins;
+// fast: [lane][e] float2 tables, pieces [round][half][lane][4 taps], DCT [ceps][kLaneStride] (the plan stays in registers)
+constexpr int kFastTab = 16 * kLaneStride;
+constexpr int kFastTw256 = 0, kFastTw512 = kFastTab, kFastWnd = 2 * kFastTab, kFastMelw = 3 * kFastTab,
+              kFastDct = kFastMelw + kMaxMelW, kFastConst = kFastDct + kMaxCeps * kLaneStride;
+static_assert(kMaxBins <= kLaneStride - 4 && kFastMelw % 4 == 0 && kFastDct % 4 == 0, "16-byte units");
 
 struct MfccParams {
   int win, shift, nbins, nceps, snip_edges, remove_dc;
@@ -139,19 +158,17 @@ __device__ __forceinline__ void dft16(v2f (&a)[16]) {
     for (int ka = kb + 1; ka < 4; ka++) { const v2f t = a[4 * kb + ka]; a[4 * kb + ka] = a[4 * ka + kb]; a[4 * ka + kb] = t; }
 }
 
-// kJ = ⌈window / 32⌉ packed sample pairs per lane (13 for MFA's 25 ms at 16 kHz)
-template <int kJ, bool kEnergy = false>
+// kJ = ⌈window / 32⌉ packed sample pairs per lane (13 for MFA's 25 ms at 16 kHz).  kFast: the tail after the power spectrum
+// with compile-time trip counts and the per-lane tables in [lane][entry] order (above); same arithmetic in the same order.
+template <int kJ, bool kEnergy, bool kFast>
 __global__ __launch_bounds__(64 * kWavesPerBlock, 4) void mfcc_kernel(MfccParams p, const int16_t *__restrict__ pcm,
                                                                         const int64_t *__restrict__ sample_off,
                                                                         const int64_t *__restrict__ frame_off,
                                                                         float *__restrict__ out) {
-  __shared__ float s_tile[kWavesPerBlock][kTileFloats];
-  __shared__ v2f s_tw256[256];
-  __shared__ v2f s_tw512[256];
-  __shared__ float s_melw[kMaxMelW];
-  __shared__ float s_dct[kMaxDct];
-  __shared__ v2f s_wnd[256];
-  __shared__ int s_info[kMaxPieces + kMaxBins];
+  __shared__ __attribute__((aligned(16))) float s_tile[kWavesPerBlock][kTileFloats];
+  __shared__ __attribute__((aligned(16))) float s_const[kFast ? kFastConst : kGenConst];
+  constexpr int kTw256 = kFast ? kFastTw256 : kGenTw256, kTw512 = kFast ? kFastTw512 : kGenTw512,
+                kWnd = kFast ? kFastWnd : kGenWnd, kMelw = kFast ? kFastMelw : kGenMelw, kDct = kFast ? kFastDct : kGenDct;
   const int utt = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int q = lane >> 4, i = lane & 15;
@@ -160,13 +177,27 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 4) void mfcc_kernel(MfccParams
   const int T = (int)(frame_off[utt + 1] - f0);
   if ((int)blockIdx.x * kFramesPerBlock >= T) return;  // whole workgroup: nothing to do
   for (int k = threadIdx.x; k < 256; k += 64 * kWavesPerBlock) {
-    s_tw256[k] = (v2f){p.tw256[2 * k], p.tw256[2 * k + 1]};
-    s_tw512[k] = (v2f){p.tw512[2 * k], p.tw512[2 * k + 1]};
-    s_wnd[k] = (v2f){p.window[2 * k], p.window[2 * k + 1]};
+    const int at = kFast ? (k & 15) * kLaneStride + 2 * (k >> 4) : 2 * k;      // entry k >> 4 of lane k & 15
+    s_const[kTw256 + at] = p.tw256[2 * k]; s_const[kTw256 + at + 1] = p.tw256[2 * k + 1];
+    s_const[kTw512 + at] = p.tw512[2 * k]; s_const[kTw512 + at + 1] = p.tw512[2 * k + 1];
+    s_const[kWnd + at] = p.window[2 * k]; s_const[kWnd + at + 1] = p.window[2 * k + 1];
   }
-  for (int k = threadIdx.x; k < p.n_pieces * kPieceTaps; k += 64 * kWavesPerBlock) s_melw[k] = p.melw[k];
-  for (int k = threadIdx.x; k < p.nceps * p.nbins; k += 64 * kWavesPerBlock) s_dct[k] = p.dct[k];
-  for (int k = threadIdx.x; k < kMaxPieces + kMaxBins; k += 64 * kWavesPerBlock) s_info[k] = p.melinfo[k];
+  if constexpr (kFast) {
+    // taps 4 h … 4 h + 3 of piece 16 r + l at [r][h][l]: one 16-byte unit per lane, sixteen lanes contiguous; absent pieces,
+    // bins and coefficients carry zero weights
+    for (int k = threadIdx.x; k < kMaxMelW; k += 64 * kWavesPerBlock) {
+      const int piece = k / kPieceTaps, t = k % kPieceTaps;
+      s_const[kMelw + (((piece >> 4) * 2 + (t >> 2)) * 16 + (piece & 15)) * 4 + (t & 3)] = piece < p.n_pieces ? p.melw[k] : 0.0f;
+    }
+    for (int k = threadIdx.x; k < kMaxCeps * kLaneStride; k += 64 * kWavesPerBlock) {
+      const int row = k / kLaneStride, b = k % kLaneStride;
+      s_const[kDct + k] = row < p.nceps && b < p.nbins ? p.dct[row * p.nbins + b] : 0.0f;
+    }
+  } else {
+    for (int k = threadIdx.x; k < p.n_pieces * kPieceTaps; k += 64 * kWavesPerBlock) s_const[kMelw + k] = p.melw[k];
+    for (int k = threadIdx.x; k < p.nceps * p.nbins; k += 64 * kWavesPerBlock) s_const[kDct + k] = p.dct[k];
+    for (int k = threadIdx.x; k < kMaxPieces + kMaxBins; k += 64 * kWavesPerBlock) s_const[kGenInfo + k] = __int_as_float(p.melinfo[k]);
+  }
   float *tile = s_tile[wave];
   for (int k = lane; k < kTileFloats; k += 64) tile[k] = 0.0f;   // nothing non-finite may ever sit under a zero weight
   __syncthreads();
@@ -176,23 +207,42 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 4) void mfcc_kernel(MfccParams
   const int16_t *x = pcm + s0;
 
   // ---- per-lane constants (the window / twiddle tables are read from LDS in every pass: 60 registers otherwise)
-  const float lift_k = i < p.nceps ? p.lifter[i] : 0.0f;
+  // With 13 sample pairs per lane, what a lane takes from the small tables (its lifter, its part of the filterbank plan)
+  // is loop-invariant and the compiler keeps it in registers.  With 16 there is no room beside the FFT (it was spilled
+  // to scratch), so it is fetched again in every pass, through the lane index the compiler cannot see through.
+  auto lane_lifter = [&](int l) { return l < p.nceps ? p.lifter[l] : 0.0f; };
   v2f *tq = (v2f *)tile + q * (16 * kRowPad);     // this row's transposition tile
   float *pq = tile + q * kPStride;                  // … power spectrum
   float *partq = tile + kPartOff + q * kPartStride;  // … filterbank piece sums
   float *melq = tile + kMelOff + q * kMelStride;     // … log mel energies
+  // kFast: lane l's part of the plan: the first FFT bin of its piece in each of the six rounds, and the
+  // (first piece | pieces << 8) words of its two bins (0 pieces beyond the last bin)
+  auto lane_plan = [&](int l, int (&poff)[kFastRounds], int (&binfo)[2]) {
+#pragma unroll
+    for (int r = 0; r < kFastRounds; r++) poff[r] = p.melinfo[16 * r + l];
+    binfo[0] = p.melinfo[kMaxPieces + l]; binfo[1] = p.melinfo[kMaxPieces + 16 + l];
+  };
+  constexpr bool kKeep = kJ <= 13;
+  float lift_k = 0.0f;
+  int poff[kFastRounds] = {}, binfo[2] = {};
+  if constexpr (kKeep) {
+    lift_k = lane_lifter(i);
+    if constexpr (kFast) lane_plan(i, poff, binfo);
+  }
 
   // samples of frame f as packed pairs (x[2m] | x[2m+1] << 16), m = i + 16 j
-  auto load_frame = [&](int f, unsigned (&raw)[kJ]) {
+  auto load_frame = [&](int f, int li, unsigned (&raw)[kJ]) {
     const int64_t start = p.snip_edges ? (int64_t)f * p.shift : (int64_t)p.shift * f + p.shift / 2 - p.win / 2;
     const bool fast = start >= 0 && start + 32 * kJ <= n && (((s0 + start) & 1) == 0);
     if (__all(fast)) {          // interior frames (all but the first and last one or two): aligned 4-byte loads
       const unsigned *xs = reinterpret_cast<const unsigned *>(x + start);
 #pragma unroll
-      for (int j = 0; j < kJ; j++) raw[j] = xs[16 * j + i];
+      for (int j = 0; j < kJ; j++) raw[j] = xs[16 * j + li];
       return;
     }
-#pragma unroll
+    // edge frames, sample by sample.  A rolled loop (register j is picked by a uniform compare): unrolled, its 64-bit
+    // address arithmetic was most of the kernel's code and held registers across the hot path
+#pragma unroll 1
     for (int j = 0; j < kJ; j++) {
       unsigned both = 0;
 #pragma unroll
@@ -206,27 +256,47 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 4) void mfcc_kernel(MfccParams
         }
         both |= val << (16 * e);
       }
-      raw[j] = both;
+#pragma unroll
+      for (int jj = 0; jj < kJ; jj++) raw[jj] = jj == j ? both : raw[jj];
     }
   };
   // the frame a row works on (rows past the wavefront's share repeat its last frame and do not store)
   auto frame_of = [&](int it) { return fbase + min(4 * it + q, nfr - 1); };
+  // entries first … kN − 1 of this lane in one of the three float2 tables; `at` is the lane's float offset in the table
+  auto load_tab = [&](const float *tab, int at, int first, int kN, v2f (&w)[16]) {
+    if constexpr (kFast) {
+#pragma unroll
+      for (int c = 0; c < 8; c++)
+        if (2 * c < kN) {
+          v4f t = *reinterpret_cast<const v4f *>(tab + at + 4 * c);
+          asm("" : "+v"(t));   // one 16-byte read even where half of it is not used (entry 0 of W256)
+          w[2 * c] = (v2f){t.x, t.y}; w[2 * c + 1] = (v2f){t.z, t.w};
+        }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 16; e++)
+        if (e >= first && e < kN) w[e] = *reinterpret_cast<const v2f *>(tab + at + 32 * e);
+    }
+  };
 
   unsigned nxt[kJ];
-  load_frame(frame_of(0), nxt);
+#pragma unroll
+  for (int j = 0; j < kJ; j++) nxt[j] = 0;
+  load_frame(frame_of(0), i, nxt);
   const int npass = (nfr + 3) >> 2;
   for (int it = 0; it < npass; it++) {
     const int f = frame_of(it);
     const bool live = 4 * it + q < nfr;
     int ti = i;
     asm volatile("" : "+v"(ti));   // table index the compiler cannot see through: the 60 table values are read per pass, not hoisted into registers
-    const v2f *wnd = s_wnd + ti, *tw256 = s_tw256 + ti, *tw512 = s_tw512 + ti;
+    const int tab_at = kFast ? ti * kLaneStride : 2 * ti;
+    const int li = kKeep ? i : ti;     // lane index of this pass's addresses (PCM, tile, output): with 16 pairs they are not kept either
     v2f a[16];
 #pragma unroll
     for (int j = 0; j < 16; j++) a[j] = (v2f){0.0f, 0.0f};
 #pragma unroll
     for (int j = 0; j < kJ; j++) a[j] = (v2f){(float)(short)(nxt[j] & 0xFFFFu), (float)(short)(nxt[j] >> 16)};
-    if (it + 1 < npass) load_frame(frame_of(it + 1), nxt);   // in flight while this pass is processed
+    if (it + 1 < npass) load_frame(frame_of(it + 1), li, nxt);   // in flight while this pass is processed
     // ---- samples at and beyond the window's end are zero.  load_frame's fast path brings 32·kJ samples whatever the window:
     // at 385–416 (kJ 13) and 481–512 (kJ 16) samples only the last pair can lie beyond it, but a shorter window of the same
     // instantiation (257–383, 417–479) leaves real audio in whole registers before that one.  The window weights are 0
@@ -268,6 +338,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 4) void mfcc_kernel(MfccParams
     // ---- pre-emphasis + window.  x[2m−1] is the odd sample of the previous lane (row_shr:1); lane 0 takes it from lane 15
     // of the previous register (row_ror:1 → kept where row_shr has no source); sample 0 uses itself (Kaldi)
     {
+      v2f w[16];
+      load_tab(s_const + kWnd, tab_at, 0, kJ, w);
       float prev_e[kJ];
 #pragma unroll
       for (int j = 0; j < kJ; j++) {
@@ -278,78 +350,144 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 4) void mfcc_kernel(MfccParams
 #pragma unroll
       for (int j = 0; j < kJ; j++) {
         const v2f prev = (v2f){prev_e[j], a[j].x};
-        a[j] = (a[j] - splat(p.preemph) * prev) * wnd[16 * j];
+        a[j] = (a[j] - splat(p.preemph) * prev) * w[j];
       }
     }
     if constexpr (kEnergy) { if (!p.raw_energy) log_energy = frame_log_energy(); }
     // ---- 256-point complex FFT of z[m] = x[2m] + i x[2m+1]: 16-point DFTs over j, twiddle, transpose, 16-point DFTs over i
     dft16<kJ>(a);
+    {
+      v2f w[16];
+      load_tab(s_const + kTw256, tab_at, 1, 16, w);
 #pragma unroll
-    for (int k1 = 1; k1 < 16; k1++) a[k1] = cmul(a[k1], tw256[16 * k1]);
+      for (int k1 = 1; k1 < 16; k1++) a[k1] = cmul(a[k1], w[k1]);
+    }
 #pragma unroll
-    for (int k1 = 0; k1 < 16; k1++) tq[k1 * kRowPad + i] = a[k1];
+    for (int k1 = 0; k1 < 16; k1++) tq[k1 * kRowPad + li] = a[k1];
     WAVE_SYNC();
 #pragma unroll
-    for (int n2 = 0; n2 < 16; n2++) a[n2] = tq[i * kRowPad + n2];
+    for (int n2 = 0; n2 < 16; n2++) a[n2] = tq[li * kRowPad + n2];
     WAVE_SYNC();
     dft16(a);                        // a[k2] = Z[i + 16 k2]
     // ---- real-FFT post-processing → power spectrum.  Z[256 − k] sits in lane 16 − i, register 15 − k2 (lane 0: its own
     // register 16 − k2): row_mirror brings lane 15 − i, row_shr:1 the lane before that one, and lane 0 keeps the `old` value.
     //   2E = Z[k] + conj(Z[N−k]),  2O = −i (Z[k] − conj(Z[N−k])),  2X[k] = 2E + w^k · 2O,  P = |2X|² / 4  (halving is exact)
+    {
+      v2f w[16];
+      load_tab(s_const + kTw512, tab_at, 0, 16, w);
 #pragma unroll
-    for (int k2 = 0; k2 < 16; k2++) {
-      const v2f zk = a[k2], own = a[(16 - k2) & 15], far = a[15 - k2];
-      const float cx = dpp_f32<0x111>(own.x, dpp_perm<0x140>(far.x));
-      const float cy = dpp_f32<0x111>(own.y, dpp_perm<0x140>(far.y));
-      // 2E = (zk.x + cx, zk.y − cy), D = (zk.x − cx, zk.y + cy), 2O = −i·D: the table holds −i·w^k, so 2X = 2E + (−i w^k)·D
-      float ex = zk.x + cx, ey = zk.y - cy, dx = zk.x - cx, dy = zk.y + cy;
-      asm("" : "+v"(ex), "+v"(dx));   // (kept scalar: packed, the mixed signs cost three moves per pair)
-      const v2f xk = (v2f){ex, ey} + cmul(tw512[16 * k2], (v2f){dx, dy});
-      float pw = 0.25f * fmaf(xk.y, xk.y, xk.x * xk.x);
-      if (k2 == 0 && i == 0) pw = 0.25f * (xk.x * xk.x);      // Kaldi ComputePowerSpectrum: bin 0 = DC² (the Nyquist bin is never used)
-      pq[16 * k2 + i] = pw;
-    }
-    WAVE_SYNC();
-    // ---- mel filterbank: piece (16 r + i) of the table is summed by lane i in round r
-    for (int r = 0; r < p.n_rounds; r++) {
-      const int piece = 16 * r + i;
-      const int pc = min(piece, p.n_pieces - 1);
-      const float *wv = s_melw + pc * kPieceTaps;
-      const float *pv = pq + s_info[pc];
-      float acc = 0.0f;
-#pragma unroll
-      for (int t = 0; t < kPieceTaps; t++) acc = fmaf(wv[t], pv[t], acc);
-      if (piece < p.n_pieces) partq[piece] = acc;
-    }
-    WAVE_SYNC();
-    // ---- pieces of a bin in ascending order, floor at FLT_EPSILON, log (hardware log2: ≲1e-6 absolute on values of
-    // 10–25, far inside the 2e-3 the FFT leaves); lane i finishes bins i and i + 16
-#pragma unroll
-    for (int half = 0; half < 2; half++) {
-      const int b = i + 16 * half;
-      if (b < p.nbins) {
-        const int info = s_info[kMaxPieces + b];
-        const int first = info & 0xFF, np = info >> 8;
-        float e = partq[first];
-        for (int r = 1; r < p.np_max; r++) if (r < np) e += partq[first + r];
-        melq[b] = __builtin_amdgcn_logf(fmaxf(e, 1.1920928955078125e-07f)) * 0.693147180559945309f;
+      for (int k2 = 0; k2 < 16; k2++) {
+        const v2f zk = a[k2], own = a[(16 - k2) & 15], far = a[15 - k2];
+        const float cx = dpp_f32<0x111>(own.x, dpp_perm<0x140>(far.x));
+        const float cy = dpp_f32<0x111>(own.y, dpp_perm<0x140>(far.y));
+        // 2E = (zk.x + cx, zk.y − cy), D = (zk.x − cx, zk.y + cy), 2O = −i·D: the table holds −i·w^k, so 2X = 2E + (−i w^k)·D
+        float ex = zk.x + cx, ey = zk.y - cy, dx = zk.x - cx, dy = zk.y + cy;
+        asm("" : "+v"(ex), "+v"(dx));   // (kept scalar: packed, the mixed signs cost three moves per pair)
+        const v2f xk = (v2f){ex, ey} + cmul(w[k2], (v2f){dx, dy});
+        float pw = 0.25f * fmaf(xk.y, xk.y, xk.x * xk.x);
+        if (k2 == 0 && i == 0) pw = 0.25f * (xk.x * xk.x);      // Kaldi ComputePowerSpectrum: bin 0 = DC² (the Nyquist bin is never used)
+        pq[16 * k2 + li] = pw;
       }
     }
     WAVE_SYNC();
-    // ---- DCT-II row i + lifter
-    if (i < p.nceps) {
-      const float *d = s_dct + i * p.nbins;
+    float c_out;
+    if constexpr (kFast) {
+      // ---- mel filterbank: piece (16 r + i) of the table is summed by lane i in round r; every round's 8 weights (two
+      // 16-byte units) and 8 powers are independent reads, and the sums are written after the last round (a store between
+      // two rounds would order the next round's reads behind it): the rounds wait for LDS together, not twice each
+      if constexpr (!kKeep) lane_plan(ti, poff, binfo);
+      const float *mw = s_const + kMelw + 4 * ti;
+      float psum[kFastRounds];
+#pragma unroll
+      for (int r = 0; r < kFastRounds; r++) {
+        const v4f wa = *reinterpret_cast<const v4f *>(mw + (2 * r) * 64), wb = *reinterpret_cast<const v4f *>(mw + (2 * r + 1) * 64);
+        const float *pv = pq + poff[r];
+        float acc = 0.0f;
+        acc = fmaf(wa.x, pv[0], acc); acc = fmaf(wa.y, pv[1], acc); acc = fmaf(wa.z, pv[2], acc); acc = fmaf(wa.w, pv[3], acc);
+        acc = fmaf(wb.x, pv[4], acc); acc = fmaf(wb.y, pv[5], acc); acc = fmaf(wb.z, pv[6], acc); acc = fmaf(wb.w, pv[7], acc);
+        psum[r] = acc;
+      }
+#pragma unroll
+      for (int r = 0; r < kFastRounds; r++) partq[16 * r + li] = psum[r];     // (an absent piece: +0 under zero weights, never taken below)
+      WAVE_SYNC();
+      // ---- pieces of a bin in ascending order as one batch of kFastNp reads, both bins of the lane together: an absent
+      // piece adds +0.0, which changes no bit because a bin's sum of non-negative products is never −0.0; floor, log as in
+      // the generic tail.  Bins beyond the last one are written as 0: the DCT below runs over kMaxBins under zero weights
+      float v[2][kFastNp];
+#pragma unroll
+      for (int half = 0; half < 2; half++)
+#pragma unroll
+        for (int r = 0; r < kFastNp; r++) v[half][r] = partq[(binfo[half] & 0xFF) + r];
+#pragma unroll
+      for (int half = 0; half < 2; half++) {
+        const int np = binfo[half] >> 8;
+        float e = v[half][0];
+#pragma unroll
+        for (int r = 1; r < kFastNp; r++) e += r < np ? v[half][r] : 0.0f;
+        const float le = __builtin_amdgcn_logf(fmaxf(e, 1.1920928955078125e-07f)) * 0.693147180559945309f;
+        v[half][0] = np > 0 ? le : 0.0f;
+      }
+      melq[li] = v[0][0]; melq[li + 16] = v[1][0];
+      WAVE_SYNC();
+      // ---- DCT-II row i + lifter: the row (lane stride kLaneStride) and the row's log energies in 16-byte units
+      const float *d = s_const + kDct + tab_at;
       float acc = 0.0f;
-      for (int b = 0; b < p.nbins; b++) acc = fmaf(d[b], melq[b], acc);
-      float c_out = acc * lift_k;
-      if constexpr (kEnergy) { if (i == 0) c_out = fmaxf(log_energy, p.log_energy_floor); }   // C0 := log energy (MfccComputer::Compute)
-      if (live) out[(f0 + f) * p.nceps + i] = c_out;
+#pragma unroll
+      for (int c = 0; c < kMaxBins / 4; c++) {
+        const v4f dw = *reinterpret_cast<const v4f *>(d + 4 * c), m = *reinterpret_cast<const v4f *>(melq + 4 * c);
+        acc = fmaf(dw.x, m.x, acc); acc = fmaf(dw.y, m.y, acc); acc = fmaf(dw.z, m.z, acc); acc = fmaf(dw.w, m.w, acc);
+      }
+      c_out = acc * (kKeep ? lift_k : lane_lifter(ti));
+    } else {
+      // ---- mel filterbank: piece (16 r + i) of the table is summed by lane i in round r
+      const float *s_melw = s_const + kMelw, *s_dct = s_const + kDct, *s_info = s_const + kGenInfo;
+      for (int r = 0; r < p.n_rounds; r++) {
+        const int piece = 16 * r + i;
+        const int pc = min(piece, p.n_pieces - 1);
+        const float *wv = s_melw + pc * kPieceTaps;
+        const float *pv = pq + __float_as_int(s_info[pc]);
+        float acc = 0.0f;
+#pragma unroll
+        for (int t = 0; t < kPieceTaps; t++) acc = fmaf(wv[t], pv[t], acc);
+        if (piece < p.n_pieces) partq[piece] = acc;
+      }
+      WAVE_SYNC();
+      // ---- pieces of a bin in ascending order, floor at FLT_EPSILON, log (hardware log2: ≲1e-6 absolute on values of
+      // 10–25, far inside the 2e-3 the FFT leaves); lane i finishes bins i and i + 16
+#pragma unroll
+      for (int half = 0; half < 2; half++) {
+        const int b = i + 16 * half;
+        if (b < p.nbins) {
+          const int info = __float_as_int(s_info[kMaxPieces + b]);
+          const int first = info & 0xFF, np = info >> 8;
+          float e = partq[first];
+          for (int r = 1; r < p.np_max; r++) if (r < np) e += partq[first + r];
+          melq[b] = __builtin_amdgcn_logf(fmaxf(e, 1.1920928955078125e-07f)) * 0.693147180559945309f;
+        }
+      }
+      WAVE_SYNC();
+      // ---- DCT-II row i + lifter
+      float acc = 0.0f;
+      if (i < p.nceps) {
+        const float *d = s_dct + i * p.nbins;
+        for (int b = 0; b < p.nbins; b++) acc = fmaf(d[b], melq[b], acc);
+      }
+      c_out = acc * (kKeep ? lift_k : lane_lifter(ti));
     }
+    if constexpr (kEnergy) { if (i == 0) c_out = fmaxf(log_energy, p.log_energy_floor); }   // C0 := log energy (MfccComputer::Compute)
+    if (i < p.nceps && live) out[(f0 + f) * p.nceps + li] = c_out;
     WAVE_SYNC();
   }
 }
 
 float mel_scale(float f) { return 1127.0f * logf(1.0f + f / 700.0f); }
+
+template <int kJ, bool kEnergy, bool kFast>
+void mfcc_launch(mfa_ctx *c, dim3 grid, const MfccParams &p, const int16_t *d_pcm, const int64_t *d_sample_off,
+                        const int64_t *d_frame_off, float *d_mfcc) {
+  hipLaunchKernelGGL((mfcc_kernel<kJ, kEnergy, kFast>), grid, dim3(64 * kWavesPerBlock), 0, c->stream, p, d_pcm, d_sample_off,
+                     d_frame_off, d_mfcc);
+}
 
 }  // namespace
 
@@ -467,6 +605,15 @@ MFA_API int32_t mfa_mfcc_num_frames(mfa_ctx *c, int64_t n) {
   return (int32_t)((n + c->shift / 2) / c->shift);
 }
 
+// Which tail the next mfa_mfcc_batch launches: 1 the specialised one, 2 the generic one (a plan beyond its bounds, or
+// MFA_MFCC_GENERIC=1, read at every call), 0 before mfa_mfcc_configure.
+MFA_API int mfa_mfcc_path(mfa_ctx *c) {
+  if (!c->mfcc_ready) return 0;
+  const char *generic = getenv("MFA_MFCC_GENERIC");
+  const bool force_generic = generic && generic[0] == '1';
+  return !force_generic && c->mel_np_max <= kFastNp ? 1 : 2;
+}
+
 MFA_API int mfa_mfcc_batch(mfa_ctx *c, const int16_t *d_pcm, const int64_t *d_sample_off, const int64_t *d_frame_off,
                            int32_t n_utt, int32_t max_frames, float *d_mfcc) {
   if (!c->mfcc_ready) return c->fail("mfa_mfcc_configure has not been called");
@@ -482,13 +629,17 @@ MFA_API int mfa_mfcc_batch(mfa_ctx *c, const int16_t *d_pcm, const int64_t *d_sa
   p.n_pieces = c->n_melw; p.n_rounds = (c->n_melw + 15) / 16; p.np_max = c->mel_np_max;
   dim3 grid((max_frames + kFramesPerBlock - 1) / kFramesPerBlock, n_utt);
   KernelTimer kt(c, MFA_K_MFCC);
-  const bool energy = c->mfcc.use_energy != 0;       // (its own instantiations: the default kernel carries nothing for it)
-  if (c->win <= 32 * 13) {
-    if (energy) hipLaunchKernelGGL((mfcc_kernel<13, true>), grid, dim3(64 * kWavesPerBlock), 0, c->stream, p, d_pcm, d_sample_off, d_frame_off, d_mfcc);
-    else hipLaunchKernelGGL((mfcc_kernel<13, false>), grid, dim3(64 * kWavesPerBlock), 0, c->stream, p, d_pcm, d_sample_off, d_frame_off, d_mfcc);
-  } else {
-    if (energy) hipLaunchKernelGGL((mfcc_kernel<16, true>), grid, dim3(64 * kWavesPerBlock), 0, c->stream, p, d_pcm, d_sample_off, d_frame_off, d_mfcc);
-    else hipLaunchKernelGGL((mfcc_kernel<16, false>), grid, dim3(64 * kWavesPerBlock), 0, c->stream, p, d_pcm, d_sample_off, d_frame_off, d_mfcc);
+  // instantiations: 13 or 16 sample pairs per lane; with use_energy (the default kernel carries nothing for it); tail
+  const int which = (c->win <= 32 * 13 ? 0 : 4) + (c->mfcc.use_energy != 0 ? 2 : 0) + (mfa_mfcc_path(c) == 1 ? 1 : 0);
+  switch (which) {
+    case 0: mfcc_launch<13, false, false>(c, grid, p, d_pcm, d_sample_off, d_frame_off, d_mfcc); break;
+    case 1: mfcc_launch<13, false, true>(c, grid, p, d_pcm, d_sample_off, d_frame_off, d_mfcc); break;
+    case 2: mfcc_launch<13, true, false>(c, grid, p, d_pcm, d_sample_off, d_frame_off, d_mfcc); break;
+    case 3: mfcc_launch<13, true, true>(c, grid, p, d_pcm, d_sample_off, d_frame_off, d_mfcc); break;
+    case 4: mfcc_launch<16, false, false>(c, grid, p, d_pcm, d_sample_off, d_frame_off, d_mfcc); break;
+    case 5: mfcc_launch<16, false, true>(c, grid, p, d_pcm, d_sample_off, d_frame_off, d_mfcc); break;
+    case 6: mfcc_launch<16, true, false>(c, grid, p, d_pcm, d_sample_off, d_frame_off, d_mfcc); break;
+    default: mfcc_launch<16, true, true>(c, grid, p, d_pcm, d_sample_off, d_frame_off, d_mfcc); break;
   }
   MFA_HIP_CHECK(c, hipGetLastError());
   return 0;

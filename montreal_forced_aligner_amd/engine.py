@@ -100,6 +100,11 @@ class AlignmentEngine(GraphPacking, FrontEndStages):
         self.mfcc_opts = opts            # (a refused option set leaves the library, and so this object, at the previous one)
         self.num_ceps = int(opts.num_coefficients)
 
+    def mfcc_path(self) -> str:
+        """Which tail of the MFCC kernel the configured options take now: ``"specialised"`` (compile-time trip counts) or
+        ``"generic"`` (a filterbank plan beyond its bounds, or ``MFA_MFCC_GENERIC=1``, read at every call)."""
+        return {1: "specialised", 2: "generic"}[int(self.lib.mfa_mfcc_path(self.ctx))]
+
     def load_gmm(self, gmm: DiagGmmModel) -> None:
         po, gc, mi, iv = model_arrays(gmm)
         check(self.ctx, self.lib.mfa_load_gmm(self.ctx, gmm.dim, gmm.num_pdfs, po.ctypes.data, gc.ctypes.data,
