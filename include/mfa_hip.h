@@ -565,6 +565,30 @@ MFA_API int mfa_debug_gmm_acc_host(int32_t dim, int32_t num_pdfs, const int32_t 
                                    int32_t n_tids, double *h_occ, double *h_mean, double *h_var, double *h_tot,
                                    int64_t *h_tid_count, float *h_post, int32_t post_stride);
 
+/* GMM statistics from two feature matrices of the same frames: replaces Kaldi gmm-acc-stats-twofeats, which the reference's
+ * SatTrainer.create_align_model runs to build final.alimdl (MFA/acoustic_modeling/sat.py: posteriors from the
+ * speaker-adapted features, sufficient statistics from the unadapted ones; restated from its description as above).
+ * The contract is mfa_gmm_acc_batch's, word for word, with two differences:
+ *   the log-likelihood chain, the softmax, gamma_g and the frame's log-likelihood (so tot[0]) use row t of d_feats_post;
+ *   the x_k of mean[g][k] = fma(gamma_g, x_k, mean[g][k]) and var[g][k] = fma(gamma_g, x_k * x_k, var[g][k]) are row t of
+ *   d_feats_sum.
+ * Both matrices are [total_frames][dim] of the loaded model's dim.  Frames that take no part, the ordering by pdf (the stable
+ * sort), the chunks of mfa_gmm_acc_chunk_frames(), the chunk-order reduction, the absence of floating-point atomics, the
+ * limits and refusals, total_frames == 0 and the four timing slots are mfa_gmm_acc_batch's; a NULL d_feats_sum with frames is
+ * refused too.  A consequence: with d_feats_sum holding the values of d_feats_post the result has the bits of mfa_gmm_acc_batch on
+ * that input. */
+MFA_API int mfa_gmm_acc_twofeats_batch(mfa_ctx *ctx, const float *d_feats_post, const float *d_feats_sum, int64_t total_frames,
+                                       const int32_t *d_ali, const int32_t *d_tid2pdf, const float *d_tid_weight, int32_t n_tids,
+                                       double *d_occ, double *d_mean, double *d_var, double *d_tot, int64_t *d_tid_count);
+/* Its host twin: mfa_debug_gmm_acc_host with h_feats_sum [total_frames][dim] after h_feats; the same loop, the x of the sums
+ * from h_feats_sum.  Returns as mfa_debug_gmm_acc_host; -1 also for a NULL h_feats_sum with frames. */
+MFA_API int mfa_debug_gmm_acc_twofeats_host(int32_t dim, int32_t num_pdfs, const int32_t *h_pdf_offsets, const float *h_gconsts,
+                                            const float *h_means_invvars, const float *h_inv_vars, const float *h_feats,
+                                            const float *h_feats_sum, int64_t total_frames, const int32_t *h_pdf,
+                                            const float *h_weight, const int32_t *h_tid, int32_t n_tids, double *h_occ,
+                                            double *h_mean, double *h_var, double *h_tot, int64_t *h_tid_count, float *h_post,
+                                            int32_t post_stride);
+
 /* ---- Equal alignment: replaces kalpy gmm_align_equal (MFA/acoustic_modeling/monophone.py:108; Kaldi align-equal =
  *      EqualAlign, restated here from its description — Kaldi's source is not among this project's references, and its
  *      random numbers are not reproducible here: parity unpinned by construction).  The first alignment of

@@ -185,6 +185,9 @@ SIGNATURES = {
     "mfa_gmm_acc_batch": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mfa_debug_gmm_acc_host": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _i32]),
+    "mfa_gmm_acc_twofeats_batch": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mfa_debug_gmm_acc_twofeats_host": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _i32]),
     "mfa_align_equal_batch": (C.c_int, [_vp, C.POINTER(GraphBatch), _vp, _i64, _i64, _vp, C.c_uint32, _vp, _vp]),
     "mfa_debug_align_equal_host": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp]),
     "mfa_lda_acc_slab_frames": (_i32, []),
@@ -209,7 +212,7 @@ SIGNATURES = {
 
 
 # entry points that builds loaded through MFA_HIP_SO (older ones, for A/B timing) may lack
-_NEWER = {"mfa_mfcc_path"}
+_NEWER = {"mfa_mfcc_path", "mfa_gmm_acc_twofeats_batch", "mfa_debug_gmm_acc_twofeats_host"}
 
 
 def lib() -> C.CDLL:

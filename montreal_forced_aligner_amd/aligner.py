@@ -28,7 +28,7 @@ from . import graph as _graph
 from . import sharding
 from . import adapt as _adapt
 from . import kaldi_io
-from .engine import AlignmentEngine, GmmStats, fmllr_statistics, gmm_statistics, redo_capacity
+from .engine import AlignmentEngine, GmmStats, fmllr_statistics, gmm_statistics, gmm_statistics_twofeats, redo_capacity
 from .model import DiagGmmModel, TransitionModel
 from .stats import LdaStats, MlltStats, TreeStats, lda_statistics, mllt_statistics, silence_weights, tree_statistics
 from .staging import StagingRing
@@ -146,6 +146,7 @@ class CorpusAligner:
         self.adapt_counts: Dict[str, tuple] = {}         # Gaussians (updated, kept) per model
         self.lda_stats: Optional[LdaStats] = None        # the statistics of the last ``estimate_lda``
         self.mllt_stats: Optional[MlltStats] = None      # the statistics of the last ``estimate_mllt``
+        self.alimdl_stats: Optional[GmmStats] = None     # the statistics of the last ``estimate_alignment_model``
         self.tree_stats: Optional[TreeStats] = None      # the statistics of the last ``tree_statistics``
         self.tree_skipped = 0                            # ... and the utterances it skipped
         self.lda = None if lda is None else np.asarray(lda, dtype=np.float32)
@@ -666,6 +667,46 @@ class CorpusAligner:
             self._load(self.am)
         beta, G = _mllt.mllt_accs(self.mllt_stats, self.raw_am)
         return _mllt.estimate_mllt(beta, G, num_sweeps=num_sweeps)
+
+    # ------------------------------------------------------------------ alignment model of a speaker-adapted model
+    def _twofeats_accumulate(self, utts, kept, spk_ids, cmvn, raw_am, tm: Optional[TransitionModel] = None) -> GmmStats:
+        """Two-feature GMM statistics of the resident batches ``kept`` (adapted features and alignments of
+        ``_align(..., keep_last=True)``, inside the same ``_run``): posteriors on the resident features, sums of the same
+        frames' unadapted features (no transform; the MFCC cache is used), under ``raw_am`` as its file holds it.  ``tm``:
+        the transition model of the alignments (default: the aligner's)."""
+        model = DiagGmmModel.from_raw(raw_am)
+        self.engine.load_gmm(model)
+        self._loaded = model
+        tm = self.tm if tm is None else tm
+        d_lda = None if self.lda is None else torch.from_numpy(self.lda).to(self.engine.device)
+        st = GmmStats.zeros(model.num_gauss, model.dim, tm.num_transition_ids + 1)
+        for idx, feats, ali, fo, _rows in kept:
+            unadapted, fo2, _rows2 = self._batch_features(utts, idx, spk_ids, cmvn, d_lda, None)
+            assert np.array_equal(fo, fo2)
+            gmm_statistics_twofeats(self.engine, feats, unadapted, ali, tm, into=st)
+        return st
+
+    def estimate_alignment_model(self, utterances: Sequence[CorpusUtterance], power: float = 0.25):
+        """The alignment model of the SAT stage (MFA/acoustic_modeling/sat.py:46-130, :307-372; Kaldi
+        gmm-acc-stats-twofeats + gmm-est), the sibling of ``estimate_lda`` / ``estimate_mllt``: align with
+        ``speaker_adapted=True``, keep the last pass's adapted features and alignments resident, accumulate two-feature
+        statistics under ``raw_am`` as its file holds it — posteriors on the adapted features, sums of the unadapted ones
+        (``gmm_statistics_twofeats``, kept as ``alimdl_stats``) — and return ``train.alignment_model``'s
+        (ali_raw_tm, ali_raw_am) with the statistics: (ali_raw_tm, ali_raw_am, stats).  ``power`` is the reference's mix-up
+        exponent; there is no mix-up here (``train.alignment_model`` says why), so it changes nothing.  Needs ``raw_tm=``
+        and ``raw_am=`` of the constructor."""
+        from .train import alignment_model
+
+        if self.raw_tm is None or self.raw_am is None:
+            raise ValueError("estimate_alignment_model needs the models as read from their files: CorpusAligner(..., raw_tm=, raw_am=)")
+        utts = list(utterances)
+        with self._run():
+            _results, kept = self._align(utts, True, False, None, keep_last=True)
+            spk_ids, cmvn = self.speaker_cmvn(utts)            # (from the cached MFCCs: the bits of the alignment passes)
+            self.alimdl_stats = self._twofeats_accumulate(utts, kept, spk_ids, cmvn, self.raw_am)
+            self._load(self.am)
+        ali_raw_tm, ali_raw_am = alignment_model(self.raw_tm, self.raw_am, self.alimdl_stats)
+        return ali_raw_tm, ali_raw_am, self.alimdl_stats
 
     # ------------------------------------------------------------------ tree statistics
     def _tree_accumulate(self, kept, ci_phones: Sequence[int]):

@@ -11,6 +11,8 @@
 //   sums     gmm_acc_kernel, one workgroup per unit = (pdf, chunk of kChunk consecutive entries of its segment)
 //   reduce   per pdf, the units' partials in chunk order into the caller's accumulators; the two totals in unit order
 // No floating-point atomics anywhere.
+// mfa_gmm_acc_twofeats_batch (Kaldi gmm-acc-stats-twofeats: the alignment model of the SAT stage) is the same five steps with
+// gmm_acc_kernel<true>: posteriors from one feature matrix, the sums' x from a second one of the same frames.
 #include <algorithm>
 #include <cstring>
 
@@ -39,6 +41,13 @@ struct AccParams {
   double *partial;     // per unit [n_gauss][2·D + 1]: occupancy, first-order sums, second-order sums
   double *unit_tot;    // per unit {Σ w·loglike, Σ w}
 };
+// The two-feature form's arguments, in a type of its own: the one-feature kernel's argument block, and with it the
+// compiler's register allocation, stay what they were.
+struct AccParams2 : AccParams {
+  const float *feats_sum;     // the rows the sums are formed from
+};
+template <bool kTwoFeats> struct AccParamsOf { using type = AccParams; };
+template <> struct AccParamsOf<true> { using type = AccParams2; };
 
 // One workgroup: exclusive scans over the pdfs of (frames, units, partial rows = units × Gaussians).
 __global__ __launch_bounds__(256) void gmm_acc_scan_kernel(const int32_t *cnt, const int32_t *ngauss, int P, int32_t *seg_off,
@@ -75,8 +84,13 @@ __global__ __launch_bounds__(256) void gmm_acc_scan_kernel(const int32_t *cnt, c
 // Posterior phase: wavefront = 8 frames of the tile, lane = Gaussian (two rounds of 64), weights of the round in LDS as
 // [k][Gaussian].  Sum phase: thread (gg = tid / 16, l = tid % 16) keeps mean / var of Gaussians gg + 16 j (j < 8) in columns
 // l + 16 c (c < 3) in registers over the whole chunk: 48 double FMAs per frame at 128 Gaussians, 6 · ceil(n / 16) in general.
-__global__ __launch_bounds__(256) void gmm_acc_kernel(AccParams p) {
+// kTwoFeats (mfa_gmm_acc_twofeats_batch): the posterior phase reads the rows of p.feats as ever, the sum phase the same
+// frames' rows of p.feats_sum, gathered with them and staged in a tile of their own (x2_s: 6 272 B more LDS, 53 760 B in all;
+// three workgroups of a CU's 160 KB either way).  Without it the kernel is the one-feature kernel, instruction for instruction.
+template <bool kTwoFeats>
+__global__ __launch_bounds__(256) void gmm_acc_kernel(typename AccParamsOf<kTwoFeats>::type p) {
   __shared__ float x_s[kTile][kXStride];
+  __shared__ float x2_s[kTwoFeats ? kTile : 1][kTwoFeats ? kXStride : 1];
   __shared__ float w_s[2 * kMaxDim][64];
   __shared__ float post_s[kTile][kMaxGauss];
   __shared__ float fw_s[kTile], fll_s[kTile];
@@ -106,13 +120,20 @@ __global__ __launch_bounds__(256) void gmm_acc_kernel(AccParams p) {
   // registers while this tile is worked on, and only stored to LDS at the top of the next round.
   constexpr int kStage = kTile * kMaxDim / 256;
   static_assert(kStage * 256 == kTile * kMaxDim, "every thread stages the same number of elements");
-  float nx[kStage], nw = 0.0f;
+  float nx[kStage], nx2[kTwoFeats ? kStage : 1], nw = 0.0f;
   auto fetch = [&](int t0) {
     const int nc = min(kTile, s1 - t0);
 #pragma unroll
     for (int i = 0; i < kStage; i++) {
       const int e = tid + 256 * i, t = e / kMaxDim, k = e % kMaxDim;
-      nx[i] = t < nc && k < D ? p.feats[(size_t)p.idx[t0 + t] * D + k] : 0.0f;         // columns up to 48 read as 0
+      if constexpr (kTwoFeats) {
+        const bool in = t < nc && k < D;
+        const size_t at = in ? (size_t)p.idx[t0 + t] * D + k : 0;
+        nx[i] = in ? p.feats[at] : 0.0f;
+        nx2[i] = in ? p.feats_sum[at] : 0.0f;
+      } else {
+        nx[i] = t < nc && k < D ? p.feats[(size_t)p.idx[t0 + t] * D + k] : 0.0f;       // columns up to 48 read as 0
+      }
     }
     if (tid < kTile) nw = tid < nc ? p.weight[p.idx[t0 + tid]] : 0.0f;
   };
@@ -124,6 +145,7 @@ __global__ __launch_bounds__(256) void gmm_acc_kernel(AccParams p) {
     for (int i = 0; i < kStage; i++) {
       const int e = tid + 256 * i;
       x_s[e / kMaxDim][e % kMaxDim] = nx[i];
+      if constexpr (kTwoFeats) x2_s[e / kMaxDim][e % kMaxDim] = nx2[i];
     }
     if (tid < kTile) fw_s[tid] = nw;
     if (t0 + kTile < s1) fetch(t0 + kTile);
@@ -170,7 +192,7 @@ __global__ __launch_bounds__(256) void gmm_acc_kernel(AccParams p) {
     for (int t = 0; t < nc; t++) {
       float xf[kColsPerThread];
 #pragma unroll
-      for (int c = 0; c < kColsPerThread; c++) xf[c] = x_s[t][l + 16 * c];
+      for (int c = 0; c < kColsPerThread; c++) xf[c] = kTwoFeats ? x2_s[t][l + 16 * c] : x_s[t][l + 16 * c];
 #pragma unroll
       for (int j = 0; j < kGaussPerThread; j++) {
         if (16 * j < ng) {              // the same for the whole workgroup
@@ -262,9 +284,12 @@ extern "C" {
 MFA_API int32_t mfa_gmm_acc_chunk_frames(void) { return kChunk; }
 MFA_API int32_t mfa_gmm_acc_max_dim(void) { return kMaxDim; }
 
-MFA_API int mfa_gmm_acc_batch(mfa_ctx *c, const float *d_feats, int64_t total_frames, const int32_t *d_ali,
-                              const int32_t *d_tid2pdf, const float *d_tid_weight, int32_t n_tids, double *d_occ, double *d_mean,
-                              double *d_var, double *d_tot, int64_t *d_tid_count) {
+}  // extern "C"
+
+// d_feats_sum NULL: the one-feature form.
+static int gmm_acc_run(mfa_ctx *c, const float *d_feats, const float *d_feats_sum, int64_t total_frames, const int32_t *d_ali,
+                       const int32_t *d_tid2pdf, const float *d_tid_weight, int32_t n_tids, double *d_occ, double *d_mean,
+                       double *d_var, double *d_tot, int64_t *d_tid_count) {
   MFA_HIP_CHECK(c, hipSetDevice(c->device));
   if (!c->gmm_ready) return c->fail("mfa_load_gmm has not been called");
   const int D = c->dim, P = c->num_pdfs;
@@ -328,7 +353,14 @@ MFA_API int mfa_gmm_acc_batch(mfa_ctx *c, const float *d_feats, int64_t total_fr
     KernelTimer kt(c, MFA_K_ACC_SUMS);
     AccParams ap{D, c->kpad, P, c->d_w.ptr<float>(), c->d_gc.ptr<float>(), c->d_row0.ptr<int32_t>(), d_ngauss,
                  d_feats, val2, wgt, seg, ub, prow, part, utot};
-    hipLaunchKernelGGL(gmm_acc_kernel, dim3((unsigned)units_max), dim3(256), 0, c->stream, ap);
+    if (d_feats_sum) {
+      AccParams2 ap2;
+      static_cast<AccParams &>(ap2) = ap;
+      ap2.feats_sum = d_feats_sum;
+      hipLaunchKernelGGL(gmm_acc_kernel<true>, dim3((unsigned)units_max), dim3(256), 0, c->stream, ap2);
+    } else {
+      hipLaunchKernelGGL(gmm_acc_kernel<false>, dim3((unsigned)units_max), dim3(256), 0, c->stream, ap);
+    }
     MFA_HIP_CHECK(c, hipGetLastError());
   }
   {
@@ -339,6 +371,21 @@ MFA_API int mfa_gmm_acc_batch(mfa_ctx *c, const float *d_feats, int64_t total_fr
     MFA_HIP_CHECK(c, hipGetLastError());
   }
   return 0;
+}
+
+extern "C" {
+
+MFA_API int mfa_gmm_acc_batch(mfa_ctx *c, const float *d_feats, int64_t total_frames, const int32_t *d_ali,
+                              const int32_t *d_tid2pdf, const float *d_tid_weight, int32_t n_tids, double *d_occ, double *d_mean,
+                              double *d_var, double *d_tot, int64_t *d_tid_count) {
+  return gmm_acc_run(c, d_feats, nullptr, total_frames, d_ali, d_tid2pdf, d_tid_weight, n_tids, d_occ, d_mean, d_var, d_tot, d_tid_count);
+}
+
+MFA_API int mfa_gmm_acc_twofeats_batch(mfa_ctx *c, const float *d_feats_post, const float *d_feats_sum, int64_t total_frames,
+                                       const int32_t *d_ali, const int32_t *d_tid2pdf, const float *d_tid_weight, int32_t n_tids,
+                                       double *d_occ, double *d_mean, double *d_var, double *d_tot, int64_t *d_tid_count) {
+  if (!d_feats_sum && total_frames > 0) return c->fail("GMM statistics, two features: no matrix to form the sums from (d_feats_sum is NULL)");
+  return gmm_acc_run(c, d_feats_post, d_feats_sum, total_frames, d_ali, d_tid2pdf, d_tid_weight, n_tids, d_occ, d_mean, d_var, d_tot, d_tid_count);
 }
 
 }  // extern "C"

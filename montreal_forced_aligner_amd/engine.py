@@ -28,7 +28,7 @@ from .pipeline import Pipeline   # noqa: F401
 from .ragged import _rows_by_group, _speaker_groups, max_len, offsets   # noqa: F401
 from .staging import StagingPool, StagingRing
 from .stats import (GmmStats, LdaStats, MlltStats, TreeStats, check_delta_fmllr, fmllr_statistics, gmm_statistics, gmm_statistics_host,   # noqa: F401
-                    lda_statistics, lda_statistics_host, mllt_statistics, mllt_statistics_host, model_arrays, tid_tables, tree_statistics, tree_statistics_host)
+                    gmm_statistics_twofeats, gmm_statistics_twofeats_host, lda_statistics, lda_statistics_host, mllt_statistics, mllt_statistics_host, model_arrays, tid_tables, tree_statistics, tree_statistics_host)
 
 STATUS_OK, STATUS_RETRIED, STATUS_FAILED, STATUS_TOKEN_OVERFLOW, STATUS_BP_OVERFLOW, STATUS_UNSUPPORTED = 0, 1, 2, 3, 4, 5
 

@@ -794,6 +794,50 @@ class GmmStatsAccumulator:
         flush()
 
 
+class TwoFeatsStatsAccumulator(GmmStatsAccumulator):
+    """The accumulation of the reference's SAT alignment model (``AccStatsTwoFeatsFunction``, MFA/acoustic_modeling/sat.py:46-130;
+    Kaldi gmm-acc-stats-twofeats): ``accumulate_stats(feature_archive, si_feature_archive, alignment_archive, callback=None)``
+    — posteriors from ``feature_archive`` (the speaker-adapted features), sums from ``si_feature_archive`` (the same frames,
+    unadapted) —, then ``gmm_accs`` / ``transition_accs``.  Batching and the skip rule are ``GmmStatsAccumulator``'s; an
+    utterance missing from either archive, or with different frame counts in the two, is skipped as well."""
+
+    def accumulate_stats(self, feature_archive, si_feature_archive, alignment_archive, callback=None) -> None:
+        import torch
+        from .engine import gmm_statistics_twofeats
+
+        eng = get_engine()
+        if eng.gmm is not self.acoustic_model:
+            eng.load_gmm(self.acoustic_model)
+        feats = dict(feature_archive) if not isinstance(feature_archive, dict) else feature_archive
+        si_feats = dict(si_feature_archive) if not isinstance(si_feature_archive, dict) else si_feature_archive
+        rows, si_rows, alis, total = [], [], [], 0
+
+        def flush():
+            nonlocal rows, si_rows, alis, total
+            if rows:
+                gmm_statistics_twofeats(eng, torch.from_numpy(np.concatenate(rows).astype(np.float32)).to(eng.device),
+                                        torch.from_numpy(np.concatenate(si_rows).astype(np.float32)).to(eng.device),
+                                        torch.from_numpy(np.concatenate(alis).astype(np.int32)).to(eng.device), self.transition_model,
+                                        into=self.gmm_accs.stats)
+            rows, si_rows, alis, total = [], [], [], 0
+
+        for al in alignment_archive:
+            x, y = feats.get(al.utterance_id), si_feats.get(al.utterance_id)
+            if x is None or y is None:
+                continue
+            a = np.asarray(al.alignment, dtype=np.int32)
+            if a.shape[0] != x.shape[0] or np.shape(y) != np.shape(x):
+                logger.warning("utterance %s: %d alignment entries for features %s and %s, skipped", al.utterance_id, a.shape[0],
+                               np.shape(x), np.shape(y))
+                continue
+            rows.append(np.asarray(x)); si_rows.append(np.asarray(y)); alis.append(a); total += a.shape[0]
+            if callback:
+                callback(al.utterance_id)
+            if total >= self.batch_frames:
+                flush()
+        flush()
+
+
 # ------------------------------------------------------------------------------------------------ LDA
 class LdaEstimateOptions:
     """``_kalpy.transform.LdaEstimateOptions``: ``dim`` 40, ``allow_large_dim`` False, ``remove_offset`` False."""

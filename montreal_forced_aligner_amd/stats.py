@@ -145,8 +145,28 @@ def gmm_statistics(engine, feats: torch.Tensor, ali: torch.Tensor, tm: Transitio
     ``feats`` float32 [ΣT, dim] and ``ali`` int32 [ΣT] transition-ids on the device (0 where an utterance failed: those frames
     take no part); ``weights``: per transition-id frame weights (default 1).  ``into``: statistics to add to — the device sums
     start from its values, so a corpus accumulated batch by batch is one chain of additions — and the object returned."""
+    return _gmm_statistics(engine, feats, None, ali, tm, weights, into, "gmm_statistics")
+
+
+def gmm_statistics_twofeats(engine, feats_post: torch.Tensor, feats_sum: torch.Tensor, ali: torch.Tensor, tm: TransitionModel,
+                            weights: Optional[np.ndarray] = None, into: Optional[GmmStats] = None) -> GmmStats:
+    """GMM statistics from two feature matrices of the same frames (mfa_gmm_acc_twofeats_batch; Kaldi
+    gmm-acc-stats-twofeats): posteriors and log-likelihood from ``feats_post``, the first- and second-order sums from
+    ``feats_sum``.  Everything else as ``gmm_statistics``.  What builds ``final.alimdl``: posteriors on the speaker-adapted
+    features, sums of the unadapted ones."""
+    if not isinstance(feats_sum, torch.Tensor) or not isinstance(feats_post, torch.Tensor):
+        raise _lib.MfaHipError("gmm_statistics_twofeats: both feature matrices must be tensors on the device")
+    if tuple(feats_sum.shape) != tuple(feats_post.shape) or feats_sum.dtype != feats_post.dtype:
+        raise _lib.MfaHipError(f"gmm_statistics_twofeats: the matrices differ: {tuple(feats_post.shape)} {feats_post.dtype} for the "
+                               f"posteriors, {tuple(feats_sum.shape)} {feats_sum.dtype} for the sums")
+    if feats_sum.device != feats_post.device:
+        raise _lib.MfaHipError(f"gmm_statistics_twofeats: the matrices are on different devices ({feats_post.device}, {feats_sum.device})")
+    return _gmm_statistics(engine, feats_post, feats_sum, ali, tm, weights, into, "gmm_statistics_twofeats")
+
+
+def _gmm_statistics(engine, feats, feats_sum, ali, tm, weights, into, what) -> GmmStats:
     if engine.gmm is None:
-        raise _lib.MfaHipError("gmm_statistics: no acoustic model loaded (AlignmentEngine.load_gmm)")
+        raise _lib.MfaHipError(f"{what}: no acoustic model loaded (AlignmentEngine.load_gmm)")
     dev = engine.device
     gmm = engine.gmm
     G, D = gmm.num_gauss, gmm.dim
@@ -154,13 +174,15 @@ def gmm_statistics(engine, feats: torch.Tensor, ali: torch.Tensor, tm: Transitio
     n_tids = int(id2pdf.shape[0])
     st = into if into is not None else GmmStats.zeros(G, D, n_tids)
     if st.mean_acc.shape != (G, D) or st.tid_count.shape != (n_tids,):
-        raise ValueError("gmm_statistics: `into` does not fit the loaded model")
+        raise ValueError(f"{what}: `into` does not fit the loaded model")
     total = int(ali.shape[0])
     if feats.shape[0] != total or (total and feats.shape[1] != D):
-        raise _lib.MfaHipError(f"gmm_statistics: features {tuple(feats.shape)} for {total} frames of a model of dim {D}")
+        raise _lib.MfaHipError(f"{what}: features {tuple(feats.shape)} for {total} frames of a model of dim {D}")
     if feats.dtype != torch.float32 or not feats.is_cuda or not ali.is_cuda:
-        raise _lib.MfaHipError("gmm_statistics: features must be float32 and, like the alignments, on the device")
+        raise _lib.MfaHipError(f"{what}: features must be float32 and, like the alignments, on the device")
     feats = feats.contiguous()
+    if feats_sum is not None:
+        feats_sum = feats_sum.contiguous()
     ali = ali.to(torch.int32).contiguous()
     occ = torch.from_numpy(st.occ).to(dev)
     mean = torch.from_numpy(np.ascontiguousarray(st.mean_acc)).to(dev)
@@ -168,8 +190,13 @@ def gmm_statistics(engine, feats: torch.Tensor, ali: torch.Tensor, tm: Transitio
     tot = torch.tensor([st.tot_like, st.tot_count], dtype=torch.float64, device=dev)
     cnt = torch.from_numpy(st.tid_count).to(dev)
     d_pdf, d_w = torch.from_numpy(id2pdf).to(dev), torch.from_numpy(w).to(dev)
-    check(engine.ctx, engine.lib.mfa_gmm_acc_batch(engine.ctx, _ptr(feats), total, _ptr(ali), _ptr(d_pdf), _ptr(d_w), n_tids,
-                                                    _ptr(occ), _ptr(mean), _ptr(var), _ptr(tot), _ptr(cnt)), "mfa_gmm_acc_batch")
+    if feats_sum is None:
+        check(engine.ctx, engine.lib.mfa_gmm_acc_batch(engine.ctx, _ptr(feats), total, _ptr(ali), _ptr(d_pdf), _ptr(d_w), n_tids,
+                                                        _ptr(occ), _ptr(mean), _ptr(var), _ptr(tot), _ptr(cnt)), "mfa_gmm_acc_batch")
+    else:
+        check(engine.ctx, engine.lib.mfa_gmm_acc_twofeats_batch(engine.ctx, _ptr(feats), _ptr(feats_sum), total, _ptr(ali), _ptr(d_pdf),
+                                                                 _ptr(d_w), n_tids, _ptr(occ), _ptr(mean), _ptr(var), _ptr(tot),
+                                                                 _ptr(cnt)), "mfa_gmm_acc_twofeats_batch")
     st.occ, st.mean_acc, st.var_acc, st.tid_count = occ.cpu().numpy(), mean.cpu().numpy(), var.cpu().numpy(), cnt.cpu().numpy()
     t = tot.cpu().numpy()
     st.tot_like, st.tot_count = float(t[0]), float(t[1])
@@ -180,6 +207,22 @@ def gmm_statistics_host(gmm: DiagGmmModel, feats: np.ndarray, ali: np.ndarray, t
                         weights: Optional[np.ndarray] = None, into: Optional[GmmStats] = None, want_post: bool = False):
     """The same call on the host twin (mfa_debug_gmm_acc_host: no device, frames in ascending index): the specification the
     device is held to.  numpy arrays in; with ``want_post`` also returns every frame's posteriors [ΣT, largest pdf]."""
+    return _gmm_statistics_host(gmm, feats, None, ali, tm, weights, into, want_post)
+
+
+def gmm_statistics_twofeats_host(gmm: DiagGmmModel, feats_post: np.ndarray, feats_sum: np.ndarray, ali: np.ndarray,
+                                 tm: TransitionModel, weights: Optional[np.ndarray] = None, into: Optional[GmmStats] = None,
+                                 want_post: bool = False):
+    """``gmm_statistics_twofeats`` on the host twin (mfa_debug_gmm_acc_twofeats_host): posteriors from ``feats_post``, sums
+    from ``feats_sum``."""
+    if feats_sum is None:
+        raise _lib.MfaHipError("gmm_statistics_twofeats_host: no matrix to form the sums from")
+    if np.shape(feats_sum) != np.shape(feats_post):
+        raise _lib.MfaHipError(f"gmm_statistics_twofeats_host: the matrices differ in shape: {np.shape(feats_post)}, {np.shape(feats_sum)}")
+    return _gmm_statistics_host(gmm, feats_post, feats_sum, ali, tm, weights, into, want_post)
+
+
+def _gmm_statistics_host(gmm, feats, feats_sum, ali, tm, weights, into, want_post):
     lib = _lib.lib()
     id2pdf, w = tid_tables(tm, weights)
     n_tids = int(id2pdf.shape[0])
@@ -197,12 +240,17 @@ def gmm_statistics_host(gmm: DiagGmmModel, feats: np.ndarray, ali: np.ndarray, t
     cnt = np.ascontiguousarray(st.tid_count, dtype=np.int64)
     stride = int(np.diff(po).max())
     post = np.zeros((ali.shape[0], stride), dtype=np.float32) if want_post else None
-    rc = lib.mfa_debug_gmm_acc_host(D, gmm.num_pdfs, po.ctypes.data, gc.ctypes.data, mi.ctypes.data, iv.ctypes.data,
-                                    feats.ctypes.data, int(ali.shape[0]), pdf.ctypes.data, fw.ctypes.data, ali.ctypes.data, n_tids,
-                                    occ.ctypes.data, mean.ctypes.data, var.ctypes.data, tot.ctypes.data, cnt.ctypes.data,
-                                    None if post is None else post.ctypes.data, stride)
+    tail = (int(ali.shape[0]), pdf.ctypes.data, fw.ctypes.data, ali.ctypes.data, n_tids, occ.ctypes.data, mean.ctypes.data,
+            var.ctypes.data, tot.ctypes.data, cnt.ctypes.data, None if post is None else post.ctypes.data, stride)
+    if feats_sum is None:
+        rc = lib.mfa_debug_gmm_acc_host(D, gmm.num_pdfs, po.ctypes.data, gc.ctypes.data, mi.ctypes.data, iv.ctypes.data,
+                                        feats.ctypes.data, *tail)
+    else:
+        feats_sum = np.ascontiguousarray(feats_sum, dtype=np.float32)
+        rc = lib.mfa_debug_gmm_acc_twofeats_host(D, gmm.num_pdfs, po.ctypes.data, gc.ctypes.data, mi.ctypes.data, iv.ctypes.data,
+                                                 feats.ctypes.data, feats_sum.ctypes.data, *tail)
     if rc != 0:
-        raise _lib.MfaHipError(f"mfa_debug_gmm_acc_host: {'a pdf of more than 128 Gaussians' if rc == -2 else 'bad arguments'}")
+        raise _lib.MfaHipError(f"mfa_debug_gmm_acc{'_twofeats' if feats_sum is not None else ''}_host: {'a pdf of more than 128 Gaussians' if rc == -2 else 'bad arguments'}")
     st.occ, st.mean_acc, st.var_acc, st.tid_count = occ, mean, var, cnt
     st.tot_like, st.tot_count = float(tot[0]), float(tot[1])
     return (st, post) if want_post else st

@@ -12,10 +12,15 @@ labels — ``final.mdl`` and ``tree`` out.
 ``TriphoneTrainer`` (below) builds a tree from the previous model's alignments — tree statistics on the device, questions, tree
 and initial model on the host (``tree``) — and trains on it.  ``LdaTrainer`` is the LDA stage, on the tree it is given or on
 one it builds the same way: the previous model's alignments → LDA statistics and estimate → one
-Gaussian per pdf on the splice + LDA features → the same loop, shared through ``GmmTrainerBase``.
+Gaussian per pdf on the splice + LDA features → the same loop, shared through ``GmmTrainerBase``.  ``SatTrainer`` is the
+speaker-adapted stage on either feature path: per-speaker fMLLR under the previous model, a tree on the adapted features, the
+same loop with fMLLR re-estimated and composed at ``fmllr_iterations``, and after it the speaker-independent alignment model
+(``alignment_model``) from two-feature statistics — posteriors on the adapted features, sums of the unadapted ones —, so that
+the stage ends in a ``final.mdl`` + ``final.alimdl`` pair.
 
 The device is driven through a backend of three calls — ``equal_align``, ``align``, ``accumulate``, and for the tree
-``tree_accumulate`` and ``convert_alignments`` — so that the same loop runs on the host twins in tests.  ``DeviceBackend`` is ``CorpusAligner``'s machinery: features, CMVN and graphs as ``align``
+``tree_accumulate`` and ``convert_alignments``, for the SAT stage ``align_previous``, ``estimate_transforms`` and
+``accumulate_two_feats`` — so that the same loop runs on the host twins in tests.  ``DeviceBackend`` is ``CorpusAligner``'s machinery: features, CMVN and graphs as ``align``
 makes them, ``_align(..., keep_last=True)`` for features and alignments that stay on the device, ``gmm_statistics(into=)``.
 """
 from __future__ import annotations
@@ -152,6 +157,24 @@ def previous_models(previous):
     if hasattr(previous, "raw_tm"):
         return (previous.raw_tm, previous.raw_am, previous.tree)
     return tuple(previous)
+
+
+def alignment_model(raw_tm, raw_am, stats: GmmStats):
+    """The speaker-independent alignment model (``final.alimdl``) of a speaker-adapted model from its two-feature statistics
+    (``stats.gmm_statistics_twofeats``: posteriors on the adapted features, sums of the unadapted ones):
+    (``adapt.transition_update(raw_tm, stats.tid_count)``, ``mle.mle_update(raw_am, stats,
+    remove_low_count_gaussians=False)[0]``).
+
+    There is no mix-up.  The reference passes ``mixup=current_gaussians`` here (MFA/acoustic_modeling/sat.py:352-357), Kaldi's
+    ``train_sat.sh`` does not mix up, and ``CorpusAligner`` and ``mfa_fmllr_stats_model`` refuse an alignment model whose
+    Gaussians per pdf differ from ``final.mdl``'s: the layout of ``raw_am`` is kept, Gaussian for Gaussian."""
+    return _alignment_model(raw_tm, raw_am, stats)[:2]
+
+
+def _alignment_model(raw_tm, raw_am, stats: GmmStats):
+    """``alignment_model`` and the update's counts: (ali_raw_tm, ali_raw_am, Gaussians updated, variances floored)."""
+    new_am, updated, _removed, floored = mle.mle_update(raw_am, stats, remove_low_count_gaussians=False)
+    return _adapt.transition_update(raw_tm, stats.tid_count), new_am, updated, floored
 
 
 def default_roots(topology: kaldi_io.HmmTopology, shared_phones, silence_phones: Sequence[int]):
@@ -676,3 +699,267 @@ class LdaTrainer(GmmTrainerBase):
         return CorpusAligner(TransitionModel(self.raw_tm), DiagGmmModel.from_raw(self.raw_am), self.tree, self.lexicon,
                              lda=self.lda_mat, mfcc_options=self.mfcc_options, silence_phones=self.silence_phones,
                              raw_tm=self.raw_tm, raw_am=self.raw_am, **kw)
+
+
+# ---- the speaker-adapted (SAT) stage ----------------------------------------------------------------------------------------------
+FMLLR_MAX_DIM = 41                             # mfa_fmllr_acc_batch's limit (csrc/fmllr.hip)
+REFERENCE_FMLLR_ITERATIONS = (2, 4, 6, 12)     # SatTrainer.fmllr_iterations of the reference (MFA/acoustic_modeling/sat.py)
+
+
+class SatDeviceBackend(DeviceBackend):
+    """``SatTrainer``'s calls on the device: ``DeviceBackend``'s on features that carry per-speaker fMLLR transforms.
+    ``transforms`` [n_spk, D, D+1] float32 (rows in ``speaker_cmvn``'s order, named by ``speakers``; identity at first) is
+    what the resident features carry; ``steps`` keeps every ``estimate_transforms``' own matrices, before composition."""
+
+    def __init__(self, utterances, lexicon, options=None, mfcc_options: Optional[dict] = None, silence_phones: Sequence[int] = (),
+                 device: int = 0, engine=None, lda: Optional[np.ndarray] = None):
+        super().__init__(utterances, lexicon, options, mfcc_options, silence_phones, device, engine)
+        self.lda = None if lda is None else np.ascontiguousarray(lda, dtype=np.float32)
+        if self.lda is not None:
+            self.dim = int(self.lda.shape[0])
+        self.transforms: Optional[np.ndarray] = None
+        self.speakers: List[str] = []
+        self.steps: List[np.ndarray] = []
+
+    def _speaker_rows(self, al):
+        """(speaker → row, CMVN statistics) inside a ``_run``; ``speakers`` by row."""
+        spk_ids, cmvn = al.speaker_cmvn(self.utts)
+        self.speakers = [name for name, _row in sorted(spk_ids.items(), key=lambda kv: kv[1])]
+        return spk_ids, cmvn
+
+    def _aligned(self, al, beam: float, transforms) -> int:
+        usual = al.opt.beam
+        al.opt.beam = float(beam)
+        try:
+            with al._run():
+                results, self.kept = al._align(self.utts, False, False, transforms, keep_last=True)
+                self._speaker_rows(al)
+        finally:
+            al.opt.beam = usual
+        return sum(r is None for r in results)
+
+    def align_previous(self, raw_tm, raw_am, tree, previous_lda, beam: float, previous_transforms: Optional[np.ndarray] = None) -> int:
+        """Align with the previous stage's model on its own features — Δ+ΔΔ, or splice + ``previous_lda`` —; with
+        ``previous_transforms`` the features carry them and ``transforms`` starts from them, else from the identity.  The
+        resident features are the adapted ones."""
+        self.lda = None if previous_lda is None else np.ascontiguousarray(previous_lda, dtype=np.float32)
+        if self.lda is not None:
+            self.dim = int(self.lda.shape[0])
+        self.al = None
+        al = self._aligner(raw_tm, raw_am, tree)
+        prev = None if previous_transforms is None else np.ascontiguousarray(previous_transforms, dtype=np.float32)
+        failed = self._aligned(al, beam, prev)
+        D, n = self.dim, len(self.speakers)
+        if prev is not None and tuple(prev.shape) != (n, D, D + 1):
+            raise ValueError(f"previous_transforms of shape {tuple(prev.shape)} for {n} speakers of dimension {D}")
+        self.transforms = prev.copy() if prev is not None else np.tile(np.eye(D, D + 1, dtype=np.float32), (n, 1, 1))
+        self.steps = []
+        return failed
+
+    def estimate_transforms(self, raw_tm, raw_am) -> Dict:
+        """Per-speaker fMLLR from the resident adapted features and alignments under the model as its file holds it
+        (single-model statistics, ``opt.silence_weight``; ``fmllr.estimate_fmllr(min_count=opt.fmllr_min_count)``), each
+        composed onto ``transforms``; the resident features are recomputed with the composed transforms, the alignments
+        stay.  Returns speakers (estimated), rejected (names: too few frames, degenerate statistics, no gain), and over the
+        estimated speakers objf_impr_per_frame and frames."""
+        import torch
+
+        from . import fmllr as _fmllr
+        from .stats import fmllr_statistics
+
+        al = self.al
+        model = DiagGmmModel.from_raw(raw_am)
+        al.engine.load_gmm(model)
+        al._loaded = model
+        tm = TransitionModel(raw_tm)
+        n, D = len(self.speakers), self.dim
+        beta, K, G = np.zeros(n), np.zeros((n, D, D + 1)), np.zeros((n, D, D + 1, D + 1))
+        for _idx, feats, ali, fo, rows in self.kept:
+            ids, b, k, g = fmllr_statistics(al.engine, feats, fo, ali, tm, rows, self.silence_phones, self.opt.silence_weight)
+            beta[ids] += b; K[ids] += k; G[ids] += g
+        step = np.tile(np.eye(D, D + 1, dtype=np.float32), (n, 1, 1))
+        rejected, impr, frames, done = [], 0.0, 0.0, 0
+        for s in range(n):
+            step[s], gain, why = _fmllr.estimate_fmllr(beta[s], K[s], G[s], min_count=self.opt.fmllr_min_count)
+            if why is not None:
+                rejected.append(self.speakers[s])
+                continue
+            done, impr, frames = done + 1, impr + gain, frames + float(beta[s])
+            self.transforms[s] = _fmllr.compose_transforms(step[s], self.transforms[s])
+        self.steps.append(step)
+        d_lda = None if self.lda is None else torch.from_numpy(self.lda).to(al.engine.device)
+        d_w = torch.from_numpy(self.transforms).to(al.engine.device)
+        with al._run():
+            spk_ids, cmvn = self._speaker_rows(al)
+            self.kept = [(idx, al._batch_features(self.utts, idx, spk_ids, cmvn, d_lda, d_w)[0], ali, fo, rows)
+                         for idx, _feats, ali, fo, rows in self.kept]
+        return dict(speakers=done, rejected=rejected, objf_impr_per_frame=impr / frames if frames else 0.0, frames=frames)
+
+    def align(self, raw_tm, raw_am, tree, beam: float) -> int:
+        """Realignment on the adapted features: one pass with ``transforms`` in the features."""
+        return self._aligned(self._aligner(raw_tm, raw_am, tree), beam, self.transforms)
+
+    def accumulate_two_feats(self, raw_tm, raw_am) -> GmmStats:
+        """Two-feature statistics of the resident batches under the model as its file holds it: posteriors on the resident
+        adapted features, sums of the same frames' unadapted ones (``CorpusAligner._twofeats_accumulate``)."""
+        al = self.al
+        with al._run():
+            spk_ids, cmvn = self._speaker_rows(al)
+            return al._twofeats_accumulate(self.utts, self.kept, spk_ids, cmvn, raw_am, TransitionModel(raw_tm))
+
+
+class SatTrainer(GmmTrainerBase):
+    """The reference's ``SatTrainer`` (MFA/acoustic_modeling/sat.py): a speaker-adapted model on a tree built here, and its
+    speaker-independent alignment model.  ``SatTrainer(utterances, lexicon, previous=(raw_tm, raw_am, tree)).train()`` then
+    ``write(directory)`` (``final.mdl``, ``tree``, ``final.alimdl``, with an LDA ``lda.mat``) / ``aligner()``.  ``previous`` may
+    also be a trained stage: an ``LdaTrainer``'s ``lda_mat`` and a ``SatTrainer``'s ``transforms`` are picked up
+    (``previous_lda=`` / ``previous_transforms=`` give them by hand).
+
+      iteration 0   align with ``previous`` on its own features (Δ+ΔΔ, or splice + LDA; with ``previous_transforms`` in them)
+                    → unless ``previous_transforms`` was given, per-speaker fMLLR under the previous model
+                    (``backend.estimate_transforms``) → tree statistics of the adapted features, questions, tree, initial
+                    model, alignments converted (``tree_stage``) → GMM statistics → transition update, ``mle_update``
+      iteration i   ``GmmTrainerBase._iterate``; at an iteration of ``fmllr_iterations``, after the realignment if one is
+                    scheduled and before the statistics (sat.py:279-297): fMLLR under the current model, composed onto
+                    ``transforms``; the resident features are recomputed, the alignments stay
+      afterwards    two-feature statistics of the resident batches (``stats.gmm_statistics_twofeats``: posteriors on the
+                    adapted features, sums of the unadapted ones) → ``alignment_model`` → ``ali_raw_tm`` / ``ali_raw_am``,
+                    with ``alimdl_stats`` and ``history_alimdl`` = {loglike, frames, updated, floored}
+
+    Options carry the reference's names and defaults (sat.py:159-220, triphone.py): ``num_iterations`` 35, ``num_leaves`` 2500,
+    ``max_gaussians`` 15000, ``power`` 0.2, ``fmllr_iterations`` (2, 4, 6, 12) — entries outside 1..``num_iterations`` are
+    refused —, ``boost_silence`` 1.0 (in ``align_options``), realignment at every tenth iteration,
+    ``final_gaussian_iteration`` = ``num_iterations`` − 10.  ``history`` as ``TriphoneTrainer``'s; iteration 0's entry and the
+    scheduled iterations' carry ``fmllr`` = {speakers, rejected, objf_impr_per_frame, frames}.  ``transforms`` [n_spk, D, D+1]
+    and ``speakers`` (their rows' names) stay on the trainer, ``fmllr_steps`` keeps every estimate before composition.
+    Refused with a message: a feature dimension above the GMM statistics' 48, and Δ+ΔΔ features above fMLLR's 41."""
+
+    def __init__(self, utterances=None, lexicon=None, previous=None, previous_lda: Optional[np.ndarray] = None,
+                 previous_transforms: Optional[np.ndarray] = None, roots=None, extra_questions: Sequence[Sequence[int]] = (),
+                 num_iterations: int = 35, num_leaves: int = 2500, max_gaussians: int = 15000, cluster_threshold: float = -1.0,
+                 power: float = 0.2, fmllr_iterations: Sequence[int] = REFERENCE_FMLLR_ITERATIONS, align_options=None,
+                 seed: int = 1234, min_gaussian_occupancy: float = 3.0, shared_phones: Optional[Sequence[Sequence[int]]] = None,
+                 silence_phones: Sequence[int] = (), mfcc_options: Optional[dict] = None, device: int = 0, engine=None,
+                 backend=None):
+        from . import _lib
+        from .aligner import AlignOptions
+
+        if previous is None or lexicon is None:
+            raise ValueError("SatTrainer needs a lexicon and the previous stage's (raw_tm, raw_am, tree)")
+        if num_iterations < 1 or num_leaves < 1:
+            raise ValueError("num_iterations and num_leaves must be at least 1")
+        self.fmllr_iterations = tuple(int(i) for i in fmllr_iterations)
+        if any(i < 1 or i > int(num_iterations) for i in self.fmllr_iterations):
+            raise ValueError(f"SatTrainer: fmllr_iterations {self.fmllr_iterations} outside 1..{int(num_iterations)}")
+        self.lexicon, self.previous = lexicon, previous_models(previous)
+        if previous_lda is None:
+            previous_lda = getattr(previous, "lda_mat", None)
+        if previous_transforms is None:
+            previous_transforms = getattr(previous, "transforms", None)
+        self.lda_mat = None if previous_lda is None else np.asarray(previous_lda, dtype=np.float32)
+        self.previous_transforms = None if previous_transforms is None else np.asarray(previous_transforms, dtype=np.float32)
+        self.roots, self.extra_questions = roots, [list(q) for q in extra_questions]
+        self.num_iterations, self.num_leaves, self.max_gaussians = int(num_iterations), int(num_leaves), int(max_gaussians)
+        self.cluster_threshold, self.power, self.seed = float(cluster_threshold), float(power), int(seed)
+        self.min_gaussian_occupancy = float(min_gaussian_occupancy)
+        self.shared_phones = shared_phones
+        self.opt = align_options or AlignOptions(boost_silence=1.0)
+        self.silence_phones, self.mfcc_options = list(silence_phones), dict(mfcc_options or {})
+        self.raw_tm, self.raw_am, self.tree = self.previous
+        dim, limit = int(self.raw_am.dim), int(_lib.lib().mfa_gmm_acc_max_dim())
+        if self.lda_mat is not None and int(self.lda_mat.shape[0]) != dim:
+            raise ValueError(f"SatTrainer: an LDA matrix of {self.lda_mat.shape[0]} rows for a previous model of dimension {dim}")
+        if dim > limit:
+            raise ValueError(f"SatTrainer: feature dimension {dim} above {limit} (the GMM statistics' feature dimension)")
+        if self.lda_mat is None and dim > FMLLR_MAX_DIM:
+            raise ValueError(f"SatTrainer: Δ+ΔΔ features of dimension {dim} above {FMLLR_MAX_DIM} (the fMLLR statistics' on that path)")
+        self.backend = backend if backend is not None else SatDeviceBackend(utterances, lexicon, self.opt, self.mfcc_options,
+                                                                             self.silence_phones, device, engine, self.lda_mat)
+        self.initial_gaussians = self.raw_am.num_pdfs           # until the tree is built
+        self.final_gaussian_iteration = self.num_iterations - 10
+        self.realignment_iterations = list(range(10, self.num_iterations, 10))
+        self.current_gaussians = self.initial_gaussians
+        self.rng = np.random.default_rng(self.seed)
+        self.history: List[Dict] = []
+        self.initial_stats: Optional[GmmStats] = None
+        self.tree_stats = None
+        self.tree_record: Optional[Dict] = None
+        self.ali_raw_tm = self.ali_raw_am = None
+        self.alimdl_stats: Optional[GmmStats] = None
+        self.history_alimdl: Optional[Dict] = None
+        self.iteration = 0
+
+    @property
+    def transforms(self) -> Optional[np.ndarray]:
+        return self.backend.transforms
+
+    @property
+    def speakers(self) -> List[str]:
+        return self.backend.speakers
+
+    @property
+    def fmllr_steps(self) -> List[np.ndarray]:
+        return self.backend.steps
+
+    def train(self) -> "SatTrainer":
+        b = self.backend
+        prev_tm, prev_am, prev_tree = self.previous
+        self.iteration = 0
+        failed = b.align_previous(prev_tm, prev_am, prev_tree, self.lda_mat, self.opt.beam, self.previous_transforms)
+        fmllr = None if self.previous_transforms is not None else b.estimate_transforms(prev_tm, prev_am)
+        self.raw_tm, self.raw_am, self.tree, info = tree_stage(b, prev_tm, prev_tm.topo, self.roots, self.shared_phones,
+                                                               self.silence_phones, self.extra_questions, self.num_leaves,
+                                                               self.cluster_threshold)
+        self.tree_stats, self.tree_record = info.pop("tree_stats"), info.pop("tree_record")
+        self.initial_gaussians = self.current_gaussians = self.raw_am.num_pdfs
+        stats = b.accumulate(self.raw_tm, self.raw_am)
+        self.initial_stats = stats.copy()
+        self._update(stats, failed, True, min_gaussian_occupancy=self.min_gaussian_occupancy)
+        self.history[-1].update(info)
+        if fmllr is not None:
+            self.history[-1]["fmllr"] = fmllr
+        self._iterate(failed, self.opt.beam)
+        self.finalize_training()
+        return self
+
+    def _before_statistics(self, iteration: int) -> Optional[Dict]:
+        if iteration not in self.fmllr_iterations:
+            return None
+        return dict(fmllr=self.backend.estimate_transforms(self.raw_tm, self.raw_am))
+
+    def finalize_training(self) -> None:
+        """The alignment model: two-feature statistics of the resident batches under the final model → ``alignment_model``."""
+        st = self.backend.accumulate_two_feats(self.raw_tm, self.raw_am)
+        self.ali_raw_tm, self.ali_raw_am, updated, floored = _alignment_model(self.raw_tm, self.raw_am, st)
+        self.alimdl_stats = st
+        self.history_alimdl = dict(loglike=st.loglike_per_frame, frames=st.tot_count, updated=updated, floored=floored)
+
+    def write(self, directory) -> List[Path]:
+        """``final.mdl``, ``tree``, ``final.alimdl`` (``ali_raw_tm`` + ``ali_raw_am``) and, with an LDA, ``lda.mat``."""
+        if self.ali_raw_am is None:
+            raise ValueError("SatTrainer.write: train has not been run")
+        files = super().write(directory)
+        out = Path(directory)
+        with open(out / "final.alimdl", "wb") as f:
+            kaldi_io.write_model(f, self.ali_raw_tm, self.ali_raw_am)
+        files.append(out / "final.alimdl")
+        if self.lda_mat is not None:
+            with open(out / "lda.mat", "wb") as f:
+                f.write(b"\0B")
+                kaldi_io.write_matrix(f, self.lda_mat)
+            files.append(out / "lda.mat")
+        return files
+
+    def aligner(self, **kw):
+        """A ``CorpusAligner`` on the trained pair (on the training engine when the device backend ran): ``final.mdl``,
+        ``ali_am=`` / ``raw_ali_am=`` the alignment model, ``lda=`` when there is one.  Both passes run on ``final.mdl``'s
+        transition model, as ``CorpusAligner`` does for any SAT model: ``ali_raw_tm`` is written to ``final.alimdl`` and not
+        used here."""
+        from .aligner import CorpusAligner
+
+        kw.setdefault("engine", getattr(self.backend, "engine", None))
+        kw.setdefault("options", self.opt)
+        return CorpusAligner(TransitionModel(self.raw_tm), DiagGmmModel.from_raw(self.raw_am), self.tree, self.lexicon,
+                             lda=self.lda_mat, ali_am=DiagGmmModel.from_raw(self.ali_raw_am), mfcc_options=self.mfcc_options,
+                             silence_phones=self.silence_phones, raw_tm=self.raw_tm, raw_am=self.raw_am,
+                             raw_ali_am=self.ali_raw_am, **kw)

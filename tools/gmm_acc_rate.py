@@ -4,7 +4,9 @@ does not depend on their values).  Alignments are runs of 3 – 12 frames per pd
 Reported: the median over ``--rounds`` calls of mfa_gmm_acc_batch per stage, by the library's event pairs (mfa_kernel_timing,
 slots 8 – 11: lookup, ordering, sums, reduction); the MFCC launch on the same batch (slot 0); the streaming floor — features
 read once and accumulators read and written once, at 8 TB/s —; and the host twin (mfa_debug_gmm_acc_host, one thread) on the
-first ``--host-frames`` frames of the same data, with its rate carried to the whole batch.  GPU.
+first ``--host-frames`` frames of the same data, with its rate carried to the whole batch.  Beside the one-feature stages
+the same four slots of mfa_gmm_acc_twofeats_batch on the same batch (``two_feats``: the second matrix is an affine image of
+the first, resident as well), when the library has it (an older build under MFA_HIP_SO has not).  GPU.
   python tools/gmm_acc_rate.py [--utts 8192] [--seconds 10] [--rounds 10] [--host-frames 200000] [--commit ID]
                                [--out profiles/gmm_acc_rate.json | --out '']"""
 import argparse
@@ -19,7 +21,7 @@ import numpy as np
 import torch
 
 from montreal_forced_aligner_amd import model as M
-from montreal_forced_aligner_amd.engine import AlignmentEngine, GmmStats, gmm_statistics, gmm_statistics_host
+from montreal_forced_aligner_amd.engine import AlignmentEngine, GmmStats, gmm_statistics, gmm_statistics_host, gmm_statistics_twofeats
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--utts", type=int, default=8192)
@@ -104,6 +106,25 @@ for _ in range(args.rounds):
     bits = got.occ.tobytes() + got.mean_acc.tobytes() + got.var_acc.tobytes()
     first = bits if first is None else first
     reproducible = first == bits
+
+# the two-feature path: the same batch, the sums from a second resident matrix
+two = None
+if hasattr(eng.lib, "mfa_gmm_acc_twofeats_batch"):
+    feats_sum = feats * 0.9 + 0.25
+    for _ in range(args.warmup):
+        gmm_statistics_twofeats(eng, feats, feats_sum, ali, tm, into=st)
+    torch.cuda.synchronize()
+    two = {"lookup": [], "order": [], "sums": [], "reduce": []}
+    for _ in range(args.rounds):
+        eng.reset_kernel_times()
+        torch.cuda.synchronize()
+        got2 = gmm_statistics_twofeats(eng, feats, feats_sum, ali, tm)
+        torch.cuda.synchronize()
+        for k, name in enumerate(two):
+            two[name].append(eng._kernel_time(8 + k)["ms"])
+    two_follows_post = bool(got2.occ.tobytes() == got.occ.tobytes() and got2.tot_like == got.tot_like
+                            and got2.mean_acc.tobytes() != got.mean_acc.tobytes())
+    del feats_sum
 eng.kernel_timing(False)
 
 n_host = min(T, args.host_frames)
@@ -127,9 +148,20 @@ rep = {"commit": commit, "utterances": args.utts, "seconds_per_utterance": args.
        "feature_bytes": T * D * 4, "accumulator_bytes": acc_bytes, "streaming_floor_ms_at_8TBps": round(floor_ms, 4),
        "host_twin_frames": n_host, "host_twin_ms": round(t_host, 1), "host_twin_ms_whole_batch_at_that_rate": round(t_host * T / n_host, 0),
        "device_counts_equal_host_twin": counts_equal, "two_rounds_same_bits": bool(reproducible)}
+if two is not None:
+    rep["two_feats"] = {"lookup_ms": round(med(two["lookup"]), 4), "order_ms": round(med(two["order"]), 4),
+                        "sums_ms": round(med(two["sums"]), 4), "reduce_ms": round(med(two["reduce"]), 4),
+                        "stages_total_ms": round(sum(med(v) for v in two.values()), 4),
+                        "sums_ms_all_rounds": [round(v, 4) for v in two["sums"]],
+                        "occ_and_loglike_equal_one_feature": two_follows_post}
+rep["sums_ms_all_rounds"] = [round(v, 4) for v in stage["sums"]]
 print(f"{T} frames x {D}, {P} pdfs x {NG}: lookup {rep['lookup_ms']:.3f} + order {rep['order_ms']:.3f} + sums {rep['sums_ms']:.3f} + reduce "
       f"{rep['reduce_ms']:.3f} = {total:.3f} ms; MFCC {rep['mfcc_ms']:.3f} ms; floor {floor_ms:.3f} ms; host twin {t_host:.0f} ms on {n_host} frames",
       flush=True)
+if two is not None:
+    t2 = rep["two_feats"]
+    print(f"two features: lookup {t2['lookup_ms']:.3f} + order {t2['order_ms']:.3f} + sums {t2['sums_ms']:.3f} + reduce {t2['reduce_ms']:.3f} "
+          f"= {t2['stages_total_ms']:.3f} ms", flush=True)
 print(json.dumps(rep))
 if args.out:
     with open(args.out, "w") as f:
