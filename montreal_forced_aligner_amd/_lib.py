@@ -101,7 +101,7 @@ def build_native(force: bool = False, verbose: bool = False) -> Path:
     src_dir = _PKG / "csrc"
     srcs = [src_dir / s for s in _SOURCES]
     headers = ("ctx.hpp", "dev_buf.hpp", "gmm_common.hpp", "gmm_f32.hpp", "gmm_split.hpp", "gmm_pack.hpp", "viterbi_common.hpp", "viterbi_eps.hpp", "viterbi_wave.hpp", "viterbi_small.hpp",
-               "resample_plan.hpp", "pitch_plan.hpp", "compress_math.hpp", "gmm_acc_math.hpp", "tid_lookup.hpp", "align_equal_math.hpp", "lda_acc_math.hpp", "mllt_acc_math.hpp", "tree_acc_math.hpp")
+               "resample_plan.hpp", "pitch_plan.hpp", "compress_math.hpp", "gmm_acc_math.hpp", "gmm_acc_twin.hpp", "acc_posterior.hpp", "acc_segments.hpp", "tid_lookup.hpp", "align_equal_math.hpp", "lda_acc_math.hpp", "mllt_acc_math.hpp", "tree_acc_math.hpp")
     deps = srcs + [src_dir / h for h in headers] + [_PKG.parent / "include" / "mfa_hip.h"]
     if not force and _SO.exists() and all(_SO.stat().st_mtime >= d.stat().st_mtime for d in deps if d.exists()):
         return _SO

@@ -3,34 +3,31 @@
 // Arithmetic contract: include/mfa_hip.h "GMM statistics"; the shared arithmetic: gmm_acc_math.hpp; the host twin:
 // gmm_acc_host.cpp.
 //
+// The five steps are the segment skeleton of acc_segments.hpp, the posterior phase is acc_posterior.hpp's:
 //   lookup   fmllr_tid_lookup_kernel (tid_lookup.hpp): per frame the sort key (pdf; num_pdfs = takes no part), the pdfs'
-//            frame counts and the transition-id counts (integer atomics: exact)
-//   order    rocPRIM radix_sort_pairs (stable) of (pdf, frame index): every pdf's segment lists its frames in ascending
-//            frame index, so every sum below is a function of the input alone
-//   scan     one workgroup: segment starts, first unit and first partial row of every pdf
+//            frame counts and the transition-id counts
+//   order    rocPRIM radix_sort_pairs (stable) of (pdf, frame index)
+//   scan     segment starts, first unit and first partial row of every pdf
 //   sums     gmm_acc_kernel, one workgroup per unit = (pdf, chunk of kChunk consecutive entries of its segment)
 //   reduce   per pdf, the units' partials in chunk order into the caller's accumulators; the two totals in unit order
-// No floating-point atomics anywhere.
 // mfa_gmm_acc_twofeats_batch (Kaldi gmm-acc-stats-twofeats: the alignment model of the SAT stage) is the same five steps with
 // gmm_acc_kernel<true>: posteriors from one feature matrix, the sums' x from a second one of the same frames.
 #include <algorithm>
-#include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "acc_posterior.hpp"
+#include "acc_segments.hpp"
 #include "ctx.hpp"
-#include "gmm_acc_math.hpp"
 #include "tid_lookup.hpp"
 
 namespace {
 
 constexpr int kChunk = 512;      // C: entries of a pdf's segment per unit (mfa_gmm_acc_chunk_frames)
-constexpr int kTile = 32;        // frames staged in LDS at a time; 8 per wavefront in the posterior phase
-constexpr int kMaxGauss = 128;   // two rounds of lane = Gaussian
-constexpr int kMaxDim = 48;      // a thread owns columns l, l + 16, l + 32 (l < 16) of 8 Gaussians
-constexpr int kXStride = kMaxDim + 1;
+constexpr int kTile = kAccTile, kMaxGauss = kAccMaxGauss, kXStride = kAccXStride;
+constexpr int kMaxDim = kAccMaxDim;   // a thread owns columns l, l + 16, l + 32 (l < 16) of 8 Gaussians
 constexpr int kColsPerThread = kMaxDim / 16, kGaussPerThread = kMaxGauss / 16;
-static_assert(kChunk % kTile == 0 && kTile == 4 * 8 && kMaxDim % 16 == 0 && kMaxGauss == 2 * 64, "gmm_acc_kernel tiling");
+static_assert(kChunk % kTile == 0 && kMaxDim % 16 == 0, "gmm_acc_kernel tiling");
 
 struct AccParams {
   int D, kpad, num_pdfs;
@@ -49,41 +46,21 @@ struct AccParams2 : AccParams {
 template <bool kTwoFeats> struct AccParamsOf { using type = AccParams; };
 template <> struct AccParamsOf<true> { using type = AccParams2; };
 
-// One workgroup: exclusive scans over the pdfs of (frames, units, partial rows = units × Gaussians).
-__global__ __launch_bounds__(256) void gmm_acc_scan_kernel(const int32_t *cnt, const int32_t *ngauss, int P, int32_t *seg_off,
-                                                           int32_t *unit_base, int64_t *prow) {
-  __shared__ int32_t sf[256], su[256];
-  __shared__ int64_t sr[256];
-  const int per = (P + 255) / 256, a = min(P, (int)threadIdx.x * per), b = min(P, a + per);
-  int32_t f = 0, u = 0;
-  int64_t r = 0;
-  for (int p = a; p < b; p++) { const int un = (cnt[p] + kChunk - 1) / kChunk; f += cnt[p]; u += un; r += (int64_t)un * ngauss[p]; }
-  sf[threadIdx.x] = f; su[threadIdx.x] = u; sr[threadIdx.x] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int32_t af = 0, au = 0;
-    int64_t ar = 0;
-    for (int i = 0; i < 256; i++) {
-      const int32_t tf = sf[i], tu = su[i];
-      const int64_t tr = sr[i];
-      sf[i] = af; su[i] = au; sr[i] = ar;
-      af += tf; au += tu; ar += tr;
-    }
-    seg_off[P] = af; unit_base[P] = au; prow[P] = ar;
+// acc_scan_kernel<3> over the pdfs: frames, units, partial rows = units × Gaussians
+struct GmmAccScan {
+  const int32_t *cnt; const int32_t *ngauss;
+  int32_t *seg_off; int32_t *unit_base; int64_t *prow;
+  __device__ void add(int q, int64_t (&v)[3]) const {
+    const int64_t c = cnt[q], un = (c + kChunk - 1) / kChunk;
+    v[0] += c; v[1] += un; v[2] += un * ngauss[q];
   }
-  __syncthreads();
-  f = sf[threadIdx.x]; u = su[threadIdx.x]; r = sr[threadIdx.x];
-  for (int p = a; p < b; p++) {
-    seg_off[p] = f; unit_base[p] = u; prow[p] = r;
-    const int un = (cnt[p] + kChunk - 1) / kChunk;
-    f += cnt[p]; u += un; r += (int64_t)un * ngauss[p];
-  }
-}
+  __device__ void put(int q, const int64_t (&v)[3]) const { seg_off[q] = (int32_t)v[0]; unit_base[q] = (int32_t)v[1]; prow[q] = v[2]; }
+};
 
 // grid: an upper bound of the units (the true count is unit_base[num_pdfs], known on the device only); 256 threads.
-// Posterior phase: wavefront = 8 frames of the tile, lane = Gaussian (two rounds of 64), weights of the round in LDS as
-// [k][Gaussian].  Sum phase: thread (gg = tid / 16, l = tid % 16) keeps mean / var of Gaussians gg + 16 j (j < 8) in columns
-// l + 16 c (c < 3) in registers over the whole chunk: 48 double FMAs per frame at 128 Gaussians, 6 · ceil(n / 16) in general.
+// Posterior phase: acc_posterior.hpp.  Sum phase: thread (gg = tid / 16, l = tid % 16) keeps mean / var of Gaussians gg + 16 j
+// (j < 8) in columns l + 16 c (c < 3) in registers over the whole chunk: 48 double FMAs per frame at 128 Gaussians,
+// 6 · ceil(n / 16) in general.
 // kTwoFeats (mfa_gmm_acc_twofeats_batch): the posterior phase reads the rows of p.feats as ever, the sum phase the same
 // frames' rows of p.feats_sum, gathered with them and staged in a tile of their own (x2_s: 6 272 B more LDS, 53 760 B in all;
 // three workgroups of a CU's 160 KB either way).  Without it the kernel is the one-feature kernel, instruction for instruction.
@@ -96,19 +73,13 @@ __global__ __launch_bounds__(256) void gmm_acc_kernel(typename AccParamsOf<kTwoF
   __shared__ float fw_s[kTile], fll_s[kTile];
   const int unit = blockIdx.x, P = p.num_pdfs;
   if (unit >= p.unit_base[P]) return;
-  int lo = 0, hi = P;                 // unit_base[lo] <= unit < unit_base[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (p.unit_base[mid] <= unit) lo = mid; else hi = mid;
-  }
-  const int pdf = lo, chunk = unit - p.unit_base[pdf];
+  const int pdf = acc_owner(p.unit_base, P, unit), chunk = unit - p.unit_base[pdf];
   const int ng = p.ngauss[pdf], r0 = p.row0[pdf], D = p.D;
   const int s0 = p.seg_off[pdf] + chunk * kChunk, s1 = min(p.seg_off[pdf + 1], s0 + kChunk);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, gg = tid >> 4, l = tid & 15;
   const int rounds = (ng + 63) >> 6;
   float gcv[2];
-#pragma unroll
-  for (int rnd = 0; rnd < 2; rnd++) gcv[rnd] = lane + 64 * rnd < ng ? p.gc[r0 + lane + 64 * rnd] : 0.0f;
+  acc_gconsts(p.gc, r0, ng, lane, gcv);
   double m[kGaussPerThread][kColsPerThread], v[kGaussPerThread][kColsPerThread];
 #pragma unroll
   for (int j = 0; j < kGaussPerThread; j++)
@@ -116,78 +87,17 @@ __global__ __launch_bounds__(256) void gmm_acc_kernel(typename AccParamsOf<kTwoF
     for (int c = 0; c < kColsPerThread; c++) { m[j][c] = 0.0; v[j][c] = 0.0; }
   double occ = 0.0, tot_like = 0.0, tot_count = 0.0;
 
-  // The gather of a tile is two dependent global loads (sorted index, then the row): the next tile's rows are fetched into
-  // registers while this tile is worked on, and only stored to LDS at the top of the next round.
-  constexpr int kStage = kTile * kMaxDim / 256;
-  static_assert(kStage * 256 == kTile * kMaxDim, "every thread stages the same number of elements");
-  float nx[kStage], nx2[kTwoFeats ? kStage : 1], nw = 0.0f;
-  auto fetch = [&](int t0) {
-    const int nc = min(kTile, s1 - t0);
-#pragma unroll
-    for (int i = 0; i < kStage; i++) {
-      const int e = tid + 256 * i, t = e / kMaxDim, k = e % kMaxDim;
-      if constexpr (kTwoFeats) {
-        const bool in = t < nc && k < D;
-        const size_t at = in ? (size_t)p.idx[t0 + t] * D + k : 0;
-        nx[i] = in ? p.feats[at] : 0.0f;
-        nx2[i] = in ? p.feats_sum[at] : 0.0f;
-      } else {
-        nx[i] = t < nc && k < D ? p.feats[(size_t)p.idx[t0 + t] * D + k] : 0.0f;       // columns up to 48 read as 0
-      }
-    }
-    if (tid < kTile) nw = tid < nc ? p.weight[p.idx[t0 + tid]] : 0.0f;
-  };
-  fetch(s0);
+  const float *feats_sum = nullptr;
+  float (*x2)[kXStride] = nullptr;
+  if constexpr (kTwoFeats) { feats_sum = p.feats_sum; x2 = x2_s; }
+  AccStaged<kTwoFeats> next;          // the next tile's rows: in flight while this tile is worked on
+  acc_fetch(next, p.feats, feats_sum, p.idx, p.weight, D, s0, s1, tid);
   for (int t0 = s0; t0 < s1; t0 += kTile) {
     const int nc = min(kTile, s1 - t0);
     __syncthreads();                  // the previous tile's sum phase has read x_s, post_s, fw_s, fll_s
-#pragma unroll
-    for (int i = 0; i < kStage; i++) {
-      const int e = tid + 256 * i;
-      x_s[e / kMaxDim][e % kMaxDim] = nx[i];
-      if constexpr (kTwoFeats) x2_s[e / kMaxDim][e % kMaxDim] = nx2[i];
-    }
-    if (tid < kTile) fw_s[tid] = nw;
-    if (t0 + kTile < s1) fetch(t0 + kTile);
-    float ll[8][2];
-#pragma unroll
-    for (int rnd = 0; rnd < 2; rnd++) {
-      if (rnd < rounds) {
-        if (rounds > 1 || t0 == s0) {   // one round: its weights stay for the whole chunk
-          __syncthreads();              // the other round's readers are done
-          for (int i = tid; i < 2 * D * 64; i += 256) {
-            const int k = i >> 6, g = (i & 63) + 64 * rnd;
-            w_s[k][i & 63] = g < ng ? p.w[mfa_packed_offset(r0 + g, k, p.kpad)] : 0.0f;
-          }
-        }
-        __syncthreads();
-        const bool have = lane + 64 * rnd < ng;
-        float blk[8];                   // rows past the chunk's end are zeros: computed, never used
-        gmm_acc_loglike_block<8>(gcv[rnd], D, &w_s[0][lane], 64, &w_s[D][lane], 64, x_s[wave * 8], kXStride, blk);
-#pragma unroll
-        for (int f = 0; f < 8; f++) ll[f][rnd] = have && wave * 8 + f < nc ? blk[f] : -INFINITY;
-      } else {
-#pragma unroll
-        for (int f = 0; f < 8; f++) ll[f][rnd] = -INFINITY;
-      }
-    }
-#pragma unroll
-    for (int f = 0; f < 8; f++) {
-      const int t = wave * 8 + f;
-      if (t < nc) {                     // the same for the whole wavefront
-        float mx = fmaxf(ll[f][0], ll[f][1]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-        const float e0 = lane < ng ? expf(ll[f][0] - mx) : 0.0f, e1 = lane + 64 < ng ? expf(ll[f][1] - mx) : 0.0f;
-        float sum = e0 + e1;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        const float inv = 1.0f / sum, wgt = fw_s[t];
-        post_s[t][lane] = gmm_acc_posterior(e0, inv, wgt);
-        post_s[t][lane + 64] = gmm_acc_posterior(e1, inv, wgt);
-        if (lane == 0) fll_s[t] = gmm_acc_frame_loglike(mx, sum);
-      }
-    }
+    acc_stage_store(next, x_s, x2, fw_s, tid);
+    if (t0 + kTile < s1) acc_fetch(next, p.feats, feats_sum, p.idx, p.weight, D, t0 + kTile, s1, tid);
+    acc_posterior_phase<false>(p.w, p.kpad, r0, ng, D, gcv, t0, s0, nc, x_s, w_s, post_s, fw_s, fll_s, tid, lane, wave, rounds);
     __syncthreads();
     for (int t = 0; t < nc; t++) {
       float xf[kColsPerThread];
@@ -202,10 +112,7 @@ __global__ __launch_bounds__(256) void gmm_acc_kernel(typename AccParamsOf<kTwoF
         }
       }
     }
-    if (tid < kMaxGauss)
-      for (int t = 0; t < nc; t++) occ += (double)post_s[t][tid];
-    if (tid == 255)
-      for (int t = 0; t < nc; t++) gmm_acc_total(fw_s[t], fll_s[t], tot_like, tot_count);
+    acc_occ_totals(post_s, fw_s, fll_s, nc, tid, occ, tot_like, tot_count);
   }
 
   const int W = 2 * D + 1;
@@ -233,8 +140,7 @@ struct ReduceParams {
 };
 
 // grid (pdf, tile of 256 elements of its [n_gauss][2·D + 1] sums): the caller's value, then the pdf's partials in chunk
-// order.  The loads of 8 chunks are issued together (a pdf that holds a seventh of the corpus has thousands of chunks and one
-// thread per element to walk them); the additions stay one after the other, in chunk order.
+// order (acc_ordered_sum).
 __global__ __launch_bounds__(256) void gmm_acc_reduce_kernel(ReduceParams p) {
   const int pdf = blockIdx.x, nu = p.unit_base[pdf + 1] - p.unit_base[pdf];
   if (nu == 0) return;
@@ -245,37 +151,8 @@ __global__ __launch_bounds__(256) void gmm_acc_reduce_kernel(ReduceParams p) {
   const double *base = p.partial + (size_t)p.prow[pdf] * W + e;
   const int g = e / W, c = e % W;
   double *dst = c == 0 ? p.occ + g0 + g : c <= D ? p.mean + (g0 + g) * D + (c - 1) : p.var + (g0 + g) * D + (c - 1 - D);
-  double a = *dst;
-  int ch = 0;
-  for (; ch + 8 <= nu; ch += 8) {
-    double v[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) v[i] = base[(size_t)(ch + i) * n];
-#pragma unroll
-    for (int i = 0; i < 8; i++) a += v[i];
-  }
-  for (; ch < nu; ch++) a += base[(size_t)ch * n];
-  *dst = a;
+  *dst = acc_ordered_sum(base, (size_t)n, nu, *dst);
 }
-
-// one workgroup: the units' totals in unit order onto the caller's two
-__global__ __launch_bounds__(256) void gmm_acc_totals_kernel(const double *unit_tot, const int32_t *unit_base, int P, double *tot) {
-  __shared__ double s[256][2];
-  const int n = unit_base[P];
-  double a = 0.0, b = 0.0;
-  if (threadIdx.x == 0) { a = tot[0]; b = tot[1]; }
-  for (int u0 = 0; u0 < n; u0 += 256) {
-    __syncthreads();
-    const int u = u0 + threadIdx.x;
-    if (u < n) { s[threadIdx.x][0] = unit_tot[2 * (size_t)u]; s[threadIdx.x][1] = unit_tot[2 * (size_t)u + 1]; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-      for (int i = 0; i < min(256, n - u0); i++) { a += s[i][0]; b += s[i][1]; }
-  }
-  if (threadIdx.x == 0 && n > 0) { tot[0] = a; tot[1] = b; }
-}
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -291,48 +168,31 @@ static int gmm_acc_run(mfa_ctx *c, const float *d_feats, const float *d_feats_su
                        const int32_t *d_tid2pdf, const float *d_tid_weight, int32_t n_tids, double *d_occ, double *d_mean,
                        double *d_var, double *d_tot, int64_t *d_tid_count) {
   MFA_HIP_CHECK(c, hipSetDevice(c->device));
-  if (!c->gmm_ready) return c->fail("mfa_load_gmm has not been called");
-  const int D = c->dim, P = c->num_pdfs;
-  if (D > kMaxDim) return c->fail("GMM statistics: feature dim %d > %d (a thread of the sum kernel owns 3 of 48 columns)", D, kMaxDim);
-  int max_ng = 0;
-  int64_t G = 0;
-  for (int p = 0; p < P; p++) {
-    if (c->h_ngauss[p] > kMaxGauss) return c->fail("GMM statistics: pdf %d has more than %d Gaussians", p, kMaxGauss);
-    max_ng = std::max(max_ng, (int)c->h_ngauss[p]);
-    G += c->h_ngauss[p];
-  }
-  if (total_frames <= 0) return 0;
-  if (total_frames >= ((int64_t)1 << 31) - kChunk) return c->fail("GMM statistics: %lld frames in one call (at most 2^31 - %d)", (long long)total_frames, kChunk + 1);
-  if (n_tids <= 0) return c->fail("GMM statistics: empty transition-id table");
-  if (!c->d_acc_tabs) {
-    std::vector<int32_t> tabs((size_t)2 * P + 1);
-    int32_t off = 0;
-    for (int p = 0; p < P; p++) { tabs[p] = c->h_ngauss[p]; tabs[P + p] = off; off += c->h_ngauss[p]; }
-    tabs[2 * P] = off;
-    if (dev_upload_commit<MfaHipDev>(c, "the pdfs' Gaussian counts", {{&c->d_acc_tabs, tabs.data(), tabs.size() * 4}})) return -1;
-  }
-  const int32_t *d_ngauss = c->d_acc_tabs.ptr<int32_t>(), *d_goff = d_ngauss + P;
+  AccModel am;
+  if (const int rc = acc_model_tabs(c, "GMM statistics", kMaxDim, "a thread of the sum kernel owns 3 of 48 columns", kMaxGauss, kChunk,
+                                    total_frames, n_tids, am))
+    return rc < 0 ? rc : 0;
+  const int D = c->dim, P = c->num_pdfs, max_ng = am.max_ng;
+  const int32_t *d_ngauss = am.d_ngauss, *d_goff = am.d_goff;
 
   const size_t T = (size_t)total_frames, W = 2 * (size_t)D + 1;
   const size_t units_max = T / kChunk + (size_t)P;                              // Σ ceil(n_p / C) <= floor(T / C) + P
-  const size_t rows_max = (T / kChunk + 1) * (size_t)max_ng + (size_t)G;        // Σ ceil(n_p / C)·g_p <= (T / C)·max g + Σ g_p
-  const unsigned end_bit = [&] { unsigned b = 1; while (((uint64_t)1 << b) <= (uint64_t)P) b++; return b; }();
+  const size_t rows_max = (T / kChunk + 1) * (size_t)max_ng + (size_t)am.G;     // Σ ceil(n_p / C)·g_p <= (T / C)·max g + Σ g_p
+  const unsigned end_bit = acc_end_bit((uint64_t)P);
   size_t sort_bytes = 0;
   MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
                                              (uint32_t *)nullptr, T, 0u, end_bit, c->stream));
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = align256(o + bytes); return at; };
-  const size_t o_key = take(T * 4), o_key2 = take(T * 4), o_val = take(T * 4), o_val2 = take(T * 4), o_wgt = take(T * 4),
-               o_cnt = take(((size_t)P + 1) * 4), o_seg = take(((size_t)P + 1) * 4), o_ub = take(((size_t)P + 1) * 4),
-               o_prow = take(((size_t)P + 1) * 8), o_utot = take(units_max * 16), o_part = take(rows_max * W * 8),
-               o_sort = take(sort_bytes);
-  if (c->d_ws.reserve(c, o, "the GMM statistics workspace")) return -1;
-  char *ws = c->d_ws.ptr<char>();
-  uint32_t *key = (uint32_t *)(ws + o_key), *key2 = (uint32_t *)(ws + o_key2), *val = (uint32_t *)(ws + o_val), *val2 = (uint32_t *)(ws + o_val2);
-  float *wgt = (float *)(ws + o_wgt);
-  int32_t *cnt = (int32_t *)(ws + o_cnt), *seg = (int32_t *)(ws + o_seg), *ub = (int32_t *)(ws + o_ub);
-  int64_t *prow = (int64_t *)(ws + o_prow);
-  double *utot = (double *)(ws + o_utot), *part = (double *)(ws + o_part);
+  Workspace ws;
+  const size_t o_key = ws.take(T * 4), o_key2 = ws.take(T * 4), o_val = ws.take(T * 4), o_val2 = ws.take(T * 4), o_wgt = ws.take(T * 4),
+               o_cnt = ws.take(((size_t)P + 1) * 4), o_seg = ws.take(((size_t)P + 1) * 4), o_ub = ws.take(((size_t)P + 1) * 4),
+               o_prow = ws.take(((size_t)P + 1) * 8), o_utot = ws.take(units_max * 16), o_part = ws.take(rows_max * W * 8),
+               o_sort = ws.take(sort_bytes);
+  if (ws.reserve(c, "the GMM statistics workspace")) return -1;
+  uint32_t *key = ws.at<uint32_t>(o_key), *key2 = ws.at<uint32_t>(o_key2), *val = ws.at<uint32_t>(o_val), *val2 = ws.at<uint32_t>(o_val2);
+  float *wgt = ws.at<float>(o_wgt);
+  int32_t *cnt = ws.at<int32_t>(o_cnt), *seg = ws.at<int32_t>(o_seg), *ub = ws.at<int32_t>(o_ub);
+  int64_t *prow = ws.at<int64_t>(o_prow);
+  double *utot = ws.at<double>(o_utot), *part = ws.at<double>(o_part);
 
   {
     KernelTimer kt(c, MFA_K_ACC_LOOKUP);
@@ -345,8 +205,8 @@ static int gmm_acc_run(mfa_ctx *c, const float *d_feats, const float *d_feats_su
   }
   {
     KernelTimer kt(c, MFA_K_ACC_SORT);
-    MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(ws + o_sort, sort_bytes, key, key2, val, val2, T, 0u, end_bit, c->stream));
-    hipLaunchKernelGGL(gmm_acc_scan_kernel, dim3(1), dim3(256), 0, c->stream, cnt, d_ngauss, P, seg, ub, prow);
+    MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(ws.at<char>(o_sort), sort_bytes, key, key2, val, val2, T, 0u, end_bit, c->stream));
+    hipLaunchKernelGGL((acc_scan_kernel<3, GmmAccScan>), dim3(1), dim3(256), 0, c->stream, GmmAccScan{cnt, d_ngauss, seg, ub, prow}, P);
     MFA_HIP_CHECK(c, hipGetLastError());
   }
   {
@@ -367,7 +227,7 @@ static int gmm_acc_run(mfa_ctx *c, const float *d_feats, const float *d_feats_su
     KernelTimer kt(c, MFA_K_ACC_REDUCE);
     ReduceParams rp{D, d_ngauss, d_goff, ub, prow, part, d_occ, d_mean, d_var};
     hipLaunchKernelGGL(gmm_acc_reduce_kernel, dim3((unsigned)P, (unsigned)((max_ng * (2 * D + 1) + 255) / 256)), dim3(256), 0, c->stream, rp);
-    hipLaunchKernelGGL(gmm_acc_totals_kernel, dim3(1), dim3(256), 0, c->stream, utot, ub, P, d_tot);
+    hipLaunchKernelGGL(acc_totals_kernel, dim3(1), dim3(256), 0, c->stream, utot, ub, P, d_tot);
     MFA_HIP_CHECK(c, hipGetLastError());
   }
   return 0;

@@ -3,21 +3,22 @@
 // Arithmetic contract: include/mfa_hip.h "LDA statistics"; the shared arithmetic: lda_acc_math.hpp; the host twin:
 // lda_acc_host.cpp.
 //
+// The ordering by class, the units and the reductions are the segment skeleton of acc_segments.hpp:
 //   lookup   lda_lookup_kernel: per frame its utterance, class and weight (after the random prune), the sort key (class;
-//            n_classes = takes no part), the classes' frame counts and the transition-id counts (integer atomics: exact);
+//            n_classes = takes no part), the classes' frame counts and the transition-id counts;
 //            lda_offsets_kernel: every utterance's CMVN offsets as float32
 //   second   lda_second_kernel, one workgroup per slab of kSlab consecutive frames of the batch: Σ (w·x)·xᵀ on the f64
 //            matrix pipe, the lower-triangle 16×16 tiles spread over four wavefronts; the slab's partial to the workspace
-//   order    rocPRIM radix_sort_pairs (stable) of (class, frame index), then one workgroup scans segment starts and units
+//   order    rocPRIM radix_sort_pairs (stable) of (class, frame index), then the scan of segment starts and units
 //   class    lda_class_kernel, one workgroup per unit = (class, chunk of kChunk consecutive entries of its segment):
 //            Σ w and Σ w·x from zero in frame order
 //   reduce   the caller's value, then the slabs' (the class's chunks') partials in order; the second moment's upper
 //            triangle is a copy of the lower
-// No floating-point atomics anywhere.
 #include <algorithm>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "acc_segments.hpp"
 #include "ctx.hpp"
 #include "lda_acc_math.hpp"
 
@@ -37,16 +38,6 @@ static_assert(kSlab % kTile == 0 && kTile % 4 == 0 && kMaxS % 16 == 0, "lda_seco
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
-// Largest u in [0, n_utt) with frame_off[u] <= t: for t inside the batch that utterance is not empty and holds t.
-__device__ inline int lda_utt_of(const int64_t *frame_off, int n_utt, int64_t t) {
-  int lo = 0, hi = n_utt;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (frame_off[mid] <= t) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 struct LookupParams {
   const int32_t *ali; const int64_t *frame_off; int32_t n_utt; int64_t n;
   const int32_t *tid2class; const float *tid_weight; int32_t n_tids, n_classes;
@@ -61,7 +52,7 @@ __global__ __launch_bounds__(256) void lda_lookup_kernel(LookupParams p) {
   float w = 0.0f;
   const int tid = in ? p.ali[t] : 0;
   bool take = in && lda_frame_class(tid, p.tid2class, p.tid_weight, p.n_tids, p.n_classes, &c, &w);
-  if (in) u = lda_utt_of(p.frame_off, p.n_utt, t);
+  if (in) u = acc_owner(p.frame_off, p.n_utt, t);   // for t inside the batch that utterance is not empty and holds t
   if (take && p.theta > 0.0f) {
     w = lda_prune_weight(w, p.theta, p.seed, p.utt_key[u], (uint32_t)(t - p.frame_off[u]));
     take = w != 0.0f;
@@ -72,19 +63,11 @@ __global__ __launch_bounds__(256) void lda_lookup_kernel(LookupParams p) {
     p.weight[t] = take ? w : 0.0f;
     p.utt[t] = u;
   }
-  // one atomic per run of equal transition-ids inside the wavefront (tid_lookup.hpp has the reasoning)
-  const int lane = threadIdx.x & 63;
-  const int key = take ? tid : -1;
-  const int prev = __shfl_up(key, 1);
-  const bool ends = lane == 0 || prev != key;
-  const bool head = take && ends;
-  const unsigned long long starts = __ballot(ends);
-  if (head) {
-    const unsigned long long above = lane == 63 ? 0ull : starts >> (lane + 1);
-    const int len = above ? __ffsll((long long)above) : 64 - lane;
+  // one atomic per run of equal transition-ids inside the wavefront (acc_segments.hpp has the reasoning)
+  acc_wave_runs(take, tid, [&](int len) {
     atomicAdd(&p.class_count[c], len);
     if (p.tid_count) atomicAdd(&p.tid_count[tid], (unsigned long long)len);
-  }
+  });
 }
 
 // off[u][d] = what CMVN subtracts from column d of utterance u's rows (0 without CMVN)
@@ -131,7 +114,7 @@ __global__ __launch_bounds__(256) void lda_second_kernel(SecondParams p) {
     acc[q] = double4_t{0.0, 0.0, 0.0, 0.0};
   }
 
-  int u = lda_utt_of(p.frame_off, p.n_utt, g0);
+  int u = acc_owner(p.frame_off, p.n_utt, g0);
   int64_t g = g0;
   while (g < g1) {
     while (u + 1 < p.n_utt && p.frame_off[u + 1] <= g) u++;
@@ -177,8 +160,8 @@ __global__ __launch_bounds__(256) void lda_second_kernel(SecondParams p) {
   }
 }
 
-// One thread per element (i, j <= i) of the lower triangle: the caller's value, then the slabs' partials in slab order; the
-// sum goes to both (i, j) and (j, i).
+// One thread per element (i, j <= i) of the lower triangle: the caller's value, then the slabs' partials in slab order
+// (acc_ordered_sum); the sum goes to both (i, j) and (j, i).
 __global__ __launch_bounds__(256) void lda_second_reduce_kernel(const double *partial, int n_slabs, int S, int nb, double *second) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= S * S) return;
@@ -187,44 +170,18 @@ __global__ __launch_bounds__(256) void lda_second_reduce_kernel(const double *pa
   const int I = i >> 4, J = j >> 4, ntiles = nb * (nb + 1) / 2;
   const size_t stride = (size_t)ntiles * 256;
   const double *base = partial + (size_t)(I * (I + 1) / 2 + J) * 256 + (i & 15) * 16 + (j & 15);
-  double a = second[(size_t)i * S + j];
-  int s = 0;
-  for (; s + 8 <= n_slabs; s += 8) {
-    double v[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) v[k] = base[(size_t)(s + k) * stride];
-#pragma unroll
-    for (int k = 0; k < 8; k++) a += v[k];
-  }
-  for (; s < n_slabs; s++) a += base[(size_t)s * stride];
+  const double a = acc_ordered_sum(base, stride, n_slabs, second[(size_t)i * S + j]);
   second[(size_t)i * S + j] = a;
   second[(size_t)j * S + i] = a;
 }
 
-// One workgroup: exclusive scans over the classes of (frames, units).
-__global__ __launch_bounds__(256) void lda_scan_kernel(const int32_t *cnt, int C, int32_t *seg_off, int32_t *unit_base) {
-  __shared__ int32_t sf[256], su[256];
-  const int per = (C + 255) / 256, a = min(C, (int)threadIdx.x * per), b = min(C, a + per);
-  int32_t f = 0, u = 0;
-  for (int c = a; c < b; c++) { f += cnt[c]; u += (cnt[c] + kChunk - 1) / kChunk; }
-  sf[threadIdx.x] = f; su[threadIdx.x] = u;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int32_t af = 0, au = 0;
-    for (int i = 0; i < 256; i++) {
-      const int32_t tf = sf[i], tu = su[i];
-      sf[i] = af; su[i] = au;
-      af += tf; au += tu;
-    }
-    seg_off[C] = af; unit_base[C] = au;
-  }
-  __syncthreads();
-  f = sf[threadIdx.x]; u = su[threadIdx.x];
-  for (int c = a; c < b; c++) {
-    seg_off[c] = f; unit_base[c] = u;
-    f += cnt[c]; u += (cnt[c] + kChunk - 1) / kChunk;
-  }
-}
+// acc_scan_kernel<2> over the classes: frames, units
+struct LdaScan {
+  const int32_t *cnt;
+  int32_t *seg_off; int32_t *unit_base;
+  __device__ void add(int q, int64_t (&v)[2]) const { v[0] += cnt[q]; v[1] += (cnt[q] + kChunk - 1) / kChunk; }
+  __device__ void put(int q, const int64_t (&v)[2]) const { seg_off[q] = (int32_t)v[0]; unit_base[q] = (int32_t)v[1]; }
+};
 
 struct ClassParams {
   const float *mfcc; const int64_t *frame_off; int64_t n;
@@ -243,12 +200,7 @@ __global__ __launch_bounds__(128) void lda_class_kernel(ClassParams p) {
   __shared__ float w_s[kChunk];
   const int unit = blockIdx.x, C = p.C;
   if (unit >= p.unit_base[C]) return;
-  int lo = 0, hi = C;                 // unit_base[lo] <= unit < unit_base[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (p.unit_base[mid] <= unit) lo = mid; else hi = mid;
-  }
-  const int cls = lo, chunk = unit - p.unit_base[cls];
+  const int cls = acc_owner(p.unit_base, C, unit), chunk = unit - p.unit_base[cls];
   const int s0 = p.seg_off[cls] + chunk * kChunk, s1 = min(p.seg_off[cls + 1], s0 + kChunk), n = s1 - s0;
   const int tid = threadIdx.x;
   for (int e = tid; e < n; e += 128) {
@@ -278,7 +230,8 @@ __global__ __launch_bounds__(128) void lda_class_kernel(ClassParams p) {
   }
 }
 
-// grid: the classes; 256 threads over the class's [S + 1] sums: the caller's value, then its units' partials in chunk order.
+// grid: the classes; 256 threads over the class's [S + 1] sums: the caller's value, then its units' partials in chunk order
+// (acc_ordered_sum).
 __global__ __launch_bounds__(256) void lda_class_reduce_kernel(const double *partial, const int32_t *unit_base, int S, double *zero,
                                                                double *first) {
   const int cls = blockIdx.x, u0 = unit_base[cls], nu = unit_base[cls + 1] - u0;
@@ -286,20 +239,8 @@ __global__ __launch_bounds__(256) void lda_class_reduce_kernel(const double *par
   if (nu == 0 || e > S) return;
   double *dst = e == 0 ? zero + cls : first + (size_t)cls * S + (e - 1);
   const double *base = partial + (size_t)u0 * (S + 1) + e;
-  double a = *dst;
-  int ch = 0;
-  for (; ch + 8 <= nu; ch += 8) {
-    double v[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) v[k] = base[(size_t)(ch + k) * (S + 1)];
-#pragma unroll
-    for (int k = 0; k < 8; k++) a += v[k];
-  }
-  for (; ch < nu; ch++) a += base[(size_t)ch * (S + 1)];
-  *dst = a;
+  *dst = acc_ordered_sum(base, (size_t)(S + 1), nu, *dst);
 }
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -331,22 +272,21 @@ MFA_API int mfa_lda_acc_batch(mfa_ctx *c, const float *d_mfcc, const int64_t *d_
   const size_t T = (size_t)total_frames;
   const size_t n_slabs = (T + kSlab - 1) / kSlab;
   const size_t units_max = T / kChunk + (size_t)C;                              // Σ ceil(n_c / chunk) <= floor(T / chunk) + C
-  const unsigned end_bit = [&] { unsigned b = 1; while (((uint64_t)1 << b) <= (uint64_t)C) b++; return b; }();
+  const unsigned end_bit = acc_end_bit((uint64_t)C);
   size_t sort_bytes = 0;
   MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
                                              (uint32_t *)nullptr, T, 0u, end_bit, c->stream));
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = align256(o + bytes); return at; };
-  const size_t o_key = take(T * 4), o_key2 = take(T * 4), o_val = take(T * 4), o_val2 = take(T * 4), o_wgt = take(T * 4),
-               o_utt = take(T * 4), o_off = take((size_t)n_utt * dim * 4), o_cnt = take(((size_t)C + 1) * 4),
-               o_seg = take(((size_t)C + 1) * 4), o_ub = take(((size_t)C + 1) * 4), o_cpart = take(units_max * ((size_t)S + 1) * 8),
-               o_spart = take(n_slabs * (size_t)ntiles * 256 * 8), o_sort = take(sort_bytes);
-  if (c->d_ws.reserve(c, o, "the LDA statistics workspace")) return -1;
-  char *ws = c->d_ws.ptr<char>();
-  uint32_t *key = (uint32_t *)(ws + o_key), *key2 = (uint32_t *)(ws + o_key2), *val = (uint32_t *)(ws + o_val), *val2 = (uint32_t *)(ws + o_val2);
-  float *wgt = (float *)(ws + o_wgt), *off = (float *)(ws + o_off);
-  int32_t *utt = (int32_t *)(ws + o_utt), *cnt = (int32_t *)(ws + o_cnt), *seg = (int32_t *)(ws + o_seg), *ub = (int32_t *)(ws + o_ub);
-  double *cpart = (double *)(ws + o_cpart), *spart = (double *)(ws + o_spart);
+  Workspace ws;
+  const size_t o_key = ws.take(T * 4), o_key2 = ws.take(T * 4), o_val = ws.take(T * 4), o_val2 = ws.take(T * 4), o_wgt = ws.take(T * 4),
+               o_utt = ws.take(T * 4), o_off = ws.take((size_t)n_utt * dim * 4), o_cnt = ws.take(((size_t)C + 1) * 4),
+               o_seg = ws.take(((size_t)C + 1) * 4), o_ub = ws.take(((size_t)C + 1) * 4),
+               o_cpart = ws.take(units_max * ((size_t)S + 1) * 8), o_spart = ws.take(n_slabs * (size_t)ntiles * 256 * 8),
+               o_sort = ws.take(sort_bytes);
+  if (ws.reserve(c, "the LDA statistics workspace")) return -1;
+  uint32_t *key = ws.at<uint32_t>(o_key), *key2 = ws.at<uint32_t>(o_key2), *val = ws.at<uint32_t>(o_val), *val2 = ws.at<uint32_t>(o_val2);
+  float *wgt = ws.at<float>(o_wgt), *off = ws.at<float>(o_off);
+  int32_t *utt = ws.at<int32_t>(o_utt), *cnt = ws.at<int32_t>(o_cnt), *seg = ws.at<int32_t>(o_seg), *ub = ws.at<int32_t>(o_ub);
+  double *cpart = ws.at<double>(o_cpart), *spart = ws.at<double>(o_spart);
 
   {
     KernelTimer kt(c, MFA_K_LDA_LOOKUP);
@@ -366,8 +306,8 @@ MFA_API int mfa_lda_acc_batch(mfa_ctx *c, const float *d_mfcc, const int64_t *d_
   }
   {
     KernelTimer kt(c, MFA_K_LDA_CLASS);
-    MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(ws + o_sort, sort_bytes, key, key2, val, val2, T, 0u, end_bit, c->stream));
-    hipLaunchKernelGGL(lda_scan_kernel, dim3(1), dim3(256), 0, c->stream, cnt, C, seg, ub);
+    MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(ws.at<char>(o_sort), sort_bytes, key, key2, val, val2, T, 0u, end_bit, c->stream));
+    hipLaunchKernelGGL((acc_scan_kernel<2, LdaScan>), dim3(1), dim3(256), 0, c->stream, LdaScan{cnt, seg, ub}, C);
     ClassParams cp{d_mfcc, d_frame_off, total_frames, dim, splice_ctx, S, C, off, wgt, utt, val2, seg, ub, cpart};
     hipLaunchKernelGGL(lda_class_kernel, dim3((unsigned)units_max), dim3(128), 0, c->stream, cp);
     MFA_HIP_CHECK(c, hipGetLastError());

@@ -5,19 +5,21 @@
 // Arithmetic contract: include/mfa_hip.h "MLLT statistics"; the shared arithmetic: mllt_acc_math.hpp over gmm_acc_math.hpp;
 // the host twin: mllt_acc_host.cpp.
 //
+// The steps are the segment skeleton of acc_segments.hpp, the posterior phase is acc_posterior.hpp's:
 //   lookup   fmllr_tid_lookup_kernel (tid_lookup.hpp), as the GMM statistics run it
-//   order    rocPRIM radix_sort_pairs (stable) of (pdf, frame index); one workgroup scans the pdfs' segment starts, their
-//            units (chunks of kChunk entries) and sub-units (chunks of kSub entries: the GMM statistics' chunks)
+//   order    rocPRIM radix_sort_pairs (stable) of (pdf, frame index); the scan gives the pdfs' segment starts, their units
+//            (chunks of kChunk entries) and sub-units (chunks of kSub entries: the GMM statistics' chunks)
 //   sums     mllt_acc_kernel, one workgroup per (unit, group of kGroup Gaussians of the pdf): the posteriors of all the pdf's
-//            Gaussians exactly as gmm_acc_kernel forms them, then the group's lower-triangle 16×16 tiles of Σ (γ·d)·dᵀ on
-//            the f64 matrix pipe; group 0 also sums occ and the totals per sub-unit
+//            Gaussians by the pieces gmm_acc_kernel forms them with, then the group's lower-triangle 16×16 tiles of
+//            Σ (γ·d)·dᵀ on the f64 matrix pipe; group 0 also sums occ and the totals per sub-unit
 //   reduce   per pdf, the units' partials in chunk order onto the caller's full (both triangles written), the sub-units'
 //            onto occ, the totals in (pdf, sub-unit) order
-// No floating-point atomics anywhere.
 #include <algorithm>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "acc_posterior.hpp"
+#include "acc_segments.hpp"
 #include "ctx.hpp"
 #include "mllt_acc_math.hpp"
 #include "tid_lookup.hpp"
@@ -27,53 +29,30 @@ namespace {
 constexpr int kSub = 512;        // entries per occ / totals partial: mfa_gmm_acc_chunk_frames(), so that both have that call's bits
 constexpr int kSubsPerChunk = 8;
 constexpr int kChunk = kSub * kSubsPerChunk;   // entries of a pdf's segment per unit (mfa_mllt_acc_chunk_frames)
-constexpr int kTile = 32;        // frames staged in LDS at a time; 8 per wavefront in the posterior phase
-constexpr int kMaxGauss = 128;   // two rounds of lane = Gaussian
-constexpr int kMaxDim = 48;
-constexpr int kXStride = kMaxDim + 1;
+constexpr int kTile = kAccTile, kMaxGauss = kAccMaxGauss, kMaxDim = kAccMaxDim, kXStride = kAccXStride;
 constexpr int kBlocks = kMaxDim / 16;                    // 16-wide blocks of the padded feature vector
 constexpr int kTiles = kBlocks * (kBlocks + 1) / 2;      // lower-triangle tiles of one Gaussian: 6
 constexpr int kWaves = 4;
 constexpr int kGaussPerWave = 4;                         // 4 · 6 tiles · 4 doubles = 192 accumulator registers per lane
 constexpr int kGroup = kWaves * kGaussPerWave;           // Gaussians of a pdf per workgroup
-static_assert(kSub % kTile == 0 && kTile == 4 * 8 && kMaxDim % 16 == 0 && kMaxGauss == 2 * 64 && kMaxGauss % kGroup == 0,
-              "mllt_acc_kernel tiling");
+static_assert(kSub % kTile == 0 && kTile % 4 == 0 && kMaxDim % 16 == 0 && kMaxGauss % kGroup == 0, "mllt_acc_kernel tiling");
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
-struct ScanParams {
-  const int32_t *cnt; const int32_t *ngauss; int P;
+// acc_scan_kernel<5> over the pdfs
+struct MlltAccScan {
+  const int32_t *cnt; const int32_t *ngauss;
   int32_t *seg_off, *unit_base, *sub_base;    // [P + 1] each: first sorted entry, first unit, first sub-unit of every pdf
   int64_t *prow, *srow;                       // [P + 1]: first partial row (units × Gaussians), first occ row (sub-units × Gaussians)
-};
-
-// One workgroup: exclusive scans over the pdfs.
-__global__ __launch_bounds__(256) void mllt_acc_scan_kernel(ScanParams p) {
-  __shared__ int64_t s[256][5];
-  const int P = p.P, per = (P + 255) / 256, a = min(P, (int)threadIdx.x * per), b = min(P, a + per);
-  int64_t v[5] = {0, 0, 0, 0, 0};
-  auto add = [&](int q) {
-    const int64_t c = p.cnt[q], un = (c + kChunk - 1) / kChunk, sn = (c + kSub - 1) / kSub, ng = p.ngauss[q];
+  __device__ void add(int q, int64_t (&v)[5]) const {
+    const int64_t c = cnt[q], un = (c + kChunk - 1) / kChunk, sn = (c + kSub - 1) / kSub, ng = ngauss[q];
     v[0] += c; v[1] += un; v[2] += sn; v[3] += un * ng; v[4] += sn * ng;
-  };
-  for (int q = a; q < b; q++) add(q);
-  for (int k = 0; k < 5; k++) s[threadIdx.x][k] = v[k];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t acc[5] = {0, 0, 0, 0, 0};
-    for (int i = 0; i < 256; i++)
-      for (int k = 0; k < 5; k++) { const int64_t t = s[i][k]; s[i][k] = acc[k]; acc[k] += t; }
-    p.seg_off[P] = (int32_t)acc[0]; p.unit_base[P] = (int32_t)acc[1]; p.sub_base[P] = (int32_t)acc[2];
-    p.prow[P] = acc[3]; p.srow[P] = acc[4];
   }
-  __syncthreads();
-  for (int k = 0; k < 5; k++) v[k] = s[threadIdx.x][k];
-  for (int q = a; q < b; q++) {
-    p.seg_off[q] = (int32_t)v[0]; p.unit_base[q] = (int32_t)v[1]; p.sub_base[q] = (int32_t)v[2];
-    p.prow[q] = v[3]; p.srow[q] = v[4];
-    add(q);
+  __device__ void put(int q, const int64_t (&v)[5]) const {
+    seg_off[q] = (int32_t)v[0]; unit_base[q] = (int32_t)v[1]; sub_base[q] = (int32_t)v[2];
+    prow[q] = v[3]; srow[q] = v[4];
   }
-}
+};
 
 struct AccParams {
   int D, kpad, num_pdfs;
@@ -89,9 +68,12 @@ struct AccParams {
 
 // grid (an upper bound of the units — the true count is unit_base[num_pdfs], known on the device only —, groups of kGroup
 // Gaussians); 256 threads.
-// Posterior phase: gmm_acc_kernel's, operation for operation — wavefront = 8 frames of the tile, lane = Gaussian (two rounds
-// of 64), the same butterfly sums — so that γ, occ and the totals carry that kernel's bits.  Every group forms the posteriors
-// of the whole pdf (the softmax needs them all): at most 128 · 2·dim float32 FMAs per frame beside the group's 16 · 6 matrix
+// Posterior phase: acc_posterior_phase (acc_posterior.hpp), the function gmm_acc_kernel runs, so that γ, occ and the totals
+// carry that kernel's bits; rows of post_s past the chunk's end are written as zeros for the moment phase.  The small pieces
+// around it (owner search, gconsts, prefetch, LDS store, the occ / totals loops) are written out here although
+// acc_posterior.hpp and acc_segments.hpp have them: with any of them called, the compiler schedules this kernel's 192
+// accumulator registers another way and the sums stage takes 35.5 ms, not 35.0 (tools/mllt_rate.py's shape).
+// Every group forms the posteriors of the whole pdf (the softmax needs them all): at most 128 · 2·dim float32 FMAs per frame beside the group's 16 · 6 matrix
 // instructions per 4 frames.
 // Moment phase: wavefront v owns Gaussians group·16 + v + 4 q (q < 4) and all their tiles.  A step of the instruction takes
 // 4 frames, the operand layout is lda_second_kernel's: lane l gives, for the tile's row block I and column block J,
@@ -105,7 +87,7 @@ __global__ __launch_bounds__(256) void mllt_acc_kernel(AccParams p) {
   __shared__ float fw_s[kTile], fll_s[kTile];
   const int unit = blockIdx.x, group = blockIdx.y, P = p.num_pdfs;
   if (unit >= p.unit_base[P]) return;
-  int lo = 0, hi = P;                 // unit_base[lo] <= unit < unit_base[hi]
+  int lo = 0, hi = P;                 // acc_owner, written out (see above): unit_base[lo] <= unit < unit_base[hi]
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
     if (p.unit_base[mid] <= unit) lo = mid; else hi = mid;
@@ -141,17 +123,16 @@ __global__ __launch_bounds__(256) void mllt_acc_kernel(AccParams p) {
     occ = 0.0; tot_like = 0.0; tot_count = 0.0;
   };
 
-  // The gather of a tile is two dependent global loads (sorted index, then the row): the next tile's rows are fetched into
-  // registers while this tile is worked on, and only stored to LDS at the top of the next round.
-  constexpr int kStage = kTile * kMaxDim / 256;
-  static_assert(kStage * 256 == kTile * kMaxDim, "every thread stages the same number of elements");
+  // acc_fetch and acc_stage_store, written out (see above): the next tile's rows are fetched into registers while this tile
+  // is worked on, and only stored to LDS at the top of the next round.
+  constexpr int kStage = kAccStage;
   float nx[kStage], nw = 0.0f;
   auto fetch = [&](int t0) {
     const int nc = min(kTile, s1 - t0);
 #pragma unroll
     for (int i = 0; i < kStage; i++) {
       const int e = tid + 256 * i, t = e / kMaxDim, k = e % kMaxDim;
-      nx[i] = t < nc && k < D ? p.feats[(size_t)p.idx[t0 + t] * D + k] : 0.0f;         // columns up to 48 and rows past the end read as 0
+      nx[i] = t < nc && k < D ? p.feats[(size_t)p.idx[t0 + t] * D + k] : 0.0f;
     }
     if (tid < kTile) nw = tid < nc ? p.weight[p.idx[t0 + tid]] : 0.0f;
   };
@@ -167,48 +148,7 @@ __global__ __launch_bounds__(256) void mllt_acc_kernel(AccParams p) {
     }
     if (tid < kTile) fw_s[tid] = nw;
     if (t0 + kTile < s1) fetch(t0 + kTile);
-    float ll[8][2];
-#pragma unroll
-    for (int rnd = 0; rnd < 2; rnd++) {
-      if (rnd < rounds) {
-        if (rounds > 1 || t0 == s0) {   // one round: its weights stay for the whole chunk
-          __syncthreads();              // the other round's readers are done
-          for (int i = tid; i < 2 * D * 64; i += 256) {
-            const int k = i >> 6, g = (i & 63) + 64 * rnd;
-            w_s[k][i & 63] = g < ng ? p.w[mfa_packed_offset(r0 + g, k, p.kpad)] : 0.0f;
-          }
-        }
-        __syncthreads();
-        const bool have = lane + 64 * rnd < ng;
-        float blk[8];                   // rows past the chunk's end are zeros: computed, never used
-        gmm_acc_loglike_block<8>(gcv[rnd], D, &w_s[0][lane], 64, &w_s[D][lane], 64, x_s[wave * 8], kXStride, blk);
-#pragma unroll
-        for (int f = 0; f < 8; f++) ll[f][rnd] = have && wave * 8 + f < nc ? blk[f] : -INFINITY;
-      } else {
-#pragma unroll
-        for (int f = 0; f < 8; f++) ll[f][rnd] = -INFINITY;
-      }
-    }
-#pragma unroll
-    for (int f = 0; f < 8; f++) {
-      const int t = wave * 8 + f;
-      if (t < nc) {                     // the same for the whole wavefront
-        float mx = fmaxf(ll[f][0], ll[f][1]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-        const float e0 = lane < ng ? expf(ll[f][0] - mx) : 0.0f, e1 = lane + 64 < ng ? expf(ll[f][1] - mx) : 0.0f;
-        float sum = e0 + e1;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        const float inv = 1.0f / sum, wgt = fw_s[t];
-        post_s[t][lane] = gmm_acc_posterior(e0, inv, wgt);
-        post_s[t][lane + 64] = gmm_acc_posterior(e1, inv, wgt);
-        if (lane == 0) fll_s[t] = gmm_acc_frame_loglike(mx, sum);
-      } else {                          // a frame past the chunk's end is a zero operand of the last step
-        post_s[t][lane] = 0.0f;
-        post_s[t][lane + 64] = 0.0f;
-      }
-    }
+    acc_posterior_phase<true>(p.w, p.kpad, r0, ng, D, gcv, t0, s0, nc, x_s, w_s, post_s, fw_s, fll_s, tid, lane, wave, rounds);
     __syncthreads();
     for (int r = 0; r < nc; r += 4) {
       const float *xr = x_s[r + lk];
@@ -275,8 +215,7 @@ struct ReduceParams {
 };
 
 // grid (pdf, tile of 256 elements of its [n_gauss][D·(D + 1)/2] lower triangles): the caller's value (read from the lower
-// triangle), then the pdf's partials in chunk order; the sum goes to (i, j) and (j, i).  The loads of 8 chunks are issued
-// together, the additions stay one after the other.
+// triangle), then the pdf's partials in chunk order (acc_ordered_sum); the sum goes to (i, j) and (j, i).
 __global__ __launch_bounds__(256) void mllt_acc_reduce_kernel(ReduceParams p) {
   const int pdf = blockIdx.x, nu = p.unit_base[pdf + 1] - p.unit_base[pdf];
   if (nu == 0) return;
@@ -290,16 +229,7 @@ __global__ __launch_bounds__(256) void mllt_acc_reduce_kernel(ReduceParams p) {
   const int j = rem - i * (i + 1) / 2;
   double *sq = p.full + (size_t)(p.goff[pdf] + g) * D * D;
   const double *base = p.partial + (size_t)p.prow[pdf] * LT + e;
-  double a = sq[(size_t)i * D + j];
-  int ch = 0;
-  for (; ch + 8 <= nu; ch += 8) {
-    double v[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) v[k] = base[(size_t)(ch + k) * n];
-#pragma unroll
-    for (int k = 0; k < 8; k++) a += v[k];
-  }
-  for (; ch < nu; ch++) a += base[(size_t)ch * n];
+  const double a = acc_ordered_sum(base, (size_t)n, nu, sq[(size_t)i * D + j]);
   sq[(size_t)i * D + j] = a;
   sq[(size_t)j * D + i] = a;
 }
@@ -314,25 +244,6 @@ __global__ __launch_bounds__(128) void mllt_acc_occ_kernel(ReduceParams p) {
   p.occ[p.goff[pdf] + g] = a;
 }
 
-// one workgroup: the sub-units' totals in order onto the caller's two
-__global__ __launch_bounds__(256) void mllt_acc_totals_kernel(const double *sub_tot, const int32_t *sub_base, int P, double *tot) {
-  __shared__ double s[256][2];
-  const int n = sub_base[P];
-  double a = 0.0, b = 0.0;
-  if (threadIdx.x == 0) { a = tot[0]; b = tot[1]; }
-  for (int u0 = 0; u0 < n; u0 += 256) {
-    __syncthreads();
-    const int u = u0 + threadIdx.x;
-    if (u < n) { s[threadIdx.x][0] = sub_tot[2 * (size_t)u]; s[threadIdx.x][1] = sub_tot[2 * (size_t)u + 1]; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-      for (int i = 0; i < min(256, n - u0); i++) { a += s[i][0]; b += s[i][1]; }
-  }
-  if (threadIdx.x == 0 && n > 0) { tot[0] = a; tot[1] = b; }
-}
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" {
@@ -344,53 +255,36 @@ MFA_API int mfa_mllt_acc_batch(mfa_ctx *c, const float *d_feats, int64_t total_f
                                const int32_t *d_tid2pdf, const float *d_tid_weight, int32_t n_tids, const float *d_means,
                                double *d_occ, double *d_full, double *d_tot) {
   MFA_HIP_CHECK(c, hipSetDevice(c->device));
-  if (!c->gmm_ready) return c->fail("mfa_load_gmm has not been called");
-  const int D = c->dim, P = c->num_pdfs;
-  if (D > kMaxDim) return c->fail("MLLT statistics: feature dim %d > %d (three 16-wide blocks of the matrix tiles)", D, kMaxDim);
-  int max_ng = 0;
-  int64_t G = 0;
-  for (int p = 0; p < P; p++) {
-    if (c->h_ngauss[p] > kMaxGauss) return c->fail("MLLT statistics: pdf %d has more than %d Gaussians", p, kMaxGauss);
-    max_ng = std::max(max_ng, (int)c->h_ngauss[p]);
-    G += c->h_ngauss[p];
-  }
-  if (total_frames <= 0) return 0;
-  if (total_frames >= ((int64_t)1 << 31) - kChunk) return c->fail("MLLT statistics: %lld frames in one call (at most 2^31 - %d)", (long long)total_frames, kChunk + 1);
-  if (n_tids <= 0) return c->fail("MLLT statistics: empty transition-id table");
+  AccModel am;
+  if (const int rc = acc_model_tabs(c, "MLLT statistics", kMaxDim, "three 16-wide blocks of the matrix tiles", kMaxGauss, kChunk,
+                                    total_frames, n_tids, am))
+    return rc < 0 ? rc : 0;
   if (!d_feats || !d_ali || !d_tid2pdf || !d_tid_weight || !d_means) return c->fail("MLLT statistics: NULL input array");
   if (!d_occ || !d_full || !d_tot) return c->fail("MLLT statistics: NULL accumulator");
-  if (!c->d_acc_tabs) {               // the table of the GMM statistics, built by whichever call comes first
-    std::vector<int32_t> tabs((size_t)2 * P + 1);
-    int32_t off = 0;
-    for (int p = 0; p < P; p++) { tabs[p] = c->h_ngauss[p]; tabs[P + p] = off; off += c->h_ngauss[p]; }
-    tabs[2 * P] = off;
-    if (dev_upload_commit<MfaHipDev>(c, "the pdfs' Gaussian counts", {{&c->d_acc_tabs, tabs.data(), tabs.size() * 4}})) return -1;
-  }
-  const int32_t *d_ngauss = c->d_acc_tabs.ptr<int32_t>(), *d_goff = d_ngauss + P;
+  const int D = c->dim, P = c->num_pdfs, max_ng = am.max_ng;
+  const int32_t *d_ngauss = am.d_ngauss, *d_goff = am.d_goff;
 
   const size_t T = (size_t)total_frames, LT = (size_t)D * (D + 1) / 2;
   const size_t units_max = T / kChunk + (size_t)P;                              // Σ ceil(n_p / C) <= floor(T / C) + P
   const size_t subs_max = T / kSub + (size_t)P;
-  const size_t rows_max = (T / kChunk + 1) * (size_t)max_ng + (size_t)G;        // Σ ceil(n_p / C)·g_p <= (T / C)·max g + Σ g_p
-  const size_t srows_max = (T / kSub + 1) * (size_t)max_ng + (size_t)G;
-  const unsigned end_bit = [&] { unsigned b = 1; while (((uint64_t)1 << b) <= (uint64_t)P) b++; return b; }();
+  const size_t rows_max = (T / kChunk + 1) * (size_t)max_ng + (size_t)am.G;        // Σ ceil(n_p / C)·g_p <= (T / C)·max g + Σ g_p
+  const size_t srows_max = (T / kSub + 1) * (size_t)max_ng + (size_t)am.G;
+  const unsigned end_bit = acc_end_bit((uint64_t)P);
   size_t sort_bytes = 0;
   MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
                                              (uint32_t *)nullptr, T, 0u, end_bit, c->stream));
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = align256(o + bytes); return at; };
-  const size_t o_key = take(T * 4), o_key2 = take(T * 4), o_val = take(T * 4), o_val2 = take(T * 4), o_wgt = take(T * 4),
-               o_cnt = take(((size_t)P + 1) * 4), o_seg = take(((size_t)P + 1) * 4), o_ub = take(((size_t)P + 1) * 4),
-               o_sb = take(((size_t)P + 1) * 4), o_prow = take(((size_t)P + 1) * 8), o_srow = take(((size_t)P + 1) * 8),
-               o_stot = take(subs_max * 16), o_opart = take(srows_max * 8), o_part = take(rows_max * LT * 8),
-               o_sort = take(sort_bytes);
-  if (c->d_ws.reserve(c, o, "the MLLT statistics workspace")) return -1;
-  char *ws = c->d_ws.ptr<char>();
-  uint32_t *key = (uint32_t *)(ws + o_key), *key2 = (uint32_t *)(ws + o_key2), *val = (uint32_t *)(ws + o_val), *val2 = (uint32_t *)(ws + o_val2);
-  float *wgt = (float *)(ws + o_wgt);
-  int32_t *cnt = (int32_t *)(ws + o_cnt), *seg = (int32_t *)(ws + o_seg), *ub = (int32_t *)(ws + o_ub), *sb = (int32_t *)(ws + o_sb);
-  int64_t *prow = (int64_t *)(ws + o_prow), *srow = (int64_t *)(ws + o_srow);
-  double *stot = (double *)(ws + o_stot), *opart = (double *)(ws + o_opart), *part = (double *)(ws + o_part);
+  Workspace ws;
+  const size_t o_key = ws.take(T * 4), o_key2 = ws.take(T * 4), o_val = ws.take(T * 4), o_val2 = ws.take(T * 4), o_wgt = ws.take(T * 4),
+               o_cnt = ws.take(((size_t)P + 1) * 4), o_seg = ws.take(((size_t)P + 1) * 4), o_ub = ws.take(((size_t)P + 1) * 4),
+               o_sb = ws.take(((size_t)P + 1) * 4), o_prow = ws.take(((size_t)P + 1) * 8), o_srow = ws.take(((size_t)P + 1) * 8),
+               o_stot = ws.take(subs_max * 16), o_opart = ws.take(srows_max * 8), o_part = ws.take(rows_max * LT * 8),
+               o_sort = ws.take(sort_bytes);
+  if (ws.reserve(c, "the MLLT statistics workspace")) return -1;
+  uint32_t *key = ws.at<uint32_t>(o_key), *key2 = ws.at<uint32_t>(o_key2), *val = ws.at<uint32_t>(o_val), *val2 = ws.at<uint32_t>(o_val2);
+  float *wgt = ws.at<float>(o_wgt);
+  int32_t *cnt = ws.at<int32_t>(o_cnt), *seg = ws.at<int32_t>(o_seg), *ub = ws.at<int32_t>(o_ub), *sb = ws.at<int32_t>(o_sb);
+  int64_t *prow = ws.at<int64_t>(o_prow), *srow = ws.at<int64_t>(o_srow);
+  double *stot = ws.at<double>(o_stot), *opart = ws.at<double>(o_opart), *part = ws.at<double>(o_part);
 
   {
     KernelTimer kt(c, MFA_K_MLLT_LOOKUP);
@@ -403,9 +297,8 @@ MFA_API int mfa_mllt_acc_batch(mfa_ctx *c, const float *d_feats, int64_t total_f
   }
   {
     KernelTimer kt(c, MFA_K_MLLT_SORT);
-    MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(ws + o_sort, sort_bytes, key, key2, val, val2, T, 0u, end_bit, c->stream));
-    ScanParams sp{cnt, d_ngauss, P, seg, ub, sb, prow, srow};
-    hipLaunchKernelGGL(mllt_acc_scan_kernel, dim3(1), dim3(256), 0, c->stream, sp);
+    MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(ws.at<char>(o_sort), sort_bytes, key, key2, val, val2, T, 0u, end_bit, c->stream));
+    hipLaunchKernelGGL((acc_scan_kernel<5, MlltAccScan>), dim3(1), dim3(256), 0, c->stream, MlltAccScan{cnt, d_ngauss, seg, ub, sb, prow, srow}, P);
     MFA_HIP_CHECK(c, hipGetLastError());
   }
   {
@@ -422,7 +315,7 @@ MFA_API int mfa_mllt_acc_batch(mfa_ctx *c, const float *d_feats, int64_t total_f
     hipLaunchKernelGGL(mllt_acc_reduce_kernel, dim3((unsigned)P, (unsigned)(((size_t)max_ng * LT + 255) / 256)), dim3(256), 0,
                        c->stream, rp);
     hipLaunchKernelGGL(mllt_acc_occ_kernel, dim3((unsigned)P), dim3(128), 0, c->stream, rp);
-    hipLaunchKernelGGL(mllt_acc_totals_kernel, dim3(1), dim3(256), 0, c->stream, stot, sb, P, d_tot);
+    hipLaunchKernelGGL(acc_totals_kernel, dim3(1), dim3(256), 0, c->stream, stot, sb, P, d_tot);
     MFA_HIP_CHECK(c, hipGetLastError());
   }
   return 0;

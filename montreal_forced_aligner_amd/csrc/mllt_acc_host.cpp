@@ -1,10 +1,12 @@
 // Host twin of the MLLT statistics (mllt_acc.hip): the whole arithmetic contract of include/mfa_hip.h on host arrays, frames
-// in ascending index, expf / logf from libm, plain loops.  No context, no device, no HIP header: this file, mllt_acc_math.hpp
-// and gmm_acc_math.hpp are all tests/native/mllt_acc_check.cpp needs.
+// in ascending index, expf / logf from libm, plain loops.  No context, no device, no HIP header: this file, mllt_acc_math.hpp,
+// gmm_acc_twin.hpp (a frame's exponentials, shared with gmm_acc_host.cpp) and gmm_acc_math.hpp are all
+// tests/native/mllt_acc_check.cpp needs.
 #include <cstdint>
 #include <vector>
 
 #include "../../include/mfa_hip.h"
+#include "gmm_acc_twin.hpp"
 #include "mllt_acc_math.hpp"
 
 extern "C" MFA_API int mfa_debug_mllt_acc_host(int32_t dim, int32_t num_pdfs, const int32_t *h_pdf_offsets, const float *h_gconsts,
@@ -17,16 +19,12 @@ extern "C" MFA_API int mfa_debug_mllt_acc_host(int32_t dim, int32_t num_pdfs, co
   if (total_frames > 0 && (!h_feats || !h_pdf || !h_weight)) return -1;
   if (!h_occ || !h_full || !h_tot) return -1;
   if (dim > 48) return -3;
-  int max_gauss = 0;
-  for (int p = 0; p < num_pdfs; p++) {
-    const int n = h_pdf_offsets[p + 1] - h_pdf_offsets[p];
-    if (n <= 0) return -1;
-    if (n > 128) return -2;
-    if (n > max_gauss) max_gauss = n;
-  }
+  const int max_gauss = gmm_acc_twin_max_gauss(num_pdfs, h_pdf_offsets);
+  if (max_gauss < 0) return max_gauss;
   if (h_post && post_stride < max_gauss) return -1;
   const size_t DD = (size_t)dim * dim;
-  std::vector<float> half((size_t)dim), d((size_t)dim), ll((size_t)max_gauss), e((size_t)max_gauss);
+  GmmAccTwinFrame f(dim, max_gauss);
+  std::vector<float> d((size_t)dim);
   std::vector<char> touched((size_t)num_pdfs, 0);
   for (int64_t t = 0; t < total_frames; t++) {
     if (h_post)
@@ -37,18 +35,10 @@ extern "C" MFA_API int mfa_debug_mllt_acc_host(int32_t dim, int32_t num_pdfs, co
     touched[p] = 1;
     const int g0 = h_pdf_offsets[p], n = h_pdf_offsets[p + 1] - g0;
     const float *x = h_feats + t * dim;
-    float mx = -INFINITY;
+    f.fill(dim, n, h_gconsts + g0, h_means_invvars + (size_t)g0 * dim, h_inv_vars + (size_t)g0 * dim, x);
+    const float inv = 1.0f / f.sum;
     for (int g = 0; g < n; g++) {
-      const float *iv = h_inv_vars + (size_t)(g0 + g) * dim;
-      for (int k = 0; k < dim; k++) half[k] = -0.5f * iv[k];          // the packed model's second row (gmm_pack_rows)
-      ll[g] = gmm_acc_loglike(h_gconsts[g0 + g], dim, h_means_invvars + (size_t)(g0 + g) * dim, 1, half.data(), 1, x);
-      mx = fmaxf(mx, ll[g]);
-    }
-    float sum = 0.0f;
-    for (int g = 0; g < n; g++) { e[g] = expf(ll[g] - mx); sum += e[g]; }
-    const float inv = 1.0f / sum;
-    for (int g = 0; g < n; g++) {
-      const float post = gmm_acc_posterior(e[g], inv, w);
+      const float post = gmm_acc_posterior(f.e[g], inv, w);
       if (h_post) h_post[t * post_stride + g] = post;
       const double gamma = (double)post;
       h_occ[g0 + g] += gamma;
@@ -60,7 +50,7 @@ extern "C" MFA_API int mfa_debug_mllt_acc_host(int32_t dim, int32_t num_pdfs, co
         for (int j = 0; j <= i; j++) mllt_acc_add(gdi, d[j], full[(size_t)i * dim + j]);
       }
     }
-    gmm_acc_total(w, gmm_acc_frame_loglike(mx, sum), h_tot[0], h_tot[1]);
+    gmm_acc_total(w, gmm_acc_frame_loglike(f.mx, f.sum), h_tot[0], h_tot[1]);
   }
   // the upper triangle is a copy of the lower, for the Gaussians of every pdf a frame was added to
   for (int p = 0; p < num_pdfs; p++) {

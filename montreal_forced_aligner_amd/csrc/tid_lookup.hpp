@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "acc_segments.hpp"
+
 // What the GMM statistics add to the pass (all NULL for the fMLLR caller): the frame's sort key and value — its pdf, or
 // num_pdfs for a frame that takes no part (id 0 or outside the table, weight 0, a pdf the model does not have), and its
 // own index —, the pdfs' frame counts and the transition-ids' (integer atomics: exact in any order).
@@ -33,19 +35,10 @@ static __global__ void fmllr_tid_lookup_kernel(const int32_t *ali, int64_t n, co
       s.key[t] = take ? (uint32_t)p : (uint32_t)s.num_pdfs;
       s.val[t] = (uint32_t)t;
     }
-    // An alignment is runs of one transition-id (self-loops), and silence holds a good share of a corpus: one atomic per
-    // run of equal ids inside the wavefront, not one per frame, keeps the hot counters from serialising the launch.
-    const int lane = threadIdx.x & 63;
-    const int key = take ? tid : -1;
-    const int prev = __shfl_up(key, 1);
-    const bool head = take && (lane == 0 || prev != key);
-    const bool ends = lane == 0 || prev != key;                 // a run of any kind starts here
-    const unsigned long long starts = __ballot(ends);
-    if (head) {
-      const unsigned long long above = lane == 63 ? 0ull : starts >> (lane + 1);
-      const int len = above ? __ffsll((long long)above) : 64 - lane;
+    // one atomic per run of equal transition-ids inside the wavefront (acc_segments.hpp has the reasoning)
+    acc_wave_runs(take, tid, [&](int len) {
       atomicAdd(&s.pdf_count[p], len);
       if (s.tid_count) atomicAdd(&s.tid_count[tid], (unsigned long long)len);
-    }
+    });
   }
 }

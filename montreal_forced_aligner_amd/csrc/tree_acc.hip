@@ -12,7 +12,7 @@
 //   sums    tree_small_kernel, wavefronts striding over the events: an event of at most one chunk is summed and written; a
 //           longer one gets a run of partial rows (an integer atomic hands out the rows: where they lie is not part of the
 //           result).  tree_big_kernel, wavefronts striding over those (event, chunk) units; tree_big_reduce_kernel adds an
-//           event's partials in chunk order.
+//           event's partials in chunk order.  The workspace is carved by acc_segments.hpp's Workspace.
 // A unit is a wavefront: lane = column, the rows of 16 frames fetched whole through the sorted index (all 64 lanes load),
 // staged in the wavefront's own LDS slice and added in frame order.  No floating-point atomics anywhere.
 #include <algorithm>
@@ -20,6 +20,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "acc_segments.hpp"
 #include "ctx.hpp"
 #include "tree_acc_math.hpp"
 
@@ -257,7 +258,10 @@ __global__ __launch_bounds__(256) void tree_big_kernel(SumParams p) {
   }
 }
 
-// Wavefronts striding over the long events: lane = column; the event's partials in chunk order, 8 loads issued together.
+// Wavefronts striding over the long events: lane = column; the event's partials in chunk order, from the first one (an
+// event's row is written, not added to).  acc_ordered_sum's order (acc_segments.hpp), for Σx and Σx² at once: the 16 loads of
+// 8 chunks are issued together.  Two calls of acc_ordered_sum gave the same bits and cost 1 % of the sums stage
+// (1.177 ms against 1.165 ms at tools/tree_acc_rate.py's shape), so the loop stays here.
 __global__ __launch_bounds__(256) void tree_big_reduce_kernel(SumParams p) {
   if (*p.n_events > p.cap) return;
   const int dim = p.dim;
@@ -282,8 +286,6 @@ __global__ __launch_bounds__(256) void tree_big_reduce_kernel(SumParams p) {
     p.ev_sumsq[(size_t)e * dim + w.lane] = b;
   }
 }
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -322,17 +324,16 @@ MFA_API int mfa_tree_acc_batch(mfa_ctx *c, const float *d_feats, const int64_t *
   MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
                                              (uint32_t *)nullptr, T, 0u, end_bit, c->stream));
   MFA_HIP_CHECK(c, rocprim::inclusive_scan(nullptr, scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, T, rocprim::plus<uint32_t>(), c->stream));
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = align256(o + bytes); return at; };
-  const size_t o_key = take(T * 8), o_key2 = take(T * 8), o_val = take(T * 4), o_val2 = take(T * 4), o_left = take(T * 4),
-               o_rank = take(T * 4), o_start = take((T + 1) * 4), o_cnt = take(8), o_big = take(big_ev_cap * 8),
-               o_desc = take(unit_cap * 8), o_part = take(unit_cap * 2 * (size_t)dim * 8), o_tmp = take(std::max(sort_bytes, scan_bytes));
-  if (c->d_ws.reserve(c, o, "the tree statistics workspace")) return -1;
-  char *ws = c->d_ws.ptr<char>();
-  uint64_t *key = (uint64_t *)(ws + o_key), *key2 = (uint64_t *)(ws + o_key2);
-  uint32_t *val = (uint32_t *)(ws + o_val), *val2 = (uint32_t *)(ws + o_val2), *rank = (uint32_t *)(ws + o_rank);
-  uint32_t *flag = (uint32_t *)(ws + o_left);              // the left neighbours are done with when the heads are flagged
-  int32_t *left = (int32_t *)(ws + o_left), *ev_start = (int32_t *)(ws + o_start), *counters = (int32_t *)(ws + o_cnt);
+  Workspace ws;
+  const size_t o_key = ws.take(T * 8), o_key2 = ws.take(T * 8), o_val = ws.take(T * 4), o_val2 = ws.take(T * 4), o_left = ws.take(T * 4),
+               o_rank = ws.take(T * 4), o_start = ws.take((T + 1) * 4), o_cnt = ws.take(8), o_big = ws.take(big_ev_cap * 8),
+               o_desc = ws.take(unit_cap * 8), o_part = ws.take(unit_cap * 2 * (size_t)dim * 8),
+               o_tmp = ws.take(std::max(sort_bytes, scan_bytes));
+  if (ws.reserve(c, "the tree statistics workspace")) return -1;
+  uint64_t *key = ws.at<uint64_t>(o_key), *key2 = ws.at<uint64_t>(o_key2);
+  uint32_t *val = ws.at<uint32_t>(o_val), *val2 = ws.at<uint32_t>(o_val2), *rank = ws.at<uint32_t>(o_rank);
+  uint32_t *flag = ws.at<uint32_t>(o_left);                // the left neighbours are done with when the heads are flagged
+  int32_t *left = ws.at<int32_t>(o_left), *ev_start = ws.at<int32_t>(o_start), *counters = ws.at<int32_t>(o_cnt);
   const unsigned frame_blocks = (unsigned)((T + 255) / 256);
 
   {
@@ -345,9 +346,9 @@ MFA_API int mfa_tree_acc_batch(mfa_ctx *c, const float *d_feats, const int64_t *
   }
   {
     KernelTimer kt(c, MFA_K_TREE_ORDER);
-    MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(ws + o_tmp, sort_bytes, key, key2, val, val2, T, 0u, end_bit, c->stream));
+    MFA_HIP_CHECK(c, rocprim::radix_sort_pairs(ws.at<char>(o_tmp), sort_bytes, key, key2, val, val2, T, 0u, end_bit, c->stream));
     hipLaunchKernelGGL(tree_heads_kernel, dim3(frame_blocks), dim3(256), 0, c->stream, key2, total_frames, none, flag);
-    MFA_HIP_CHECK(c, rocprim::inclusive_scan(ws + o_tmp, scan_bytes, flag, rank, T, rocprim::plus<uint32_t>(), c->stream));
+    MFA_HIP_CHECK(c, rocprim::inclusive_scan(ws.at<char>(o_tmp), scan_bytes, flag, rank, T, rocprim::plus<uint32_t>(), c->stream));
     EventParams ep{key2, val2, rank, total_frames, none, bits, cap, d_frame_event, ev_start, d_n_events, d_ev_key};
     hipLaunchKernelGGL(tree_events_kernel, dim3(frame_blocks), dim3(256), 0, c->stream, ep);
     MFA_HIP_CHECK(c, hipGetLastError());
@@ -356,7 +357,7 @@ MFA_API int mfa_tree_acc_batch(mfa_ctx *c, const float *d_feats, const int64_t *
     KernelTimer kt(c, MFA_K_TREE_SUMS);
     MFA_HIP_CHECK(c, hipMemsetAsync(counters, 0, 8, c->stream));
     SumParams sp{d_feats, val2, ev_start, d_n_events, cap, dim, d_ev_count, d_ev_sum, d_ev_sumsq, counters,
-                 (int32_t *)(ws + o_big), (int32_t *)(ws + o_desc), (double *)(ws + o_part), (int32_t)big_ev_cap, (int32_t)unit_cap};
+                 ws.at<int32_t>(o_big), ws.at<int32_t>(o_desc), ws.at<double>(o_part), (int32_t)big_ev_cap, (int32_t)unit_cap};
     // eight workgroups a CU at the most: a wavefront walks the events (units) its stride gives it
     const size_t ev_max = std::min(T, (size_t)cap);
     const unsigned g_small = (unsigned)std::min((ev_max + kWaves - 1) / kWaves, (size_t)cus * 8);

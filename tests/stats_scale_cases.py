@@ -65,6 +65,13 @@ def occupied_frames(P, occupied) -> np.ndarray:
     return counts
 
 
+def step_frames(Cg, Cm) -> np.ndarray:
+    """The reductions add eight partials a step, then the rest one by one: pdfs of 7, 8 and 9 units of the GMM statistics
+    (7·Cg, 8·Cg and 8·Cg + 1 frames) and one of 7 units of the MLLT statistics (7·Cm frames; tests/test_stats_scale_cpu.py's
+    other cases hold 8, 9 and 10), with two small pdfs between them."""
+    return np.array([7 * Cg, 2, 8 * Cg, 3, 8 * Cg + 1, 7 * Cm])
+
+
 def _zero_weight_pdf(counts) -> int:
     """A pdf of one to three frames whose second transition-id gets weight 0 (its own frames carry the first)."""
     small = np.flatnonzero((np.asarray(counts) >= 1) & (np.asarray(counts) <= 3))
@@ -316,6 +323,16 @@ def tree_long_event_case(chunk, dim=13, integer=True) -> TR.Case:
     if not integer:
         case.feats = (rng.normal(size=case.feats.shape) * np.linspace(12.0, 1.5, dim) + rng.normal(0, 5.0, size=dim)).astype(np.float32)
     return case
+
+
+@lru_cache(maxsize=None)
+def tree_step_event_case(chunk, dim=13) -> TR.Case:
+    """A context-independent three-state phone whose states last 7·chunk + 1, 8·chunk + 1 and 9·chunk + 1 frames: events of
+    8, 9 and 10 chunks, so that 7, 8 and 9 partials are added to an event's first (eight a step, then the rest)."""
+    tm = TR.mono_tm()
+    ali = np.concatenate([TR.phone_path(tm, 1, [7 * chunk + 1, 8 * chunk + 1, 9 * chunk + 1]), TR.phone_path(tm, 4, [3, 2, 2]),
+                          TR.phone_path(tm, 3, [1])])
+    return _tree_case(tm, [ali], dim, TR.CI, 5002)
 
 
 def de_bruijn(k, n=3):

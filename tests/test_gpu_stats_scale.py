@@ -221,6 +221,15 @@ def test_tree_on_long_events(engine, dim):
     assert {8 * C.TREE_CHUNK + 1, 17 * C.TREE_CHUNK} <= set(st.count.tolist())
 
 
+def test_tree_on_events_at_the_reductions_step(engine):
+    """Events of 8, 9 and 10 chunks: tree_big_reduce_kernel adds 7, 8 and 9 partials to the first (eight a step, then the rest)."""
+    _constants_are_the_librarys(engine)
+    case = S.tree_step_event_case(C.TREE_CHUNK)
+    st, _fe = tree_is_exact(engine, case)
+    print(C.tree_line("events of 8, 9, 10 chunks", case, st))
+    assert sorted(S.units(st.count, C.TREE_CHUNK).tolist())[-3:] == [8, 9, 10]
+
+
 def test_tree_with_more_events_than_wavefronts(engine):
     cus = _cus(engine)
     k = S.small_event_phones(cus)

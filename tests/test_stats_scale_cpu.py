@@ -40,6 +40,7 @@ def key_count_cases():
     for P in S.KEY_COUNTS:
         out.append((f"P={P}", 13, S.key_count_frames(P, CG, CM), dict(gmm_units=(1, 10), mllt_units=(1, 2, 8), min_units=257 if P >= 511 else 0)))
     out.append(("P=257 long last", 13, S.key_count_frames(257, CG, CM, last=9 * CM + 1), dict(gmm_units=(10,), mllt_units=(10,))))
+    out.append(("P=6 at the reduction step", 13, S.step_frames(CG, CM), dict(gmm_step=(7, 8, 9), mllt_step=(7,))))
     out.append(("P=4960 sparse", 13, S.sparse_frames(4960), dict(sparse=True)))
     for dim in (40, 48):
         for occupied in (256, 257, 400):
@@ -60,6 +61,10 @@ def reaches_its_path(name, case, counts, want, order):
     for n in want.get("gmm_units", ()):
         assert n in ug, (name, "GMM units", n)
     for n in want.get("mllt_units", ()):
+        assert n in um, (name, "MLLT units", n)
+    for n in want.get("gmm_step", ()):
+        assert n in ug, (name, "GMM units", n)
+    for n in want.get("mllt_step", ()):
         assert n in um, (name, "MLLT units", n)
     if "gmm_units" in want:
         assert ug.max() >= 8 and um.max() >= 8 and got[0] == 9 * CG + 1 and CG in got, name
@@ -162,6 +167,11 @@ def lda_cases():
     for C, order in ((255, "shuffled"), (256, "shuffled"), (256, "aligned"), (257, "shuffled")):
         out.append((f"dim 13: {C} classes, slab + 1, {order}", (13, 3, (LDA_SLAB - 40, 41), C, ((C - 1, LDA_CHUNK + 1),), order),
                     dict(slabs=2, units=(2,), order=order)))
+    # the reductions add eight partials a step, then the rest: 7 and 8 slabs (9 above), classes of 7, 8 and 9 units
+    step_classes = ((0, 7 * LDA_CHUNK), (300, 8 * LDA_CHUNK), (599, 8 * LDA_CHUNK + 1))
+    for slabs in (7, 8):
+        out.append((f"dim 13: 600 classes, {slabs} slabs, shuffled", (13, 3, (slabs * LDA_SLAB - 4000, 4000), 600, step_classes, "shuffled"),
+                    dict(slabs=slabs, units=(7, 8, 9), order="shuffled")))
     return out
 
 
@@ -261,6 +271,13 @@ def test_tree_twin_on_long_events():
     print(tree_line("long events", case, st))
     assert {8 * TREE_CHUNK + 1, 17 * TREE_CHUNK} <= set(st.count.tolist())
     assert sorted(S.units(st.count, TREE_CHUNK).tolist())[-2:] == [9, 17]
+
+
+def test_tree_twin_on_events_at_the_reductions_step():
+    case = S.tree_step_event_case(TREE_CHUNK)
+    st = tree_equal_to_ref(case, tree_host(case))
+    print(tree_line("events of 8, 9, 10 chunks", case, st))
+    assert sorted(S.units(st.count, TREE_CHUNK).tolist())[-3:] == [8, 9, 10]
 
 
 def test_tree_twin_with_every_frame_its_own_event():
