@@ -149,6 +149,7 @@ class CorpusAligner:
         self.alimdl_stats: Optional[GmmStats] = None     # the statistics of the last ``estimate_alignment_model``
         self.tree_stats: Optional[TreeStats] = None      # the statistics of the last ``tree_statistics``
         self.tree_skipped = 0                            # ... and the utterances it skipped
+        self.pronunciation_counts = None                 # pronprob.PronunciationCounts of the last ``pronunciation_statistics``
         self.lda = None if lda is None else np.asarray(lda, dtype=np.float32)
         self.opt = options or AlignOptions()
         self.engine = engine or AlignmentEngine(device)
@@ -736,6 +737,43 @@ class CorpusAligner:
         if self.tree_stats is None:
             raise ValueError("tree_statistics: no utterances")
         return self.tree_stats
+
+    # ------------------------------------------------------------------ pronunciation probabilities
+    def pronunciation_statistics(self, utterances: Sequence[CorpusUtterance], speaker_adapted: bool = False):
+        """The counts of the pronunciation-probability stage (GeneratePronunciationsFunction, MFA/alignment/multiprocessing.py:
+        1476-1570): ``align`` with the interval stage on, then ``pronprob.count_from_intervals`` over every batch's interval
+        arrays — the tables ``pronprob.count_from_ctm`` gives over the ``ctm`` objects of the same alignment, without building
+        one.  An utterance counts in the batch its result comes from (with an alignment model: the first pass's when the
+        second lost it); one that failed, or whose interval stage failed, counts nowhere.  Kept as ``pronunciation_counts``."""
+        from . import pronprob
+
+        with self._run():
+            results = self._align(list(utterances), speaker_adapted, True, None)[0]
+        ex = self._extractor()
+        index = pronprob.PronunciationIndex(self.lexicon)
+        chosen: Dict[int, tuple] = {}                     # per batch: its interval arrays and the utterances that count in it
+        by_object = []                                    # (an utterance only the Python interval stage could take: its ctm)
+        for r in results:
+            if r is not None and r._lazy is not None:
+                batch, k = r._lazy[0], r._lazy[1]
+                chosen.setdefault(id(batch), (batch, np.zeros(batch.n_utt, dtype=bool)))[1][k] = True
+            elif r is not None and r._ctm is not None:
+                by_object.append(r._ctm)
+        del results
+        counts = pronprob.count_from_ctm(self.lexicon, by_object, index)
+        for batch, select in chosen.values():
+            counts += pronprob.count_from_intervals(ex, batch, select, index)
+        self.pronunciation_counts = counts
+        return counts
+
+    def train_dictionary(self, utterances: Sequence[CorpusUtterance], speaker_adapted: bool = False):
+        """``mfa train_dictionary`` on this aligner's model (DictionaryTrainer, MFA/alignment/pretrained.py:561-613):
+        ``pronunciation_statistics`` then ``pronprob.estimate`` — (a new ``LexiconCompiler`` with the re-estimated records,
+        the four silence numbers).  The aligner keeps the lexicon it has; ``pronprob.write_dictionary`` /
+        ``write_silence_info`` write the result."""
+        from . import pronprob
+
+        return pronprob.estimate(self.lexicon, self.pronunciation_statistics(utterances, speaker_adapted))
 
     def _reload(self, raw_tm, raw_am, raw_ali_am) -> None:
         """Make the adapted models the aligner's own: transition model (graphs, scaled probabilities), boosted copies, device."""

@@ -16,7 +16,9 @@ Gaussian per pdf on the splice + LDA features → the same loop, shared through 
 speaker-adapted stage on either feature path: per-speaker fMLLR under the previous model, a tree on the adapted features, the
 same loop with fMLLR re-estimated and composed at ``fmllr_iterations``, and after it the speaker-independent alignment model
 (``alignment_model``) from two-feature statistics — posteriors on the adapted features, sums of the unadapted ones —, so that
-the stage ends in a ``final.mdl`` + ``final.alimdl`` pair.
+the stage ends in a ``final.mdl`` + ``final.alimdl`` pair.  ``PronunciationProbabilityTrainer`` (at the end) trains no model: it
+aligns with the previous stage's, counts the aligned pronunciations and the silences around them (``pronprob``) and hands the
+next stage a lexicon with probabilities.
 
 The device is driven through a backend of three calls — ``equal_align``, ``align``, ``accumulate``, and for the tree
 ``tree_accumulate`` and ``convert_alignments``, for the SAT stage ``align_previous``, ``estimate_transforms`` and
@@ -963,3 +965,121 @@ class SatTrainer(GmmTrainerBase):
                              lda=self.lda_mat, ali_am=DiagGmmModel.from_raw(self.ali_raw_am), mfcc_options=self.mfcc_options,
                              silence_phones=self.silence_phones, raw_tm=self.raw_tm, raw_am=self.raw_am,
                              raw_ali_am=self.ali_raw_am, **kw)
+
+
+# ---- the pronunciation-probability stage ------------------------------------------------------------------------------------------
+class PronunciationDeviceBackend:
+    """``PronunciationProbabilityTrainer``'s one call on the device: ``CorpusAligner.pronunciation_statistics`` with the
+    previous stage's model — one pass, or with ``speaker_adapted`` the alignment model's pass, fMLLR and a second pass."""
+
+    def __init__(self, utterances, lexicon, options=None, mfcc_options: Optional[dict] = None, silence_phones: Sequence[int] = (),
+                 device: int = 0, engine=None):
+        from .aligner import AlignOptions
+
+        self.utts = list(utterances)
+        self.lexicon, self.opt = lexicon, options or AlignOptions()
+        self.mfcc_options, self.silence_phones = dict(mfcc_options or {}), list(silence_phones)
+        self.device, self.engine = device, engine
+        self.al = None
+
+    def pronunciation_counts(self, raw_tm, raw_am, tree, lda, ali_raw_am, speaker_adapted: bool):
+        """(``pronprob.PronunciationCounts`` of the corpus, utterances without an alignment)."""
+        from .aligner import CorpusAligner
+
+        self.al = CorpusAligner(TransitionModel(raw_tm), DiagGmmModel.from_raw(raw_am), tree, self.lexicon, lda=lda,
+                                options=self.opt, device=self.device, engine=self.engine, mfcc_options=self.mfcc_options,
+                                silence_phones=self.silence_phones, raw_tm=raw_tm, raw_am=raw_am,
+                                ali_am=None if ali_raw_am is None else DiagGmmModel.from_raw(ali_raw_am), raw_ali_am=ali_raw_am)
+        self.engine = self.al.engine
+        counts = self.al.pronunciation_statistics(self.utts, speaker_adapted=speaker_adapted)
+        return counts, len(self.al.failed)
+
+
+class PronunciationProbabilityTrainer:
+    """The reference's ``PronunciationProbabilityTrainer`` (MFA/acoustic_modeling/pronunciation_probabilities.py; the estimate
+    in MFA/alignment/base.py:937-1176): no model is trained — the corpus is aligned with the previous stage's model, the
+    aligned pronunciations and the silences around them are counted, and the lexicon is re-estimated from the counts.
+    ``PronunciationProbabilityTrainer(previous, utterances, lexicon).train()`` then ``write(directory)``.
+
+    ``previous``: a trained stage or ``(raw_tm, raw_am, tree)``.  From a stage its ``lda_mat``, its alignment model
+    (``ali_raw_tm`` / ``ali_raw_am``) and its ``transforms`` are picked up (``previous_lda=`` / ``ali_model=(raw_tm, raw_am)``
+    give the first two by hand); with an alignment model the alignment is the two-pass one (``speaker_adapted=`` overrides).
+
+    ``train`` sets ``counts`` (``pronprob.PronunciationCounts``), ``lexicon`` (the re-estimated ``LexiconCompiler``; the one
+    given stays as ``source_lexicon``), ``info`` (the four silence numbers) and ``failed``.  ``raw_tm`` / ``raw_am`` / ``tree``
+    (and ``lda_mat``, ``transforms``) are the previous stage's, so that the stage can itself be a ``previous``:
+    ``SatTrainer(utterances, lexicon=stage.lexicon, previous=stage)`` continues on graphs compiled from the new lexicon.
+    ``write`` writes the model files of the previous stage (``final.mdl``, ``tree``, with them ``final.alimdl`` / ``lda.mat``
+    when there are any), ``lexicon.dict`` and ``silence_probabilities.json``."""
+
+    DICTIONARY, SILENCE_INFO = "lexicon.dict", "silence_probabilities.json"
+
+    def __init__(self, previous=None, utterances=None, lexicon=None, previous_lda: Optional[np.ndarray] = None, ali_model=None,
+                 speaker_adapted: Optional[bool] = None, align_options=None, silence_phones: Optional[Sequence[int]] = None,
+                 mfcc_options: Optional[dict] = None, device: int = 0, engine=None, backend=None):
+        if previous is None or lexicon is None:
+            raise ValueError("PronunciationProbabilityTrainer needs a lexicon and the previous stage's (raw_tm, raw_am, tree)")
+        self.source_lexicon, self.previous = lexicon, previous_models(previous)
+        self.raw_tm, self.raw_am, self.tree = self.previous
+        if previous_lda is None:
+            previous_lda = getattr(previous, "lda_mat", None)
+        self.lda_mat = None if previous_lda is None else np.asarray(previous_lda, dtype=np.float32)
+        if ali_model is None and getattr(previous, "ali_raw_am", None) is not None:
+            ali_model = (previous.ali_raw_tm, previous.ali_raw_am)
+        self.ali_raw_tm, self.ali_raw_am = ali_model if ali_model is not None else (None, None)
+        self.transforms = getattr(previous, "transforms", None)
+        self.speaker_adapted = (self.ali_raw_am is not None) if speaker_adapted is None else bool(speaker_adapted)
+        self.opt = align_options or getattr(previous, "opt", None)
+        self.silence_phones = list(getattr(previous, "silence_phones", ()) if silence_phones is None else silence_phones)
+        self.mfcc_options = dict(getattr(previous, "mfcc_options", {}) if mfcc_options is None else mfcc_options)
+        if engine is None:
+            engine = getattr(getattr(previous, "backend", None), "engine", None)
+        self.backend = backend if backend is not None else PronunciationDeviceBackend(utterances, lexicon, self.opt, self.mfcc_options,
+                                                                                      self.silence_phones, device, engine)
+        self.lexicon = None
+        self.info: Optional[Dict] = None
+        self.counts = None
+        self.failed = 0
+
+    def train(self) -> "PronunciationProbabilityTrainer":
+        from . import pronprob
+
+        self.counts, self.failed = self.backend.pronunciation_counts(self.raw_tm, self.raw_am, self.tree, self.lda_mat,
+                                                                     self.ali_raw_am, self.speaker_adapted)
+        if self.counts.utterances == 0:
+            raise ValueError("PronunciationProbabilityTrainer: the previous model aligned no utterance")
+        self.lexicon, self.info = pronprob.estimate(self.source_lexicon, self.counts)
+        return self
+
+    def write(self, directory) -> List[Path]:
+        from . import pronprob
+
+        if self.lexicon is None:
+            raise ValueError("PronunciationProbabilityTrainer.write: train has not been run")
+        out = Path(directory)
+        files = GmmTrainerBase.write(self, out)
+        if self.ali_raw_am is not None:
+            with open(out / "final.alimdl", "wb") as f:
+                kaldi_io.write_model(f, self.ali_raw_tm if self.ali_raw_tm is not None else self.raw_tm, self.ali_raw_am)
+            files.append(out / "final.alimdl")
+        if self.lda_mat is not None:
+            with open(out / "lda.mat", "wb") as f:
+                f.write(b"\0B")
+                kaldi_io.write_matrix(f, self.lda_mat)
+            files.append(out / "lda.mat")
+        files.append(pronprob.write_dictionary(out / self.DICTIONARY, self.lexicon))
+        files.append(pronprob.write_silence_info(out / self.SILENCE_INFO, self.info))
+        return files
+
+    def aligner(self, **kw):
+        """A ``CorpusAligner`` on the previous stage's model and the re-estimated lexicon (on the training engine when the
+        device backend ran)."""
+        from .aligner import CorpusAligner
+
+        kw.setdefault("engine", getattr(self.backend, "engine", None))
+        if self.opt is not None:
+            kw.setdefault("options", self.opt)
+        return CorpusAligner(TransitionModel(self.raw_tm), DiagGmmModel.from_raw(self.raw_am), self.tree, self.lexicon,
+                             lda=self.lda_mat, ali_am=None if self.ali_raw_am is None else DiagGmmModel.from_raw(self.ali_raw_am),
+                             mfcc_options=self.mfcc_options, silence_phones=self.silence_phones, raw_tm=self.raw_tm,
+                             raw_am=self.raw_am, raw_ali_am=self.ali_raw_am, **kw)
