@@ -49,7 +49,7 @@ MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
 /* Per-kernel accumulated HIP-event times since the last reset.  which: 0 mfcc, 1 cmvn, 2 feats, 3 gmm, 4 viterbi,
  * 5 resample, 6 pitch, 7 feature codec, 8-11 GMM statistics (lookup, ordering, sums, reduction), 12 equal alignment,
  * 13-16 LDA statistics (lookup, second moment, ordering + class sums, reductions), 17-20 MLLT statistics (lookup,
- * ordering, sums, reductions), 21-23 tree statistics (keys, ordering, sums).
+ * ordering, sums, reductions), 21-23 tree statistics (keys, ordering, sums), 24 speech activity (each entry point's launches).
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -262,6 +262,97 @@ MFA_API int mfa_compress_batch(mfa_ctx *ctx, const float *d_feats, const int64_t
  * h_out [rows][cols], each or NULL.  No context, no device.  < 0: an empty table. */
 MFA_API int mfa_debug_compress_host(const float *h_table, int32_t rows, int32_t cols, float *h_global, uint16_t *h_colhdr,
                                     uint8_t *h_bytes, float *h_out);
+
+/* ---- Speech activity: Kaldi's energy VAD (compute-vad, kalpy VadComputer), apply-cmvn-sliding, select-voiced-frames +
+ *      subsample-feats, and the runs of voiced frames the reference's segmenter walks frame by frame
+ *      (MFA/vad/multiprocessing.py:324-406, MFA/vad/models.py:44-130, MFA/corpus/features.py:284-342).
+ * All of them take a ragged batch with d_frame_off[0] = 0 and total_frames = d_frame_off[n_utt] < 2^31, given by the caller
+ * (the grids are sized from it), and are parallel over the frames inside an utterance.  The arithmetic lives in
+ * csrc/vad_math.hpp, host and device; the mfa_debug_*_host twins (csrc/vad_host.cpp: no context, no device) run the same
+ * operations in the same order, and every result below has the same bits on either side, whatever else is in the batch, in
+ * whatever order, and whatever the grid.
+ *
+ * The integer scan all of them rest on: d_scan[f] = Σ d_values[g] over the frames g < f of f's own utterance (an exclusive
+ * scan that starts again at every d_frame_off boundary), d_totals[u] = the utterance's sum (either may be NULL).  Built
+ * reduce-then-scan: sums of blocks of mfa_vad_scan_block_frames() consecutive frames, an exclusive scan of the block sums
+ * by one workgroup (a thread walks more than one block sum once there are more than mfa_vad_scan_totals_threads() of
+ * them), then the scan inside every block.  No workgroup waits for another.  Sums must stay below 2^31. */
+MFA_API int32_t mfa_vad_scan_block_frames(void);
+MFA_API int32_t mfa_vad_scan_totals_threads(void);
+MFA_API int mfa_vad_scan_batch(mfa_ctx *ctx, const int32_t *d_values, const int64_t *d_frame_off, int32_t n_utt,
+                               int64_t total_frames, int32_t *d_scan, int32_t *d_totals);
+MFA_API int mfa_debug_vad_scan_host(const int32_t *h_values, const int64_t *h_frame_off, int32_t n_utt, int32_t *h_scan,
+                                    int32_t *h_totals);
+
+/* Energy VAD (Kaldi ComputeVadEnergy) on column 0 of d_feats float32 [total_frames][stride], e(t) = that column:
+ *   thr(u)     = (float)((double)energy_threshold + (double)energy_mean_scale · (sum / T)) for energy_mean_scale != 0 and
+ *                T > 0, else energy_threshold.  sum is float64 in this order: the utterance is cut into chunks of
+ *                mfa_vad_sum_chunk_frames() frames from its first frame; inside a chunk, lane l of 256 adds frames l, l + 256, …
+ *                in that order from 0.0; the 256 lane sums are folded by halving (lane l += lane l + 128, then + 64, … + 1);
+ *                the chunk sums are added in chunk order from 0.0.
+ *   voiced(t)  iff (float)num >= (float)den · proportion_threshold (one float32 product), den = frames of [t − ctx, t + ctx]
+ *                inside the utterance, num = those of them with e > thr, from the scan above — exact for any
+ *                frames_context >= 0.
+ * d_vad float32 [total_frames] 1.0 / 0.0 (what compute-vad writes), d_thr float32 [n_utt], d_voiced int32 [n_utt] (NULL:
+ * not wanted).  The reference's adaptive mode (threshold = the mean of c0, mean scale 0) is energy_threshold 0,
+ * energy_mean_scale 1 here; numpy's float32 pairwise mean and this float64 mean can differ in the last bit. */
+typedef struct {
+  float energy_threshold;      /* Kaldi 5.0; the reference passes 5.5 */
+  float energy_mean_scale;     /* 0.5 */
+  float proportion_threshold;  /* 0.6 */
+  int32_t frames_context;      /* 0 */
+} mfa_vad_opts;
+MFA_API int32_t mfa_vad_sum_chunk_frames(void);
+MFA_API int mfa_vad_batch(mfa_ctx *ctx, const float *d_feats, int32_t stride, const int64_t *d_frame_off, int32_t n_utt,
+                          int64_t total_frames, int32_t max_frames, const mfa_vad_opts *opts, float *d_vad, float *d_thr,
+                          int32_t *d_voiced);
+MFA_API int mfa_debug_vad_host(const float *h_feats, int32_t stride, const int64_t *h_frame_off, int32_t n_utt,
+                               const mfa_vad_opts *opts, float *h_vad, float *h_thr, int32_t *h_voiced);
+
+/* Sliding-window CMVN (Kaldi SlidingWindowCmn) of columns [0, dim) of d_feats [total_frames][stride] into d_out of the
+ * same shape (not d_feats itself); columns [dim, stride) are copied.  The window of frame t of T:
+ *   center: start = t − cmn_window / 2, end = start + cmn_window; else start = t − cmn_window, end = t + 1;
+ *   start < 0: end −= start, start = 0;  not center and end > t: end = max(t + 1, min_window);
+ *   end > T: start −= end − T, end = T, start = max(start, 0).
+ * out = (float)((x − sum / n) · f) in float64, rounded once; f = 1 without norm_vars or with n = 1, else
+ * 1 / sqrt(max(sumsq / n − (sum / n)², 1e-10)).  sum and sumsq are float64 running sums with this order: the utterance is
+ * cut into tiles of mfa_sliding_cmvn_tile_frames() frames from its first frame; a tile's first frame adds its window's
+ * frames in frame order from 0.0; every next frame first takes off the frames that left the window, in frame order, then
+ * adds the ones that entered, in frame order (a window that does not continue the previous one is summed from 0.0 again). */
+typedef struct {
+  int32_t cmn_window;          /* Kaldi 600; the reference's archive 300 */
+  int32_t min_window;          /* 100 */
+  int32_t center;              /* 0 */
+  int32_t norm_vars;           /* 0 */
+} mfa_sliding_cmvn_opts;
+MFA_API int32_t mfa_sliding_cmvn_tile_frames(void);
+MFA_API int mfa_sliding_cmvn_batch(mfa_ctx *ctx, const float *d_feats, const int64_t *d_frame_off, int32_t n_utt,
+                                   int32_t max_frames, int32_t dim, int32_t stride, const mfa_sliding_cmvn_opts *opts,
+                                   float *d_out);
+MFA_API int mfa_debug_sliding_cmvn_host(const float *h_feats, const int64_t *h_frame_off, int32_t n_utt, int32_t dim,
+                                        int32_t stride, const mfa_sliding_cmvn_opts *opts, float *h_out);
+
+/* Frame selection: select-voiced-frames (rows with d_vad[f] != 0; NULL: all rows) followed by subsample-feats n >= 1 (rows
+ * 0, n, 2n, … of what remains: ceil(T' / n) rows; Kaldi's negative offset form is refused).  Two steps, as the caller sizes
+ * the output: mfa_select_frames_count writes d_out_off int64 [n_utt + 1] (the new frame offsets) and d_src int32
+ * [total_frames], whose first d_out_off[n_utt] entries name the source row of every output row; mfa_select_frames_batch
+ * is the gather of n_out rows of dim columns (strides in floats) by that map. */
+MFA_API int mfa_select_frames_count(mfa_ctx *ctx, const float *d_vad, const int64_t *d_frame_off, int32_t n_utt,
+                                    int64_t total_frames, int32_t n, int32_t *d_src, int64_t *d_out_off);
+MFA_API int mfa_select_frames_batch(mfa_ctx *ctx, const float *d_feats, int32_t stride, int32_t dim, const int32_t *d_src,
+                                    int64_t n_out, float *d_out, int32_t out_stride);
+MFA_API int mfa_debug_select_frames_host(const float *h_vad, const int64_t *h_frame_off, int32_t n_utt, int32_t n,
+                                         int32_t *h_src, int64_t *h_out_off);
+
+/* Runs of voiced frames: every maximal run of frames with d_vad != 0 inside an utterance, in order, as (first frame, last
+ * frame + 1) relative to the utterance's first frame; d_run_off int64 [n_utt + 1]: run_off[u] .. run_off[u + 1] are the
+ * runs of utterance u.  d_run_begin / d_run_end int32 [capacity]: runs beyond capacity are counted, not written — the
+ * caller reads d_run_off[n_utt] and calls again with room for all when it is larger. */
+MFA_API int mfa_vad_runs_batch(mfa_ctx *ctx, const float *d_vad, const int64_t *d_frame_off, int32_t n_utt,
+                               int64_t total_frames, int64_t capacity, int32_t *d_run_begin, int32_t *d_run_end,
+                               int64_t *d_run_off);
+MFA_API int mfa_debug_vad_runs_host(const float *h_vad, const int64_t *h_frame_off, int32_t n_utt, int64_t capacity,
+                                    int32_t *h_run_begin, int32_t *h_run_end, int64_t *h_run_off);
 
 /* ---- Acoustic model: replaces GmmAligner.__init__'s model load (+ .boost_silence, applied by the host to gconsts)
  *      (MFA/alignment/multiprocessing.py:814-815).  Host arrays, SoA over all Gaussians:

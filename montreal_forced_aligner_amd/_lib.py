@@ -14,7 +14,7 @@ _PKG = Path(__file__).resolve().parent
 _SO = Path(os.environ["MFA_HIP_SO"]).resolve() if os.environ.get("MFA_HIP_SO") else _PKG / "libmfa_hip.so"   # (override: A/B builds)
 _SOURCES = ["api.hip", "mfcc.hip", "feats.hip", "gmm.hip", "gmm_band.hip", "gmm_pack.cpp", "score_plan.cpp", "viterbi.hip", "viterbi_general.hip",
             "fmllr.hip", "gmm_acc.hip", "gmm_acc_host.cpp", "resample.hip", "resample_plan.cpp", "pitch.hip", "pitch_plan.cpp", "compress.hip", "align_equal.hip", "align_equal_host.cpp",
-            "lda_acc.hip", "lda_acc_host.cpp", "mllt_acc.hip", "mllt_acc_host.cpp", "tree_acc.hip", "tree_acc_host.cpp"]
+            "lda_acc.hip", "lda_acc_host.cpp", "mllt_acc.hip", "mllt_acc_host.cpp", "tree_acc.hip", "tree_acc_host.cpp", "vad.hip", "vad_host.cpp"]
 _LIB = None
 
 
@@ -60,6 +60,15 @@ class PitchOpts(C.Structure):
     ]
 
 
+class VadOpts(C.Structure):
+    _fields_ = [("energy_threshold", C.c_float), ("energy_mean_scale", C.c_float), ("proportion_threshold", C.c_float),
+                ("frames_context", C.c_int32)]
+
+
+class SlidingCmvnOpts(C.Structure):
+    _fields_ = [("cmn_window", C.c_int32), ("min_window", C.c_int32), ("center", C.c_int32), ("norm_vars", C.c_int32)]
+
+
 class GraphBatch(C.Structure):
     _fields_ = [
         ("n_utt", C.c_int32),
@@ -101,7 +110,7 @@ def build_native(force: bool = False, verbose: bool = False) -> Path:
     src_dir = _PKG / "csrc"
     srcs = [src_dir / s for s in _SOURCES]
     headers = ("ctx.hpp", "dev_buf.hpp", "gmm_common.hpp", "gmm_f32.hpp", "gmm_split.hpp", "gmm_pack.hpp", "viterbi_common.hpp", "viterbi_eps.hpp", "viterbi_wave.hpp", "viterbi_small.hpp",
-               "resample_plan.hpp", "pitch_plan.hpp", "compress_math.hpp", "gmm_acc_math.hpp", "gmm_acc_twin.hpp", "acc_posterior.hpp", "acc_segments.hpp", "tid_lookup.hpp", "align_equal_math.hpp", "lda_acc_math.hpp", "mllt_acc_math.hpp", "tree_acc_math.hpp")
+               "resample_plan.hpp", "pitch_plan.hpp", "compress_math.hpp", "gmm_acc_math.hpp", "gmm_acc_twin.hpp", "acc_posterior.hpp", "acc_segments.hpp", "tid_lookup.hpp", "align_equal_math.hpp", "lda_acc_math.hpp", "mllt_acc_math.hpp", "tree_acc_math.hpp", "vad_math.hpp")
     deps = srcs + [src_dir / h for h in headers] + [_PKG.parent / "include" / "mfa_hip.h"]
     if not force and _SO.exists() and all(_SO.stat().st_mtime >= d.stat().st_mtime for d in deps if d.exists()):
         return _SO
@@ -156,6 +165,21 @@ SIGNATURES = {
     "mfa_compress_resident_values": (_i32, []),
     "mfa_compress_batch": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "mfa_debug_compress_host": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mfa_vad_scan_block_frames": (_i32, []),
+    "mfa_vad_scan_totals_threads": (_i32, []),
+    "mfa_vad_scan_batch": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _vp]),
+    "mfa_debug_vad_scan_host": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    "mfa_vad_sum_chunk_frames": (_i32, []),
+    "mfa_vad_batch": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i64, _i32, C.POINTER(VadOpts), _vp, _vp, _vp]),
+    "mfa_debug_vad_host": (C.c_int, [_vp, _i32, _vp, _i32, C.POINTER(VadOpts), _vp, _vp, _vp]),
+    "mfa_sliding_cmvn_tile_frames": (_i32, []),
+    "mfa_sliding_cmvn_batch": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(SlidingCmvnOpts), _vp]),
+    "mfa_debug_sliding_cmvn_host": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.POINTER(SlidingCmvnOpts), _vp]),
+    "mfa_select_frames_count": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp]),
+    "mfa_select_frames_batch": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _i32]),
+    "mfa_debug_select_frames_host": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "mfa_vad_runs_batch": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp]),
+    "mfa_debug_vad_runs_host": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _vp]),
     "mfa_load_gmm": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mfa_gmm_slot": (_i32, [_vp, _i32]),
     "mfa_gmm_sort_pdf_list": (C.c_int, [_vp, _vp, _i32, _vp]),

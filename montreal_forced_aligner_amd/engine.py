@@ -41,7 +41,7 @@ KERNEL_SLOTS = ("mfcc", "cmvn", "feats", "gmm", "viterbi", "resample", "pitch", 
                 "acc_lookup", "acc_sort", "acc_sums", "acc_reduce", "equal_align",
                 "lda_lookup", "lda_second", "lda_class", "lda_reduce",
                 "mllt_lookup", "mllt_sort", "mllt_sums", "mllt_reduce",
-                "tree_keys", "tree_order", "tree_sums")
+                "tree_keys", "tree_order", "tree_sums", "vad")
 
 
 def _out_ptrs(out: Dict[str, Optional[torch.Tensor]]):
@@ -233,6 +233,30 @@ class AlignmentEngine(GraphPacking, FrontEndStages):
         check(self.ctx, self.lib.mfa_compress_batch(self.ctx, _ptr(feats), _ptr(d_frame_off), n_utt, int(feats.shape[1]), c0, c1,
                                                     _ptr(cmvn), _ptr(d_utt2spk), int(cmvn.shape[2]) - 1 if cmvn is not None else 0,
                                                     _ptr(out), _ptr(glob), _ptr(colhdr), _ptr(data)), "mfa_compress_batch")
+
+    def _launch_vad(self, feats, d_frame_off, n_utt: int, total: int, max_frames: int, opts, vad, thr, voiced) -> None:
+        check(self.ctx, self.lib.mfa_vad_batch(self.ctx, _ptr(feats), int(feats.shape[1]), _ptr(d_frame_off), n_utt, total, max_frames,
+                                               C.byref(opts), _ptr(vad), _ptr(thr), _ptr(voiced)), "mfa_vad_batch")
+
+    def _launch_sliding_cmvn(self, feats, d_frame_off, n_utt: int, max_frames: int, dim: int, opts, out) -> None:
+        check(self.ctx, self.lib.mfa_sliding_cmvn_batch(self.ctx, _ptr(feats), _ptr(d_frame_off), n_utt, max_frames, dim,
+                                                        int(feats.shape[1]), C.byref(opts), _ptr(out)), "mfa_sliding_cmvn_batch")
+
+    def _launch_select_count(self, vad, d_frame_off, n_utt: int, total: int, n: int, src, out_off) -> None:
+        check(self.ctx, self.lib.mfa_select_frames_count(self.ctx, _ptr(vad), _ptr(d_frame_off), n_utt, total, n, _ptr(src),
+                                                         _ptr(out_off)), "mfa_select_frames_count")
+
+    def _launch_select(self, feats, src, n_out: int, out) -> None:
+        check(self.ctx, self.lib.mfa_select_frames_batch(self.ctx, _ptr(feats), int(feats.shape[1]), int(feats.shape[1]), _ptr(src),
+                                                         n_out, _ptr(out), int(out.shape[1])), "mfa_select_frames_batch")
+
+    def _launch_vad_runs(self, vad, d_frame_off, n_utt: int, total: int, capacity: int, begin, end, run_off) -> None:
+        check(self.ctx, self.lib.mfa_vad_runs_batch(self.ctx, _ptr(vad), _ptr(d_frame_off), n_utt, total, capacity, _ptr(begin),
+                                                    _ptr(end), _ptr(run_off)), "mfa_vad_runs_batch")
+
+    def _launch_scan(self, values, d_frame_off, n_utt: int, total: int, scan, totals) -> None:
+        check(self.ctx, self.lib.mfa_vad_scan_batch(self.ctx, _ptr(values), _ptr(d_frame_off), n_utt, total, _ptr(scan),
+                                                    _ptr(totals)), "mfa_vad_scan_batch")
 
     def _launch_score(self, feats, d_frame_off, n_utt: int, max_frames: int, pdf_list, d_pdf_off, class_counts, pdf_first_frame,
                       d_ll_off, out) -> None:

@@ -1,7 +1,10 @@
-"""Stages around the MFCC: sample-rate conversion ahead of it, pitch and voicing pasted after CMVN, and the 8-bit feature
-codec (Kaldi CompressedMatrix) — ``FrontEndStages``, methods of ``AlignmentEngine``.
+"""Stages around the MFCC: sample-rate conversion ahead of it, pitch and voicing pasted after CMVN, the 8-bit feature
+codec (Kaldi CompressedMatrix), and speech activity (energy VAD, sliding-window CMVN, voiced-frame selection with
+subsampling, voiced runs) — ``FrontEndStages``, methods of ``AlignmentEngine``; the speech-activity stage's host twins
+as functions.
 
-Uses of the engine: ``lib``, ``ctx``, ``device``, ``_dev``, ``_launch_compress``; ``mfcc_opts`` / ``num_ceps`` /
+Uses of the engine: ``lib``, ``ctx``, ``device``, ``_dev``, ``_launch_compress``, ``_launch_vad`` / ``_launch_sliding_cmvn`` /
+``_launch_select_count`` / ``_launch_select`` / ``_launch_vad_runs`` / ``_launch_scan``; ``mfcc_opts`` / ``num_ceps`` /
 ``configure_mfcc`` / ``frame_offsets`` / ``mfcc`` (the MFCC stage); its own fields ``pitch_opts`` and ``num_pitch_cols``.
 """
 from __future__ import annotations
@@ -13,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PitchOpts, _ptr, check
+from ._lib import PitchOpts, SlidingCmvnOpts, VadOpts, _ptr, check
 from .ragged import max_len, offsets
 
 # Kaldi's PitchExtractionOptions / ProcessPitchOptions at MFA's values (MFA/models.py:551-576 sets max_f0 800 and
@@ -24,6 +27,13 @@ DEFAULT_PITCH = dict(sample_frequency=16000.0, frame_length_ms=25.0, frame_shift
                      lowpass_filter_width=1, upsample_filter_width=5, snip_edges=1, normalization_context=75,
                      add_pov_feature=1, add_normalized_log_pitch=1, add_raw_log_pitch=0, add_delta_pitch=0)
 _PITCH_ALIAS = {"frame_length": "frame_length_ms", "frame_shift": "frame_shift_ms"}    # kalpy's names (milliseconds)
+
+# Kaldi's VadEnergyOptions (kalpy VadComputer's arguments; the reference's segmenter passes energy_threshold 5.5) and
+# SlidingWindowCmnOptions (the reference's speaker-task archive: cmn_window 300, center)
+DEFAULT_VAD = dict(energy_threshold=5.0, energy_mean_scale=0.5, proportion_threshold=0.6, frames_context=0)
+_VAD_ALIAS = {"vad_energy_threshold": "energy_threshold", "vad_energy_mean_scale": "energy_mean_scale",
+              "vad_frames_context": "frames_context", "vad_proportion_threshold": "proportion_threshold"}
+DEFAULT_SLIDING_CMVN = dict(cmn_window=600, min_window=100, center=0, norm_vars=0)
 
 
 class FrontEndStages:
@@ -273,3 +283,144 @@ class FrontEndStages:
         data = torch.empty(int(fo[-1]) * nc, dtype=torch.uint8, device=self.device)
         self._launch_compress(feats, self._dev(fo), n_utt, c0, c1, None, None, None, glob, colhdr, data)
         return glob, colhdr, data
+
+    # ------------------------------------------------------------------ speech activity (energy VAD, sliding CMVN, selection, runs)
+    def _ragged_input(self, x: torch.Tensor, frame_off, what: str, dims: int = 2, dtype=torch.float32):
+        """A contiguous device tensor whose rows are exactly the batch's frames, and its offsets (int64, from 0)."""
+        if not (x.is_cuda and x.dtype == dtype and x.dim() == dims and x.is_contiguous()):
+            raise _lib.MfaHipError(f"{what}: the input must be a contiguous {dtype} tensor of {dims} dimension(s) on the device")
+        fo = np.ascontiguousarray(frame_off, dtype=np.int64)
+        if fo.ndim != 1 or fo.shape[0] < 1 or fo[0] != 0 or (np.diff(fo) < 0).any() or fo[-1] != x.shape[0]:
+            raise _lib.MfaHipError(f"{what}: frame offsets must run from 0 to the {x.shape[0]} rows of the input")
+        return fo, fo.shape[0] - 1
+
+    def vad_scan_block_frames(self) -> int:
+        """Frames per block of the per-utterance integer scan (mfa_vad_scan_block_frames); one workgroup scans the block sums,
+        a thread of it more than one beyond ``vad_scan_totals_threads()`` blocks."""
+        return int(self.lib.mfa_vad_scan_block_frames())
+
+    def vad_scan_totals_threads(self) -> int:
+        return int(self.lib.mfa_vad_scan_totals_threads())
+
+    def sliding_cmvn_tile_frames(self) -> int:
+        return int(self.lib.mfa_sliding_cmvn_tile_frames())
+
+    def segment_scan(self, values: torch.Tensor, frame_off: np.ndarray):
+        """The scan the stage rests on, by itself: (exclusive scan of int32 ``values`` inside every utterance, the utterances'
+        sums)."""
+        fo, n_utt = self._ragged_input(values, frame_off, "scan", 1, torch.int32)
+        scan = torch.empty_like(values)
+        totals = torch.empty(n_utt, dtype=torch.int32, device=self.device)
+        self._launch_scan(values, self._dev(fo), n_utt, int(fo[-1]), scan, totals)
+        return scan, totals
+
+    def vad(self, feats: torch.Tensor, frame_off: np.ndarray, **opts):
+        """Kaldi's energy VAD on column 0 of ``feats`` (MFCC with use_energy: the log energy).  Options: ``DEFAULT_VAD``.
+        Returns (vad float32 [ΣT] of 1.0 / 0.0 — what compute-vad writes —, thresholds float32 [n_utt], voiced counts int32
+        [n_utt]).  The reference's adaptive mode is ``energy_threshold=0, energy_mean_scale=1``."""
+        o = _lib.options(VadOpts, DEFAULT_VAD, opts, "VAD", _VAD_ALIAS)
+        fo, n_utt = self._ragged_input(feats, frame_off, "VAD")
+        vad = torch.empty(int(fo[-1]), dtype=torch.float32, device=self.device)
+        thr = torch.empty(n_utt, dtype=torch.float32, device=self.device)
+        voiced = torch.empty(n_utt, dtype=torch.int32, device=self.device)
+        self._launch_vad(feats, self._dev(fo), n_utt, int(fo[-1]), max_len(fo), o, vad, thr, voiced)
+        return vad, thr, voiced
+
+    def sliding_cmvn(self, feats: torch.Tensor, frame_off: np.ndarray, dim: Optional[int] = None, **opts) -> torch.Tensor:
+        """Kaldi's SlidingWindowCmn (apply-cmvn-sliding) on the first ``dim`` columns (default: all) of every utterance; the
+        other columns are copied.  Options: ``DEFAULT_SLIDING_CMVN``.  A new tensor."""
+        o = _lib.options(SlidingCmvnOpts, DEFAULT_SLIDING_CMVN, opts, "sliding CMVN")
+        fo, n_utt = self._ragged_input(feats, frame_off, "sliding CMVN")
+        out = torch.empty_like(feats)
+        self._launch_sliding_cmvn(feats, self._dev(fo), n_utt, max_len(fo), int(feats.shape[1]) if dim is None else int(dim), o, out)
+        return out
+
+    def select_frames(self, feats: torch.Tensor, frame_off: np.ndarray, vad: Optional[torch.Tensor] = None, subsample_n: int = 1):
+        """select-voiced-frames (rows with ``vad`` != 0; None: all) then subsample-feats ``subsample_n`` (rows 0, n, 2n, … of
+        what remains).  Returns (features, frame_off) of the rows kept.  One scan, one gather; the host waits once, for
+        the new offsets."""
+        fo, n_utt = self._ragged_input(feats, frame_off, "frame selection")
+        if vad is not None and (not vad.is_cuda or vad.dtype != torch.float32 or vad.dim() != 1 or vad.shape[0] != feats.shape[0]
+                                or not vad.is_contiguous()):
+            raise _lib.MfaHipError("frame selection: the VAD vector must be a contiguous float32 tensor on the device, one value per row")
+        src = torch.empty(int(fo[-1]), dtype=torch.int32, device=self.device)
+        d_out_off = torch.empty(n_utt + 1, dtype=torch.int64, device=self.device)
+        self._launch_select_count(vad, self._dev(fo), n_utt, int(fo[-1]), int(subsample_n), src, d_out_off)
+        out_off = d_out_off.cpu().numpy()
+        out = torch.empty((int(out_off[-1]), int(feats.shape[1])), dtype=torch.float32, device=self.device)
+        self._launch_select(feats, src, int(out_off[-1]), out)
+        return out, out_off
+
+    def vad_runs(self, vad: torch.Tensor, frame_off: np.ndarray, capacity: Optional[int] = None):
+        """The maximal runs of voiced frames of every utterance: (run_begin int32 [R], run_end int32 [R] = last frame + 1, both
+        relative to the utterance, run_off int64 [n_utt + 1]) as host arrays.  The first call brings room for ``capacity``
+        runs (default: a run per 16 frames and one per utterance); when the batch has more it is run again with room for
+        all of them, which cannot fall short."""
+        fo, n_utt = self._ragged_input(vad, frame_off, "voiced runs", 1)
+        total = int(fo[-1])
+        cap = min((total + 1) // 2 + n_utt, total // 16 + n_utt) if capacity is None else int(capacity)
+        d_fo = self._dev(fo)
+        run_off = torch.empty(n_utt + 1, dtype=torch.int64, device=self.device)
+        while True:
+            begin = torch.empty(cap, dtype=torch.int32, device=self.device)
+            end = torch.empty(cap, dtype=torch.int32, device=self.device)
+            self._launch_vad_runs(vad, d_fo, n_utt, total, cap, begin, end, run_off)
+            ro = run_off.cpu().numpy()
+            if int(ro[-1]) <= cap:
+                return begin[: int(ro[-1])].cpu().numpy(), end[: int(ro[-1])].cpu().numpy(), ro
+            cap = int(ro[-1])
+
+
+# ---------------------------------------------------------------------- the host twins of the speech-activity stage
+# (csrc/vad_host.cpp: the kernels' arithmetic in their order on host arrays; no context, no device — tests and tools)
+def _host_offsets(frame_off) -> np.ndarray:
+    return np.ascontiguousarray(frame_off, dtype=np.int64)
+
+
+def _twin(rc: int, what: str) -> None:
+    if rc != 0:
+        raise _lib.MfaHipError(f"{what}: arguments refused")
+
+
+def vad_scan_host(values: np.ndarray, frame_off):
+    v, fo = np.ascontiguousarray(values, dtype=np.int32), _host_offsets(frame_off)
+    scan, totals = np.empty_like(v), np.empty(fo.shape[0] - 1, dtype=np.int32)
+    _twin(_lib.lib().mfa_debug_vad_scan_host(v.ctypes.data, fo.ctypes.data, fo.shape[0] - 1, scan.ctypes.data, totals.ctypes.data), "scan twin")
+    return scan, totals
+
+
+def vad_host(feats: np.ndarray, frame_off, **opts):
+    x, fo = np.ascontiguousarray(feats, dtype=np.float32), _host_offsets(frame_off)
+    o = _lib.options(VadOpts, DEFAULT_VAD, opts, "VAD", _VAD_ALIAS)
+    n = fo.shape[0] - 1
+    vad, thr, voiced = np.empty(x.shape[0], dtype=np.float32), np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
+    _twin(_lib.lib().mfa_debug_vad_host(x.ctypes.data, x.shape[1], fo.ctypes.data, n, C.byref(o), vad.ctypes.data, thr.ctypes.data,
+                                        voiced.ctypes.data), "VAD twin")
+    return vad, thr, voiced
+
+
+def sliding_cmvn_host(feats: np.ndarray, frame_off, dim: Optional[int] = None, **opts) -> np.ndarray:
+    x, fo = np.ascontiguousarray(feats, dtype=np.float32), _host_offsets(frame_off)
+    o = _lib.options(SlidingCmvnOpts, DEFAULT_SLIDING_CMVN, opts, "sliding CMVN")
+    out = np.empty_like(x)
+    _twin(_lib.lib().mfa_debug_sliding_cmvn_host(x.ctypes.data, fo.ctypes.data, fo.shape[0] - 1, x.shape[1] if dim is None else int(dim),
+                                                 x.shape[1], C.byref(o), out.ctypes.data), "sliding CMVN twin")
+    return out
+
+
+def select_frames_host(feats: np.ndarray, frame_off, vad: Optional[np.ndarray] = None, subsample_n: int = 1):
+    fo = _host_offsets(frame_off)
+    v = None if vad is None else np.ascontiguousarray(vad, dtype=np.float32)
+    src, out_off = np.empty(int(fo[-1]), dtype=np.int32), np.empty(fo.shape[0], dtype=np.int64)
+    _twin(_lib.lib().mfa_debug_select_frames_host(None if v is None else v.ctypes.data, fo.ctypes.data, fo.shape[0] - 1, int(subsample_n),
+                                                  src.ctypes.data, out_off.ctypes.data), "selection twin")
+    return np.asarray(feats)[src[: int(out_off[-1])]], out_off
+
+
+def vad_runs_host(vad: np.ndarray, frame_off):
+    v, fo = np.ascontiguousarray(vad, dtype=np.float32), _host_offsets(frame_off)
+    cap = (int(fo[-1]) + 1) // 2 + fo.shape[0]
+    begin, end, run_off = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32), np.empty(fo.shape[0], dtype=np.int64)
+    _twin(_lib.lib().mfa_debug_vad_runs_host(v.ctypes.data, fo.ctypes.data, fo.shape[0] - 1, cap, begin.ctypes.data, end.ctypes.data,
+                                             run_off.ctypes.data), "runs twin")
+    return begin[: int(run_off[-1])], end[: int(run_off[-1])], run_off

@@ -304,17 +304,75 @@ class CmvnComputer:
         kaldi_io.write_table(ark, entries, "matrix", ark.with_suffix(".scp") if write_scp else None)
 
 
+# apply-cmvn-sliding as the reference's speaker-task archive runs it (FinalFeatureFunction, MFA/corpus/features.py:284-342)
+SLIDING_CMVN_ARCHIVE = dict(cmn_window=300, center=1, norm_vars=0)
+
+
+class VadComputer:
+    """``VadComputer(energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0, proportion_threshold=0.6)``: Kaldi's
+    energy VAD (compute-vad) on column 0 of a feature matrix, on the device."""
+
+    def __init__(self, energy_threshold: float = 5.0, energy_mean_scale: float = 0.5, frames_context: int = 0,
+                 proportion_threshold: float = 0.6):
+        self.options = dict(energy_threshold=float(energy_threshold), energy_mean_scale=float(energy_mean_scale),
+                            frames_context=int(frames_context), proportion_threshold=float(proportion_threshold))
+
+    def compute_vad(self, feats: np.ndarray) -> np.ndarray:
+        """float32 [T] of 1.0 / 0.0, one per frame."""
+        return self._batch([np.asarray(feats)])[0]
+
+    def _batch(self, mats: Sequence[np.ndarray]) -> List[np.ndarray]:
+        import torch
+
+        eng = get_engine()
+        fo = offsets([m.shape[0] for m in mats])
+        d = torch.from_numpy(np.ascontiguousarray(np.concatenate(mats), dtype=np.float32)).to(eng.device)
+        vad = eng.vad(d, fo, **self.options)[0].cpu().numpy()
+        return [vad[fo[i]: fo[i + 1]].copy() for i in range(len(mats))]
+
+    def export_vad(self, file_name, feature_archive, write_scp: bool = False, callback=None, batch_size: int = 256) -> None:
+        """``vad.ark`` (+ ``.scp``) of float vectors keyed by utterance for (utt key, matrix) pairs; an utterance without
+        frames is skipped, as compute-vad skips it.  ``callback(n)`` after every batch of n utterances."""
+        ark = Path(file_name)
+        entries, batch = [], []
+
+        def flush():
+            entries.extend(zip([k for k, _ in batch], self._batch([m for _, m in batch])))
+            if callback is not None:
+                callback(len(batch))
+            batch.clear()
+
+        for key, m in (feature_archive.items() if isinstance(feature_archive, dict) else feature_archive):
+            if np.asarray(m).shape[0] == 0:
+                logger.warning("Empty feature matrix for utterance %s", key)
+                continue
+            batch.append((key, np.asarray(m)))
+            if len(batch) >= batch_size:
+                flush()
+        if batch:
+            flush()
+        kaldi_io.write_table(ark, entries, "vector", ark.with_suffix(".scp") if write_scp else None)
+
+
 class FeatureArchive:
     """``FeatureArchive(scp, utt2spk=, cmvn_file_name=, lda_mat_file_name=, transform_file_name=, deltas=, …)``: iterable of
     (utt_id, final feature matrix) — Job.construct_feature_archive's chain (MFA/db.py:2101-2136): base features from the
-    scp (compressed or not) → per-speaker CMVN → Δ+ΔΔ or splice(±3)+LDA → per-speaker fMLLR.  Utterances are pushed
-    through the device in batches of ``batch_size``; ``utt2spk`` is a dict or a Kaldi utt2spk file."""
+    scp (compressed or not) → sliding-window CMVN (``use_sliding_cmvn``: cmn_window 300, centred) or else per-speaker CMVN →
+    Δ+ΔΔ or splice(±3)+LDA → per-speaker fMLLR → the voiced frames of ``vad_file_name`` → every ``subsample_n``-th of them.
+    An utterance whose VAD vector is missing, of another length than its features, or without a voiced frame is skipped with
+    a warning (select-voiced-frames).  Utterances are pushed through the device in batches of ``batch_size``; ``utt2spk`` is
+    a dict or a Kaldi utt2spk file.  kalpy and Kaldi being absent where this was written, the order of the last three steps and
+    the sliding window's options are restated from their published behaviour, unpinned."""
 
     def __init__(self, file_name, utt2spk=None, cmvn_file_name=None, lda_mat_file_name=None, transform_file_name=None,
                  vad_file_name=None, deltas: bool = False, splices: bool = False, splice_frames: int = 3, subsample_n: int = 0,
-                 use_sliding_cmvn: bool = False, batch_size: int = 256):
-        if vad_file_name is not None or subsample_n or use_sliding_cmvn:
-            raise NotImplementedError("vad / subsampling / sliding CMVN are not part of the alignment path")
+                 use_sliding_cmvn: bool = False, batch_size: int = 256, stages=None):
+        if subsample_n < 0:
+            raise NotImplementedError("subsample-feats with a negative n (Kaldi's offset form) is not built")
+        self.subsample_n = int(subsample_n) or 1
+        self.use_sliding_cmvn = bool(use_sliding_cmvn)
+        self.vad_read_specifier = vad_file_name
+        self._stages = stages        # the stage methods' owner (default: the process's engine); tensors live on its ``device``
         self.file_name = Path(file_name)
         self.utt2spk = self._read_map(utt2spk)
         self.cmvn_read_specifier = cmvn_file_name
@@ -328,6 +386,7 @@ class FeatureArchive:
         self._cache: Dict[str, bytes] = {}
         self._cmvn = self._read_table(cmvn_file_name)
         self._trans = self._read_table(transform_file_name)
+        self._vad = self._read_table(vad_file_name, "vector")
         self._lda = None if lda_mat_file_name is None else kaldi_io.read_matrix_file(Path(lda_mat_file_name).read_bytes())
         if self._trans is not None and self._lda is None and not self.use_deltas:
             # CMVN-only features are not final features: the reference transforms after the deltas or the LDA (MFA/db.py:2101-2136)
@@ -339,13 +398,13 @@ class FeatureArchive:
             return m
         return dict(line.split()[:2] for line in Path(m).read_text(encoding="utf8").splitlines() if line.strip())
 
-    def _read_table(self, name) -> Optional[Dict[str, np.ndarray]]:
+    def _read_table(self, name, kind: str = "matrix") -> Optional[Dict[str, np.ndarray]]:
         if name is None:
             return None
         name = Path(name)
         if name.suffix == ".scp":
-            return {k: kaldi_io.read_scp_object(self._cache, p, o, "matrix") for k, p, o in kaldi_io.read_scp(name)}
-        return dict(kaldi_io.read_ark(name.read_bytes(), "matrix"))
+            return {k: kaldi_io.read_scp_object(self._cache, p, o, kind) for k, p, o in kaldi_io.read_scp(name)}
+        return dict(kaldi_io.read_ark(name.read_bytes(), kind))
 
     def _base(self) -> Iterator[Tuple[str, np.ndarray]]:
         if self._entries is not None:
@@ -365,6 +424,13 @@ class FeatureArchive:
                 st[i] = self._cmvn[s]
         return st
 
+    @staticmethod
+    def noop_cmvn_rows(n_spk: int, dim: int) -> np.ndarray:
+        """Statistics that leave the features as they are: the "mean 0 over count 1" row of ``cmvn_rows`` for every speaker."""
+        st = np.zeros((n_spk, 2, dim + 1), dtype=np.float64)
+        st[:, 0, dim] = 1.0
+        return st
+
     def base_rows(self) -> Iterator[Tuple[str, np.ndarray, str]]:
         """(utt_id, base feature matrix as stored, speaker name): for a consumer that applies CMVN (``cmvn_rows``) and
         splices (``splice_frames``) on the device itself — ``LdaStatsAccumulator``."""
@@ -374,15 +440,32 @@ class FeatureArchive:
     def __iter__(self) -> Iterator[Tuple[str, np.ndarray]]:
         import torch
 
-        eng = get_engine()
+        eng = self._stages if self._stages is not None else get_engine()
         batch: List[Tuple[str, np.ndarray]] = []
 
         def flush():
+            if self._vad is not None:      # select-voiced-frames: such an utterance is skipped with a warning
+                kept = []
+                for k, m in batch:
+                    v = self._vad.get(k)
+                    if v is None:
+                        logger.warning("No VAD input found for utterance %s", k)
+                    elif v.shape[0] != m.shape[0]:
+                        logger.warning("Mismatch in number of frames %d for features and VAD %d, for utterance %s", m.shape[0], v.shape[0], k)
+                    elif not np.any(v != 0):
+                        logger.warning("No features voiced for utterance %s", k)
+                    else:
+                        kept.append((k, m))
+                batch[:] = kept
+                if not batch:
+                    return []
             spk_names = [self.utt2spk.get(k, k) if self.utt2spk else k for k, _ in batch]
             ids = {s: i for i, s in enumerate(dict.fromkeys(spk_names))}
             u2s = np.array([ids[s] for s in spk_names], dtype=np.int32)
             dim = batch[0][1].shape[1]
             st = self.cmvn_rows(ids, dim)
+            if self.use_sliding_cmvn:      # instead of the speakers' CMVN: the feature kernel gets "mean 0 over count 1" rows
+                st = None if not (self.use_deltas or self._lda is not None) else self.noop_cmvn_rows(len(ids), dim)
             cm = None if st is None else torch.from_numpy(st).to(eng.device)
             lda = None if self._lda is None else torch.from_numpy(self._lda.astype(np.float32)).to(eng.device)
             fm = None
@@ -395,15 +478,21 @@ class FeatureArchive:
                 fm = torch.from_numpy(ft).to(eng.device)
             fo = offsets([m.shape[0] for _, m in batch])
             d = torch.from_numpy(np.concatenate([m for _, m in batch]).astype(np.float32)).to(eng.device)
+            if self.use_sliding_cmvn:
+                d = eng.sliding_cmvn(d, fo, **SLIDING_CMVN_ARCHIVE)
             if self.use_splices and lda is None:
                 raise NotImplementedError("spliced features without an LDA matrix")
             if not self.use_deltas and lda is None:
                 out = d if cm is None else None
                 if out is None:   # CMVN only (FinalFeatureFunction's output): Δ kernel's first block is the CMVN-applied base
                     out = eng.features(d, fo, u2s, cm)[:, :dim]
-                out = out.cpu().numpy()
             else:
-                out = eng.features(d, fo, u2s, cm, lda=lda, fmllr=fm, splice_context=self.splice_frames).cpu().numpy()
+                out = eng.features(d, fo, u2s, cm, lda=lda, fmllr=fm, splice_context=self.splice_frames)
+            if self._vad is not None or self.subsample_n > 1:      # last: voiced frames, then every n-th of them
+                vad = None if self._vad is None else \
+                    torch.from_numpy(np.concatenate([self._vad[k] for k, _ in batch]).astype(np.float32)).to(eng.device)
+                out, fo = eng.select_frames(out.contiguous(), fo, vad, self.subsample_n)
+            out = out.cpu().numpy()
             res = [(k, out[fo[i]: fo[i + 1]].copy()) for i, (k, _) in enumerate(batch)]
             batch.clear()
             return res
