@@ -49,7 +49,8 @@ MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
 /* Per-kernel accumulated HIP-event times since the last reset.  which: 0 mfcc, 1 cmvn, 2 feats, 3 gmm, 4 viterbi,
  * 5 resample, 6 pitch, 7 feature codec, 8-11 GMM statistics (lookup, ordering, sums, reduction), 12 equal alignment,
  * 13-16 LDA statistics (lookup, second moment, ordering + class sums, reductions), 17-20 MLLT statistics (lookup,
- * ordering, sums, reductions), 21-23 tree statistics (keys, ordering, sums), 24 speech activity (each entry point's launches).
+ * ordering, sums, reductions), 21-23 tree statistics (keys, ordering, sums), 24 speech activity (each entry point's launches),
+ * 25-28 diagonal UBM (selection, posteriors, sums, reductions).
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -881,6 +882,78 @@ MFA_API int mfa_debug_tree_acc_host(const float *h_feats, const int64_t *h_frame
                                     const int32_t *h_tid_flags, int32_t n_tids, const uint8_t *h_phone_ci, int32_t n_phones,
                                     int64_t cap, int32_t *h_frame_event, int64_t *h_n_events, int64_t *h_skipped,
                                     uint64_t *h_ev_key, int64_t *h_ev_count, double *h_ev_sum, double *h_ev_sumsq);
+
+/* ---- Diagonal UBM: replaces the per-job work of the reference's DubmTrainer (MFA/ivector/trainer.py:105-388,
+ *      MFA/ivector/multiprocessing.py:64-140 and :233-280): Gaussian selection (Kaldi gmm-gselect =
+ *      DiagGmm::GaussianSelection) and the global statistics over the selected Gaussians (gmm-global-acc-stats --gselect =
+ *      AccumDiagGmm::AccumulateFromDiag), restated here from the algorithms' descriptions — Kaldi's source is not among this
+ *      project's references: parity unpinned, DESIGN §2.
+ * Both calls take the model — one mixture of G Gaussians — as device arrays with the call: d_gconsts [G], d_means_invvars
+ * [G][dim], d_inv_vars [G][dim].  There is no context state and mfa_load_gmm is not involved.
+ *
+ * Gaussian selection.  Arithmetic contract.  For every frame t and every Gaussian g, ll_g is the GMM statistics' float32 fmaf
+ * chain (above).  With n = min(num_gselect, G), d_gselect [total_frames][n] (int32) receives the n Gaussians of largest
+ * ll, best first, in the order of (ll, index) pairs sorted descending: at equal ll the larger index comes first (how
+ * Kaldi's sort of pairs is remembered: unpinned).  The order is that of the 64-bit keys of csrc/ubm_math.hpp (the
+ * order-preserving image of the float's bits, then the index), which is total over every bit pattern: whatever the features
+ * are, NaN and infinity included, a frame's indices are distinct and lie in [0, G), and nothing faults.  (The key tells
+ * -0 from +0; a NaN sorts above +inf or below -inf by its sign bit.)  d_loglike [total_frames] (may be NULL) receives the
+ * frame's log-sum-exp over the SELECTED Gaussians only: m + logf(s), m the best ll, s = sum of expf(ll - m), float32.
+ * Order on the device: none that matters for d_gselect — the result is a function of the input alone; the expf(ll - m) of
+ * d_loglike are added across a wavefront's lanes.  The [frames][G] log-likelihoods are never written to memory.
+ * mfa_debug_ubm_gselect_host is the same contract on host arrays with libm's expf / logf: both run csrc/gmm_acc_math.hpp and
+ * csrc/ubm_math.hpp, so the ll bits, and with them the indices and their order, are the device's by construction; only
+ * d_loglike may differ (expf / logf themselves and the order in which the exponentials are added).
+ * Limits (refused with a message, the context stays usable): dim <= 0 or dim > 48; G <= 0 or G > 2048 (32 rounds of lane =
+ * Gaussian); num_gselect <= 0 or min(num_gselect, G) > 64 (a frame's list is one wavefront register); a NULL array that
+ * would be read or written; 2^31 frames or more.  total_frames == 0 is no error and writes nothing.  Asynchronous on the ctx
+ * stream; timing slot 25.  mfa_ubm_gselect_tile_frames(): the frames a workgroup of the selection stages at a time (tests cut
+ * their batches around it). */
+MFA_API int32_t mfa_ubm_gselect_tile_frames(void);
+MFA_API int mfa_ubm_gselect_batch(mfa_ctx *ctx, const float *d_feats, int64_t total_frames, int32_t dim, int32_t G,
+                                  const float *d_gconsts, const float *d_means_invvars, const float *d_inv_vars,
+                                  int32_t num_gselect, int32_t *d_gselect, float *d_loglike);
+/* Host twin.  Returns 0, -1 for bad arguments (dim <= 0, a NULL array that would be read or written), -2 for dim > 48, -3
+ * for G outside [1, 2048], -4 for num_gselect <= 0 or min(num_gselect, G) > 64, -5 for 2^31 frames or more. */
+MFA_API int mfa_debug_ubm_gselect_host(const float *h_feats, int64_t total_frames, int32_t dim, int32_t G,
+                                       const float *h_gconsts, const float *h_means_invvars, const float *h_inv_vars,
+                                       int32_t num_gselect, int32_t *h_gselect, float *h_loglike);
+
+/* Global GMM statistics.  Arithmetic contract.  A frame's Gaussians: with d_gselect ([total_frames][n] int32) its n listed
+ * indices, of which one outside [0, G) is skipped; with d_gselect NULL every Gaussian (n is ignored: the init phase's dense
+ * E-step).  The frame's weight w is d_frame_weight[t], or 1 when that is NULL.  A frame with no valid index, or with weight
+ * 0, takes no part.  Otherwise, over the frame's Gaussians, the GMM statistics' softmax operation for operation: ll_g (the
+ * chain), m = max ll, e_g = expf(ll_g - m), s = sum of e_g, gamma_g = e_g * (1 / s) * w, the frame's log-likelihood
+ * LL = m + logf(s), all float32; and the GMM statistics' sums (double, explicit fma):
+ *   occ[g] += gamma_g;  mean[g][k] = fma(gamma_g, x_k, mean[g][k]);  var[g][k] = fma(gamma_g, x_k * x_k, var[g][k]) with
+ *   the square formed in double;  tot[0] = fma(w, LL, tot[0]);  tot[1] += w.
+ * d_occ [G], d_mean / d_var [G][dim], d_tot [2] are added to, never overwritten; a Gaussian that no frame selects keeps the
+ * caller's bits.  d_post (may be NULL; only with a d_gselect): [total_frames][n] float receives gamma in the list's order, 0
+ * for a skipped entry and for a frame that takes no part.  A list's indices are distinct, as the selection writes them; a
+ * list that repeats an index is outside the contract (on the device one of the repeated entries counts; nothing faults).
+ * Feature rows are finite; a value that is not enters the device's sums as 0 beside the NaN its gamma already is.
+ * Order on the device: the batch's frames are cut into slabs of mfa_ubm_acc_slab_frames() consecutive frames; a slab is
+ * summed from zero in frame order, 4 frames per step of the f64 matrix instruction (a Gaussian that a frame does not list
+ * adds an exact zero there); the slabs are added in order onto the caller's value, tot likewise from the slabs' totals.  The
+ * slabs run in passes sized to the context's workspace; the slab order makes the result independent of the passes.  The
+ * result is a function of the input alone: two calls on the same input give the same bits.  No floating-point atomics.
+ * mfa_debug_ubm_acc_host is the same contract on host arrays, frames in ascending index, a frame's Gaussians in list order,
+ * expf / logf from libm: the ll bits are the device's by construction; only expf / logf, the order in which a frame's e_g
+ * are added, and the order and rounding of the double sums may differ.
+ * Limits (refused with a message, the context stays usable): those of the selection for dim, G and the frames; with a
+ * non-NULL d_gselect n <= 0 or n > 64; d_post without d_gselect; a NULL array that would be read or written.
+ * total_frames == 0 is no error and writes nothing.  Asynchronous on the ctx stream; timing slots 26-28. */
+MFA_API int32_t mfa_ubm_acc_slab_frames(void);
+MFA_API int mfa_ubm_acc_batch(mfa_ctx *ctx, const float *d_feats, int64_t total_frames, int32_t dim, int32_t G,
+                              const float *d_gconsts, const float *d_means_invvars, const float *d_inv_vars, int32_t n,
+                              const int32_t *d_gselect, const float *d_frame_weight, double *d_occ, double *d_mean, double *d_var,
+                              double *d_tot, float *d_post);
+/* Host twin.  Return codes as mfa_debug_ubm_gselect_host; -4 for n outside [1, 64] with a non-NULL h_gselect; -1 also for
+ * h_post without h_gselect. */
+MFA_API int mfa_debug_ubm_acc_host(const float *h_feats, int64_t total_frames, int32_t dim, int32_t G, const float *h_gconsts,
+                                   const float *h_means_invvars, const float *h_inv_vars, int32_t n, const int32_t *h_gselect,
+                                   const float *h_frame_weight, double *h_occ, double *h_mean, double *h_var, double *h_tot,
+                                   float *h_post);
 
 #ifdef __cplusplus
 }

@@ -41,7 +41,8 @@ KERNEL_SLOTS = ("mfcc", "cmvn", "feats", "gmm", "viterbi", "resample", "pitch", 
                 "acc_lookup", "acc_sort", "acc_sums", "acc_reduce", "equal_align",
                 "lda_lookup", "lda_second", "lda_class", "lda_reduce",
                 "mllt_lookup", "mllt_sort", "mllt_sums", "mllt_reduce",
-                "tree_keys", "tree_order", "tree_sums", "vad")
+                "tree_keys", "tree_order", "tree_sums", "vad",
+                "ubm_select", "ubm_post", "ubm_sums", "ubm_reduce")
 
 
 def _out_ptrs(out: Dict[str, Optional[torch.Tensor]]):
@@ -253,6 +254,19 @@ class AlignmentEngine(GraphPacking, FrontEndStages):
     def _launch_vad_runs(self, vad, d_frame_off, n_utt: int, total: int, capacity: int, begin, end, run_off) -> None:
         check(self.ctx, self.lib.mfa_vad_runs_batch(self.ctx, _ptr(vad), _ptr(d_frame_off), n_utt, total, capacity, _ptr(begin),
                                                     _ptr(end), _ptr(run_off)), "mfa_vad_runs_batch")
+
+    def _launch_ubm_gselect(self, feats, model, num_gselect: int, gselect, loglike) -> None:
+        """``model``: the device tensors (gconsts, means_invvars, inv_vars) of one mixture."""
+        gc, mi, iv = model
+        check(self.ctx, self.lib.mfa_ubm_gselect_batch(self.ctx, _ptr(feats), int(feats.shape[0]), int(mi.shape[1]), int(gc.shape[0]),
+                                                       _ptr(gc), _ptr(mi), _ptr(iv), num_gselect, _ptr(gselect), _ptr(loglike)),
+              "mfa_ubm_gselect_batch")
+
+    def _launch_ubm_acc(self, feats, model, n: int, gselect, frame_weight, occ, mean, var, tot, post) -> None:
+        gc, mi, iv = model
+        check(self.ctx, self.lib.mfa_ubm_acc_batch(self.ctx, _ptr(feats), int(feats.shape[0]), int(mi.shape[1]), int(gc.shape[0]),
+                                                   _ptr(gc), _ptr(mi), _ptr(iv), n, _ptr(gselect), _ptr(frame_weight), _ptr(occ),
+                                                   _ptr(mean), _ptr(var), _ptr(tot), _ptr(post)), "mfa_ubm_acc_batch")
 
     def _launch_scan(self, values, d_frame_off, n_utt: int, total: int, scan, totals) -> None:
         check(self.ctx, self.lib.mfa_vad_scan_batch(self.ctx, _ptr(values), _ptr(d_frame_off), n_utt, total, _ptr(scan),

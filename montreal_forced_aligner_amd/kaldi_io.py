@@ -240,6 +240,17 @@ def write_int_vector(f: BinaryIO, v) -> None:
     f.write(b"\x04" + struct.pack("<i", v.shape[0]) + v.tobytes())
 
 
+def read_int_vector_vector(r: "BinaryReader") -> List[np.ndarray]:
+    """Kaldi's vector<vector<int32>> (Int32VectorVectorHolder: a gselect archive's entry): the count, then the vectors."""
+    return [r.int_vector() for _ in range(r.int32())]
+
+
+def write_int_vector_vector(f: BinaryIO, vv) -> None:
+    _w_int32(f, len(vv))
+    for v in vv:
+        write_int_vector(f, v)
+
+
 # --------------------------------------------------------------------------- model objects
 @dataclass
 class HmmState:
@@ -336,24 +347,45 @@ def read_am_diag_gmm(r: BinaryReader) -> RawAmDiagGmm:
     n = r.int32()
     am = RawAmDiagGmm(dim, [], [], [], [])
     for _ in range(n):
-        tok = r.token()
-        if tok != "<DiagGMM>":
-            raise KaldiFormatError(f"expected <DiagGMM>, got {tok}")
-        tok = r.token()
-        if tok == "<GCONSTS>":
-            am.gconsts.append(r.vector().astype(np.float32))
-            tok = r.token()
-        else:
-            am.gconsts.append(None)
-        if tok != "<WEIGHTS>":
-            raise KaldiFormatError(f"expected <WEIGHTS>, got {tok}")
-        am.weights.append(r.vector().astype(np.float32))
-        r.expect("<MEANS_INVVARS>")
-        am.means_invvars.append(r.matrix().astype(np.float32))
-        r.expect("<INV_VARS>")
-        am.inv_vars.append(r.matrix().astype(np.float32))
-        r.expect("</DiagGMM>")
+        gc, w, mi, iv = read_diag_gmm(r)
+        am.gconsts.append(gc); am.weights.append(w); am.means_invvars.append(mi); am.inv_vars.append(iv)
     return am
+
+
+def read_diag_gmm(r: BinaryReader):
+    """One ``<DiagGMM>`` object — a pdf of ``final.mdl``, or the whole of a ``.dubm`` file after its binary header — as
+    (gconsts or None, weights, means_invvars, inv_vars), float32."""
+    tok = r.token()
+    if tok != "<DiagGMM>":
+        raise KaldiFormatError(f"expected <DiagGMM>, got {tok}")
+    tok = r.token()
+    gc = None
+    if tok == "<GCONSTS>":
+        gc = r.vector().astype(np.float32)
+        tok = r.token()
+    if tok != "<WEIGHTS>":
+        raise KaldiFormatError(f"expected <WEIGHTS>, got {tok}")
+    w = r.vector().astype(np.float32)
+    r.expect("<MEANS_INVVARS>")
+    mi = r.matrix().astype(np.float32)
+    r.expect("<INV_VARS>")
+    iv = r.matrix().astype(np.float32)
+    r.expect("</DiagGMM>")
+    return gc, w, mi, iv
+
+
+def write_diag_gmm(f: BinaryIO, gconsts, weights, means_invvars, inv_vars) -> None:
+    """One ``<DiagGMM>`` object, as ``read_diag_gmm`` takes it."""
+    _w_token(f, "<DiagGMM>")
+    _w_token(f, "<GCONSTS>")
+    write_vector(f, gconsts)
+    _w_token(f, "<WEIGHTS>")
+    write_vector(f, weights)
+    _w_token(f, "<MEANS_INVVARS>")
+    write_matrix(f, means_invvars)
+    _w_token(f, "<INV_VARS>")
+    write_matrix(f, inv_vars)
+    _w_token(f, "</DiagGMM>")
 
 
 def read_model(data: bytes) -> Tuple[RawTransitionModel, RawAmDiagGmm]:
@@ -403,16 +435,7 @@ def write_model(f: BinaryIO, tm: RawTransitionModel, am: RawAmDiagGmm) -> None:
     _w_token(f, "<NUMPDFS>")
     _w_int32(f, am.num_pdfs)
     for i in range(am.num_pdfs):
-        _w_token(f, "<DiagGMM>")
-        _w_token(f, "<GCONSTS>")
-        write_vector(f, am.gconsts[i])
-        _w_token(f, "<WEIGHTS>")
-        write_vector(f, am.weights[i])
-        _w_token(f, "<MEANS_INVVARS>")
-        write_matrix(f, am.means_invvars[i])
-        _w_token(f, "<INV_VARS>")
-        write_matrix(f, am.inv_vars[i])
-        _w_token(f, "</DiagGMM>")
+        write_diag_gmm(f, am.gconsts[i], am.weights[i], am.means_invvars[i], am.inv_vars[i])
 
 
 def read_matrix_file(data: bytes) -> np.ndarray:
@@ -617,7 +640,7 @@ def write_fst(f: BinaryIO, fst: Fst) -> None:
 
 # --------------------------------------------------------------------------- ark / scp tables
 def read_ark(data: bytes, kind: str) -> Iterator[Tuple[str, object]]:
-    """Iterate a binary ark held in memory.  kind: 'matrix' | 'vector' | 'int_vector' | 'fst'."""
+    """Iterate a binary ark held in memory.  kind: 'matrix' | 'vector' | 'int_vector' | 'int_vector_vector' | 'fst'."""
     r = BinaryReader(data)
     n = len(data)
     while r.p < n:
@@ -634,6 +657,8 @@ def read_ark(data: bytes, kind: str) -> Iterator[Tuple[str, object]]:
             yield key, r.vector()
         elif kind == "int_vector":
             yield key, r.int_vector()
+        elif kind == "int_vector_vector":
+            yield key, read_int_vector_vector(r)
         else:
             raise ValueError(kind)
 
@@ -654,6 +679,8 @@ def write_ark_entry(f: BinaryIO, key: str, obj, kind: str) -> int:
         write_vector(f, obj)
     elif kind == "int_vector":
         write_int_vector(f, obj)
+    elif kind == "int_vector_vector":
+        write_int_vector_vector(f, obj)
     else:
         raise ValueError(kind)
     return off
@@ -693,7 +720,8 @@ def read_scp_object(ark_cache: Dict[str, bytes], path: str, offset: int, kind: s
     if kind == "fst":
         return read_fst(r)
     r.expect_binary_header()
-    return {"matrix": r.matrix, "vector": r.vector, "int_vector": r.int_vector}[kind]()
+    return {"matrix": r.matrix, "vector": r.vector, "int_vector": r.int_vector,
+            "int_vector_vector": lambda: read_int_vector_vector(r)}[kind]()
 
 
 def load_acoustic_model_archive(path) -> Dict[str, bytes]:

@@ -1297,3 +1297,178 @@ def write_gmm_model(path, transition_model, acoustic_model) -> None:
 HierarchicalCtm = _ctm.HierarchicalCtm
 CtmInterval = _ctm.CtmInterval
 WordCtmInterval = _ctm.WordCtmInterval
+
+
+# ------------------------------------------------------------------------------------------------ diagonal UBM
+class MleDiagGmmOptions:
+    """``_kalpy.gmm.MleDiagGmmOptions``: Kaldi's defaults."""
+
+    def __init__(self, min_gaussian_weight: float = 1.0e-5, min_gaussian_occupancy: float = 10.0, min_variance: float = 0.001,
+                 remove_low_count_gaussians: bool = True):
+        self.min_gaussian_weight, self.min_gaussian_occupancy = min_gaussian_weight, min_gaussian_occupancy
+        self.min_variance, self.remove_low_count_gaussians = min_variance, remove_low_count_gaussians
+
+
+class AccumDiagGmm:
+    """``_kalpy.gmm.AccumDiagGmm`` as MFA/ivector/trainer.py:329-336 uses it: ``Resize(model, flags)``, ``Add(scale, other)``.
+    ``stats`` is the one-pdf ``GmmStats`` behind it."""
+
+    def __init__(self, stats=None):
+        self.stats = stats
+
+    def Resize(self, model: "DiagGmm", flags=None) -> None:
+        from .stats import GmmStats
+        self.stats = GmmStats.zeros(model.NumGauss(), model.Dim(), 1)
+
+    def Add(self, scale: float, other: "AccumDiagGmm") -> None:
+        if float(scale) != 1.0:
+            raise NotImplementedError("AccumDiagGmm.Add: only scale 1.0")
+        self.stats += other.stats
+
+
+class DiagGmm:
+    """kalpy's ``DiagGmm`` as the reference's UBM stage calls it (MFA/ivector/trainer.py:292-305, :330-346,
+    MFA/ivector/multiprocessing.py:110-124): ``DiagGmm(num_gauss, dim)``, ``init_from_random_frames(feats)``,
+    ``train_one_iter(feats, options, iteration, num_threads)``, ``Split(n, perturb_factor)``, ``NumGauss()``,
+    ``gaussian_selection(feats, n)``, ``mle_update(accs, remove_low_count_gaussians=)``.  ``ubm`` is the ``ubm.DiagUbm``
+    behind it; the E-steps run on the process's engine."""
+
+    def __init__(self, num_gauss: int = 0, dim: int = 0, ubm=None, seed: int = 0):
+        self.ubm = ubm
+        self._num_gauss, self._dim = int(num_gauss), int(dim)
+        self._rng = np.random.default_rng(seed)
+
+    @classmethod
+    def read(cls, path) -> "DiagGmm":
+        from .ubm import DiagUbm
+        return cls(ubm=DiagUbm.read(path))
+
+    def write(self, path) -> None:
+        self.ubm.write(path)
+
+    def NumGauss(self) -> int:
+        return self.ubm.num_gauss if self.ubm is not None else self._num_gauss
+
+    def Dim(self) -> int:
+        return self.ubm.dim if self.ubm is not None else self._dim
+
+    def init_from_random_frames(self, feats) -> None:
+        from . import ubm as _ubm
+        self.ubm = _ubm.init_from_random_frames(np.asarray(feats), self._num_gauss, self._rng)
+
+    def _device(self, feats):
+        import torch
+        eng = get_engine()
+        return eng, torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(eng.device)
+
+    def train_one_iter(self, feats, options: Optional[MleDiagGmmOptions] = None, iteration: int = 0, num_threads: int = 1) -> float:
+        """One dense EM iteration on ``feats`` (gmm-global-init-from-feats' TrainOneIter).  Returns the average log-likelihood
+        per frame under the model it started from."""
+        from . import ubm as _ubm
+        from .stats import ubm_statistics
+        o = options or MleDiagGmmOptions()
+        eng, x = self._device(feats)
+        st = ubm_statistics(eng, x, self.ubm)
+        self.ubm = _ubm.update(self.ubm, st, o.remove_low_count_gaussians, o.min_gaussian_weight,
+                               min_gaussian_occupancy=o.min_gaussian_occupancy, min_variance=o.min_variance)[0]
+        return st.loglike_per_frame
+
+    def Split(self, target_components: int, perturb_factor: float = 0.1) -> None:
+        from . import ubm as _ubm
+        self.ubm = _ubm.split(self.ubm, int(target_components), perturb_factor, self._rng)
+
+    def gaussian_selection(self, feats, num_gselect: int):
+        """(per frame the list of its best Gaussians, best first; the frames' summed log-likelihood over them)."""
+        from .stats import gaussian_selection
+        eng, x = self._device(feats)
+        gs, ll = gaussian_selection(eng, x, self.ubm, int(num_gselect))
+        return gs.cpu().numpy().tolist(), float(ll.double().sum().item())
+
+    def mle_update(self, gmm_accs: AccumDiagGmm, remove_low_count_gaussians: bool = True, min_gaussian_weight: float = 1.0e-4):
+        from . import ubm as _ubm
+        self.ubm, updated, removed, floored = _ubm.update(self.ubm, gmm_accs.stats, remove_low_count_gaussians, min_gaussian_weight)
+        return updated, removed, floored
+
+
+class GselectArchive:
+    """``GselectArchive(path)``: iterable of (utt_id, list of per-frame lists) and ``archive[utt_id]`` over an
+    Int32VectorVector ark (Kaldi gmm-gselect's output).  ``GselectArchive.write(path, entries)`` writes one."""
+
+    def __init__(self, file_name):
+        self.file_name = Path(file_name)
+        self._table: Optional[Dict[str, List[np.ndarray]]] = None
+
+    @staticmethod
+    def write(file_name, entries) -> None:
+        kaldi_io.write_table(file_name, ((k, [np.asarray(row, dtype=np.int32) for row in v]) for k, v in entries), "int_vector_vector")
+
+    def _load(self) -> Dict[str, List[np.ndarray]]:
+        if self._table is None:
+            self._table = dict(kaldi_io.read_ark(self.file_name.read_bytes(), "int_vector_vector"))
+        return self._table
+
+    def __iter__(self):
+        return ((k, [r.tolist() for r in v]) for k, v in self._load().items())
+
+    def __getitem__(self, key: str):
+        return [r.tolist() for r in self._load()[key]]
+
+    def matrix(self, key: str) -> np.ndarray:
+        """The utterance's lists as int32 [frames, n]; lists shorter than the longest are padded with −1 (no Gaussian)."""
+        rows = self._load()[key]
+        n = max((r.shape[0] for r in rows), default=0)
+        out = np.full((len(rows), n), -1, dtype=np.int32)
+        for i, r in enumerate(rows):
+            out[i, : r.shape[0]] = r
+        return out
+
+    def __contains__(self, key) -> bool:
+        return key in self._load()
+
+    def close(self) -> None:
+        self._table = None
+
+
+class GlobalGmmStatsAccumulator:
+    """``GlobalGmmStatsAccumulator(model_path)``: ``accumulate_stats(feature_archive, gselect_archive, callback=None)`` over
+    (key, matrix) features and a ``GselectArchive``, then ``gmm_accs`` (MFA/ivector/multiprocessing.py:271-280; Kaldi
+    gmm-global-acc-stats --gselect).  Utterances are batched onto the device (``stats.ubm_statistics``); one without a
+    selection, or whose selection has another number of frames, is skipped with a warning."""
+
+    def __init__(self, model_path, batch_frames: int = 500_000):
+        self.model_path = model_path
+        self.model = DiagGmm.read(model_path)
+        self.gmm_accs = AccumDiagGmm()
+        self.gmm_accs.Resize(self.model)
+        self.batch_frames = int(batch_frames)
+
+    def accumulate_stats(self, feature_archive, gselect_archive: GselectArchive, callback=None) -> None:
+        import torch
+        from .stats import ubm_statistics
+
+        eng = get_engine()
+        rows, sels, total = [], [], 0
+
+        def flush():
+            nonlocal rows, sels, total
+            if rows:
+                n = max(s.shape[1] for s in sels)
+                sel = np.concatenate([np.pad(s, ((0, 0), (0, n - s.shape[1])), constant_values=-1) for s in sels])
+                ubm_statistics(eng, torch.from_numpy(np.concatenate(rows).astype(np.float32)).to(eng.device), self.model.ubm,
+                               torch.from_numpy(sel).to(eng.device), into=self.gmm_accs.stats)
+            rows, sels, total = [], [], 0
+
+        for key, x in feature_archive:
+            if key not in gselect_archive:
+                logger.warning("No gselect information for utterance %s", key)
+                continue
+            g = gselect_archive.matrix(key)
+            if g.shape[0] != x.shape[0]:
+                logger.warning("utterance %s: gselect of %d frames for %d feature frames, skipped", key, g.shape[0], x.shape[0])
+                continue
+            rows.append(np.asarray(x)); sels.append(g); total += g.shape[0]
+            if callback:
+                callback(key)
+            if total >= self.batch_frames:
+                flush()
+        flush()

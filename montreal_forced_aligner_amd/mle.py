@@ -125,17 +125,19 @@ def split_targets(pdf_occ: Sequence[float], num_comp: Sequence[int], target_tota
 
 def mix_up(raw_am: kaldi_io.RawAmDiagGmm, pdf_occ: Sequence[float], target_total: int, power: float = 0.25,
            min_count: float = 20.0, perturb_factor: float = 0.01,
-           rng: Optional[np.random.Generator] = None) -> Tuple[kaldi_io.RawAmDiagGmm, np.ndarray]:
+           rng: Optional[np.random.Generator] = None,
+           max_per_pdf: Optional[int] = MAX_GAUSSIANS_PER_PDF) -> Tuple[kaldi_io.RawAmDiagGmm, np.ndarray]:
     """AmDiagGmm::SplitByCount: every pdf is split up to its ``split_targets`` count.  One split: the component of largest
     weight (the first on ties) gives half its weight to a copy appended to the pdf; with z ~ N(0, 1) per dimension from
     ``rng`` the copy's mean is μ + perturb_factor·√σ²·z and the original's μ − perturb_factor·√σ²·z; variances are copied
-    and the gconsts recomputed.  A target beyond 128 Gaussians in a pdf is refused (the statistics kernel's limit).
+    and the gconsts recomputed.  A target beyond ``max_per_pdf`` Gaussians in a pdf is refused: by default 128, the limit of
+    the statistics kernel over alignments; the diagonal UBM, one mixture of up to 2048 (``ubm.split``), passes its own.
     Returns (new model, Gaussians per pdf)."""
     rng = np.random.default_rng(0) if rng is None else rng
     targets = split_targets(pdf_occ, [w.shape[0] for w in raw_am.weights], target_total, power, min_count)
-    if len(targets) and int(targets.max()) > MAX_GAUSSIANS_PER_PDF:
+    if max_per_pdf is not None and len(targets) and int(targets.max()) > max_per_pdf:
         raise ValueError(f"mix_up: pdf {int(targets.argmax())} would get {int(targets.max())} Gaussians; the statistics "
-                         f"kernel takes at most {MAX_GAUSSIANS_PER_PDF} per pdf")
+                         f"kernel takes at most {max_per_pdf} per pdf")
     new = kaldi_io.RawAmDiagGmm(raw_am.dim, [], [], [], [])
     for p in range(raw_am.num_pdfs):
         w = raw_am.weights[p].astype(np.float32)

@@ -748,3 +748,124 @@ def tree_statistics_host(feats: np.ndarray, frame_off: np.ndarray, ali: np.ndarr
             break
         cap = n_events
     return TreeStats(key[:n_events], cnt[:n_events], s[:n_events], q[:n_events]), frame_event, skipped
+
+
+# ---- diagonal UBM: Gaussian selection and the global statistics over the selected Gaussians (include/mfa_hip.h "Diagonal UBM")
+def _ubm_device_model(engine, ubm):
+    """A ``ubm.DiagUbm`` as the device tensors (gconsts, means_invvars, inv_vars), uploaded once per model object and device."""
+    cache = ubm.__dict__.setdefault("_device_arrays", {})
+    key = str(engine.device)
+    if key not in cache:
+        cache.clear()
+        cache[key] = tuple(torch.from_numpy(a).to(engine.device) for a in ubm.arrays())
+    return cache[key]
+
+
+def _ubm_feats(feats, ubm, what):
+    if not isinstance(feats, torch.Tensor) or feats.dtype != torch.float32 or not feats.is_cuda or feats.dim() != 2:
+        raise _lib.MfaHipError(f"{what}: features must be a float32 matrix on the device")
+    if feats.shape[0] and feats.shape[1] != ubm.dim:
+        raise _lib.MfaHipError(f"{what}: features {tuple(feats.shape)} for a model of dim {ubm.dim}")
+    return feats.contiguous()
+
+
+def gaussian_selection(engine, feats: torch.Tensor, ubm, num_gselect: int):
+    """Every frame's ``min(num_gselect, G)`` best Gaussians of ``ubm`` (a ``ubm.DiagUbm``), best first, and its log-likelihood
+    over them (mfa_ubm_gselect_batch; Kaldi gmm-gselect).  ``feats`` float32 [T, dim] on the device.  Returns (gselect int32
+    [T, n], loglike float32 [T]) on the device."""
+    feats = _ubm_feats(feats, ubm, "gaussian_selection")
+    n = max(min(int(num_gselect), ubm.num_gauss), 0)
+    gselect = torch.empty((feats.shape[0], n), dtype=torch.int32, device=engine.device)
+    loglike = torch.empty(feats.shape[0], dtype=torch.float32, device=engine.device)
+    engine._launch_ubm_gselect(feats, _ubm_device_model(engine, ubm), int(num_gselect), gselect, loglike)
+    return gselect, loglike
+
+
+def ubm_statistics(engine, feats: torch.Tensor, ubm, gselect: Optional[torch.Tensor] = None,
+                   frame_weight: Optional[torch.Tensor] = None, into: Optional[GmmStats] = None, want_post: bool = False):
+    """Global GMM statistics of one batch (mfa_ubm_acc_batch; Kaldi gmm-global-acc-stats): posteriors over each frame's
+    ``gselect`` row (int32 [T, n] on the device), or over every Gaussian with ``gselect=None``.  ``frame_weight``: float32 [T]
+    on the device (default 1).  ``into``: one-pdf statistics to add to, and the object returned.  With ``want_post`` (needs a
+    ``gselect``) also returns the posteriors, float32 [T, n] on the device."""
+    feats = _ubm_feats(feats, ubm, "ubm_statistics")
+    dev, G, D, T = engine.device, ubm.num_gauss, ubm.dim, int(feats.shape[0])
+    st = into if into is not None else GmmStats.zeros(G, D, 1)
+    if st.mean_acc.shape != (G, D):
+        raise ValueError("ubm_statistics: `into` does not fit the model")
+    n = 0
+    if gselect is not None:
+        if gselect.dtype != torch.int32 or not gselect.is_cuda or gselect.dim() != 2 or gselect.shape[0] != T:
+            raise _lib.MfaHipError(f"ubm_statistics: the selection must be an int32 [frames, n] tensor on the device (got {tuple(gselect.shape)} {gselect.dtype})")
+        gselect, n = gselect.contiguous(), int(gselect.shape[1])
+    elif want_post:
+        raise _lib.MfaHipError("ubm_statistics: posteriors come in the order of a selection: want_post needs gselect")
+    if frame_weight is not None:
+        if frame_weight.dtype != torch.float32 or not frame_weight.is_cuda or tuple(frame_weight.shape) != (T,):
+            raise _lib.MfaHipError("ubm_statistics: frame weights must be a float32 vector on the device, one per frame")
+        frame_weight = frame_weight.contiguous()
+    occ = torch.from_numpy(np.ascontiguousarray(st.occ)).to(dev)
+    mean = torch.from_numpy(np.ascontiguousarray(st.mean_acc)).to(dev)
+    var = torch.from_numpy(np.ascontiguousarray(st.var_acc)).to(dev)
+    tot = torch.tensor([st.tot_like, st.tot_count], dtype=torch.float64, device=dev)
+    post = torch.empty((T, n), dtype=torch.float32, device=dev) if want_post else None
+    engine._launch_ubm_acc(feats, _ubm_device_model(engine, ubm), n, gselect, frame_weight, occ, mean, var, tot, post)
+    st.occ, st.mean_acc, st.var_acc = occ.cpu().numpy(), mean.cpu().numpy(), var.cpu().numpy()
+    t = tot.cpu().numpy()
+    st.tot_like, st.tot_count = float(t[0]), float(t[1])
+    return (st, post) if want_post else st
+
+
+_UBM_TWIN_CODES = {-2: "feature dimension above 48", -3: "Gaussians outside [1, 2048]", -4: "Gaussians per frame outside [1, 64]",
+                   -5: "2^31 frames or more"}
+
+
+def gaussian_selection_host(feats: np.ndarray, ubm, num_gselect: int):
+    """``gaussian_selection`` on the host twin (mfa_debug_ubm_gselect_host): numpy arrays in and out."""
+    feats = np.ascontiguousarray(feats, dtype=np.float32)
+    if feats.ndim != 2 or (feats.shape[0] and feats.shape[1] != ubm.dim):
+        raise _lib.MfaHipError(f"gaussian_selection_host: features {feats.shape} for a model of dim {ubm.dim}")
+    gc, mi, iv = ubm.arrays()
+    n = max(min(int(num_gselect), ubm.num_gauss), 0)
+    gselect = np.empty((feats.shape[0], n), dtype=np.int32)
+    loglike = np.empty(feats.shape[0], dtype=np.float32)
+    rc = _lib.lib().mfa_debug_ubm_gselect_host(feats.ctypes.data, int(feats.shape[0]), int(mi.shape[1]), int(gc.shape[0]), gc.ctypes.data,
+                                               mi.ctypes.data, iv.ctypes.data, int(num_gselect), gselect.ctypes.data, loglike.ctypes.data)
+    if rc != 0:
+        raise _lib.MfaHipError(f"mfa_debug_ubm_gselect_host: {_UBM_TWIN_CODES.get(rc, 'bad arguments')}")
+    return gselect, loglike
+
+
+def ubm_statistics_host(feats: np.ndarray, ubm, gselect: Optional[np.ndarray] = None, frame_weight: Optional[np.ndarray] = None,
+                        into: Optional[GmmStats] = None, want_post: bool = False):
+    """``ubm_statistics`` on the host twin (mfa_debug_ubm_acc_host: frames in ascending index, plain loops): the specification
+    the device is held to.  numpy arrays in; with ``want_post`` also returns the posteriors [T, n]."""
+    feats = np.ascontiguousarray(feats, dtype=np.float32)
+    if feats.ndim != 2 or (feats.shape[0] and feats.shape[1] != ubm.dim):
+        raise _lib.MfaHipError(f"ubm_statistics_host: features {feats.shape} for a model of dim {ubm.dim}")
+    G, D, T = ubm.num_gauss, ubm.dim, int(feats.shape[0])
+    st = into if into is not None else GmmStats.zeros(G, D, 1)
+    if st.mean_acc.shape != (G, D):
+        raise ValueError("ubm_statistics_host: `into` does not fit the model")
+    gc, mi, iv = ubm.arrays()
+    n = 0
+    if gselect is not None:
+        gselect = np.ascontiguousarray(gselect, dtype=np.int32)
+        if gselect.ndim != 2 or gselect.shape[0] != T:
+            raise _lib.MfaHipError(f"ubm_statistics_host: a selection of shape {gselect.shape} for {T} frames")
+        n = int(gselect.shape[1])
+    elif want_post:
+        raise _lib.MfaHipError("ubm_statistics_host: want_post needs gselect")
+    fw = None if frame_weight is None else np.ascontiguousarray(frame_weight, dtype=np.float32)
+    if fw is not None and fw.shape != (T,):
+        raise _lib.MfaHipError("ubm_statistics_host: one frame weight per frame")
+    occ, mean, var = (np.ascontiguousarray(a, dtype=np.float64) for a in (st.occ, st.mean_acc, st.var_acc))
+    tot = np.array([st.tot_like, st.tot_count], dtype=np.float64)
+    post = np.zeros((T, n), dtype=np.float32) if want_post else None
+    p = lambda a: None if a is None else a.ctypes.data
+    rc = _lib.lib().mfa_debug_ubm_acc_host(p(feats), T, int(mi.shape[1]), int(gc.shape[0]), p(gc), p(mi), p(iv), n, p(gselect), p(fw),
+                                           p(occ), p(mean), p(var), p(tot), p(post))
+    if rc != 0:
+        raise _lib.MfaHipError(f"mfa_debug_ubm_acc_host: {_UBM_TWIN_CODES.get(rc, 'bad arguments')}")
+    st.occ, st.mean_acc, st.var_acc = occ, mean, var
+    st.tot_like, st.tot_count = float(tot[0]), float(tot[1])
+    return (st, post) if want_post else st
