@@ -493,6 +493,20 @@ MFA_API int mfa_align_general_batch(mfa_ctx *ctx, const mfa_graph_batch *graphs,
                                     float *d_like, float *d_frame_like, int32_t *d_status);
 /* Bytes of device workspace mfa_align_batch will hold for a batch shape (so callers can budget HBM). */
 MFA_API size_t mfa_align_workspace_bytes(mfa_ctx *ctx, int32_t n_utt, int64_t total_frames, const mfa_align_opts *opts);
+/* Host query, no device work: the launches mfa_align_batch (lazy = 0) or mfa_align_features_batch (lazy = 1) makes for a
+ * batch whose largest graph has max_states states and max_arcs arcs, eps != 0 when a graph of the batch has epsilon input
+ * arcs — the same plan the decoder itself consumes (csrc/viterbi_plan.hpp).  One row of seven int32 per launch, in launch
+ * order, into h_out (room for `cap` rows; further rows are not written):
+ *   {pass (0 beam, 1 retry beam), code (0: every utterance; -2: those the first tier gave up; -1: those still pending),
+ *    N (live-token capacity), C (candidate capacity), dynamic LDS bytes, token lists in LDS (1) or in HBM (0),
+ *    log2 of the hashed state-to-slot table's size (0: one entry per graph state)}.
+ * N below the capacity asked for means that the tables did not fit in 160 KiB and the capacity was halved until they did:
+ * a token overflow (status 3) is then possible even with one token per graph state.  With lazy = 1 the first of two pass-0
+ * launches is the small first-tier kernel, whose LDS layout is its own; its row holds the general kernel's figures.
+ * Returns the number of launches, -1 if the decoder would refuse the batch (tables beyond 160 KiB at 64 tokens), -2 for
+ * bad arguments. */
+MFA_API int mfa_debug_viterbi_plan(const mfa_align_opts *opts, int32_t max_states, int32_t max_arcs, int32_t eps, int32_t lazy,
+                                   int32_t *h_out, int32_t cap);
 
 /* ---- Alignment from features, acoustic scores evaluated LAZILY: the same replacement as mfa_align_batch, but it takes the
  *      features GmmAligner.align_utterance(fst, feats) takes (MFA/alignment/multiprocessing.py:846-853;

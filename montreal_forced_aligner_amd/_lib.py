@@ -109,7 +109,7 @@ def build_native(force: bool = False, verbose: bool = False) -> Path:
     """Compile the HIP sources for gfx950 into libmfa_hip.so next to this file (hipcc cross-compiles without a GPU)."""
     src_dir = _PKG / "csrc"
     srcs = [src_dir / s for s in _SOURCES]
-    headers = ("ctx.hpp", "dev_buf.hpp", "gmm_common.hpp", "gmm_f32.hpp", "gmm_split.hpp", "gmm_pack.hpp", "viterbi_common.hpp", "viterbi_eps.hpp", "viterbi_wave.hpp", "viterbi_small.hpp",
+    headers = ("ctx.hpp", "dev_buf.hpp", "gmm_common.hpp", "gmm_f32.hpp", "gmm_split.hpp", "gmm_pack.hpp", "viterbi_common.hpp", "viterbi_eps.hpp", "viterbi_wave.hpp", "viterbi_small.hpp", "viterbi_plan.hpp",
                "resample_plan.hpp", "pitch_plan.hpp", "compress_math.hpp", "gmm_acc_math.hpp", "gmm_acc_twin.hpp", "acc_posterior.hpp", "acc_segments.hpp", "tid_lookup.hpp", "align_equal_math.hpp", "lda_acc_math.hpp", "mllt_acc_math.hpp", "tree_acc_math.hpp", "vad_math.hpp", "ubm_math.hpp")
     deps = srcs + [src_dir / h for h in headers] + [_PKG.parent / "include" / "mfa_hip.h"]
     if not force and _SO.exists() and all(_SO.stat().st_mtime >= d.stat().st_mtime for d in deps if d.exists()):
@@ -189,6 +189,7 @@ SIGNATURES = {
     "mfa_debug_gmm_pack": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _i32, _vp]),
     "mfa_debug_viterbi_stamps": (C.c_int, [_vp, _vp]),
+    "mfa_debug_viterbi_plan": (C.c_int, [C.POINTER(AlignOpts), _i32, _i32, _i32, _i32, _vp, _i32]),
     "mfa_gmm_score_batch": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mfa_align_batch": (C.c_int, [_vp, C.POINTER(GraphBatch), _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, C.POINTER(AlignOpts),
                                   _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -242,7 +243,7 @@ SIGNATURES = {
 
 
 # entry points that builds loaded through MFA_HIP_SO (older ones, for A/B timing) may lack
-_NEWER = {"mfa_mfcc_path", "mfa_gmm_acc_twofeats_batch", "mfa_debug_gmm_acc_twofeats_host"}
+_NEWER = {"mfa_mfcc_path", "mfa_gmm_acc_twofeats_batch", "mfa_debug_gmm_acc_twofeats_host", "mfa_debug_viterbi_plan"}
 
 
 def lib() -> C.CDLL:

@@ -20,8 +20,9 @@
 //
 // Sources, one translation unit: viterbi_common.hpp (constants, parameters, wavefront primitives, finalisation),
 // viterbi_eps.hpp (slot table and epsilon closures the two frame-loop kernels share), viterbi_wave.hpp (viterbi_kernel),
-// viterbi_small.hpp (viterbi_small_kernel, viterbi_finish_kernel); this file: helper kernels, workspace and launch
-// plan, align_impl, the C entry points.
+// viterbi_small.hpp (viterbi_small_kernel, viterbi_finish_kernel), viterbi_plan.hpp (the launch plan: host code without HIP,
+// also behind mfa_debug_viterbi_plan and swept by tests/native/viterbi_plan_check.cpp); this file: helper kernels,
+// workspace, align_impl, the C entry points.
 #include <cstdlib>
 #include <cstring>
 
@@ -31,6 +32,7 @@
 #include "viterbi_common.hpp"
 #include "viterbi_wave.hpp"
 #include "viterbi_small.hpp"
+#include "viterbi_plan.hpp"
 
 namespace {
 
@@ -68,23 +70,12 @@ __global__ void arcnext_kernel(mfa_graph_batch g, uint4 *out, u32 *epsinfo, int 
     }
 }
 
-constexpr int kLlCap = 512;
-// state→slot hash table: a power of two, at least four entries per live-token slot
-// — unless one entry per graph state is smaller (the large tiers of the rare passes): then 0 = direct map
-int hash_bits(int S, int N) {
-  int b = 8;
-  while ((1 << b) < 4 * N) b++;
-  return ((size_t)4 << b) <= (size_t)((S + 1) & ~1) * 4 ? b : 0;
-}
-// Dynamic-LDS bytes of a viterbi_kernel launch.  Kept by hand in step with the "LDS carve" at the top of viterbi_kernel
-// (viterbi_wave.hpp): an array added there needs its term here, or the kernel runs past its allocation.
-size_t lds_bytes(int S, int N, int C, bool lists_in_lds, bool eps = false) {
-  const int hb = hash_bits(S, N);
-  const size_t table = hb ? ((size_t)4 << hb) : (size_t)((S + 1) & ~1) * 4;
-  return (size_t)N * 8 + table + (size_t)N * 7 * 4 + (size_t)C * 4 + (size_t)kLlCap * 4 + 16 + (size_t)kBmWords * 4 +
-         (lists_in_lds ? (size_t)N * 32 : 0) + (eps ? (size_t)N * kEpsWordsPerSlot * 4 : 0);   // eps: EpsArrays
-}
-constexpr size_t kLdsLimit = 160 * 1024;
+// The launch plan (capacities, LDS bytes, where the token lists live, the state→slot table) is viterbi_plan.hpp's: host code
+// without HIP, which restates these constants of the kernels.
+constexpr int kLlCap = vplan::kLlCap;
+static_assert(vplan::kBmWords == kBmWords && vplan::kEpsWordsPerSlot == kEpsWordsPerSlot && vplan::kSmallN == kSmallN,
+              "viterbi_plan.hpp restates the kernels' constants");
+static_assert(vplan::kCodePending == ST_PENDING && vplan::kCodeGrow == ST_GROW, "viterbi_plan.hpp restates the status codes");
 
 struct WsLayout {
   size_t arcnext, state, cost, sta, stb, stkey, bp, tokoff, hash, list, count, vstate, band, eps, total;
@@ -110,22 +101,6 @@ WsLayout ws_layout(int n_utt, int64_t total_frames, int N, int C, int bpf, int64
   return w;
 }
 
-// N = live-token capacity, C = per-frame candidate capacity.  One token per state and one candidate per arc are hard
-// upper bounds, so the retry pass (whose beam keeps most of the graph alive) can always be given room that cannot overflow.
-int pick_caps(const mfa_align_opts *o, int max_states, int max_arcs, int pass, int *N, int *C) {
-  int n = o->max_tokens > 0 ? o->max_tokens : 1024;
-  if (pass == 1) n = n * 4;
-  if (n > max_states) n = max_states;
-  n = (n + 63) & ~63;
-  if (n < 64) n = 64;
-  int c = pass == 1 ? 8 * n : 4 * n;
-  if (c > max_arcs) c = max_arcs;
-  c = (c + 63) & ~63;
-  if (c < 256) c = 256;
-  *N = n; *C = c;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -133,6 +108,11 @@ extern "C" {
 MFA_API int mfa_debug_viterbi_stamps(mfa_ctx *c, void *d_stamps) {
   c->vit_stamps = d_stamps;
   return 0;
+}
+
+MFA_API int mfa_debug_viterbi_plan(const mfa_align_opts *o, int32_t max_states, int32_t max_arcs, int32_t eps, int32_t lazy,
+                                   int32_t *h_out, int32_t cap) {
+  return vplan::viterbi_plan_rows(o, max_states, max_arcs, eps != 0, lazy != 0, h_out, cap);
 }
 
 MFA_API size_t mfa_align_workspace_bytes(mfa_ctx *c, int32_t n_utt, int64_t total_frames, const mfa_align_opts *o) {
@@ -162,14 +142,19 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
   if (max_arcs >= (1 << 25)) return c->fail("graphs with more than 2^25 arcs are not supported");
   const int bpf = o->bp_tokens_per_frame > 0 ? o->bp_tokens_per_frame : 512;
   const int passes = o->retry_beam != 0.0f ? 2 : 1;
-  int N[2], C[2];
-  for (int ps = 0; ps < 2; ps++) pick_caps(o, max_states, max_arcs, ps, &N[ps], &C[ps]);
-  const int Nw = passes == 2 ? N[1] : N[0], Cw = passes == 2 ? C[1] : C[0];
   // graphs with epsilon input arcs: the decoder kernels' kEps instantiations, one {first epsilon arc, count} word per state
   // in the workspace
   const bool eps = g->d_state_nemit != nullptr;
   if (eps && max_arcs >= (1 << 24)) return c->fail("graphs with epsilon arcs and more than 2^24 arcs are not supported");
   const int64_t eps_states = eps ? (int64_t)n_utt * max_states : 0;
+  // the launch plan (viterbi_plan.hpp): capacities per pass, then per launch the LDS carve, where the token lists live, the
+  // state→slot table
+  vplan::Plan plan = vplan::viterbi_plan(o, max_states, max_arcs, eps, lazy != nullptr);
+  if (plan.refused >= 0) {
+    const vplan::Launch &L = plan.l[plan.refused];
+    return c->fail("Viterbi tables need %zu bytes of LDS (> 160 KiB): %d states, %d tokens", L.lds, max_states, L.N);
+  }
+  const int Nw = passes == 2 ? plan.N[1] : plan.N[0], Cw = passes == 2 ? plan.C[1] : plan.C[0];
   WsLayout w = ws_layout(n_utt, total_frames, Nw, Cw, bpf, total_arcs, eps_states);
   if (c->d_ws.reserve(c, w.total, "the decoder workspace")) return -1;
   unsigned char *base = c->d_ws.ptr<unsigned char>();
@@ -178,13 +163,9 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
   // Launch plan.  The decoder is latency-bound (one wavefront walks one utterance frame by frame), so throughput is the
   // number of wavefronts a CU can keep resident, and that is set by the LDS tables, which scale with the token capacity.
   // With the normal beam a frame rarely holds more than a few dozen tokens, so every utterance is first decoded with
-  // small tables (first_tier); the few that overflow them are marked ST_GROW and decoded again, from scratch and with
+  // small tables (the first tier); the few that overflow them are marked ST_GROW and decoded again, from scratch and with
   // the same beam, at the caller's full capacity.  Then the retry-beam pass for utterances that did not reach a final state.
   if (lazy && mfa_gmm_presplit(c, lazy, d_frame_off, n_utt, total_frames) != 0) return -1;
-  // First-tier capacity.  With the hashed state→slot table nothing in the decoder's LDS scales with the graph: 64 tokens
-  // need 9.5 KB → 16 wavefronts per CU (a whole batch of 4 096 resident at once on 256 CUs), 128 tokens 14.6 KB → 10.
-  // The lazy path's first tier is viterbi_small_kernel (kSmallN tokens), the dense path's the general kernel.
-  const int first_tier = lazy ? kSmallN : 128;
   // Speculative look-ahead of the windowed first tier.  The proven band lets a token advance one arc per frame, K − 1
   // arcs by the window's last frame; speech advances a third of that (synthetic 10 s utterances: 21 states per 64 frames on
   // average, 34 at the 99th percentile, 38 at most).  The window is scored for a look-ahead of K / 2 arcs instead (32 for
@@ -202,36 +183,18 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
   }
   int eps_pops_env = 0;                  // MFA_VIT_EPS_POPS (tests: forces the hand-over to the general decoder)
   { const char *e = getenv("MFA_VIT_EPS_POPS"); if (e && atoi(e) > 0) eps_pops_env = atoi(e); }
-  struct Launch { int pass, N, C, code, grow; };
-  std::vector<Launch> plan;
-  if (N[0] > first_tier) {
-    plan.push_back({0, first_tier, std::min(C[0], 4 * first_tier), 0, 1});
-    plan.push_back({0, N[0], C[0], ST_GROW, 0});
-  } else {
-    plan.push_back({0, N[0], C[0], 0, 0});
-  }
-  if (passes == 2) plan.push_back({1, N[1], C[1], ST_PENDING, 0});
-  for (Launch &L : plan) {
+  for (int li = 0; li < plan.n; li++) {
+    const vplan::Launch &L = plan.l[li];
     const int ps = L.pass;
     // the windowed first tier of the lazy path: viterbi_small_kernel, then viterbi_finish_kernel
     const bool small_tier = lazy && L.grow;
-    // token lists in LDS when everything fits comfortably; in HBM for big graphs / the wide retry beam; and if even the
-    // atomically updated tables do not fit, shrink the token capacity (an overflow is then reported per utterance)
-    // (the list passes — table growth, retry beam — hold a handful of utterances: occupancy does not matter there, the
-    //  per-frame latency of HBM-resident lists does)
-    bool lists_in_lds = lds_bytes(max_states, L.N, L.C, true, eps) <= kLdsLimit / 2 ||
-                        ((ps == 0 || L.code != 0) && lds_bytes(max_states, L.N, L.C, true, eps) <= kLdsLimit);
-    while (lds_bytes(max_states, L.N, L.C, lists_in_lds, eps) > kLdsLimit && L.N > 64) {
-      L.N = (L.N / 2 + 63) & ~63;
-      if (L.C > 8 * L.N) L.C = 8 * L.N;
-    }
-    size_t lds = lds_bytes(max_states, L.N, L.C, lists_in_lds, eps);
-    if (lds > kLdsLimit) return c->fail("Viterbi tables need %zu bytes of LDS (> 160 KiB): %d states, %d tokens", lds, max_states, L.N);
+    const bool lists_in_lds = L.lists_in_lds;
+    const size_t lds = L.lds;
     VitParams p;
     memset(&p, 0, sizeof(p));
     p.g = *g; p.ll = d_loglikes; p.ll_off = d_ll_off; p.ll_cols = d_ll_cols; p.frame_off = d_frame_off;
     p.beam = ps == 0 ? o->beam : o->retry_beam; p.scale = o->acoustic_scale;
-    p.nmax = L.N; p.cmax = L.C; p.bpf = bpf; p.pass = ps; p.grow = L.grow; p.hbits = hash_bits(max_states, L.N);
+    p.nmax = L.N; p.cmax = L.C; p.bpf = bpf; p.pass = ps; p.grow = L.grow; p.hbits = L.hbits;
     // workspace strides follow this launch's capacities (lists, parked lists and stash are per-launch scratch; the
     // largest launch's fits in `w`)
     WsLayout wp = ws_layout(n_utt, total_frames, L.N, L.C, bpf, total_arcs, eps_states);

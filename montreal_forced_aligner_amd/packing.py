@@ -70,7 +70,15 @@ class PackedGraphs:
     def hard_bounds(self) -> Tuple[int, int]:
         """(max_tokens, bp_tokens_per_frame) that the decoder's capacity statuses cannot occur with: one token per graph state
         — and, for graphs with epsilon arcs, room behind the back-pointer trail for the path the traceback writes there
-        (T + E arc indices, E ≤ T·S in the worst case: half a record per frame and state)."""
+        (T + E arc indices, E ≤ T·S in the worst case: half a record per frame and state).
+
+        The exception: the back-pointer bound always holds, the token bound only while the decoder's tables for one token
+        per state fit its 160 KiB of LDS.  Beyond that the launch plan (csrc/viterbi_plan.hpp) halves the token capacity
+        until they fit, and an utterance that keeps more tokens alive than that comes back with status 3 all the same.
+        For graphs of about 3.8 arcs a state this starts at 2 881 states, at 1 921 when the batch holds epsilon arcs
+        (tests/native/viterbi_plan_check.cpp measures it; ``mfa_debug_viterbi_plan`` answers for a given batch: N below
+        ``max_states`` rounded up to 64).  ``engine.redo_capacity`` therefore sends what still reports a capacity status
+        after this step to the general decoder, which has no such limit."""
         s = max(1, int(self.max_states))
         return s, s + (s // 2 + 2 if self.has_eps else 0)
 
