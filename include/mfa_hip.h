@@ -969,6 +969,98 @@ MFA_API int mfa_debug_ubm_acc_host(const float *h_feats, int64_t total_frames, i
                                    const float *h_frame_weight, double *h_occ, double *h_mean, double *h_var, double *h_tot,
                                    float *h_post);
 
+/* ---- I-vector extractor: replaces the per-job work of the reference's IvectorTrainer (MFA/ivector/trainer.py:390-632,
+ *      MFA/ivector/multiprocessing.py:143-231 and :283-331) and of ExtractIvectorsFunction (MFA/corpus/features.py:956-1015):
+ *      gauss-to-post's pruning, the utterance statistics and the E-step of Kaldi's ivector-extractor programs with
+ *      use_weights = false, restated here from the algorithm's description — Kaldi's source is not among this project's
+ *      references: parity unpinned, DESIGN §2.
+ * Notation: G Gaussians, feature dimension D, i-vector dimension R, P = R (R + 1) / 2.  A symmetric matrix is its packed
+ * lower triangle, row-major: element (r, c), c <= r, at r (r + 1) / 2 + c.  The model comes with the call as device arrays
+ * of double: W [G][D][R] (W_i = SigmaInv_i M_i), U [G][P] (U_i = M_i^T SigmaInv_i M_i) and the scalar prior_offset.  There is
+ * no context state.  All three calls are asynchronous on the ctx stream; no floating-point atomics anywhere: each result
+ * is a function of the input alone, and two calls on the same input give the same bits.
+ *
+ * Posterior pruning.  Arithmetic contract (csrc/ivector_math.hpp, ivector_prune_frame), per frame of n float32 entries in
+ * list order: an entry survives when it is >= min_post (a NaN never is); when none survives, the first of the largest
+ * entries does, if it is positive; the survivors are summed in list order, s; a survivor becomes p / s * scale (two
+ * roundings), every other entry 0.  A frame whose survivors do not sum to a positive number (all zeros: a frame that took no
+ * part in the statistics that wrote it) becomes all zeros.  d_out may be d_post (in place).  The host twin runs the same
+ * function: the bits are the device's by construction.  Limits: n outside [1, 64]; 2^31 frames or more; a NULL array.
+ * total_frames == 0 is no error.  Timing slot 29. */
+MFA_API int mfa_ivector_prune_post_batch(mfa_ctx *ctx, const float *d_post, int64_t total_frames, int32_t n, float min_post,
+                                         float scale, float *d_out);
+/* Host twin.  Returns 0, -1 for a NULL array or a negative count, -4 for n outside [1, 64], -5 for 2^31 frames or more. */
+MFA_API int mfa_debug_ivector_prune_post_host(const float *h_post, int64_t total_frames, int32_t n, float min_post, float scale,
+                                              float *h_out);
+
+/* Utterance statistics.  d_frame_off [n_utt + 1] (int64, ascending from 0 to total_frames) cuts d_feats [total_frames][dim]
+ * into utterances; d_gselect / d_post [total_frames][n] are a frame's Gaussians and their (pruned) posteriors: an index
+ * outside [0, G) is skipped, a list's indices are distinct (one that repeats an index is outside the contract: on the
+ * device one of the entries counts; nothing faults).  Arithmetic contract, in double, p the float posterior made double:
+ *   gamma[u][g] = sum over the utterance's frames of p;  X[u][g][k] = sum of p * x_k;
+ *   S[g][pk(j, k)] += sum over all frames of p * (x_j * x_k), the product of two floats formed in double (exact).
+ * A feature value that is not finite enters the sums as 0.  d_gamma [n_utt][G] and d_X [n_utt][G][dim] are overwritten for
+ * every utterance (one without frames gets zeros); d_S [G][dim (dim + 1) / 2] (may be NULL) is added to, never overwritten.
+ * max_count > 0 (extraction): an utterance whose sum of gamma over the Gaussians exceeds it has gamma and X multiplied by
+ * max_count / that sum; S is not scaled.  max_count <= 0: no scaling.
+ * Order on the device: an utterance's frames in order, 4 per step of the f64 matrix instruction, from zero (a Gaussian that
+ * a frame does not list adds an exact zero there).  S: the batch's frames cut into slabs of
+ * mfa_ivector_scatter_slab_frames() frames, each summed from zero in frame order, the slabs added in order onto the
+ * caller's value — frame order is utterance order; the slabs run in passes sized to the workspace (MFA_IVECTOR_PASS_SLABS
+ * overrides, for tests), and the slab order makes the result independent of the passes.  Two calls that split a batch at a
+ * multiple of the slab add to S what one call adds.  The sum of gamma for max_count: each of 256 threads its Gaussians
+ * g = t, t + 256, ... ascending, then a binary tree.
+ * mfa_debug_ivector_utt_stats_host is the same contract in plain loops, frames ascending, a frame's entries in list order,
+ * separate multiply and add: only the order and the rounding of the double sums may differ.
+ * Limits (refused with a message, the context stays usable): dim outside [1, 48]; G outside [1, 2048]; n outside [1, 64];
+ * 2^31 frames or more; a NULL array that would be read or written.  n_utt == 0 is no error.  Timing slots 30 (gamma, X and
+ * max_count) and 31 (S). */
+MFA_API int32_t mfa_ivector_scatter_slab_frames(void);
+MFA_API int mfa_ivector_utt_stats_batch(mfa_ctx *ctx, const float *d_feats, const int64_t *d_frame_off, int32_t n_utt,
+                                        int64_t total_frames, int32_t dim, int32_t G, int32_t n, const int32_t *d_gselect,
+                                        const float *d_post, double max_count, double *d_gamma, double *d_X, double *d_S);
+/* Host twin; total_frames is h_frame_off[n_utt].  Returns 0, -1 for a NULL array, a negative count or offsets that do not
+ * ascend from 0, -2 dim, -3 G, -4 n, -5 2^31 frames or more. */
+MFA_API int mfa_debug_ivector_utt_stats_host(const float *h_feats, const int64_t *h_frame_off, int32_t n_utt, int32_t dim, int32_t G,
+                                             int32_t n, const int32_t *h_gselect, const float *h_post, double max_count,
+                                             double *h_gamma, double *h_X, double *h_S);
+
+/* E-step.  Arithmetic contract, in double, per utterance u (gamma [n_utt][G], X [n_utt][G][dim] as the statistics write them):
+ *   Q = I + sum_g gamma[g] U_g and lin = prior_offset e0 + sum_(g, k) X[g][k] W_g[k][.]: the prior term first, then g (and
+ *   k within g) ascending;  Q = L L^T by Cholesky;  Var = Q^-1 = L^-T L^-1;  mu = L^-T (L^-1 lin);  Sc = Var + mu mu^T.
+ * d_ivec_mean [n_utt][R] receives mu; d_ivec_var [n_utt][P] (may be NULL) Var; d_aux [n_utt][2] (may be NULL) the two
+ * numbers of the objective that need the factorisation: lin . mu and log det Q.  The accumulators are all NULL (extraction)
+ * or all set, and are added to, never overwritten: over the utterances that take part, in utterance order,
+ *   Gamma[g] += gamma[g];  Y[g][k][r] += X[g][k] mu[r];  Rq[g][.] += gamma[g] Sc;  isum += mu;  iscat += Sc;  n[0] += 1.
+ * An utterance takes part when some gamma is not zero and every element of mu is finite.  A Q that is not positive definite
+ * cannot arise from gamma >= 0 and a valid U; a non-finite input gives NaN in that utterance's mu, Var and aux only, the
+ * utterance takes no part, and nothing faults (no index depends on a value).
+ * Order on the device: the utterances run in chunks sized to the context's workspace ([chunk][P] doubles;
+ * MFA_IVECTOR_PASS_UTTS=<utterances> overrides, for tests), a chunk being a multiple of 4 utterances, the K of the f64 matrix
+ * instruction (an override is rounded up to one).  Per chunk: Q and lin as products [chunk x G][G x P] and
+ * [chunk x G dim][G dim x R] on the matrix instruction, k ascending, 4 per step; one workgroup per utterance holds the packed
+ * triangle in LDS and runs the twin's operations (left-looking Cholesky, L^-1 in place by columns from the last, every
+ * element's sum over k ascending in one thread); Rq and Y as products over the chunk's utterances whose accumulator starts
+ * from the caller's value, 4 utterances per step; Gamma, isum, iscat and n one thread per element, utterances in order.
+ * Chunks follow one another in utterance order and begin at multiples of 4, so every step holds the same four utterances
+ * whatever the chunk size: the result does not depend on the chunking.
+ * mfa_debug_ivector_estep_host is the same contract in plain loops, utterances ascending: only the order and rounding of
+ * the products' sums (and log) may differ; given the same Q and lin, the factorisation's operations are the same.
+ * Limits (refused with a message, the context stays usable): dim outside [1, 48]; G outside [1, 2048]; R outside [1, 192]
+ * (the packed triangle, 148 224 B at 192, lives in one workgroup's LDS); some but not all accumulators; a NULL array that
+ * would be read or written; 2^31 utterances or more.  n_utt == 0 is no error.  Timing slots 32 (Q, lin), 33 (the solve),
+ * 34 (the accumulators). */
+MFA_API int mfa_ivector_estep_batch(mfa_ctx *ctx, const double *d_gamma, const double *d_X, int32_t n_utt, int32_t dim, int32_t G,
+                                    int32_t R, const double *d_W, const double *d_U, double prior_offset, double *d_ivec_mean,
+                                    double *d_ivec_var, double *d_aux, double *d_Gamma, double *d_Y, double *d_Rq, double *d_isum,
+                                    double *d_iscat, double *d_n);
+/* Host twin.  Returns 0, -1 for a NULL array, a negative count or some but not all accumulators, -2 dim, -3 G, -5 2^31
+ * utterances or more, -6 R outside [1, 192]. */
+MFA_API int mfa_debug_ivector_estep_host(const double *h_gamma, const double *h_X, int32_t n_utt, int32_t dim, int32_t G, int32_t R,
+                                         const double *h_W, const double *h_U, double prior_offset, double *h_ivec_mean,
+                                         double *h_ivec_var, double *h_aux, double *h_Gamma, double *h_Y, double *h_Rq,
+                                         double *h_isum, double *h_iscat, double *h_n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,8 @@ KERNEL_SLOTS = ("mfcc", "cmvn", "feats", "gmm", "viterbi", "resample", "pitch", 
                 "lda_lookup", "lda_second", "lda_class", "lda_reduce",
                 "mllt_lookup", "mllt_sort", "mllt_sums", "mllt_reduce",
                 "tree_keys", "tree_order", "tree_sums", "vad",
-                "ubm_select", "ubm_post", "ubm_sums", "ubm_reduce")
+                "ubm_select", "ubm_post", "ubm_sums", "ubm_reduce",
+                "ivec_prune", "ivec_utt", "ivec_scatter", "ivec_products", "ivec_solve", "ivec_acc")
 
 
 def _out_ptrs(out: Dict[str, Optional[torch.Tensor]]):
@@ -267,6 +268,24 @@ class AlignmentEngine(GraphPacking, FrontEndStages):
         check(self.ctx, self.lib.mfa_ubm_acc_batch(self.ctx, _ptr(feats), int(feats.shape[0]), int(mi.shape[1]), int(gc.shape[0]),
                                                    _ptr(gc), _ptr(mi), _ptr(iv), n, _ptr(gselect), _ptr(frame_weight), _ptr(occ),
                                                    _ptr(mean), _ptr(var), _ptr(tot), _ptr(post)), "mfa_ubm_acc_batch")
+
+    def _launch_ivector_prune(self, post, min_post: float, scale: float, out) -> None:
+        check(self.ctx, self.lib.mfa_ivector_prune_post_batch(self.ctx, _ptr(post), int(post.shape[0]), int(post.shape[1]), float(min_post),
+                                                              float(scale), _ptr(out)), "mfa_ivector_prune_post_batch")
+
+    def _launch_ivector_utt_stats(self, feats, d_frame_off, n_utt: int, G: int, gselect, post, max_count: float, gamma, X, S) -> None:
+        check(self.ctx, self.lib.mfa_ivector_utt_stats_batch(self.ctx, _ptr(feats), _ptr(d_frame_off), n_utt, int(feats.shape[0]),
+                                                             int(feats.shape[1]), G, int(gselect.shape[1]), _ptr(gselect), _ptr(post),
+                                                             float(max_count), _ptr(gamma), _ptr(X), _ptr(S)),
+              "mfa_ivector_utt_stats_batch")
+
+    def _launch_ivector_estep(self, gamma, X, W, U, prior_offset: float, mean, var, aux, acc) -> None:
+        """``acc``: None (extraction) or the six accumulators (Γ, Y, Rq, isum, iscat, n)."""
+        a = acc if acc is not None else (None,) * 6
+        check(self.ctx, self.lib.mfa_ivector_estep_batch(self.ctx, _ptr(gamma), _ptr(X), int(gamma.shape[0]), int(W.shape[1]),
+                                                         int(W.shape[0]), int(W.shape[2]), _ptr(W), _ptr(U), float(prior_offset),
+                                                         _ptr(mean), _ptr(var), _ptr(aux), *(_ptr(t) for t in a)),
+              "mfa_ivector_estep_batch")
 
     def _launch_scan(self, values, d_frame_off, n_utt: int, total: int, scan, totals) -> None:
         check(self.ctx, self.lib.mfa_vad_scan_batch(self.ctx, _ptr(values), _ptr(d_frame_off), n_utt, total, _ptr(scan),

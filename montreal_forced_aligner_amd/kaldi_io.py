@@ -251,6 +251,66 @@ def write_int_vector_vector(f: BinaryIO, vv) -> None:
         write_int_vector(f, v)
 
 
+def write_double(f: BinaryIO, v: float) -> None:
+    """A double in Kaldi's basic-type form: the size marker 8, then the value (``BinaryReader.float32`` reads it back)."""
+    f.write(b"\x08" + struct.pack("<d", float(v)))
+
+
+def write_sp_matrix(f: BinaryIO, packed: np.ndarray, rows: int) -> None:
+    """A symmetric matrix as Kaldi's packed matrix is remembered (layout unpinned: Kaldi's source is not among this project's
+    references): token ``DP`` (double) or ``FP`` (float), the row count, then the lower triangle row by row — element (r, c),
+    c <= r, at r (r + 1) / 2 + c."""
+    p = np.ascontiguousarray(packed)
+    if p.ndim != 1 or p.shape[0] != rows * (rows + 1) // 2:
+        raise ValueError(f"a packed triangle of {p.shape} values for {rows} rows")
+    if p.dtype == np.float64:
+        _w_token(f, "DP")
+    else:
+        p = p.astype("<f4")
+        _w_token(f, "FP")
+    _w_int32(f, rows)
+    f.write(p.tobytes())
+
+
+def read_sp_matrix(r: "BinaryReader") -> np.ndarray:
+    """The packed lower triangle ``write_sp_matrix`` wrote, in its own precision."""
+    t = r.token()
+    if t not in ("FP", "DP"):
+        raise KaldiFormatError(f"expected FP/DP, got {t!r}")
+    rows = r.int32()
+    dt = "<f4" if t == "FP" else "<f8"
+    return np.frombuffer(r.read(rows * (rows + 1) // 2 * int(dt[2])), dtype=dt).copy()
+
+
+def pack_lower(m: np.ndarray) -> np.ndarray:
+    """[..., R, R] symmetric → [..., R (R + 1) / 2] packed lower triangle, row-major."""
+    r, c = np.tril_indices(m.shape[-1])
+    return np.ascontiguousarray(m[..., r, c])
+
+
+def unpack_lower(p: np.ndarray, rows: int) -> np.ndarray:
+    """The inverse of ``pack_lower``: the full symmetric matrix."""
+    r, c = np.tril_indices(rows)
+    m = np.zeros(p.shape[:-1] + (rows, rows), dtype=p.dtype)
+    m[..., r, c] = p
+    m[..., c, r] = p
+    return m
+
+
+def write_posterior(f: BinaryIO, post) -> None:
+    """Kaldi's Posterior (vector<vector<pair<int32, BaseFloat>>>) as it is remembered (unpinned): the frame count, then per
+    frame the pair count and the (index, float) pairs, every number behind its size marker."""
+    _w_int32(f, len(post))
+    for frame in post:
+        _w_int32(f, len(frame))
+        for idx, p in frame:
+            f.write(b"\x04" + struct.pack("<i", int(idx)) + b"\x04" + struct.pack("<f", float(p)))
+
+
+def read_posterior(r: "BinaryReader") -> List[List[Tuple[int, float]]]:
+    return [[(r.int32(), r.float32()) for _ in range(r.int32())] for _ in range(r.int32())]
+
+
 # --------------------------------------------------------------------------- model objects
 @dataclass
 class HmmState:
@@ -659,6 +719,8 @@ def read_ark(data: bytes, kind: str) -> Iterator[Tuple[str, object]]:
             yield key, r.int_vector()
         elif kind == "int_vector_vector":
             yield key, read_int_vector_vector(r)
+        elif kind == "posterior":
+            yield key, read_posterior(r)
         else:
             raise ValueError(kind)
 
@@ -681,6 +743,8 @@ def write_ark_entry(f: BinaryIO, key: str, obj, kind: str) -> int:
         write_int_vector(f, obj)
     elif kind == "int_vector_vector":
         write_int_vector_vector(f, obj)
+    elif kind == "posterior":
+        write_posterior(f, obj)
     else:
         raise ValueError(kind)
     return off

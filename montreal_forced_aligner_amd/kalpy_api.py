@@ -1472,3 +1472,182 @@ class GlobalGmmStatsAccumulator:
             if total >= self.batch_frames:
                 flush()
         flush()
+
+
+# ---- i-vector extractor ------------------------------------------------------------------------------------------------------
+def _generate_post(self, feats, num_post: int = 20, min_post: float = 0.025):
+    """kalpy's ``DiagGmm.generate_post``: per frame the (Gaussian, posterior) pairs of its ``num_post`` best Gaussians after
+    gauss-to-post's pruning at ``min_post`` (scale 1), in the selection's order (MFA/ivector/multiprocessing.py:166-173)."""
+    from .stats import gaussian_selection, prune_posteriors, ubm_statistics
+    eng, x = self._device(feats)
+    gs, _ll = gaussian_selection(eng, x, self.ubm, int(num_post))
+    _st, post = ubm_statistics(eng, x, self.ubm, gs, want_post=True)
+    post = prune_posteriors(eng, post, float(min_post), 1.0, inplace=True)
+    g, p = gs.cpu().numpy(), post.cpu().numpy()
+    return [[(int(i), float(v)) for i, v in zip(gr, pr) if v != 0.0] for gr, pr in zip(g, p)]
+
+
+DiagGmm.generate_post = _generate_post
+
+
+def ScalePosterior(scale: float, post):
+    """Kaldi's ScalePosterior: every posterior multiplied by ``scale`` in float32 (a new list; a scale of 0 empties the frames)."""
+    s = np.float32(scale)
+    if s == 0:
+        return [[] for _ in post]
+    return [[(int(i), float(np.float32(p) * s)) for i, p in frame] for frame in post]
+
+
+def posterior_matrices(post, n: Optional[int] = None):
+    """A Posterior as the device takes it: int32 indices and float32 posteriors [frames, n], short frames padded with (−1, 0)."""
+    n = max((len(f) for f in post), default=0) if n is None else n
+    n = max(n, 1)
+    g = np.full((len(post), n), -1, dtype=np.int32)
+    p = np.zeros((len(post), n), dtype=np.float32)
+    for t, frame in enumerate(post):
+        for j, (i, v) in enumerate(frame):
+            g[t, j], p[t, j] = i, v
+    return g, p
+
+
+class PosteriorArchive:
+    """``PosteriorArchive(path)``: (utt_id, Posterior) pairs and ``archive[utt_id]`` over a Posterior ark (``kaldi_io``'s
+    "posterior" kind).  ``PosteriorArchive.write(path, entries)`` writes one."""
+
+    def __init__(self, file_name):
+        self.file_name = Path(file_name)
+        self._table = None
+
+    @staticmethod
+    def write(file_name, entries) -> None:
+        kaldi_io.write_table(file_name, entries, "posterior")
+
+    def _load(self):
+        if self._table is None:
+            self._table = dict(kaldi_io.read_ark(self.file_name.read_bytes(), "posterior"))
+        return self._table
+
+    def __iter__(self):
+        return iter(self._load().items())
+
+    def __getitem__(self, key: str):
+        return self._load()[key]
+
+    def __contains__(self, key) -> bool:
+        return key in self._load()
+
+
+class IvectorExtractorStatsAccumulator:
+    """``IvectorExtractorStatsAccumulator(ie_path)``: ``accumulate_stats(feature_archive, post_reader, callback=None)`` over
+    (key, matrix) features and a mapping from key to Posterior (a ``PosteriorArchive`` or a dict), then ``ivector_stats``
+    (MFA/ivector/multiprocessing.py:283-331; Kaldi ivector-extractor-acc-stats).  Utterances are batched onto the device
+    (``stats.ivector_utterance_statistics``, ``stats.ivector_estep``); one without posteriors, or whose posteriors have another
+    number of frames, is skipped with a warning."""
+
+    def __init__(self, ie_path, batch_frames: int = 500_000):
+        from .ivector import IvectorExtractorModel, IvectorStats
+        self.ie_path = ie_path
+        self.model = IvectorExtractorModel.read(ie_path)
+        self.ivector_stats = IvectorStats.zeros(self.model.num_gauss, self.model.dim, self.model.ivector_dim)
+        self.batch_frames = int(batch_frames)
+
+    def accumulate_stats(self, feature_archive, post_reader, callback=None) -> None:
+        import torch
+        from .stats import ivector_estep, ivector_utterance_statistics
+
+        eng = get_engine()
+        rows, posts, total = [], [], 0
+
+        def flush():
+            nonlocal rows, posts, total
+            if rows:
+                n = max(max((len(f) for f in p), default=0) for p in posts)
+                mats = [posterior_matrices(p, n) for p in posts]
+                off = np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]).astype(np.int64)
+                dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(eng.device)
+                S = dev(self.ivector_stats.S)
+                gamma, X, S = ivector_utterance_statistics(eng, dev(np.concatenate(rows).astype(np.float32)), off,
+                                                           dev(np.concatenate([m[0] for m in mats])),
+                                                           dev(np.concatenate([m[1] for m in mats])), self.model.num_gauss, S=S)
+                ivector_estep(eng, self.model, gamma, X, into=self.ivector_stats)
+                self.ivector_stats.S = S.cpu().numpy()
+            rows, posts, total = [], [], 0
+
+        for key, x in feature_archive:
+            if key not in post_reader:
+                logger.warning("No posteriors for utterance %s", key)
+                continue
+            post = post_reader[key]
+            if len(post) != x.shape[0]:
+                logger.warning("utterance %s: posteriors of %d frames for %d feature frames, skipped", key, len(post), x.shape[0])
+                continue
+            rows.append(np.asarray(x)); posts.append(post); total += x.shape[0]
+            if callback:
+                callback(key)
+            if total >= self.batch_frames:
+                flush()
+        flush()
+
+
+class IvectorExtractor:
+    """``IvectorExtractor(dubm_path, ie_path, acoustic_weight=, max_count=, num_gselect=, min_post=)`` with
+    ``extract_ivector(feats)`` and ``export_ivectors(ark_path, feature_archive, write_scp=, callback=)``, as
+    ExtractIvectorsFunction drives kalpy's (MFA/corpus/features.py:956-1015; Kaldi ivector-extract): selection and softmax
+    under the UBM, pruning with scale ``acoustic_weight``, the utterance statistics with ``max_count``, the E-step without
+    accumulators.  The vector handed out is μ with ``prior_offset`` subtracted from element 0, float32; the ark is a
+    float-vector table."""
+
+    def __init__(self, dubm_path, ie_path, acoustic_weight: float = 1.0, max_count: float = 0.0, num_gselect: int = 20,
+                 min_post: float = 0.025, batch_frames: int = 500_000):
+        from .ivector import IvectorExtractorModel
+        from .ubm import DiagUbm
+        self.ubm = DiagUbm.read(dubm_path)
+        self.model = IvectorExtractorModel.read(ie_path)
+        if self.ubm.num_gauss != self.model.num_gauss or self.ubm.dim != self.model.dim:
+            raise ValueError("IvectorExtractor: the UBM and the extractor do not fit together")
+        self.acoustic_weight, self.max_count = float(acoustic_weight), float(max_count)
+        self.num_gselect, self.min_post, self.batch_frames = int(num_gselect), float(min_post), int(batch_frames)
+
+    def _extract(self, mats) -> np.ndarray:
+        """i-vectors [utterances, R] of the feature matrices ``mats`` as one device batch."""
+        import torch
+        from .stats import gaussian_selection, ivector_estep, ivector_utterance_statistics, prune_posteriors, ubm_statistics
+        eng = get_engine()
+        off = np.concatenate([[0], np.cumsum([m.shape[0] for m in mats])]).astype(np.int64)
+        x = torch.from_numpy(np.ascontiguousarray(np.concatenate(mats), dtype=np.float32)).to(eng.device)
+        gs, _ll = gaussian_selection(eng, x, self.ubm, self.num_gselect)
+        _st, post = ubm_statistics(eng, x, self.ubm, gs, want_post=True)
+        post = prune_posteriors(eng, post, self.min_post, self.acoustic_weight, inplace=True)
+        gamma, X, _ = ivector_utterance_statistics(eng, x, off, gs, post, self.ubm.num_gauss, max_count=self.max_count)
+        mean = ivector_estep(eng, self.model, gamma, X)[0].cpu().numpy()
+        mean[:, 0] -= self.model.prior_offset
+        return mean.astype(np.float32)
+
+    def extract_ivector(self, feats) -> np.ndarray:
+        feats = np.asarray(feats)
+        if feats.ndim != 2 or feats.shape[0] == 0:
+            raise ValueError("extract_ivector: an utterance without frames")
+        return self._extract([feats])[0]
+
+    def export_ivectors(self, file_name, feature_archive, write_scp: bool = False, callback=None) -> None:
+        entries, keys, mats, total = [], [], [], 0
+
+        def flush():
+            nonlocal keys, mats, total
+            if mats:
+                entries.extend(zip(keys, self._extract(mats)))
+            keys, mats, total = [], [], 0
+
+        for key, x in feature_archive:
+            x = np.asarray(x)
+            if x.shape[0] == 0:
+                logger.warning("utterance %s has no frames, skipped", key)
+                continue
+            keys.append(key); mats.append(x); total += x.shape[0]
+            if callback:
+                callback(key)
+            if total >= self.batch_frames:
+                flush()
+        flush()
+        file_name = Path(file_name)
+        kaldi_io.write_table(file_name, entries, "vector", file_name.with_suffix(".scp") if write_scp else None)

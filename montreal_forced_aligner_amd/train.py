@@ -1304,3 +1304,144 @@ class DubmTrainer:
             m.write(d / f"{i}.dubm"); out.append(d / f"{i}.dubm")
         self.ubm.write(d / "final.dubm")
         return out + [d / "final.dubm"]
+
+
+# ---- i-vector extractor ------------------------------------------------------------------------------------------------------
+class IvectorHostBackend(UbmHostBackend):
+    """The i-vector stage's calls on the host twins: selection, posteriors, pruning and the utterance statistics once
+    (``prepare``), then an E-step per iteration (``estep``) over the statistics it keeps.  The device backend below has the
+    same calls."""
+
+    def __init__(self, batch_frames: int = 500_000):
+        super().__init__(batch_frames)
+        self.utt_stats: List = []               # per batch (γ [U, G], X [U, G, D])
+        self.S = None                           # global second-order statistics [G, D (D + 1) / 2]
+
+    def _offsets(self, keys) -> np.ndarray:
+        return np.array([0] + [a + n for _key, a, n in keys], dtype=np.int64)
+
+    def _batch_stats(self, b, off, ubm, num_gselect, min_post, scale):
+        from .stats import (gaussian_selection_host, ivector_utterance_statistics_host, prune_posteriors_host, ubm_statistics_host)
+        gs, _ll = gaussian_selection_host(b, ubm, num_gselect)
+        _st, post = ubm_statistics_host(b, ubm, gs, want_post=True)
+        post = prune_posteriors_host(post, min_post, scale)
+        gamma, X, self.S = ivector_utterance_statistics_host(b, off, gs, post, ubm.num_gauss, S=self.S, want_S=True)
+        return gamma, X
+
+    def prepare(self, ubm, num_gselect: int, min_post: float, scale: float) -> None:
+        self.S, self.utt_stats = None, []
+        for b, keys in zip(self.batches, self.batch_keys):
+            self.utt_stats.append(self._batch_stats(b, self._offsets(keys), ubm, num_gselect, min_post, scale))
+
+    def _estep(self, model, gamma, X, st):
+        from .stats import ivector_estep_host
+        ivector_estep_host(model, gamma, X, into=st)
+
+    def estep(self, model):
+        from .ivector import IvectorStats
+        st = IvectorStats.zeros(model.num_gauss, model.dim, model.ivector_dim)
+        for gamma, X in self.utt_stats:
+            self._estep(model, gamma, X, st)
+        st.S = np.array(self.to_host(self.S), dtype=np.float64)
+        return st
+
+
+class IvectorDeviceBackend(IvectorHostBackend):
+    """The same calls on the device (mfa_ubm_gselect_batch, mfa_ubm_acc_batch's posteriors, mfa_ivector_*): features, selections,
+    posteriors and the utterance statistics are device tensors and stay there between the iterations."""
+
+    def __init__(self, device: int = 0, engine=None, batch_frames: int = 500_000):
+        super().__init__(batch_frames)
+        if engine is None:
+            from .engine import AlignmentEngine
+            engine = AlignmentEngine(device)
+        self.engine = engine
+
+    def _to_batch(self, mats):
+        import torch
+        return torch.from_numpy(super()._to_batch(mats)).to(self.engine.device)
+
+    def to_host(self, feats) -> np.ndarray:
+        return feats.cpu().numpy()
+
+    def _batch_stats(self, b, off, ubm, num_gselect, min_post, scale):
+        from .stats import gaussian_selection, ivector_utterance_statistics, prune_posteriors, ubm_statistics
+        gs, _ll = gaussian_selection(self.engine, b, ubm, num_gselect)
+        _st, post = ubm_statistics(self.engine, b, ubm, gs, want_post=True)
+        post = prune_posteriors(self.engine, post, min_post, scale, inplace=True)
+        gamma, X, self.S = ivector_utterance_statistics(self.engine, b, off, gs, post, ubm.num_gauss, S=self.S, want_S=True)
+        return gamma, X
+
+    def _estep(self, model, gamma, X, st):
+        from .stats import ivector_estep
+        ivector_estep(self.engine, model, gamma, X, into=st)
+
+
+class IvectorTrainer:
+    """The reference's ``IvectorTrainer`` (MFA/ivector/trainer.py:390-632; Kaldi train_ivector_extractor.sh) over the device
+    calls, ``use_weights = False``.
+
+      read        ``final.dubm`` (a path or a ``ubm.DiagUbm``); ``ivector.IvectorExtractorModel.from_diag_ubm`` with a seeded
+                  numpy generator; ``1.ie``
+      statistics  once: every frame's ``num_gselect`` best Gaussians, their softmax, gauss-to-post's pruning at ``min_post``
+                  with scale ``posterior_scale · subsample`` (multiprocessing.py:174), then γ and X per utterance and the
+                  global S — none depends on the extractor, so they stay resident
+      iterations  ``num_iterations`` rounds of E-step → ``ivector.update``; ``<i + 1>.ie``, at the end ``final.ie``
+
+    ``features``: (key, matrix) pairs, as ``DubmTrainer`` takes them.  ``objectives``: per iteration, ``ivector.objective`` of
+    the model the iteration started from.  ``on_statistics(iteration, model, statistics)``: tests compare backends here."""
+
+    def __init__(self, num_iterations: int = 10, subsample: int = 5, gaussian_min_count: float = 100, ivector_dimension: int = 192,
+                 num_gselect: int = 20, min_post: float = 0.025, posterior_scale: float = 1.0, seed: int = 0, backend=None,
+                 device: int = 0, engine=None, update_variances: bool = True):
+        self.num_iterations, self.subsample, self.gaussian_min_count = int(num_iterations), int(subsample), float(gaussian_min_count)
+        self.ivector_dimension, self.num_gselect, self.min_post = int(ivector_dimension), int(num_gselect), float(min_post)
+        self.posterior_scale, self.seed, self.update_variances = float(posterior_scale), int(seed), bool(update_variances)
+        self.backend = backend if backend is not None else IvectorDeviceBackend(device, engine)
+        self.model = None
+        self.models: List = []                   # the initial model and the one after every iteration
+        self.objectives: List[float] = []
+        self.update_counts: List[tuple] = []     # per iteration (Gaussians updated, skipped for their count, eigenvalues floored)
+        self.on_statistics = None
+
+    def feature_archive_options(self) -> Dict:
+        return dict(subsample_n=self.subsample, use_sliding_cmvn=True)
+
+    def initialize(self, features, dubm) -> None:
+        from . import ivector as _iv
+        from . import ubm as _ubm
+
+        ubm = dubm if isinstance(dubm, _ubm.DiagUbm) else _ubm.DiagUbm.read(dubm)
+        if self.backend.load(features) == 0:
+            raise ValueError("IvectorTrainer: no feature frames")
+        self.ubm = ubm
+        self.model = _iv.IvectorExtractorModel.from_diag_ubm(ubm, self.ivector_dimension, np.random.default_rng(self.seed))
+        self.models = [self.model]
+        self.backend.prepare(ubm, self.num_gselect, self.min_post, self.posterior_scale * self.subsample)
+
+    def train(self, features, dubm, directory=None) -> "IvectorTrainer":
+        from . import ivector as _iv
+
+        self.initialize(features, dubm)
+        self.objectives, self.update_counts = [], []
+        for i in range(1, self.num_iterations + 1):
+            st = self.backend.estep(self.model)
+            if self.on_statistics is not None:
+                self.on_statistics(i, self.model, st)
+            self.objectives.append(_iv.objective(self.model, st))
+            self.model, *counts = _iv.update(self.model, st, self.gaussian_min_count, self.update_variances)
+            self.update_counts.append(tuple(counts))
+            self.models.append(self.model)
+        if directory is not None:
+            self.write(directory)
+        return self
+
+    def write(self, directory) -> List[Path]:
+        """``1.ie`` … ``<num_iterations + 1>.ie`` and ``final.ie``."""
+        d = Path(directory)
+        d.mkdir(parents=True, exist_ok=True)
+        out = []
+        for i, m in enumerate(self.models, start=1):
+            m.write(d / f"{i}.ie"); out.append(d / f"{i}.ie")
+        self.model.write(d / "final.ie")
+        return out + [d / "final.ie"]
