@@ -50,7 +50,8 @@ MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
  * 5 resample, 6 pitch, 7 feature codec, 8-11 GMM statistics (lookup, ordering, sums, reduction), 12 equal alignment,
  * 13-16 LDA statistics (lookup, second moment, ordering + class sums, reductions), 17-20 MLLT statistics (lookup,
  * ordering, sums, reductions), 21-23 tree statistics (keys, ordering, sums), 24 speech activity (each entry point's launches),
- * 25-28 diagonal UBM (selection, posteriors, sums, reductions).
+ * 25-28 diagonal UBM (selection, posteriors, sums, reductions), 29-34 i-vector extractor (pruning, utterance statistics,
+ * scatter, products, solve, accumulators), 35-38 PLDA (transform, prepare, sweep, merge).
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -1060,6 +1061,89 @@ MFA_API int mfa_debug_ivector_estep_host(const double *h_gamma, const double *h_
                                          const double *h_W, const double *h_U, double prior_offset, double *h_ivec_mean,
                                          double *h_ivec_var, double *h_aux, double *h_Gamma, double *h_Y, double *h_Rq,
                                          double *h_isum, double *h_iscat, double *h_n);
+
+/* ---- PLDA: what consumes an i-vector in the reference — the transform of IvectorCorpusMixin.transform_ivectors and
+ *      collect_speaker_ivectors (MFA/corpus/ivector_corpus.py:316-452), and the pairwise log-likelihood ratios behind
+ *      PldaClassificationFunction, cluster_matrix and calculate_distance_threshold (MFA/diarization/multiprocessing.py), which
+ *      the reference asks of Kaldi's Plda one pair at a time.  Restated here from the algorithm's description — Kaldi's source
+ *      is not among this project's references: parity unpinned, DESIGN §2.
+ * The model comes with the call as device arrays of double: transform [D][D], offset [D] (= -transform mean) and psi [D].
+ * There is no context state.  No atomics anywhere: each result is a function of the input alone, and two calls on the same
+ * input give the same bits.
+ *
+ * Transform.  Arithmetic contract, per row x of d_x [n][D]: u = transform x + offset, the accumulator starting from offset
+ * and the products added k ascending, 4 per step of the f64 matrix instruction (D zero-padded to a multiple of 4: the
+ * padding's +0 products can turn a -0 result into +0, nothing else); then the row is multiplied by its factor:
+ *   norm 0: none;  norm 1 (simple): sqrt(D / sum_k u_k^2);  norm 2 (the model's): sqrt(D / sum_k u_k^2 / (psi_k + 1 / n_row)),
+ * n_row = d_num_examples[row] (int32; NULL: 1).  Order on the device: the sum is one wavefront's — lane l adds its elements
+ * k = l, l + 64, ... ascending, then the 64 sums meet in a butterfly (xor 32, 16, ... 1).  A row whose sum is 0 or not finite,
+ * or whose n_row is below 1, gets what the formula gives (NaN or infinities); nothing faults.  d_out [n][D] may not be d_x.
+ * mfa_debug_plda_transform_host is the same contract in plain loops, k ascending: only the order and rounding of the sums
+ * may differ.  Limits (refused with a message, the context stays usable): D outside [1, 1024]; norm outside [0, 2]; 2^31
+ * rows or more; a NULL array that would be read or written (d_psi only with norm 2).  n == 0 is no error.  Asynchronous on
+ * the ctx stream; timing slot 35. */
+MFA_API int mfa_plda_transform_batch(mfa_ctx *ctx, const double *d_x, int64_t n, int32_t D, const double *d_transform,
+                                     const double *d_offset, const double *d_psi, const int32_t *d_num_examples, int32_t norm,
+                                     double *d_out);
+/* Host twin.  Returns 0, -1 for a NULL array, a negative count or a norm outside [0, 2], -2 for D outside [1, 1024], -5 for
+ * 2^31 rows or more. */
+MFA_API int mfa_debug_plda_transform_host(const double *h_x, int64_t n, int32_t D, const double *h_transform, const double *h_offset,
+                                          const double *h_psi, const int32_t *h_num_examples, int32_t norm, double *h_out);
+
+/* Scoring.  d_test [n_test][D] and d_train [n_train][D] are vectors in the model's space (the transform's output);
+ * d_train_n [n_train] (int32; NULL: 1) the number of examples a train vector is the mean of.  Arithmetic contract, in double.
+ * Per train column j and element k (csrc/plda_math.hpp), with g = train[j][k], n = train_n[j]:
+ *   a = n psi_k / (n psi_k + 1);  v = 1 + psi_k / (n psi_k + 1);
+ *   A_jk = -1/2 (1 / v - 1 / (1 + psi_k)), computed as -1/2 psi_k a / (v (1 + psi_k));  B_jk = (a g) / v;
+ *   c_j = -1/2 (sum_k log v - sum_k log(1 + psi_k) + sum_k (a g)^2 / v), computed as 1/2 (sum_k log1p(psi_k a / v) -
+ *   sum_k (a g)^2 / v), each sum over k ascending (the computed forms take no difference of nearly equal numbers);
+ * and score[i][j] = c_j + sum_k p_ik^2 A_jk + sum_k p_ik B_jk, p = test: the log-likelihood ratio of "test i has train j's
+ * class" against "it has a class of its own", expanded so that the whole matrix is one product with K = 2 D.  Order on the
+ * device: the accumulator starts from c_j; k ascending, 4 per step of the f64 matrix instruction, D zero-padded to a multiple
+ * of 4; per step first the four products (p p) A — the square is formed first, a separate rounding — then the four p B.
+ * Three outputs, each optional (NULL: off), at least one required:
+ *   (a) d_scores [n_test][n_train]: every score, the diagonal included whatever exclude_diagonal says;
+ *   (b) d_best_idx [n_test] (int32) and d_best_score [n_test]: a row's best candidate; -1 and -inf when it has none;
+ *   (c) d_knn_idx / d_knn_score [n_test][k], 1 <= k <= 64: a row's k best candidates, best first, padded with -1 and -inf.
+ * A row's candidates are its columns whose score is finite (a NaN or an infinity is never selected), without column j == i
+ * when exclude_diagonal is not 0 (test and train are the same vectors).  The order is one strict order: the larger score
+ * first, at equal scores the lower index (+0 and -0 are equal).  (b) and (c) are taken from the very accumulator values that
+ * (a) stores: they are exactly the first 1 and k of that order over the matrix row, whatever the tiling.  A NaN in test row i
+ * stays in row i of the matrix, one in train column j in column j.
+ * On the device a wavefront keeps a row's list across its whole sweep of the columns; for few rows and many columns the
+ * columns are cut into passes (MFA_PLDA_PASS_COLS=<columns per pass> overrides, rounded up to a multiple of 64; for tests)
+ * whose lists are merged in pass order.  The order being strict, the result does not depend on the passes.
+ * mfa_debug_plda_score_host is the same contract in plain loops: A and B are the device's bits (basic operations only), c may
+ * differ by log1p; the sums run k ascending in the device's step structure, so only what the matrix instruction does inside a
+ * step may differ.  Given the same matrix the selections are the same.
+ * Limits (refused with a message, the context stays usable): D outside [1, 1024]; k outside [1, 64] when (c) is asked for;
+ * every output NULL, or an index output without its scores; a psi entry that is not positive and finite; a train_n below 1
+ * (these two are found on the device by the prepare step, which the call waits for; without train vectors there is no
+ * prepare step and psi is not looked at); 2^31 test or train vectors or more; a NULL array
+ * that would be read.  n_test == 0 is no error and writes nothing; n_train == 0 writes the empty lists.  Timing slots 36
+ * (prepare), 37 (sweep), 38 (merge). */
+MFA_API int mfa_plda_score_batch(mfa_ctx *ctx, const double *d_test, int64_t n_test, const double *d_train, int64_t n_train,
+                                 int32_t D, const int32_t *d_train_n, const double *d_psi, int32_t exclude_diagonal, int32_t k,
+                                 double *d_scores, int32_t *d_best_idx, double *d_best_score, int32_t *d_knn_idx,
+                                 double *d_knn_score);
+/* Host twin.  Returns 0, -1 for a NULL array, a negative count or an index output without its scores, -2 D, -3 k, -4 a psi
+ * entry that is not positive and finite, -5 2^31 vectors or more, -6 a train_n below 1, -7 every output NULL. */
+MFA_API int mfa_debug_plda_score_host(const double *h_test, int64_t n_test, const double *h_train, int64_t n_train, int32_t D,
+                                      const int32_t *h_train_n, const double *h_psi, int32_t exclude_diagonal, int32_t k,
+                                      double *h_scores, int32_t *h_best_idx, double *h_best_score, int32_t *h_knn_idx,
+                                      double *h_knn_score);
+/* The prepare step alone, on the host: h_A, h_B [n_train][D] and h_c [n_train].  Return codes as the scoring twin's. */
+MFA_API int mfa_debug_plda_prepare_host(const double *h_train, int64_t n_train, int32_t D, const int32_t *h_train_n, const double *h_psi,
+                                        double *h_A, double *h_B, double *h_c);
+/* The sweep alone over the caller's operands A, B [n_train][D] and c [n_train] (tests: operands chosen so that every product
+ * and sum is exact), on the device and on the host: the scoring contract from "score[i][j] =" on, the same limits. */
+MFA_API int mfa_debug_plda_sweep_batch(mfa_ctx *ctx, const double *d_test, int64_t n_test, int32_t D, const double *d_A,
+                                       const double *d_B, const double *d_c, int64_t n_train, int32_t exclude_diagonal, int32_t k,
+                                       double *d_scores, int32_t *d_best_idx, double *d_best_score, int32_t *d_knn_idx,
+                                       double *d_knn_score);
+MFA_API int mfa_debug_plda_sweep_host(const double *h_test, int64_t n_test, int32_t D, const double *h_A, const double *h_B,
+                                      const double *h_c, int64_t n_train, int32_t exclude_diagonal, int32_t k, double *h_scores,
+                                      int32_t *h_best_idx, double *h_best_score, int32_t *h_knn_idx, double *h_knn_score);
 
 #ifdef __cplusplus
 }

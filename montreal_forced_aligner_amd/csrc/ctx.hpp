@@ -22,7 +22,8 @@ enum { MFA_K_MFCC = 0, MFA_K_CMVN = 1, MFA_K_FEATS = 2, MFA_K_GMM = 3, MFA_K_VIT
        MFA_K_TREE_KEYS = 21, MFA_K_TREE_ORDER = 22, MFA_K_TREE_SUMS = 23,
        MFA_K_VAD = 24, MFA_K_UBM_SELECT = 25, MFA_K_UBM_POST = 26, MFA_K_UBM_SUMS = 27, MFA_K_UBM_REDUCE = 28,
        MFA_K_IVEC_PRUNE = 29, MFA_K_IVEC_UTT = 30, MFA_K_IVEC_SCATTER = 31, MFA_K_IVEC_PRODUCTS = 32, MFA_K_IVEC_SOLVE = 33, MFA_K_IVEC_ACC = 34,
-       MFA_K_COUNT = 35 };
+       MFA_K_PLDA_TRANSFORM = 35, MFA_K_PLDA_PREPARE = 36, MFA_K_PLDA_SWEEP = 37, MFA_K_PLDA_MERGE = 38,
+       MFA_K_COUNT = 39 };
 
 // The device operations of dev_buf.hpp as HIP calls.  Every device pointer a context owns is an MfaBuf: freed with the
 // context, grown with reserve(), tables replaced as a set with dev_upload_commit<MfaHipDev>().
@@ -127,7 +128,7 @@ struct mfa_ctx {
 
   // d_ws is one scratch buffer shared by the CMVN and feature (feats.hip), Viterbi (viterbi.hip), fMLLR statistics (fmllr.hip), GMM
   // statistics (gmm_acc.hip), feature codec (compress.hip), equal alignment (align_equal.hip), LDA statistics (lda_acc.hip),
-  // MLLT statistics (mllt_acc.hip), tree statistics (tree_acc.hip), speech-activity (vad.hip), diagonal-UBM (ubm.hip) and i-vector (ivector.hip) stages: each lays its own workspace over it for the length of one call, and the order of
+  // MLLT statistics (mllt_acc.hip), tree statistics (tree_acc.hip), speech-activity (vad.hip), diagonal-UBM (ubm.hip), i-vector (ivector.hip) and PLDA (plda.hip) stages: each lays its own workspace over it for the length of one call, and the order of
   // ctx->stream is all that keeps them apart.
   MfaBuf d_ws;
   MfaBuf d_gen_ws;             // workspace of the general-graph decoder (viterbi_general.hip)

@@ -13,8 +13,8 @@
 //            ivec_scatter_kernel, grid (slab of 2048 frames × block of 64 Gaussians × group of 64 packed columns): the same A
 //            tile, B the products x_j·x_k formed in double (exact); the slab's partial to the workspace.
 //            ivec_scatter_reduce_kernel: the caller's S, then the slabs' partials in slab order.
-//   E-step   per chunk of utterances: ivec_gemm_kernel twice (Q = I + γ·U, lin = prior + X·W), ivec_solve_kernel (a workgroup
-//            per utterance, the packed triangle in LDS: Cholesky, L⁻¹ in place, μ, Var, Sc), ivec_gemm_kernel twice more
+//   E-step   per chunk of utterances: f64_gemm_kernel (f64_gemm.hpp) twice (Q = I + γ·U, lin = prior + X·W), ivec_solve_kernel (a workgroup
+//            per utterance, the packed triangle in LDS: Cholesky, L⁻¹ in place, μ, Var, Sc), f64_gemm_kernel twice more
 //            (Rq += γᵀ·Sc, Y += Xᵀ·μ, the accumulator continued from the caller's value) and ivec_small_acc_kernel (Γ, isum,
 //            iscat, n: a thread per element, the chunk's utterances in order).
 // Every sum has a fixed order and no floating-point atomics: two calls on the same input give the same bits.
@@ -22,6 +22,7 @@
 
 #include "acc_segments.hpp"
 #include "ctx.hpp"
+#include "f64_gemm.hpp"
 #include "ivector_math.hpp"
 
 namespace {
@@ -34,7 +35,6 @@ constexpr int kSlab = 2048;                // frames per partial of the scatter 
 constexpr int kScatBlocks = 4;             // 16-wide column blocks of a scatter workgroup: 64 packed columns
 constexpr size_t kScatPassBytes = (size_t)96 << 20;
 constexpr size_t kEstepPassBytes = (size_t)192 << 20;
-constexpr int kGemmBlocks = 4;             // 16-wide column blocks a wavefront of the product kernel owns
 static_assert(kSlab % kTileF == 0 && kTileF % 4 == 0, "ivector tiling");
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
@@ -205,67 +205,6 @@ __global__ __launch_bounds__(256) void ivec_scatter_reduce_kernel(const double *
   S[e] = a;
 }
 
-// C [M][N] = init + A·B on the f64 matrix instruction, k ascending, 4 per step.  A(i, k) = A[i·sai + k·sak], B(k, j) =
-// B[k·N + j] (rows of N contiguous columns), C rows of N columns.  kInit 0: the accumulator starts from C's value (C is added
-// to); 1: from the packed identity (1 where column j is a diagonal element r (r + 3) / 2); 2: from `offset` in column 0.
-// kmask (may be NULL): a k whose kmask is 0 gives A = 0.  grid (column groups of 64, row groups of 64); a wavefront owns 16
-// rows and kGemmBlocks column blocks, operands straight from memory (they are served by the L2: the chunk is sized to it).
-struct GemmParams {
-  const double *A; int64_t sai, sak;
-  const double *B; double *C;
-  int M, N, K;
-  const int32_t *kmask;
-  double offset;
-};
-
-template <int kInit>
-__global__ __launch_bounds__(256) void ivec_gemm_kernel(GemmParams p) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lc = lane & 15, lk = lane >> 4;
-  const int row0 = blockIdx.y * 64 + wave * 16, col0 = blockIdx.x * (16 * kGemmBlocks);
-  if (row0 >= p.M) return;                             // the whole wavefront
-  double4_t acc[kGemmBlocks];
-#pragma unroll
-  for (int nb = 0; nb < kGemmBlocks; nb++) {
-    const int col = col0 + nb * 16 + lc;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int row = row0 + lk + 4 * r;
-      double v = 0.0;
-      if (kInit == 0) { if (row < p.M && col < p.N) v = p.C[(size_t)row * p.N + col]; }
-      else if (kInit == 1) {
-        int d = (int)((sqrt(8.0 * (double)col + 1.0) - 1.0) * 0.5);
-        while (d * (d + 3) / 2 < col) d++;
-        while (d > 0 && d * (d + 3) / 2 > col) d--;
-        v = d * (d + 3) / 2 == col ? 1.0 : 0.0;
-      } else v = col == 0 ? p.offset : 0.0;
-      acc[nb][r] = v;
-    }
-  }
-  const int arow = row0 + lc;
-  const bool arow_in = arow < p.M;
-  const double *Ar = p.A + (size_t)(arow_in ? arow : 0) * p.sai;
-  for (int k0 = 0; k0 < p.K; k0 += 4) {
-    const int k = k0 + lk;
-    const bool k_in = k < p.K && (!p.kmask || p.kmask[k] != 0);
-    const double a = arow_in && k_in ? Ar[(size_t)k * p.sak] : 0.0;
-#pragma unroll
-    for (int nb = 0; nb < kGemmBlocks; nb++) {
-      const int col = col0 + nb * 16 + lc;
-      const double b = k_in && col < p.N ? p.B[(size_t)k * p.N + col] : 0.0;
-      acc[nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[nb], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int nb = 0; nb < kGemmBlocks; nb++) {
-    const int col = col0 + nb * 16 + lc;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int row = row0 + lk + 4 * r;
-      if (row < p.M && col < p.N) p.C[(size_t)row * p.N + col] = acc[nb][r];
-    }
-  }
-}
-
 struct SolveParams {
   int R, G;
   const double *gamma;   // the chunk's [C][G]
@@ -401,12 +340,6 @@ size_t env_count(const char *name) {
   return v > 0 ? (size_t)v : 0;
 }
 
-template <int kInit>
-void launch_gemm(mfa_ctx *c, const GemmParams &g) {
-  hipLaunchKernelGGL(ivec_gemm_kernel<kInit>, dim3((unsigned)((g.N + 16 * kGemmBlocks - 1) / (16 * kGemmBlocks)), (unsigned)((g.M + 63) / 64)),
-                     dim3(256), 0, c->stream, g);
-}
-
 }  // namespace
 
 extern "C" {
@@ -504,10 +437,10 @@ MFA_API int mfa_ivector_estep_batch(mfa_ctx *c, const double *d_gamma, const dou
     const double *gam = d_gamma + u0 * G, *Xc = d_X + u0 * GD;
     {
       KernelTimer kt(c, MFA_K_IVEC_PRODUCTS);
-      launch_gemm<1>(c, GemmParams{gam, G, 1, d_U, Q, C, P, G, nullptr, 0.0});
-      launch_gemm<2>(c, GemmParams{Xc, GD, 1, d_W, lin, C, R, GD, nullptr, prior_offset});
+      launch_gemm<1>(c, GemmParams{gam, G, 1, d_U, P, 1, Q, C, P, G, nullptr, 0.0, nullptr});
+      launch_gemm<2>(c, GemmParams{Xc, GD, 1, d_W, R, 1, lin, C, R, GD, nullptr, prior_offset, nullptr});
       MFA_HIP_CHECK(c, hipGetLastError());
-      MFA_DEBUG_POINT(c, "ivec_gemm_kernel Q, lin: utts=[%zu, %zu) R=%d", u0, u0 + C, R);
+      MFA_DEBUG_POINT(c, "f64_gemm_kernel Q, lin: utts=[%zu, %zu) R=%d", u0, u0 + C, R);
     }
     {
       KernelTimer kt(c, MFA_K_IVEC_SOLVE);
@@ -520,8 +453,8 @@ MFA_API int mfa_ivector_estep_batch(mfa_ctx *c, const double *d_gamma, const dou
     }
     if (!acc) continue;
     KernelTimer kt(c, MFA_K_IVEC_ACC);
-    launch_gemm<0>(c, GemmParams{gam, 1, G, Q, d_Rq, G, P, C, live, 0.0});
-    launch_gemm<0>(c, GemmParams{Xc, 1, GD, lin, d_Y, GD, R, C, live, 0.0});
+    launch_gemm<0>(c, GemmParams{gam, 1, G, Q, P, 1, d_Rq, G, P, C, live, 0.0, nullptr});
+    launch_gemm<0>(c, GemmParams{Xc, 1, GD, lin, R, 1, d_Y, GD, R, C, live, 0.0, nullptr});
     hipLaunchKernelGGL(ivec_small_acc_kernel, dim3((unsigned)((G + R + P + 1 + 255) / 256)), dim3(256), 0, c->stream, gam, lin, Q, live, C, G, R,
                        P, d_Gamma, d_isum, d_iscat, d_n);
     MFA_HIP_CHECK(c, hipGetLastError());

@@ -1,0 +1,405 @@
+// The PLDA stage on gfx950: what consumes an i-vector in the reference (MFA/corpus/ivector_corpus.py:123-452 transform_ivectors
+// and collect_speaker_ivectors; MFA/diarization/multiprocessing.py PldaClassificationFunction, cluster_matrix,
+// calculate_distance_threshold): the transform into the model's space with its length normalisation, and the matrix of
+// log-likelihood ratios between test and train vectors with its row-wise consumers (best train vector, k nearest) fused into
+// the sweep.  Restated from the algorithm (Kaldi's source is not among this project's references): parity unpinned, DESIGN §2.
+// Arithmetic contract: include/mfa_hip.h "PLDA"; the shared arithmetic: plda_math.hpp; the host twins: plda_host.cpp.  The
+// model comes with every call as device arrays: no context state.
+//
+//   transform  f64_gemm_kernel<3> (f64_gemm.hpp: u = x·Tᵀ + offset on the f64 matrix instruction), plda_norm_kernel (a
+//              wavefront per row: the sum of the factor in a fixed order, the row scaled in place)
+//   prepare    plda_prepare_kernel, a thread per train column: A, B as [k][column] (the sweep's B operands, columns padded to
+//              64 and k to 4 with zeros) and c; plda_pack_kernel the same layout from the caller's A, B, c (the debug entry)
+//   sweep      plda_sweep_kernel, grid (blocks of 64 test rows × column passes): a wavefront owns 16 rows and walks its pass's
+//              columns 64 at a time.  score = c_j + Σ_k p²·A + Σ_k p·B, k ascending, 4 per step: the test operand is loaded
+//              once per step and squared in a register for the first of the step's two matrix instructions.  The tile goes
+//              to the score matrix straight from the accumulators, and through LDS to put a row's 64 columns on lanes: a
+//              row's best list stays in one register pair per lane across the whole sweep (lane j the j-th best)
+//   merge      plda_merge_kernel, a wavefront per row: the passes' lists in pass order into one, then the outputs
+// The lists have one strict order (plda_better): whatever the passes are, the merged list is the first k of that order.  No
+// atomics; every sum has a fixed order: two calls on the same input give the same bits.
+#include <algorithm>
+
+#include "acc_segments.hpp"
+#include "ctx.hpp"
+#include "f64_gemm.hpp"
+#include "plda_math.hpp"
+
+namespace {
+
+constexpr int kRowBlock = 64;              // test rows of a sweep workgroup: 16 per wavefront
+constexpr int kColStep = 64;               // columns of a step: 4 blocks of the instruction's 16, afterwards one per lane
+constexpr int kTileStride = 80;            // doubles per LDS tile row: 16 mod 32, so the four rows a store touches share no bank
+constexpr int kMinPassCols = 512;          // an automatic split leaves a pass at least this many columns
+#ifndef PLDA_STEPS_IN_FLIGHT
+#define PLDA_STEPS_IN_FLIGHT 2
+#endif
+constexpr int kStepsInFlight = PLDA_STEPS_IN_FLIGHT;   // steps of k whose operands a sweep wavefront loads ahead of their instructions
+constexpr int kGemmRows = 1 << 20;         // rows per launch of the transform's product (grid.y)
+
+typedef double double4_t __attribute__((ext_vector_type(4)));
+
+// A thread per padded column j: column j < Ns from the train vector, the padding zeros.  flags[0] |= a psi that is not
+// positive and finite, flags[1] |= a train_n below 1 (plain stores of the same value).
+__global__ __launch_bounds__(256) void plda_prepare_kernel(const double *train, const int32_t *train_n, const double *psi, int Ns, int D,
+                                                           int Dpad, int64_t Nspad, double *At, double *Bt, double *c, int32_t *flags) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= Nspad) return;
+  const bool in = j < Ns;
+  const int32_t n = in && train_n ? train_n[j] : 1;
+  if (n < 1) flags[1] = 1;
+  double s_logr = 0.0, s_quad = 0.0;
+  for (int k = 0; k < Dpad; k++) {
+    double a = 0.0, b = 0.0;
+    if (in && k < D) {
+      const double ps = psi[k];
+      if (!plda_psi_ok(ps)) flags[0] = 1;
+      const PldaTerm t = plda_column_term(train[(size_t)j * D + k], ps, (double)n);
+      a = t.A; b = t.B;
+      s_logr += t.logr; s_quad += t.quad;
+    }
+    At[(size_t)k * Nspad + j] = a;
+    Bt[(size_t)k * Nspad + j] = b;
+  }
+  c[j] = in ? plda_column_const(s_logr, s_quad) : 0.0;
+}
+
+__global__ __launch_bounds__(256) void plda_pack_kernel(const double *A, const double *B, const double *cin, int Ns, int D, int Dpad,
+                                                        int64_t Nspad, double *At, double *Bt, double *c) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= Nspad) return;
+  const bool in = j < Ns;
+  for (int k = 0; k < Dpad; k++) {
+    const bool kin = in && k < D;
+    At[(size_t)k * Nspad + j] = kin ? A[(size_t)j * D + k] : 0.0;
+    Bt[(size_t)k * Nspad + j] = kin ? B[(size_t)j * D + k] : 0.0;
+  }
+  c[j] = in ? cin[j] : 0.0;
+}
+
+// One candidate per lane (cand: it is one) into the row's sorted list (cs, ci): lane j the j-th best of plda_better's order,
+// (-inf, -1) an empty entry; the first keff lanes are the answer.  The candidates are tested against the keff-th best with
+// one ballot; those that pass are inserted one at a time, lowest lane first: the position is the number of better entries,
+// the entries from there on move up a lane.
+__device__ __forceinline__ void plda_insert(double &cs, int32_t &ci, double s, int32_t idx, bool cand, int keff, int lane) {
+  double ts = __shfl(cs, keff - 1);
+  int32_t ti = __shfl(ci, keff - 1);
+  uint64_t mask = __ballot(cand && plda_better(s, idx, ts, ti));
+  while (mask) {
+    const int l = __ffsll((long long)mask) - 1;
+    mask &= mask - 1;
+    const double ks = __shfl(s, l);
+    const int32_t ki = __shfl(idx, l);
+    if (plda_better(ks, ki, ts, ti)) {
+      const int pos = __popcll(__ballot(plda_better(cs, ci, ks, ki)));
+      const double us = __shfl_up(cs, 1);
+      const int32_t ui = __shfl_up(ci, 1);
+      cs = lane < pos ? cs : (lane == pos ? ks : us);
+      ci = lane < pos ? ci : (lane == pos ? ki : ui);
+      ts = __shfl(cs, keff - 1);
+      ti = __shfl(ci, keff - 1);
+    }
+  }
+}
+
+struct SweepParams {
+  const double *test; int Nt, Ns, D, Dpad; int64_t Nspad;
+  const double *At, *Bt, *c;       // [Dpad][Nspad], [Dpad][Nspad], [Nspad]
+  int64_t cols_per_pass;           // a multiple of kColStep
+  int keff;                        // entries of a row's list; 0: no lists
+  int exclude_diag;
+  double *scores;                  // [Nt][Ns] or NULL
+  double *part_s; int32_t *part_i; // [passes][Nt][keff]
+};
+
+// kSteps steps of 4 k onto the accumulators, in order: all their operands are loaded first, so that kSteps × 9 loads are in
+// flight before the first matrix instruction waits for one; the order of the instructions is that of single steps.
+template <int kSteps>
+__device__ __forceinline__ void sweep_steps(const SweepParams &p, const double *Ar, bool arow_in, int k, int64_t col, double4_t (&acc)[4]) {
+  double a[kSteps], bA[kSteps][4], bB[kSteps][4];
+#pragma unroll
+  for (int s = 0; s < kSteps; s++) {
+    const int ks = k + 4 * s;
+    a[s] = arow_in && ks < p.D ? Ar[ks] : 0.0;
+    const double *Ak = p.At + (size_t)ks * p.Nspad + col, *Bk = p.Bt + (size_t)ks * p.Nspad + col;
+#pragma unroll
+    for (int nb = 0; nb < 4; nb++) { bA[s][nb] = Ak[nb * 16]; bB[s][nb] = Bk[nb * 16]; }
+  }
+#pragma unroll
+  for (int s = 0; s < kSteps; s++) {
+    const double a2 = a[s] * a[s];
+#pragma unroll
+    for (int nb = 0; nb < 4; nb++) {
+      acc[nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, bA[s][nb], acc[nb], 0, 0, 0);
+      acc[nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], bB[s][nb], acc[nb], 0, 0, 0);
+    }
+  }
+}
+
+// grid (blocks of 64 rows, passes).  Lane l of a step gives A[i = l & 15][k = l >> 4] = the test row's p_k (squared for the
+// first instruction) and B[k][j = l & 15] = A_jk or B_jk of column j.  Register r of lane l is D[row = (l >> 4) + 4 r][col =
+// l & 15].  The accumulator starts from c_j.
+__global__ __launch_bounds__(256) void plda_sweep_kernel(SweepParams p) {
+  __shared__ double tile[4][16][kTileStride];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lc = lane & 15, lk = lane >> 4;
+  const int64_t row0 = (int64_t)blockIdx.x * kRowBlock + wave * 16;
+  const bool wave_has = row0 < p.Nt;
+  const int64_t c_begin = (int64_t)blockIdx.y * p.cols_per_pass, c_end = min(p.Nspad, c_begin + p.cols_per_pass);
+  double ls[16];
+  int32_t li[16];
+#pragma unroll
+  for (int rr = 0; rr < 16; rr++) { ls[rr] = -INFINITY; li[rr] = -1; }
+  const int64_t arow = row0 + lc;
+  const bool arow_in = arow < p.Nt;
+  const double *Ar = p.test + (size_t)(arow_in ? arow : 0) * p.D;
+  for (int64_t c0 = c_begin; c0 < c_end; c0 += kColStep) {
+    double4_t acc[4];
+    if (wave_has) {
+#pragma unroll
+      for (int nb = 0; nb < 4; nb++) {
+        const double cj = p.c[c0 + nb * 16 + lc];
+        acc[nb] = double4_t{cj, cj, cj, cj};
+      }
+      int k0 = 0;
+      for (; k0 + 4 * kStepsInFlight <= p.Dpad; k0 += 4 * kStepsInFlight)
+        sweep_steps<kStepsInFlight>(p, Ar, arow_in, k0 + lk, c0 + lc, acc);
+      for (; k0 < p.Dpad; k0 += 4) sweep_steps<1>(p, Ar, arow_in, k0 + lk, c0 + lc, acc);
+      if (p.scores) {
+#pragma unroll
+        for (int nb = 0; nb < 4; nb++) {
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const int64_t row = row0 + lk + 4 * r, col = c0 + nb * 16 + lc;
+            if (row < p.Nt && col < p.Ns) p.scores[(size_t)row * p.Ns + col] = acc[nb][r];
+          }
+        }
+      }
+    }
+    if (p.keff == 0) continue;                       // the same for the whole grid
+    __syncthreads();                                 // the previous step's readers are done
+    if (wave_has) {
+#pragma unroll
+      for (int nb = 0; nb < 4; nb++) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) tile[wave][lk + 4 * r][nb * 16 + lc] = acc[nb][r];
+      }
+    }
+    __syncthreads();
+    if (!wave_has) continue;
+    const int64_t col = c0 + lane;
+#pragma unroll
+    for (int rr = 0; rr < 16; rr++) {
+      const int64_t row = row0 + rr;
+      if (row >= p.Nt) continue;                     // the same for the whole wavefront
+      const double s = tile[wave][rr][lane];
+      const bool cand = col < p.Ns && plda_candidate(s) && !(p.exclude_diag && col == row);
+      plda_insert(ls[rr], li[rr], s, (int32_t)col, cand, p.keff, lane);
+    }
+  }
+  if (p.keff == 0 || !wave_has) return;
+#pragma unroll
+  for (int rr = 0; rr < 16; rr++) {
+    const int64_t row = row0 + rr;
+    if (row >= p.Nt || lane >= p.keff) continue;
+    const size_t at = ((size_t)blockIdx.y * p.Nt + row) * p.keff + lane;
+    p.part_s[at] = ls[rr];
+    p.part_i[at] = li[rr];
+  }
+}
+
+// grid: 4 rows a workgroup, a wavefront each: the passes' lists in pass order into one list, then the outputs.
+__global__ __launch_bounds__(256) void plda_merge_kernel(const double *part_s, const int32_t *part_i, int passes, int Nt, int keff, int k,
+                                                         int32_t *best_idx, double *best_score, int32_t *knn_idx, double *knn_score) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+  if (row >= Nt) return;
+  double cs = -INFINITY;
+  int32_t ci = -1;
+  for (int ps = 0; ps < passes; ps++) {
+    const size_t at = ((size_t)ps * Nt + row) * keff + lane;
+    const double s = lane < keff ? part_s[at] : -INFINITY;
+    const int32_t idx = lane < keff ? part_i[at] : -1;
+    plda_insert(cs, ci, s, idx, idx >= 0, keff, lane);
+  }
+  if (best_idx && lane == 0) { best_idx[row] = ci; best_score[row] = cs; }
+  if (knn_idx && lane < k) { knn_idx[(size_t)row * k + lane] = ci; knn_score[(size_t)row * k + lane] = cs; }
+}
+
+// grid: 4 rows a workgroup, a wavefront each.  The row's sum: lane l its elements k = l, l + 64, … ascending, then the
+// lanes' sums in a butterfly (xor 32, 16, … 1); the row is multiplied by sqrt(D / sum).
+__global__ __launch_bounds__(256) void plda_norm_kernel(double *u, int64_t N, int D, const double *psi, const int32_t *num_examples, int norm) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+  if (row >= N) return;
+  double *ur = u + (size_t)row * D;
+  const double inv_n = 1.0 / (double)(num_examples ? num_examples[row] : 1);
+  double sum = 0.0;
+  for (int k = lane; k < D; k += 64) sum += plda_norm_term(ur[k], norm == 2 ? psi[k] : 0.0, inv_n, norm);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  const double f = sqrt((double)D / sum);
+  for (int k = lane; k < D; k += 64) ur[k] *= f;
+}
+
+size_t env_count(const char *name) {
+  const char *e = getenv(name);
+  const long v = e ? atol(e) : 0;
+  return v > 0 ? (size_t)v : 0;
+}
+
+int refuse(mfa_ctx *c, const char *who, int rc, int D, int k, long long nt, long long ns) {
+  switch (rc) {
+    case -2: return c->fail("%s: dimension %d (1 to %d)", who, D, kPldaMaxDim);
+    case -3: return c->fail("%s: lists of %d entries (1 to %d: a row's list is one wavefront register)", who, k, kPldaMaxK);
+    case -5: return c->fail("%s: %lld test and %lld train vectors in one call (fewer than 2^31 each)", who, nt, ns);
+    default: return c->fail("%s: a negative count", who);
+  }
+}
+
+struct Outputs {
+  double *scores; int32_t *best_idx; double *best_score; int32_t *knn_idx; double *knn_score;
+};
+
+// The checks every scoring entry begins with.  Returns 0: go on; 1: nothing to do; -1: refused.
+int score_checks(mfa_ctx *c, const char *who, int64_t Nt, int64_t Ns, int D, int k, const void *test, const Outputs &o) {
+  const bool knn = o.knn_idx || o.knn_score;
+  const int rc = plda_check_shape(D, knn ? k : 1, Nt, Ns);
+  if (rc) return refuse(c, who, rc, D, k, (long long)Nt, (long long)Ns);
+  if (Nt == 0) return 1;
+  if (!o.scores && !o.best_idx && !o.best_score && !knn) return c->fail("%s: every output is NULL", who);
+  if ((o.best_idx != nullptr) != (o.best_score != nullptr) || (o.knn_idx != nullptr) != (o.knn_score != nullptr))
+    return c->fail("%s: an index output and its score output come together", who);
+  if (!test) return c->fail("%s: NULL test vectors", who);
+  return 0;
+}
+
+struct Operands {
+  Workspace ws;
+  size_t o_at = 0, o_bt = 0, o_c = 0, o_flags = 0, o_ps = 0, o_pi = 0;
+  int Dpad = 0, keff = 0, passes = 1;
+  int64_t Nspad = 0, cols_per_pass = kColStep;
+};
+
+// The workspace of one scoring call: the operands, the flags and the passes' lists.
+int lay_out(mfa_ctx *c, Operands &op, int64_t Nt, int64_t Ns, int D, int k, const Outputs &o) {
+  op.Dpad = (D + 3) / 4 * 4;
+  op.Nspad = (Ns + kColStep - 1) / kColStep * kColStep;
+  op.keff = o.knn_idx ? k : (o.best_idx ? 1 : 0);
+  const int64_t row_blocks = (Nt + kRowBlock - 1) / kRowBlock;
+  const size_t forced = env_count("MFA_PLDA_PASS_COLS");
+  int64_t cols = op.Nspad;
+  if (forced) cols = (int64_t)std::min<size_t>(forced, (size_t)1 << 31);
+  else {
+    const int cus = mfa_num_cus(c);
+    if (cus <= 0) return -1;
+    const int64_t want = (2 * (int64_t)cus + row_blocks - 1) / row_blocks;     // passes that fill the device twice
+    if (want > 1) cols = std::max<int64_t>(kMinPassCols, (op.Nspad + want - 1) / want);
+  }
+  cols = std::max<int64_t>(cols, (op.Nspad + 65534) / 65535);                 // grid.y
+  op.cols_per_pass = std::max<int64_t>(kColStep, (cols + kColStep - 1) / kColStep * kColStep);
+  op.passes = (int)std::max<int64_t>(1, (op.Nspad + op.cols_per_pass - 1) / op.cols_per_pass);
+  const size_t mat = (size_t)op.Dpad * (size_t)op.Nspad * 8;
+  op.o_at = op.ws.take(mat); op.o_bt = op.ws.take(mat); op.o_c = op.ws.take((size_t)op.Nspad * 8); op.o_flags = op.ws.take(8);
+  op.o_ps = op.ws.take((size_t)op.passes * Nt * op.keff * 8);
+  op.o_pi = op.ws.take((size_t)op.passes * Nt * op.keff * 4);
+  return op.ws.reserve(c, "the PLDA scoring workspace");
+}
+
+int sweep(mfa_ctx *c, const Operands &op, const double *d_test, int64_t Nt, int64_t Ns, int D, int exclude_diag, int k, const Outputs &o) {
+  {
+    KernelTimer kt(c, MFA_K_PLDA_SWEEP);
+    const SweepParams sp{d_test, (int)Nt, (int)Ns, D, op.Dpad, op.Nspad, op.ws.at<double>(op.o_at), op.ws.at<double>(op.o_bt),
+                         op.ws.at<double>(op.o_c), op.cols_per_pass, op.keff, exclude_diag ? 1 : 0, o.scores,
+                         op.ws.at<double>(op.o_ps), op.ws.at<int32_t>(op.o_pi)};
+    hipLaunchKernelGGL(plda_sweep_kernel, dim3((unsigned)((Nt + kRowBlock - 1) / kRowBlock), (unsigned)op.passes), dim3(256), 0, c->stream, sp);
+    MFA_HIP_CHECK(c, hipGetLastError());
+    MFA_DEBUG_POINT(c, "plda_sweep_kernel rows=%lld cols=%lld D=%d passes=%d k=%d", (long long)Nt, (long long)Ns, D, op.passes, op.keff);
+  }
+  if (op.keff == 0) return 0;
+  KernelTimer kt(c, MFA_K_PLDA_MERGE);
+  hipLaunchKernelGGL(plda_merge_kernel, dim3((unsigned)((Nt + 3) / 4)), dim3(256), 0, c->stream, op.ws.at<double>(op.o_ps),
+                     op.ws.at<int32_t>(op.o_pi), op.passes, (int)Nt, op.keff, k, o.best_idx, o.best_score, o.knn_idx, o.knn_score);
+  MFA_HIP_CHECK(c, hipGetLastError());
+  MFA_DEBUG_POINT(c, "plda_merge_kernel rows=%lld passes=%d", (long long)Nt, op.passes);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+MFA_API int mfa_plda_transform_batch(mfa_ctx *c, const double *d_x, int64_t n, int32_t D, const double *d_transform, const double *d_offset,
+                                     const double *d_psi, const int32_t *d_num_examples, int32_t norm, double *d_out) {
+  MFA_HIP_CHECK(c, hipSetDevice(c->device));
+  const char *who = "PLDA transform";
+  const int rc = plda_check_shape(D, 1, n, 0);
+  if (rc) return refuse(c, who, rc, D, 1, (long long)n, 0);
+  if (norm < 0 || norm > 2) return c->fail("%s: length normalisation %d (0 none, 1 simple, 2 the model's)", who, norm);
+  if (n == 0) return 0;
+  if (!d_x || !d_transform || !d_offset || !d_out || (norm == 2 && !d_psi)) return c->fail("%s: NULL array", who);
+  if (d_x == d_out) return c->fail("%s: the output may not be the input", who);
+  KernelTimer kt(c, MFA_K_PLDA_TRANSFORM);
+  for (int64_t r0 = 0; r0 < n; r0 += kGemmRows) {
+    const int m = (int)std::min<int64_t>(kGemmRows, n - r0);
+    launch_gemm<3>(c, GemmParams{d_x + (size_t)r0 * D, D, 1, d_transform, 1, D, d_out + (size_t)r0 * D, m, D, D, nullptr, 0.0, d_offset});
+  }
+  if (norm != 0)
+    hipLaunchKernelGGL(plda_norm_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, d_out, n, D, d_psi, d_num_examples, norm);
+  MFA_HIP_CHECK(c, hipGetLastError());
+  MFA_DEBUG_POINT(c, "plda transform rows=%lld D=%d norm=%d", (long long)n, D, norm);
+  return 0;
+}
+
+MFA_API int mfa_plda_score_batch(mfa_ctx *c, const double *d_test, int64_t n_test, const double *d_train, int64_t n_train, int32_t D,
+                                 const int32_t *d_train_n, const double *d_psi, int32_t exclude_diagonal, int32_t k, double *d_scores,
+                                 int32_t *d_best_idx, double *d_best_score, int32_t *d_knn_idx, double *d_knn_score) {
+  MFA_HIP_CHECK(c, hipSetDevice(c->device));
+  const char *who = "PLDA scoring";
+  const Outputs o{d_scores, d_best_idx, d_best_score, d_knn_idx, d_knn_score};
+  const int st = score_checks(c, who, n_test, n_train, D, k, d_test, o);
+  if (st) return st < 0 ? st : 0;
+  if (!d_psi || (n_train > 0 && !d_train)) return c->fail("%s: NULL model or train vectors", who);
+  Operands op;
+  if (lay_out(c, op, n_test, n_train, D, k, o)) return -1;
+  int32_t *flags = op.ws.at<int32_t>(op.o_flags);
+  if (op.Nspad > 0) {
+    KernelTimer kt(c, MFA_K_PLDA_PREPARE);
+    MFA_HIP_CHECK(c, hipMemsetAsync(flags, 0, 8, c->stream));
+    hipLaunchKernelGGL(plda_prepare_kernel, dim3((unsigned)((op.Nspad + 255) / 256)), dim3(256), 0, c->stream, d_train, d_train_n, d_psi,
+                       (int)n_train, D, op.Dpad, op.Nspad, op.ws.at<double>(op.o_at), op.ws.at<double>(op.o_bt), op.ws.at<double>(op.o_c),
+                       flags);
+    MFA_HIP_CHECK(c, hipGetLastError());
+    MFA_DEBUG_POINT(c, "plda_prepare_kernel cols=%lld D=%d", (long long)n_train, D);
+  }
+  if (op.Nspad > 0) {                                  // the two refusals that only the data can tell
+    int32_t h_flags[2] = {0, 0};
+    MFA_HIP_CHECK(c, hipMemcpyAsync(h_flags, flags, 8, hipMemcpyDeviceToHost, c->stream));
+    MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    if (h_flags[0]) return c->fail("%s: a psi entry that is not positive and finite", who);
+    if (h_flags[1]) return c->fail("%s: a train vector's number of examples below 1", who);
+  }
+  return sweep(c, op, d_test, n_test, n_train, D, exclude_diagonal, k, o);
+}
+
+MFA_API int mfa_debug_plda_sweep_batch(mfa_ctx *c, const double *d_test, int64_t n_test, int32_t D, const double *d_A, const double *d_B,
+                                       const double *d_c, int64_t n_train, int32_t exclude_diagonal, int32_t k, double *d_scores,
+                                       int32_t *d_best_idx, double *d_best_score, int32_t *d_knn_idx, double *d_knn_score) {
+  MFA_HIP_CHECK(c, hipSetDevice(c->device));
+  const char *who = "PLDA sweep";
+  const Outputs o{d_scores, d_best_idx, d_best_score, d_knn_idx, d_knn_score};
+  const int st = score_checks(c, who, n_test, n_train, D, k, d_test, o);
+  if (st) return st < 0 ? st : 0;
+  if (n_train > 0 && (!d_A || !d_B || !d_c)) return c->fail("%s: NULL operands", who);
+  Operands op;
+  if (lay_out(c, op, n_test, n_train, D, k, o)) return -1;
+  if (op.Nspad > 0) {
+    KernelTimer kt(c, MFA_K_PLDA_PREPARE);
+    hipLaunchKernelGGL(plda_pack_kernel, dim3((unsigned)((op.Nspad + 255) / 256)), dim3(256), 0, c->stream, d_A, d_B, d_c, (int)n_train, D,
+                       op.Dpad, op.Nspad, op.ws.at<double>(op.o_at), op.ws.at<double>(op.o_bt), op.ws.at<double>(op.o_c));
+    MFA_HIP_CHECK(c, hipGetLastError());
+    MFA_DEBUG_POINT(c, "plda_pack_kernel cols=%lld D=%d", (long long)n_train, D);
+  }
+  return sweep(c, op, d_test, n_test, n_train, D, exclude_diagonal, k, o);
+}
+
+}  // extern "C"

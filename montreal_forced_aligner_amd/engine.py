@@ -43,7 +43,8 @@ KERNEL_SLOTS = ("mfcc", "cmvn", "feats", "gmm", "viterbi", "resample", "pitch", 
                 "mllt_lookup", "mllt_sort", "mllt_sums", "mllt_reduce",
                 "tree_keys", "tree_order", "tree_sums", "vad",
                 "ubm_select", "ubm_post", "ubm_sums", "ubm_reduce",
-                "ivec_prune", "ivec_utt", "ivec_scatter", "ivec_products", "ivec_solve", "ivec_acc")
+                "ivec_prune", "ivec_utt", "ivec_scatter", "ivec_products", "ivec_solve", "ivec_acc",
+                "plda_transform", "plda_prepare", "plda_sweep", "plda_merge")
 
 
 def _out_ptrs(out: Dict[str, Optional[torch.Tensor]]):
@@ -286,6 +287,26 @@ class AlignmentEngine(GraphPacking, FrontEndStages):
                                                          int(W.shape[0]), int(W.shape[2]), _ptr(W), _ptr(U), float(prior_offset),
                                                          _ptr(mean), _ptr(var), _ptr(aux), *(_ptr(t) for t in a)),
               "mfa_ivector_estep_batch")
+
+    def _launch_plda_transform(self, x, model, num_examples, norm: int, out) -> None:
+        """``model``: the device tensors (transform, offset, psi) of a ``plda.PldaModel``; ``norm`` 0 none, 1 simple, 2 the model's."""
+        T, off, psi = model
+        check(self.ctx, self.lib.mfa_plda_transform_batch(self.ctx, _ptr(x), int(x.shape[0]), int(T.shape[0]), _ptr(T), _ptr(off), _ptr(psi),
+                                                          _ptr(num_examples), int(norm), _ptr(out)), "mfa_plda_transform_batch")
+
+    def _launch_plda_score(self, test, train, train_n, psi, exclude_diagonal: bool, k: int, scores, best, knn, operands=None) -> None:
+        """``best`` / ``knn``: None or the (index, score) pair of tensors.  ``operands``: the debug entry's (A, B, c) in place of
+        ``train``, ``train_n`` and ``psi`` (mfa_debug_plda_sweep_batch)."""
+        b, q = best or (None, None), knn or (None, None)
+        outs = (_ptr(scores), _ptr(b[0]), _ptr(b[1]), _ptr(q[0]), _ptr(q[1]))
+        nt, D = int(test.shape[0]), int(test.shape[1])
+        if operands is not None:
+            A, B, c = operands
+            check(self.ctx, self.lib.mfa_debug_plda_sweep_batch(self.ctx, _ptr(test), nt, D, _ptr(A), _ptr(B), _ptr(c), int(c.shape[0]),
+                                                                int(bool(exclude_diagonal)), int(k), *outs), "mfa_debug_plda_sweep_batch")
+        else:
+            check(self.ctx, self.lib.mfa_plda_score_batch(self.ctx, _ptr(test), nt, _ptr(train), int(train.shape[0]), D, _ptr(train_n),
+                                                          _ptr(psi), int(bool(exclude_diagonal)), int(k), *outs), "mfa_plda_score_batch")
 
     def _launch_scan(self, values, d_frame_off, n_utt: int, total: int, scan, totals) -> None:
         check(self.ctx, self.lib.mfa_vad_scan_batch(self.ctx, _ptr(values), _ptr(d_frame_off), n_utt, total, _ptr(scan),

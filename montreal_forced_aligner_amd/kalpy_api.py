@@ -1651,3 +1651,201 @@ class IvectorExtractor:
         flush()
         file_name = Path(file_name)
         kaldi_io.write_table(file_name, entries, "vector", file_name.with_suffix(".scp") if write_scp else None)
+
+
+# ------------------------------------------------------------------------------------------------ PLDA (kalpy.ivector)
+def ivector_normalize_length(ivector) -> np.ndarray:
+    """``_kalpy.ivector.ivector_normalize_length``: the vector (or every row) scaled to norm √D.  kalpy's works in place on a
+    Kaldi vector; a numpy array given here is changed in place too, and returned."""
+    from .plda import normalize_length
+    out = normalize_length(ivector)
+    if isinstance(ivector, np.ndarray) and ivector.dtype == np.float64:
+        ivector[...] = out
+        return ivector
+    return out
+
+
+def ivector_subtract_mean(ivectors) -> np.ndarray:
+    """``_kalpy.ivector.ivector_subtract_mean``: the vectors with their mean taken off, as rows [n, D].  A list of numpy
+    vectors is also updated in place, as kalpy updates its list of Kaldi vectors."""
+    from .plda import subtract_mean
+    out = subtract_mean(np.stack([np.asarray(v, dtype=np.float64) for v in ivectors]))
+    if isinstance(ivectors, list):
+        for v, row in zip(ivectors, out):
+            if isinstance(v, np.ndarray) and v.dtype == np.float64:
+                v[...] = row
+    return out
+
+
+class Plda:
+    """kalpy's ``Plda`` as the reference uses it (MFA/corpus/ivector_corpus.py:316-452, MFA/diarization/multiprocessing.py):
+    ``transform_ivector``, ``log_likelihood`` and the distances built on it, one pair at a time on the host — and the batched
+    forms that replace the reference's per-pair Python calls (``pairwise``, ``log_likelihood_distance_vectorized``) on the
+    device.  ``distance`` is defined here as −LLR (kalpy's own mapping of the ratio to a distance is not among this project's
+    references: INTEGRATION.md)."""
+
+    def __init__(self, model=None):
+        self.model = model
+
+    @classmethod
+    def read(cls, path) -> "Plda":
+        from .plda import PldaModel
+        return cls(PldaModel.read(path))
+
+    def write(self, path, binary: bool = True) -> None:
+        self.model.write(path, binary)
+
+    def Dim(self) -> int:
+        return self.model.dim
+
+    def transform_ivector(self, ivector, num_examples: int = 1, normalize_length: bool = True, simple_length_norm: bool = False):
+        return self.model.transform_ivector(np.asarray(ivector, dtype=np.float64), num_examples, normalize_length, simple_length_norm)
+
+    def transform_ivectors(self, ivectors, num_examples=None, normalize_length: bool = True, simple_length_norm: bool = False) -> np.ndarray:
+        """Rows [n, D] on the device (``stats.plda_transform``); numpy out."""
+        from .stats import plda_transform
+        return plda_transform(get_engine(), self.model, ivectors, num_examples, normalize_length, simple_length_norm).cpu().numpy()
+
+    def log_likelihood(self, train_ivector, num_train_examples: int, test_ivector) -> float:
+        """The log-likelihood ratio of one pair of transformed vectors, on the host: the direct form, the specification."""
+        return float(self.model.log_likelihood_ratio(train_ivector, num_train_examples, test_ivector))
+
+    def distance(self, train_ivector, test_ivector, num_train_examples: int = 1) -> float:
+        return -self.log_likelihood(train_ivector, num_train_examples, test_ivector)
+
+    def log_likelihood_distance_vectorized(self, train_ivectors, test_ivector, num_train_examples=None) -> np.ndarray:
+        """One test vector against every train vector: −LLR [n_train], on the device."""
+        return -self.pairwise(np.atleast_2d(test_ivector), train_ivectors, num_train_examples)[0]
+
+    def pairwise(self, test_ivectors, train_ivectors=None, num_train_examples=None) -> np.ndarray:
+        """The matrix [test, train] of log-likelihood ratios on the device (``stats.plda_scores``): what the reference builds
+        through ``pairwise_distances(metric=plda.log_likelihood)``.  ``train_ivectors`` None: the test vectors themselves."""
+        from .stats import plda_scores
+        train = test_ivectors if train_ivectors is None else train_ivectors
+        return plda_scores(get_engine(), self.model, test_ivectors, train, num_train_examples)
+
+    def nearest(self, test_ivectors, k: int, train_ivectors=None, num_train_examples=None):
+        """The k best train vectors of every test vector (indices, LLRs), no matrix stored (``stats.plda_knn``): what the
+        reference's ``NearestNeighbors(metric=<callable>)`` is asked for.  ``train_ivectors`` None: the test vectors, each
+        without itself."""
+        from .stats import plda_knn
+        same = train_ivectors is None
+        idx, score = plda_knn(get_engine(), self.model, test_ivectors, test_ivectors if same else train_ivectors, k, num_train_examples,
+                              exclude_diagonal=same)
+        return idx.cpu().numpy(), score.cpu().numpy()
+
+
+class PldaStats:
+    """kalpy's ``PldaStats``: ``AddSamples(weight, group)``, ``Sort()``, ``Dim()``."""
+
+    def __init__(self):
+        from .plda import PldaStats as _Stats
+        self.stats = _Stats()
+
+    def AddSamples(self, weight: float, group) -> None:
+        self.stats.add_samples(float(weight), np.asarray(group, dtype=np.float64))
+
+    def Sort(self) -> None:
+        self.stats.sort()
+
+    def Dim(self) -> int:
+        return self.stats.dim
+
+
+@dataclass
+class PldaEstimationConfig:
+    num_em_iters: int = 10
+
+
+class PldaEstimator:
+    """``PldaEstimator(stats).Estimate(config, plda)`` fills ``plda`` (a ``Plda``), as compute_plda calls it
+    (MFA/corpus/ivector_corpus.py:277-281)."""
+
+    def __init__(self, stats: PldaStats):
+        self.stats = stats
+
+    def Estimate(self, config: PldaEstimationConfig, plda: Plda) -> None:
+        from .plda import estimate_plda
+        plda.model = estimate_plda(self.stats.stats, config.num_em_iters)
+
+
+@dataclass
+class PldaUnsupervisedAdaptorConfig:
+    mean_diff_scale: float = 1.0
+    within_covar_scale: float = 0.3
+    between_covar_scale: float = 0.7
+
+
+class PldaUnsupervisedAdaptor:
+    """``AddStats(weight, ivector)`` then ``UpdatePlda(config, plda)``, which changes ``plda`` in place, as adapt_plda calls
+    them (MFA/corpus/ivector_corpus.py:123-139)."""
+
+    def __init__(self):
+        self._vectors: List[Tuple[float, np.ndarray]] = []
+
+    def AddStats(self, weight: float, ivector) -> None:
+        self._vectors.append((float(weight), np.array(ivector, dtype=np.float64)))
+
+    def UpdatePlda(self, config: PldaUnsupervisedAdaptorConfig, plda: Plda) -> None:
+        from .plda import PldaUnsupervisedAdaptor as _Adaptor
+        ad = _Adaptor(config.mean_diff_scale, config.within_covar_scale, config.between_covar_scale)
+        for w, v in self._vectors:
+            ad.add_stats(w, v)
+        plda.model = ad.update_plda(plda.model)
+
+
+class PldaScorer:
+    """``PldaScorer(plda_path)`` as PldaClassificationFunction uses kalpy's (MFA/diarization/multiprocessing.py):
+    ``load_speaker_ivectors`` prepares the speakers as ``collect_speaker_ivectors`` does (length norm, subtract mean, length
+    norm, the transform with each speaker's utterance count); ``classify_speaker`` returns (speaker index, LLR) of one
+    utterance vector, ``classify_speakers`` of a batch, both through the device's fused best-column sweep.  ``backend="host"``
+    runs the same chain on the host twins (tests)."""
+
+    def __init__(self, plda_path, backend: str = "device"):
+        self.plda = plda_path if isinstance(plda_path, Plda) else Plda.read(plda_path)
+        self.backend = backend
+        self.speaker_ids: List[str] = []
+        self.speaker_ivectors: Optional[np.ndarray] = None      # transformed, [speakers, D]
+        self.num_speaker_examples: Optional[np.ndarray] = None
+
+    def _transform(self, x, n=None) -> np.ndarray:
+        from . import stats as _stats
+        if self.backend == "host":
+            return _stats.plda_transform_host(self.plda.model, x, n)
+        return _stats.plda_transform(get_engine(), self.plda.model, x, n).cpu().numpy()
+
+    def load_speaker_ivectors(self, train_ivector_path, num_utts_path=None) -> None:
+        """``train_ivector_path``: a vector ark of per-speaker mean i-vectors, or (key, vector) pairs; ``num_utts_path``: the text
+        file "speaker count" per line, or a mapping; missing: 1 each."""
+        from .plda import normalize_length, subtract_mean
+        if isinstance(train_ivector_path, (str, Path)):
+            entries = list(kaldi_io.read_ark(Path(train_ivector_path).read_bytes(), "vector"))
+        else:
+            entries = list(train_ivector_path)
+        if isinstance(num_utts_path, (str, Path)):
+            counts = {a: int(b) for a, b in (line.split() for line in Path(num_utts_path).read_text().splitlines() if line.strip())}
+        else:
+            counts = dict(num_utts_path or {})
+        self.speaker_ids = [str(k) for k, _ in entries]
+        x = np.stack([np.asarray(v, dtype=np.float64) for _, v in entries])
+        x = normalize_length(subtract_mean(normalize_length(x)))
+        self.num_speaker_examples = np.array([counts.get(k, 1) for k in self.speaker_ids], dtype=np.int32)
+        self.speaker_ivectors = self._transform(x, self.num_speaker_examples)
+
+    def classify_speakers(self, ivectors, transformed: bool = False):
+        """(speaker index int32 [n], LLR float64 [n]) of utterance vectors [n, D]; not yet in the model's space unless
+        ``transformed``.  −1 for a vector without a finite score."""
+        from . import stats as _stats
+        if self.speaker_ivectors is None:
+            raise RuntimeError("PldaScorer: load_speaker_ivectors first")
+        x = np.atleast_2d(np.asarray(ivectors, dtype=np.float64))
+        if not transformed:
+            x = self._transform(x)
+        if self.backend == "host":
+            return _stats.plda_classify_host(self.plda.model, x, self.speaker_ivectors, self.num_speaker_examples)
+        idx, score = _stats.plda_classify(get_engine(), self.plda.model, x, self.speaker_ivectors, self.num_speaker_examples)
+        return idx.cpu().numpy(), score.cpu().numpy()
+
+    def classify_speaker(self, ivector, transformed: bool = False):
+        idx, score = self.classify_speakers(np.atleast_2d(ivector), transformed)
+        return int(idx[0]), float(score[0])

@@ -1035,3 +1035,191 @@ def ivector_estep_host(model, gamma: np.ndarray, X: np.ndarray, into=None, want_
         into.n = float(acc[5][0])
         _ivec_add_aux(into, aux, gamma)
     return mean, var, aux
+
+
+# ---- PLDA: the transform, the score matrix and its row-wise consumers (include/mfa_hip.h "PLDA") ---------------------------------
+_PLDA_TWIN_CODES = {-2: "dimension outside [1, 1024]", -3: "list length outside [1, 64]", -4: "a psi entry that is not positive and finite",
+                    -5: "2^31 vectors or more", -6: "a number of examples below 1", -7: "every output is off"}
+PLDA_BLOCK_BYTES = 256 << 20        # device bytes of one row block of ``plda_scores``
+PLDA_MATRIX_BYTES = 4 << 30         # the largest full matrix ``plda_scores`` hands out
+
+
+def _plda_twin(rc: int, name: str) -> None:
+    if rc != 0:
+        raise _lib.MfaHipError(f"{name}: {_PLDA_TWIN_CODES.get(rc, 'bad arguments')}")
+
+
+def _plda_device_model(engine, model):
+    """A ``plda.PldaModel`` as the device tensors (transform, offset, psi), uploaded once per model object and device."""
+    cache = model.__dict__.setdefault("_device_arrays", {})
+    key = str(engine.device)
+    if key not in cache:
+        cache.clear()
+        cache[key] = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(engine.device)
+                           for a in (model.transform, model.offset, model.psi))
+    return cache[key]
+
+
+def _plda_vectors(engine, x, D: int, what: str) -> torch.Tensor:
+    """Rows of float64 [n, D] on the device, from a numpy array or a tensor."""
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64))
+    if t.dim() != 2 or (t.shape[0] and t.shape[1] != D):
+        raise _lib.MfaHipError(f"{what}: vectors {tuple(t.shape)} for a model of dimension {D}")
+    return t.to(device=engine.device, dtype=torch.float64).contiguous()
+
+
+def _plda_counts(engine, n, rows: int, what: str):
+    if n is None:
+        return None
+    t = n if isinstance(n, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(n, dtype=np.int32))
+    if tuple(t.shape) != (rows,):
+        raise _lib.MfaHipError(f"{what}: one number of examples per vector ({tuple(t.shape)} for {rows})")
+    return t.to(device=engine.device, dtype=torch.int32).contiguous()
+
+
+def _plda_norm(normalize_length: bool, simple_length_norm: bool) -> int:
+    return 0 if not normalize_length else (1 if simple_length_norm else 2)
+
+
+def plda_transform(engine, model, x, num_examples=None, normalize_length: bool = True, simple_length_norm: bool = False) -> torch.Tensor:
+    """``model.transform_ivector`` of every row of ``x`` ([n, D], numpy or a tensor) on the device (mfa_plda_transform_batch):
+    float64 [n, D] on the device, where the scoring calls take it.  ``num_examples``: int32 [n], default 1."""
+    x = _plda_vectors(engine, x, model.dim, "plda_transform")
+    out = torch.empty_like(x)
+    engine._launch_plda_transform(x, _plda_device_model(engine, model), _plda_counts(engine, num_examples, x.shape[0], "plda_transform"),
+                                  _plda_norm(normalize_length, simple_length_norm), out)
+    return out
+
+
+def plda_transform_host(model, x, num_examples=None, normalize_length: bool = True, simple_length_norm: bool = False) -> np.ndarray:
+    """``plda_transform`` on the host twin (plain loops): numpy in and out."""
+    x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+    if x.shape[0] and x.shape[1] != model.dim:
+        raise _lib.MfaHipError(f"plda_transform_host: vectors {x.shape} for a model of dimension {model.dim}")
+    n = None if num_examples is None else np.ascontiguousarray(num_examples, dtype=np.int32)
+    if n is not None and n.shape != (x.shape[0],):
+        raise _lib.MfaHipError("plda_transform_host: one number of examples per vector")
+    out = np.empty_like(x)
+    T, off, psi = (np.ascontiguousarray(a, dtype=np.float64) for a in (model.transform, model.offset, model.psi))
+    _plda_twin(_lib.lib().mfa_debug_plda_transform_host(x.ctypes.data, int(x.shape[0]), model.dim, T.ctypes.data, off.ctypes.data,
+                                                        psi.ctypes.data, None if n is None else n.ctypes.data,
+                                                        _plda_norm(normalize_length, simple_length_norm), out.ctypes.data),
+               "mfa_debug_plda_transform_host")
+    return out
+
+
+def _plda_score_call(engine, model, test, train, train_n, exclude_diagonal, k, want_scores, want_best, want_knn, operands=None):
+    """One scoring call: (scores or None, (best index, best score) or None, (k-NN indices, scores) or None), on the device."""
+    D = model.dim if operands is None else int(np.shape(operands[0])[1])
+    test = _plda_vectors(engine, test, D, "PLDA scoring")
+    dev, nt = engine.device, int(test.shape[0])
+    if operands is None:
+        train = _plda_vectors(engine, train, D, "PLDA scoring")
+        ns = int(train.shape[0])
+        train_n = _plda_counts(engine, train_n, ns, "PLDA scoring")
+        psi = _plda_device_model(engine, model)[2]
+    else:
+        operands = tuple(torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev) if not isinstance(a, torch.Tensor) else a
+                         for a in operands)
+        ns, psi = int(operands[2].shape[0]), None
+    scores = torch.empty((nt, ns), dtype=torch.float64, device=dev) if want_scores else None
+    best = (torch.empty(nt, dtype=torch.int32, device=dev), torch.empty(nt, dtype=torch.float64, device=dev)) if want_best else None
+    knn = (torch.empty((nt, k), dtype=torch.int32, device=dev), torch.empty((nt, k), dtype=torch.float64, device=dev)) if want_knn else None
+    engine._launch_plda_score(test, train, train_n, psi, exclude_diagonal, k, scores, best, knn, operands)
+    return scores, best, knn
+
+
+def plda_scores(engine, model, test, train, train_n=None, block_bytes: int = PLDA_BLOCK_BYTES,
+                max_bytes: int = PLDA_MATRIX_BYTES) -> np.ndarray:
+    """The matrix [test, train] of log-likelihood ratios (mfa_plda_score_batch), vectors in the model's space (``plda_transform``),
+    ``train_n`` the examples behind each train vector.  The device writes row blocks of at most ``block_bytes``; the matrix
+    is handed out as a numpy array.  One larger than ``max_bytes`` is refused: the consumers that need no stored matrix are
+    ``plda_classify`` and ``plda_knn``."""
+    test = _plda_vectors(engine, test, model.dim, "plda_scores")
+    train = _plda_vectors(engine, train, model.dim, "plda_scores")
+    nt, ns = int(test.shape[0]), int(train.shape[0])
+    if nt * ns * 8 > max_bytes:
+        raise _lib.MfaHipError(f"plda_scores: a matrix of {nt} x {ns} scores ({nt * ns * 8} bytes) exceeds {max_bytes} bytes: "
+                               "use plda_knn or plda_classify, which keep no matrix")
+    train_n = _plda_counts(engine, train_n, ns, "plda_scores")
+    out = np.empty((nt, ns))
+    rows = max(1, int(block_bytes) // max(ns * 8, 1))
+    for r0 in range(0, nt, rows):
+        out[r0: r0 + rows] = _plda_score_call(engine, model, test[r0: r0 + rows], train, train_n, False, 1, True, False, False)[0].cpu().numpy()
+    return out
+
+
+def plda_classify(engine, model, test, train, train_n=None, exclude_diagonal: bool = False):
+    """Every test vector's best train vector: (index int32 [n_test], score float64 [n_test]) on the device; −1 and −inf for a
+    row without a finite score.  Ties go to the lower index.  No matrix is stored."""
+    return _plda_score_call(engine, model, test, train, train_n, exclude_diagonal, 1, False, True, False)[1]
+
+
+def plda_knn(engine, model, test, train, k: int, train_n=None, exclude_diagonal: bool = False):
+    """Every test vector's ``k`` (1 to 64) best train vectors, best first: (indices int32 [n_test, k], scores float64 [n_test, k])
+    on the device, padded with −1 and −inf.  ``exclude_diagonal``: test and train are the same vectors, skip j == i."""
+    return _plda_score_call(engine, model, test, train, train_n, exclude_diagonal, int(k), False, False, True)[2]
+
+
+def plda_sweep(engine, test, A, B, c, exclude_diagonal: bool = False, k: int = 1, want_scores=True, want_best=True, want_knn=True):
+    """The sweep alone over the caller's operands (mfa_debug_plda_sweep_batch; tests)."""
+    return _plda_score_call(engine, None, test, None, None, exclude_diagonal, int(k), want_scores, want_best, want_knn, operands=(A, B, c))
+
+
+def plda_prepare_host(model, train, train_n=None):
+    """(A [n, D], B [n, D], c [n]) of the train vectors on the host twin (mfa_debug_plda_prepare_host)."""
+    train = np.ascontiguousarray(np.atleast_2d(train), dtype=np.float64)
+    n = None if train_n is None else np.ascontiguousarray(train_n, dtype=np.int32)
+    psi = np.ascontiguousarray(model.psi, dtype=np.float64)
+    A, B, c = np.empty_like(train), np.empty_like(train), np.empty(train.shape[0])
+    _plda_twin(_lib.lib().mfa_debug_plda_prepare_host(train.ctypes.data, int(train.shape[0]), int(train.shape[1]),
+                                                      None if n is None else n.ctypes.data, psi.ctypes.data, A.ctypes.data, B.ctypes.data,
+                                                      c.ctypes.data), "mfa_debug_plda_prepare_host")
+    return A, B, c
+
+
+def _plda_host_call(model, test, train, train_n, exclude_diagonal, k, want_scores, want_best, want_knn, operands=None):
+    test = np.ascontiguousarray(np.atleast_2d(test), dtype=np.float64)
+    nt, D = int(test.shape[0]), int(test.shape[1])
+    p = lambda a: None if a is None else a.ctypes.data
+    if operands is None:
+        train = np.ascontiguousarray(np.atleast_2d(train), dtype=np.float64)
+        if model.dim != D or (train.shape[0] and train.shape[1] != D):
+            raise _lib.MfaHipError(f"PLDA scoring: vectors {test.shape} and {train.shape} for a model of dimension {model.dim}")
+        ns = int(train.shape[0])
+        n = None if train_n is None else np.ascontiguousarray(train_n, dtype=np.int32)
+        if n is not None and n.shape != (ns,):
+            raise _lib.MfaHipError("PLDA scoring: one number of examples per train vector")
+        psi = np.ascontiguousarray(model.psi, dtype=np.float64)
+    else:
+        A, B, c = (np.ascontiguousarray(a, dtype=np.float64) for a in operands)
+        ns = int(c.shape[0])
+    scores = np.empty((nt, ns)) if want_scores else None
+    bi, bs = (np.empty(nt, np.int32), np.empty(nt)) if want_best else (None, None)
+    ki, ks = (np.empty((nt, k), np.int32), np.empty((nt, k))) if want_knn else (None, None)
+    outs = (p(scores), p(bi), p(bs), p(ki), p(ks))
+    if operands is None:
+        _plda_twin(_lib.lib().mfa_debug_plda_score_host(p(test), nt, p(train), ns, D, p(n), p(psi), int(bool(exclude_diagonal)), int(k), *outs),
+                   "mfa_debug_plda_score_host")
+    else:
+        _plda_twin(_lib.lib().mfa_debug_plda_sweep_host(p(test), nt, D, p(A), p(B), p(c), ns, int(bool(exclude_diagonal)), int(k), *outs),
+                   "mfa_debug_plda_sweep_host")
+    return scores, (bi, bs) if want_best else None, (ki, ks) if want_knn else None
+
+
+def plda_scores_host(model, test, train, train_n=None) -> np.ndarray:
+    """``plda_scores`` on the host twin (the expanded form in plain loops): numpy in and out."""
+    return _plda_host_call(model, test, train, train_n, False, 1, True, False, False)[0]
+
+
+def plda_classify_host(model, test, train, train_n=None, exclude_diagonal: bool = False):
+    return _plda_host_call(model, test, train, train_n, exclude_diagonal, 1, False, True, False)[1]
+
+
+def plda_knn_host(model, test, train, k: int, train_n=None, exclude_diagonal: bool = False):
+    return _plda_host_call(model, test, train, train_n, exclude_diagonal, int(k), False, False, True)[2]
+
+
+def plda_sweep_host(test, A, B, c, exclude_diagonal: bool = False, k: int = 1, want_scores=True, want_best=True, want_knn=True):
+    """``plda_sweep`` on the host twin (mfa_debug_plda_sweep_host)."""
+    return _plda_host_call(None, test, None, None, exclude_diagonal, int(k), want_scores, want_best, want_knn, operands=(A, B, c))

@@ -1445,3 +1445,19 @@ class IvectorTrainer:
             m.write(d / f"{i}.ie"); out.append(d / f"{i}.ie")
         self.model.write(d / "final.ie")
         return out + [d / "final.ie"]
+
+    def compute_plda(self, ivectors, utt2spk, directory=None, minimum_utterance_count: int = 1, num_em_iters: int = 10):
+        """The reference's ``compute_plda`` (MFA/corpus/ivector_corpus.py:196-283), where its ``IvectorTrainer`` ends: a PLDA
+        model from the extracted i-vectors and their speakers (``plda.train_plda``: every vector length-normalised, a class per
+        speaker, the reference's three refusals as ``plda.PldaTrainingError``), written as ``plda`` beside ``final.ie`` when a
+        ``directory`` is given.  ``ivectors``: utterance → vector, or the vector ark ``export_ivectors`` wrote."""
+        from . import plda as _plda
+
+        if isinstance(ivectors, (str, Path)):
+            ivectors = dict(kaldi_io.read_ark(Path(ivectors).read_bytes(), "vector"))
+        self.plda = _plda.train_plda(ivectors, utt2spk, minimum_utterance_count, num_em_iters)
+        if directory is not None:
+            d = Path(directory)
+            d.mkdir(parents=True, exist_ok=True)
+            self.plda.write(d / "plda")
+        return self.plda
