@@ -51,7 +51,7 @@ MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
  * 13-16 LDA statistics (lookup, second moment, ordering + class sums, reductions), 17-20 MLLT statistics (lookup,
  * ordering, sums, reductions), 21-23 tree statistics (keys, ordering, sums), 24 speech activity (each entry point's launches),
  * 25-28 diagonal UBM (selection, posteriors, sums, reductions), 29-34 i-vector extractor (pruning, utterance statistics,
- * scatter, products, solve, accumulators), 35-38 PLDA (transform, prepare, sweep, merge).
+ * scatter, products, solve, accumulators), 35-38 PLDA (transform, prepare, sweep, merge), 39-42 clustering (symmetrise, degree, rounds, labels).
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -1144,6 +1144,62 @@ MFA_API int mfa_debug_plda_sweep_batch(mfa_ctx *ctx, const double *d_test, int64
 MFA_API int mfa_debug_plda_sweep_host(const double *h_test, int64_t n_test, int32_t D, const double *h_A, const double *h_B,
                                       const double *h_c, int64_t n_train, int32_t exclude_diagonal, int32_t k, double *h_scores,
                                       int32_t *h_best_idx, double *h_best_score, int32_t *h_knn_idx, double *h_knn_score);
+
+/* Neighbour bits: a fourth consumer of the same sweep, and the sweep for two more metrics.  What the reference's
+ * cluster_matrix and calculate_distance_threshold (MFA/diarization/multiprocessing.py) need of the vectors of a corpus.
+ *   (d) d_bits [n_test][W] (uint64), W = ceil(n_train / 64): bit j & 63 of word j >> 6 of row i is set iff score[i][j] >=
+ *       threshold, a plain comparison on the very accumulator value that (a) stores: never for a NaN score; with threshold =
+ *       -inf for every score that is not NaN.  Bits of columns >= n_train are 0.  Column passes own whole words, so nothing
+ *       is merged and the words do not depend on MFA_PLDA_PASS_COLS.  Every word of every row is written.
+ * metric chooses the prepare step (csrc/plda_math.hpp); the sweep's arithmetic and order are those of the scoring contract:
+ *   0 plda: A, B, c as above (d_train_n, d_psi as above);
+ *   1 euclidean: A_jk = -1, B_jk = 2 g, c_j = -sum_k g^2 (k ascending): score = -|p - g|^2 in its expanded form;
+ *   2 dot: A_jk = 0, B_jk = g, c_j = 0: score = p . g (the cosine of rows the caller made unit length).
+ * For metrics 1 and 2 d_train_n and d_psi are not looked at.  The outputs (a), (b), (c) are as in mfa_plda_score_batch, for any
+ * metric; at least one of (a) to (d) is required; threshold is only looked at with (d).
+ * Limits: those of mfa_plda_score_batch, and a metric outside [0, 2], a threshold that is NaN when (d) is asked for.  The
+ * context stays usable.  n_test == 0 is no error and writes nothing.  Timing slots 36 to 38.
+ * mfa_debug_neighbor_sweep_batch takes the caller's operands like mfa_debug_plda_sweep_batch; the _host functions are the same
+ * contracts in plain loops (return codes as mfa_debug_plda_score_host, -8 an unknown metric, -9 a NaN threshold). */
+MFA_API int mfa_neighbor_bits_batch(mfa_ctx *ctx, const double *d_test, int64_t n_test, const double *d_train, int64_t n_train,
+                                    int32_t D, int32_t metric, const int32_t *d_train_n, const double *d_psi,
+                                    int32_t exclude_diagonal, int32_t k, double threshold, double *d_scores, int32_t *d_best_idx,
+                                    double *d_best_score, int32_t *d_knn_idx, double *d_knn_score, uint64_t *d_bits);
+MFA_API int mfa_debug_neighbor_bits_host(const double *h_test, int64_t n_test, const double *h_train, int64_t n_train, int32_t D,
+                                         int32_t metric, const int32_t *h_train_n, const double *h_psi, int32_t exclude_diagonal,
+                                         int32_t k, double threshold, double *h_scores, int32_t *h_best_idx, double *h_best_score,
+                                         int32_t *h_knn_idx, double *h_knn_score, uint64_t *h_bits);
+MFA_API int mfa_debug_neighbor_sweep_batch(mfa_ctx *ctx, const double *d_test, int64_t n_test, int32_t D, const double *d_A,
+                                           const double *d_B, const double *d_c, int64_t n_train, int32_t exclude_diagonal,
+                                           int32_t k, double threshold, double *d_scores, int32_t *d_best_idx, double *d_best_score,
+                                           int32_t *d_knn_idx, double *d_knn_score, uint64_t *d_bits);
+MFA_API int mfa_debug_neighbor_sweep_host(const double *h_test, int64_t n_test, int32_t D, const double *h_A, const double *h_B,
+                                          const double *h_c, int64_t n_train, int32_t exclude_diagonal, int32_t k, double threshold,
+                                          double *h_scores, int32_t *h_best_idx, double *h_best_score, int32_t *h_knn_idx,
+                                          double *h_knn_score, uint64_t *h_bits);
+
+/* ---- Clustering: DBSCAN on the neighbour bit matrix of N points (the square case of (d): test = train), what the
+ *      reference's cluster_matrix asks of scikit-learn for ClusterType.dbscan.  Integer work with a unique answer; no atomics;
+ *      every output is a function of the input alone.  In order:
+ *   symmetrise, in place: bits[i][j] |= bits[j][i] (an edge is a pair that passes in either direction — the expanded score is
+ *     not bit-symmetric in i and j), the diagonal is set, bits of columns >= N are cleared;
+ *   d_count [N] (int32): the popcount of row i, the point itself included; d_core [N] (int32 0 / 1): count >= min_samples;
+ *   components of the core points over the edges between core points; a component's root is its smallest index;
+ *   d_labels [N] (int32): clusters are numbered 0, 1, ... in ascending order of their root; a core point takes its cluster's
+ *     number, any other point the smallest number among its core neighbours, -1 without one (scikit-learn's result: a cluster
+ *     starts at the lowest unvisited core index, and the first cluster to reach a border point keeps it).
+ * *h_n_clusters: the number of clusters; *h_rounds: the rounds the component search took (a round: every core point takes the
+ * smallest root among its core neighbours and offers it to its old root, then roots follow their roots; the search ends with the first round that changes
+ * nothing; the rounds work in place, so their number depends on the order the device ran the wavefronts in — it is a
+ * measurement, the one result here that is not a function of the input alone).  The call waits for the device between rounds
+ * and before it returns.
+ * Limits (refused with a message, the context stays usable): N outside [0, 2^31); min_samples below 1; a NULL array or
+ * result.  N == 0 writes nothing but the two results (0).  Timing slots 39 (symmetrise), 40 (degree), 41 (rounds), 42 (labels).
+ * The host twin does the same to h_bits by any sequential method.  Returns 0, -1 a NULL array, -2 N, -3 min_samples. */
+MFA_API int mfa_dbscan_from_bits(mfa_ctx *ctx, uint64_t *d_bits, int64_t N, int32_t min_samples, int32_t *d_labels, int32_t *d_core,
+                                 int32_t *d_count, int32_t *h_n_clusters, int32_t *h_rounds);
+MFA_API int mfa_debug_dbscan_from_bits_host(uint64_t *h_bits, int64_t N, int32_t min_samples, int32_t *h_labels, int32_t *h_core,
+                                            int32_t *h_count, int32_t *h_n_clusters);
 
 #ifdef __cplusplus
 }

@@ -23,7 +23,8 @@ enum { MFA_K_MFCC = 0, MFA_K_CMVN = 1, MFA_K_FEATS = 2, MFA_K_GMM = 3, MFA_K_VIT
        MFA_K_VAD = 24, MFA_K_UBM_SELECT = 25, MFA_K_UBM_POST = 26, MFA_K_UBM_SUMS = 27, MFA_K_UBM_REDUCE = 28,
        MFA_K_IVEC_PRUNE = 29, MFA_K_IVEC_UTT = 30, MFA_K_IVEC_SCATTER = 31, MFA_K_IVEC_PRODUCTS = 32, MFA_K_IVEC_SOLVE = 33, MFA_K_IVEC_ACC = 34,
        MFA_K_PLDA_TRANSFORM = 35, MFA_K_PLDA_PREPARE = 36, MFA_K_PLDA_SWEEP = 37, MFA_K_PLDA_MERGE = 38,
-       MFA_K_COUNT = 39 };
+       MFA_K_CLUSTER_SYMM = 39, MFA_K_CLUSTER_DEGREE = 40, MFA_K_CLUSTER_ROUNDS = 41, MFA_K_CLUSTER_LABELS = 42,
+       MFA_K_COUNT = 43 };
 
 // The device operations of dev_buf.hpp as HIP calls.  Every device pointer a context owns is an MfaBuf: freed with the
 // context, grown with reserve(), tables replaced as a set with dev_upload_commit<MfaHipDev>().
@@ -128,7 +129,7 @@ struct mfa_ctx {
 
   // d_ws is one scratch buffer shared by the CMVN and feature (feats.hip), Viterbi (viterbi.hip), fMLLR statistics (fmllr.hip), GMM
   // statistics (gmm_acc.hip), feature codec (compress.hip), equal alignment (align_equal.hip), LDA statistics (lda_acc.hip),
-  // MLLT statistics (mllt_acc.hip), tree statistics (tree_acc.hip), speech-activity (vad.hip), diagonal-UBM (ubm.hip), i-vector (ivector.hip) and PLDA (plda.hip) stages: each lays its own workspace over it for the length of one call, and the order of
+  // MLLT statistics (mllt_acc.hip), tree statistics (tree_acc.hip), speech-activity (vad.hip), diagonal-UBM (ubm.hip), i-vector (ivector.hip), PLDA (plda.hip) and clustering (cluster.hip) stages: each lays its own workspace over it for the length of one call, and the order of
   // ctx->stream is all that keeps them apart.
   MfaBuf d_ws;
   MfaBuf d_gen_ws;             // workspace of the general-graph decoder (viterbi_general.hip)
@@ -211,6 +212,12 @@ struct KernelTimer {
 };
 
 int mfa_resolve_timers(mfa_ctx *ctx);
+
+// The reduce-then-scan exclusive scan of int32 values (vad.hip), for the stages that number things: d_G [total + 1] from d_v
+// [total], total > 0; d_bsum [P] and d_base [P + 1] are its scratch, P = mfa_int_scan_blocks(total).  Three launches on
+// ctx->stream.  Not part of the ABI.
+size_t mfa_int_scan_blocks(int64_t total);
+void mfa_int_scan(mfa_ctx *ctx, const int32_t *d_v, int64_t total, int32_t *d_bsum, int32_t *d_base, int32_t *d_G);
 
 // ---- lazy (windowed) scoring: internal interface between the decoder driver (viterbi.hip) and the scoring kernels
 // (gmm_band.hip).  Not part of the ABI.

@@ -16,6 +16,9 @@
 //              to the score matrix straight from the accumulators, and through LDS to put a row's 64 columns on lanes: a
 //              row's best list stays in one register pair per lane across the whole sweep (lane j the j-th best)
 //   merge      plda_merge_kernel, a wavefront per row: the passes' lists in pass order into one, then the outputs
+//   neighbours neighbor_sweep_kernel, the same sweep body (sweep_body<kBits>) with a fourth consumer: a row's 64 columns of a
+//              step against a threshold, one ballot, is a finished word of the neighbour bit matrix that cluster.hip works on;
+//              metric_prepare_kernel gives the same sweep the euclidean and dot metrics (mfa_neighbor_bits_batch)
 // The lists have one strict order (plda_better): whatever the passes are, the merged list is the first k of that order.  No
 // atomics; every sum has a fixed order: two calls on the same input give the same bits.
 #include <algorithm>
@@ -62,6 +65,23 @@ __global__ __launch_bounds__(256) void plda_prepare_kernel(const double *train, 
     Bt[(size_t)k * Nspad + j] = b;
   }
   c[j] = in ? plda_column_const(s_logr, s_quad) : 0.0;
+}
+
+// The prepare step of metrics 1 and 2 (plda_math.hpp), the same layout.
+__global__ __launch_bounds__(256) void metric_prepare_kernel(const double *train, int metric, int Ns, int D, int Dpad, int64_t Nspad,
+                                                             double *At, double *Bt, double *c) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= Nspad) return;
+  const bool in = j < Ns;
+  double sum = 0.0;
+  for (int k = 0; k < Dpad; k++) {
+    const bool kin = in && k < D;
+    const double g = kin ? train[(size_t)j * D + k] : 0.0;
+    At[(size_t)k * Nspad + j] = kin ? metric_term_A(metric) : 0.0;
+    Bt[(size_t)k * Nspad + j] = kin ? metric_term_B(metric, g) : 0.0;
+    if (kin) sum = metric_const_add(metric, sum, g);
+  }
+  c[j] = in ? metric_const(metric, sum) : 0.0;
 }
 
 __global__ __launch_bounds__(256) void plda_pack_kernel(const double *A, const double *B, const double *cin, int Ns, int D, int Dpad,
@@ -136,10 +156,18 @@ __device__ __forceinline__ void sweep_steps(const SweepParams &p, const double *
   }
 }
 
+// The fourth consumer's output: a row's 64 columns of a step as one word of the neighbour matrix.
+struct BitsOut {
+  uint64_t *bits;                  // [Nt][W], W = Nspad / 64
+  double threshold;                // bit set iff score >= threshold (a NaN score: never)
+};
+
 // grid (blocks of 64 rows, passes).  Lane l of a step gives A[i = l & 15][k = l >> 4] = the test row's p_k (squared for the
 // first instruction) and B[k][j = l & 15] = A_jk or B_jk of column j.  Register r of lane l is D[row = (l >> 4) + 4 r][col =
-// l & 15].  The accumulator starts from c_j.
-__global__ __launch_bounds__(256) void plda_sweep_kernel(SweepParams p) {
+// l & 15].  The accumulator starts from c_j.  One body for both kernels below: kBits adds the neighbour words (b is not
+// looked at without it), everything else is the same text, so the instantiation without them is the sweep it always was.
+template <bool kBits>
+__device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &b) {
   __shared__ double tile[4][16][kTileStride];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lc = lane & 15, lk = lane >> 4;
   const int64_t row0 = (int64_t)blockIdx.x * kRowBlock + wave * 16;
@@ -175,7 +203,7 @@ __global__ __launch_bounds__(256) void plda_sweep_kernel(SweepParams p) {
         }
       }
     }
-    if (p.keff == 0) continue;                       // the same for the whole grid
+    if (!kBits && p.keff == 0) continue;             // the same for the whole grid
     __syncthreads();                                 // the previous step's readers are done
     if (wave_has) {
 #pragma unroll
@@ -187,6 +215,18 @@ __global__ __launch_bounds__(256) void plda_sweep_kernel(SweepParams p) {
     __syncthreads();
     if (!wave_has) continue;
     const int64_t col = c0 + lane;
+    if constexpr (kBits) {
+      // a ballot per row is the row's finished word; lane rr keeps row rr's, so that the 16 words leave in one vector store.
+      // A pass owns whole words (its columns are a multiple of 64), and columns from Ns on never set a bit.
+      uint64_t word = 0;
+#pragma unroll
+      for (int rr = 0; rr < 16; rr++) {
+        const uint64_t w = __ballot(col < p.Ns && plda_neighbor(tile[wave][rr][lane], b.threshold));
+        word = lane == rr ? w : word;
+      }
+      if (lane < 16 && row0 + lane < p.Nt) b.bits[(size_t)(row0 + lane) * (size_t)(p.Nspad / kColStep) + (size_t)(c0 / kColStep)] = word;
+      if (p.keff == 0) continue;                     // the same for the whole grid
+    }
 #pragma unroll
     for (int rr = 0; rr < 16; rr++) {
       const int64_t row = row0 + rr;
@@ -206,6 +246,9 @@ __global__ __launch_bounds__(256) void plda_sweep_kernel(SweepParams p) {
     p.part_i[at] = li[rr];
   }
 }
+
+__global__ __launch_bounds__(256) void plda_sweep_kernel(SweepParams p) { sweep_body<false>(p, BitsOut{nullptr, 0.0}); }
+__global__ __launch_bounds__(256) void neighbor_sweep_kernel(SweepParams p, BitsOut b) { sweep_body<true>(p, b); }
 
 // grid: 4 rows a workgroup, a wavefront each: the passes' lists in pass order into one list, then the outputs.
 __global__ __launch_bounds__(256) void plda_merge_kernel(const double *part_s, const int32_t *part_i, int passes, int Nt, int keff, int k,
@@ -258,6 +301,7 @@ int refuse(mfa_ctx *c, const char *who, int rc, int D, int k, long long nt, long
 
 struct Outputs {
   double *scores; int32_t *best_idx; double *best_score; int32_t *knn_idx; double *knn_score;
+  uint64_t *bits = nullptr; double threshold = 0.0;   // the neighbour words and their threshold (the neighbour entries only)
 };
 
 // The checks every scoring entry begins with.  Returns 0: go on; 1: nothing to do; -1: refused.
@@ -266,7 +310,8 @@ int score_checks(mfa_ctx *c, const char *who, int64_t Nt, int64_t Ns, int D, int
   const int rc = plda_check_shape(D, knn ? k : 1, Nt, Ns);
   if (rc) return refuse(c, who, rc, D, k, (long long)Nt, (long long)Ns);
   if (Nt == 0) return 1;
-  if (!o.scores && !o.best_idx && !o.best_score && !knn) return c->fail("%s: every output is NULL", who);
+  if (!o.scores && !o.best_idx && !o.best_score && !knn && !o.bits) return c->fail("%s: every output is NULL", who);
+  if (o.bits && o.threshold != o.threshold) return c->fail("%s: a threshold that is not a number", who);
   if ((o.best_idx != nullptr) != (o.best_score != nullptr) || (o.knn_idx != nullptr) != (o.knn_score != nullptr))
     return c->fail("%s: an index output and its score output come together", who);
   if (!test) return c->fail("%s: NULL test vectors", who);
@@ -311,9 +356,12 @@ int sweep(mfa_ctx *c, const Operands &op, const double *d_test, int64_t Nt, int6
     const SweepParams sp{d_test, (int)Nt, (int)Ns, D, op.Dpad, op.Nspad, op.ws.at<double>(op.o_at), op.ws.at<double>(op.o_bt),
                          op.ws.at<double>(op.o_c), op.cols_per_pass, op.keff, exclude_diag ? 1 : 0, o.scores,
                          op.ws.at<double>(op.o_ps), op.ws.at<int32_t>(op.o_pi)};
-    hipLaunchKernelGGL(plda_sweep_kernel, dim3((unsigned)((Nt + kRowBlock - 1) / kRowBlock), (unsigned)op.passes), dim3(256), 0, c->stream, sp);
+    const dim3 grid((unsigned)((Nt + kRowBlock - 1) / kRowBlock), (unsigned)op.passes);
+    if (o.bits) hipLaunchKernelGGL(neighbor_sweep_kernel, grid, dim3(256), 0, c->stream, sp, BitsOut{o.bits, o.threshold});
+    else hipLaunchKernelGGL(plda_sweep_kernel, grid, dim3(256), 0, c->stream, sp);
     MFA_HIP_CHECK(c, hipGetLastError());
-    MFA_DEBUG_POINT(c, "plda_sweep_kernel rows=%lld cols=%lld D=%d passes=%d k=%d", (long long)Nt, (long long)Ns, D, op.passes, op.keff);
+    MFA_DEBUG_POINT(c, "plda_sweep_kernel rows=%lld cols=%lld D=%d passes=%d k=%d bits=%d", (long long)Nt, (long long)Ns, D, op.passes, op.keff,
+                    o.bits != nullptr);
   }
   if (op.keff == 0) return 0;
   KernelTimer kt(c, MFA_K_PLDA_MERGE);
@@ -321,6 +369,40 @@ int sweep(mfa_ctx *c, const Operands &op, const double *d_test, int64_t Nt, int6
                      op.ws.at<int32_t>(op.o_pi), op.passes, (int)Nt, op.keff, k, o.best_idx, o.best_score, o.knn_idx, o.knn_score);
   MFA_HIP_CHECK(c, hipGetLastError());
   MFA_DEBUG_POINT(c, "plda_merge_kernel rows=%lld passes=%d", (long long)Nt, op.passes);
+  return 0;
+}
+
+// The model's prepare step onto the laid-out operands, and the two refusals that only the data can tell.
+int prepare_plda(mfa_ctx *c, const char *who, const Operands &op, const double *d_train, int64_t n_train, int D, const int32_t *d_train_n,
+                 const double *d_psi) {
+  int32_t *flags = op.ws.at<int32_t>(op.o_flags);
+  if (op.Nspad > 0) {
+    KernelTimer kt(c, MFA_K_PLDA_PREPARE);
+    MFA_HIP_CHECK(c, hipMemsetAsync(flags, 0, 8, c->stream));
+    hipLaunchKernelGGL(plda_prepare_kernel, dim3((unsigned)((op.Nspad + 255) / 256)), dim3(256), 0, c->stream, d_train, d_train_n, d_psi,
+                       (int)n_train, D, op.Dpad, op.Nspad, op.ws.at<double>(op.o_at), op.ws.at<double>(op.o_bt), op.ws.at<double>(op.o_c),
+                       flags);
+    MFA_HIP_CHECK(c, hipGetLastError());
+    MFA_DEBUG_POINT(c, "plda_prepare_kernel cols=%lld D=%d", (long long)n_train, D);
+  }
+  if (op.Nspad > 0) {                                  // the two refusals that only the data can tell
+    int32_t h_flags[2] = {0, 0};
+    MFA_HIP_CHECK(c, hipMemcpyAsync(h_flags, flags, 8, hipMemcpyDeviceToHost, c->stream));
+    MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    if (h_flags[0]) return c->fail("%s: a psi entry that is not positive and finite", who);
+    if (h_flags[1]) return c->fail("%s: a train vector's number of examples below 1", who);
+  }
+  return 0;
+}
+
+// The debug entries' prepare step: the caller's operands into the sweep's layout.
+int pack_operands(mfa_ctx *c, const Operands &op, const double *d_A, const double *d_B, const double *d_c, int64_t n_train, int D) {
+  if (op.Nspad == 0) return 0;
+  KernelTimer kt(c, MFA_K_PLDA_PREPARE);
+  hipLaunchKernelGGL(plda_pack_kernel, dim3((unsigned)((op.Nspad + 255) / 256)), dim3(256), 0, c->stream, d_A, d_B, d_c, (int)n_train, D,
+                     op.Dpad, op.Nspad, op.ws.at<double>(op.o_at), op.ws.at<double>(op.o_bt), op.ws.at<double>(op.o_c));
+  MFA_HIP_CHECK(c, hipGetLastError());
+  MFA_DEBUG_POINT(c, "plda_pack_kernel cols=%lld D=%d", (long long)n_train, D);
   return 0;
 }
 
@@ -361,22 +443,31 @@ MFA_API int mfa_plda_score_batch(mfa_ctx *c, const double *d_test, int64_t n_tes
   if (!d_psi || (n_train > 0 && !d_train)) return c->fail("%s: NULL model or train vectors", who);
   Operands op;
   if (lay_out(c, op, n_test, n_train, D, k, o)) return -1;
-  int32_t *flags = op.ws.at<int32_t>(op.o_flags);
-  if (op.Nspad > 0) {
+  if (prepare_plda(c, who, op, d_train, n_train, D, d_train_n, d_psi)) return -1;
+  return sweep(c, op, d_test, n_test, n_train, D, exclude_diagonal, k, o);
+}
+
+MFA_API int mfa_neighbor_bits_batch(mfa_ctx *c, const double *d_test, int64_t n_test, const double *d_train, int64_t n_train, int32_t D,
+                                    int32_t metric, const int32_t *d_train_n, const double *d_psi, int32_t exclude_diagonal, int32_t k,
+                                    double threshold, double *d_scores, int32_t *d_best_idx, double *d_best_score, int32_t *d_knn_idx,
+                                    double *d_knn_score, uint64_t *d_bits) {
+  MFA_HIP_CHECK(c, hipSetDevice(c->device));
+  const char *who = "neighbour sweep";
+  const Outputs o{d_scores, d_best_idx, d_best_score, d_knn_idx, d_knn_score, d_bits, threshold};
+  if (!plda_metric_ok(metric)) return c->fail("%s: metric %d (0 plda, 1 euclidean, 2 dot)", who, metric);
+  const int st = score_checks(c, who, n_test, n_train, D, k, d_test, o);
+  if (st) return st < 0 ? st : 0;
+  if ((metric == kMetricPlda && !d_psi) || (n_train > 0 && !d_train)) return c->fail("%s: NULL model or train vectors", who);
+  Operands op;
+  if (lay_out(c, op, n_test, n_train, D, k, o)) return -1;
+  if (metric == kMetricPlda) {
+    if (prepare_plda(c, who, op, d_train, n_train, D, d_train_n, d_psi)) return -1;
+  } else if (op.Nspad > 0) {
     KernelTimer kt(c, MFA_K_PLDA_PREPARE);
-    MFA_HIP_CHECK(c, hipMemsetAsync(flags, 0, 8, c->stream));
-    hipLaunchKernelGGL(plda_prepare_kernel, dim3((unsigned)((op.Nspad + 255) / 256)), dim3(256), 0, c->stream, d_train, d_train_n, d_psi,
-                       (int)n_train, D, op.Dpad, op.Nspad, op.ws.at<double>(op.o_at), op.ws.at<double>(op.o_bt), op.ws.at<double>(op.o_c),
-                       flags);
+    hipLaunchKernelGGL(metric_prepare_kernel, dim3((unsigned)((op.Nspad + 255) / 256)), dim3(256), 0, c->stream, d_train, metric, (int)n_train,
+                       D, op.Dpad, op.Nspad, op.ws.at<double>(op.o_at), op.ws.at<double>(op.o_bt), op.ws.at<double>(op.o_c));
     MFA_HIP_CHECK(c, hipGetLastError());
-    MFA_DEBUG_POINT(c, "plda_prepare_kernel cols=%lld D=%d", (long long)n_train, D);
-  }
-  if (op.Nspad > 0) {                                  // the two refusals that only the data can tell
-    int32_t h_flags[2] = {0, 0};
-    MFA_HIP_CHECK(c, hipMemcpyAsync(h_flags, flags, 8, hipMemcpyDeviceToHost, c->stream));
-    MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    if (h_flags[0]) return c->fail("%s: a psi entry that is not positive and finite", who);
-    if (h_flags[1]) return c->fail("%s: a train vector's number of examples below 1", who);
+    MFA_DEBUG_POINT(c, "metric_prepare_kernel cols=%lld D=%d metric=%d", (long long)n_train, D, metric);
   }
   return sweep(c, op, d_test, n_test, n_train, D, exclude_diagonal, k, o);
 }
@@ -392,13 +483,23 @@ MFA_API int mfa_debug_plda_sweep_batch(mfa_ctx *c, const double *d_test, int64_t
   if (n_train > 0 && (!d_A || !d_B || !d_c)) return c->fail("%s: NULL operands", who);
   Operands op;
   if (lay_out(c, op, n_test, n_train, D, k, o)) return -1;
-  if (op.Nspad > 0) {
-    KernelTimer kt(c, MFA_K_PLDA_PREPARE);
-    hipLaunchKernelGGL(plda_pack_kernel, dim3((unsigned)((op.Nspad + 255) / 256)), dim3(256), 0, c->stream, d_A, d_B, d_c, (int)n_train, D,
-                       op.Dpad, op.Nspad, op.ws.at<double>(op.o_at), op.ws.at<double>(op.o_bt), op.ws.at<double>(op.o_c));
-    MFA_HIP_CHECK(c, hipGetLastError());
-    MFA_DEBUG_POINT(c, "plda_pack_kernel cols=%lld D=%d", (long long)n_train, D);
-  }
+  if (pack_operands(c, op, d_A, d_B, d_c, n_train, D)) return -1;
+  return sweep(c, op, d_test, n_test, n_train, D, exclude_diagonal, k, o);
+}
+
+MFA_API int mfa_debug_neighbor_sweep_batch(mfa_ctx *c, const double *d_test, int64_t n_test, int32_t D, const double *d_A, const double *d_B,
+                                           const double *d_c, int64_t n_train, int32_t exclude_diagonal, int32_t k, double threshold,
+                                           double *d_scores, int32_t *d_best_idx, double *d_best_score, int32_t *d_knn_idx,
+                                           double *d_knn_score, uint64_t *d_bits) {
+  MFA_HIP_CHECK(c, hipSetDevice(c->device));
+  const char *who = "neighbour sweep";
+  const Outputs o{d_scores, d_best_idx, d_best_score, d_knn_idx, d_knn_score, d_bits, threshold};
+  const int st = score_checks(c, who, n_test, n_train, D, k, d_test, o);
+  if (st) return st < 0 ? st : 0;
+  if (n_train > 0 && (!d_A || !d_B || !d_c)) return c->fail("%s: NULL operands", who);
+  Operands op;
+  if (lay_out(c, op, n_test, n_train, D, k, o)) return -1;
+  if (pack_operands(c, op, d_A, d_B, d_c, n_train, D)) return -1;
   return sweep(c, op, d_test, n_test, n_train, D, exclude_diagonal, k, o);
 }
 

@@ -14,6 +14,7 @@ namespace {
 
 struct Outputs {
   double *scores; int32_t *best_idx; double *best_score; int32_t *knn_idx; double *knn_score;
+  uint64_t *bits = nullptr; double threshold = 0.0;   // the neighbour words [Nt][ceil(Ns / 64)] and their threshold
 };
 
 // 0 go on, 1 nothing to do, negative: the twin's return code
@@ -22,10 +23,25 @@ int score_checks(int64_t Nt, int64_t Ns, int D, int k, const void *test, const O
   const int rc = plda_check_shape(D, knn ? k : 1, Nt, Ns);
   if (rc) return rc;
   if (Nt == 0) return 1;
-  if (!o.scores && !o.best_idx && !o.best_score && !knn) return -7;
+  if (!o.scores && !o.best_idx && !o.best_score && !knn && !o.bits) return -7;
+  if (o.bits && o.threshold != o.threshold) return -9;
   if ((o.best_idx != nullptr) != (o.best_score != nullptr) || (o.knn_idx != nullptr) != (o.knn_score != nullptr)) return -1;
   if (!test) return -1;
   return 0;
+}
+
+// metrics 1 and 2 (plda_math.hpp)
+void prepare_metric(const double *train, int64_t Ns, int D, int32_t metric, double *A, double *B, double *c) {
+  for (int64_t j = 0; j < Ns; j++) {
+    double sum = 0.0;
+    for (int k = 0; k < D; k++) {
+      const double g = train[(size_t)j * D + k];
+      A[(size_t)j * D + k] = metric_term_A(metric);
+      B[(size_t)j * D + k] = metric_term_B(metric, g);
+      sum = metric_const_add(metric, sum, g);
+    }
+    c[j] = metric_const(metric, sum);
+  }
 }
 
 int prepare(const double *train, int64_t Ns, int D, const int32_t *train_n, const double *psi, double *A, double *B, double *c) {
@@ -53,9 +69,12 @@ void sweep(const double *test, int64_t Nt, int D, const double *A, const double 
   const double ninf = -std::numeric_limits<double>::infinity();
   std::vector<double> ls((size_t)(keff > 0 ? keff : 1));
   std::vector<int32_t> li((size_t)(keff > 0 ? keff : 1));
+  const size_t W = (size_t)((Ns + 63) / 64);
   for (int64_t i = 0; i < Nt; i++) {
     const double *p = test + (size_t)i * D;
     for (int e = 0; e < keff; e++) { ls[e] = ninf; li[e] = -1; }
+    if (o.bits)
+      for (size_t w = 0; w < W; w++) o.bits[(size_t)i * W + w] = 0;
     for (int64_t j = 0; j < Ns; j++) {
       const double *Aj = A + (size_t)j * D, *Bj = B + (size_t)j * D;
       double s = c[j];
@@ -65,6 +84,7 @@ void sweep(const double *test, int64_t Nt, int D, const double *A, const double 
         for (int kk = k0; kk < k1; kk++) s += p[kk] * Bj[kk];
       }
       if (o.scores) o.scores[(size_t)i * Ns + j] = s;
+      if (o.bits && plda_neighbor(s, o.threshold)) o.bits[(size_t)i * W + (size_t)(j >> 6)] |= (uint64_t)1 << (j & 63);
       if (keff == 0 || !plda_candidate(s) || (exclude_diag && j == i)) continue;
       if (!plda_better(s, (int32_t)j, ls[keff - 1], li[keff - 1])) continue;
       int pos = keff - 1;
@@ -138,5 +158,39 @@ extern "C" MFA_API int mfa_debug_plda_score_host(const double *h_test, int64_t n
   const int rc = prepare(h_train, n_train, D, h_train_n, h_psi, A.data(), B.data(), c.data());
   if (rc) return rc;
   sweep(h_test, n_test, D, A.data(), B.data(), c.data(), n_train, exclude_diagonal, k, o);
+  return 0;
+}
+
+// The neighbour entries' twins: mfa_neighbor_bits_batch and mfa_debug_neighbor_sweep_batch in plain loops.  Return codes as the
+// scoring twin's, and -8 an unknown metric, -9 a threshold that is not a number.
+extern "C" MFA_API int mfa_debug_neighbor_bits_host(const double *h_test, int64_t n_test, const double *h_train, int64_t n_train, int32_t D,
+                                                    int32_t metric, const int32_t *h_train_n, const double *h_psi, int32_t exclude_diagonal,
+                                                    int32_t k, double threshold, double *h_scores, int32_t *h_best_idx, double *h_best_score,
+                                                    int32_t *h_knn_idx, double *h_knn_score, uint64_t *h_bits) {
+  const Outputs o{h_scores, h_best_idx, h_best_score, h_knn_idx, h_knn_score, h_bits, threshold};
+  if (!plda_metric_ok(metric)) return -8;
+  const int st = score_checks(n_test, n_train, D, k, h_test, o);
+  if (st) return st < 0 ? st : 0;
+  if ((metric == kMetricPlda && !h_psi) || (n_train > 0 && !h_train)) return -1;
+  std::vector<double> A((size_t)n_train * D), B((size_t)n_train * D), c((size_t)n_train);
+  if (metric == kMetricPlda) {
+    const int rc = prepare(h_train, n_train, D, h_train_n, h_psi, A.data(), B.data(), c.data());
+    if (rc) return rc;
+  } else {
+    prepare_metric(h_train, n_train, D, metric, A.data(), B.data(), c.data());
+  }
+  sweep(h_test, n_test, D, A.data(), B.data(), c.data(), n_train, exclude_diagonal, k, o);
+  return 0;
+}
+
+extern "C" MFA_API int mfa_debug_neighbor_sweep_host(const double *h_test, int64_t n_test, int32_t D, const double *h_A, const double *h_B,
+                                                     const double *h_c, int64_t n_train, int32_t exclude_diagonal, int32_t k,
+                                                     double threshold, double *h_scores, int32_t *h_best_idx, double *h_best_score,
+                                                     int32_t *h_knn_idx, double *h_knn_score, uint64_t *h_bits) {
+  const Outputs o{h_scores, h_best_idx, h_best_score, h_knn_idx, h_knn_score, h_bits, threshold};
+  const int st = score_checks(n_test, n_train, D, k, h_test, o);
+  if (st) return st < 0 ? st : 0;
+  if (n_train > 0 && (!h_A || !h_B || !h_c)) return -1;
+  sweep(h_test, n_test, D, h_A, h_B, h_c, n_train, exclude_diagonal, k, o);
   return 0;
 }

@@ -52,6 +52,20 @@ MFA_ACC_FN double plda_column_const(double sum_logr, double sum_quad) { return 0
 MFA_ACC_FN bool plda_better(double s1, int32_t i1, double s2, int32_t i2) { return s1 > s2 || (s1 == s2 && i1 < i2); }
 MFA_ACC_FN bool plda_candidate(double s) { return s - s == 0.0; }   // finite: not NaN, not an infinity
 
+// The neighbour matrix's bit: a plain comparison on the accumulator value, false for a NaN on either side.
+MFA_ACC_FN bool plda_neighbor(double s, double threshold) { return s >= threshold; }
+
+// The sweep's metrics: each is a prepare step (A, B, c) for the same arithmetic c_j + sum p^2 A + sum p B.
+//   0 plda: plda_column_term / plda_column_const;
+//   1 euclidean: A = -1, B = 2 g, c = -sum_k g^2 (k ascending): the score is -|p - g|^2 expanded;
+//   2 dot: A = 0, B = g, c = 0: the score is p . g (the cosine of rows made unit length beforehand).
+constexpr int kMetricPlda = 0, kMetricEuclidean = 1, kMetricDot = 2;
+MFA_ACC_FN bool plda_metric_ok(int32_t metric) { return metric >= kMetricPlda && metric <= kMetricDot; }
+MFA_ACC_FN double metric_term_A(int32_t metric) { return metric == kMetricEuclidean ? -1.0 : 0.0; }
+MFA_ACC_FN double metric_term_B(int32_t metric, double g) { return metric == kMetricEuclidean ? 2.0 * g : g; }
+MFA_ACC_FN double metric_const_add(int32_t metric, double sum, double g) { return metric == kMetricEuclidean ? sum + g * g : sum; }
+MFA_ACC_FN double metric_const(int32_t metric, double sum) { return metric == kMetricEuclidean ? -sum : 0.0; }
+
 // A row's length-normalisation factor from its sum: norm 0 none (1), 1 simple: sqrt(D / sum u_k^2), 2 the model's:
 // sqrt(D / sum u_k^2 / (psi_k + 1/n)).
 MFA_ACC_FN double plda_norm_term(double u, double psi, double inv_n, int norm) {

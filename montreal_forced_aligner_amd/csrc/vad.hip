@@ -253,6 +253,12 @@ __global__ __launch_bounds__(kThreads) void run_offsets_kernel(const int32_t *G,
 
 }  // namespace
 
+// The scan for the other stages (ctx.hpp): cluster.hip numbers its clusters with it.
+size_t mfa_int_scan_blocks(int64_t total) { return (size_t)((total + kVadScanBlock - 1) / kVadScanBlock); }
+void mfa_int_scan(mfa_ctx *c, const int32_t *d_v, int64_t total, int32_t *d_bsum, int32_t *d_base, int32_t *d_G) {
+  global_scan(c, d_v, total, d_bsum, d_base, d_G);
+}
+
 extern "C" {
 
 MFA_API int32_t mfa_vad_scan_block_frames(void) { return kVadScanBlock; }

@@ -44,7 +44,8 @@ KERNEL_SLOTS = ("mfcc", "cmvn", "feats", "gmm", "viterbi", "resample", "pitch", 
                 "tree_keys", "tree_order", "tree_sums", "vad",
                 "ubm_select", "ubm_post", "ubm_sums", "ubm_reduce",
                 "ivec_prune", "ivec_utt", "ivec_scatter", "ivec_products", "ivec_solve", "ivec_acc",
-                "plda_transform", "plda_prepare", "plda_sweep", "plda_merge")
+                "plda_transform", "plda_prepare", "plda_sweep", "plda_merge",
+                "cluster_symmetrise", "cluster_degree", "cluster_rounds", "cluster_labels")
 
 
 def _out_ptrs(out: Dict[str, Optional[torch.Tensor]]):
@@ -307,6 +308,30 @@ class AlignmentEngine(GraphPacking, FrontEndStages):
         else:
             check(self.ctx, self.lib.mfa_plda_score_batch(self.ctx, _ptr(test), nt, _ptr(train), int(train.shape[0]), D, _ptr(train_n),
                                                           _ptr(psi), int(bool(exclude_diagonal)), int(k), *outs), "mfa_plda_score_batch")
+
+    def _launch_neighbor_bits(self, test, train, metric: int, train_n, psi, exclude_diagonal: bool, k: int, threshold: float, scores, best,
+                              knn, bits, operands=None) -> None:
+        """The sweep for a metric (0 plda, 1 euclidean, 2 dot) with the neighbour words among its outputs (mfa_neighbor_bits_batch);
+        ``operands`` as in ``_launch_plda_score`` (mfa_debug_neighbor_sweep_batch)."""
+        b, q = best or (None, None), knn or (None, None)
+        outs = (_ptr(scores), _ptr(b[0]), _ptr(b[1]), _ptr(q[0]), _ptr(q[1]), _ptr(bits))
+        nt, D = int(test.shape[0]), int(test.shape[1])
+        if operands is not None:
+            A, B, c = operands
+            check(self.ctx, self.lib.mfa_debug_neighbor_sweep_batch(self.ctx, _ptr(test), nt, D, _ptr(A), _ptr(B), _ptr(c), int(c.shape[0]),
+                                                                    int(bool(exclude_diagonal)), int(k), float(threshold), *outs),
+                  "mfa_debug_neighbor_sweep_batch")
+        else:
+            check(self.ctx, self.lib.mfa_neighbor_bits_batch(self.ctx, _ptr(test), nt, _ptr(train), int(train.shape[0]), D, int(metric),
+                                                             _ptr(train_n), _ptr(psi), int(bool(exclude_diagonal)), int(k), float(threshold),
+                                                             *outs), "mfa_neighbor_bits_batch")
+
+    def _launch_dbscan(self, bits, n: int, min_samples: int, labels, core, count):
+        """DBSCAN on the neighbour words ``bits`` [n, ceil(n / 64)], symmetrised in place (mfa_dbscan_from_bits): (clusters, rounds)."""
+        n_clusters, rounds = C.c_int32(0), C.c_int32(0)
+        check(self.ctx, self.lib.mfa_dbscan_from_bits(self.ctx, _ptr(bits), int(n), int(min_samples), _ptr(labels), _ptr(core), _ptr(count),
+                                                      C.byref(n_clusters), C.byref(rounds)), "mfa_dbscan_from_bits")
+        return int(n_clusters.value), int(rounds.value)
 
     def _launch_scan(self, values, d_frame_off, n_utt: int, total: int, scan, totals) -> None:
         check(self.ctx, self.lib.mfa_vad_scan_batch(self.ctx, _ptr(values), _ptr(d_frame_off), n_utt, total, _ptr(scan),

@@ -1849,3 +1849,20 @@ class PldaScorer:
     def classify_speaker(self, ivector, transformed: bool = False):
         idx, score = self.classify_speakers(np.atleast_2d(ivector), transformed)
         return int(idx[0]), float(score[0])
+
+
+# ------------------------------------------------------------------------------------------------ speaker clustering
+from .cluster import ClusterType, DistanceMetric  # noqa: E402  (the reference's montreal_forced_aligner.data enums)
+
+
+def cluster_matrix(ivectors: np.ndarray, cluster_type: ClusterType, metric: DistanceMetric = DistanceMetric.euclidean, strict=True,
+                   no_visuals=False, working_directory=None, **kwargs) -> np.ndarray:
+    """The reference's ``cluster_matrix`` (MFA/diarization/multiprocessing.py) under its signature, on the process's engine:
+    ``kwargs`` carry ``distance_threshold``, ``plda`` (a ``Plda``) and ``min_cluster_size`` as there.  ``ClusterType.dbscan`` only
+    (``cluster.cluster_matrix``); nothing is drawn, so ``no_visuals`` and ``working_directory`` are accepted and unused."""
+    from . import cluster as _cluster
+    known = {k: kwargs.pop(k) for k in ("distance_threshold", "plda", "min_cluster_size", "backend") if k in kwargs}
+    if kwargs:
+        raise TypeError(f"cluster_matrix: unexpected keyword arguments {sorted(kwargs)}")
+    backend = known.get("backend", "device")
+    return _cluster.cluster_matrix(ivectors, cluster_type, metric, strict=strict, engine=get_engine() if backend == "device" else None, **known)

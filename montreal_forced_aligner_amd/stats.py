@@ -1223,3 +1223,194 @@ def plda_knn_host(model, test, train, k: int, train_n=None, exclude_diagonal: bo
 def plda_sweep_host(test, A, B, c, exclude_diagonal: bool = False, k: int = 1, want_scores=True, want_best=True, want_knn=True):
     """``plda_sweep`` on the host twin (mfa_debug_plda_sweep_host)."""
     return _plda_host_call(None, test, None, None, exclude_diagonal, int(k), want_scores, want_best, want_knn, operands=(A, B, c))
+
+
+# ---- the sweep for any metric and its fourth consumer, the neighbour bit matrix; DBSCAN on it (include/mfa_hip.h "Neighbour bits",
+# "Clustering") ------------------------------------------------------------------------------------------------------------------
+METRIC_CODES = {"plda": 0, "euclidean": 1, "dot": 2, "cosine": 2}      # cosine: the dot metric on rows made unit length here
+NEIGHBOR_BITS_BYTES = 4 << 30                                # the largest bit matrix ``neighbor_bits`` hands out
+_PLDA_TWIN_CODES.update({-8: "an unknown metric", -9: "a threshold that is not a number"})
+_CLUSTER_TWIN_CODES = {-2: "a number of points outside [0, 2^31)", -3: "min_samples below 1"}
+
+
+def metric_code(metric) -> int:
+    name = getattr(metric, "name", metric)
+    if name not in METRIC_CODES:
+        raise _lib.MfaHipError(f"metric {metric!r}: one of {sorted(METRIC_CODES)}")
+    return METRIC_CODES[name]
+
+
+def score_threshold(metric, eps: float) -> float:
+    """The sweep's threshold for "distance <= eps": plda −eps (the distance is −LLR), euclidean −eps² (eps < 0: no pair passes),
+    cosine 1 − eps."""
+    code, eps = metric_code(metric), float(eps)
+    if code == 0:
+        return -eps
+    if code == 1:
+        return float("inf") if eps < 0 else -(eps * eps)
+    return 1.0 - eps
+
+
+def score_to_distance(metric, scores):
+    """Distances from the sweep's scores (numpy): −score, sqrt(−score) floored at 0, 1 − score."""
+    code, s = metric_code(metric), np.asarray(scores, dtype=np.float64)
+    if code == 0:
+        return -s
+    return np.sqrt(np.maximum(-s, 0.0)) if code == 1 else 1.0 - s
+
+
+def _unit_rows(x):
+    """Rows made unit length in float64 (torch or numpy); a zero row becomes NaN and is nobody's neighbour."""
+    if isinstance(x, torch.Tensor):
+        return x / torch.sqrt((x * x).sum(dim=1, keepdim=True))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return x / np.sqrt((x * x).sum(axis=1, keepdims=True))
+
+
+def _metric_dim(code: int, model, x) -> int:
+    if code == 0:
+        if model is None:
+            raise _lib.MfaHipError("the plda metric needs the model")
+        return model.dim
+    return int(np.shape(x)[-1])
+
+
+def metric_sweep(engine, metric, test, train, threshold=None, model=None, train_n=None, exclude_diagonal: bool = False, k: int = 1,
+                 want_scores=False, want_best=False, want_knn=False, want_bits=True, operands=None):
+    """One sweep on the device for ``metric`` ("plda", "euclidean", "cosine", or "dot": cosine's sweep on the rows as they are;
+    mfa_neighbor_bits_batch): (scores, best, knn, bits), each
+    None unless asked for.  ``threshold`` is on the score, as the library takes it (``score_threshold``); ``bits`` is int64
+    [n_test, ceil(n_train / 64)] on the device, the words' bits as they are.  ``operands``: the debug entry's (A, B, c)."""
+    if operands is None:
+        code = metric_code(metric)
+        D = _metric_dim(code, model, test)
+        test, train = _plda_vectors(engine, test, D, "neighbour sweep"), _plda_vectors(engine, train, D, "neighbour sweep")
+        if getattr(metric, "name", metric) == "cosine":
+            test, train = _unit_rows(test), _unit_rows(train)
+        ns = int(train.shape[0])
+        train_n = _plda_counts(engine, train_n, ns, "neighbour sweep") if code == 0 else None
+        psi = _plda_device_model(engine, model)[2] if code == 0 else None
+    else:
+        code, psi, train, train_n = 0, None, None, None
+        operands = tuple(torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(engine.device) if not isinstance(a, torch.Tensor) else a
+                         for a in operands)
+        test = _plda_vectors(engine, test, int(operands[0].shape[1]), "neighbour sweep")
+        ns = int(operands[2].shape[0])
+    dev, nt = engine.device, int(test.shape[0])
+    if want_bits and threshold is None:
+        raise _lib.MfaHipError("neighbour sweep: the bits need a threshold")
+    scores = torch.empty((nt, ns), dtype=torch.float64, device=dev) if want_scores else None
+    best = (torch.empty(nt, dtype=torch.int32, device=dev), torch.empty(nt, dtype=torch.float64, device=dev)) if want_best else None
+    knn = (torch.empty((nt, k), dtype=torch.int32, device=dev), torch.empty((nt, k), dtype=torch.float64, device=dev)) if want_knn else None
+    bits = torch.empty((nt, (ns + 63) // 64), dtype=torch.int64, device=dev) if want_bits else None
+    if ns == 0 and not (want_scores or want_best or want_knn):
+        return None, None, None, bits                  # no train vectors: rows of no words, nothing to ask the library for
+    engine._launch_neighbor_bits(test, train, code, train_n, psi, exclude_diagonal, int(k), 0.0 if threshold is None else float(threshold),
+                                 scores, best, knn, bits, operands)
+    return scores, best, knn, bits
+
+
+def metric_sweep_host(metric, test, train, threshold=None, model=None, train_n=None, exclude_diagonal: bool = False, k: int = 1,
+                      want_scores=False, want_best=False, want_knn=False, want_bits=True, operands=None):
+    """``metric_sweep`` on the host twins (mfa_debug_neighbor_bits_host / mfa_debug_neighbor_sweep_host): numpy in and out, ``bits``
+    uint64."""
+    test = np.ascontiguousarray(np.atleast_2d(test), dtype=np.float64)
+    nt, D = int(test.shape[0]), int(test.shape[1])
+    p = lambda a: None if a is None else a.ctypes.data
+    if operands is None:
+        code = metric_code(metric)
+        train = np.ascontiguousarray(np.atleast_2d(train), dtype=np.float64)
+        if _metric_dim(code, model, test) != D or (train.shape[0] and train.shape[1] != D):
+            raise _lib.MfaHipError(f"neighbour sweep: vectors {test.shape} and {train.shape} do not go together")
+        if getattr(metric, "name", metric) == "cosine":
+            test, train = np.ascontiguousarray(_unit_rows(test)), np.ascontiguousarray(_unit_rows(train))
+        ns = int(train.shape[0])
+        n = None if train_n is None or code != 0 else np.ascontiguousarray(train_n, dtype=np.int32)
+        if n is not None and n.shape != (ns,):
+            raise _lib.MfaHipError("neighbour sweep: one number of examples per train vector")
+        psi = np.ascontiguousarray(model.psi, dtype=np.float64) if code == 0 else None
+    else:
+        A, B, c = (np.ascontiguousarray(a, dtype=np.float64) for a in operands)
+        ns = int(c.shape[0])
+    if want_bits and threshold is None:
+        raise _lib.MfaHipError("neighbour sweep: the bits need a threshold")
+    thr = 0.0 if threshold is None else float(threshold)
+    scores = np.empty((nt, ns)) if want_scores else None
+    bi, bs = (np.empty(nt, np.int32), np.empty(nt)) if want_best else (None, None)
+    ki, ks = (np.empty((nt, k), np.int32), np.empty((nt, k))) if want_knn else (None, None)
+    bits = np.zeros((nt, (ns + 63) // 64), dtype=np.uint64) if want_bits else None
+    outs = (p(scores), p(bi), p(bs), p(ki), p(ks), p(bits))
+    if ns == 0 and not (want_scores or want_best or want_knn):
+        return None, None, None, bits
+    if operands is None:
+        _plda_twin(_lib.lib().mfa_debug_neighbor_bits_host(p(test), nt, p(train), ns, D, code, p(n), p(psi), int(bool(exclude_diagonal)),
+                                                           int(k), thr, *outs), "mfa_debug_neighbor_bits_host")
+    else:
+        _plda_twin(_lib.lib().mfa_debug_neighbor_sweep_host(p(test), nt, D, p(A), p(B), p(c), ns, int(bool(exclude_diagonal)), int(k), thr,
+                                                            *outs), "mfa_debug_neighbor_sweep_host")
+    return scores, (bi, bs) if want_best else None, (ki, ks) if want_knn else None, bits
+
+
+def _bits_size_check(nt: int, ns: int, max_bytes: int) -> None:
+    size = nt * ((ns + 63) // 64) * 8
+    if size > max_bytes:
+        raise _lib.MfaHipError(f"neighbor_bits: a bit matrix of {nt} x {ns} pairs ({size} bytes) exceeds {max_bytes} bytes")
+
+
+def neighbor_bits(engine, metric, test, train, eps: float, model=None, train_n=None, max_bytes: int = NEIGHBOR_BITS_BYTES) -> torch.Tensor:
+    """The ε-neighbourhoods as a bit matrix: int64 words [n_test, ceil(n_train / 64)] on the device, bit j & 63 of word j >> 6 of row i
+    set iff the distance of test i to train j is at most ``eps`` in ``metric`` (plda: −LLR, vectors in the model's space).  N²/8
+    bytes where the score matrix takes 8 N²; one above ``max_bytes`` is refused."""
+    _bits_size_check(int(np.shape(test)[0]), int(np.shape(train)[0]), max_bytes)
+    return metric_sweep(engine, metric, test, train, score_threshold(metric, eps), model, train_n)[3]
+
+
+def neighbor_bits_host(metric, test, train, eps: float, model=None, train_n=None, max_bytes: int = NEIGHBOR_BITS_BYTES) -> np.ndarray:
+    _bits_size_check(int(np.shape(test)[0]), int(np.shape(train)[0]), max_bytes)
+    return metric_sweep_host(metric, test, train, score_threshold(metric, eps), model, train_n)[3]
+
+
+def knn(engine, metric, test, train, k: int, model=None, train_n=None, exclude_diagonal: bool = False):
+    """``plda_knn`` for any metric: (indices int32 [n_test, k], scores float64 [n_test, k]) on the device, the nearest first; the
+    scores are the sweep's (``score_to_distance`` makes distances of them)."""
+    return metric_sweep(engine, metric, test, train, None, model, train_n, exclude_diagonal, int(k), want_knn=True, want_bits=False)[2]
+
+
+def knn_host(metric, test, train, k: int, model=None, train_n=None, exclude_diagonal: bool = False):
+    return metric_sweep_host(metric, test, train, None, model, train_n, exclude_diagonal, int(k), want_knn=True, want_bits=False)[2]
+
+
+def _square_bits(bits, n) -> int:
+    n = int(bits.shape[0]) if n is None else int(n)
+    if bits.ndim != 2 or tuple(bits.shape) != (n, (n + 63) // 64):
+        raise _lib.MfaHipError(f"dbscan_from_bits: words {tuple(bits.shape)} for {n} points (a square matrix of [n, ceil(n / 64)] words)")
+    return n
+
+
+def dbscan_from_bits(engine, bits, min_samples: int, n=None):
+    """DBSCAN on a square neighbour matrix (mfa_dbscan_from_bits): dict(labels, core, count: int32 [n] on the device, n_clusters, rounds,
+    bits: the symmetrised matrix).  A tensor on the engine's device is symmetrised in place; anything else is copied first."""
+    if isinstance(bits, torch.Tensor) and bits.dtype == torch.int64 and bits.device == engine.device and bits.is_contiguous():
+        d = bits
+    else:
+        a = bits.cpu().numpy() if isinstance(bits, torch.Tensor) else np.asarray(bits)
+        d = torch.from_numpy(np.ascontiguousarray(a).astype(np.uint64, copy=False).view(np.int64).copy()).to(engine.device)
+    n = _square_bits(d, n)
+    labels, core, count = (torch.empty(n, dtype=torch.int32, device=engine.device) for _ in range(3))
+    n_clusters, rounds = engine._launch_dbscan(d, n, int(min_samples), labels, core, count)
+    return dict(labels=labels, core=core, count=count, n_clusters=n_clusters, rounds=rounds, bits=d)
+
+
+def dbscan_from_bits_host(bits, min_samples: int, n=None):
+    """``dbscan_from_bits`` on the host twin: numpy arrays, the input left alone."""
+    import ctypes as C
+    a = bits.cpu().numpy() if isinstance(bits, torch.Tensor) else np.asarray(bits)
+    h = np.ascontiguousarray(a).view(np.uint64).copy() if a.dtype == np.int64 else np.ascontiguousarray(a, dtype=np.uint64).copy()
+    n = _square_bits(h, n)
+    labels, core, count = (np.empty(n, np.int32) for _ in range(3))
+    n_clusters = C.c_int32(0)
+    rc = _lib.lib().mfa_debug_dbscan_from_bits_host(h.ctypes.data, n, int(min_samples), labels.ctypes.data, core.ctypes.data, count.ctypes.data,
+                                                   C.byref(n_clusters))
+    if rc != 0:
+        raise _lib.MfaHipError(f"mfa_debug_dbscan_from_bits_host: {_CLUSTER_TWIN_CODES.get(rc, 'bad arguments')}")
+    return dict(labels=labels, core=core, count=count, n_clusters=int(n_clusters.value), bits=h)
