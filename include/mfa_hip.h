@@ -1201,6 +1201,42 @@ MFA_API int mfa_dbscan_from_bits(mfa_ctx *ctx, uint64_t *d_bits, int64_t N, int3
 MFA_API int mfa_debug_dbscan_from_bits_host(uint64_t *h_bits, int64_t N, int32_t min_samples, int32_t *h_labels, int32_t *h_core,
                                             int32_t *h_count, int32_t *h_n_clusters);
 
+/* ---- HDBSCAN: the part of the reference's ClusterType.hdbscan that costs O(N^2 D) — every point's core distance and the
+ *      minimum spanning tree of the mutual-reachability graph — on N points, with no N x N array stored.  The cluster tree
+ *      on the N - 1 edges is host work (montreal_forced_aligner_amd/hdbscan.py).  Shared arithmetic: csrc/hdbscan_math.hpp.
+ * The pair form: point i gets a row y_i (D doubles) and a scalar q_i, and the score of the unordered pair is
+ *   v(i, j) = (q_i + q_j) + w * sum_k y_ik y_jk   (k ascending, the sweep's sum with test = y, A = 0, B = y, c = 0)
+ * the same bits for (i, j) and (j, i); larger is nearer.  metric (the codes of mfa_neighbor_bits_batch):
+ *   0 plda, one example a vector: y_k = x_k sqrt(b_k), q = c/2 - 1/2 sum a_k x_k^2, w = 1, with a_k, b_k, c the prepare
+ *     step's coefficients at n = 1: v is the log-likelihood ratio; 1 euclidean: y = x, q = -sum x^2, w = 2: v = -|x_i - x_j|^2;
+ *   2 dot: y = x, q = 0, w = 1.
+ * mfa_hdbscan_core_batch: d_y [N][D], d_q [N] from d_x [N][D] (d_psi [D] for metric 0 only), and d_core [N]: the k-th best
+ *   v(i, j) over j != i with v finite (k = min_samples - 1: scikit-learn's count includes the point itself), the order of the
+ *   k-nearest lists; -inf for a point with fewer than k finite scores; k = 0: +inf.  d_v [N][N] or NULL: every v as the
+ *   consumer sees it (tests).  d_x and d_y may be the same array for metrics 1 and 2.
+ * mfa_hdbscan_mst_batch: from d_y, d_q, d_core (metric gives w) the spanning forest of the graph whose edges are the pairs
+ *   with v finite, weighted m = min(v, core_i, core_j), under the strict order "larger m, then smaller min(i, j), then
+ *   smaller max(i, j)": Boruvka rounds, each one sweep; *h_n_edges edges (N - 1 when the graph is connected) in d_edge_lo <
+ *   d_edge_hi, d_edge_score [N - 1], in the order the rounds found them; *h_rounds rounds (at most 40: each at least halves
+ *   the components that can still be joined).  The edge set is unique: the same bits every run and for every
+ *   MFA_PLDA_PASS_COLS.  Vectors that are not finite are not refused: such a point has no finite score and no edge.
+ *   The call waits for the device once a round.
+ * Limits (refused with a message, the context stays usable): D outside [1, 1024]; k outside [0, 64]; 2^31 points or more; a
+ * metric outside [0, 2]; a psi entry that is not positive and finite (metric 0); a NULL array or result.  N == 0 writes
+ * nothing.  Timing slots 36 (prepare), 37 (sweeps), 38 (merges), 41 (the rounds' component work).
+ * The host twins: the same contracts in plain loops; the tree twin is Kruskal under the same order, on h_v [N][N] when it
+ * is given (then h_y, h_q are not looked at), and the core twin reads its scores from h_v_in [N][N] when that is given.
+ * Return 0, -1 a NULL array or a negative count, -2 D, -3 k, -4 psi, -5 N, -8 an unknown metric. */
+MFA_API int mfa_hdbscan_core_batch(mfa_ctx *ctx, const double *d_x, int64_t N, int32_t D, int32_t metric, const double *d_psi, int32_t k,
+                                   double *d_y, double *d_q, double *d_core, double *d_v);
+MFA_API int mfa_hdbscan_mst_batch(mfa_ctx *ctx, const double *d_y, const double *d_q, const double *d_core, int64_t N, int32_t D,
+                                  int32_t metric, int32_t *d_edge_lo, int32_t *d_edge_hi, double *d_edge_score, int32_t *h_n_edges,
+                                  int32_t *h_rounds);
+MFA_API int mfa_debug_hdbscan_core_host(const double *h_x, int64_t N, int32_t D, int32_t metric, const double *h_psi, int32_t k,
+                                        double *h_y, double *h_q, double *h_core, double *h_v, const double *h_v_in);
+MFA_API int mfa_debug_hdbscan_mst_host(const double *h_y, const double *h_q, const double *h_core, const double *h_v, int64_t N, int32_t D,
+                                       int32_t metric, int32_t *h_edge_lo, int32_t *h_edge_hi, double *h_edge_score, int32_t *h_n_edges);
+
 #ifdef __cplusplus
 }
 #endif

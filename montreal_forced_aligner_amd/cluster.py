@@ -171,5 +171,63 @@ def cluster_utterances(utterance_ids: Sequence, ivectors, cluster_type=ClusterTy
     return dict(zip(utterance_ids, speaker_names(cluster_matrix(x, cluster_type, **kwargs))))
 
 
-__all__ = ["ClusterType", "DistanceMetric", "NoKneeError", "cluster_matrix", "cluster_utterances", "distance_threshold", "knee_index",
-           "kth_neighbor_distances", "speaker_names"]
+def hdbscan_matrix(ivectors, metric="cosine", plda=None, distance_threshold=None, min_cluster_size: int = 15, min_samples=None,
+                   strict: bool = True, backend: str = "device", engine=None, edges=None) -> np.ndarray:
+    """What the reference's ``cluster_matrix`` asks of HDBSCAN for ``ClusterType.hdbscan``: the label of every row of ``ivectors`` (−1:
+    noise), clusters numbered by their smallest member.  ``min_samples`` defaults to ``max(5, min_cluster_size // 4)`` and
+    ``cluster_selection_epsilon`` is ``distance_threshold`` or its estimate at ``min_cluster_size``, the reference's rules; cosine is
+    euclidean on unit rows, as there, and so is its threshold.  The device computes the core scores and the minimum spanning tree
+    of the mutual-reachability graph (``stats.core_scores``, ``stats.mreach_mst``) with no N × N array; the cluster tree on the
+    N − 1 edges is host work (``hdbscan.cluster_tree_labels``).  For the plda metric the vectors are already in the model's space and
+    the distance is −LLR, measured in the cluster tree from the spanning tree's smallest edge (ε is on the −LLR scale).  ``edges``: a spanning tree (lo, hi, score) to use in place of the sweep's (tests: the host path on the
+    device's own edges).  ``cluster_matrix(…, ClusterType.hdbscan)`` does not route here yet."""
+    from . import hdbscan as _hdbscan
+    metric = _metric(metric)
+    _check_backend(backend)
+    x = _vectors(ivectors, metric, plda)
+    if int(min_cluster_size) < 2:
+        raise ValueError(f"min_cluster_size {min_cluster_size}: 2 or more")
+    if min_samples is None:
+        min_samples = max(5, int(min_cluster_size) // 4)
+    k = int(min_samples) - 1
+    if k < 0 or k > MAX_NEIGHBOURS:
+        raise ValueError(f"min_samples {min_samples}: 1 to {MAX_NEIGHBOURS + 1} (the core distance keeps at most {MAX_NEIGHBOURS} "
+                         "neighbours a point)")
+    _, unit, dist_metric = stats.pair_metric(metric.value)
+    if unit:
+        x = np.ascontiguousarray(stats._unit_rows(x))
+    fit_metric = DistanceMetric(dist_metric)
+    eps = distance_threshold if distance_threshold is not None else _estimate_threshold(x, fit_metric, min_cluster_size, plda, backend, engine)
+    n = x.shape[0]
+    if edges is None:
+        if backend == "host":
+            pf = stats.core_scores_host(dist_metric, x, k, _model(plda))
+            edges = stats.mreach_mst_host(dist_metric, pf["y"], pf["q"], pf["core"])
+        else:
+            pf = stats.core_scores(_engine(engine), dist_metric, x, k, _model(plda))
+            edges = stats.mreach_mst(_engine(engine), dist_metric, pf["y"], pf["q"], pf["core"])
+    lo, hi, score = (edges["lo"], edges["hi"], edges["score"]) if isinstance(edges, dict) else edges
+    dist, eps = stats.score_to_distance(dist_metric, score), float(eps)
+    if metric is DistanceMetric.plda and np.isfinite(dist).any():
+        # −LLR is a signed distance (on a corpus whose speakers the model knows every pair's can be negative), and λ = 1 / d needs
+        # one that is not: the tree's distances, and ε with them, are measured from its smallest edge.  The hierarchy does not
+        # depend on the zero point; the λ do, and this choice makes the labels a function of LLR differences alone.
+        d0 = float(dist[np.isfinite(dist)].min())
+        dist, eps = dist - d0, eps - d0
+    labels = _hdbscan.cluster_tree_labels(n, lo, hi, dist, int(min_cluster_size), eps)
+    if strict and np.unique(labels).shape[0] == 1:
+        raise ValueError("Only found one cluster, please adjust cluster parameters to generate more clusters.")
+    return labels.astype(np.int64)
+
+
+def hdbscan_utterances(utterance_ids: Sequence, ivectors, **kwargs) -> Dict:
+    """{utterance: speaker name} from ``hdbscan_matrix``; ``kwargs`` go to it."""
+    utterance_ids = list(utterance_ids)
+    x = np.atleast_2d(ivectors)
+    if len(utterance_ids) != x.shape[0]:
+        raise ValueError(f"{len(utterance_ids)} utterances for {x.shape[0]} vectors")
+    return dict(zip(utterance_ids, speaker_names(hdbscan_matrix(x, **kwargs))))
+
+
+__all__ = ["ClusterType", "DistanceMetric", "NoKneeError", "cluster_matrix", "cluster_utterances", "distance_threshold", "hdbscan_matrix",
+           "hdbscan_utterances", "knee_index", "kth_neighbor_distances", "speaker_names"]

@@ -129,7 +129,7 @@ struct mfa_ctx {
 
   // d_ws is one scratch buffer shared by the CMVN and feature (feats.hip), Viterbi (viterbi.hip), fMLLR statistics (fmllr.hip), GMM
   // statistics (gmm_acc.hip), feature codec (compress.hip), equal alignment (align_equal.hip), LDA statistics (lda_acc.hip),
-  // MLLT statistics (mllt_acc.hip), tree statistics (tree_acc.hip), speech-activity (vad.hip), diagonal-UBM (ubm.hip), i-vector (ivector.hip), PLDA (plda.hip) and clustering (cluster.hip) stages: each lays its own workspace over it for the length of one call, and the order of
+  // MLLT statistics (mllt_acc.hip), tree statistics (tree_acc.hip), speech-activity (vad.hip), diagonal-UBM (ubm.hip), i-vector (ivector.hip), PLDA (plda.hip), clustering (cluster.hip) and HDBSCAN (hdbscan.hip) stages: each lays its own workspace over it for the length of one call, and the order of
   // ctx->stream is all that keeps them apart.
   MfaBuf d_ws;
   MfaBuf d_gen_ws;             // workspace of the general-graph decoder (viterbi_general.hip)

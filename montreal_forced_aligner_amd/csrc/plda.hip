@@ -26,6 +26,8 @@
 #include "acc_segments.hpp"
 #include "ctx.hpp"
 #include "f64_gemm.hpp"
+#include "hdbscan_math.hpp"
+#include "pair_sweep.hpp"
 #include "plda_math.hpp"
 
 namespace {
@@ -162,12 +164,29 @@ struct BitsOut {
   double threshold;                // bit set iff score >= threshold (a NaN score: never)
 };
 
+// The pair consumers' inputs (hdbscan_math.hpp): the epilogue's q and w, and per mode: the core consumer's optional score
+// matrix; the edge consumer's core scores, components and per-pass outputs.
+struct PairIn {
+  const double *q; double w;       // [N]
+  double *v;                       // [N][N] or NULL
+  const double *core; const int32_t *comp;   // [N], [N]
+  double *part_m; int32_t *part_j; // [passes][N]
+};
+
+constexpr int kSweepPlain = 0, kSweepBits = 1, kSweepCore = 2, kSweepEdge = 3;
+
 // grid (blocks of 64 rows, passes).  Lane l of a step gives A[i = l & 15][k = l >> 4] = the test row's p_k (squared for the
 // first instruction) and B[k][j = l & 15] = A_jk or B_jk of column j.  Register r of lane l is D[row = (l >> 4) + 4 r][col =
 // l & 15].  The accumulator starts from c_j.  One body for both kernels below: kBits adds the neighbour words (b is not
 // looked at without it), everything else is the same text, so the instantiation without them is the sweep it always was.
-template <bool kBits>
-__device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &b) {
+// The pair modes (kSweepCore, kSweepEdge; pr is not looked at without them) run the same sum with A = 0, c = 0 on a square
+// problem and finish the score in the consumer, after the tile is staged: s = (q_row + q_col) + w · sum, the same bits for
+// (i, j) and (j, i).  A row's q, core score and component sit in lane (row & 15) and are broadcast per row; a column's are
+// read once per 64-column step.  Core: the k-nearest lists on s, diagonal excluded.  Edge: one running best per lane per row
+// under edge_better (ls, li: the score and the far end), one butterfly per row at the end of the pass.
+template <int kMode>
+__device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &b, const PairIn &pr) {
+  constexpr bool kBits = kMode == kSweepBits, kPair = kMode == kSweepCore || kMode == kSweepEdge;
   __shared__ double tile[4][16][kTileStride];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lc = lane & 15, lk = lane >> 4;
   const int64_t row0 = (int64_t)blockIdx.x * kRowBlock + wave * 16;
@@ -180,6 +199,12 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &
   const int64_t arow = row0 + lc;
   const bool arow_in = arow < p.Nt;
   const double *Ar = p.test + (size_t)(arow_in ? arow : 0) * p.D;
+  double q_l = 0.0, core_l = 0.0;                    // of row row0 + (lane & 15)
+  int32_t comp_l = -1;
+  if constexpr (kPair) {
+    q_l = arow_in ? pr.q[arow] : 0.0;
+    if constexpr (kMode == kSweepEdge) { core_l = arow_in ? pr.core[arow] : 0.0; comp_l = arow_in ? pr.comp[arow] : -1; }
+  }
   for (int64_t c0 = c_begin; c0 < c_end; c0 += kColStep) {
     double4_t acc[4];
     if (wave_has) {
@@ -203,7 +228,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &
         }
       }
     }
-    if (!kBits && p.keff == 0) continue;             // the same for the whole grid
+    if (!kBits && !kPair && p.keff == 0) continue;   // the same for the whole grid
     __syncthreads();                                 // the previous step's readers are done
     if (wave_has) {
 #pragma unroll
@@ -227,6 +252,32 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &
       if (lane < 16 && row0 + lane < p.Nt) b.bits[(size_t)(row0 + lane) * (size_t)(p.Nspad / kColStep) + (size_t)(c0 / kColStep)] = word;
       if (p.keff == 0) continue;                     // the same for the whole grid
     }
+    if constexpr (kPair) {
+      const bool cin = col < p.Ns;
+      const double qc = cin ? pr.q[col] : 0.0;
+      double corec = 0.0;
+      int32_t compc = -1;
+      if constexpr (kMode == kSweepEdge) { corec = cin ? pr.core[col] : 0.0; compc = cin ? pr.comp[col] : -1; }
+#pragma unroll
+      for (int rr = 0; rr < 16; rr++) {
+        const int64_t row = row0 + rr;
+        if (row >= p.Nt) continue;                   // the same for the whole wavefront
+        const double s = pair_score(__shfl(q_l, rr), qc, pr.w, tile[wave][rr][lane]);
+        const bool cand = cin && plda_candidate(s) && col != row;
+        if constexpr (kMode == kSweepCore) {
+          if (pr.v && cin) pr.v[(size_t)row * p.Ns + col] = s;
+          if (p.keff > 0) plda_insert(ls[rr], li[rr], s, (int32_t)col, cand, p.keff, lane);
+        } else {
+          const double m = mreach_score(s, __shfl(core_l, rr), corec);
+          const int32_t compr = __shfl(comp_l, rr);  // every lane takes part: not inside the condition
+          if (cand && compc != compr && (li[rr] < 0 || row_edge_better((int32_t)row, m, (int32_t)col, ls[rr], li[rr]))) {
+            ls[rr] = m;
+            li[rr] = (int32_t)col;
+          }
+        }
+      }
+      continue;
+    }
 #pragma unroll
     for (int rr = 0; rr < 16; rr++) {
       const int64_t row = row0 + rr;
@@ -235,6 +286,24 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &
       const bool cand = col < p.Ns && plda_candidate(s) && !(p.exclude_diag && col == row);
       plda_insert(ls[rr], li[rr], s, (int32_t)col, cand, p.keff, lane);
     }
+  }
+  if constexpr (kMode == kSweepEdge) {
+    if (!wave_has) return;
+#pragma unroll
+    for (int rr = 0; rr < 16; rr++) {
+      const int64_t row = row0 + rr;
+      if (row >= p.Nt) continue;                     // the same for the whole wavefront
+      double m = ls[rr];
+      int32_t j = li[rr];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {             // a strict total order: every lane ends with the same best
+        const double om = __shfl_xor(m, o);
+        const int32_t oj = __shfl_xor(j, o);
+        if (oj >= 0 && (j < 0 || row_edge_better((int32_t)row, om, oj, m, j))) { m = om; j = oj; }
+      }
+      if (lane == 0) { pr.part_m[(size_t)blockIdx.y * p.Nt + row] = m; pr.part_j[(size_t)blockIdx.y * p.Nt + row] = j; }
+    }
+    return;
   }
   if (p.keff == 0 || !wave_has) return;
 #pragma unroll
@@ -247,8 +316,44 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &
   }
 }
 
-__global__ __launch_bounds__(256) void plda_sweep_kernel(SweepParams p) { sweep_body<false>(p, BitsOut{nullptr, 0.0}); }
-__global__ __launch_bounds__(256) void neighbor_sweep_kernel(SweepParams p, BitsOut b) { sweep_body<true>(p, b); }
+__global__ __launch_bounds__(256) void plda_sweep_kernel(SweepParams p) { sweep_body<kSweepPlain>(p, BitsOut{nullptr, 0.0}, PairIn{}); }
+__global__ __launch_bounds__(256) void neighbor_sweep_kernel(SweepParams p, BitsOut b) { sweep_body<kSweepBits>(p, b, PairIn{}); }
+__global__ __launch_bounds__(256) void pair_core_sweep_kernel(SweepParams p, PairIn pr) { sweep_body<kSweepCore>(p, BitsOut{nullptr, 0.0}, pr); }
+__global__ __launch_bounds__(256) void pair_edge_sweep_kernel(SweepParams p, PairIn pr) { sweep_body<kSweepEdge>(p, BitsOut{nullptr, 0.0}, pr); }
+
+// The pair form's operands, a thread per padded column j: A = 0, B = y as [k][column], c = 0.
+__global__ __launch_bounds__(256) void pair_pack_kernel(const double *y, int Ns, int D, int Dpad, int64_t Nspad, double *At, double *Bt, double *c) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= Nspad) return;
+  const bool in = j < Ns;
+  for (int k = 0; k < Dpad; k++) {
+    At[(size_t)k * Nspad + j] = 0.0;
+    Bt[(size_t)k * Nspad + j] = in && k < D ? y[(size_t)j * D + k] : 0.0;
+  }
+  c[j] = 0.0;
+}
+
+// A thread per point: the core score is the k-th entry of the merged list (−inf where the list is short); k = 0: +inf.
+__global__ __launch_bounds__(256) void pair_core_kernel(const double *knn_score, int64_t N, int k, double *core) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < N) core[i] = k > 0 ? knn_score[(size_t)i * k + (k - 1)] : INFINITY;
+}
+
+// A thread per row: the passes' bests in pass order into one.
+__global__ __launch_bounds__(256) void pair_edge_merge_kernel(const double *part_m, const int32_t *part_j, int passes, int64_t N, double *row_m,
+                                                              int32_t *row_j) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  double m = -INFINITY;
+  int32_t j = -1;
+  for (int ps = 0; ps < passes; ps++) {
+    const double om = part_m[(size_t)ps * N + i];
+    const int32_t oj = part_j[(size_t)ps * N + i];
+    if (oj >= 0 && (j < 0 || row_edge_better((int32_t)i, om, oj, m, j))) { m = om; j = oj; }
+  }
+  row_m[i] = m;
+  row_j[i] = j;
+}
 
 // grid: 4 rows a workgroup, a wavefront each: the passes' lists in pass order into one list, then the outputs.
 __global__ __launch_bounds__(256) void plda_merge_kernel(const double *part_s, const int32_t *part_i, int passes, int Nt, int keff, int k,
@@ -325,24 +430,30 @@ struct Operands {
   int64_t Nspad = 0, cols_per_pass = kColStep;
 };
 
-// The workspace of one scoring call: the operands, the flags and the passes' lists.
-int lay_out(mfa_ctx *c, Operands &op, int64_t Nt, int64_t Ns, int D, int k, const Outputs &o) {
-  op.Dpad = (D + 3) / 4 * 4;
-  op.Nspad = (Ns + kColStep - 1) / kColStep * kColStep;
-  op.keff = o.knn_idx ? k : (o.best_idx ? 1 : 0);
+// The column passes of a sweep of Nt rows over Nspad columns.
+int plan_passes(mfa_ctx *c, int64_t Nt, int64_t Nspad, int64_t &cols_per_pass, int &passes) {
   const int64_t row_blocks = (Nt + kRowBlock - 1) / kRowBlock;
   const size_t forced = env_count("MFA_PLDA_PASS_COLS");
-  int64_t cols = op.Nspad;
+  int64_t cols = Nspad;
   if (forced) cols = (int64_t)std::min<size_t>(forced, (size_t)1 << 31);
   else {
     const int cus = mfa_num_cus(c);
     if (cus <= 0) return -1;
     const int64_t want = (2 * (int64_t)cus + row_blocks - 1) / row_blocks;     // passes that fill the device twice
-    if (want > 1) cols = std::max<int64_t>(kMinPassCols, (op.Nspad + want - 1) / want);
+    if (want > 1) cols = std::max<int64_t>(kMinPassCols, (Nspad + want - 1) / want);
   }
-  cols = std::max<int64_t>(cols, (op.Nspad + 65534) / 65535);                 // grid.y
-  op.cols_per_pass = std::max<int64_t>(kColStep, (cols + kColStep - 1) / kColStep * kColStep);
-  op.passes = (int)std::max<int64_t>(1, (op.Nspad + op.cols_per_pass - 1) / op.cols_per_pass);
+  cols = std::max<int64_t>(cols, (Nspad + 65534) / 65535);                    // grid.y
+  cols_per_pass = std::max<int64_t>(kColStep, (cols + kColStep - 1) / kColStep * kColStep);
+  passes = (int)std::max<int64_t>(1, (Nspad + cols_per_pass - 1) / cols_per_pass);
+  return 0;
+}
+
+// The workspace of one scoring call: the operands, the flags and the passes' lists.
+int lay_out(mfa_ctx *c, Operands &op, int64_t Nt, int64_t Ns, int D, int k, const Outputs &o) {
+  op.Dpad = (D + 3) / 4 * 4;
+  op.Nspad = (Ns + kColStep - 1) / kColStep * kColStep;
+  op.keff = o.knn_idx ? k : (o.best_idx ? 1 : 0);
+  if (plan_passes(c, Nt, op.Nspad, op.cols_per_pass, op.passes)) return -1;
   const size_t mat = (size_t)op.Dpad * (size_t)op.Nspad * 8;
   op.o_at = op.ws.take(mat); op.o_bt = op.ws.take(mat); op.o_c = op.ws.take((size_t)op.Nspad * 8); op.o_flags = op.ws.take(8);
   op.o_ps = op.ws.take((size_t)op.passes * Nt * op.keff * 8);
@@ -406,7 +517,74 @@ int pack_operands(mfa_ctx *c, const Operands &op, const double *d_A, const doubl
   return 0;
 }
 
+SweepParams pair_params(const MfaPairSweep &op, const double *d_y, int64_t N, int D, int keff) {
+  return SweepParams{d_y, (int)N, (int)N, D, op.Dpad, op.Nspad, op.ws.at<double>(op.o_at), op.ws.at<double>(op.o_bt), op.ws.at<double>(op.o_c),
+                     op.cols_per_pass, keff, 1, nullptr, op.ws.at<double>(op.o_ps), op.ws.at<int32_t>(op.o_pi)};
+}
+
 }  // namespace
+
+int mfa_pair_lay_out(mfa_ctx *c, MfaPairSweep &op, int64_t N, int D, int k) {
+  op.Dpad = (D + 3) / 4 * 4;
+  op.Nspad = (N + kColStep - 1) / kColStep * kColStep;
+  op.keff = k;
+  if (plan_passes(c, N, op.Nspad, op.cols_per_pass, op.passes)) return -1;
+  const size_t mat = (size_t)op.Dpad * (size_t)op.Nspad * 8, per = (size_t)std::max(k, 1);
+  op.o_at = op.ws.take(mat); op.o_bt = op.ws.take(mat); op.o_c = op.ws.take((size_t)op.Nspad * 8);
+  op.o_ps = op.ws.take((size_t)op.passes * N * per * 8);
+  op.o_pi = op.ws.take((size_t)op.passes * N * per * 4);
+  op.o_ks = op.ws.take((size_t)N * per * 8);
+  op.o_ki = op.ws.take((size_t)N * per * 4);
+  return 0;
+}
+
+int mfa_pair_pack(mfa_ctx *c, const MfaPairSweep &op, const double *d_y, int64_t N, int D) {
+  KernelTimer kt(c, MFA_K_PLDA_PREPARE);
+  hipLaunchKernelGGL(pair_pack_kernel, dim3((unsigned)((op.Nspad + 255) / 256)), dim3(256), 0, c->stream, d_y, (int)N, D, op.Dpad, op.Nspad,
+                     op.ws.at<double>(op.o_at), op.ws.at<double>(op.o_bt), op.ws.at<double>(op.o_c));
+  MFA_HIP_CHECK(c, hipGetLastError());
+  MFA_DEBUG_POINT(c, "pair_pack_kernel cols=%lld D=%d", (long long)N, D);
+  return 0;
+}
+
+int mfa_pair_core_sweep(mfa_ctx *c, const MfaPairSweep &op, const double *d_y, const double *d_q, double w, int64_t N, int D, int k,
+                        double *d_core, double *d_v) {
+  const dim3 grid((unsigned)((N + kRowBlock - 1) / kRowBlock), (unsigned)op.passes);
+  if (k > 0 || d_v) {
+    KernelTimer kt(c, MFA_K_PLDA_SWEEP);
+    hipLaunchKernelGGL(pair_core_sweep_kernel, grid, dim3(256), 0, c->stream, pair_params(op, d_y, N, D, k),
+                       PairIn{d_q, w, d_v, nullptr, nullptr, nullptr, nullptr});
+    MFA_HIP_CHECK(c, hipGetLastError());
+    MFA_DEBUG_POINT(c, "pair_core_sweep_kernel N=%lld D=%d passes=%d k=%d", (long long)N, D, op.passes, k);
+  }
+  KernelTimer kt(c, MFA_K_PLDA_MERGE);
+  if (k > 0)
+    hipLaunchKernelGGL(plda_merge_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream, op.ws.at<double>(op.o_ps),
+                       op.ws.at<int32_t>(op.o_pi), op.passes, (int)N, k, k, (int32_t *)nullptr, (double *)nullptr, op.ws.at<int32_t>(op.o_ki),
+                       op.ws.at<double>(op.o_ks));
+  hipLaunchKernelGGL(pair_core_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, op.ws.at<double>(op.o_ks), N, k, d_core);
+  MFA_HIP_CHECK(c, hipGetLastError());
+  MFA_DEBUG_POINT(c, "pair_core_kernel N=%lld k=%d", (long long)N, k);
+  return 0;
+}
+
+int mfa_pair_edge_sweep(mfa_ctx *c, const MfaPairSweep &op, const double *d_y, const double *d_q, double w, const double *d_core,
+                        const int32_t *d_comp, int64_t N, int D, double *d_row_m, int32_t *d_row_j) {
+  const dim3 grid((unsigned)((N + kRowBlock - 1) / kRowBlock), (unsigned)op.passes);
+  {
+    KernelTimer kt(c, MFA_K_PLDA_SWEEP);
+    hipLaunchKernelGGL(pair_edge_sweep_kernel, grid, dim3(256), 0, c->stream, pair_params(op, d_y, N, D, 0),
+                       PairIn{d_q, w, nullptr, d_core, d_comp, op.ws.at<double>(op.o_ps), op.ws.at<int32_t>(op.o_pi)});
+    MFA_HIP_CHECK(c, hipGetLastError());
+    MFA_DEBUG_POINT(c, "pair_edge_sweep_kernel N=%lld D=%d passes=%d", (long long)N, D, op.passes);
+  }
+  KernelTimer kt(c, MFA_K_PLDA_MERGE);
+  hipLaunchKernelGGL(pair_edge_merge_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, op.ws.at<double>(op.o_ps),
+                     op.ws.at<int32_t>(op.o_pi), op.passes, N, d_row_m, d_row_j);
+  MFA_HIP_CHECK(c, hipGetLastError());
+  MFA_DEBUG_POINT(c, "pair_edge_merge_kernel N=%lld passes=%d", (long long)N, op.passes);
+  return 0;
+}
 
 extern "C" {
 

@@ -333,6 +333,19 @@ class AlignmentEngine(GraphPacking, FrontEndStages):
                                                       C.byref(n_clusters), C.byref(rounds)), "mfa_dbscan_from_bits")
         return int(n_clusters.value), int(rounds.value)
 
+    def _launch_hdbscan_core(self, x, metric: int, psi, k: int, y, q, core, v) -> None:
+        """The pair form's prepare step and the core scores (mfa_hdbscan_core_batch); ``v``: None or the [n, n] score matrix."""
+        check(self.ctx, self.lib.mfa_hdbscan_core_batch(self.ctx, _ptr(x), int(x.shape[0]), int(x.shape[1]), int(metric), _ptr(psi), int(k),
+                                                        _ptr(y), _ptr(q), _ptr(core), _ptr(v)), "mfa_hdbscan_core_batch")
+
+    def _launch_hdbscan_mst(self, y, q, core, metric: int, lo, hi, score):
+        """Borůvka on the mutual-reachability graph (mfa_hdbscan_mst_batch): (edges, rounds)."""
+        n_edges, rounds = C.c_int32(0), C.c_int32(0)
+        check(self.ctx, self.lib.mfa_hdbscan_mst_batch(self.ctx, _ptr(y), _ptr(q), _ptr(core), int(y.shape[0]), int(y.shape[1]), int(metric),
+                                                       _ptr(lo), _ptr(hi), _ptr(score), C.byref(n_edges), C.byref(rounds)),
+              "mfa_hdbscan_mst_batch")
+        return int(n_edges.value), int(rounds.value)
+
     def _launch_scan(self, values, d_frame_off, n_utt: int, total: int, scan, totals) -> None:
         check(self.ctx, self.lib.mfa_vad_scan_batch(self.ctx, _ptr(values), _ptr(d_frame_off), n_utt, total, _ptr(scan),
                                                     _ptr(totals)), "mfa_vad_scan_batch")

@@ -1866,3 +1866,16 @@ def cluster_matrix(ivectors: np.ndarray, cluster_type: ClusterType, metric: Dist
         raise TypeError(f"cluster_matrix: unexpected keyword arguments {sorted(kwargs)}")
     backend = known.get("backend", "device")
     return _cluster.cluster_matrix(ivectors, cluster_type, metric, strict=strict, engine=get_engine() if backend == "device" else None, **known)
+
+
+def hdbscan_matrix(ivectors: np.ndarray, metric: DistanceMetric = DistanceMetric.cosine, strict=True, no_visuals=False,
+                   working_directory=None, **kwargs) -> np.ndarray:
+    """The ``ClusterType.hdbscan`` branch of the reference's ``cluster_matrix`` on the process's engine (``cluster.hdbscan_matrix``):
+    ``kwargs`` carry ``distance_threshold``, ``plda``, ``min_cluster_size`` and ``min_samples``.  ``cluster_matrix`` itself still
+    refuses ``ClusterType.hdbscan``; nothing is drawn."""
+    from . import cluster as _cluster
+    known = {k: kwargs.pop(k) for k in ("distance_threshold", "plda", "min_cluster_size", "min_samples", "backend") if k in kwargs}
+    if kwargs:
+        raise TypeError(f"hdbscan_matrix: unexpected keyword arguments {sorted(kwargs)}")
+    backend = known.get("backend", "device")
+    return _cluster.hdbscan_matrix(ivectors, metric, strict=strict, engine=get_engine() if backend == "device" else None, **known)

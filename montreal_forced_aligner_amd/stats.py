@@ -1414,3 +1414,143 @@ def dbscan_from_bits_host(bits, min_samples: int, n=None):
     if rc != 0:
         raise _lib.MfaHipError(f"mfa_debug_dbscan_from_bits_host: {_CLUSTER_TWIN_CODES.get(rc, 'bad arguments')}")
     return dict(labels=labels, core=core, count=count, n_clusters=int(n_clusters.value), bits=h)
+
+
+# ---- HDBSCAN: the pair form, the core scores and the mutual-reachability spanning tree (include/mfa_hip.h "HDBSCAN") -------------------
+_HDBSCAN_TWIN_CODES = {-2: "dimension outside [1, 1024]", -3: "neighbours outside [0, 64]", -4: "a psi entry that is not positive and finite",
+                       -5: "2^31 points or more", -8: "an unknown metric"}
+
+
+def pair_metric(metric):
+    """(the library's metric code, rows made unit length first, the metric of ``score_to_distance``) of the pair form: cosine is
+    euclidean on unit rows, which is what the reference's hdbscan branch clusters."""
+    name = getattr(metric, "name", metric)
+    code = metric_code(name)
+    return (1, True, "euclidean") if name == "cosine" else (code, False, name)
+
+
+def _hdbscan_twin(rc: int, name: str) -> None:
+    if rc != 0:
+        raise _lib.MfaHipError(f"{name}: {_HDBSCAN_TWIN_CODES.get(rc, 'bad arguments')}")
+
+
+def _pair_k(k) -> int:
+    k = int(k)
+    if not 0 <= k <= 64:
+        raise _lib.MfaHipError(f"core_scores: {k} neighbours (0 to 64: a row's list is one wavefront register); min_samples up to 65")
+    return k
+
+
+def core_scores(engine, metric, x, k: int, model=None, want_v: bool = False):
+    """The pair form of ``x`` [n, D] and every point's core score (mfa_hdbscan_core_batch): dict(y [n, D], q [n], core [n], v [n, n] or
+    None, code) on the device.  ``k = min_samples − 1`` (0 to 64): the core score is the k-th best score over the other points, −inf
+    for a point with fewer than k finite ones, +inf at k = 0.  Scores are larger-is-nearer; ``score_to_distance`` of
+    ``pair_metric(metric)[2]`` makes distances of them."""
+    code, unit, _ = pair_metric(metric)
+    k = _pair_k(k)
+    x = _plda_vectors(engine, x, _metric_dim(code, model, x), "core_scores")
+    if unit:
+        x = _unit_rows(x)
+    n, dev = int(x.shape[0]), engine.device
+    psi = _plda_device_model(engine, model)[2] if code == 0 else None
+    y, q, core = torch.empty_like(x), torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+    v = torch.empty((n, n), dtype=torch.float64, device=dev) if want_v else None
+    engine._launch_hdbscan_core(x, code, psi, k, y, q, core, v)
+    return dict(y=y, q=q, core=core, v=v, code=code)
+
+
+def pair_prepare(engine, metric, x, model=None):
+    """(y [n, D], q [n]) of the pair form on the device: v(i, j) = (q_i + q_j) + w · y_i · y_j, bit-symmetric in (i, j)."""
+    r = core_scores(engine, metric, x, 0, model)
+    return r["y"], r["q"]
+
+
+def core_scores_host(metric, x, k: int, model=None, want_v: bool = False, v=None):
+    """``core_scores`` on the host twin: numpy arrays.  ``v``: a score matrix to take the core scores from (tests: the device's own)."""
+    code, unit, _ = pair_metric(metric)
+    k = _pair_k(k)
+    x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+    if _metric_dim(code, model, x) != x.shape[1]:
+        raise _lib.MfaHipError(f"core_scores_host: vectors {x.shape} for a model of dimension {model.dim}")
+    if unit:
+        x = np.ascontiguousarray(_unit_rows(x))
+    n = int(x.shape[0])
+    psi = np.ascontiguousarray(model.psi, dtype=np.float64) if code == 0 else None
+    v_in = None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+    if v_in is not None and v_in.shape != (n, n):
+        raise _lib.MfaHipError(f"core_scores_host: a score matrix {v_in.shape} for {n} points")
+    y, q, core = np.empty_like(x), np.empty(n), np.empty(n)
+    out_v = np.empty((n, n)) if want_v else None
+    p = lambda a: None if a is None else a.ctypes.data
+    _hdbscan_twin(_lib.lib().mfa_debug_hdbscan_core_host(p(x), n, int(x.shape[1]), code, p(psi), k, p(y), p(q), p(core), p(out_v), p(v_in)),
+                  "mfa_debug_hdbscan_core_host")
+    return dict(y=y, q=q, core=core, v=out_v, code=code)
+
+
+def pair_prepare_host(metric, x, model=None):
+    r = core_scores_host(metric, x, 0, model)
+    return r["y"], r["q"]
+
+
+def finish_tree(n: int, lo, hi, score):
+    """The spanning forest's edges sorted by the edge order (larger score, then smaller lo, then smaller hi); the components that
+    no finite score joins are tied to the first one's smallest member at score −inf (distance +inf): n − 1 edges."""
+    lo, hi, score = np.asarray(lo, np.int32), np.asarray(hi, np.int32), np.asarray(score, np.float64)
+    if n > 1 and lo.shape[0] < n - 1:
+        parent = np.arange(n)
+
+        def find(a):
+            while parent[a] != a:
+                parent[a] = parent[parent[a]]
+                a = parent[a]
+            return a
+        for a, b in zip(lo.tolist(), hi.tolist()):
+            ra, rb = find(a), find(b)
+            parent[max(ra, rb)] = min(ra, rb)                      # the smaller root stays: a root is its component's smallest member
+        roots = sorted({find(i) for i in range(n)})
+        lo = np.concatenate([lo, np.full(len(roots) - 1, roots[0], np.int32)])
+        hi = np.concatenate([hi, np.asarray(roots[1:], np.int32)])
+        score = np.concatenate([score, np.full(len(roots) - 1, -np.inf)])
+    order = np.lexsort((hi, lo, -score))
+    return lo[order], hi[order], score[order]
+
+
+def mreach_mst(engine, metric, y, q, core):
+    """The minimum spanning tree of the mutual-reachability graph (mfa_hdbscan_mst_batch) from the pair form and the core scores on
+    the device: dict(lo, hi, score: numpy [n − 1], sorted by the edge order; found: the edges the device found, rounds).  No n × n
+    array is stored: every Borůvka round is one sweep."""
+    code = pair_metric(metric)[0]
+    dev = engine.device
+    y = y.to(device=dev, dtype=torch.float64).contiguous() if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y, np.float64)).to(dev)
+    q, core = (a.to(device=dev, dtype=torch.float64).contiguous() if isinstance(a, torch.Tensor)
+               else torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev) for a in (q, core))
+    n = int(y.shape[0])
+    if y.dim() != 2 or tuple(q.shape) != (n,) or tuple(core.shape) != (n,):
+        raise _lib.MfaHipError(f"mreach_mst: y {tuple(y.shape)}, q {tuple(q.shape)} and core {tuple(core.shape)} do not go together")
+    m = max(n - 1, 1)
+    lo, hi = torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.int32, device=dev)
+    score = torch.empty(m, dtype=torch.float64, device=dev)
+    found, rounds = engine._launch_hdbscan_mst(y, q, core, code, lo, hi, score)
+    flo, fhi, fs = finish_tree(n, lo[:found].cpu().numpy(), hi[:found].cpu().numpy(), score[:found].cpu().numpy())
+    return dict(lo=flo, hi=fhi, score=fs, found=found, rounds=rounds)
+
+
+def mreach_mst_host(metric, y, q, core, v=None):
+    """``mreach_mst`` on the host twin, Kruskal under the same edge order; ``v``: a score matrix to use in place of the pair form's."""
+    import ctypes as C
+    code = pair_metric(metric)[0]
+    y = np.ascontiguousarray(np.atleast_2d(y), dtype=np.float64)
+    q, core = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(core, dtype=np.float64)
+    n = int(y.shape[0])
+    v = None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+    if q.shape != (n,) or core.shape != (n,) or (v is not None and v.shape != (n, n)):
+        raise _lib.MfaHipError("mreach_mst_host: y, q, core and v do not go together")
+    m = max(n - 1, 1)
+    lo, hi, score = np.empty(m, np.int32), np.empty(m, np.int32), np.empty(m)
+    found = C.c_int32(0)
+    _hdbscan_twin(_lib.lib().mfa_debug_hdbscan_mst_host(y.ctypes.data, q.ctypes.data, core.ctypes.data, None if v is None else v.ctypes.data, n,
+                                                        int(y.shape[1]), code, lo.ctypes.data, hi.ctypes.data, score.ctypes.data,
+                                                        C.byref(found)), "mfa_debug_hdbscan_mst_host")
+    f = int(found.value)
+    flo, fhi, fs = finish_tree(n, lo[:f], hi[:f], score[:f])
+    return dict(lo=flo, hi=fhi, score=fs, found=f)
