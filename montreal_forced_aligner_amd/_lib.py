@@ -305,6 +305,28 @@ def check(ctx, rc: int, what: str) -> None:
         raise MfaHipError(f"{what}: {msg.decode() if msg else 'error'}")
 
 
+def twin_check(rc: int, name: str, codes: dict = {}) -> None:
+    """The return code of a host twin (no context, so no ``mfa_last_error``): ``codes`` holds its stage's reasons."""
+    if rc != 0:
+        raise MfaHipError(f"{name}: {codes.get(rc, 'bad arguments')}")
+
+
+def twin_call(name: str, codes: dict, *args) -> None:
+    """Host twin ``name`` of the library on ``args``, the numpy arrays among them as pointers (``_np_ptr``; ``args`` keeps them
+    alive across the call), its return code through ``twin_check``."""
+    twin_check(getattr(lib(), name)(*(_np_ptr(a) if hasattr(a, "ctypes") else a for a in args)), name, codes)
+
+
 def _ptr(t):
     """A torch tensor (or None) as the pointer argument of a library call."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _elem_ptr(t, index: int):
+    """Element ``index`` of a 1-D torch tensor as the pointer argument of a library call."""
+    return C.c_void_p(t.data_ptr() + index * t.element_size())
+
+
+def _np_ptr(a):
+    """A numpy array (or None) as the pointer argument of a library call; the caller keeps it alive across the call."""
+    return None if a is None else a.ctypes.data

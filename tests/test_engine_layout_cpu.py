@@ -10,26 +10,90 @@ import numpy as np
 import pytest
 import torch
 
-from montreal_forced_aligner_amd import _lib, engine, frontend, packing, pipeline, ragged, staging, stats
+from montreal_forced_aligner_amd import _lib, engine, frontend, packing, pipeline, ragged, speaker_train, staging, stats, train
+from montreal_forced_aligner_amd.stats import _common, alignment, pairs, speaker
 
 REEXPORTS = {
     engine: ("AlignmentEngine", "redo_capacity", "DEFAULT_MFCC"),
     pipeline: ("Pipeline",),
     packing: ("PackedGraphs",),
     staging: ("StagingPool", "StagingRing"),
-    stats: ("GmmStats", "check_delta_fmllr", "fmllr_statistics", "gmm_statistics", "gmm_statistics_host", "tid_tables"),
+    alignment: ("GmmStats", "check_delta_fmllr", "fmllr_statistics", "gmm_statistics", "gmm_statistics_host", "tid_tables"),
     ragged: ("offsets", "_speaker_groups"),
     frontend: ("DEFAULT_PITCH", "_PITCH_ALIAS"),
     _lib: ("_ptr",),
 }
 
+# the public names of stats.py before it became a package, and ``_unit_rows``, by the module that defines each now
+STATS_NAMES = {
+    alignment: ("model_arrays", "check_delta_fmllr", "tid_tables", "silence_weights", "fmllr_statistics", "GmmStats", "gmm_statistics",
+                "gmm_statistics_twofeats", "gmm_statistics_host", "gmm_statistics_twofeats_host", "LdaStats", "lda_statistics",
+                "lda_statistics_host", "gaussian_means", "MlltStats", "mllt_statistics", "mllt_statistics_host", "TREE_NO_KEY",
+                "TREE_MAX_PHONES", "TREE_MAX_CLASSES", "tree_key", "TreeStats", "tree_tid_tables", "tree_statistics",
+                "tree_statistics_host"),
+    speaker: ("gaussian_selection", "ubm_statistics", "gaussian_selection_host", "ubm_statistics_host", "prune_posteriors",
+              "prune_posteriors_host", "ivector_utterance_statistics", "ivector_utterance_statistics_host", "ivector_estep",
+              "ivector_estep_host"),
+    pairs: ("PLDA_BLOCK_BYTES", "PLDA_MATRIX_BYTES", "plda_transform", "plda_transform_host", "plda_scores", "plda_classify", "plda_knn",
+            "plda_sweep", "plda_prepare_host", "plda_scores_host", "plda_classify_host", "plda_knn_host", "plda_sweep_host",
+            "METRIC_CODES", "NEIGHBOR_BITS_BYTES", "metric_code", "score_threshold", "score_to_distance", "metric_sweep",
+            "metric_sweep_host", "neighbor_bits", "neighbor_bits_host", "knn", "knn_host", "dbscan_from_bits", "dbscan_from_bits_host",
+            "pair_metric", "core_scores", "pair_prepare", "core_scores_host", "pair_prepare_host", "finish_tree", "mreach_mst",
+            "mreach_mst_host", "_unit_rows"),
+}
+TRAIN_NAMES = ("UbmHostBackend", "UbmDeviceBackend", "DubmTrainer", "IvectorHostBackend", "IvectorDeviceBackend", "IvectorTrainer")
+
+
+def _is_the_object_its_home_defines(package, name, home):
+    obj = getattr(home, name)
+    assert getattr(package, name) is obj
+    if hasattr(obj, "__module__"):            # (classes and functions: defined there, not passed through)
+        assert obj.__module__ == home.__name__
+
 
 @pytest.mark.parametrize("name,home", [(n, m) for m, names in REEXPORTS.items() for n in names])
 def test_engine_reexports_the_object_of_the_new_module(name, home):
-    obj = getattr(home, name)
-    assert getattr(engine, name) is obj
-    if hasattr(obj, "__module__"):            # (classes and functions: defined there, not passed through)
-        assert obj.__module__ == home.__name__
+    _is_the_object_its_home_defines(engine, name, home)
+
+
+def test_the_list_of_stats_names_is_whole():
+    names = [n for group in STATS_NAMES.values() for n in group]
+    assert len(names) == len(set(names)) == 69 + 1
+
+
+@pytest.mark.parametrize("name,home", [(n, m) for m, names in STATS_NAMES.items() for n in names])
+def test_stats_reexports_the_object_of_its_submodule(name, home):
+    _is_the_object_its_home_defines(stats, name, home)
+
+
+@pytest.mark.parametrize("name", TRAIN_NAMES)
+def test_train_reexports_the_speaker_trainers(name):
+    _is_the_object_its_home_defines(train, name, speaker_train)
+
+
+def test_device_model_cache_is_kept_per_model_for_one_device_at_a_time():
+    calls = []
+
+    class Model:
+        def arrays(self):
+            calls.append(1)
+            return np.arange(3.0), np.ones((2, 2), dtype=np.float32)
+
+    class Engine:
+        device = torch.device("cpu")
+
+    model, eng = Model(), Engine()
+    first = _common.device_model(eng, model, model.arrays)
+    assert isinstance(first, tuple) and [t.dtype for t in first] == [torch.float64, torch.float32]
+    assert all(t.device == eng.device for t in first) and torch.equal(first[0], torch.arange(3.0, dtype=torch.float64))
+    assert _common.device_model(eng, model, model.arrays) is first and len(calls) == 1      # the same tuple, nothing computed again
+    assert _common.device_model(eng, Model(), model.arrays) is not first                    # kept on the model object
+    eng.device = torch.device("meta")
+    second = _common.device_model(eng, model, model.arrays)
+    assert second is not first and all(t.device.type == "meta" for t in second)
+    assert list(model._device_arrays) == ["meta"]                                            # the other device's copies are let go
+    eng.device = torch.device("cpu")
+    assert _common.device_model(eng, model, model.arrays) is not first                       # so going back uploads again
 
 
 def test_ragged_imports_without_torch():
