@@ -121,7 +121,8 @@ struct mfa_ctx {
   MfaBuf d_xsplit_bad;         // int … and the tile's "a scaled feature left the f16 range" flag
   bool xsplit_ready = false;   // d_xsplit holds the operands of the batch mfa_align_features_batch is working on
   MfaBuf d_col_row0;           // int32 lazy scoring: first packed model row of every score column of the batch (row0[pdf_list[j]])
-  MfaBuf d_band_ranges;        // int32 [n_utt][11][2]: per window, the band's index range in each run of class 0 and in classes 2..4
+  MfaBuf d_col_own_last;       // int32 lazy scoring: per score column of the batch, the largest BFS depth of a state one of its arcs leaves
+  MfaBuf d_band_ranges;       // int32 [n_utt][11][2]: per window, the band's index range in each run of class 0 and in classes 2..4
   int num_cus = 0;             // mfa_num_cus
   // caller-owned debug buffers: not owned, never freed here
   void *vit_stamps = nullptr;  // per-utterance phase cycle counters of the decoder (-DVIT_STAMPS builds)
@@ -246,7 +247,8 @@ struct MfaWindowScore {
 constexpr int kMfaRunSlots = MFA_PLAN_MAX_GROUPS;
 constexpr int kMfaRangeSlots = kMfaRunSlots + 5;
 const int32_t *mfa_band_ranges(mfa_ctx *ctx);
-int mfa_gmm_presplit(mfa_ctx *c, const MfaLazyScoring *lazy, const int64_t *d_frame_off, int n_utt, int64_t total_frames);
+int mfa_gmm_presplit(mfa_ctx *c, const MfaLazyScoring *lazy, const mfa_graph_batch *g, const int64_t *d_frame_off, int n_utt,
+                     int64_t total_frames);
 int mfa_gmm_lazy_supported(mfa_ctx *ctx);   // the loaded model fits the MFMA kernels (dim <= 48)
 // Score, for every listed utterance, the (frame, pdf) cells of the window that lie inside the band.  Enqueues on ctx->stream.
 int mfa_gmm_score_window(mfa_ctx *ctx, const MfaLazyScoring *lazy, const MfaWindowScore *ws, const int64_t *d_frame_off,

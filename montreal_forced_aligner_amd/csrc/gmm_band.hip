@@ -3,6 +3,7 @@
 //                           f16×2 pass, then a bf16×3 pass over the sub-tiles the first one declined;
 //   gmm_presplit_kernel     once per batch: the f16 operand pieces of every 64-frame tile, in the band kernel's register layout;
 //   gmm_col_rows_kernel     once per batch: the first packed model row of every score column;
+//   gmm_col_own_last_kernel once per batch: every score column's own last depth (class 0 skips columns below the band with it);
 //   gmm_band_ranges_kernel  once per window: the band's index range in every class (and run of class 0) of every utterance.
 // Single-Gaussian pdfs (and everything under MFA_GMM_BF16=0) go to gmm_band_f32_kernel, the exact-f32 tile walk, which lives
 // next to its score_tile in gmm.hip's unit (gmm_f32.hpp) and is reached through mfa_gmm_launch_band_f32.  mfa_gmm_score_window (end of file)
@@ -43,6 +44,30 @@ __global__ void gmm_col_rows_kernel(GmmParams p, int32_t *out) {
     int r = p.row0[pdf];
     if (p.col_nb_packed) { const int nb = p.nblk[pdf]; if (nb > 1) r |= nb - 1; }
     out[j] = r;
+  }
+}
+
+// Lazy scoring, once per batch: every score column's OWN last depth — the largest BFS depth of a state one of the column's arcs
+// leaves.  The plan's last_depth is the running maximum of this along a run (which makes the band an index range); the band
+// kernel tests the column's own value inside that range and skips what no token can ask for.  One workgroup per utterance;
+// epsilon input arcs (the tail of a state's arcs when the batch has d_state_nemit) emit no column.
+__global__ void gmm_col_own_last_kernel(mfa_graph_batch g, const int32_t *state_depth, const int64_t *pdf_off, int32_t *out) {
+  const int utt = blockIdx.x;
+  const int64_t l0 = pdf_off[utt];
+  const int P = (int)(pdf_off[utt + 1] - l0);
+  for (int j = threadIdx.x; j < P; j += blockDim.x) out[l0 + j] = 0;
+  __syncthreads();
+  const int64_t so = g.d_state_off[utt], ab = g.d_arc_base[utt];
+  const int S = (int)(g.d_state_off[utt + 1] - so);
+  const int32_t *arc_off = g.d_arc_off + so + utt;
+  const int32_t *nemit = g.d_state_nemit ? g.d_state_nemit + so : nullptr;
+  for (int s_ = threadIdx.x; s_ < S; s_ += blockDim.x) {
+    const int d = state_depth[2 * (so + s_)];
+    const int a0 = arc_off[s_], a1 = nemit ? a0 + nemit[s_] : arc_off[s_ + 1];
+    for (int a = a0; a < a1; a++) {
+      const int c = g.d_arc_col[ab + a];
+      if ((unsigned)c < (unsigned)P) atomicMax(&out[l0 + c], d);
+    }
   }
 }
 
@@ -256,6 +281,9 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
     // band range [lo, hi) of every class this kernel scores: 0 (one 32-row block per pdf), 1 (several blocks per pdf) and 2, 3, 4
     // (16-, 8-, 4-row slots); class 5 (single Gaussians) is the f32 band kernel's
     int lo_c[5], hi_c[5], base_c[5];
+    // the band's lower depth bound, read as gmm_band_ranges_kernel reads it (lag windows included): class 0 tests every
+    // column's own last depth against it
+    const int band_lo = band_of(p, utt).lo;
     {   // looked up once per utterance and window by gmm_band_ranges_kernel
       const int32_t *rg = p.ranges + (size_t)utt * kRangeSlots * 2;
       int off = 0;
@@ -321,21 +349,24 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
     // a step (SplitOps::mfma_step; the order table is the shared one), the accumulator seed from the gconst registers
     // (init_from_gconst) and this flush (flush_staged), all in gmm_common.hpp.  Change them together.
     constexpr int kProd = Ops::kProd;
-    // `cnt` staged columns, the first of them score column c0 of the utterance's matrix → HBM as 128-byte row segments
-    auto flush_cols = [&](int c0, int cnt) {
+    // the staged columns whose bit is set in `cols` (bit 0: score column c0 of the utterance's matrix) → HBM as 128-byte row
+    // segments; a column without its bit was not staged and keeps what the matrix held
+    auto flush_cols = [&](int c0, uint32_t cols) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const bool mine = ((cols >> col) & 1u) != 0u;
 #pragma unroll 4
       for (int i = 0; i < 32; i++) {
         const int rr = h + 2 * i, t = t_base + rr;
-        if (col < cnt && t < T) __builtin_nontemporal_store(stage[rr * 33 + col], &out[(size_t)t * P + c0 + col]);
+        if (mine && t < T) __builtin_nontemporal_store(stage[rr * 33 + col], &out[(size_t)t * P + c0 + col]);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
     };
 
     // ---------------------------------------------------------------- class 0: one pdf per 32-row block
+    int blocks0 = 0;                                             // blocks visited (the stamps' count)
     if (lo < hi) {
       const uint4 *wsrc = (kHalf ? p.wh : p.wb) + lane;
       const float *gsrc = (kHalf ? p.gch : p.gc) + 4 * h;
@@ -344,15 +375,38 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
       // the second load wait for the first — the youngest entry of the in-order vmcnt queue — i.e. drained every outstanding
       // operand load of the next block at the top of each block.
       const int32_t *crow = p.col_row0 + l0;
-      auto row0_at = [&](int jj) { return crow[min(jj, last)]; };
-      auto block_at = [&](int jj) {
-        const int blk = __builtin_amdgcn_readfirstlane(row0_at(jj)) >> 5;
-        return blk;
+      const int32_t *cown = p.col_own_last + l0;
+      // The range is walked in staging windows of 32 columns (the flush unit) from `lo`.  Per window, lane i holds column
+      // j0 + i's row word and own last depth — one coalesced trip — and the wavefront derives two masks from them:
+      //   need: columns a token can ask for — own last depth ≥ the band's lower bound.  The range keeps a column as long as
+      //         an earlier column of the run spans further (last_depth is a running maximum); a token on state s has
+      //         band.lo ≤ depth(s), an arc of column c leaving s has depth(s) ≤ own_last(c): own_last(c) < band.lo is never read;
+      //   uniq: of those, the first occurrence of each row word.  A pdf met again more than a cluster span deeper has a
+      //         second column in the same run (pdf mod groups): the same block, the same 64 scores.
+      // The block loop visits the bits of uniq; a repeat gets the staged scores of its first occurrence before the flush
+      // (the bits a second evaluation would give), and the flush stores the needed columns only.
+      auto win_words = [&](int j0, int &rw, int &ol) {           // (past the range: the last column again, masked by win_masks)
+        const int idx = min(j0 + col, last);
+        rw = crow[idx]; ol = cown[idx];
       };
+      auto win_masks = [&](int j0, int rw, int ol, int &first, uint32_t &need) -> uint32_t {
+        need = (uint32_t)__ballot(lane < hi - j0 && lane < 32 && ol >= band_lo);
+        first = col;
+        for (uint32_t m = need; m != 0u; m &= m - 1u) {          // ascending: the lowest needed column with this lane's row word
+          const int k = __builtin_ctz(m);
+          if (__builtin_amdgcn_readlane(rw, k) == rw && k < first) first = k;
+        }
+        return (uint32_t)__ballot(lane < 32 && ((need >> col) & 1u) != 0u && first == col);
+      };
+      int j0 = lo, rw, ol, first;
+      uint32_t need, uniq;
+      win_words(j0, rw, ol);
+      uniq = win_masks(j0, rw, ol, first, need);
+      while (uniq == 0u && j0 + 32 < hi) { j0 += 32; win_words(j0, rw, ol); uniq = win_masks(j0, rw, ol, first, need); }
       op8 a[kSteps][kPieces];
       f32x4 g[4];
-      {
-        const int blk = block_at(lo);
+      if (uniq != 0u) {
+        const int blk = __builtin_amdgcn_readlane(rw, __builtin_ctz(uniq)) >> 5;
         const uint4 *src = wsrc + (size_t)blk * kUnits;
 #pragma unroll
         for (int q = 0; q < 4; q++) g[q] = *reinterpret_cast<const f32x4 *>(gsrc + (size_t)blk * 32 + 8 * q);
@@ -361,10 +415,28 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
 #pragma unroll
           for (int q = 0; q < kPieces; q++) a[s_][q] = __builtin_bit_cast(op8, src[(s_ * kPieces + q) * 64]);
       }
-      int blk_next = block_at(lo + 1);
-      for (int j = lo; j < hi; j++) {
+      while (uniq != 0u) {                                       // one staging window with blocks to score per round
+        // the next window's words, requested ahead of this window's operand loads (the oldest entries of the in-order vmcnt
+        // queue by the time the window's last block asks for them)
+        int j0_n = j0 + 32, rw_n, ol_n, first_n = 0;
+        uint32_t need_n = 0u, uniq_n = 0u;
+        win_words(j0_n, rw_n, ol_n);
+        uint32_t rest = uniq;
+        blocks0 += __builtin_popcount(uniq);
+        do {
         stamps.cycle(0);
-        const int x_next2 = row0_at(j + 2);                      // lookup two blocks ahead (oldest entry of the vmcnt queue)
+        const int c = __builtin_ctz(rest);                       // staged column = the bit's position
+        rest &= rest - 1u;
+        int blk_next;                                            // the next visited block: of this window, or the first of the next
+        if (rest != 0u) blk_next = __builtin_amdgcn_readlane(rw, __builtin_ctz(rest)) >> 5;
+        else {
+          if (j0_n < hi) {
+            uniq_n = win_masks(j0_n, rw_n, ol_n, first_n, need_n);
+            while (uniq_n == 0u && j0_n + 32 < hi) { j0_n += 32; win_words(j0_n, rw_n, ol_n); uniq_n = win_masks(j0_n, rw_n, ol_n, first_n, need_n); }
+          }
+          // (nothing follows: the same block again, unused)
+          blk_next = (uniq_n != 0u ? __builtin_amdgcn_readlane(rw_n, __builtin_ctz(uniq_n)) : __builtin_amdgcn_readlane(rw, c)) >> 5;
+        }
         f32x16 init, acc[2];
 #pragma unroll
         for (int rr = 0; rr < 16; rr++) init[rr] = g[rr >> 2][rr & 3];
@@ -392,15 +464,23 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
           __builtin_amdgcn_sched_barrier(0);
         }
         stamps.cycle(1);
-        blk_next = __builtin_amdgcn_readfirstlane(x_next2) >> 5;
         stamps.cycle(2);
         const Lse lse0 = block_lse(acc[0], h, l2e_s), lse1 = block_lse(acc[1], h, l2e_s);
-        const int jj = (j - lo) & 31;
-        stage[(32 * h + col) * 33 + jj] = finish((h ? lse1.m : lse0.m) * inv_s, h ? lse1.s : lse0.s);
+        stage[(32 * h + col) * 33 + c] = finish((h ? lse1.m : lse0.m) * inv_s, h ? lse1.s : lse0.s);
         stamps.cycle_lds_landed(3);
-        if (jj == 31 || j == last) flush_cols(j - jj, jj + 1);
+        if (rest == 0u) {
+          // repeats: every lane copies its own staged row (row 32 h + col = lane) from the first occurrence's column —
+          // lane-local LDS traffic, program order suffices
+          for (uint32_t m = need & ~uniq; m != 0u; m &= m - 1u) {
+            const int k = __builtin_ctz(m);
+            stage[lane * 33 + k] = stage[lane * 33 + __builtin_amdgcn_readlane(first, k)];
+          }
+          flush_cols(j0, need);
+        }
         stamps.cycle(4);
         stamps.block_done();
+        } while (rest != 0u);
+        j0 = j0_n; rw = rw_n; first = first_n; need = need_n; uniq = uniq_n;
       }
       stamps.add_block_phases(p, lane == 0 && kHalf);
     }
@@ -539,14 +619,14 @@ __global__ __launch_bounds__(256, 2) void gmm_band_kernel(GmmParams p) {
         if ((done & 31) == 0 || jb == jb1 - 1) {
           const int first = (done - 1) & ~31;            // first staged column of the open window
           const int valid = min(done, hi_s - jb0 * kPdfs) - first;   // columns of pdfs inside the class's range
-          flush_cols(col0 + first, valid);
+          flush_cols(col0 + first, valid >= 32 ? ~0u : (1u << valid) - 1u);
         }
       }
     };
     run_small(std::integral_constant<int, 16>{}, base_c[2], lo_c[2], hi_c[2]);
     run_small(std::integral_constant<int, 8>{}, base_c[3], lo_c[3], hi_c[3]);
     run_small(std::integral_constant<int, 4>{}, base_c[4], lo_c[4], hi_c[4]);
-    stamps.add_kernel_phases(p, lane == 0 && kHalf, hi - lo);
+    stamps.add_kernel_phases(p, lane == 0 && kHalf, blocks0);
     if constexpr (kStrided) {                            // the stage goes to the wavefront's next item
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -568,11 +648,18 @@ static int col_nb_packed_for(const mfa_ctx *c) {
 int mfa_gmm_lazy_supported(mfa_ctx *c) { return c->gmm_ready && (c->kpad == 80 || c->kpad == 96); }
 
 // Pre-split f16 operands of the whole batch (see gmm_presplit_kernel); mfa_gmm_score_window then hands them to the band kernel.
-int mfa_gmm_presplit(mfa_ctx *c, const MfaLazyScoring *lazy, const int64_t *d_frame_off, int n_utt, int64_t total_frames) {
+int mfa_gmm_presplit(mfa_ctx *c, const MfaLazyScoring *lazy, const mfa_graph_batch *g, const int64_t *d_frame_off, int n_utt,
+                     int64_t total_frames) {
   c->xsplit_ready = false;
-  {   // first model row of every score column of the batch (the band kernels read nothing else to find a block)
+  {   // first model row of every score column of the batch (the band kernels read nothing else to find a block), and the
+      // column's own last depth.  The latter comes from what the decoder is handed anyway — the graph batch's arcs and their
+      // columns, the plan's state depths — rather than from a new output of mfa_build_score_plan*: no exported signature and
+      // nothing in the host's packing changes, and it is one launch per batch over arrays already on the device.
     const int64_t cols_cap = (int64_t)n_utt * std::max(1, lazy->plan.max_cols);
     if (c->d_col_row0.reserve(c, (size_t)cols_cap * sizeof(int32_t), "the score columns' row table")) return -1;
+    if (c->d_col_own_last.reserve(c, (size_t)cols_cap * sizeof(int32_t), "the score columns' own last depths")) return -1;
+    hipLaunchKernelGGL(gmm_col_own_last_kernel, dim3(n_utt), dim3(256), 0, c->stream, *g, lazy->plan.d_state_depth, lazy->plan.d_pdf_off,
+                       c->d_col_own_last.ptr<int32_t>());
     GmmParams q;
     memset(&q, 0, sizeof(q));
     q.row0 = c->d_row0.ptr<int32_t>(); q.pdf_list = lazy->plan.d_pdf_list; q.pdf_off = lazy->plan.d_pdf_off; q.n_utt = n_utt;
@@ -652,7 +739,7 @@ int mfa_gmm_score_window(mfa_ctx *c, const MfaLazyScoring *lazy, const MfaWindow
     if (c->d_gmm_redo.reserve(c, (size_t)split_waves * sizeof(int), "the scoring redo list")) return -1;
     p.redo = c->d_gmm_redo.ptr<int>();
     p.wb = c->d_wb.ptr<const uint4>();
-    p.col_row0 = c->d_col_row0.ptr<int32_t>();
+    p.col_row0 = c->d_col_row0.ptr<int32_t>(); p.col_own_last = c->d_col_own_last.ptr<int32_t>();
     p.col_nb_packed = col_nb_packed_for(c);
     if (passes.f16) {
       p.wh = c->d_wh.ptr<const uint4>(); p.gch = c->d_gch.ptr<float>(); p.fscale = c->d_fscale.ptr<float>();

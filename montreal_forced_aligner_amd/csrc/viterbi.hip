@@ -165,7 +165,7 @@ int align_impl(mfa_ctx *c, const mfa_graph_batch *g, const float *d_loglikes, co
   // With the normal beam a frame rarely holds more than a few dozen tokens, so every utterance is first decoded with
   // small tables (the first tier); the few that overflow them are marked ST_GROW and decoded again, from scratch and with
   // the same beam, at the caller's full capacity.  Then the retry-beam pass for utterances that did not reach a final state.
-  if (lazy && mfa_gmm_presplit(c, lazy, d_frame_off, n_utt, total_frames) != 0) return -1;
+  if (lazy && mfa_gmm_presplit(c, lazy, g, d_frame_off, n_utt, total_frames) != 0) return -1;
   // Speculative look-ahead of the windowed first tier.  The proven band lets a token advance one arc per frame, K − 1
   // arcs by the window's last frame; speech advances a third of that (synthetic 10 s utterances: 21 states per 64 frames on
   // average, 34 at the 99th percentile, 38 at most).  The window is scored for a look-ahead of K / 2 arcs instead (32 for
