@@ -51,7 +51,8 @@ MFA_API int mfa_timer_end_ms(mfa_ctx *ctx, float *h_ms);
  * 13-16 LDA statistics (lookup, second moment, ordering + class sums, reductions), 17-20 MLLT statistics (lookup,
  * ordering, sums, reductions), 21-23 tree statistics (keys, ordering, sums), 24 speech activity (each entry point's launches),
  * 25-28 diagonal UBM (selection, posteriors, sums, reductions), 29-34 i-vector extractor (pruning, utterance statistics,
- * scatter, products, solve, accumulators), 35-38 PLDA (transform, prepare, sweep, merge), 39-42 clustering (symmetrise, degree, rounds, labels).
+ * scatter, products, solve, accumulators), 35-38 PLDA (transform, prepare, sweep, merge), 39-42 clustering (symmetrise, degree, rounds, labels),
+ * 43-44 silhouette (offsets, sweep).
  * Enabled with mfa_kernel_timing(ctx, 1) (adds an event pair around each launch). */
 MFA_API int mfa_kernel_timing(mfa_ctx *ctx, int enable);
 MFA_API int mfa_kernel_time_ms(mfa_ctx *ctx, int which, float *h_ms, int *h_launches);
@@ -1236,6 +1237,33 @@ MFA_API int mfa_debug_hdbscan_core_host(const double *h_x, int64_t N, int32_t D,
                                         double *h_y, double *h_q, double *h_core, double *h_v, const double *h_v_in);
 MFA_API int mfa_debug_hdbscan_mst_host(const double *h_y, const double *h_q, const double *h_core, const double *h_v, int64_t N, int32_t D,
                                        int32_t metric, int32_t *h_edge_lo, int32_t *h_edge_hi, double *h_edge_score, int32_t *h_n_edges);
+
+/* ---- Silhouette: the last step of the reference's cluster_matrix, metrics.silhouette_score(to_fit, c_labels, metric), as the
+ *      coefficient of every point, on N points whose rows are ordered by cluster, with no N x N array stored.  Shared
+ *      arithmetic: csrc/silhouette_math.hpp.  The scores are the pair form's v(i, j) of "HDBSCAN" above (the same metric codes,
+ *      the same prepare step); the distance is d = -v (0 plda: the signed -LLR as it is), sqrt(max(-v, 0)) (1 euclidean),
+ *      1 - v (2 dot: the cosine distance when the rows have unit length).
+ * d_off [C + 1] (int32): cluster c is the rows (and columns) off[c] .. off[c + 1] - 1; off[0] = 0, off[C] = N, strictly
+ *   ascending (no empty cluster).
+ * For row i of cluster own and every cluster c:  S(i, c) = sum of d(i, j) over j in c, j != i (the diagonal never enters).
+ *   The order of the sum: column j adds to partial (j & 63) >> 4 of four, each starting from +0 over its columns ascending, and
+ *   S = (P0 + P1) + (P2 + P3).
+ *   a = S(i, own) / (n_own - 1), 0 when n_own = 1;  b = the least S(i, c) / n_c over c != own, taken in ascending c from +inf
+ *   with "if (m < b) { b = m; bj = c; }": ties go to the lower cluster, a NaN mean is never taken; bj = -1 with b = +inf if none was.
+ *   s = 0 when n_own = 1 (scikit-learn's rule); otherwise den = max(a, b) (a < b ? b : a), s = 0 when den == 0, else (b - a) / den.
+ *   The counts enter as doubles; every quotient is one IEEE division.  For metric 0 s may leave [-1, 1].
+ * d_sil [N]; d_a, d_b [N] and d_bj [N] (int32) or NULL; d_v [N][N] or NULL: every v as the consumer sees it (tests).
+ * The sweep runs in one column pass whatever MFA_PLDA_PASS_COLS says: a cluster is never split, and two calls give the same bits.
+ * Shape check (silhouette_math.hpp sil_check_shape): N >= 0; D in [1, 1024]; N < 2^31; for N > 0, 2 <= C <= N.
+ * Limits (refused with a message, the context stays usable): that shape check; a metric outside [0, 2]; a psi entry that is not
+ * positive and finite (metric 0); offsets that break the rule above; a NULL d_x, d_off, d_sil (d_psi for metric 0).  N == 0
+ * writes nothing.  The call waits for the device once (the flags).  Timing slots 36 (prepare and pack), 43 (offsets), 44 (sweep).
+ * The host twin: the same contract in plain loops and the same order of every sum; it reads its scores from h_v_in [N][N] when
+ * that is given.  Returns 0, -1 a NULL array or a negative count, -2 D, -4 psi, -5 N, -6 C, -7 the offsets, -8 an unknown metric. */
+MFA_API int mfa_silhouette_batch(mfa_ctx *ctx, const double *d_x, int64_t N, int32_t D, int32_t metric, const double *d_psi,
+                                 const int32_t *d_off, int32_t C, double *d_sil, double *d_a, double *d_b, int32_t *d_bj, double *d_v);
+MFA_API int mfa_debug_silhouette_host(const double *h_x, int64_t N, int32_t D, int32_t metric, const double *h_psi, const int32_t *h_off,
+                                      int32_t C, double *h_sil, double *h_a, double *h_b, int32_t *h_bj, double *h_v, const double *h_v_in);
 
 #ifdef __cplusplus
 }

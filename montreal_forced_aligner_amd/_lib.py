@@ -15,7 +15,8 @@ _SO = Path(os.environ["MFA_HIP_SO"]).resolve() if os.environ.get("MFA_HIP_SO") e
 _SOURCES = ["api.hip", "mfcc.hip", "feats.hip", "gmm.hip", "gmm_band.hip", "gmm_pack.cpp", "score_plan.cpp", "viterbi.hip", "viterbi_general.hip",
             "fmllr.hip", "gmm_acc.hip", "gmm_acc_host.cpp", "resample.hip", "resample_plan.cpp", "pitch.hip", "pitch_plan.cpp", "compress.hip", "align_equal.hip", "align_equal_host.cpp",
             "lda_acc.hip", "lda_acc_host.cpp", "mllt_acc.hip", "mllt_acc_host.cpp", "tree_acc.hip", "tree_acc_host.cpp", "vad.hip", "vad_host.cpp", "ubm.hip", "ubm_host.cpp",
-            "ivector.hip", "ivector_host.cpp", "plda.hip", "plda_host.cpp", "cluster.hip", "cluster_host.cpp", "hdbscan.hip", "hdbscan_host.cpp"]
+            "ivector.hip", "ivector_host.cpp", "plda.hip", "plda_host.cpp", "cluster.hip", "cluster_host.cpp", "hdbscan.hip", "hdbscan_host.cpp",
+            "silhouette.hip", "silhouette_host.cpp"]
 _LIB = None
 
 
@@ -111,7 +112,7 @@ def build_native(force: bool = False, verbose: bool = False) -> Path:
     src_dir = _PKG / "csrc"
     srcs = [src_dir / s for s in _SOURCES]
     headers = ("ctx.hpp", "dev_buf.hpp", "gmm_common.hpp", "gmm_f32.hpp", "gmm_split.hpp", "gmm_pack.hpp", "viterbi_common.hpp", "viterbi_eps.hpp", "viterbi_wave.hpp", "viterbi_small.hpp", "viterbi_plan.hpp",
-               "resample_plan.hpp", "pitch_plan.hpp", "compress_math.hpp", "gmm_acc_math.hpp", "gmm_acc_twin.hpp", "acc_posterior.hpp", "acc_segments.hpp", "tid_lookup.hpp", "align_equal_math.hpp", "lda_acc_math.hpp", "mllt_acc_math.hpp", "tree_acc_math.hpp", "vad_math.hpp", "ubm_math.hpp", "ivector_math.hpp", "f64_gemm.hpp", "plda_math.hpp", "cluster_math.hpp", "hdbscan_math.hpp", "pair_sweep.hpp")
+               "resample_plan.hpp", "pitch_plan.hpp", "compress_math.hpp", "gmm_acc_math.hpp", "gmm_acc_twin.hpp", "acc_posterior.hpp", "acc_segments.hpp", "tid_lookup.hpp", "align_equal_math.hpp", "lda_acc_math.hpp", "mllt_acc_math.hpp", "tree_acc_math.hpp", "vad_math.hpp", "ubm_math.hpp", "ivector_math.hpp", "f64_gemm.hpp", "plda_math.hpp", "cluster_math.hpp", "hdbscan_math.hpp", "pair_sweep.hpp", "silhouette_math.hpp")
     deps = srcs + [src_dir / h for h in headers] + [_PKG.parent / "include" / "mfa_hip.h"]
     if not force and _SO.exists() and all(_SO.stat().st_mtime >= d.stat().st_mtime for d in deps if d.exists()):
         return _SO
@@ -265,6 +266,8 @@ SIGNATURES = {
     "mfa_hdbscan_mst_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "mfa_debug_hdbscan_core_host": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mfa_debug_hdbscan_mst_host": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(_i32)]),
+    "mfa_silhouette_batch": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mfa_debug_silhouette_host": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mfa_align_workspace_bytes": (C.c_size_t, [_vp, _i32, _i64, C.POINTER(AlignOpts)]),
 }
 

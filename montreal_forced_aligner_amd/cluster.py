@@ -3,8 +3,10 @@ and the naming of ``SpeakerDiarizer.cluster_utterances`` (MFA/diarization/speake
 
 The device path never stores a distance matrix: the sweep writes the ε-neighbourhoods as a bit matrix (``stats.neighbor_bits``)
 and DBSCAN runs on the bits (``stats.dbscan_from_bits``); the threshold estimate takes its k-th neighbour distances from the
-sweep's k-nearest consumer.  ``backend="host"`` runs the host twins of the same calls.  What is restated and unpinned:
-DESIGN.md, "Clustering".
+sweep's k-nearest consumer.  ``hdbscan_matrix`` is the ``ClusterType.hdbscan`` branch; ``cluster_vectors`` runs either type and then,
+as the reference does after every clustering, the silhouette score (``silhouette_samples``: the cluster sums come out of one more
+sweep over the points ordered by label).  ``backend="host"`` runs the host twins of the same calls.  What is restated and
+unpinned: DESIGN.md, "Clustering", "HDBSCAN", "Silhouette".
 """
 from __future__ import annotations
 
@@ -229,5 +231,117 @@ def hdbscan_utterances(utterance_ids: Sequence, ivectors, **kwargs) -> Dict:
     return dict(zip(utterance_ids, speaker_names(hdbscan_matrix(x, **kwargs))))
 
 
-__all__ = ["ClusterType", "DistanceMetric", "NoKneeError", "cluster_matrix", "cluster_utterances", "distance_threshold", "hdbscan_matrix",
-           "hdbscan_utterances", "knee_index", "kth_neighbor_distances", "speaker_names"]
+ONE_CLUSTER = "Only found one cluster, please adjust cluster parameters to generate more clusters."
+
+
+def silhouette_from_means(a, b, n_own, shift: float = 0.0) -> np.ndarray:
+    """The coefficients from every point's a and b (``stats.silhouette(…, want_parts=True)``) with every distance moved by
+    ``shift``: a singleton scores 0; den = max(a, b) + shift, den == 0 scores 0, any other den (b − a) / den."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    den = np.where(a < b, b, a) + float(shift)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where((np.asarray(n_own) == 1) | (den == 0.0), 0.0, (b - a) / den)
+
+
+def _silhouette(vectors, labels, metric, plda, noise: str, backend: str, engine):
+    """(the coefficients [n] in the caller's order, NaN for a row that was left out; the rows that took part)."""
+    metric = _metric(metric)
+    _check_backend(backend)
+    if noise not in ("cluster", "exclude"):
+        raise ValueError(f"noise {noise!r}: 'cluster' (label -1 is one more cluster) or 'exclude'")
+    x = _vectors(vectors, metric, plda)
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or labels.shape[0] != x.shape[0]:
+        raise ValueError(f"{labels.shape} labels for {x.shape[0]} vectors")
+    if labels.shape[0] and not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError(f"labels of type {labels.dtype}: integers")
+    if not np.isfinite(x).all():
+        raise ValueError("vectors that are not finite")
+    keep = np.flatnonzero(labels != -1) if noise == "exclude" else np.arange(labels.shape[0])
+    n = int(keep.shape[0])
+    counts = np.unique(labels[keep], return_counts=True)[1]
+    if not 2 <= counts.shape[0] <= n - 1:
+        raise ValueError(f"Number of labels is {counts.shape[0]}. Valid values are 2 to n_samples - 1 (inclusive): {n} samples")
+    order = keep[np.argsort(labels[keep], kind="stable")]          # the points by label: every cluster one range of rows
+    offsets = np.concatenate([[0], np.cumsum(counts)])
+    xs, name = x[order], metric.value
+    if metric is DistanceMetric.cosine:                            # the cosine distance: 1 − dot on unit rows
+        xs, name = np.ascontiguousarray(stats._unit_rows(xs)), "dot"
+    parts = metric is DistanceMetric.plda
+    if backend == "host":
+        r = stats.silhouette_host(name, xs, offsets, _model(plda), want_parts=parts)
+        best = stats.core_scores_host(name, xs, 1, _model(plda))["core"] if parts else None
+    else:
+        r = {k: (v.cpu().numpy() if k in ("sil", "a", "b") and v is not None else v)
+             for k, v in stats.silhouette(_engine(engine), name, xs, offsets, _model(plda), want_parts=parts).items()}
+        best = stats.core_scores(_engine(engine), name, xs, 1, _model(plda))["core"].cpu().numpy() if parts else None
+    sil = r["sil"]
+    if parts:
+        # −LLR is a signed distance, and (b − a) / max(a, b) ranks clusterings only for one that is never negative (with a and b both
+        # negative the quotient changes sign exactly where the clustering is right).  As in hdbscan_matrix, the plda distances are
+        # measured from the smallest one between two points: a mean of d − d0 is the mean of d less d0, so a and b move by −d0, the
+        # cluster that gives b stays, and only the denominator changes.
+        d0 = -float(np.max(best))
+        sil = silhouette_from_means(r["a"], r["b"], np.repeat(counts, counts), -d0)
+    out = np.full(labels.shape[0], np.nan)
+    out[order] = sil
+    return out, keep
+
+
+def silhouette_samples(vectors, labels, metric="cosine", plda=None, noise: str = "cluster", backend: str = "device", engine=None) -> np.ndarray:
+    """scikit-learn's ``silhouette_samples(vectors, labels, metric=metric)``: every point's (b − a) / max(a, b), a the mean distance
+    to the other points of its cluster and b the least mean distance to another cluster; a cluster of one scores 0.  ``labels`` are
+    arbitrary integers.  ``noise="cluster"`` is scikit-learn's and the reference's rule: label −1 is one more cluster;
+    ``noise="exclude"`` leaves those rows out and returns NaN for them.  ``cosine`` is 1 − dot on unit rows; for the plda metric
+    the vectors are already in the model's space and the distance is −LLR measured from the smallest one between two of the points
+    (−LLR is signed, and the quotient ranks clusterings only for a distance that is never negative; one more sweep finds that
+    pair, and a and b move by the same amount: ``silhouette_from_means``).  The device
+    sums every cluster's distances inside the pair sweep (``stats.silhouette``): no N × N array.  Fewer than 2 labels, more than
+    N − 1, vectors that are not finite and a length mismatch raise ``ValueError``."""
+    return _silhouette(vectors, labels, metric, plda, noise, backend, engine)[0]
+
+
+def silhouette_score(vectors, labels, metric="cosine", plda=None, noise: str = "cluster", backend: str = "device", engine=None) -> float:
+    """The mean of ``silhouette_samples`` over the rows that took part (the reference's ``metrics.silhouette_score``), on the host."""
+    s, keep = _silhouette(vectors, labels, metric, plda, noise, backend, engine)
+    return float(np.mean(s[keep]))
+
+
+def cluster_vectors(ivectors, cluster_type, metric="cosine", plda=None, strict: bool = True, backend: str = "device", engine=None, **kwargs):
+    """The reference's ``cluster_matrix`` to its end for the two cluster types that are built: (labels, silhouette score).
+    ``ClusterType.dbscan`` goes to ``cluster_matrix`` and ``ClusterType.hdbscan`` to ``hdbscan_matrix`` with ``kwargs``; the score
+    then follows the reference's ``score_metric``: hdbscan with cosine scores euclidean distances on unit rows, dbscan with cosine
+    cosine distances, plda −LLR (from its smallest value: ``silhouette_samples``), label −1 one more cluster.  One label raises the reference's ``ValueError`` under ``strict`` and
+    gives ``score = None`` without; as many labels as points give ``score = None``."""
+    ctype = cluster_type if isinstance(cluster_type, ClusterType) else ClusterType(getattr(cluster_type, "value", cluster_type))
+    metric = _metric(metric)
+    if ctype is ClusterType.dbscan:
+        labels = cluster_matrix(ivectors, ctype, metric, plda=plda, strict=False, backend=backend, engine=engine, **kwargs)
+    elif ctype is ClusterType.hdbscan:
+        labels = hdbscan_matrix(ivectors, metric, plda=plda, strict=False, backend=backend, engine=engine, **kwargs)
+    else:
+        raise NotImplementedError(f"The cluster type '{ctype}' is not supported: {ClusterType.dbscan} and {ClusterType.hdbscan} are built")
+    found = np.unique(labels).shape[0]
+    if found == 1 and strict:
+        raise ValueError(ONE_CLUSTER)
+    if not 2 <= found <= labels.shape[0] - 1:
+        return labels, None
+    to_fit, score_metric = _vectors(ivectors, metric, plda), metric
+    if ctype is ClusterType.hdbscan and metric is DistanceMetric.cosine:
+        to_fit, score_metric = np.ascontiguousarray(stats._unit_rows(to_fit)), DistanceMetric.euclidean
+    return labels, silhouette_score(to_fit, labels, score_metric, plda, "cluster", backend, engine)
+
+
+def cluster_vectors_utterances(utterance_ids: Sequence, ivectors, cluster_type=ClusterType.dbscan, **kwargs):
+    """({utterance: speaker name}, silhouette score) from ``cluster_vectors``; ``kwargs`` go to it."""
+    utterance_ids = list(utterance_ids)
+    x = np.atleast_2d(ivectors)
+    if len(utterance_ids) != x.shape[0]:
+        raise ValueError(f"{len(utterance_ids)} utterances for {x.shape[0]} vectors")
+    labels, score = cluster_vectors(x, cluster_type, **kwargs)
+    return dict(zip(utterance_ids, speaker_names(labels))), score
+
+
+__all__ = ["ClusterType", "DistanceMetric", "NoKneeError", "cluster_matrix", "cluster_utterances", "cluster_vectors",
+           "cluster_vectors_utterances", "distance_threshold", "hdbscan_matrix", "hdbscan_utterances", "knee_index", "kth_neighbor_distances",
+           "silhouette_from_means", "silhouette_samples", "silhouette_score", "speaker_names"]

@@ -24,7 +24,8 @@ enum { MFA_K_MFCC = 0, MFA_K_CMVN = 1, MFA_K_FEATS = 2, MFA_K_GMM = 3, MFA_K_VIT
        MFA_K_IVEC_PRUNE = 29, MFA_K_IVEC_UTT = 30, MFA_K_IVEC_SCATTER = 31, MFA_K_IVEC_PRODUCTS = 32, MFA_K_IVEC_SOLVE = 33, MFA_K_IVEC_ACC = 34,
        MFA_K_PLDA_TRANSFORM = 35, MFA_K_PLDA_PREPARE = 36, MFA_K_PLDA_SWEEP = 37, MFA_K_PLDA_MERGE = 38,
        MFA_K_CLUSTER_SYMM = 39, MFA_K_CLUSTER_DEGREE = 40, MFA_K_CLUSTER_ROUNDS = 41, MFA_K_CLUSTER_LABELS = 42,
-       MFA_K_COUNT = 43 };
+       MFA_K_SIL_OFFSETS = 43, MFA_K_SIL_SWEEP = 44,
+       MFA_K_COUNT = 45 };
 
 // The device operations of dev_buf.hpp as HIP calls.  Every device pointer a context owns is an MfaBuf: freed with the
 // context, grown with reserve(), tables replaced as a set with dev_upload_commit<MfaHipDev>().

@@ -139,6 +139,16 @@ int refuse(mfa_ctx *c, const char *who, int rc, int D, int k, long long n) {
 
 }  // namespace
 
+int mfa_pair_prepare(mfa_ctx *c, const double *d_x, int32_t metric, const double *d_psi, int64_t N, int D, double *d_y, double *d_q,
+                     int32_t *d_flags) {
+  KernelTimer kt(c, MFA_K_PLDA_PREPARE);
+  MFA_HIP_CHECK(c, hipMemsetAsync(d_flags, 0, 8, c->stream));
+  hipLaunchKernelGGL(pair_prepare_kernel, dim3(blocks(N, 256)), dim3(256), 0, c->stream, d_x, metric, d_psi, N, D, d_y, d_q, d_flags);
+  MFA_HIP_CHECK(c, hipGetLastError());
+  MFA_DEBUG_POINT(c, "pair_prepare_kernel N=%lld D=%d metric=%d", (long long)N, D, metric);
+  return 0;
+}
+
 extern "C" MFA_API int mfa_hdbscan_core_batch(mfa_ctx *c, const double *d_x, int64_t N, int32_t D, int32_t metric, const double *d_psi, int32_t k,
                                               double *d_y, double *d_q, double *d_core, double *d_v) {
   MFA_HIP_CHECK(c, hipSetDevice(c->device));
@@ -153,13 +163,7 @@ extern "C" MFA_API int mfa_hdbscan_core_batch(mfa_ctx *c, const double *d_x, int
   const size_t o_flags = op.ws.take(8);
   if (op.ws.reserve(c, "the HDBSCAN workspace")) return -1;
   int32_t *flags = op.ws.at<int32_t>(o_flags);
-  {
-    KernelTimer kt(c, MFA_K_PLDA_PREPARE);
-    MFA_HIP_CHECK(c, hipMemsetAsync(flags, 0, 8, c->stream));
-    hipLaunchKernelGGL(pair_prepare_kernel, dim3(blocks(N, 256)), dim3(256), 0, c->stream, d_x, metric, d_psi, N, D, d_y, d_q, flags);
-    MFA_HIP_CHECK(c, hipGetLastError());
-    MFA_DEBUG_POINT(c, "pair_prepare_kernel N=%lld D=%d metric=%d", (long long)N, D, metric);
-  }
+  if (mfa_pair_prepare(c, d_x, metric, d_psi, N, D, d_y, d_q, flags)) return -1;
   int32_t h_flags[2] = {0, 0};
   MFA_HIP_CHECK(c, hipMemcpyAsync(h_flags, flags, 8, hipMemcpyDeviceToHost, c->stream));
   MFA_HIP_CHECK(c, hipStreamSynchronize(c->stream));

@@ -24,3 +24,11 @@ int mfa_pair_core_sweep(mfa_ctx *c, const MfaPairSweep &op, const double *d_y, c
 // d_row_m, d_row_j [N]: every row's best edge to a point of another component under edge_better (j = −1: none).
 int mfa_pair_edge_sweep(mfa_ctx *c, const MfaPairSweep &op, const double *d_y, const double *d_q, double w, const double *d_core,
                         const int32_t *d_comp, int64_t N, int D, double *d_row_m, int32_t *d_row_j);
+// The silhouette consumer (silhouette_math.hpp), always one column pass: d_off [C + 1] the clusters' column ranges (checked by
+// the caller: the kernel trusts them), d_own [N] every row's cluster; d_sil [N], and d_a, d_b, d_bj [N], d_v [N][N] or NULL.
+int mfa_pair_silhouette_sweep(mfa_ctx *c, const MfaPairSweep &op, const double *d_y, const double *d_q, double w, int32_t metric,
+                              const int32_t *d_off, int32_t C, const int32_t *d_own, int64_t N, int D, double *d_sil, double *d_a, double *d_b,
+                              int32_t *d_bj, double *d_v);
+// The pair form's prepare step (hdbscan.hip): d_y [N][D], d_q [N] from d_x; d_flags (two int32, zeroed here) [0] |= a bad psi.
+int mfa_pair_prepare(mfa_ctx *c, const double *d_x, int32_t metric, const double *d_psi, int64_t N, int D, double *d_y, double *d_q,
+                     int32_t *d_flags);

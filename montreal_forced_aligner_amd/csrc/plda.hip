@@ -19,6 +19,8 @@
 //   neighbours neighbor_sweep_kernel, the same sweep body (sweep_body<kBits>) with a fourth consumer: a row's 64 columns of a
 //              step against a threshold, one ballot, is a finished word of the neighbour bit matrix that cluster.hip works on;
 //              metric_prepare_kernel gives the same sweep the euclidean and dot metrics (mfa_neighbor_bits_batch)
+//   silhouette pair_sil_sweep_kernel, the same sweep body (sweep_body<kSweepSil>) on the pair form with the columns ordered by
+//              cluster: a lane owns (row = lane & 15, quarter = lane >> 4) and keeps one running sum, a, b and bj
 // The lists have one strict order (plda_better): whatever the passes are, the merged list is the first k of that order.  No
 // atomics; every sum has a fixed order: two calls on the same input give the same bits.
 #include <algorithm>
@@ -29,12 +31,14 @@
 #include "hdbscan_math.hpp"
 #include "pair_sweep.hpp"
 #include "plda_math.hpp"
+#include "silhouette_math.hpp"
 
 namespace {
 
 constexpr int kRowBlock = 64;              // test rows of a sweep workgroup: 16 per wavefront
 constexpr int kColStep = 64;               // columns of a step: 4 blocks of the instruction's 16, afterwards one per lane
 constexpr int kTileStride = 80;            // doubles per LDS tile row: 16 mod 32, so the four rows a store touches share no bank
+constexpr int kSilTileStride = 81;         // the silhouette consumer's: 1 mod 32, so an 8-byte read's 32 lanes (16 rows, 2 quarters) share no bank
 constexpr int kMinPassCols = 512;          // an automatic split leaves a pass at least this many columns
 #ifndef PLDA_STEPS_IN_FLIGHT
 #define PLDA_STEPS_IN_FLIGHT 2
@@ -173,7 +177,17 @@ struct PairIn {
   double *part_m; int32_t *part_j; // [passes][N]
 };
 
-constexpr int kSweepPlain = 0, kSweepBits = 1, kSweepCore = 2, kSweepEdge = 3;
+// The silhouette consumer's inputs and outputs (silhouette_math.hpp): the metric of the distance, the clusters' column ranges
+// and every row's cluster; q and w come in PairIn.
+struct SilIn {
+  int32_t metric, C;
+  const int32_t *off, *own;        // [C + 1], [N]
+  double *sil, *a, *b;             // [N]; a, b or NULL
+  int32_t *bj;                     // [N] or NULL
+  double *v;                       // [N][N] or NULL
+};
+
+constexpr int kSweepPlain = 0, kSweepBits = 1, kSweepCore = 2, kSweepEdge = 3, kSweepSil = 4;
 
 // grid (blocks of 64 rows, passes).  Lane l of a step gives A[i = l & 15][k = l >> 4] = the test row's p_k (squared for the
 // first instruction) and B[k][j = l & 15] = A_jk or B_jk of column j.  Register r of lane l is D[row = (l >> 4) + 4 r][col =
@@ -184,10 +198,17 @@ constexpr int kSweepPlain = 0, kSweepBits = 1, kSweepCore = 2, kSweepEdge = 3;
 // (i, j) and (j, i).  A row's q, core score and component sit in lane (row & 15) and are broadcast per row; a column's are
 // read once per 64-column step.  Core: the k-nearest lists on s, diagonal excluded.  Edge: one running best per lane per row
 // under edge_better (ls, li: the score and the far end), one butterfly per row at the end of the pass.
+// The silhouette mode (kSweepSil; sl is not looked at without it) is the pair form's sum again, in one column pass (grid.y ==
+// 1: a cluster is never split).  The columns are ordered by cluster, so a cluster boundary is the same column for every row:
+// after staging, lane l owns row l & 15 and reads that row's 16 columns of quarter l >> 4 from the tile (contiguous; the tile's
+// stride is kSilTileStride here), makes distances of them and adds them, columns ascending, into one running sum; the
+// clusters that meet the step are walked in wave-uniform segments (a column outside the segment, a padding column and the
+// diagonal add +0).  At a cluster's end the four quarters are added with two xor shuffles (16, then 32: (P0 + P1) + (P2 + P3)
+// in every lane) and the mean is folded into the row's a or b (sil_fold).  The state of a lane is one sum, a, b, bj.
 template <int kMode>
-__device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &b, const PairIn &pr) {
-  constexpr bool kBits = kMode == kSweepBits, kPair = kMode == kSweepCore || kMode == kSweepEdge;
-  __shared__ double tile[4][16][kTileStride];
+__device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &b, const PairIn &pr, const SilIn &sl) {
+  constexpr bool kBits = kMode == kSweepBits, kPair = kMode == kSweepCore || kMode == kSweepEdge, kSil = kMode == kSweepSil;
+  __shared__ double tile[4][16][kSil ? kSilTileStride : kTileStride];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lc = lane & 15, lk = lane >> 4;
   const int64_t row0 = (int64_t)blockIdx.x * kRowBlock + wave * 16;
   const bool wave_has = row0 < p.Nt;
@@ -201,10 +222,14 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &
   const double *Ar = p.test + (size_t)(arow_in ? arow : 0) * p.D;
   double q_l = 0.0, core_l = 0.0;                    // of row row0 + (lane & 15)
   int32_t comp_l = -1;
-  if constexpr (kPair) {
+  if constexpr (kPair || kSil) {
     q_l = arow_in ? pr.q[arow] : 0.0;
     if constexpr (kMode == kSweepEdge) { core_l = arow_in ? pr.core[arow] : 0.0; comp_l = arow_in ? pr.comp[arow] : -1; }
   }
+  SilRow sr = sil_row_init();                        // kSil: of row row0 + (lane & 15), the same in its four lanes
+  double sil_sum = 0.0;                              // this lane's partial of the cluster sil_c
+  int32_t sil_c = 0, own_l = -1;                     // sil_c: the cluster that holds the next column (wave-uniform)
+  if constexpr (kSil) own_l = arow_in ? sl.own[arow] : -1;
   for (int64_t c0 = c_begin; c0 < c_end; c0 += kColStep) {
     double4_t acc[4];
     if (wave_has) {
@@ -228,7 +253,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &
         }
       }
     }
-    if (!kBits && !kPair && p.keff == 0) continue;   // the same for the whole grid
+    if (!kBits && !kPair && !kSil && p.keff == 0) continue;   // the same for the whole grid
     __syncthreads();                                 // the previous step's readers are done
     if (wave_has) {
 #pragma unroll
@@ -239,6 +264,34 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &
     }
     __syncthreads();
     if (!wave_has) continue;
+    if constexpr (kSil) {
+      const int64_t colq = c0 + 16 * lk;             // this lane's first column of the step
+      double d[16];
+#pragma unroll
+      for (int t = 0; t < 16; t++) {
+        const int64_t cl = colq + t;
+        const bool cin = cl < p.Ns;
+        const double s = pair_score(q_l, cin ? pr.q[cl] : 0.0, pr.w, tile[wave][lc][16 * lk + t]);
+        if (sl.v && cin && arow_in) sl.v[(size_t)arow * p.Ns + cl] = s;
+        d[t] = cin && cl != arow ? sil_distance(sl.metric, s) : 0.0;
+      }
+      const int64_t step_end = min(c0 + kColStep, (int64_t)p.Ns);
+      int64_t pos = c0;
+      while (pos < step_end && sil_c < sl.C) {       // wave-uniform: the segments of the clusters that meet this step
+        const int64_t cl_end = sl.off[sil_c + 1], seg_end = min(cl_end, step_end);
+        const int lo = (int)max(pos - colq, (int64_t)0), hi = (int)min(seg_end - colq, (int64_t)16);   // this lane's part [lo, hi)
+#pragma unroll
+        for (int t = 0; t < 16; t++) sil_sum += t >= lo && t < hi ? d[t] : 0.0;
+        if (seg_end == cl_end) {                     // the cluster ends here
+          const double h = sil_sum + __shfl_xor(sil_sum, 16);
+          sil_fold(sr, own_l, sil_c, h + __shfl_xor(h, 32), cl_end - (int64_t)sl.off[sil_c]);
+          sil_sum = 0.0;
+          sil_c++;
+        }
+        pos = seg_end;
+      }
+      continue;
+    }
     const int64_t col = c0 + lane;
     if constexpr (kBits) {
       // a ballot per row is the row's finished word; lane rr keeps row rr's, so that the 16 words leave in one vector store.
@@ -287,6 +340,14 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &
       plda_insert(ls[rr], li[rr], s, (int32_t)col, cand, p.keff, lane);
     }
   }
+  if constexpr (kSil) {
+    if (!arow_in || lk != 0) return;
+    sl.sil[arow] = sil_finish((int64_t)sl.off[own_l + 1] - sl.off[own_l], sr.a, sr.b);
+    if (sl.a) sl.a[arow] = sr.a;
+    if (sl.b) sl.b[arow] = sr.b;
+    if (sl.bj) sl.bj[arow] = sr.bj;
+    return;
+  }
   if constexpr (kMode == kSweepEdge) {
     if (!wave_has) return;
 #pragma unroll
@@ -316,10 +377,11 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p, const BitsOut &
   }
 }
 
-__global__ __launch_bounds__(256) void plda_sweep_kernel(SweepParams p) { sweep_body<kSweepPlain>(p, BitsOut{nullptr, 0.0}, PairIn{}); }
-__global__ __launch_bounds__(256) void neighbor_sweep_kernel(SweepParams p, BitsOut b) { sweep_body<kSweepBits>(p, b, PairIn{}); }
-__global__ __launch_bounds__(256) void pair_core_sweep_kernel(SweepParams p, PairIn pr) { sweep_body<kSweepCore>(p, BitsOut{nullptr, 0.0}, pr); }
-__global__ __launch_bounds__(256) void pair_edge_sweep_kernel(SweepParams p, PairIn pr) { sweep_body<kSweepEdge>(p, BitsOut{nullptr, 0.0}, pr); }
+__global__ __launch_bounds__(256) void plda_sweep_kernel(SweepParams p) { sweep_body<kSweepPlain>(p, BitsOut{nullptr, 0.0}, PairIn{}, SilIn{}); }
+__global__ __launch_bounds__(256) void neighbor_sweep_kernel(SweepParams p, BitsOut b) { sweep_body<kSweepBits>(p, b, PairIn{}, SilIn{}); }
+__global__ __launch_bounds__(256) void pair_core_sweep_kernel(SweepParams p, PairIn pr) { sweep_body<kSweepCore>(p, BitsOut{nullptr, 0.0}, pr, SilIn{}); }
+__global__ __launch_bounds__(256) void pair_edge_sweep_kernel(SweepParams p, PairIn pr) { sweep_body<kSweepEdge>(p, BitsOut{nullptr, 0.0}, pr, SilIn{}); }
+__global__ __launch_bounds__(256) void pair_sil_sweep_kernel(SweepParams p, PairIn pr, SilIn sl) { sweep_body<kSweepSil>(p, BitsOut{nullptr, 0.0}, pr, sl); }
 
 // The pair form's operands, a thread per padded column j: A = 0, B = y as [k][column], c = 0.
 __global__ __launch_bounds__(256) void pair_pack_kernel(const double *y, int Ns, int D, int Dpad, int64_t Nspad, double *At, double *Bt, double *c) {
@@ -583,6 +645,19 @@ int mfa_pair_edge_sweep(mfa_ctx *c, const MfaPairSweep &op, const double *d_y, c
                      op.ws.at<int32_t>(op.o_pi), op.passes, N, d_row_m, d_row_j);
   MFA_HIP_CHECK(c, hipGetLastError());
   MFA_DEBUG_POINT(c, "pair_edge_merge_kernel N=%lld passes=%d", (long long)N, op.passes);
+  return 0;
+}
+
+int mfa_pair_silhouette_sweep(mfa_ctx *c, const MfaPairSweep &op, const double *d_y, const double *d_q, double w, int32_t metric,
+                              const int32_t *d_off, int32_t C, const int32_t *d_own, int64_t N, int D, double *d_sil, double *d_a, double *d_b,
+                              int32_t *d_bj, double *d_v) {
+  SweepParams sp = pair_params(op, d_y, N, D, 0);
+  sp.cols_per_pass = op.Nspad;                         // one pass, whatever the plan says: a cluster is never split
+  KernelTimer kt(c, MFA_K_SIL_SWEEP);
+  hipLaunchKernelGGL(pair_sil_sweep_kernel, dim3((unsigned)((N + kRowBlock - 1) / kRowBlock), 1), dim3(256), 0, c->stream, sp,
+                     PairIn{d_q, w, nullptr, nullptr, nullptr, nullptr, nullptr}, SilIn{metric, C, d_off, d_own, d_sil, d_a, d_b, d_bj, d_v});
+  MFA_HIP_CHECK(c, hipGetLastError());
+  MFA_DEBUG_POINT(c, "pair_sil_sweep_kernel N=%lld D=%d C=%d", (long long)N, D, C);
   return 0;
 }
 

@@ -45,7 +45,8 @@ KERNEL_SLOTS = ("mfcc", "cmvn", "feats", "gmm", "viterbi", "resample", "pitch", 
                 "ubm_select", "ubm_post", "ubm_sums", "ubm_reduce",
                 "ivec_prune", "ivec_utt", "ivec_scatter", "ivec_products", "ivec_solve", "ivec_acc",
                 "plda_transform", "plda_prepare", "plda_sweep", "plda_merge",
-                "cluster_symmetrise", "cluster_degree", "cluster_rounds", "cluster_labels")
+                "cluster_symmetrise", "cluster_degree", "cluster_rounds", "cluster_labels",
+                "silhouette_offsets", "silhouette_sweep")
 
 
 def _out_ptrs(out: Dict[str, Optional[torch.Tensor]]):
@@ -345,6 +346,12 @@ class AlignmentEngine(GraphPacking, FrontEndStages):
                                                        _ptr(lo), _ptr(hi), _ptr(score), C.byref(n_edges), C.byref(rounds)),
               "mfa_hdbscan_mst_batch")
         return int(n_edges.value), int(rounds.value)
+
+    def _launch_silhouette(self, x, metric: int, psi, off, sil, a, b, bj, v) -> None:
+        """Every row's silhouette coefficient under the cluster column ranges ``off`` (int32 [C + 1]; mfa_silhouette_batch)."""
+        check(self.ctx, self.lib.mfa_silhouette_batch(self.ctx, _ptr(x), int(x.shape[0]), int(x.shape[1]), int(metric), _ptr(psi), _ptr(off),
+                                                      int(off.shape[0]) - 1, _ptr(sil), _ptr(a), _ptr(b), _ptr(bj), _ptr(v)),
+              "mfa_silhouette_batch")
 
     def _launch_scan(self, values, d_frame_off, n_utt: int, total: int, scan, totals) -> None:
         check(self.ctx, self.lib.mfa_vad_scan_batch(self.ctx, _ptr(values), _ptr(d_frame_off), n_utt, total, _ptr(scan),

@@ -1879,3 +1879,29 @@ def hdbscan_matrix(ivectors: np.ndarray, metric: DistanceMetric = DistanceMetric
         raise TypeError(f"hdbscan_matrix: unexpected keyword arguments {sorted(kwargs)}")
     backend = known.get("backend", "device")
     return _cluster.hdbscan_matrix(ivectors, metric, strict=strict, engine=get_engine() if backend == "device" else None, **known)
+
+
+def cluster_vectors(ivectors: np.ndarray, cluster_type: ClusterType, metric: DistanceMetric = DistanceMetric.cosine, strict=True,
+                    no_visuals=False, working_directory=None, **kwargs):
+    """The reference's ``cluster_matrix`` to its end on the process's engine (``cluster.cluster_vectors``): (labels, the silhouette
+    score it logs), for ``ClusterType.dbscan`` and ``ClusterType.hdbscan``.  ``kwargs`` carry ``distance_threshold``, ``plda``,
+    ``min_cluster_size`` and, for hdbscan, ``min_samples``; nothing is drawn."""
+    from . import cluster as _cluster
+    known = {k: kwargs.pop(k) for k in ("distance_threshold", "plda", "min_cluster_size", "min_samples", "backend") if k in kwargs}
+    if kwargs:
+        raise TypeError(f"cluster_vectors: unexpected keyword arguments {sorted(kwargs)}")
+    backend = known.get("backend", "device")
+    return _cluster.cluster_vectors(ivectors, cluster_type, metric, strict=strict, engine=get_engine() if backend == "device" else None, **known)
+
+
+def silhouette_samples(X: np.ndarray, labels, metric="euclidean", plda=None, noise: str = "cluster", backend: str = "device") -> np.ndarray:
+    """``sklearn.metrics.silhouette_samples(X, labels, metric=metric)`` on the process's engine (``cluster.silhouette_samples``);
+    ``metric="plda"`` with ``plda=`` takes the place of the reference's callable ``plda.distance``."""
+    from . import cluster as _cluster
+    return _cluster.silhouette_samples(X, labels, metric, plda, noise, backend, get_engine() if backend == "device" else None)
+
+
+def silhouette_score(X: np.ndarray, labels, metric="euclidean", plda=None, noise: str = "cluster", backend: str = "device") -> float:
+    """``sklearn.metrics.silhouette_score(X, labels, metric=metric)`` (MFA/diarization/multiprocessing.py:452) on the process's engine."""
+    from . import cluster as _cluster
+    return _cluster.silhouette_score(X, labels, metric, plda, noise, backend, get_engine() if backend == "device" else None)

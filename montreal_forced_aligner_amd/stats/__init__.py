@@ -6,7 +6,7 @@ methods: they use its ``lib``, ``ctx``, ``device``, ``_dev``, the loaded ``gmm``
   ``speaker``    the diagonal UBM (Gaussian selection, global statistics) and the i-vector extractor (pruning, utterance
                  statistics, E-step)
   ``pairs``      the PLDA transform, the sweep for any metric and its consumers (scores, best, k-NN, neighbour bits),
-                 ``dbscan_from_bits``, and HDBSCAN's pair form, core scores and spanning tree
+                 ``dbscan_from_bits``, HDBSCAN's pair form, core scores and spanning tree, and the silhouette coefficients
   ``_common``    what their wrappers share: the device-model cache, ``GmmStats`` to accumulators and back, frame tables
 
 A new stage goes into the module of its role (or a new one beside them) and is re-exported here; code inside the package
@@ -22,7 +22,7 @@ from .pairs import (METRIC_CODES, NEIGHBOR_BITS_BYTES, PLDA_BLOCK_BYTES, PLDA_MA
                     metric_sweep, metric_sweep_host, mreach_mst, mreach_mst_host, neighbor_bits, neighbor_bits_host, pair_metric,
                     pair_prepare, pair_prepare_host, plda_classify, plda_classify_host, plda_knn, plda_knn_host, plda_prepare_host,
                     plda_scores, plda_scores_host, plda_sweep, plda_sweep_host, plda_transform, plda_transform_host, score_threshold,
-                    score_to_distance)
+                    score_to_distance, silhouette, silhouette_host)
 from .speaker import (gaussian_selection, gaussian_selection_host, ivector_estep, ivector_estep_host,   # noqa: F401
                       ivector_utterance_statistics, ivector_utterance_statistics_host, prune_posteriors, prune_posteriors_host,
                       ubm_statistics, ubm_statistics_host)

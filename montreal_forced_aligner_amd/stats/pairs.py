@@ -1,6 +1,6 @@
 """Statistics over pairs of vectors: the PLDA transform, the sweep of every test vector over every train vector for any metric
-and its consumers (scores, best, k-NN, neighbour bits), DBSCAN on the bits, and HDBSCAN's pair form, core scores and spanning
-tree; device call and host twin each.
+and its consumers (scores, best, k-NN, neighbour bits), DBSCAN on the bits, HDBSCAN's pair form, core scores and spanning
+tree, and the silhouette coefficients; device call and host twin each.
 """
 from __future__ import annotations
 
@@ -514,3 +514,63 @@ def mreach_mst_host(metric, y, q, core, v=None):
     f = int(found.value)
     flo, fhi, fs = finish_tree(n, lo[:f], hi[:f], score[:f])
     return dict(lo=flo, hi=fhi, score=fs, found=f)
+
+
+# ---- Silhouette: every point's coefficient from the pair sweep, the columns ordered by cluster (include/mfa_hip.h "Silhouette") ---------
+_SILHOUETTE_TWIN_CODES = {-2: "dimension outside [1, 1024]", -4: "a psi entry that is not positive and finite", -5: "2^31 points or more",
+                          -6: "a number of clusters outside [2, the number of points]",
+                          -7: "offsets that are not 0 = off[0] < ... < off[C] = the number of points", -8: "an unknown metric"}
+
+
+def _silhouette_offsets(offsets) -> np.ndarray:
+    off = np.ascontiguousarray(offsets, dtype=np.int32)
+    if off.ndim != 1 or off.shape[0] < 1:
+        raise _lib.MfaHipError(f"silhouette: offsets {off.shape} (one more than the clusters)")
+    return off
+
+
+def _silhouette_result(sil, parts, v, code):
+    a, b, bj = parts if parts is not None else (None, None, None)
+    return dict(sil=sil, a=a, b=b, bj=bj, v=v, code=code)
+
+
+def silhouette(engine, metric, x, offsets, model=None, want_parts: bool = False, want_v: bool = False):
+    """Every row's silhouette coefficient (mfa_silhouette_batch) for rows ordered by cluster: cluster c is the rows
+    ``offsets[c] : offsets[c + 1]``.  dict(sil [n], a, b [n] and bj int32 [n] or None, v [n, n] or None, code) on the device.
+    ``metric`` as ``core_scores`` takes it: cosine is euclidean on unit rows there too; the cosine distance itself is "dot" on rows the
+    caller made unit length.  No n × n array is stored unless ``want_v``."""
+    code, unit, _ = pair_metric(metric)
+    x = _plda_vectors(engine, x, _metric_dim(code, model, x), "silhouette")
+    if unit:
+        x = _unit_rows(x)
+    n, dev = int(x.shape[0]), engine.device
+    off = torch.from_numpy(_silhouette_offsets(offsets)).to(dev)
+    psi = _plda_device_model(engine, model)[2] if code == 0 else None
+    sil = torch.empty(n, dtype=torch.float64, device=dev)
+    parts = (torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
+             torch.empty(n, dtype=torch.int32, device=dev)) if want_parts else None
+    v = torch.empty((n, n), dtype=torch.float64, device=dev) if want_v else None
+    engine._launch_silhouette(x, code, psi, off, sil, *(parts or (None, None, None)), v)
+    return _silhouette_result(sil, parts, v, code)
+
+
+def silhouette_host(metric, x, offsets, model=None, want_parts: bool = False, want_v: bool = False, v=None):
+    """``silhouette`` on the host twin: numpy arrays.  ``v``: a score matrix to take the distances from (tests: the device's own)."""
+    code, unit, _ = pair_metric(metric)
+    x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+    if _metric_dim(code, model, x) != x.shape[1]:
+        raise _lib.MfaHipError(f"silhouette_host: vectors {x.shape} for a model of dimension {model.dim}")
+    if unit:
+        x = np.ascontiguousarray(_unit_rows(x))
+    n = int(x.shape[0])
+    off = _silhouette_offsets(offsets)
+    psi = np.ascontiguousarray(model.psi, dtype=np.float64) if code == 0 else None
+    v_in = None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+    if v_in is not None and v_in.shape != (n, n):
+        raise _lib.MfaHipError(f"silhouette_host: a score matrix {v_in.shape} for {n} points")
+    sil = np.empty(n)
+    parts = (np.empty(n), np.empty(n), np.empty(n, np.int32)) if want_parts else None
+    out_v = np.empty((n, n)) if want_v else None
+    twin_call("mfa_debug_silhouette_host", _SILHOUETTE_TWIN_CODES, x, n, int(x.shape[1]), code, psi, off, int(off.shape[0]) - 1, sil,
+              *(parts or (None, None, None)), out_v, v_in)
+    return _silhouette_result(sil, parts, out_v, code)
