@@ -536,6 +536,29 @@ struct FasterDecoder {
   // optional (design studies of the device's lazy-scoring bands): per frame, over the tokens ENTERING the frame,
   // {min of depth[s][1], max of depth[s][0], number of tokens, depth[.][0] of the best token}
   const int32_t *stat_depth = nullptr; int32_t *stat_band = nullptr;
+  // TEST ONLY (orc_align_feats_trace).  `variant`: 0 = FasterDecoder as it is; 1 … 6 = one rule deliberately wrong, so that a
+  // test case can show that it tells right from wrong:
+  //   1  tokens processed in order of state number instead of hash-list order
+  //   2  hash-list order with the buckets ignored: every state a bucket of its own (= order of first creation)
+  //   3  min_active cutoff: the smallest cost with min_active + 1 costs strictly below it (`<` for `<=` in the selection)
+  //   4  a token expands when cost <= cutoff instead of cost < cutoff
+  //   5  among candidates of equal cost for one state the last one wins instead of the first
+  //   6  the running cutoff is not seeded from the best token's arcs before the tokens are expanded
+  // `trace`: per frame kTraceCols counters of the pass being decoded, see orc_align_feats_trace.
+  int variant = 0; int32_t *trace = nullptr; bool chose_min_active = false;
+  static constexpr int kTraceCols = 8;
+
+  int ListSize() const { int n = 0; for (int e = toks.GetList(); e != -1; e = toks.elems[e].tail) n++; return n; }
+
+  // variants 1 and 2: relink the list just taken from the hash (its buckets are already cleared) in the wrong order
+  int Reorder(int head) {
+    std::vector<int> v;
+    for (int e = head; e != -1; e = toks.elems[e].tail) v.push_back(e);
+    if (variant == 1) std::stable_sort(v.begin(), v.end(), [&](int a, int b) { return toks.elems[a].key < toks.elems[b].key; });
+    else std::sort(v.begin(), v.end());              // pool index = order of insertion
+    for (size_t i = 0; i < v.size(); i++) toks.elems[v[i]].tail = i + 1 < v.size() ? v[i + 1] : -1;
+    return v.empty() ? -1 : v[0];
+  }
 
   FasterDecoder(const Graph &gr, float bm, int32_t maxa, int32_t mina, float bd, float hr)
       : g(gr), beam(bm), max_active(maxa), min_active(mina), beam_delta(bd), hash_ratio(hr) { toks.SetSize(1000); }
@@ -570,7 +593,7 @@ struct FasterDecoder {
       double w = pool[toks.elems[e].val].cost; tmp.push_back(w);
       if (w < best_cost) { best_cost = w; *best_elem = e; }
     }
-    *tok_count = count;
+    *tok_count = count; chose_min_active = false;
     double beam_cutoff = best_cost + beam, min_active_cutoff = std::numeric_limits<double>::infinity(),
            max_active_cutoff = std::numeric_limits<double>::infinity();
     if (tmp.size() > (size_t)max_active) {
@@ -584,8 +607,17 @@ struct FasterDecoder {
         std::nth_element(tmp.begin(), tmp.begin() + min_active,
                          tmp.size() > (size_t)max_active ? tmp.begin() + max_active : tmp.end());
         min_active_cutoff = tmp[min_active];
+        if (variant == 3) {
+          min_active_cutoff = std::numeric_limits<double>::infinity();
+          for (double w : tmp) {
+            size_t below = 0;
+            for (double x : tmp) below += x < w;
+            if (below >= (size_t)min_active + 1 && w < min_active_cutoff) min_active_cutoff = w;
+          }
+        }
       }
     }
+    chose_min_active = min_active_cutoff > beam_cutoff;
     if (min_active_cutoff > beam_cutoff) { *adaptive_beam = (float)(min_active_cutoff - best_cost + beam_delta); return min_active_cutoff; }
     *adaptive_beam = beam; return beam_cutoff;
   }
@@ -593,6 +625,7 @@ struct FasterDecoder {
   double ProcessEmitting(const Decodable &dec) {
     int frame = num_frames_decoded;
     int last_toks = toks.Clear();
+    if (variant == 1 || variant == 2) last_toks = Reorder(last_toks);
     size_t tok_cnt; float adaptive_beam; int best_elem = -1;
     double weight_cutoff = GetCutoff(last_toks, &tok_cnt, &adaptive_beam, &best_elem);
     if (stat_depth && stat_band) {
@@ -608,7 +641,7 @@ struct FasterDecoder {
     size_t new_sz = (size_t)((float)tok_cnt * hash_ratio);  // PossiblyResizeHash
     if (new_sz > toks.Size()) toks.SetSize(new_sz);
     double next_weight_cutoff = std::numeric_limits<double>::infinity();
-    if (best_elem != -1) {
+    if (best_elem != -1 && variant != 6) {
       int32_t state = toks.elems[best_elem].key; int tok = toks.elems[best_elem].val;
       for (int64_t a = g.arc_off[state]; a < g.arc_off[state + 1]; a++) {
         const orc_arc &arc = g.arcs[a];
@@ -619,9 +652,14 @@ struct FasterDecoder {
         }
       }
     }
+    int32_t n_under = 0, n_cand = 0, n_at_cut = 0, max_narc = 0;
     for (int e = last_toks; e != -1; e = toks.elems[e].tail) {
       int32_t state = toks.elems[e].key; int tok = toks.elems[e].val;
-      if (pool[tok].cost < weight_cutoff) {
+      if (pool[tok].cost == weight_cutoff) n_at_cut++;
+      if (variant == 4 ? pool[tok].cost <= weight_cutoff : pool[tok].cost < weight_cutoff) {
+        n_under++;
+        { int32_t k = 0; for (int64_t a = g.arc_off[state]; a < g.arc_off[state + 1]; a++) k += g.arcs[a].ilabel != 0;
+          n_cand += k; max_narc = std::max(max_narc, k); }
         for (int64_t a = g.arc_off[state]; a < g.arc_off[state + 1]; a++) {
           orc_arc arc = g.arcs[a];
           if (arc.ilabel != 0) {
@@ -632,12 +670,18 @@ struct FasterDecoder {
               bool ins; int e_found = toks.Insert(arc.nextstate, new_tok, &ins);
               if (new_weight + adaptive_beam < next_weight_cutoff) next_weight_cutoff = new_weight + adaptive_beam;
               if (!ins) {
-                if (pool[toks.elems[e_found].val].cost > pool[new_tok].cost) toks.elems[e_found].val = new_tok;
+                const double old = pool[toks.elems[e_found].val].cost;
+                if (variant == 5 ? old >= pool[new_tok].cost : old > pool[new_tok].cost) toks.elems[e_found].val = new_tok;
               }
             }
           }
         }
       }
+    }
+    if (trace) {
+      int32_t *r = trace + (size_t)kTraceCols * frame;
+      r[0] = (int32_t)tok_cnt; r[1] = n_under; r[2] = n_cand; r[3] = ListSize(); r[4] = r[3];
+      r[5] = chose_min_active ? 1 : 0; r[6] = n_at_cut; r[7] = max_narc;
     }
     num_frames_decoded++;
     return next_weight_cutoff;
@@ -664,7 +708,10 @@ struct FasterDecoder {
 
   void Decode(const Decodable &dec) {
     InitDecoding();
-    while (num_frames_decoded < dec.T) { double c = ProcessEmitting(dec); ProcessNonemitting(c); }
+    while (num_frames_decoded < dec.T) {
+      double c = ProcessEmitting(dec); ProcessNonemitting(c);
+      if (trace) trace[(size_t)kTraceCols * (num_frames_decoded - 1) + 4] = ListSize();
+    }
   }
 
   bool ReachedFinal() const {
@@ -717,10 +764,11 @@ struct FasterDecoder {
 static int32_t align_with(const Graph &g, const Decodable &dec, int32_t T, float acoustic_scale, float beam, float retry_beam,
                           int32_t *ali, int32_t *words, int32_t cap_words, int32_t *n_words, float *like,
                           float *per_frame_loglike, int64_t *stats, const int32_t *stat_depth = nullptr,
-                          int32_t *stat_band = nullptr) {
+                          int32_t *stat_band = nullptr, int32_t variant = 0, int32_t *trace = nullptr) {
   FasterDecoder d(g, beam, std::numeric_limits<int32_t>::max(), 20, 0.5f, 2.0f);
-  d.stat_depth = stat_depth; d.stat_band = stat_band;
+  d.stat_depth = stat_depth; d.stat_band = stat_band; d.variant = variant; d.trace = trace;
   d.Decode(dec);
+  d.trace = nullptr;                       // (the trace is the first beam's pass)
   bool ans = d.ReachedFinal(); int status = 0;
   if (!ans && retry_beam != 0.0f) { status = 1; d.beam = retry_beam; d.Decode(dec); ans = d.ReachedFinal(); }
   if (stats) { stats[0] = d.stat_max_toks; stats[1] = d.stat_sum_toks; }
@@ -764,6 +812,31 @@ ORC_API int32_t orc_align_feats(int32_t num_states, int32_t start, const int64_t
   dec.pdf_offsets = pdf_offsets; dec.InitLazy(num_pdfs);
   int32_t st = align_with(g, dec, T, acoustic_scale, beam, retry_beam, ali, words, cap_words, n_words, like, per_frame_loglike, stats,
                           state_depth, frame_band);
+  if (stats) stats[2] = dec.evals;
+  return st;
+}
+
+// TEST ONLY: orc_align_feats with one decoder rule optionally wrong (FasterDecoder::variant; 0 = exact, the results of
+// orc_align_feats) and a trace of the first beam's pass, per frame t eight counters:
+//   [0] tokens entering the frame           [1] of them under the cutoff (they expand)
+//   [2] candidates = emitting arcs of [1]   [3] tokens created by ProcessEmitting (distinct destination states)
+//   [4] tokens after ProcessNonemitting     [5] 1 when GetCutoff took the min_active cutoff
+//                                               (also with min_active tokens or fewer: no cutoff at all)
+//   [6] tokens whose cost equals the cutoff [7] most emitting arcs of one expanding token
+ORC_API int32_t orc_align_feats_trace(int32_t num_states, int32_t start, const int64_t *arc_off, const orc_arc *arcs,
+                                      const float *final_w, const float *feats, int32_t T, int32_t D, const float *gconsts,
+                                      const float *means_invvars, const float *inv_vars, const int32_t *pdf_offsets,
+                                      int32_t num_pdfs, const int32_t *tid2pdf, float acoustic_scale, float beam, float retry_beam,
+                                      int32_t *ali, int32_t *words, int32_t cap_words, int32_t *n_words, float *like,
+                                      float *per_frame_loglike, int64_t *stats /*[3] or NULL*/, int32_t variant,
+                                      int32_t *trace /*[T][8] or NULL*/) {
+  if (start < 0 || num_states == 0) return 2;
+  Graph g{num_states, start, arc_off, arcs, final_w};
+  Decodable dec{nullptr, T, 0, tid2pdf, acoustic_scale};
+  dec.feats = feats; dec.D = D; dec.gconsts = gconsts; dec.means_invvars = means_invvars; dec.inv_vars = inv_vars;
+  dec.pdf_offsets = pdf_offsets; dec.InitLazy(num_pdfs);
+  int32_t st = align_with(g, dec, T, acoustic_scale, beam, retry_beam, ali, words, cap_words, n_words, like, per_frame_loglike, stats,
+                          nullptr, nullptr, variant, trace);
   if (stats) stats[2] = dec.evals;
   return st;
 }

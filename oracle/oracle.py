@@ -249,6 +249,45 @@ def align_feats(num_states, start, arc_offsets, arcs, final, feats, gconsts, mea
     return out
 
 
+TRACE_COLS = ("n_in", "n_under", "n_cand", "n_created", "n_closed", "min_active", "n_at_cutoff", "max_narc")
+VARIANTS = dict(exact=0, order_by_state=1, order_ignores_buckets=2, select_lt=3, expand_le=4, last_arc_wins=5, no_seed=6)
+
+
+def align_feats_trace(num_states, start, arc_offsets, arcs, final, feats, gconsts, means_invvars, inv_vars, pdf_offsets, tid2pdf,
+                      acoustic_scale, beam, retry_beam, variant="exact"):
+    """TEST ONLY.  ``align_feats`` (orc_align_feats_trace) with, optionally, one decoder rule deliberately wrong
+    (``VARIANTS``; "exact" gives align_feats' results) and ``trace``: int32 [T, 8] of the first beam's pass, columns
+    ``TRACE_COLS`` — per frame the tokens entering it, those under the cutoff, their candidates (emitting arcs), the tokens
+    created (before / after the epsilon closure), whether the min_active rule chose the cutoff, the tokens exactly at the
+    cutoff, and the most emitting arcs of one expanding token."""
+    arc_offsets = np.ascontiguousarray(arc_offsets, np.int64)
+    arcs = np.ascontiguousarray(arcs.astype(ARC_DTYPE))
+    final = np.ascontiguousarray(final, np.float32)
+    feats = np.ascontiguousarray(feats, np.float32)
+    gconsts = np.ascontiguousarray(gconsts, np.float32)
+    means_invvars = np.ascontiguousarray(means_invvars, np.float32)
+    inv_vars = np.ascontiguousarray(inv_vars, np.float32)
+    pdf_offsets = np.ascontiguousarray(pdf_offsets, np.int32)
+    tid2pdf = np.ascontiguousarray(np.maximum(tid2pdf, 0), np.int32)
+    T, D = feats.shape
+    ali = np.zeros(T, np.int32)
+    cap_words = T + 16
+    words = np.zeros(cap_words, np.int32)
+    n_words = C.c_int32(0)
+    like = C.c_float(0)
+    pf = np.zeros(T, np.float32)
+    stats = np.zeros(3, np.int64)
+    trace = np.zeros((T, len(TRACE_COLS)), np.int32)
+    fn = lib().orc_align_feats_trace
+    fn.restype = C.c_int32
+    st = fn(C.c_int32(num_states), C.c_int32(start), _p(arc_offsets), _p(arcs), _p(final), _p(feats), C.c_int32(T), C.c_int32(D),
+            _p(gconsts), _p(means_invvars), _p(inv_vars), _p(pdf_offsets), C.c_int32(pdf_offsets.shape[0] - 1), _p(tid2pdf),
+            C.c_float(acoustic_scale), C.c_float(beam), C.c_float(retry_beam), _p(ali), _p(words), C.c_int32(cap_words),
+            C.byref(n_words), C.byref(like), _p(pf), _p(stats), C.c_int32(VARIANTS[variant]), _p(trace))
+    return dict(status=int(st), ali=ali, words=words[: n_words.value].copy(), like=float(like.value), per_frame=pf,
+                max_toks=int(stats[0]), sum_toks=int(stats[1]), cells=int(stats[2]), trace=trace)
+
+
 def split_to_phones(ali, id2state, is_self_loop, is_final, tuples):
     ali = np.ascontiguousarray(ali, np.int32)
     T = ali.shape[0]
